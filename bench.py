@@ -80,8 +80,18 @@ def parse():
                     "tools/prof_stats.sh / prof_pmc.sh run under rocprofv3, so that the profile holds these launches and no others")
     ap.add_argument("--allow-slow-libzstd", action="store_true", help="run the metric even when the callers' libzstd is the image's 4x slower Pillow build "
                     "(default: refuse — every end-to-end number and cpu_baseline would be that build's)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                    "(float32 / float64, at most 64 MB; rank 0): every frame size and a seeded sample of the frames of the last ZSTD_compress2 "
+                    "pass, every block's sequence count and a seeded sample of the sequences of the last kernel launch — so that two builds "
+                    "can be compared output for output")
     ap.add_argument("--product-multi-gpu", type=int, default=0, help=argparse.SUPPRESS)  # internal: only that leg, in a process that sees every GPU
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and 16 * a.blocks > DUMP_MAX_BYTES // 4:  # (a count per block, a frame size per chunk, chunks <= blocks)
+        ap.error("--dump-outputs: %d blocks per step, more than the %d whose counts and frame sizes fit a quarter of %d bytes"
+                 % (a.blocks, DUMP_MAX_BYTES // 64, DUMP_MAX_BYTES))
+    return a
 
 
 def load_corpus(name: str, size: int) -> tuple[bytes, str]:
@@ -196,6 +206,55 @@ def write_details(out: dict) -> str | None:
     return name
 
 
+# --dump-outputs: what the timed steps computed in their last step, as a caller of each timed path receives it.  The sample is a fixed,
+# seeded choice of chunks / blocks, so that runs with the same arguments (hence the same inputs) write the same files.  The sampled frames
+# and the sampled sequences take at most 3/8 of the budget each, the per-block counts and frame sizes the last quarter (checked in parse()).
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+DUMP_SEED = 1
+DUMP_FRAMES = 32   # chunks whose frames are written byte for byte (32 x ~128 KiB x 4 B at most)
+DUMP_BLOCKS = 16   # blocks whose sequences are written (16 x sequence_bound(128 KiB) x 4 x 8 B at most)
+
+
+def dump_count(k: int, bytes_each: int) -> int:
+    """k, or fewer when k samples of up to bytes_each bytes would not fit 3/8 of the budget"""
+    return max(1, min(k, DUMP_MAX_BYTES * 3 // 8 // max(bytes_each, 1)))
+
+
+def dump_sample(n: int, k: int):
+    """k of range(n), ascending: the same indices for every run with the same n"""
+    import numpy as np
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(n, k), replace=False))
+
+
+def kernel_outputs(d_cnt, d_seqs, stride: int) -> dict:
+    """the last launch of the dominant kernel: every block's sequence count (0xFFFFFFFF = error) and the sequences
+    (offset, litLength, matchLength, rep) of the sampled blocks, concatenated in block order"""
+    import numpy as np
+    cnt = d_cnt.cpu().numpy().view(np.uint32)
+    pick = dump_sample(len(cnt), dump_count(DUMP_BLOCKS, stride * 4 * 8))
+    rows = [d_seqs[i * stride:i * stride + (0 if cnt[i] == 0xFFFFFFFF else min(int(cnt[i]), stride))].cpu().numpy().view(np.uint32)
+            for i in pick]
+    return {"kernel_counts": cnt.astype(np.float64), "kernel_sample_blocks": pick.astype(np.float64),
+            "kernel_sample_sequences": np.concatenate(rows).reshape(-1, 4).astype(np.float64)}
+
+
+def frame_outputs(dst, sizes, stride: int, n: int) -> dict:
+    """the last ZSTD_compress2 pass: every chunk's frame size and the frame bytes of the sampled chunks, concatenated in chunk order"""
+    import numpy as np
+    pick = dump_sample(n, dump_count(DUMP_FRAMES, stride * 4))
+    raw = b"".join(C.string_at(C.addressof(dst) + int(c) * stride, sizes[c]) for c in pick)
+    return {"frame_sizes": np.array(sizes[:n], dtype=np.float64), "frame_sample_chunks": pick.astype(np.float64),
+            "frame_sample_bytes": np.frombuffer(raw, dtype=np.uint8).astype(np.float32)}
+
+
+def dump_outputs(d: str, arrays: dict) -> None:
+    import numpy as np
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes, more than %d" % (total, DUMP_MAX_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 # ----------------------------------------------------------------------------- CPU legs
@@ -618,10 +677,11 @@ def bind_rank_to_its_gpus_node(plug, world: int, rank: int, dist):
         return {"bound": False, "why": repr(e)[:200]}
 
 
-def e2e_steps(front, params, buf: bytes, chunk: int, steps: int, warmup: int, sync, barrier):
+def e2e_steps(front, params, buf: bytes, chunk: int, steps: int, warmup: int, sync, barrier, last: dict | None = None):
     """The timed region of the metric: `steps` passes of `buf` through QZSTD_frontCompress (ZSTD_compress2 per chunk on a pool of
     CCtx threads, qatSequenceProducer registered, segments announced one ahead), after `warmup` untimed ones; barrier + device
-    synchronize on both sides.  Returns (wall seconds of this rank, per-pass seconds, frames info)."""
+    synchronize on both sides.  Returns (wall seconds of this rank, per-pass seconds, frames info); `last`, when given, receives the
+    frames of the last timed pass (frame_outputs())."""
     F = front.lib
     f = F.QZSTD_createFront(C.byref(params))
     if not f:
@@ -648,6 +708,8 @@ def e2e_steps(front, params, buf: bytes, chunk: int, steps: int, warmup: int, sy
         barrier()
         sync()
         wall = time.perf_counter() - t0
+        if last is not None:
+            last.update(frame_outputs(dst, sizes, stride, n))
         st, fs = (C.c_ulong * 2)(), (C.c_ulong * 8)()
         F.QZSTD_frontStats(f, st)
         F.QZSTD_frontFailStats(f, fs)
@@ -770,12 +832,15 @@ def main():
     cnt = d_cnt.cpu().numpy().astype("uint32")
     n_err = int((cnt == 0xFFFFFFFF).sum())
     seq_total = int(cnt[cnt != 0xFFFFFFFF].sum())
+    dumped = kernel_outputs(d_cnt, d_seqs, stride) if a.dump_outputs and rank == 0 else None
 
     if a.kernel_only:
         if rank == 0:
+            if dumped is not None:
+                dump_outputs(a.dump_outputs, dumped)
             alg_bytes = size + 16 * seq_total
             print(json.dumps({"kernel_only": True, "level": level, "block_bytes": block, "blocks": nb, "launches_timed": a.steps,
-                              "kernel_ms_avg": round(kern_avg_ms, 3), "kernel_input_MBps": round(size / (kern_avg_ms * 1e-3) / 1e6, 1),
+                              "ms_per_step": round(kern_wall / a.steps * 1e3, 3), "kernel_ms_avg": round(kern_avg_ms, 3), "kernel_input_MBps": round(size / (kern_avg_ms * 1e-3) / 1e6, 1),
                               "algorithmic_bytes_per_launch": alg_bytes, "achieved_GBps": round(alg_bytes / (kern_avg_ms * 1e-3) / 1e9, 1),
                               "frac_of_hbm_peak": round(alg_bytes / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
                               "sequences_per_block": round(seq_total / max(nb - n_err, 1), 1), "error_blocks": n_err}))
@@ -801,7 +866,9 @@ def main():
     if level & 0x100:
         os.environ["QZSTD_HIP_EXT_REPCODES"] = "1"
     wall, per_pass, e2e_info = e2e_steps(front, prm, e2e_buf, block, a.steps, a.warmup, torch.cuda.synchronize,
-                                         (dist.barrier if world > 1 else (lambda: None)))
+                                         (dist.barrier if world > 1 else (lambda: None)), last=dumped)
+    if dumped is not None:
+        dump_outputs(a.dump_outputs, dumped)
     wall = S.reduce_max_seconds(wall, dist if world > 1 else None, None)  # gloo: a CPU tensor
     # ---- the software path over THE SAME BYTES, the same chunking, the same thread pool (round-5 verdict: cpu_baseline was timed on the first
     # 32 MiB of the corpus while `value` ran over all of it): QZSTD_frontCompress with useProducer = 0 — ZSTD_compress2 per chunk, plugin

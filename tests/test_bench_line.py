@@ -79,3 +79,52 @@ def test_write_details_names_a_file(tmp_path, monkeypatch):
     assert name == "bench_details.json"
     assert json.load(open(tmp_path / "bench_details.json")) == {"a": 1}
     assert json.load(open(tmp_path / "gpurun_out" / "bench_details.json")) == {"a": 1}
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: the last step's arrays as float32 / float64 .npy files, a seeded sample of chunks and blocks (the same one every
+    run), at most 64 MB in all"""
+    import ctypes as C
+
+    import numpy as np
+    import torch
+
+    import bench
+    pick = bench.dump_sample(8192, bench.DUMP_BLOCKS)
+    assert np.array_equal(pick, bench.dump_sample(8192, bench.DUMP_BLOCKS)) and len(set(pick.tolist())) == bench.DUMP_BLOCKS
+    assert list(pick) == sorted(pick) and bench.dump_sample(5, 16).tolist() == [0, 1, 2, 3, 4]
+    # the samples shrink instead of going over the budget: 3/8 of it for the frames, 3/8 for the sequences
+    seq_bytes = (131072 // 3 + 1 + 131072 // 1024 + 1) * 4 * 8
+    assert bench.dump_count(bench.DUMP_BLOCKS, seq_bytes) == bench.DUMP_BLOCKS  # 128 KiB blocks: the whole sample fits
+    assert bench.dump_count(16, 8 * 1000 * 1000) == 3 and bench.dump_count(16, 10 ** 9) == 1
+    assert bench.DUMP_BLOCKS * seq_bytes + bench.DUMP_FRAMES * (131072 + 1024) * 4 <= bench.DUMP_MAX_BYTES * 3 // 4
+
+    # the kernel's results: a count per block (0xFFFFFFFF = error) and `stride` entries of 4 words per block
+    nb, stride = 64, 8
+    seqs = torch.arange(nb * stride * 4, dtype=torch.int32).reshape(-1, 4)
+    cnt = torch.tensor([i % (stride + 1) for i in range(nb)], dtype=torch.int32)
+    pick = bench.dump_sample(nb, bench.DUMP_BLOCKS)
+    cnt[int(pick[0])] = -1
+    k = bench.kernel_outputs(cnt, seqs, stride)
+    assert k["kernel_counts"].dtype == np.float64 and k["kernel_counts"][pick[0]] == 0xFFFFFFFF
+    assert np.array_equal(k["kernel_sample_blocks"], pick)
+    want = np.concatenate([seqs[i * stride:i * stride + (0 if i == pick[0] else int(cnt[i]))].numpy() for i in pick])
+    assert np.array_equal(k["kernel_sample_sequences"], want.astype(np.float64))
+
+    # the frames: one per chunk, `stride` bytes apart in the destination buffer
+    n, fstride = 40, 16
+    dst = (C.c_char * (n * fstride)).from_buffer_copy((bytes(range(256)) * 3)[:n * fstride])
+    sizes = (C.c_size_t * n)(*[3 + i % 7 for i in range(n)])
+    f = bench.frame_outputs(dst, sizes, fstride, n)
+    chunks = f["frame_sample_chunks"].astype(int)
+    assert np.array_equal(chunks, bench.dump_sample(n, bench.DUMP_FRAMES)) and np.array_equal(f["frame_sizes"], list(sizes))
+    assert f["frame_sample_bytes"].dtype == np.float32
+    assert bytes(f["frame_sample_bytes"].astype(np.uint8)) == b"".join(dst.raw[c * fstride:c * fstride + sizes[c]] for c in chunks)
+
+    bench.dump_outputs(str(tmp_path / "out"), dict(k, **f))
+    for name, v in dict(k, **f).items():
+        got = np.load(tmp_path / "out" / (name + ".npy"))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, v), name
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 100)
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "small"), dict(k, **f))
