@@ -66,4 +66,6 @@ void QZSTD_freeFront(QZSTD_Front *f);
 #if defined(__cplusplus)
 }
 #endif
+/* device-resident input: declared in a header of its own, included here so that every user of this header sees it */
+#include "qzstd_frontend_device.h"
 #endif /* QZSTD_FRONTEND_H */

@@ -251,4 +251,6 @@ int qzstd_hip_host_node_of(const void *hptr);
 #if defined(__cplusplus)
 }
 #endif
+/* device-resident input: declared in a header of its own, included here so that every user of this header sees it */
+#include "qzstd_hip_device.h"
 #endif /* QZSTD_HIP_H */

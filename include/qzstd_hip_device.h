@@ -1,0 +1,54 @@
+/*
+ * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
+ * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy and the compaction kernel.
+ * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
+ * exported by the same library (libqatseqprod).
+ */
+#ifndef QZSTD_HIP_DEVICE_H
+#define QZSTD_HIP_DEVICE_H
+
+#include "qzstd_hip.h"
+
+#if defined(__cplusplus)
+extern "C" {
+#endif
+
+/* the library's device index of a pointer into DEVICE memory (hipPointerGetAttributes); < 0 for host, pinned-host, managed or
+ * unknown memory and for a device the library does not use.  Starts no work on any GPU. */
+int qzstd_hip_pointer_device(const void *p);
+/* events, so that the library's streams wait for work a caller queued on a stream of its own (NULL = the default stream) */
+void *qzstd_hip_event_create(int device);
+void qzstd_hip_event_destroy(int device, void *event);
+int qzstd_hip_event_record(int device, void *event, void *stream);
+int qzstd_hip_stream_wait_event(int device, void *stream, void *event);
+/* strided device->device copy (qzstd_hip_memcpy2d_d2h's layout): reads exactly `width` bytes of every source row */
+int qzstd_hip_memcpy2d_d2d(int device, void *stream, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height);
+
+/*
+ * Compaction: one launch's match-finder results (d_src, d_blocks, d_seqs, d_nseq exactly as qzstd_hip_find_sequences left them,
+ * 16-byte entries: no QZSTD_HIP_MARK_COMPACT items) packed densely into ONE device arena, so that a single D2H copy brings back
+ * what libzstd needs to build the frames (ZSTD_compressSequencesAndLiterals):
+ *
+ *   [0, 8 * nBlocks)                  per block a header {count, litBytes}: entries including the delimiter, literal bytes;
+ *                                     count = QZSTD_HIP_NSEQ_ERROR (litBytes 0) for a block the matcher failed, a block whose
+ *                                     entries do not cover exactly [srcOff, srcOff + srcLen), and every block from the first one
+ *                                     that would not fit arenaBytes on: such a block contributes nothing below
+ *   QZSTD_HIP_COMPACT_ENTRIES_OFF(n)  every block's entries, block after block, QZSTD_HIP_PACK(off, lit, ml, 0), delimiters included
+ *   ... + 8 * (sum of counts)         every block's literal bytes, block after block
+ *
+ * The literals are copied out of d_src inside [srcOff, srcOff + srcLen) of each block and nowhere else.  d_work: scratch of
+ * qzstd_hip_compact_workspace_bytes(nBlocks) bytes, private to the launch until it completes.  Asynchronous on `stream`.
+ */
+#define QZSTD_HIP_COMPACT_ENTRIES_OFF(nBlocks) ((((size_t)(nBlocks) * 8u) + 15u) & ~(size_t)15u)
+typedef struct {
+    uint32_t count;    /* entries of the block, delimiter included, or QZSTD_HIP_NSEQ_ERROR */
+    uint32_t litBytes; /* literal bytes of the block */
+} qzstd_hip_compact_hdr_t;
+size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks);
+int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
+                      const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work, size_t workBytes);
+
+#if defined(__cplusplus)
+}
+#endif
+#endif /* QZSTD_HIP_DEVICE_H */

@@ -6,11 +6,16 @@
  * keeps several claims: the one it is entropy-coding and the next two (QZSTD_FRONT_AHEAD), already announced to the GPUs
  * (QZSTD_hintSource), so match-finding always runs ahead of the thread that will consume it.
  */
+#define _GNU_SOURCE /* dladdr */
 #include "qzstd_frontend.h"
+#include "qzstd_frontend_device.h"
 
 #include "qatseqprod.h"
+#include "qzstd_hip_device.h"
 
+#include <dlfcn.h>
 #include <pthread.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -26,7 +31,17 @@ typedef struct {
     ZSTD_CCtx *zc;
     void *state;
     int ok;
+    /* device-resident input (QZSTD_frontCompressDevice): the frame's sequences unpacked, its raw bytes when they are needed */
+    ZSTD_Sequence *seqs;
+    size_t seqsCap;
+    unsigned char *raw;
+    void *rawStream;
+    int rawDev;
 } QF_Worker;
+
+typedef struct QF_DevPart_s QF_DevPart;
+typedef struct QF_DevSlot_s QF_DevSlot;
+static void qfDevSlotsFree(QZSTD_Front *f);
 
 struct QZSTD_Front_s {
     QZSTD_FrontParams p;
@@ -45,6 +60,12 @@ struct QZSTD_Front_s {
     int uniform;      /* every claim a whole segment: the levels whose match-finding, not the entropy stage, sets the pace (see qfClaim) */
     unsigned ahead;   /* claims a worker keeps announced beyond the one it is entropy-coding: $QZSTD_FRONT_AHEAD, 1..3, default 2 */
     unsigned long served[2];
+    /* device-resident input: the part the workers entropy-code (NULL: a QZSTD_frontCompress job) and the device jobs' counters */
+    const QF_DevPart *part;
+    int devBusy;
+    unsigned long long devStats[4];
+    QF_DevSlot *devSlot; /* two, kept from call to call (device buffers, pinned arenas, streams) for device devSlotDev */
+    int devSlotDev;
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -96,9 +117,16 @@ static void qfAnnounce(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
     (void)QZSTD_hintSourceEx(w->state, f->src + off, len, grid, f->p.level, QZSTD_HINT_STABLE);
 }
 
+static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c);
+
 static int qfCompressSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 {
     size_t c;
+    if (f->part) {
+        for (c = sg->c0; c < sg->c1; c++)
+            if (qfDeviceFrame(f, w, c) != 0) return -1;
+        return 0;
+    }
     for (c = sg->c0; c < sg->c1; c++) {
         const size_t off = c * f->p.chunkSize;
         const size_t n = f->srcSize - off < f->p.chunkSize ? f->srcSize - off : f->p.chunkSize;
@@ -131,7 +159,7 @@ static void *qfWorker(void *arg)
                 more = qfClaim(f, claims, &q[n]);
                 if (!more) break;
                 claims++;
-                if (!bad) qfAnnounce(f, w, &q[n]);
+                if (!bad && !f->part) qfAnnounce(f, w, &q[n]);
                 n++;
             }
             if (n == 0) break;
@@ -212,6 +240,19 @@ QZSTD_Front *QZSTD_createFront(const QZSTD_FrontParams *p)
 
 size_t QZSTD_frontFrameStride(const QZSTD_Front *f) { return f ? f->stride : 0; }
 
+/* hands the workers chunks [0, nChunks) of a job (called with f->mu held) and waits for them */
+static int qfRunJobLocked(QZSTD_Front *f, size_t nChunks)
+{
+    f->nChunks = nChunks;
+    f->nextChunk = 0;
+    f->failed = 0;
+    f->running = f->p.nThreads;
+    f->gen++;
+    pthread_cond_broadcast(&f->cvWork);
+    while (f->running) pthread_cond_wait(&f->cvDone, &f->mu);
+    return f->failed;
+}
+
 size_t QZSTD_frontCompress(QZSTD_Front *f, const void *src, size_t srcSize, void *dst, size_t dstCapacity, size_t *frameSizes)
 {
     size_t nChunks;
@@ -225,14 +266,7 @@ size_t QZSTD_frontCompress(QZSTD_Front *f, const void *src, size_t srcSize, void
     f->srcSize = srcSize;
     f->dst = (unsigned char *)dst;
     f->sizes = frameSizes;
-    f->nChunks = nChunks;
-    f->nextChunk = 0;
-    f->failed = 0;
-    f->running = f->p.nThreads;
-    f->gen++;
-    pthread_cond_broadcast(&f->cvWork);
-    while (f->running) pthread_cond_wait(&f->cvDone, &f->mu);
-    failed = f->failed;
+    failed = qfRunJobLocked(f, nChunks);
     pthread_mutex_unlock(&f->mu);
     return failed ? (size_t)-1 : nChunks;
 }
@@ -289,10 +323,441 @@ void QZSTD_freeFront(QZSTD_Front *f)
         if (w->ok) pthread_join(w->th, NULL);
         if (w->zc) ZSTD_freeCCtx(w->zc);
         if (w->state) QZSTD_freeSeqProdState(w->state);
+        free(w->seqs);
+        if (w->raw) qzstd_hip_host_free(w->raw);
+        if (w->rawStream) qzstd_hip_stream_destroy(w->rawDev, w->rawStream);
     }
+    qfDevSlotsFree(f);
     free(f->w);
     pthread_mutex_destroy(&f->mu);
     pthread_cond_destroy(&f->cvWork);
     pthread_cond_destroy(&f->cvDone);
     free(f);
+}
+
+/* ---------------------------------------------------------------- device-resident input -- */
+/*
+ * QZSTD_frontCompressDevice: the input is cut into PARTS of whole chunks (at most QF_PART_BYTES).  Per part, on one of two device slots:
+ * the match-finder (qzstd_hip_find_sequences), the compaction (qzstd_hip_compact: packed entries + literal bytes in one dense arena), the
+ * arena's headers and then the arena itself D2H into pinned memory.  The workers entropy-code part k straight from its arena
+ * (ZSTD_compressSequencesAndLiterals) while the GPU works on parts k + 1 and k + 2.  The calling thread does the GPU side.
+ *
+ * The new entry points of the device layer are weak references: a device layer without them (an older library, the CPU suite's mock)
+ * makes QZSTD_frontCompressDevice fail and leaves the rest of the front-end as it was.
+ */
+extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
+extern void *qzstd_hip_event_create(int device) __attribute__((weak));
+extern void qzstd_hip_event_destroy(int device, void *event) __attribute__((weak));
+extern int qzstd_hip_event_record(int device, void *event, void *stream) __attribute__((weak));
+extern int qzstd_hip_stream_wait_event(int device, void *stream, void *event) __attribute__((weak));
+extern int qzstd_hip_memcpy2d_d2d(int device, void *stream, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width,
+                                  size_t height) __attribute__((weak));
+extern size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks) __attribute__((weak));
+extern int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
+                             const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work,
+                             size_t workBytes) __attribute__((weak));
+
+#define QF_PART_BYTES ((size_t)64 << 20)
+#define QF_DEV_WAIT_MS 60000u
+#define QF_LIT_SLACK 64u /* bytes past the arena's last literal: ZSTD_compressSequencesAndLiterals reads up to 8 past a frame's literals */
+#ifndef ZSTD_c_blockDelimiters
+#define ZSTD_c_blockDelimiters ((ZSTD_cParameter)1008) /* ZSTD_c_experimentalParam11 */
+#endif
+
+typedef size_t (*QF_SeqLitFn)(ZSTD_CCtx *, void *, size_t, const ZSTD_Sequence *, size_t, const void *, size_t, size_t, size_t);
+typedef size_t (*QF_SeqFn)(ZSTD_CCtx *, void *, size_t, const ZSTD_Sequence *, size_t, const void *, size_t);
+static QF_SeqLitFn qfSeqLit;
+static QF_SeqFn qfSeq;
+static pthread_once_t qfSeqOnce = PTHREAD_ONCE_INIT;
+
+/* ZSTD_compressSequencesAndLiterals (libzstd >= 1.5.7) and ZSTD_compressSequences, from THE libzstd this library's ZSTD_* calls bind
+ * to (with RTLD_DEEPBIND that is not the first one in the process): the object that holds ZSTD_compress2 as bound here */
+static void qfResolveSeqApi(void)
+{
+    Dl_info di;
+    void *h;
+    if (!dladdr((void *)(uintptr_t)&ZSTD_compress2, &di) || !di.dli_fname) return;
+    h = dlopen(di.dli_fname, RTLD_NOW | RTLD_NOLOAD);
+    if (!h) return;
+    if (!getenv("QZSTD_FRONT_NO_SEQLIT")) qfSeqLit = (QF_SeqLitFn)(uintptr_t)dlsym(h, "ZSTD_compressSequencesAndLiterals");
+    qfSeq = (QF_SeqFn)(uintptr_t)dlsym(h, "ZSTD_compressSequences");
+    dlclose(h); /* (RTLD_NOLOAD: the library stays, it was loaded before) */
+}
+
+/* one device slot: a part's buffers, device and pinned */
+struct QF_DevSlot_s {
+    void *stream;
+    unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned blocks, when the caller's buffer cannot be read in place */
+    qzstd_hip_block_t *hDesc; size_t hDescCap;
+    void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
+    size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
+    unsigned char *hArena; size_t hArenaCap;
+    size_t *blkSeq, *blkLit; size_t blkCap;   /* per block: first entry, first literal byte (host prefix sums of the headers) */
+    const unsigned char *hLit; size_t litTotal; /* the arena's literal bytes, in hArena */
+};
+
+struct QF_DevPart_s {
+    const unsigned char *dSrc;  /* the caller's buffer (the raw-bytes path reads its chunks from there) */
+    size_t c0, c1;              /* chunks of the job */
+    size_t nb, bpc;             /* blocks, blocks per chunk */
+    const QF_DevSlot *slot;
+    int dev;
+};
+
+static void qfSlotFree(int dev, QF_DevSlot *s)
+{
+    void *d[] = { s->dStage, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena };
+    size_t i;
+    for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
+    if (s->hDesc) qzstd_hip_host_free(s->hDesc);
+    if (s->hArena) qzstd_hip_host_free(s->hArena);
+    if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
+    free(s->blkSeq);
+    free(s->blkLit);
+    memset(s, 0, sizeof(*s));
+}
+
+static void qfDevSlotsFree(QZSTD_Front *f)
+{
+    if (!f->devSlot) return;
+    qfSlotFree(f->devSlotDev, &f->devSlot[0]);
+    qfSlotFree(f->devSlotDev, &f->devSlot[1]);
+    free(f->devSlot);
+    f->devSlot = NULL;
+}
+
+static int qfGrowD(int dev, void **p, size_t *cap, size_t need)
+{
+    if (*cap >= need && *p) return 0;
+    if (*p) qzstd_hip_free(dev, *p);
+    *p = qzstd_hip_malloc(dev, need ? need : 16);
+    *cap = *p ? need : 0;
+    return *p ? 0 : -1;
+}
+
+static int qfGrowH(void **p, size_t *cap, size_t need)
+{
+    if (*cap >= need && *p) return 0;
+    if (*p) qzstd_hip_host_free(*p);
+    *p = qzstd_hip_host_alloc(need ? need : 16);
+    *cap = *p ? need : 0;
+    return *p ? 0 : -1;
+}
+
+typedef struct {
+    QZSTD_Front *f;
+    const unsigned char *dSrc;
+    size_t srcSize, partChunks, bpc;
+    int dev, level;
+} QF_DevJob;
+
+/* queues part p (chunks [c0, c1)) on slot s: staging copy if needed, match-finder, compaction.  Device side only: the slot's pinned
+ * arena may still be read by the workers (the part fetched from it before) */
+static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1)
+{
+    const size_t chunk = j->f->p.chunkSize, off = c0 * chunk, end = c1 * chunk < j->srcSize ? c1 * chunk : j->srcSize;
+    const size_t blk = chunk < QZSTD_HIP_BLOCK_MAX ? chunk : QZSTD_HIP_BLOCK_MAX;
+    const size_t pitch = (chunk + 15u) & ~(size_t)15u; /* chunk c of the part at c * pitch when staged */
+    const int inPlace = ((uintptr_t)(j->dSrc + off) & 15u) == 0 && (chunk & 15u) == 0 && ((end - off) & 15u) == 0;
+    const size_t nb = (c1 - c0 - 1) * j->bpc + ((end - (c1 - 1) * chunk) + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
+    const unsigned char *base = j->dSrc + off;
+    size_t c, b = 0, seqCapTotal = 0;
+    int dev = j->dev;
+    if (nb > 0xFFFFFFFFu) return -1;
+    {
+        void *h = s->hDesc;
+        if (qfGrowH(&h, &s->hDescCap, nb * sizeof(qzstd_hip_block_t))) return -1;
+        s->hDesc = (qzstd_hip_block_t *)h;
+    }
+    for (c = c0; c < c1; c++) {
+        const size_t co = c * chunk, ce = co + chunk < j->srcSize ? co + chunk : j->srcSize;
+        size_t o;
+        for (o = co; o < ce; o += QZSTD_HIP_BLOCK_MAX, b++) {
+            qzstd_hip_block_t *d = &s->hDesc[b];
+            d->srcLen = (uint32_t)(ce - o < QZSTD_HIP_BLOCK_MAX ? ce - o : QZSTD_HIP_BLOCK_MAX);
+            d->srcOff = inPlace ? o - off : (c - c0) * pitch + (o - co);
+            d->seqOff = b * capPad;
+            d->seqCap = (uint32_t)cap;
+            d->parseFrom = 0;
+            d->mark = 0;
+            seqCapTotal += cap;
+        }
+    }
+    if (b != nb) return -1;
+    if (!s->stream && !(s->stream = qzstd_hip_stream_create(dev))) return -1;
+    {
+        const size_t work = qzstd_hip_workspace_bytes(j->level, (uint32_t)nb, (uint32_t)blk);
+        const size_t arena = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb) + 8u * seqCapTotal + (end - off);
+        if (qfGrowD(dev, &s->dDesc, &s->dDescCap, nb * sizeof(qzstd_hip_block_t)) || qfGrowD(dev, &s->dSeqs, &s->dSeqsCap, nb * capPad * 16u) ||
+            qfGrowD(dev, &s->dCount, &s->dCountCap, nb * 4u) || qfGrowD(dev, &s->dWork, &s->dWorkCap, work) ||
+            qfGrowD(dev, &s->dCWork, &s->dCWorkCap, qzstd_hip_compact_workspace_bytes((uint32_t)nb)) || qfGrowD(dev, &s->dArena, &s->dArenaCap, arena))
+            return -1;
+    }
+    if (!inPlace) {
+        /* the matcher reads 16-aligned blocks and up to the next multiple of 16 past each: the part's chunks go to pitch-aligned rows of
+         * library memory (one 2D copy; the last chunk alone when it is short), zero bytes behind every chunk */
+        const size_t full = (end - off) / chunk, tail = (end - off) - full * chunk;
+        void *stage = s->dStage;
+        if (qfGrowD(dev, &stage, &s->stageCap, (c1 - c0) * pitch + 16u)) return -1;
+        s->dStage = (unsigned char *)stage;
+        if (qzstd_hip_memset(dev, s->stream, s->dStage, 0, (c1 - c0) * pitch + 16u)) return -1;
+        if (full && qzstd_hip_memcpy2d_d2d(dev, s->stream, s->dStage, pitch, base, chunk, chunk, full)) return -1;
+        if (tail && qzstd_hip_memcpy2d_d2d(dev, s->stream, s->dStage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
+        base = s->dStage;
+    }
+    if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dDesc, s->hDesc, nb * sizeof(qzstd_hip_block_t)) ||
+        qzstd_hip_find_sequences(dev, s->stream, j->level, base, (const qzstd_hip_block_t *)s->dDesc, (uint32_t)nb, (uint32_t)blk, s->dSeqs,
+                                 (uint32_t *)s->dCount, s->dWork, s->dWorkCap) ||
+        qzstd_hip_compact(dev, s->stream, base, (const qzstd_hip_block_t *)s->dDesc, (uint32_t)nb, s->dSeqs, (const uint32_t *)s->dCount,
+                          s->dArena, s->dArenaCap, s->dCWork, s->dCWorkCap))
+        return -1;
+    return 0;
+}
+
+/* waits for a queued part, brings its arena back (one D2H) and fills the per-block offsets; -> the part for the workers */
+static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1, QF_DevPart *out)
+{
+    const size_t end = c1 * j->f->p.chunkSize < j->srcSize ? c1 * j->f->p.chunkSize : j->srcSize;
+    const size_t nb = (c1 - c0 - 1) * j->bpc + ((end - (c1 - 1) * j->f->p.chunkSize) + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb);
+    const qzstd_hip_compact_hdr_t *hdr;
+    size_t b, seqs = 0, lits = 0, bytes;
+    if (s->hArenaCap < eo) {
+        void *h = s->hArena;
+        if (qfGrowH(&h, &s->hArenaCap, eo + (end - c0 * j->f->p.chunkSize) + ((end - c0 * j->f->p.chunkSize) >> 2) + QF_LIT_SLACK)) return -1;
+        s->hArena = (unsigned char *)h;
+    }
+    if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
+        return -1;
+    if (s->blkCap < nb) {
+        free(s->blkSeq);
+        free(s->blkLit);
+        s->blkSeq = (size_t *)malloc(nb * sizeof(size_t));
+        s->blkLit = (size_t *)malloc(nb * sizeof(size_t));
+        s->blkCap = s->blkSeq && s->blkLit ? nb : 0;
+        if (!s->blkCap) return -1;
+    }
+    hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    for (b = 0; b < nb; b++) {
+        s->blkSeq[b] = seqs;
+        s->blkLit[b] = lits;
+        if (hdr[b].count == QZSTD_HIP_NSEQ_ERROR) continue;
+        seqs += hdr[b].count;
+        lits += hdr[b].litBytes;
+    }
+    bytes = 8u * seqs + lits;
+    if (s->hArenaCap < eo + bytes + QF_LIT_SLACK) {
+        /* grown (an eighth more than this part needs): the headers move along */
+        unsigned char *n = (unsigned char *)qzstd_hip_host_alloc(eo + bytes + QF_LIT_SLACK + (bytes >> 3));
+        if (!n) return -1;
+        memcpy(n, s->hArena, nb * 8u);
+        qzstd_hip_host_free(s->hArena);
+        s->hArena = n;
+        s->hArenaCap = eo + bytes + QF_LIT_SLACK + (bytes >> 3);
+    }
+    if (bytes && (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena + eo, (const unsigned char *)s->dArena + eo, bytes) ||
+                  qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0))
+        return -1;
+    memset(s->hArena + eo + bytes, 0, QF_LIT_SLACK);
+    s->hLit = s->hArena + eo + 8u * seqs;
+    s->litTotal = lits;
+    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes), __ATOMIC_RELAXED);
+    out->dSrc = j->dSrc;
+    out->c0 = c0;
+    out->c1 = c1;
+    out->nb = nb;
+    out->bpc = j->bpc;
+    out->slot = s;
+    out->dev = j->dev;
+    return 0;
+}
+
+/* chunk c of the part in progress -> frame */
+static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
+{
+    const QF_DevPart *pt = f->part;
+    const QF_DevSlot *s = pt->slot;
+    const size_t cg = pt->c0 + c, off = cg * f->p.chunkSize;
+    const size_t n = f->srcSize - off < f->p.chunkSize ? f->srcSize - off : f->p.chunkSize;
+    const size_t b0 = c * pt->bpc, b1 = b0 + pt->bpc < pt->nb ? b0 + pt->bpc : pt->nb;
+    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(pt->nb);
+    const unsigned long long *ent = (const unsigned long long *)(const void *)(s->hArena + eo);
+    size_t b, ns = 0, nl = 0, k, r = 0;
+    int failedBlock = 0, haveSeqs = 0;
+    unsigned char *dst = f->dst + cg * f->stride;
+    for (b = b0; b < b1; b++) {
+        if (hdr[b].count == QZSTD_HIP_NSEQ_ERROR) failedBlock = 1;
+        else { ns += hdr[b].count; nl += hdr[b].litBytes; }
+    }
+    if (!failedBlock) {
+        const unsigned long long *q = ent + s->blkSeq[b0];
+        if (w->seqsCap < ns) {
+            free(w->seqs);
+            w->seqs = (ZSTD_Sequence *)malloc(ns * sizeof(ZSTD_Sequence));
+            w->seqsCap = w->seqs ? ns : 0;
+            if (!w->seqs) return -1;
+        }
+        for (k = 0; k < ns; k++) {
+            const unsigned long long v = q[k];
+            w->seqs[k].offset = QZSTD_HIP_PACKED_OFF(v);
+            w->seqs[k].litLength = QZSTD_HIP_PACKED_LIT(v);
+            w->seqs[k].matchLength = QZSTD_HIP_PACKED_ML(v);
+            w->seqs[k].rep = 0;
+        }
+        haveSeqs = 1;
+        /* (a session that ended in an error leaves the CCtx mid-frame, where parameters cannot be set: every frame starts afresh) */
+        (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
+        if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 1))) return -1;
+        if (qfSeqLit) {
+            /* the frame's literals straight from the arena; everything behind them (later frames' literals, the slack) is readable */
+            const unsigned char *lit = s->hLit + s->blkLit[b0];
+            const size_t litCap = s->litTotal - s->blkLit[b0] + QF_LIT_SLACK;
+            r = qfSeqLit(w->zc, dst, f->stride, w->seqs, ns, lit, nl, litCap, n);
+            if (!ZSTD_isError(r)) {
+                (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
+                f->sizes[cg] = r;
+                __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
+                return 0;
+            }
+        }
+    }
+    /* the raw bytes: an incompressible block (ZSTD_compressSequencesAndLiterals cannot store a block raw), a block the matcher failed,
+     * or a libzstd without the function.  Sequences -> ZSTD_compressSequences, the identical frame; a failed block -> ZSTD_compress2 on
+     * this CCtx: its producer fails the same block and libzstd's own match-finder takes it, as on the host path */
+    if (!w->raw || w->rawDev != pt->dev) {
+        if (w->raw) qzstd_hip_host_free(w->raw);
+        if (w->rawStream) qzstd_hip_stream_destroy(w->rawDev, w->rawStream);
+        w->raw = (unsigned char *)qzstd_hip_host_alloc(f->p.chunkSize);
+        w->rawStream = qzstd_hip_stream_create(pt->dev);
+        w->rawDev = pt->dev;
+        if (!w->raw || !w->rawStream) return -1;
+    }
+    if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, pt->dSrc + off, n)) return -1;
+    if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
+        /* the copy still reads d_src: the call must not return before it is done */
+        (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
+        return -1;
+    }
+    __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->devStats[1], 1ull, __ATOMIC_RELAXED);
+    if (haveSeqs && qfSeq) {
+        (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
+        r = qfSeq(w->zc, dst, f->stride, w->seqs, ns, w->raw, n);
+        if (!ZSTD_isError(r)) {
+            (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
+            f->sizes[cg] = r;
+            return 0;
+        }
+    }
+    (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
+    (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
+    r = ZSTD_compress2(w->zc, dst, f->stride, w->raw, n);
+    if (ZSTD_isError(r)) return -1;
+    f->sizes[cg] = r;
+    return 0;
+}
+
+size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSize, void *stream, void *dst, size_t dstCapacity,
+                                 size_t *frameSizes)
+{
+    QF_DevJob j;
+    QF_DevSlot *slot;
+    QF_DevPart part[2];
+    void *ev = NULL;
+    size_t nChunks, nParts, k;
+    int rc = 0;
+    /* host-side checks: nothing has touched a GPU when one of them fails */
+    if (!f || (!d_src && srcSize) || !dst || !frameSizes || !f->p.useProducer) return (size_t)-1;
+    nChunks = (srcSize + f->p.chunkSize - 1) / f->p.chunkSize;
+    if (dstCapacity / f->stride < nChunks) return (size_t)-1;
+    if (!qzstd_hip_pointer_device || !qzstd_hip_compact || !qzstd_hip_compact_workspace_bytes || !qzstd_hip_event_create ||
+        !qzstd_hip_event_record || !qzstd_hip_stream_wait_event || !qzstd_hip_event_destroy || !qzstd_hip_memcpy2d_d2d)
+        return (size_t)-1; /* a device layer without the device-input entry points */
+    if (nChunks == 0) return 0;
+    j.dev = qzstd_hip_pointer_device(d_src);
+    if (j.dev < 0 || qzstd_hip_pointer_device((const unsigned char *)d_src + srcSize - 1) != j.dev) return (size_t)-1;
+    pthread_mutex_lock(&f->mu);
+    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+    f->devBusy = 1;
+    pthread_mutex_unlock(&f->mu);
+    pthread_once(&qfSeqOnce, qfResolveSeqApi);
+
+    j.f = f;
+    j.dSrc = (const unsigned char *)d_src;
+    j.srcSize = srcSize;
+    j.bpc = (f->p.chunkSize + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    {
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes per part (rounded down to whole chunks, at least one), default 64 MiB */
+        const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
+        j.partChunks = want / f->p.chunkSize ? want / f->p.chunkSize : 1;
+    }
+    {
+        const char *rep = getenv("QZSTD_HIP_EXT_REPCODES"); /* the producer path's level flags (QZSTD_startQatDevice) */
+        j.level = f->p.level | ((rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0);
+    }
+    nParts = (nChunks + j.partChunks - 1) / j.partChunks;
+    memset(part, 0, sizeof(part));
+    /* the slots stay with the front between calls (allocating and freeing pinned and device memory costs more than a part takes) */
+    if (f->devSlot && f->devSlotDev != j.dev) qfDevSlotsFree(f);
+    if (!f->devSlot && !(f->devSlot = (QF_DevSlot *)calloc(2, sizeof(QF_DevSlot)))) rc = -1;
+    f->devSlotDev = j.dev;
+    slot = f->devSlot;
+    /* the library's streams wait for what the caller queued on `stream` so far: the work that produced d_src */
+    for (k = 0; k < 2 && rc == 0; k++)
+        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(j.dev))) rc = -1;
+    if (rc == 0 && !(ev = qzstd_hip_event_create(j.dev))) rc = -1;
+    if (rc == 0 && (qzstd_hip_event_record(j.dev, ev, stream) || qzstd_hip_stream_wait_event(j.dev, slot[0].stream, ev) ||
+                    qzstd_hip_stream_wait_event(j.dev, slot[1].stream, ev)))
+        rc = -1;
+#define QF_PART_C0(p) ((p) * j.partChunks)
+#define QF_PART_C1(p) ((p) * j.partChunks + j.partChunks < nChunks ? (p) * j.partChunks + j.partChunks : nChunks)
+    /* two parts on the GPU ahead of the one being entropy-coded: part p lives on slot p % 2 from its queueing to its fetch */
+    for (k = 0; k < 2 && k < nParts && rc == 0; k++) rc = qfQueuePart(&j, &slot[k], QF_PART_C0(k), QF_PART_C1(k));
+    if (rc == 0) rc = qfFetchPart(&j, &slot[0], QF_PART_C0(0), QF_PART_C1(0), &part[0]);
+    for (k = 0; k < nParts && rc == 0; k++) {
+        int failed;
+        /* slot k % 2 is fetched: its device side takes part k + 2 while the workers read its pinned arena — not the device buffers */
+        if (k + 2 < nParts) {
+            if ((rc = qfQueuePart(&j, &slot[k % 2], QF_PART_C0(k + 2), QF_PART_C1(k + 2))) != 0) break;
+        }
+        pthread_mutex_lock(&f->mu);
+        f->part = &part[k % 2];
+        f->src = NULL;
+        f->srcSize = srcSize;
+        f->dst = (unsigned char *)dst;
+        f->sizes = frameSizes;
+        failed = qfRunJobLocked(f, part[k % 2].c1 - part[k % 2].c0);
+        f->part = NULL;
+        pthread_mutex_unlock(&f->mu);
+        if (failed) { rc = -1; break; }
+        if (k + 1 < nParts) {
+            /* the next part's arena into the other slot (its last reader was the job of part k - 1) */
+            rc = qfFetchPart(&j, &slot[(k + 1) % 2], QF_PART_C0(k + 1), QF_PART_C1(k + 1), &part[(k + 1) % 2]);
+        }
+    }
+#undef QF_PART_C0
+#undef QF_PART_C1
+    /* nothing the library queued may still read d_src when the call returns: a bounded wait first, then an unbounded one */
+    for (k = 0; slot && k < 2; k++) {
+        if (!slot[k].stream) continue;
+        if (qzstd_hip_stream_wait(j.dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
+            (void)qzstd_hip_stream_sync(j.dev, slot[k].stream);
+            rc = -1;
+        }
+    }
+    if (ev) qzstd_hip_event_destroy(j.dev, ev);
+    if (rc == 0) __atomic_fetch_add(&f->devStats[3], (unsigned long long)srcSize, __ATOMIC_RELAXED);
+    pthread_mutex_lock(&f->mu);
+    f->devBusy = 0;
+    pthread_mutex_unlock(&f->mu);
+    return rc == 0 ? nChunks : (size_t)-1;
+}
+
+void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->devStats[k], __ATOMIC_RELAXED) : 0ull;
 }

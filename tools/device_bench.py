@@ -1,0 +1,88 @@
+"""Device-resident input against today's way, one JSON line.
+
+On N GiB of qz_corpus.system_corpus in a GPU tensor, at levels 1 / 6 / 12 with 128 KiB frames and 16 worker threads:
+  host   t.cpu() + QZSTD_frontCompress (the tensor copied to host memory, then the producer path)
+  device QZSTD_frontCompressDevice (match-finder + compaction on the tensor's GPU, one dense D2H copy per part)
+GB/s of input (best of --reps; the window holds the library calls and, for the host way, t.cpu() — nothing else: the destination is
+sized once, one untimed pass of each way comes first, frames are read out of the destination after the window), D2H bytes per input
+byte, frames that took the raw-bytes fallback, compressed sizes, whether both ways give the same frames.
+
+  python tools/device_bench.py --gib 1 --reps 3 [--levels 1,6,12]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import qz_device as D  # noqa: E402  (torch first)
+import qz_bind as B  # noqa: E402
+import qz_corpus as K  # noqa: E402
+
+torch = D.torch
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gib", type=float, default=1.0)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--threads", type=int, default=16)
+    ap.add_argument("--chunk", type=int, default=131072)
+    ap.add_argument("--levels", default="1,6,12")
+    a = ap.parse_args()
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    size = int(a.gib * (1 << 30))
+    n = (size + a.chunk - 1) // a.chunk
+    data = K.by_name("system", size)
+    t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda:0")
+    del data
+    torch.cuda.synchronize()
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "timed": "library calls (+ t.cpu() for the host way), best of %d" % a.reps,
+           "levels": {}}
+    for level in [int(x) for x in a.levels.split(",")]:
+        fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            stream = torch.cuda.current_stream().cuda_stream
+
+            def host_pass():
+                h = t.cpu()
+                return fr.call_host(h.data_ptr(), size)
+
+            def device_pass():
+                return fr.call_device(t.data_ptr(), size, stream)
+
+            for f in (host_pass, device_pass):  # untimed: first-touch of the destination, the device slots, the pinned arenas
+                assert f()[0] == n
+            best = {"host": None, "device": None}
+            s0 = fr.stats()
+            for _ in range(a.reps):
+                for name, f in (("host", host_pass), ("device", device_pass)):
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    r, _ = f()
+                    dt = time.perf_counter() - t0
+                    assert r == n, "%s pass failed" % name
+                    best[name] = dt if best[name] is None else min(best[name], dt)
+            s1 = fr.stats()
+            r, sizes = host_pass()
+            frames_h = fr.frames(n, sizes)
+            r, sizes = device_pass()
+            frames_d = fr.frames(n, sizes)
+            out["levels"][str(level)] = {
+                "host_gbps": round(size / best["host"] / 1e9, 3), "device_gbps": round(size / best["device"] / 1e9, 3),
+                "host_ms": round(best["host"] * 1e3, 1), "device_ms": round(best["device"] * 1e3, 1),
+                "d2h_bytes_per_input_byte": round((s1[2] - s0[2]) / a.reps / size, 4),
+                "raw_fallback_frames": (s1[1] - s0[1]) // a.reps, "seqlit_frames": (s1[0] - s0[0]) // a.reps,
+                "compressed_host": sum(len(x) for x in frames_h), "compressed_device": sum(len(x) for x in frames_d),
+                "frames_identical_to_host_path": frames_h == frames_d}
+        finally:
+            fr.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

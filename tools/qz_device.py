@@ -1,0 +1,139 @@
+"""ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
+QZSTD_frontDeviceStats) and compress_tensor() for a contiguous GPU tensor of any dtype.
+
+torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
+import ctypes as C
+import os
+import sys
+
+try:
+    import torch  # noqa: F401  (first: the HIP runtime the library then binds to)
+except ImportError:  # the CPU suite's mock front-end needs no torch
+    torch = None
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import qz_bind as B  # noqa: E402
+
+ERROR = C.c_size_t(-1).value
+
+
+def bind(F):
+    """the front-end's C surface, the device entry points included, on a loaded library"""
+    F.QZSTD_createFront.restype = C.c_void_p
+    F.QZSTD_createFront.argtypes = [C.POINTER(B.FrontParams)]
+    F.QZSTD_frontFrameStride.restype = C.c_size_t
+    F.QZSTD_frontFrameStride.argtypes = [C.c_void_p]
+    F.QZSTD_frontCompress.restype = C.c_size_t
+    F.QZSTD_frontCompress.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    F.QZSTD_frontCompressDevice.restype = C.c_size_t
+    F.QZSTD_frontCompressDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                            C.POINTER(C.c_size_t)]
+    F.QZSTD_frontDeviceStats.restype = None
+    F.QZSTD_frontDeviceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    F.QZSTD_freeFront.argtypes = [C.c_void_p]
+    return F
+
+
+class DeviceFront:
+    """one QZSTD_Front (threads, level, chunk) with both ways in: host bytes (QZSTD_frontCompress) and a device address
+    (QZSTD_frontCompressDevice).  `lib`: an already loaded front-end library (tests: a mock build), else lib/libqzstdfront.so."""
+
+    def __init__(self, threads: int, level: int, chunk: int, ext_rep: int = 0, use_producer: int = 1, lib=None, segment: int = 0):
+        self.lib = bind(lib if lib is not None else B.Front().lib)
+        self.chunk = chunk
+        self.f = self.lib.QZSTD_createFront(C.byref(B.FrontParams(threads, level, chunk, segment, ext_rep, use_producer)))
+        if not self.f:
+            raise RuntimeError("QZSTD_createFront failed")
+        self.stride = self.lib.QZSTD_frontFrameStride(self.f)
+        self._dst = None
+
+    def reserve(self, size: int):
+        """size the destination for inputs of up to `size` bytes once (timed loops: no allocation inside the window)"""
+        self._buffers(size)
+
+    def frames(self, n: int, sizes) -> list:
+        """the frames the last call left in the destination"""
+        return self._frames(n, sizes)
+
+    def call_host(self, addr: int, size: int):
+        """QZSTD_frontCompress alone -> (return value, sizes); frames stay in the destination (frames())"""
+        n, sizes = self._buffers(size)
+        return self.lib.QZSTD_frontCompress(self.f, C.c_void_p(addr), size, self._dst, len(self._dst), sizes), sizes
+
+    def call_device(self, d_src: int, size: int, stream: int | None = None):
+        """QZSTD_frontCompressDevice alone -> (return value, sizes); frames stay in the destination (frames())"""
+        n, sizes = self._buffers(size)
+        return self.lib.QZSTD_frontCompressDevice(self.f, C.c_void_p(d_src), size, C.c_void_p(stream or None), self._dst,
+                                                  len(self._dst), sizes), sizes
+
+    def _buffers(self, size: int):
+        n = (size + self.chunk - 1) // self.chunk
+        if self._dst is None or len(self._dst) < max(n, 1) * self.stride:
+            self._dst = C.create_string_buffer(max(n, 1) * self.stride)
+        return n, (C.c_size_t * max(n, 1))()
+
+    def _frames(self, n, sizes):
+        raw = self._dst.raw
+        return [raw[c * self.stride:c * self.stride + sizes[c]] for c in range(n)]
+
+    def compress_host(self, data) -> list:
+        src = (C.c_char * max(len(data), 1)).from_buffer_copy(bytes(data) or b"\0")
+        return self.compress_host_ptr(C.addressof(src), len(data))
+
+    def compress_host_ptr(self, addr: int, size: int) -> list:
+        n, sizes = self._buffers(size)
+        if self.lib.QZSTD_frontCompress(self.f, C.c_void_p(addr), size, self._dst, len(self._dst), sizes) != n:
+            raise RuntimeError("QZSTD_frontCompress failed")
+        return self._frames(n, sizes)
+
+    def compress_device_raw(self, d_src: int, size: int, stream: int | None = None, dst_capacity: int | None = None):
+        """-> (return value of QZSTD_frontCompressDevice, frames or None)"""
+        n, sizes = self._buffers(size)
+        cap = len(self._dst) if dst_capacity is None else dst_capacity
+        r = self.lib.QZSTD_frontCompressDevice(self.f, C.c_void_p(d_src), size, C.c_void_p(stream or None), self._dst, cap, sizes)
+        return r, (self._frames(n, sizes) if r == n else None)
+
+    def compress_device(self, d_src: int, size: int, stream: int | None = None) -> list:
+        r, frames = self.compress_device_raw(d_src, size, stream)
+        if frames is None:
+            raise RuntimeError("QZSTD_frontCompressDevice failed (%d)" % (r if r != ERROR else -1))
+        return frames
+
+    def stats(self) -> list:
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontDeviceStats(self.f, st)
+        return list(st)
+
+    def close(self):
+        if self.f:
+            self.lib.QZSTD_freeFront(self.f)
+            self.f = None
+
+
+def compress_tensor(front: DeviceFront, t, stream=None) -> list:
+    """frames of a contiguous CUDA/HIP tensor's bytes (any dtype), as QZSTD_frontCompress frames the same bytes.  `stream`: the
+    torch.cuda.Stream (or raw hipStream_t) that produced t; default: the current stream of t's device."""
+    if not t.is_cuda or not t.is_contiguous():
+        raise ValueError("compress_tensor: a contiguous GPU tensor")
+    if stream is None:
+        stream = torch.cuda.current_stream(t.device)
+    handle = getattr(stream, "cuda_stream", stream)
+    return front.compress_device(t.data_ptr(), t.numel() * t.element_size(), handle)
+
+
+def reference_frames(zstd, oracle, data: bytes, chunk: int, level: int, ext_rep: bool = False) -> list:
+    """what QZSTD_frontCompressDevice must produce: libzstd's ZSTD_compress2 frames from the ORACLE's sequences, one 128 KiB block per
+    delimiter (ZSTD_c_blockSplitterLevel 1) above 128 KiB chunks; ext_rep: the repeat-aware profile (level | 0x100) with
+    ZSTD_c_searchForExternalRepcodes on, what QZSTD_HIP_EXT_REPCODES=1 and extRepcodes = 1 ask for"""
+    params = {"blockSplitterLevel": 1} if chunk > 131072 else {}
+    prof = None
+    if ext_rep:
+        prof = oracle.profile(level | 0x100, min(chunk, 131072))
+        zc = zstd.cctx(level, producer=oracle.producer_addr, state=C.addressof(prof), validate=True, ext_repcodes=1, **params)
+    else:
+        zc = zstd.cctx(level, producer=oracle.producer_addr, state=None, validate=True, **params)
+    try:
+        return zstd.compress_chunks(zc, data, chunk)[1]
+    finally:
+        zstd.free(zc)
+        del prof
