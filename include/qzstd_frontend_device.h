@@ -21,13 +21,13 @@ extern "C" {
  * The GPU match-finds the input in parts of whole chunks (at most 64 MiB) and packs each part's sequences and literal bytes into one
  * dense arena (qzstd_hip_compact) that comes back in one copy; the workers build the frames from it with
  * ZSTD_compressSequencesAndLiterals (explicit block delimiters, one 128 KiB block per delimiter) while the GPU works on the next
- * parts.  A frame with an incompressible or a failed block is built from its raw bytes, copied back.  Errors that return before
+ * parts.  A frame with a block libzstd would store raw, or a failed block, is built from its raw bytes, copied back.  Errors that return before
  * anything is queued: dst too small, a front created with useProducer = 0, an address that is not device memory, a call while
  * another one runs on this front. */
 size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSize, void *stream,
                                  void *dst, size_t dstCapacity, size_t *frameSizes);
-/* since creation: [0] frames from sequences + literals, [1] frames whose raw bytes were copied back (incompressible block, matcher
- * error, or a libzstd without ZSTD_compressSequencesAndLiterals), [2] bytes copied device->host, [3] bytes of input of the calls
+/* since creation: [0] frames from sequences + literals, [1] frames whose raw bytes were copied back (a block libzstd would store raw,
+ * a matcher error, or a libzstd without ZSTD_compressSequencesAndLiterals), [2] bytes copied device->host, [3] bytes of input of the calls
  * that succeeded */
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4]);
 

@@ -573,6 +573,26 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1, 
     return 0;
 }
 
+/* 1 when the frame ZSTD_compressSequencesAndLiterals built for n source bytes holds a Compressed block that libzstd stores raw — that
+ * function cannot, ZSTD_compressSequences does when the body does not beat the block's source (min(128 KiB, what is left) bytes) by
+ * ZSTD_minGain = (srcSize >> 6) + 2 bytes.  That is the gain of every strategy below btultra; above it the gain is smaller, and a frame
+ * this catches without need takes the raw-bytes path and comes out the same.  Walks the frame header (descriptor: single segment,
+ * dictionary ID and content size fields) and the 3-byte block headers. */
+static int qfStoresRawBlock(const unsigned char *fr, size_t frSize, size_t n)
+{
+    static const unsigned char didBytes[4] = { 0, 1, 2, 4 }, fcsBytes[4] = { 0, 2, 4, 8 };
+    const unsigned fhd = fr[4], single = (fhd >> 5) & 1u;
+    size_t pos = 5 + !single + didBytes[fhd & 3u] + ((fhd >> 6) == 0 ? single : fcsBytes[fhd >> 6]), k;
+    for (k = 0; pos + 3 <= frSize; k++) {
+        const unsigned h = fr[pos] | (unsigned)fr[pos + 1] << 8 | (unsigned)fr[pos + 2] << 16;
+        const size_t body = h >> 3, src = n - k * QZSTD_HIP_BLOCK_MAX < QZSTD_HIP_BLOCK_MAX ? n - k * QZSTD_HIP_BLOCK_MAX : QZSTD_HIP_BLOCK_MAX;
+        if (((h >> 1) & 3u) == 2u && body + (src >> 6) + 2 >= src) return 1;
+        pos += 3 + (((h >> 1) & 3u) == 1u ? 1 : body);
+        if (h & 1u) break; /* Last_Block */
+    }
+    return 0;
+}
+
 /* chunk c of the part in progress -> frame */
 static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
 {
@@ -615,7 +635,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             const unsigned char *lit = s->hLit + s->blkLit[b0];
             const size_t litCap = s->litTotal - s->blkLit[b0] + QF_LIT_SLACK;
             r = qfSeqLit(w->zc, dst, f->stride, w->seqs, ns, lit, nl, litCap, n);
-            if (!ZSTD_isError(r)) {
+            if (!ZSTD_isError(r) && !qfStoresRawBlock(dst, r, n)) {
                 (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
                 f->sizes[cg] = r;
                 __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
@@ -623,7 +643,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             }
         }
     }
-    /* the raw bytes: an incompressible block (ZSTD_compressSequencesAndLiterals cannot store a block raw), a block the matcher failed,
+    /* the raw bytes: a block libzstd would store raw (ZSTD_compressSequencesAndLiterals cannot), a block the matcher failed,
      * or a libzstd without the function.  Sequences -> ZSTD_compressSequences, the identical frame; a failed block -> ZSTD_compress2 on
      * this CCtx: its producer fails the same block and libzstd's own match-finder takes it, as on the host path */
     if (!w->raw || w->rawDev != pt->dev) {

@@ -3,10 +3,12 @@
  * the 2D device copy, the compaction) for the CPU stand-in of tests/mock/mock_hip.c, so that QZSTD_frontCompressDevice runs in the
  * CPU suite: "device" memory is plain host memory the test registers with qzstd_mock_device_range(); every other address is host
  * memory.  The compaction follows the kernel's contract (headers, packed entries, literals; a block whose entries do not cover it
- * exactly, and every block from the first one that does not fit the arena, contributes nothing).
+ * exactly, and every block from the first one that does not fit the arena, contributes nothing; the same refusals) —
+ * tools/qz_compact_ref.py states it and the CPU suite holds the two together.
  */
 #include "qzstd_hip_device.h"
 
+#include <stdint.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -55,7 +57,9 @@ int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_h
     uint32_t b, i;
     (void)device; (void)stream;
     if (nBlocks == 0) return 0;
-    if (!d_src || !d_blocks || !d_seqs || !d_nseq || !d_arena || !d_work || workBytes < qzstd_hip_compact_workspace_bytes(nBlocks) || arenaBytes < eo) return -1;
+    if (!d_src || !d_blocks || !d_seqs || !d_nseq || !d_arena || !d_work || workBytes < qzstd_hip_compact_workspace_bytes(nBlocks) ||
+        ((uintptr_t)d_work & 7u) || ((uintptr_t)d_arena & 15u) || arenaBytes < eo)
+        return -1;
     __sync_fetch_and_add(&gCompactLaunches, 1);
     for (b = 0; b < nBlocks; b++) { /* count */
         const qzstd_hip_block_t *k = &d_blocks[b];

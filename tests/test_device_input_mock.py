@@ -223,3 +223,242 @@ print(json.dumps({"same": same, "stats": fr.stats()}))
     assert out.returncode == 0, out.stderr[-2000:]
     res = json.loads(out.stdout.strip().splitlines()[-1])
     assert res["same"] and res["stats"][0] == 0 and res["stats"][1] == 6, res
+
+
+# ------------------------------------------------------------------ the compaction contract: the mock against tools/qz_compact_ref.py
+import numpy as np  # noqa: E402
+
+import qz_compact_ref as R  # noqa: E402
+
+
+def aligned(n: int, fill: np.ndarray | None = None, align: int = 64, skew: int = 0) -> np.ndarray:
+    """n bytes at an `align`-aligned address plus `skew`, holding `fill` (zeros by default)"""
+    raw = np.zeros(n + align + skew, dtype=np.uint8)
+    o = (-raw.ctypes.data) % align + skew
+    a = raw[o:o + n]
+    if fill is not None:
+        a[:] = fill[:n]
+    return a
+
+
+def canary(n: int, seed: int = 99) -> np.ndarray:
+    return np.random.default_rng(seed).integers(0, 256, n, dtype=np.uint8)
+
+
+def mock_compact(plug, batch, arena_bytes, slack=4096, n=None, work_bytes=None, arena_skew=0, work_skew=0, null=()):
+    """the mock's qzstd_hip_compact on a batch -> (return value, arena + slack bytes after the call, the canary they held before).
+    arena_skew / work_skew: bytes past an aligned address; null: the pointers passed as NULL"""
+    L = plug.lib
+    L.qzstd_hip_compact.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    C.c_size_t, C.c_void_p, C.c_size_t]
+    nb = len(batch.blocks) if n is None else n
+    before = canary(arena_bytes + slack, seed=arena_bytes & 0xFFFF)
+    arena = aligned(arena_bytes + slack, before, skew=arena_skew)
+    work_bytes = R.workspace_bytes(len(batch.blocks)) if work_bytes is None else work_bytes
+    work = aligned(work_bytes, skew=work_skew)
+    ptr = {"src": batch.src, "blocks": batch.blocks, "seqs": batch.seqs, "counts": batch.counts, "arena": arena, "work": work}
+    ptr = {k: None if k in null else v.ctypes.data for k, v in ptr.items()}
+    r = L.qzstd_hip_compact(0, None, ptr["src"], ptr["blocks"], nb, ptr["seqs"], ptr["counts"], ptr["arena"], arena_bytes, ptr["work"],
+                            work_bytes)
+    return r, arena.copy(), before
+
+
+def check_against_reference(plug, batch, arena_bytes, slack=4096):
+    r, got, before = mock_compact(plug, batch, arena_bytes, slack)
+    assert r == 0
+    want, used, kept = batch.reference(arena_bytes, before)
+    assert used <= arena_bytes
+    bad = np.flatnonzero(got[:arena_bytes] != want)
+    assert not len(bad), "arena bytes differ from the contract from %d (of %d; used %d)" % (bad[0], arena_bytes, used)
+    assert np.array_equal(got[arena_bytes:], before[arena_bytes:]), "bytes past arenaBytes were written"
+    return kept
+
+
+@pytest.mark.parametrize("seed", [1, 2, 3])
+def test_mock_compaction_follows_the_contract(devmock, seed):
+    """random valid batches, every block kept: headers, packed entries and literals byte for byte"""
+    plug, _ = devmock
+    rng = np.random.default_rng(seed)
+    lens = [int(x) for x in rng.integers(1, 131073, 20)] + [131072, 16, 7, 1]
+    batch = R.make_batch(rng, lens, order="shuffled" if seed == 2 else "block", gap=48 if seed == 3 else 0)
+    assert check_against_reference(plug, batch, batch.need() + 3).all()
+
+
+def test_mock_compaction_mutations(devmock):
+    """one block per rejection rule, each at its boundary: accepted and rejected exactly as the contract says"""
+    plug, _ = devmock
+    for seed in range(4):
+        batch, where = R.mutation_batch(np.random.default_rng(100 + seed))
+        kept = check_against_reference(plug, batch, batch.need())
+        for b, name in where.items():
+            assert kept[b] == R.MUTATIONS[name], (name, b)
+        assert sum(kept) == len(kept) - sum(not v for v in R.MUTATIONS.values())
+
+
+def test_mock_compaction_capacity(devmock):
+    """an arena of exactly the needed size keeps every block; one byte less drops the last one only; the first block that does not fit
+    and every block after it (a failed one among them) contribute nothing; an arena of headers alone keeps nothing"""
+    plug, _ = devmock
+    rng = np.random.default_rng(7)
+    lens = [int(x) for x in rng.integers(1, 3000, 40)]
+    batch = R.make_batch(rng, lens, mutations={30: "count_error"})
+    need = batch.need()
+    assert check_against_reference(plug, batch, need).sum() == 39
+    kept = check_against_reference(plug, batch, need - 1)
+    assert kept.sum() == 38 and not kept[39]
+    for first in (1, 17, 25):
+        kept = check_against_reference(plug, batch, batch.need(first))
+        assert kept[:first].sum() == first and not kept[first:].any()
+        kept = check_against_reference(plug, batch, batch.need(first + 1) - 1)
+        assert kept[:first].sum() == first and not kept[first:].any()
+    assert not check_against_reference(plug, batch, R.entries_off(40)).any()
+
+
+@pytest.mark.parametrize("odd", [1, 3, 513])
+def test_mock_compaction_header_padding(devmock, odd):
+    """n odd: the 8 bytes between the headers and the entries keep what they held"""
+    plug, _ = devmock
+    rng = np.random.default_rng(odd)
+    batch = R.make_batch(rng, [int(x) for x in rng.integers(1, 400, odd)])
+    check_against_reference(plug, batch, batch.need())
+
+
+def test_mock_compaction_refusals(devmock):
+    """the refusals the kernel makes, and nothing written: misaligned arena or workspace, a short workspace, an arena smaller than its
+    headers, each null pointer; nBlocks 0 returns 0"""
+    plug, _ = devmock
+    batch = R.make_batch(np.random.default_rng(5), [100, 200, 300])
+    need = batch.need()
+    cases = [dict(arena_skew=8), dict(work_skew=4), dict(work_bytes=R.workspace_bytes(3) - 1)]
+    cases += [dict(null=(k,)) for k in ("src", "blocks", "seqs", "counts", "arena", "work")]
+    for case in cases:
+        r, got, before = mock_compact(plug, batch, need, **case)
+        assert r != 0 and np.array_equal(got, before), case
+    r, got, before = mock_compact(plug, batch, R.entries_off(3) - 1)
+    assert r != 0 and np.array_equal(got, before)
+    r, got, before = mock_compact(plug, batch, need, n=0)
+    assert r == 0 and np.array_equal(got, before)
+
+
+# ------------------------------------------------------------------ near-raw blocks: libzstd stores them raw, so must the device path
+def near_raw_input(chunk: int, seed: int) -> bytes:
+    """random bytes with 0-3 % planted repeats per 128 KiB block (per chunk, when smaller); 256 KiB chunks: one block of each frame
+    near-raw, the other text that compresses well"""
+    if chunk > 131072:
+        return K.near_raw_text(seed, 4 * chunk)
+    size = {16: 1024 * 16, 100: 600 * 100, 1024: 256 * 1024, 4096: 96 * 4096, 32768: 24 * 32768, 131072: 8 * 131072}[chunk] + chunk // 3
+    return K.near_raw(seed, size, chunk)
+
+
+NEAR_RAW_CHUNKS = [16, 100, 1024, 4096, 32768, 131072, 262144]
+NEAR_RAW_LEVELS = [(1, False), (3, False), (6, False), (12, False), (1, True)]
+
+
+@pytest.mark.parametrize("level,ext_rep", NEAR_RAW_LEVELS)
+@pytest.mark.parametrize("chunk", NEAR_RAW_CHUNKS)
+def test_device_near_raw_blocks(devmock, zstd, oracle, chunk, level, ext_rep, monkeypatch):
+    """a block whose compressed body does not beat its size by (size >> 6) + 2 bytes is stored raw by libzstd: the frame takes the
+    raw-bytes path and equals the reference; every frame is counted once"""
+    plug, F = devmock
+    if ext_rep:
+        monkeypatch.setenv("QZSTD_HIP_EXT_REPCODES", "1")
+    data = near_raw_input(chunk, seed=chunk + level)
+    buf = DevBuf(plug, data)
+    fr = D.DeviceFront(3, level, chunk, ext_rep=int(ext_rep), lib=F)
+    try:
+        got = fr.compress_device(buf.addr, len(data))
+        want = reference(zstd, oracle, data, chunk, level, ext_rep)
+        bad = [c for c in range(len(want)) if got[c] != want[c]]
+        assert len(got) == len(want) and not bad, "%d of %d frames differ, first %s" % (len(bad), len(want), bad[:8])
+        st = fr.stats()
+        assert st[0] + st[1] == len(want) and st[3] == len(data), st
+    finally:
+        fr.close()
+
+
+@pytest.mark.parametrize("chunk", [131072, 393216])
+def test_device_rle_blocks(devmock, zstd, oracle, chunk):
+    """blocks of one repeated byte or of "ab" repeats (libzstd's RLE blocks, not the first block of a frame): the frames are the reference's"""
+    plug, F = devmock
+    data = bytes(chunk) + b"ab" * chunk + bytes(chunk // 2) + b"x" * 1000
+    buf = DevBuf(plug, data)
+    fr = D.DeviceFront(2, 1, chunk, lib=F)
+    try:
+        assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, chunk, 1)
+    finally:
+        fr.close()
+
+
+@pytest.mark.parametrize("chunk", [16, 32, 64, 100])
+def test_device_tiny_chunks_of_mixed_data(devmock, zstd, oracle, chunk):
+    plug, F = devmock
+    data = K.by_name("mix", 2000 * chunk // 4 + 5, seed=chunk)
+    buf = DevBuf(plug, data)
+    fr = D.DeviceFront(3, 1, chunk, lib=F)
+    try:
+        assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, chunk, 1)
+        assert sum(fr.stats()[:2]) == (len(data) + chunk - 1) // chunk
+    finally:
+        fr.close()
+
+
+# ------------------------------------------------------------------ chunk and part layouts
+@pytest.mark.parametrize("chunk,offset", [(200000, 0), (100003, 0), (300001, 3)])
+def test_device_ragged_chunks(devmock, zstd, oracle, chunk, offset):
+    """chunks that are no multiple of 16 (staged at another pitch) and chunks above 128 KiB that are no multiple of it (a short block
+    inside every frame); near-raw and text data in turn, so that both ways of building a frame run"""
+    plug, F = devmock
+    data = K.near_raw_text(chunk, 3 * chunk + 3999, chunk)
+    buf = DevBuf(plug, data, offset)
+    fr = D.DeviceFront(3, 1, chunk, lib=F)
+    try:
+        assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, chunk, 1)
+        st = fr.stats()
+        assert st[0] + st[1] == 4 and st[1] >= 1, st
+    finally:
+        fr.close()
+
+
+def test_device_many_blocks_in_one_part(devmock, zstd, oracle):
+    """1000-byte chunks: 700 blocks in one compaction launch (more than one 512-block step of the scan)"""
+    plug, F = devmock
+    data = K.by_name("mix", 700 * 1000 - 17, seed=4)
+    buf = DevBuf(plug, data)
+    fr = D.DeviceFront(3, 1, 1000, lib=F)
+    try:
+        before = plug.lib.qzstd_mock_compact_launches()
+        assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, 1000, 1)
+        assert plug.lib.qzstd_mock_compact_launches() == before + 1
+    finally:
+        fr.close()
+
+
+@pytest.mark.parametrize("part,parts", [(3 * 65536 + 1, 4), (1000, 11)])
+def test_device_part_sizes(devmock, zstd, oracle, part, parts, monkeypatch):
+    """a part size that is no whole number of chunks (rounded down: 3 chunks) and one below a chunk (one chunk per part); the part
+    count does not divide the chunk count"""
+    plug, F = devmock
+    monkeypatch.setenv("QZSTD_FRONT_DEVICE_PART", str(part))
+    data = K.by_name("text", 10 * 65536 + 999, seed=6)
+    buf = DevBuf(plug, data)
+    fr = D.DeviceFront(3, 1, 65536, lib=F)
+    try:
+        before = plug.lib.qzstd_mock_compact_launches()
+        assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, 65536, 1)
+        assert plug.lib.qzstd_mock_compact_launches() == before + parts
+    finally:
+        fr.close()
+
+
+def test_device_front_reused_across_sizes(devmock, zstd, oracle, monkeypatch):
+    """one front for a large, a small and a large call: the slot buffers grow, then are reused"""
+    plug, F = devmock
+    monkeypatch.setenv("QZSTD_FRONT_DEVICE_PART", str(8 * 32768))
+    fr = D.DeviceFront(3, 1, 32768, lib=F)
+    try:
+        for size, seed in ((40 * 32768 + 5, 1), (3 * 32768 - 7, 2), (50 * 32768 + 11, 3)):
+            data = K.by_name("mix", size, seed=seed)
+            buf = DevBuf(plug, data, seed)
+            assert fr.compress_device(buf.addr, len(data)) == reference(zstd, oracle, data, 32768, 1), size
+    finally:
+        fr.close()

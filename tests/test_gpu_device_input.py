@@ -134,7 +134,7 @@ def test_device_host_pointers_and_software_fronts_are_refused(front_lib, gpu_plu
         gpu_plugin.lib.qzstd_hip_host_free(pinned)
 
 
-@pytest.mark.parametrize("level,short", [(1, False), (6, False), (1, True)])
+@pytest.mark.parametrize("level,short", [(1, False), (6, False), (1, True), (3, False), (12, False), (0x101, False)])
 def test_compaction_kernel_bit_exact(gpu_plugin, oracle, level, short):
     """qzstd_hip_compact on a random ragged batch (one block marked failed): headers, packed entries and literal stream against a
     numpy extraction from the oracle's sequences.  short: an arena that holds the first blocks only — every block from the first one that
@@ -208,3 +208,65 @@ def test_compaction_kernel_bit_exact(gpu_plugin, oracle, level, short):
     assert eo + 8 * len(ent) + len(lit) <= arena_bytes
     assert np.array_equal(arena[eo:eo + 8 * len(ent)].view(np.uint64), ent)
     assert np.array_equal(arena[eo + 8 * len(ent):eo + 8 * len(ent) + len(lit)], lit)
+
+
+# ------------------------------------------------------------------ near-raw blocks: libzstd stores them raw, so must the device path
+def near_raw_input(chunk: int, seed: int) -> bytes:
+    """random bytes with 0-3 % planted repeats per 128 KiB block (per chunk, when smaller); above 128 KiB: one block of each frame
+    near-raw, the other text"""
+    if chunk > 131072:
+        return K.near_raw_text(seed, 4 * chunk)
+    size = {16: 1024 * 16, 100: 600 * 100, 1024: 256 * 1024, 4096: 96 * 4096, 32768: 24 * 32768, 131072: 8 * 131072}[chunk] + chunk // 3
+    return K.near_raw(seed, size, chunk)
+
+
+@pytest.mark.parametrize("level,ext_rep", [(1, False), (3, False), (6, False), (12, False), (1, True)])
+@pytest.mark.parametrize("chunk", [16, 100, 1024, 4096, 32768, 131072, 262144])
+def test_device_near_raw_blocks(front_lib, zstd, oracle, chunk, level, ext_rep, monkeypatch):
+    """a block whose compressed body does not beat its size by (size >> 6) + 2 bytes is stored raw by libzstd: such frames take the
+    raw-bytes path and equal the reference; every frame is counted once"""
+    if ext_rep:
+        monkeypatch.setenv("QZSTD_HIP_EXT_REPCODES", "1")
+    data = near_raw_input(chunk, seed=chunk + level)
+    st = check(front_lib, zstd, oracle, data, chunk, level, threads=4, ext_rep=ext_rep)
+    assert st[0] + st[1] == (len(data) + chunk - 1) // chunk and st[3] == len(data), st
+
+
+@pytest.mark.parametrize("chunk,offset", [(200000, 0), (100003, 0), (300001, 3)])
+def test_device_ragged_chunks(front_lib, zstd, oracle, chunk, offset):
+    """chunks that are no multiple of 16 (staged at another pitch by a 2D copy) and chunks above 128 KiB that are no multiple of it (a
+    short block inside every frame, read in place); near-raw and text chunks, so that both ways of building a frame run"""
+    st = check(front_lib, zstd, oracle, K.near_raw_text(chunk, 3 * chunk + 3999, chunk), chunk, 1, threads=4, offset=offset)
+    assert st[0] + st[1] == 4 and st[1] >= 1, st
+
+
+def test_device_many_small_chunks_in_one_part(front_lib, zstd, oracle):
+    """1000-byte chunks: 700 blocks in one compaction launch, more than one 512-block step of the scan"""
+    check(front_lib, zstd, oracle, K.by_name("mix", 700 * 1000 - 17, seed=4), 1000, 1, threads=4)
+
+
+def test_device_default_part_of_640_blocks(front_lib, zstd, oracle):
+    """20 MiB at 32 KiB chunks with the default part size: one launch of 640 blocks"""
+    st = check(front_lib, zstd, oracle, K.by_name("system", 20 << 20, seed=5), 32768, 1, threads=16)
+    assert st[0] + st[1] == 640, st
+
+
+@pytest.mark.parametrize("part", [3 * 65536 + 1, 1000])
+def test_device_part_sizes(front_lib, zstd, oracle, part, monkeypatch):
+    """a part size that is no whole number of chunks (rounded down to 3) and one below a chunk (one chunk per part); the part count
+    does not divide the chunk count"""
+    monkeypatch.setenv("QZSTD_FRONT_DEVICE_PART", str(part))
+    check(front_lib, zstd, oracle, K.by_name("text", 10 * 65536 + 999, seed=6), 65536, 1, threads=4)
+
+
+def test_device_front_reused_across_sizes(front_lib, zstd, oracle, monkeypatch):
+    """one front for a large, a small and a large call: the slot buffers grow, then are reused"""
+    monkeypatch.setenv("QZSTD_FRONT_DEVICE_PART", str(8 * 32768))
+    fr = D.DeviceFront(4, 1, 32768, lib=front_lib)
+    try:
+        for size, seed in ((40 * 32768 + 5, 1), (3 * 32768 - 7, 2), (50 * 32768 + 11, 3)):
+            data = K.by_name("mix", size, seed=seed)
+            t = on_gpu(b"\0" * seed + data)[seed:]
+            assert D.compress_tensor(fr, t) == D.reference_frames(zstd, oracle, data, 32768, 1), size
+    finally:
+        fr.close()

@@ -7,7 +7,8 @@ Two families:
   The GPU box runs the same image, so the bytes are reproducible there; every part is
   optional and the mix falls back to the seeded generators below when a file is absent.
 * seeded generators (``text``, ``binary_struct``, ``weblog``, ``mixed_entropy``,
-  ``mix``) — the shapes SURVEY.md §8(d) names for BASELINE configs 1-5.
+  ``mix``) — the shapes SURVEY.md §8(d) names for BASELINE configs 1-5 — and ``near_raw``
+  (random bytes with a little structure: blocks libzstd stores raw or nearly so).
 
 Nothing here reads /root/reference.
 """
@@ -131,6 +132,31 @@ def mixed_entropy(seed: int, size: int, seg: int = 64 * KiB) -> bytes:
 
 def incompressible(seed: int, size: int) -> bytes:
     return np.random.default_rng(seed).integers(0, 256, size, dtype=np.uint8).tobytes()
+
+
+def near_raw(seed: int, size: int, block: int = 128 * KiB, max_frac: float = 0.03) -> bytes:
+    """Random bytes with, per `block`, up to `max_frac` of them (a uniform draw per block) replaced by copies of earlier bytes of the
+    same block: a little structure, so that a block compresses to within a few per cent of its size — where libzstd stores it raw."""
+    rng = np.random.default_rng(seed)
+    out = rng.integers(0, 256, size, dtype=np.uint8)
+    for o in range(0, size, block):
+        n = min(block, size - o)
+        want = int(rng.uniform(0.0, max_frac) * n + rng.uniform())  # small blocks: one run now and then
+        done = 0
+        while done < want and n >= 8:
+            run = int(min(rng.integers(4, 33), n // 2))
+            p = o + int(rng.integers(run, n - run + 1))
+            q = o + int(rng.integers(0, p - o - run + 1))
+            out[p:p + run] = out[q:q + run]
+            done += run
+    return out.tobytes()
+
+
+def near_raw_text(seed: int, size: int, block: int = 128 * KiB) -> bytes:
+    """blocks of `block` bytes, near_raw and text: near_raw, text, text, near_raw, then again — frames of two blocks hold one of each,
+    in both orders"""
+    nr, tx = near_raw(seed, size, block), text(seed, size)
+    return b"".join((nr if (o // block) % 4 in (0, 3) else tx)[o:o + block] for o in range(0, size, block))
 
 
 def mix(seed: int, size: int) -> bytes:
