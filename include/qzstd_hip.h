@@ -111,6 +111,22 @@ size_t qzstd_hip_sequence_bound(size_t srcSize);
 /* dynamic LDS bytes the kernel needs for a launch whose largest block is maxBlockLen */
 size_t qzstd_hip_lds_bytes(int level, uint32_t maxBlockLen);
 
+/* Layout numbers that both the kernels (csrc/qzstd_kernels.hip) and the host's sizes (csrc/qzstd_profile.c) use.  QZ_RING and
+ * QZ_CHAIN_TABLE are tuning knobs of A/B builds (make variant XFLAGS="-DQZ_CHAIN_TABLE=n"), which pass them to every file. */
+#ifndef QZ_RING
+#define QZ_RING 32768u /* bytes of the LDS ring of recent block bytes, a power of two.  32 KiB: two workgroups per CU at levels 1-2 and 5-12.
+                        * Measured A/B (bit-exact either way): 16 KiB = three per CU buys nothing at level 1 (12.32 vs 11.96 ms per GiB: the CU is
+                        * VALU-bound, not latency-bound) and costs 13 % at the chain levels (more sources beyond the ring's reach) */
+#endif
+#define QZSTD_HIP_RING_MIRROR 128u /* bytes of the ring's start mirrored behind its end, so that a read never has to wrap */
+#ifndef QZ_CHAIN_TABLE
+#define QZ_CHAIN_TABLE 5888u /* head-table entries of the chain levels (levels >= 5) */
+#endif
+#define QZSTD_HIP_LDS_BASE 16u     /* first LDS byte the kernels use (never the null pointer): counted by qzstd_hip_lds_bytes() */
+#define QZSTD_HIP_LDS_CTRL 64u     /* the workgroup's control words */
+#define QZSTD_HIP_LDS_SVC 96u      /* the resident service's item words, at the end of the allocation */
+#define QZSTD_HIP_LDS_MAX 163840u  /* LDS per CU on gfx950 (160 KiB) */
+
 /* ---- device / memory / stream plumbing ---- */
 int qzstd_hip_device_count(void); /* number of usable devices (gfx950: the only code object in the library), <0 on error;
                                    * devices are indexed 0..count-1 in that filtered order */
@@ -219,7 +235,7 @@ typedef struct {
                                         * Eight were measured in round 4 (bit-exact): level 5 61 -> 118, level 6 102 -> 194, level 12 269 -> 347 ms per GiB — the entries of
                                         * positions whose predecessors lie in the same tile are hopped together link by link from LDS, seven dependent reads instead of three */
 #endif
-#define QZSTD_HIP_SVC_WORK_BYTES ((size_t)QZSTD_HIP_BLOCK_MAX * (8u * QZSTD_HIP_CHAIN_ENTRY_LINKS + 4u) + (size_t)QZSTD_HIP_SVC_MAX_ITEMS * 5888u * 4u) /* chain entries of the history and of the
+#define QZSTD_HIP_SVC_WORK_BYTES ((size_t)QZSTD_HIP_BLOCK_MAX * (8u * QZSTD_HIP_CHAIN_ENTRY_LINKS + 4u) + (size_t)QZSTD_HIP_SVC_MAX_ITEMS * QZ_CHAIN_TABLE * 4u) /* chain entries of the history and of the
                                        * items' own positions, first links, and one published head table per item */
 int qzstd_hip_service_submit(int device, int level, const qzstd_hip_svc_req_t *req);
 int qzstd_hip_service_stop(int device);          /* asks the resident kernels to leave and waits for them; 0 = stopped */

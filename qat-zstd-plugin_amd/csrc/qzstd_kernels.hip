@@ -65,53 +65,18 @@
 #include "qzstd_hip.h"
 #include "qzstd_hip_device.h"
 
-#ifndef QZ_REP_DEFER
-#define QZ_REP_DEFER 1 /* the launch kernels of the repeat-aware parse BELOW THE CHAIN LEVELS (level 1-4 | REPCODES) parse AFTER their tile loop, eight segments at a
-                        * time (qz_item: DEFER): 65.0 -> 23.5 ms per GiB at level 1 | REPCODES, 125.9 -> 40.4 at level 3 | REPCODES, bit-exact.  A/B: 0 = in the loop,
-                        * one wave, as the resident service's items do; 2 = deferred at the chain levels too — measured SLOWER there (level 12: 185.8 -> 192.1 ms
-                        * per GiB, config 4's shape 105.7 -> 107.8): the chain walk takes longer than the parse wave's serial chain, which the lock-step loop
-                        * hides completely, so deferring it only adds the parse's own time */
-#endif
-#ifndef QZ_PLAIN_DEFER
-#define QZ_PLAIN_DEFER 1 /* the launch kernels of levels 1-4 defer their plain parse and their emission in the same way (csrc/qzstd_profile.c must agree: the workspace) */
-#endif
-#ifndef QZ_CHAIN_SHIFT
-#define QZ_CHAIN_SHIFT 1 /* chain levels: a tile's start flags are written in the next iteration's first interval (A/B: 0) */
-#endif
-#ifndef QZ_CHAIN_DEFER_EXT
-#define QZ_CHAIN_DEFER_EXT 0 /* chain walk (round 6 A/B, 1): the 32-byte extensions of a step's links in a loop of their own, every lane taking ITS next one — bit-exact, +2 ... +7 % time (profiles/r06_ab_chain_walk.txt); 0 = inside
-                              * every link's own block, as in rounds 3-5) */
-#endif
-/* Round 6: "progress-inverse priority".  The issue arbiter serves the OLDER waves of a SIMD first, so waves 4-7 of a workgroup reach every barrier last
- * and run the end of every interval alone, with nobody to hide their latencies behind (profiles/r06_level1_wave_timing_before.txt).  A matcher wave of the
- * tile levels therefore starts an interval at priority 2 and lowers it as it gets on (1 after the first part, 0 after the second): whoever is behind
- * wins the arbitration; the parse wave stays above them at 3.  Measured (profiles/r06_ab_small_steps.txt): level 1 11.91 -> 11.78 ms per GiB (-1.1 %),
- * level 3 10.47 -> 10.31 (-1.6 %); 2 = the same with priorities 1, 0, 0: half of that; a fixed raised priority for waves 4-7: nothing.  0 = off (A/B). */
-#ifndef QZ_PROGRESS_PRIO
-#define QZ_PROGRESS_PRIO 1
-#endif
-#define QZ_PRIO(n) do { if (QZ_PROGRESS_PRIO && !CHAIN) __builtin_amdgcn_s_setprio((n) >= QZ_PROGRESS_PRIO ? (n) + 1 - QZ_PROGRESS_PRIO : 0); } while (0) /* 1: 2,1,0   2: 1,0,0 */
-/* A/B (round 6): the emission's common path trimmed — the "a capped match was extended" flag rides in bit 31 of the record's sequence base (no second LDS
- * request + scalar test per window), the own chosen bit is tested without a 64-bit shift by the lane (a quarter-rate instruction).  Fewer instructions,
- * bit-exact — and +2.8 % time at level 1 (12.25 vs 11.91 ms per GiB), +1.4 % at level 3: NOT the product (profiles/r06_ab_small_steps.txt). */
-#ifndef QZ_EMIT_TRIM
-#define QZ_EMIT_TRIM 0
-#endif
-constexpr uint32_t kExtFlag = 0x80000000u; /* QZ_EMIT_TRIM: set in ParseRecs.r3 (the window's first sequence index) when r4 / r5 hold extended lengths */
-#ifndef QZ_CHAIN_HOIST_P
-#define QZ_CHAIN_HOIST_P 0 /* A/B: 1 = the position's own 32 bytes behind its head requested and byte-aligned ONCE per tile, kept in registers over the whole walk */
-#endif
+/* Round 6: "progress-inverse priority" (QZ_PRIO, below the chain levels).  The issue arbiter serves the OLDER waves of a SIMD first, so waves 4-7 of a
+ * workgroup reach every barrier last and run the end of every interval alone, with nobody to hide their latencies behind
+ * (profiles/r06_level1_wave_timing_before.txt).  A matcher wave of the tile levels therefore starts an interval at priority 2 and lowers it as it gets on
+ * (1 after the first part, 0 after the second): whoever is behind wins the arbitration; the parse wave stays above them at 3.  Measured
+ * (profiles/r06_ab_small_steps.txt): level 1 11.91 -> 11.78 ms per GiB (-1.1 %), level 3 10.47 -> 10.31 (-1.6 %). */
+#define QZ_PRIO(n) do { if (!CHAIN) __builtin_amdgcn_s_setprio(n); } while (0)
 
 namespace {
 
 constexpr int kMatchWaves = 8;
 constexpr int kMatchThreads = kMatchWaves * 64; /* one position per matcher thread per tile */
 constexpr int kThreads = kMatchThreads + 64;     /* + 1 parse wave */
-#ifndef QZ_RING
-#define QZ_RING 32768u /* bytes of the LDS ring (csrc/qzstd_profile.c: QZ_RING_BYTES must agree).  32 KiB: two workgroups per CU at
-                        * levels 1-2 and 5-12.  Measured A/B (bit-exact either way): 16 KiB = three per CU buys nothing at level 1 (12.32 vs 11.96 ms per
-                        * GiB: the CU is VALU-bound, not latency-bound) and costs 13 % at the chain levels (more sources beyond the ring's reach) */
-#endif
 constexpr uint32_t kTileLog = 9;                 /* tile = 512 positions = kMatchThreads */
 constexpr uint32_t kTile = 1u << kTileLog;
 constexpr uint32_t kWin = kTile >> 6;            /* 64-position windows per tile (one per matcher wave) */
@@ -127,31 +92,19 @@ constexpr uint32_t kNone = 0xFFFFFFFFu;
  * ("far" candidates, a few %) are compared straight from HBM/L2 instead. */
 constexpr uint32_t kRing = QZ_RING;  /* a power of two: x mod kRing is one AND */
 constexpr uint32_t kRingMask = kRing - 1u;
-constexpr uint32_t kMirror = 128u;
+constexpr uint32_t kMirror = QZSTD_HIP_RING_MIRROR;
 constexpr uint32_t kLook = 4608u;  /* bytes staged ahead of the current tile (covers the bounded extension) */
 constexpr uint32_t kNear = kRing - kLook - 3u * kTile - 1024u; /* kRing - kLook - 3 tiles of pipeline lag - slack */
 static_assert((kRing & kRingMask) == 0u && kRing >= 16384u, "the ring is a power of two of at least 16 KiB");
-constexpr size_t kLdsPerCu = 163840u; /* 160 KB */
-#ifdef QZ_EXP_LINKS4_SPACED /* experiment: four links per entry at the SPACING of eight (same gathers and hops as four, the lines of eight) */
-constexpr uint32_t kEL = 4u;
-#else
+constexpr size_t kLdsPerCu = QZSTD_HIP_LDS_MAX;
 constexpr uint32_t kEL = QZSTD_HIP_CHAIN_ENTRY_LINKS; /* links per chain entry: the walk needs one dependent gather per kEL links */
-#endif
-constexpr uint32_t kEQ = QZSTD_HIP_CHAIN_ENTRY_LINKS / 4u; /* 16-byte words between consecutive entries (= per entry, outside the experiment) */
+constexpr uint32_t kEQ = QZSTD_HIP_CHAIN_ENTRY_LINKS / 4u; /* 16-byte words per chain entry */
 static_assert(kEL == 4u || kEL == 8u, "chain entries hold four or eight links");
-constexpr uint32_t kLdsBase = 16u; /* first LDS byte the kernel uses (csrc/qzstd_profile.c: QZ_LDS_CTRL covers it) */
-/* Tiles between the matchers and the emission of a tile = tiles of parse words and emission records kept in LDS (csrc/qzstd_profile.c: QZ_PARSE_LAG
- * must agree).  2 = the parse wave in lock-step with the matchers: THE PRODUCT at every level.  QZ_PARSE_LAG = 3 or 4 builds the round-6 experiment
- * for levels 1-4 (the round-5 verdict's "take the serial parse off the barrier-critical path"): a DECOUPLED parse wave that parses whatever tile is
- * ready, window by window, and joins the matchers' barriers when they are all waiting at one — bit-exact, and 14 % SLOWER (13.6 vs 11.9 ms per GiB
- * at level 1; profiles/r06_ab_decoupled_parse_wave.txt says why: running without pauses, the parse wave's serial chain takes 5 200 cycles per tile
- * and IS the tile's time, where the lock-step one took 4 600 and idled a quarter of the time). */
-#ifndef QZ_PARSE_LAG
-#define QZ_PARSE_LAG 2
-#endif
-constexpr uint32_t kParseLag = QZ_PARSE_LAG;
-static_assert(kParseLag >= 2u && kParseLag <= 4u, "2 = the lock-step parse wave of rounds 1-5 at every level");
-constexpr uint32_t kCtlArrive = 4u; /* control word: barriers the matcher waves have reached, summed over the eight waves (a HINT for the parse wave) */
+constexpr uint32_t kLdsBase = QZSTD_HIP_LDS_BASE; /* first LDS byte the kernel uses */
+/* Tiles between the matchers and the emission of a tile = tiles of parse words and emission records kept in LDS (qzstd_hip_lds_bytes counts two):
+ * the parse wave runs in lock-step with the matchers.  (Round 6 measured a DECOUPLED parse wave that kept three or four tiles in flight: bit-exact
+ * and 14 % slower at level 1, profiles/r06_ab_decoupled_parse_wave.txt.) */
+constexpr uint32_t kLagT = 2u;
 
 struct LaunchArgs {
     const uint8_t *src;
@@ -511,7 +464,7 @@ __device__ __forceinline__ void parse_window(const qzstd_hip_profile_t &pf, cons
     r.r0 = wrlane<W>(r.r0, (uint32_t)chosen);
     r.r1 = wrlane<W>(r.r1, (uint32_t)(chosen >> 32));
     r.r2 = wrlane<W>(r.r2, anchorIn);
-    r.r3 = wrlane<W>(r.r3, (QZ_EMIT_TRIM && ext0) ? (seqBase | kExtFlag) : seqBase);
+    r.r3 = wrlane<W>(r.r3, seqBase);
     if (ext0) { /* rare */
         r.r4 = wrlane<W>(r.r4, ext0);
         r.r5 = wrlane<W>(r.r5, ext1);
@@ -824,18 +777,14 @@ __device__ __forceinline__ void emit_window(const qzstd_hip_profile_t &pf, const
         const uint4 rec = *reinterpret_cast<const uint4 *>(srec);
         const u64 chosen = (u64)rec.x | ((u64)rec.y << 32);
         if (!chosen) return;
-        const uint32_t anchorIn = rec.z, seqBase = QZ_EMIT_TRIM ? rec.w & ~kExtFlag : rec.w;
-        const bool hasExt = QZ_EMIT_TRIM ? (rdfirst(rec.w) & kExtFlag) != 0u : true; /* uniform: a scalar branch skips the (rare) extended matches */
-        if (hasExt) {
-            const uint32_t ext0 = rdfirst(srec[4]);
-            if (ext0) {
-                const uint32_t ext1 = srec[5];
-                if ((ext0 >> 24) == lane) len = ext0 & 0xFFFFFFu; /* extended by the parse wave */
-                if (ext1 && (ext1 >> 24) == lane) len = ext1 & 0xFFFFFFu;
-            }
+        const uint32_t anchorIn = rec.z, seqBase = rec.w;
+        const uint32_t ext0 = rdfirst(srec[4]);
+        if (ext0) {
+            const uint32_t ext1 = srec[5];
+            if ((ext0 >> 24) == lane) len = ext0 & 0xFFFFFFu; /* extended by the parse wave */
+            if (ext1 && (ext1 >> 24) == lane) len = ext1 & 0xFFFFFFu;
         }
-        if (QZ_EMIT_TRIM) ch = (((lane & 32u) ? rec.y : rec.x) >> (lane & 31u)) & 1u; /* (a 64-bit shift by the lane is a quarter-rate instruction) */
-        else ch = (chosen >> lane) & 1ull;
+        ch = (chosen >> lane) & 1ull;
         const u64 lower = chosen & below(lane);
         const uint32_t myEnd = w0 + lane + len;
         const int jprev = lower ? 63 - __builtin_clzll(lower) : 0;
@@ -989,7 +938,10 @@ struct HistShare {
     uint32_t *linkFlags;/* [kSvcMaxItems]: item j has published the first links of its range */
     uint32_t *tabs;     /* [kSvcMaxItems][kSvcTabStride] in the request's scratch */
 };
-constexpr uint32_t kSvcTabStride = 5888u; /* words per published head table (the chain levels' tableSize; QZSTD_HIP_SVC_WORK_BYTES counts 32 of them) */
+constexpr uint32_t kSvcTabStride = QZ_CHAIN_TABLE; /* words per published head table (the chain levels' tableSize; QZSTD_HIP_SVC_WORK_BYTES counts 32 of them) */
+/* the deferred repeat-aware parse of a launch (qz_item) borrows the head table for eight windows of parse words; the smallest table it
+ * borrows is the chain levels' (levels 1-2: 8192 entries) */
+static_assert((uint32_t)kMatchWaves * kPvStride <= QZ_CHAIN_TABLE, "the deferred parse's eight windows of parse words must fit in the head table (QZ_CHAIN_TABLE)");
 
 /* One work item (a block, or a run of whole segments of one): `blk` describes it, gsrc = the block's bytes in device memory,
  * out = the item's result region, chainB = its chain entries (CHAIN), p1B = its array of first links (CHAIN, segment items).  Returns, in the parse wave, the item's sequence
@@ -1000,7 +952,7 @@ template <bool HAS_LONG, bool REP, bool CHAIN, bool TURNS, bool NEAR, bool DEFER
 __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_hip_block_t &blk, const uint8_t *gsrc, uint4 *out,
                                             uint4 *chainB, uint32_t *p1B, const HistShare hsh)
 {
-    /* DEFER (round 6, the launch kernels of the repeat-aware parse): THE PARSE IS TAKEN OUT OF THE TILE LOOP.  The repeat-aware parse is a serial
+    /* DEFER (round 6, every launch kernel; the resident service's items keep the parse in the loop): THE PARSE IS TAKEN OUT OF THE TILE LOOP.  The repeat-aware parse is a serial
      * state machine (cursor, two repeat offsets) — in the loop, one wave walks it while eight matcher waves wait 80 % of the time (65 ms per GiB at
      * level 1 | repcodes against 12 without).  But by definition the parse of a 4 KiB SEGMENT depends on nothing before the segment (no match
      * crosses a boundary, the repeat offsets are forgotten there: what lets the resident service cut a block into 32 items), and the candidates
@@ -1008,9 +960,11 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
      * position; the chain levels' dense first-link array, which a launch only uses before the loop) — and AFTERWARDS the block is parsed 32 KiB
      * "quarter" by quarter: the quarter's bytes are staged in the ring, EIGHT waves parse its eight segments at the same time (parse_rep_span<true>,
      * a tile of parse words at a time through a private LDS window, 8-byte records back over the words), the segments' counts are summed, and every
-     * wave emits its own segment's records, one lane per sequence.  Same definition (oracle: qzo_parse_rep), same sequences. */
-    /* DEFER at the chain levels (A/B, QZ_CHAIN8): there the ninth wave also INSERTS for the matchers (chain_insert_tile, one tile ahead); with the parse
-     * deferred, matcher wave 0 — the wave that reaches every barrier of a chain level first — takes the inserts over, and the ninth wave ends */
+     * wave emits its own segment's records, one lane per sequence.  Same definition (oracle: qzo_parse_rep), same sequences: 65.0 -> 23.5 ms per GiB at
+     * level 1 | REPCODES, 125.9 -> 40.4 at level 3 | REPCODES (profiles/r06_ab_deferred_parse.txt).  The plain parse of
+     * levels 1-4 is deferred in the same way (parse_plain_windows).  At the chain levels the ninth wave also INSERTS for the matchers
+     * (chain_insert_tile, one tile ahead); with the parse deferred, matcher wave 0 — the wave that reaches every barrier of a chain level first —
+     * takes the inserts over, and the ninth wave ends. */
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const uint32_t tid = threadIdx.x;
     const uint32_t lane = tid & 63u;
@@ -1022,28 +976,9 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     const qzstd_hip_profile_t pf = args.prof;
     const uint32_t nh = n >= pf.hashBytes ? n - pf.hashBytes + 1u : 0u; /* hashable positions */
     const uint32_t nTiles = (nh + kTile - 1u) >> kTileLog;
-    /* tiles in flight between matching and emission (kParseLag): the decoupled parse wave of levels 1-4; lock-step (2) where the parse wave also
-     * inserts for the matchers (CHAIN) or walks repeat offsets (REP) */
-    constexpr uint32_t kLagT = (CHAIN || REP) ? 2u : kParseLag;
-    constexpr bool kDecoupled = kLagT > 2u;
-    static_assert(!(DEFER && kDecoupled), "the deferred parse replaces the decoupled parse wave experiment");
     /* iterations of the tile loop: the tiles, + the kLagT in which the last tiles are parsed and emitted — which a deferring kernel below the chain
-     * levels does after the loop (at the chain levels a tile's flags are written one iteration later: QZ_CHAIN_SHIFT) */
+     * levels does after the loop (at the chain levels a tile's flags are written one iteration later) */
     const uint32_t itEnd = (DEFER && !CHAIN) ? nTiles : nTiles + kLagT;
-#ifndef QZ_TILE_SHIFT
-#define QZ_TILE_SHIFT 1 /* A/B builds: 0 = lengths, start flags and parse words of a tile all inside its own second interval, as in rounds 1-5 */
-#endif
-    /* Round 6: with the parse wave decoupled, a tile's 32-byte extensions ("tails"), lazy start flags and parse words move to the FIRST interval of
-     * the NEXT iteration: what a matcher wave does between two barriers is a chain of dependent LDS round trips (own bytes -> hash -> table read;
-     * near-table read -> candidate heads -> tails -> flag permute -> parse words: ~4 + ~6.5 per iteration before), and the wave's time between
-     * barriers IS that chain (r06_level1_wave_timing_before.txt: interval 2 takes 2 300 cycles on an otherwise idle SIMD for ~230 vector
-     * instructions).  Shifted, the tails' source bytes are requested together with the next tile's own bytes (one round trip instead of three), the
-     * position's own side of the tails comes from that same request one iteration earlier (13 dwords instead of 5: no request at all), and the flag
-     * permute overlaps the table read.  Same values, same order of table operations: bit-exact. */
-    constexpr bool kShift = kDecoupled && QZ_TILE_SHIFT != 0;
-    /* (offset, length) of the own position in earlier tiles, kept for the emission: [i] = of tile it - 1 - i once the iteration has shifted them — at the
-     * end of interval 2, or (kShift) in interval 1 after the emission, which then finds its tile one place earlier */
-    constexpr uint32_t kEmitIdx = kShift ? kLagT - 2u : kLagT - 1u;
     /* what the parse wave and the late emission read from the ring has to be there still: sources up to kNear back of a tile kLagT tiles behind the matchers */
     static_assert(kNear + kLagT * kTile + 4u <= kRing - kLook, "the ring no longer holds a near source when its tile is parsed / emitted");
     /* below the chain levels the tables are powers of two (csrc/qzstd_profile.c; the launcher refuses anything else): slot = mix >> shift */
@@ -1073,17 +1008,13 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     uint32_t *nearTab = tblL + pf.longSize;
     uint32_t *srec = nearTab + kTile;                  /* [kLagT][kWin][8]  emission records              */
     uint32_t *pv = srec + kLagT * kWin * kSrecWords;   /* [kLagT][kPvStride] per-position parse words     */
-    uint32_t *turnCtr = pv + kLagT * kPvStride;        /* control: [0] whose turn it is to update the tables (TURNS), [2] a verdict, [kCtlArrive] */
-    uint32_t *P1odd = turnCtr + 16u;                   /* [kTile] (CHAIN) predecessors of the odd tiles' positions (the even tiles': nearTab's words) */
+    uint32_t *turnCtr = pv + kLagT * kPvStride;        /* control: [0] whose turn it is to update the tables (TURNS), [2] a verdict */
+    uint32_t *P1odd = turnCtr + QZSTD_HIP_LDS_CTRL / 4u; /* [kTile] (CHAIN) predecessors of the odd tiles' positions (the even tiles': nearTab's words) */
     const uint4 *g128 = reinterpret_cast<const uint4 *>(gsrc);
     Src src;
     src.ring = (LdsWords)ring32;
     src.g = (HbmWords)reinterpret_cast<const uint32_t *>(gsrc);
-#ifdef QZ_EXP_ALLNEAR /* timing experiment only (wrong lengths for far candidates): what the device-memory side of the compares costs a kernel */
-    src.nearLimit = 0xFFFFFFFFu;
-#else
     src.nearLimit = NEAR ? 0xFFFFFFFFu : kNear;
-#endif
     const uint32_t nPad = (n + 15u) & ~15u; /* the caller keeps the buffer readable up to here */
 
     /* ---- clear the tables; segment mode below the chain levels: fast-forward over the tiles before the segment ---- */
@@ -1112,7 +1043,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     for (uint32_t i = tid; i < pf.tableSize + pf.longSize; i += kThreads) tbl[i] = 0u; /* both tables */
     if (!(CHAIN && itBegin != 0u)) { /* (the chain levels' history pass borrows these words first) */
         for (uint32_t i = tid; i < kTile; i += kThreads) nearTab[i] = 0xFFFFFFFFu;
-        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + 16u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
+        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + QZSTD_HIP_LDS_CTRL / 4u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
     }
     const bool sharedHist = CHAIN && hsh.flags != nullptr && hsh.nItems > 1u && pf.tableSize <= kSvcTabStride;
     if (itBegin != 0u || sharedHist) __syncthreads(); /* the cleared tables, before the first insert */
@@ -1267,7 +1198,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         if (tid == 0u) __hip_atomic_store(&hsh.flags[k], hsh.epoch, QZ_RLX_AGENT);
         if (!wait_for(hsh.flags)) return QZSTD_HIP_NSEQ_ERROR;
         for (uint32_t i = tid; i < kTile; i += kThreads) nearTab[i] = 0xFFFFFFFFu;
-        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + 16u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
+        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + QZSTD_HIP_LDS_CTRL / 4u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
     } else if (CHAIN && itBegin != 0u) {
         /* Chain levels, segment item: the history [0, parseFrom) has to be INSERTED AND LINKED, exactly (every position's
          * predecessor in its slot), but not walked.  Going through the tile loop for that costs one exposed HBM round trip per tile
@@ -1402,7 +1333,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         }
         __syncthreads();
         for (uint32_t i = tid; i < kTile; i += kThreads) nearTab[i] = 0xFFFFFFFFu;
-        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + 16u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
+        for (uint32_t i = tid; i < kLagT * kWin * kSrecWords + kLagT * kPvStride + QZSTD_HIP_LDS_CTRL / 4u; i += kThreads) srec[i] = 0u; /* srec, pv, control */
     }
     {
         const uint32_t hiMaskH = pf.hashBytes >= 8 ? 0xFFFFFFFFu : ((1u << (8u * (pf.hashBytes - 4u))) - 1u);
@@ -1448,43 +1379,15 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     }
     __syncthreads();
 
-    /* DEFER, plain parse, A/B (QZ_DEFER_INLOOP): what the NINTH wave — which only keeps the barriers' count in a deferring loop — could parse of the block
-     * WHILE the matchers match: a quarter tile (two windows) per iteration, between the loop's full barrier and its LDS-only one, of tiles whose words
-     * are complete.  That is a quarter of the matchers' pace — eight of a 128 KiB block's 32 segments — and takes the parse after the loop from four
-     * rounds to three.  Measured slower (below): the state stays here for the A/B build. */
-    PlainParse nwSt;                /* the segment in progress */
-    uint32_t nwSeg, nwBase, nwQ;    /* ... its index, the tile in progress, quarters of that tile done */
-    bool nwBegun = false, nwHave = false; /* inside a segment; nwNxt holds the words of the tile after this one */
-    uint32_t nwWds[kWin], nwNxt[kWin];
-    nwSeg = blk.parseFrom >> 12;
-    nwBase = nwSeg << 12;
-    nwQ = 0u;
-    nwSt = PlainParse{ nwBase, 0u, 0xFFFFFFFFu };
-#pragma unroll
-    for (uint32_t j = 0; j < kWin; j++) nwWds[j] = nwNxt[j] = 0u;
-#ifndef QZ_DEFER_INLOOP
-#define QZ_DEFER_INLOOP 0 /* A/B, 1 = the ninth wave parses a quarter tile per iteration during the loop (below).  Built bit-exact and measured SLOWER: level 1 10.81 -> 11.55 ms
-                           * per GiB, level 3 19.3 -> 20.8, level 4 19.8 -> 21.2 (only level 2, whose matchers wait for their turns anyway, gains: 15.0 -> 14.5) —
-                           * even two windows per iteration on the ninth wave delay the two matcher waves of its SIMD, and with them every barrier: what rounds
-                           * 1-5 knew as the co-critical parse wave.  Not kept: 0 = the ninth wave only keeps the barriers' count, the whole parse runs after
-                           * the loop on all nine waves.  profiles/r06_ab_deferred_parse.txt */
-#endif
-#ifndef QZ_NINTH_EXIT
-#define QZ_NINTH_EXIT 1 /* in a kernel that defers its parse below the chain levels the ninth wave has nothing to do in the tile loop: it ENDS before the loop (s_endpgm: a
-                         * barrier only waits for the waves that are left — ISA, S_BARRIER) instead of keeping the barriers' count; eight waves parse and emit after
-                         * the loop, wave 0 closes the block.  Level 1 10.82 -> 9.63 ms per GiB (-11 %), level 2 14.9 -> 12.8, 32 KiB blocks 12.2 -> 10.5, level 3 (one
-                         * workgroup per CU) unchanged: with two workgroups per CU the idle wave was the 17th and 18th of the CU — sixteen matcher waves sit four to a
-                         * SIMD.  A/B: 0 = it stays and keeps the count.  profiles/r06_ab_deferred_parse.txt */
-#endif
-    constexpr bool kNinthExit = DEFER && QZ_NINTH_EXIT != 0 && (REP || CHAIN || QZ_DEFER_INLOOP == 0);
-    constexpr bool kWave0Inserts = CHAIN && kNinthExit;
-    if (kNinthExit && !matcher) __builtin_amdgcn_endpgm(); /* (after the start-up's barrier: the wave has cleared and prefilled its share) */
+    /* A deferring kernel's ninth wave has nothing to do in the tile loop: it ENDS before the loop (s_endpgm: a barrier only waits for the waves that
+     * are left — ISA, S_BARRIER) instead of keeping the barriers' count; the eight matcher waves parse and emit after the loop, wave 0 closes the block.
+     * Level 1 10.82 -> 9.63 ms per GiB (-11 %), level 2 14.9 -> 12.8, 32 KiB blocks 12.2 -> 10.5, level 3 (one workgroup per CU) unchanged: with two
+     * workgroups per CU the idle wave was the 17th and 18th of the CU (profiles/r06_ab_deferred_parse.txt).  At the chain levels the gain is the same
+     * wave's end (level 6 75.2 -> 66.8 ms per GiB, level 12 186.0 -> 169.6): with the ninth wave alive the deferred parse was slower there. */
+    if (DEFER && !matcher) __builtin_amdgcn_endpgm(); /* (after the start-up's barrier: the wave has cleared and prefilled its share) */
     if (!matcher) {
-        /* ---------------- the parse wave: its own scalar loop, same barrier cadence ---------------- */
-#ifndef QZ_PARSE_PRIO
-#define QZ_PARSE_PRIO 3 /* the priority of the DECOUPLED parse wave (A/B builds); the lock-step one is the serial critical path: 3 */
-#endif
-        if (!QZ_ABLATED(32u)) __builtin_amdgcn_s_setprio(kDecoupled ? QZ_PARSE_PRIO : 3); /* win issue arbitration on its SIMD */
+        /* ---------------- the parse wave (DEFER = false): its own scalar loop, same barrier cadence ---------------- */
+        if (!QZ_ABLATED(32u)) __builtin_amdgcn_s_setprio(3); /* the serial critical path: win issue arbitration on its SIMD */
 #ifndef QZ_PARSE_SPLIT
 #define QZ_PARSE_SPLIT 3 /* windows parsed in interval 1 (the short one), the rest in interval 2 (A/B builds) */
 #endif
@@ -1496,96 +1399,25 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
 #define QZ_PLAP(acc)
 #endif
         uint32_t nseqEnd, anchorEnd;
-        if constexpr (kDecoupled) {
-            /* Levels 1-4 (round 6): THE DECOUPLED PARSE WAVE.  Rounds 1-5 ran the parse wave in lock-step with the matchers — windows 0-2 of tile
-             * it-1 in interval 1, windows 3-7 in interval 2 — so every interval took max(slowest matcher wave, the parse wave's serial chain) and the
-             * round-5 measurements named exactly that as what a tile waits for.  s_barrier knows no "arrive without waiting" on gfx950, so the parse
-             * wave has to execute every barrier of the matchers' loop — but WHEN is its own business as long as
-             *   (a) it parses tile k only after B2 of iteration k (the tile's parse words are complete),
-             *   (b) it lets B2 of iteration j go only once tile j + 1 - kLagT is parsed (iteration j + 1 emits that tile and, in its second
-             *       interval, overwrites the parse words of tile j + 1 - kLagT's ring slot).
-             * Between those bounds it works through the tiles window by window and, after every window, looks at a counter the matcher waves bump
-             * before each of their barriers: when all eight are waiting and (b) allows, it joins the barrier at once (a hint, not a
-             * synchronisation: a stale value only costs time).  With nothing to parse it simply waits at the next barrier.  The matchers thus
-             * wait for the parse only when it is kLagT - 1 tiles behind, not twice per tile. */
-            ParseState st = { blk.parseFrom, blk.parseFrom, 0u };
-            uint32_t bar = 0u; /* barriers of the matchers' loop executed so far: B1 of iteration j = 2 (j - itBegin), B2 = that + 1 */
-            const uint32_t nBar = 2u * (nTiles + kLagT - itBegin);
-            const uint32_t *arriveP = turnCtr + kCtlArrive;
-#ifdef QZ_DEBUG_DUMP
-            u64 pYield = 0, pHeld = 0;
-#endif
-            for (uint32_t k = itBegin; k < nTiles && !QZ_ABLATED(1u); k++) {
-                QZ_PLAP(pI1)
-                /* (a): the tile's parse words are complete after B2 of its own iteration — after B1 of the next one when the flags are written there (kShift).
-                 * Ahead of the matchers there is nothing to do but wait with them */
-                while (bar < (kShift ? 2u * (k + 1u - itBegin) + 1u : 2u * (k - itBegin) + 2u)) { QZ_BARRIER_LDS(); bar++; }
-                QZ_PLAP(pW1)
-                const uint32_t *pvT = pv + (k % kLagT) * kPvStride;
-                uint32_t word[kWin];
-#pragma unroll
-                for (uint32_t w = 0; w < kWin; w++) word[w] = pvT[64u * w + lane];
-#pragma unroll
-                for (uint32_t w = 0; w < kWin; w++) asm volatile("" : "+v"(word[w])); /* all eight requested here: ONE LDS wait per tile */
-                ParseRecs r = { 0u, 0u, 0u, 0u, 0u, 0u };
-                const uint32_t base = k << kTileLog;
-                auto yield = [&](uint32_t seenV) {
-                    const uint32_t seen = rdfirst(seenV);
-                    if (seen >= (uint32_t)kMatchWaves * (bar + 1u)) { /* every matcher wave is waiting at barrier `bar` */
-                        if (!(bar & 1u) || k + kLagT >= itBegin + (bar >> 1) + 2u) { QZ_BARRIER_LDS(); bar++;
-#ifdef QZ_DEBUG_DUMP
-                            pYield++;
-#endif
-                        }
-#ifdef QZ_DEBUG_DUMP
-                        else pHeld++;
-#endif
-                    }
-                };
-#ifndef QZ_HINT_EVERY
-#define QZ_HINT_EVERY 1 /* windows between two looks at the matchers' counter (A/B builds) */
-#endif
-#define QZ_PW(W) { if (((W) + 1u) % QZ_HINT_EVERY == 0u) { \
-                       const uint32_t seenV = __hip_atomic_load(arriveP, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); \
-                       parse_window<W>(pf, src, word[W], base, n, lane, st, r); yield(seenV); \
-                   } else parse_window<W>(pf, src, word[W], base, n, lane, st, r); }
-                QZ_PW(0) QZ_PW(1) QZ_PW(2) QZ_PW(3) QZ_PW(4) QZ_PW(5) QZ_PW(6)
-                parse_window<7>(pf, src, word[7], base, n, lane, st, r); /* (the records first, then the barrier — next iteration's loop head, or below) */
-#undef QZ_PW
-                if (lane < kWin) {
-                    uint32_t *so = srec + ((k % kLagT) * kWin + lane) * kSrecWords;
-                    *reinterpret_cast<uint4 *>(so) = make_uint4(r.r0, r.r1, r.r2, r.r3);
-                    so[4] = r.r4;
-                    so[5] = r.r5;
-                }
-            }
-            QZ_PLAP(pI1)
-            while (bar < nBar) { QZ_BARRIER_LDS(); bar++; }
-            QZ_PLAP(pW1)
-#ifdef QZ_DEBUG_DUMP
-            pI2 = pYield; pW2 = pHeld;
-#endif
-            nseqEnd = st.nseq;
-            anchorEnd = st.anchor;
-        } else if (REP) {
+        if (REP) {
             RepState st = { blk.parseFrom, blk.parseFrom, 0u, 0u, 0u, 0u, pf.segLog ? blk.parseFrom >> pf.segLog : 0u };
             for (uint32_t it = itBegin; it < itEnd; it++) {
                 const bool work = it >= 1u && it - 1u < nTiles && it - 1u >= firstTile && !QZ_ABLATED(1u);
                 const uint32_t k = it - 1u, base = k << kTileLog;
                 uint32_t *pvT = pv + (k % kLagT) * kPvStride, *srecT = srec + (k % kLagT) * kWin * kSrecWords;
-                if (work && !DEFER) {
+                if (work) {
                     st.tileSeq = st.nseq;
                     if (lane == 0u) srecT[0] = st.nseq; /* the records carry indices relative to this */
-                    if (!(CHAIN && QZ_CHAIN_SHIFT)) parse_rep_span<false>(pf, src, pvT, base, base + 64u * kSplit, n, nh, lane, st);
+                    if (!CHAIN) parse_rep_span<false>(pf, src, pvT, base, base + 64u * kSplit, n, nh, lane, st);
                 }
                 if (CHAIN && it == itBegin && it < nTiles) chain_insert_tile(pf, src, tbl, (it & 1u) ? P1odd : nearTab, it << kTileLog, n, nh, lane, args.orderedLds != 0u);
                 QZ_PLAP(pI1)
                 __syncthreads(); /* B1 */
                 QZ_PLAP(pW1)
-                if (work && !DEFER) parse_rep_span<false>(pf, src, pvT, base, base + kTile, n, nh, lane, st);
+                if (work) parse_rep_span<false>(pf, src, pvT, base, base + kTile, n, nh, lane, st);
                 if (CHAIN && it + 1u < nTiles) chain_insert_tile(pf, src, tbl, ((it + 1u) & 1u) ? P1odd : nearTab, (it + 1u) << kTileLog, n, nh, lane, args.orderedLds != 0u);
                 QZ_PLAP(pI2)
-                if (DEFER && !CHAIN) QZ_BARRIER_LDS(); else __syncthreads(); /* B2 */
+                __syncthreads(); /* B2 */
                 QZ_PLAP(pW2)
             }
             nseqEnd = st.nseq;
@@ -1595,58 +1427,15 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             for (uint32_t it = itBegin; it < itEnd; it++) {
                 const bool work = it >= 1u && it - 1u < nTiles && it - 1u >= firstTile && !QZ_ABLATED(1u);
                 const uint32_t k = it - 1u;
-                if (work && !DEFER && !(CHAIN && QZ_CHAIN_SHIFT))
+                if (work && !CHAIN)
                     parse_tile<0, kSplit>(pf, src, pv + (k % kLagT) * kPvStride, srec + (k % kLagT) * kWin * kSrecWords,
                                           k << kTileLog, n, lane, st);
                 if (CHAIN && it == itBegin && it < nTiles) chain_insert_tile(pf, src, tbl, (it & 1u) ? P1odd : nearTab, it << kTileLog, n, nh, lane, args.orderedLds != 0u);
                 QZ_PLAP(pI1)
                 __syncthreads(); /* B1 */
                 QZ_PLAP(pW1)
-                if constexpr (DEFER && !REP && !CHAIN && QZ_DEFER_INLOOP != 0) {
-                    /* B1 was a full barrier: the words the matchers stored in iterations < it are complete */
-                    const uint32_t nSegsP = (nh + 4095u) >> 12;
-                    if (nwSeg < nSegsP && (nwBase >> kTileLog) + 1u <= it) {
-                        const uint32_t tEnd = umin((nwSeg << 12) + 4096u, nTiles << kTileLog);
-                        u64 *recG = reinterpret_cast<u64 *>(p1B + (nwSeg << 12));
-                        const uint32_t lastDw = (nPad >> 2) - 1u;
-                        if (nwQ == 0u) { /* a new tile: its words (requested a tile ago if they were complete then), and the next tile's */
-                            if (nwHave) {
-#pragma unroll
-                                for (uint32_t j = 0; j < kWin; j++) nwWds[j] = nwNxt[j];
-                            } else {
-#pragma unroll
-                                for (uint32_t j = 0; j < kWin; j++) nwWds[j] = p1B[nwBase + 64u * j + lane];
-                            }
-                            nwBegun = true;
-                            const bool more = nwBase + kTile < tEnd || nwSeg + 1u < nSegsP;
-                            const uint32_t nb = nwBase + kTile < tEnd ? nwBase + kTile : (nwSeg + 1u) << 12;
-                            nwHave = more && (nb >> kTileLog) + 1u <= it;
-                            if (nwHave) {
-#pragma unroll
-                                for (uint32_t j = 0; j < kWin; j++) nwNxt[j] = p1B[nb + 64u * j + lane];
-                            }
-                        }
-                        switch (nwQ) {
-                        case 0u: parse_plain_windows<0, 2>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt); break;
-                        case 1u: parse_plain_windows<2, 4>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt); break;
-                        case 2u: parse_plain_windows<4, 6>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt); break;
-                        default: parse_plain_windows<6, 8>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt); break;
-                        }
-                        nwQ = (nwQ + 1u) & 3u;
-                        if (nwQ == 0u) {
-                            nwBase += kTile;
-                            if (nwBase >= tEnd) { /* the segment is done: its count and its last match end (LDS: srec, as the parse after the loop leaves them) */
-                                if (lane == 0u) { srec[nwSeg] = nwSt.cnt; srec[32u + nwSeg] = nwSt.endA; }
-                                nwSeg++;
-                                nwBase = nwSeg << 12;
-                                nwSt = PlainParse{ nwBase, 0u, 0xFFFFFFFFu };
-                                nwBegun = false;
-                            }
-                        }
-                    }
-                }
-                if (work && !DEFER) {
-                    if (CHAIN && QZ_CHAIN_SHIFT)
+                if (work) {
+                    if (CHAIN) /* the whole tile: its flags were written in interval 1 of this iteration */
                         parse_tile<0, kWin>(pf, src, pv + (k % kLagT) * kPvStride, srec + (k % kLagT) * kWin * kSrecWords, k << kTileLog, n, lane, st);
                     else
                         parse_tile<kSplit, kWin>(pf, src, pv + (k % kLagT) * kPvStride, srec + (k % kLagT) * kWin * kSrecWords,
@@ -1654,7 +1443,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 }
                 if (CHAIN && it + 1u < nTiles) chain_insert_tile(pf, src, tbl, ((it + 1u) & 1u) ? P1odd : nearTab, (it + 1u) << kTileLog, n, nh, lane, args.orderedLds != 0u);
                 QZ_PLAP(pI2)
-                if (DEFER && !CHAIN) QZ_BARRIER_LDS(); else __syncthreads(); /* B2 */
+                __syncthreads(); /* B2 */
                 QZ_PLAP(pW2)
             }
             nseqEnd = st.nseq;
@@ -1664,21 +1453,15 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         if (lane == 0 && !(blk.mark & QZSTD_HIP_MARK_COMPACT)) out[blk.seqCap - 2u] = make_uint4((uint32_t)pI1, (uint32_t)pW1, (uint32_t)pI2, (uint32_t)pW2);
         if (lane == 0 && !(blk.mark & QZSTD_HIP_MARK_COMPACT)) out[blk.seqCap - 12u - wave] = make_uint4(__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)), 0u, 0u, 0u); /* HW_ID: where the wave runs */
 #endif
-        if constexpr (!DEFER) {
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = nseqEnd + 1u;
         if (lane == 0 && nseqEnd < blk.seqCap) store_entry(out, nseqEnd, 0u, n - anchorEnd, 0u, blk.mark);
         if (count >= blk.seqCap - 1u) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318 */
         return count;
-        }
     }
 
     if (matcher) {
     /* ---------------- the 8 matcher waves ---------------- */
-#ifdef QZ_MATCH_PRIO_HI /* A/B: the issue arbiter prefers the OLDER waves of a SIMD — waves 4-7 of a workgroup reach every barrier last (r06_level1_wave_timing_before.txt);
-                         * a raised priority for them evens that out */
-    if (wave >= 4u) __builtin_amdgcn_s_setprio(QZ_MATCH_PRIO_HI);
-#endif
     /* Chain entries: of the positions before the item (its history) in chainB; of the item's own positions in ownB — the same array
      * on the launch paths, an array of its own where the items of a request share chainB (HistShare): there the entries of an
      * item's range are stored by the item AFTER it, written through, and nobody else may leave half-written lines of them in an
@@ -1712,7 +1495,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
 #endif
 
     /* Start flags and parse words of one tile from every position's candidate (cl = capped length, off = offset).  Below the chain levels this
-     * runs at the end of the tile's own interval 2.  At the chain levels (QZ_CHAIN_SHIFT, round 4) it runs in interval 1 of the NEXT iteration, and
+     * runs at the end of the tile's own interval 2.  At the chain levels (round 4) it runs in interval 1 of the NEXT iteration, and
      * the parse wave — which has next to nothing to do there — parses the whole tile in that iteration's interval 2: the tile's last words no
      * longer sit between the walk and the barrier. */
     auto write_flags = [&](uint32_t tileIdx, uint32_t cl, uint32_t off) {
@@ -1765,13 +1548,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             if (DEFER) p1B[(tileIdx << kTileLog) + tid] = gRep | (off << 10);
             else pv[(tileIdx % kLagT) * kPvStride + tid] = REP ? (gRep | (off << 10)) : pack_pos(nx, ns, capped ? off : cl);
     };
-    /* kShift: what interval 2 of an iteration leaves for interval 1 of the next — the candidates' offsets and head lengths (0 = none), which of
-     * them matched all 16 bytes of the head and go on ("need"), the cap, and the 36 bytes behind the position's head (dwords 4-12 of `own`) */
-    uint32_t cOff1 = 0, cOff2 = 0, cOff3 = 0, cL1 = 0, cL2 = 0, cL3 = 0, cCap = 0;
-    bool cNeed1 = false, cNeed2 = false, cNeed3 = false, cFlags = false;
-    uint32_t cP[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) cP[i] = 0u;
     for (uint32_t it = itBegin; it < itEnd; it++) {
         const uint32_t t0 = it << kTileLog;
         const uint32_t p = t0 + tid; /* own position in tile it */
@@ -1784,34 +1560,12 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
 
         /* ================= interval 1 ================= */
         QZ_PRIO(2);
-        if (kWave0Inserts && wave == 0u && it == itBegin && it < nTiles) /* (the ninth wave's job where it is alive) */
+        if (CHAIN && DEFER && wave == 0u && it == itBegin && it < nTiles) /* (the ninth wave's job in the service's items) */
             chain_insert_tile(pf, src, tbl, (it & 1u) ? P1odd : nearTab, it << kTileLog, n, nh, lane, args.orderedLds != 0u);
         /* the position's own first 20 bytes (5 aligned dwords): issued first so that their LDS latency
          * hides behind the emission below; used by the hash now and by the candidate compare later */
-#ifndef QZ_SHIFT_CARRY_P
-#define QZ_SHIFT_CARRY_P 0 /* A/B: 1 = the position's own side of its tails is requested WITH its head (13 dwords instead of 5) and carried in registers to the next
-                            * iteration (no request there; 88 VGPRs: the second workgroup no longer fits next to the first on every SIMD); 0 = requested again
-                            * with the candidates' tails */
-#endif
-        constexpr bool kCarryP = kShift && QZ_SHIFT_CARRY_P != 0;
-        constexpr int kOwn = kCarryP ? 13 : 5;
-        uint32_t own[kOwn];
-        load_dw_r<kOwn>(src, p, rp, false, own);
-        /* kShift: the tails of tile it-1 — the 32 bytes behind the head of every candidate that matched its whole head — requested NOW, together with
-         * the own bytes of tile it: one round trip for both (the candidates' ring offsets follow from the carried offsets) */
-        uint32_t TQ1[9], TQ2[9], TQ3[9], TP[9];
-        if constexpr (kShift) {
-#pragma unroll
-            for (int i = 0; i < 9; i++) asm volatile("" : "=v"(TQ1[i]), "=v"(TQ2[i]), "=v"(TQ3[i]), "=v"(TP[i])); /* only the requesting lanes ever read them: "written" without an instruction */
-            const uint32_t rpP16 = ring_back(rp, kTile - 16u); /* ring offset of (the position in tile it-1) + 16 */
-            if constexpr (kCarryP) {
-#pragma unroll
-                for (int i = 0; i < 9; i++) TP[i] = cP[i];
-            } else if (cNeed1 || cNeed2 || (HAS_LONG && cNeed3)) load_dw_r<9>(src, p - kTile + 16u, rpP16, false, TP);
-            if (cNeed1) load_dw_r<9>(src, p - kTile + 16u - cOff1, ring_back(rpP16, cOff1), cOff1 > src.nearLimit, TQ1);
-            if (HAS_LONG && cNeed3) load_dw_r<9>(src, p - kTile + 16u - cOff3, ring_back(rpP16, cOff3), cOff3 > src.nearLimit, TQ3);
-            if (cNeed2) load_dw_r<9>(src, p - kTile + 16u - cOff2, ring_back(rpP16, cOff2), false, TQ2);
-        }
+        uint32_t own[5];
+        load_dw_r<5>(src, p, rp, false, own);
         /* refill: the 512 bytes that enter the look-ahead window this iteration (HBM -> registers now,
          * registers -> ring after the barrier; the ring slots they replace left everyone's reach
          * three tiles ago) */
@@ -1821,9 +1575,9 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         const uint32_t fpos = t0 + kLook + (tid - 64u) * 16u; /* iteration it stages [t0 + kLook, t0 + kLook + kTile) */
         const bool refill = wave == 1u && it >= 1u && lane < kTile / 16u && fpos < nPad;
         if (refill) fresh = g128[fpos >> 4];
-        if (!DEFER && it >= kLagT + firstTile && !QZ_ABLATED(8u)) /* emit(it - kLagT): needs the parse of that tile (lock-step: done in interval 2 of it-1; decoupled: before the parse wave let B2 of it-1 go) */
+        if (!DEFER && it >= kLagT + firstTile && !QZ_ABLATED(8u)) /* emit(it - kLagT): needs the parse of that tile, done in interval 2 of it-1 */
             emit_window<REP>(pf, src, srec + ((it % kLagT) * kWin + wave) * kSrecWords, pv + (it % kLagT) * kPvStride + 64u * wave,
-                             offH[kEmitIdx], lenH[kEmitIdx], t0 - kLagT * kTile + 64u * wave, ring_back(rp, kLagT * kTile), lane, out, blk.seqCap,
+                             offH[kLagT - 1u], lenH[kLagT - 1u], t0 - kLagT * kTile + 64u * wave, ring_back(rp, kLagT * kTile), lane, out, blk.seqCap,
                              REP ? srec[(it % kLagT) * kWin * kSrecWords] : 0u, blk.mark);
         QZ_PRIO(1); /* (interval 1: the emission is behind) */
         uint32_t slot = 0, nslot = 0, slotL = 0, oldL = 0, tagL = 0;
@@ -1849,30 +1603,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 if (!TURNS) oldL = tblL[slotL];
             }
         }
-        if constexpr (kShift) {
-            /* tile it-1: lengths beyond the head, the choice between the candidates, start flags, parse words — while the table read of tile it is in flight */
-            uint32_t clP = 0u, offP = 0u;
-            if (cFlags) { /* uniform */
-                uint32_t l1 = cL1, l2 = cL2, l3 = cL3;
-                if (cNeed1 || cNeed2 || cNeed3) {
-                    uint32_t pa[8];
-#pragma unroll
-                    for (int i = 0; i < 8; i++) pa[i] = __builtin_amdgcn_alignbyte(TP[i + 1], TP[i], p & 3u); /* (tile it-1's position has the same alignment) */
-                    if (cNeed1) l1 = 16u + tail_cmp(pa, TQ1, (p - cOff1) & 3u);
-                    if (HAS_LONG && cNeed3) l3 = 16u + tail_cmp(pa, TQ3, (p - cOff3) & 3u);
-                    if (cNeed2) l2 = 16u + tail_cmp(pa, TQ2, (p - cOff2) & 3u);
-                }
-                l1 = umin(l1, cCap); l2 = umin(l2, cCap); l3 = umin(l3, cCap);
-                if (l1 >= 4u) { clP = l1; offP = cOff1; }
-                if (l3 >= 4u && l3 > clP) { clP = l3; offP = cOff3; }   /* 8-byte table: only if strictly longer */
-                if (l2 >= 4u && l2 >= clP) { clP = l2; offP = cOff2; }  /* same tile: ties go to the nearer source */
-                if (!QZ_ABLATED(4u)) write_flags(it - 1u, clP, offP);
-            }
-#pragma unroll
-            for (uint32_t i = kLagT - 1u; i > 0u; i--) { offH[i] = offH[i - 1u]; lenH[i] = lenH[i - 1u]; }
-            offH[0] = offP;
-            lenH[0] = clP;
-        }
         uint32_t pre[kEL];
 #pragma unroll
         for (uint32_t j = 0; j < kEL; j++) pre[j] = 0u;
@@ -1882,57 +1612,21 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             old = valid ? ((it & 1u) ? P1odd : nearTab)[tid] : 0u;
             if (old != 0u && (old >> kTagBits) - 1u < t0) entryOf((old >> kTagBits) - 1u, pre);
         }
-        if (CHAIN && QZ_CHAIN_SHIFT && it > itBegin && it - 1u < nTiles && it - 1u >= firstTile && !QZ_ABLATED(4u)) write_flags(it - 1u, lenH[0], offH[0]);
-        if (kDecoupled && lane == 0u) (void)__hip_atomic_fetch_add(turnCtr + kCtlArrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); /* "at B1": the parse wave's hint */
+        if (CHAIN && it > itBegin && it - 1u < nTiles && it - 1u >= firstTile && !QZ_ABLATED(4u)) write_flags(it - 1u, lenH[0], offH[0]);
         QZ_LAP(dI1)
-#ifdef QZ_B1_LDS_ONLY /* A/B: the barrier between the intervals orders LDS traffic only — nothing in global memory crosses it (the chain entries of the
-                       * previous tile were drained at B2, the refill's load and the predecessor's entry are waited for where they are used) */
-        QZ_BARRIER_LDS(); /* B1 */
-#else
         __syncthreads(); /* B1 */
-#endif
         QZ_LAP(dW1)
 
         /* ================= interval 2 ================= */
         QZ_PRIO(2);
-        if (kWave0Inserts && wave == 0u && it + 1u < nTiles)
+        if (CHAIN && DEFER && wave == 0u && it + 1u < nTiles)
             chain_insert_tile(pf, src, tbl, ((it + 1u) & 1u) ? P1odd : nearTab, (it + 1u) << kTileLog, n, nh, lane, args.orderedLds != 0u);
-#if defined(QZ_PAD_VALU) || defined(QZ_PAD_SALU) || defined(QZ_PAD_LDS)
-        /* calibration builds only (make variant XFLAGS=-DQZ_PAD_VALU=64 ...): what ONE more instruction of a kind costs per matcher wave
-         * and tile — the slope says which issue resource binds the kernel */
-        {
-            uint32_t padv = lane, pads = 1u;
-#ifdef QZ_PAD_VALU
-#pragma unroll
-            for (int i = 0; i < QZ_PAD_VALU; i++) asm volatile("v_add_u32 %0, %0, %1" : "+v"(padv) : "v"(lane));
-#endif
-#ifdef QZ_PAD_SALU
-#pragma unroll
-            for (int i = 0; i < QZ_PAD_SALU; i++) asm volatile("s_add_u32 %0, %0, 1" : "+s"(pads) : : "scc");
-#endif
-#ifdef QZ_PAD_LDS
-#pragma unroll
-            for (int i = 0; i < QZ_PAD_LDS; i++) { uint32_t t; asm volatile("ds_read_b32 %0, %1" : "=v"(t) : "v"((rp & ~3u) + 16u)); padv ^= t; }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
-            if (padv == 0xDEADBEEFu && pads == 0u) pv[0] = padv; /* keeps the chain alive; never true in practice */
-        }
-#endif
         if (refill) {
             const uint32_t o = ring_dw(fpos) << 2;
             ring128[o >> 4] = fresh;
             if (o < kMirror) ring128[(kRing + o) >> 4] = fresh;
         }
         uint32_t cl = 0, off = 0; /* capped candidate length, offset */
-        if constexpr (kShift) { /* what this interval leaves for interval 1 of the next iteration (set below where the position has candidates) */
-            cOff1 = cOff2 = cOff3 = cL1 = cL2 = cL3 = cCap = 0u;
-            cNeed1 = cNeed2 = cNeed3 = false;
-            cFlags = it < nTiles && !history;
-            if constexpr (kCarryP) {
-#pragma unroll
-                for (int i = 0; i < 9; i++) cP[i] = own[kOwn - 9 + i];
-            }
-        }
         if (CHAIN) {
             /* Levels >= 5: exact hash chains (oracle: qzo_candidates_chain): every position gets its exact predecessor in
              * its slot, and walks chainDepth links from there.
@@ -1975,28 +1669,9 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             const uint32_t cap = valid ? umin(umin(pf.capLen, 48u), segE - p) : 0u; /* a match never leaves its segment; candidates are measured up to 48 bytes */
             uint32_t walked = 0;
             if (history) E[0] = 0u; /* a tile before the segment (segment mode): inserted and linked, not matched */
-#if QZ_CHAIN_DEFER_EXT && QZ_CHAIN_HOIST_P
-            uint32_t pa[8];
-            {
-                uint32_t P[9];
-                load_dw_r<9>(src, p + 16u, ring_fwd(rp, 16u), false, P);
-#pragma unroll
-                for (int i = 0; i < 8; i++) pa[i] = __builtin_amdgcn_alignbyte(P[i + 1], P[i], p & 3u);
-            }
-#endif
             int bg = 0;
             QZ_CLAP(0)
-#ifndef QZ_CHAIN_PROGRESS_PRIO
-#define QZ_CHAIN_PROGRESS_PRIO 0 /* A/B: the walking waves' priority falls with the steps they have done (2 for the first two, 1 for the next two, then 0) */
-#endif
-            uint32_t stepsDone = 0u;
-            if (QZ_CHAIN_PROGRESS_PRIO) __builtin_amdgcn_s_setprio(2);
             while (__ballot(E[0] != 0u)) {
-                if (QZ_CHAIN_PROGRESS_PRIO) {
-                    if (stepsDone == 2u * QZ_CHAIN_PROGRESS_PRIO) __builtin_amdgcn_s_setprio(1);
-                    else if (stepsDone == 4u * QZ_CHAIN_PROGRESS_PRIO) __builtin_amdgcn_s_setprio(0);
-                    stepsDone++;
-                }
                 uint32_t N[kEL];
 #pragma unroll
                 for (uint32_t j = 0; j < kEL; j++) N[j] = 0u;
@@ -2046,16 +1721,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                         bool any = false;
 #pragma unroll
                         for (int g = 0; g < kG; g++) any = any || m[g];
-#ifdef QZ_HEADS_WITH_TESTS /* A/B: the candidates' 16-byte heads requested TOGETHER with the four-byte tests (one LDS round trip instead of two per step;
-                            * the heads of candidates that fail the test are fetched for nothing) */
-                        uint32_t Q[kG][5];
-#pragma unroll
-                        for (int g = 0; g < kG; g++) {
-#pragma unroll
-                            for (int i = 0; i < 5; i++) Q[g][i] = 0u;
-                            if (m[g] && cl < cap) load_dw_r<5>(src, q[g], rq[g], far[g], Q[g]);
-                        }
-#endif
                         if (any && cl != 0u) {
                             /* links come nearest first, so a later one can only win with MORE matching bytes than the best so
                              * far (its offset costs at least as much): it has to match at byte cl, in particular.  Four bytes
@@ -2073,7 +1738,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                             for (int g = 0; g < kG; g++) m[g] = m[g] && v[g] == pw;
                         }
                         QZ_CLAP(2)
-#ifndef QZ_HEADS_WITH_TESTS
                         uint32_t Q[kG][5];
 #pragma unroll
                         for (int g = 0; g < kG; g++) {
@@ -2081,52 +1745,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                             for (int i = 0; i < 5; i++) Q[g][i] = 0u;
                             if (m[g]) load_dw_r<5>(src, q[g], rq[g], far[g], Q[g]);
                         }
-#endif
-#if QZ_CHAIN_DEFER_EXT
-                        /* Round 6.  A link's LENGTH depends on nothing but (p, q): only the choice between the links is sequential.  So the step first
-                         * measures the 16-byte heads of all its surviving links, then extends the heads that matched whole — in a loop in which every
-                         * lane takes ITS next such link: as many passes as the busiest lane has (one or two) instead of one 60-instruction block per
-                         * link position that runs whenever ANY lane of the wave needs it (four per step, practically always) —, then chooses in link
-                         * order exactly as before.  A wave's time is its instruction count (profiles/r06_ab_decoupled_parse_wave.txt). */
-                        uint32_t lg[kG], needX = 0u;
-#pragma unroll
-                        for (int g = 0; g < kG; g++) {
-                            lg[g] = 0u;
-                            if (m[g] && cl < cap) {
-                                lg[g] = head_cmp(oa, Q[g], q[g] & 3u);
-                                if (lg[g] == 16u && cap > 16u) needX |= 1u << g;
-                            }
-                        }
-                        if (__ballot(needX != 0u)) {
-#if !QZ_CHAIN_HOIST_P
-                            /* the position's own 32 bytes behind the head: requested and byte-aligned once per step (they were per link) */
-                            uint32_t P[9], pa[8];
-                            load_dw_r<9>(src, p + 16u, ring_fwd(rp, 16u), false, P);
-#pragma unroll
-                            for (int i = 0; i < 8; i++) pa[i] = __builtin_amdgcn_alignbyte(P[i + 1], P[i], p & 3u);
-#endif
-                            do {
-                                if (needX != 0u) {
-                                    const uint32_t gx = first_diff_bit(needX); /* this lane's next link to extend */
-                                    needX &= needX - 1u;
-                                    uint32_t qx = q[0];
-#pragma unroll
-                                    for (int g = 1; g < kG; g++) qx = gx == (uint32_t)g ? q[g] : qx;
-                                    const uint32_t t = tail_len(src, pa, qx + 16u, ring_back(ring_fwd(rp, 16u), p - qx), p - qx > src.nearLimit);
-#pragma unroll
-                                    for (int g = 0; g < kG; g++) lg[g] = gx == (uint32_t)g ? 16u + t : lg[g];
-                                }
-                            } while (__ballot(needX != 0u));
-                        }
-#pragma unroll
-                        for (int g = 0; g < kG; g++) {
-                            if (m[g] && cl < cap) { /* (a best that fills the cap cannot be beaten: the sequential walk would not have looked) */
-                                const uint32_t l = umin(lg[g], cap);
-                                const int gn = (int)(4u * l) - (int)(31u - (uint32_t)__builtin_clz(p - q[g] + 1u));
-                                if (l >= 4u && (cl == 0u || gn > bg)) { cl = l; off = p - q[g]; bg = gn; }
-                            }
-                        }
-#else
 #pragma unroll
                         for (int g = 0; g < kG; g++) {
                             if (m[g] && cl < cap) { /* (a best that fills the cap cannot be beaten: the sequential walk would not have looked) */
@@ -2137,7 +1755,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                                 if (l >= 4u && (cl == 0u || gn > bg)) { cl = l; off = p - q[g]; bg = gn; }
                             }
                         }
-#endif
                     }
                     walked += cnt;
                 }
@@ -2153,7 +1770,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 for (uint32_t j = 0; j < kEL; j++) E[j] = full ? 0u : N[j];
                 QZ_CLAP(4)
             }
-            if (QZ_CHAIN_PROGRESS_PRIO) __builtin_amdgcn_s_setprio(0);
         } else {
         if (TURNS) {
             /* level 2 and levels >= 5 update the tables per 64 positions, in position order: the matcher waves take turns
@@ -2207,13 +1823,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
              * cap of 48) shares the position's own side — fetched and byte-aligned once — between the candidates */
             bool need1 = l1 == 16u && cap > 16u, need2 = l2 == 16u && cap > 16u, need3 = HAS_LONG && l3 == 16u && cap > 16u;
             if (QZ_ABLATED(128u)) need1 = need2 = need3 = false; /* profiling: what the extension past 16 bytes costs */
-            if (kShift) { /* the rest of this tile's lengths in interval 1 of the next iteration */
-                cOff1 = q1 != kNone ? p - q1 : 0u; cOff2 = q2 != kNone ? p - q2 : 0u; cOff3 = q3 != kNone ? p - q3 : 0u;
-                cL1 = l1; cL2 = l2; cL3 = l3;
-                cNeed1 = need1; cNeed2 = need2; cNeed3 = need3;
-                cCap = cap;
-                need1 = need2 = need3 = false;
-            }
             QZ_PRIO(1); /* (the heads are behind) */
             if (need1 || need2 || need3) {
                 const uint32_t rp16 = ring_fwd(rp, 16u);
@@ -2236,32 +1845,22 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 else { l2 = L + l; need2 = more; }
             }
             QZ_PRIO(0); /* (the tails are behind) */
-            if (!kShift) {
             l1 = umin(l1, cap); l2 = umin(l2, cap); l3 = umin(l3, cap);
             if (l1 >= 4u) { cl = l1; off = p - q1; }
             if (l3 >= 4u && l3 > cl) { cl = l3; off = p - q3; }   /* 8-byte table: only if strictly longer */
             if (l2 >= 4u && l2 >= cl) { cl = l2; off = p - q2; }  /* same tile: ties go to the nearer source */
             }
-            }
         }
         }
-        if (!kShift) {
-        if (!(CHAIN && QZ_CHAIN_SHIFT) && it < nTiles && !history && !QZ_ABLATED(4u)) write_flags(it, cl, off);
+        if (!CHAIN && it < nTiles && !history && !QZ_ABLATED(4u)) write_flags(it, cl, off);
 #pragma unroll
         for (uint32_t i = kLagT - 1u; i > 0u; i--) { offH[i] = offH[i - 1u]; lenH[i] = lenH[i - 1u]; }
         offH[0] = off;
         lenH[0] = cl;
-        }
         rp = ring_fwd(rp, kTile);
-        if (kDecoupled && lane == 0u) (void)__hip_atomic_fetch_add(turnCtr + kCtlArrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); /* "at B2" */
         QZ_LAP(dI2)
-#ifdef QZ_B2_LDS_ONLY /* A/B: below the chain levels no wave reads what another wave wrote to global memory — the barrier need not wait for the result stores
-                       * (to PINNED HOST memory in the product paths) either; the chain levels keep the full barrier: chain entries */
-        if (CHAIN) __syncthreads(); else QZ_BARRIER_LDS(); /* B2 */
-#else
         /* (DEFER below the chain levels: the parse words just stored are read after the loop — the barrier need not wait for them) */
         if (DEFER && !CHAIN) QZ_BARRIER_LDS(); else __syncthreads(); /* B2 */
-#endif
         QZ_LAP(dW2)
     }
 #ifdef QZ_DEBUG_DUMP
@@ -2285,7 +1884,9 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
 #ifdef QZ_DEBUG_DUMP
         const u64 tD0 = __builtin_amdgcn_s_memtime();
 #endif
-        if ((kNinthExit ? wave == 0u : !matcher) && lane == 0u) segCnt[2u * kMaxSegs] = nwSeg + (nwBegun ? 1u : 0u); /* the first segment nobody has begun (the ninth wave's own progress) */
+        /* the first segment to parse reaches the waves through LDS: computed in registers instead, it changes the level-1 kernel's register
+         * allocation throughout, measured +0.3 % kernel time */
+        if (wave == 0u && lane == 0u) segCnt[2u * kMaxSegs] = firstSeg;
         __syncthreads(); /* every wave's parse words are stored (the loop's last barriers may have ordered LDS only) */
 #ifdef QZ_DEBUG_DUMP
         const u64 tD1 = __builtin_amdgcn_s_memtime();
@@ -2298,8 +1899,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         /* (measured and not kept, bit-exact both: the segments handed out dynamically to all nine waves — commit d4651d4: level 1 the same, short blocks
          * +2 %; the words of the starts only + the windows' start masks — commit 72302cb: traffic -18 %, time +7 %) */
         {
-            /* which segments are left: the ninth wave has parsed segments [firstSeg, nwSeg) during the tile loop and may stand inside segment nwSeg,
-             * which it finishes itself.  S0 = the first segment nobody has begun: wave w (ALL NINE) takes S0 + w, S0 + w + 9, ... */
+            /* wave w takes segments S0 + w, S0 + w + 8, ... */
             const uint32_t S0 = rdfirst(segCnt[2u * kMaxSegs]);
             const uint32_t lastDw = (nPad >> 2) - 1u;
             auto load_tile = [&](uint32_t tb, uint32_t (&dst)[kWin]) {
@@ -2307,34 +1907,15 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 for (uint32_t j = 0; j < kWin; j++) dst[j] = p1B[tb + 64u * j + lane];
             };
             uint32_t nxt[kWin];
-            if (!matcher && nwBegun) {
-                /* the ninth wave's segment in progress: the quarter tiles left of its tile, then its other tiles */
-                const uint32_t tEnd = umin((nwSeg << kSegLog) + kSeg, nTiles << kTileLog);
-                u64 *recG = reinterpret_cast<u64 *>(p1B + (nwSeg << kSegLog));
-                if (nwQ != 0u) {
-                    if (nwQ <= 1u) parse_plain_windows<2, 4>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt);
-                    if (nwQ <= 2u) parse_plain_windows<4, 6>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt);
-                    parse_plain_windows<6, 8>(pf, src, recG, nwBase, n, lastDw, lane, nwWds, nwSt);
-                    nwBase += kTile;
-                }
-                for (uint32_t base = nwBase; base < tEnd; base += kTile) {
-                    uint32_t wds[kWin];
-                    load_tile(base, wds);
-                    parse_plain_windows<0, kWin>(pf, src, recG, base, n, lastDw, lane, wds, nwSt);
-                }
-                if (lane == 0u) { segCnt[nwSeg] = nwSt.cnt; segEndA[nwSeg] = nwSt.endA; }
-            }
-            constexpr uint32_t kParsers = kNinthExit ? (uint32_t)kMatchWaves : (uint32_t)kMatchWaves + 1u; /* waves that are left */
             uint32_t sgN = S0 + wave;
             if (sgN < nSegs) load_tile(sgN << kSegLog, nxt);
             while (sgN < nSegs) {
                 const uint32_t sg = sgN;
-                sgN = sg + kParsers;
+                sgN = sg + (uint32_t)kMatchWaves;
                 const uint32_t segStart = sg << kSegLog;
                 u64 *recG = reinterpret_cast<u64 *>(p1B + segStart);
                 const uint32_t tEnd = umin(segStart + kSeg, nTiles << kTileLog);
                 PlainParse st = { segStart, 0u, kNoAnchor };
-#ifndef QZ_EXP_NOPARSE /* (timing experiment only, no sequences: what the tile loop of a deferring kernel takes without its parse) */
                 for (uint32_t base = segStart; base < tEnd; base += kTile) {
                     uint32_t wds[kWin];
 #pragma unroll
@@ -2344,7 +1925,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                     if (base + kTile < tEnd || sgN < nSegs) load_tile(nb, nxt);
                     parse_plain_windows<0, kWin>(pf, src, recG, base, n, lastDw, lane, wds, st);
                 }
-#endif
                 if (lane == 0u) { segCnt[sg] = st.cnt; segEndA[sg] = st.endA; }
             }
         }
@@ -2368,7 +1948,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         const uint32_t anchorEndAll = lastAll == kNoAnchor ? blk.parseFrom : lastAll;
         /* PASS 2: the records of a segment, one lane per sequence (the four bytes before a match and before its source come from device memory) */
         {
-            for (uint32_t sg = firstSeg + wave; sg < nSegs; sg += kNinthExit ? (uint32_t)kMatchWaves : (uint32_t)kMatchWaves + 1u) { /* (any wave may emit any segment: the records were stored before the barrier) */
+            for (uint32_t sg = firstSeg + wave; sg < nSegs; sg += (uint32_t)kMatchWaves) { /* (any wave may emit any segment: the records were stored before the barrier) */
                 const u64 *recG = reinterpret_cast<const u64 *>(p1B + (sg << kSegLog));
                 const uint32_t cnt = rdlane(cv, sg), first = rdlane(incl, sg) - cnt;
                 uint32_t anchorIn = blk.parseFrom; /* literals pending when the segment starts: behind the last match of any segment before it */
@@ -2426,7 +2006,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                 out[blk.seqCap - 44u - wave] = make_uint4((uint32_t)(tD1 - tD0), (uint32_t)(tD2 - tD1), (uint32_t)(tD3 - tD2), (uint32_t)(__builtin_amdgcn_s_memtime() - tD3));
 #endif
         }
-        if (kNinthExit ? wave != 0u : matcher) return 0u;
+        if (wave != 0u) return 0u;
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = total + 1u;
         if (lane == 0 && total < blk.seqCap) store_entry(out, total, 0u, n - anchorEndAll, 0u, blk.mark);
@@ -2434,13 +2014,13 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         return count;
     }
 
-    /* ---------------- DEFER, the repeat-aware parse: the parse and the emission, quarter by quarter (all nine waves arrive here) ---------------- */
+    /* ---------------- DEFER, the repeat-aware parse: the parse and the emission, quarter by quarter ---------------- */
     if constexpr (DEFER && REP) {
         constexpr uint32_t kSegLog = 12u, kSeg = 1u << kSegLog, kSegsPerQ = kRing >> kSegLog; /* the launcher only starts these kernels with profile.segLog == 12 */
         static_assert(kSegsPerQ == (uint32_t)kMatchWaves, "one wave per segment of a quarter");
         constexpr uint32_t kNoAnchor = 0xFFFFFFFFu;
         __syncthreads(); /* every wave's parse words are stored (the loop's last barriers may have ordered LDS only); ring and tables are free */
-        uint32_t *pvW = tbl + wave * kPvStride; /* this wave's window of parse words: one tile (the head table's LDS: 8 x 520 words <= 5888) */
+        uint32_t *pvW = tbl + wave * kPvStride; /* this wave's window of parse words: one tile, in the head table's LDS */
         uint32_t *ctl = srec;                   /* [0, 8) the segments' counts, [8, 16) the end of their last match (kNoAnchor: none) */
         const uint32_t firstSeg = blk.parseFrom >> kSegLog, nSegs = (nh + kSeg - 1u) >> kSegLog; /* segments that hold a hashable position */
         uint32_t total = 0u, anchorCarry = blk.parseFrom; /* sequences emitted so far; where the pending literals start */
@@ -2448,7 +2028,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             const uint32_t qs = Q * kRing;
             /* the quarter's bytes into the ring: position x at x mod kRing, as in the tile loop (what a 64-byte read finds behind the ring's end
              * belongs to the next segment and is masked) */
-            for (uint32_t o = qs + tid * 16u; o < umin(qs + kRing, nPad); o += (kNinthExit ? (uint32_t)kMatchThreads : (uint32_t)kThreads) * 16u) { /* (by the threads that are left) */
+            for (uint32_t o = qs + tid * 16u; o < umin(qs + kRing, nPad); o += (uint32_t)kMatchThreads * 16u) { /* (by the eight matcher waves) */
                 const uint4 v = g128[o >> 4];
                 ring128[(o & kRingMask) >> 4] = v;
                 if ((o & kRingMask) < kMirror) ring128[(kRing + (o & kRingMask)) >> 4] = v; /* (the emission's four bytes before a position may wrap) */
@@ -2457,39 +2037,28 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             const uint32_t sg = Q * kSegsPerQ + wave; /* this wave's segment */
             const uint32_t segStart = sg << kSegLog;
             u64 *recG = reinterpret_cast<u64 *>(p1B + segStart);
-            if (matcher) {
-                uint32_t cnt = 0u, endA = kNoAnchor;
-#ifndef QZ_DEFER_PRIO
-#define QZ_DEFER_PRIO 0 /* A/B: the priority of the parsing waves (a serial chain each) against the other workgroup's matcher waves on their SIMDs */
-#endif
-                if (QZ_DEFER_PRIO) __builtin_amdgcn_s_setprio(QZ_DEFER_PRIO);
-#ifdef QZ_EXP_NOPARSE /* timing experiment only (no sequences): what the tile loop of a deferring kernel takes without its parse */
-                if (false) {
-#else
-                if (sg >= firstSeg && sg < nSegs) {
-#endif
-                    const uint32_t tEnd = umin(segStart + kSeg, nTiles << kTileLog);
-                    uint32_t nxt[kWin];
+            uint32_t cnt = 0u, endA = kNoAnchor;
+            if (sg >= firstSeg && sg < nSegs) {
+                const uint32_t tEnd = umin(segStart + kSeg, nTiles << kTileLog);
+                uint32_t nxt[kWin];
 #pragma unroll
-                    for (uint32_t j = 0; j < kWin; j++) nxt[j] = p1B[segStart + 64u * j + lane];
-                    {
-                        RepState st = { segStart, segStart, 0u, 0u, 0u, 0u, sg };
-                        for (uint32_t base = segStart; base < tEnd; base += kTile) {
+                for (uint32_t j = 0; j < kWin; j++) nxt[j] = p1B[segStart + 64u * j + lane];
+                {
+                    RepState st = { segStart, segStart, 0u, 0u, 0u, 0u, sg };
+                    for (uint32_t base = segStart; base < tEnd; base += kTile) {
 #pragma unroll
-                            for (uint32_t j = 0; j < kWin; j++) pvW[64u * j + lane] = nxt[j];
-                            if (base + kTile < tEnd) { /* the next tile's words: in flight while this one is parsed */
+                        for (uint32_t j = 0; j < kWin; j++) pvW[64u * j + lane] = nxt[j];
+                        if (base + kTile < tEnd) { /* the next tile's words: in flight while this one is parsed */
 #pragma unroll
-                                for (uint32_t j = 0; j < kWin; j++) nxt[j] = p1B[base + kTile + 64u * j + lane];
-                            }
-                            parse_rep_span<true>(pf, src, pvW, base, base + kTile, n, nh, lane, st, qs, recG);
+                            for (uint32_t j = 0; j < kWin; j++) nxt[j] = p1B[base + kTile + 64u * j + lane];
                         }
-                        cnt = st.nseq;
-                        if (cnt) endA = st.anchor;
+                        parse_rep_span<true>(pf, src, pvW, base, base + kTile, n, nh, lane, st, qs, recG);
                     }
+                    cnt = st.nseq;
+                    if (cnt) endA = st.anchor;
                 }
-                if (lane == 0u) { ctl[wave] = cnt; ctl[kSegsPerQ + wave] = endA; }
-                if (QZ_DEFER_PRIO) __builtin_amdgcn_s_setprio(0);
             }
+            if (lane == 0u) { ctl[wave] = cnt; ctl[kSegsPerQ + wave] = endA; }
             __syncthreads(); /* counts in LDS; every wave's records are stored (it reads them back itself) */
             {
                 const uint32_t cv = lane < 2u * kSegsPerQ ? ctl[lane] : 0u;
@@ -2501,29 +2070,27 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                     all += c;
                     if (a != kNoAnchor) anchorOut = a;
                 }
-                if (matcher) {
-                    const uint32_t cnt = rdlane(cv, wave);
-                    for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
-                        const uint32_t k = k0 + lane;
-                        if (k < cnt) {
-                            const u64 r = recG[k];
-                            const uint32_t pm = (uint32_t)r & 0x1FFFFu, off = (uint32_t)(r >> 17) & 0x1FFFFu, len = (uint32_t)(r >> 34) & 0x1FFFu;
-                            uint32_t lit = pm - anchorIn; /* the segment's first match: literals since the last match of any segment before */
-                            if (k) lit = (uint32_t)(r >> 47) & 0x1FFFu;
-                            const uint32_t q = pm - off;
-                            const uint32_t maxb = umin(umin(umin(pf.backExt, lit), q), pm & (kSeg - 1u));
-                            uint32_t b = 0;
-                            if (maxb) { /* as emit_window: the 4 bytes before the match and before its source, top byte = nearest */
-                                const uint32_t pb = rd32u(src, pm - 4u, false);
-                                uint32_t qb;
-                                if (q < qs + 4u) qb = q >= 4u ? rd32u(src, q - 4u, true) : rd32u(src, 0u, true) << (8u * (4u - q)); /* the source's bytes lie before the quarter */
-                                else qb = rd32u(src, q - 4u, false);
-                                const uint32_t x = pb ^ qb;
-                                b = umin(x ? (uint32_t)__builtin_clz(x) >> 3 : 4u, maxb);
-                            }
-                            const uint32_t idx = total + before + k;
-                            if (idx < blk.seqCap) store_entry(out, idx, off, lit - b, len + b, blk.mark);
+                const uint32_t cnt = rdlane(cv, wave);
+                for (uint32_t k0 = 0; k0 < cnt; k0 += 64u) {
+                    const uint32_t k = k0 + lane;
+                    if (k < cnt) {
+                        const u64 r = recG[k];
+                        const uint32_t pm = (uint32_t)r & 0x1FFFFu, off = (uint32_t)(r >> 17) & 0x1FFFFu, len = (uint32_t)(r >> 34) & 0x1FFFu;
+                        uint32_t lit = pm - anchorIn; /* the segment's first match: literals since the last match of any segment before */
+                        if (k) lit = (uint32_t)(r >> 47) & 0x1FFFu;
+                        const uint32_t q = pm - off;
+                        const uint32_t maxb = umin(umin(umin(pf.backExt, lit), q), pm & (kSeg - 1u));
+                        uint32_t b = 0;
+                        if (maxb) { /* as emit_window: the 4 bytes before the match and before its source, top byte = nearest */
+                            const uint32_t pb = rd32u(src, pm - 4u, false);
+                            uint32_t qb;
+                            if (q < qs + 4u) qb = q >= 4u ? rd32u(src, q - 4u, true) : rd32u(src, 0u, true) << (8u * (4u - q)); /* the source's bytes lie before the quarter */
+                            else qb = rd32u(src, q - 4u, false);
+                            const uint32_t x = pb ^ qb;
+                            b = umin(x ? (uint32_t)__builtin_clz(x) >> 3 : 4u, maxb);
                         }
+                        const uint32_t idx = total + before + k;
+                        if (idx < blk.seqCap) store_entry(out, idx, off, lit - b, len + b, blk.mark);
                     }
                 }
                 total += all;
@@ -2531,7 +2098,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
             }
             __syncthreads(); /* the ring and the control words are rewritten by the next quarter */
         }
-        if (kNinthExit ? wave != 0u : matcher) return 0u; /* (where the ninth wave has ended, wave 0 closes the block) */
+        if (wave != 0u) return 0u; /* (the ninth wave has ended: wave 0 closes the block) */
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = total + 1u;
         if (lane == 0 && total < blk.seqCap) store_entry(out, total, 0u, n - anchorCarry, 0u, blk.mark);
@@ -2555,26 +2122,18 @@ template <bool HAS_LONG, bool REP, bool CHAIN, bool TURNS, bool NEAR>
 __global__ __launch_bounds__(kThreads) QZ_OCCUPANCY void qzstd_find_sequences_kernel(LaunchArgs args)
 {
     const qzstd_hip_block_t blk = args.blocks[blockIdx.x];
-    /* the launch kernels parse repeat-aware levels AFTER the tile loop (qz_item: DEFER): the parse words go to the dense 4-byte array of the block's
-     * scratch region — behind the chain entries at the chain levels (chainEntries), the whole region below them */
-#ifndef QZ_CHAIN8
-#define QZ_CHAIN8 1 /* the chain levels defer their parse too, matcher wave 0 (the wave that reaches their barriers first) inserts for the others, the ninth wave ends: eight
-                     * waves per workgroup.  Bit-exact; level 6 (config 3's shape) 75.2 -> 66.8 ms per GiB, level 12 on 32 KiB web-log blocks (config 4's) 106.2 -> 90.0,
-                     * level 12 on 128 KiB 186.0 -> 169.6, level 9 290.7 -> 243.2, level 5 56.1 -> 50.1.  (With the ninth wave alive the deferred parse was SLOWER at
-                     * these levels: 185.8 -> 192.1 — the gain is the wave's end.)  A/B: 0 = nine waves, the parse wave inserts and parses in lock-step */
-#endif
-    constexpr bool kDefer = CHAIN ? (QZ_CHAIN8 != 0 || (REP && QZ_REP_DEFER > 1)) : (REP ? QZ_REP_DEFER != 0 : QZ_PLAIN_DEFER != 0);
-    const uint32_t count = qz_item<HAS_LONG, REP, CHAIN, TURNS, NEAR, kDefer>(args, blk, args.src + blk.srcOff, args.seqs + blk.seqOff,
-                                                                CHAIN ? args.chain + (size_t)blockIdx.x * args.chainStride : nullptr,
-                                                                (CHAIN || kDefer) ? reinterpret_cast<uint32_t *>(args.chain + (size_t)blockIdx.x * args.chainStride + args.chainEntries) : nullptr,
-                                                                HistShare{ nullptr, 0u, 0u, 0u, 0u, nullptr, nullptr, nullptr });
+    /* the launch kernels parse AFTER the tile loop (qz_item: DEFER): the parse words go to the dense 4-byte array of the block's scratch region — behind
+     * the chain entries at the chain levels (chainEntries), the whole region below them */
+    const uint32_t count = qz_item<HAS_LONG, REP, CHAIN, TURNS, NEAR, true>(args, blk, args.src + blk.srcOff, args.seqs + blk.seqOff,
+                                                              CHAIN ? args.chain + (size_t)blockIdx.x * args.chainStride : nullptr,
+                                                              reinterpret_cast<uint32_t *>(args.chain + (size_t)blockIdx.x * args.chainStride + args.chainEntries),
+                                                              HistShare{ nullptr, 0u, 0u, 0u, 0u, nullptr, nullptr, nullptr });
     /* The count is the host's flag when the result area is pinned host memory (announcements: host/qatseqprod.c polls the count words instead
      * of asking the runtime about the stream — a stream query waits for whatever else shares the stream's hardware queue): every wave's result
      * stores are performed, then the count with a system-scope release.  The resident service publishes its items the same way. */
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    constexpr bool kNinthGone = kDefer && QZ_NINTH_EXIT != 0 && (REP || CHAIN || QZ_DEFER_INLOOP == 0);
-    if (threadIdx.x == (kNinthGone ? 0u : (uint32_t)kMatchThreads)) /* lane 0 of the parse wave (of wave 0 where the ninth wave has ended: QZ_NINTH_EXIT) */
+    if (threadIdx.x == 0u) /* lane 0 of wave 0, which returned the count (the ninth wave has ended) */
         __hip_atomic_store(args.nseq + blockIdx.x, count, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
@@ -3429,7 +2988,7 @@ int qzstd_hip_find_sequences(int device, void *stream, int level, const void *d_
         a.chain = static_cast<uint4 *>(d_work);
         a.chainStride = (uint32_t)(need / nBlocks / sizeof(uint4));
         a.chainEntries = (uint32_t)(need / nBlocks / (4u * QZSTD_HIP_CHAIN_ENTRY_LINKS + 4u)) * kEQ;
-    } else if (a.prof.repWin ? QZ_REP_DEFER != 0 : QZ_PLAIN_DEFER != 0) { /* the deferred parse below the chain levels: one parse word (4 B) per position */
+    } else { /* the deferred parse below the chain levels: one parse word (4 B) per position */
         const size_t need = qzstd_hip_workspace_bytes(level, nBlocks, maxBlockLen);
         if (!d_work || workBytes < need || need == 0) return fail_msg("qzstd_hip_find_sequences: workspace missing or too small (qzstd_hip_workspace_bytes)");
         a.chain = static_cast<uint4 *>(d_work);
@@ -3631,7 +3190,7 @@ int svc_launch_locked(int device, Service &s, int level)
     s.lds = lds;
     SvcHost *hsDev = nullptr;
     QZ_CHECK(hipHostGetDevicePointer(reinterpret_cast<void **>(&hsDev), s.hs, 0), "hipHostGetDevicePointer");
-    uint32_t ctlOff = (uint32_t)(lds - 96u - kLdsBase), spin = (uint32_t)cfg.spinLimit;
+    uint32_t ctlOff = (uint32_t)(lds - QZSTD_HIP_LDS_SVC - kLdsBase), spin = (uint32_t)cfg.spinLimit;
     void *wargs[5] = { &a, &s.dv, &ctlOff, &spin, &s.dProfs };
     uint32_t idle = (uint32_t)cfg.idleUs, drain = 1000000u;
     void *dargs[5] = { &hsDev, &s.dv, &served, &idle, &drain };

@@ -15,10 +15,6 @@
 
 #include <string.h>
 
-#define QZ_LDS_MAX 163840u
-#define QZ_LDS_CTRL (64u + 16u) /* control words + the 16 bytes below the kernel's first LDS address (kLdsBase) */
-#define QZ_LDS_SVC 96u          /* the resident service's item words, at the end of the allocation (csrc/qzstd_kernels.hip) */
-
 
 int qzstd_hip_profile_for_level(int level, size_t blockSize, qzstd_hip_profile_t *out)
 {
@@ -34,9 +30,6 @@ int qzstd_hip_profile_for_level(int level, size_t blockSize, qzstd_hip_profile_t
      * head table hardly matters there (a collision costs one chain step): 5888 entries -> two blocks per CU */
     {
         const int chains = level >= 5;
-#ifndef QZ_CHAIN_TABLE
-#define QZ_CHAIN_TABLE 5888u /* head-table entries of the chain levels (A/B builds: make variant XFLAGS=-DQZ_CHAIN_TABLE=n) */
-#endif
         out->tableSize = chains ? QZ_CHAIN_TABLE : (level >= 3 ? 16384u : 8192u); /* below the chain levels powers of two: the slot is a shift (round 5; 16000 / 6400 and a multiply-high before) */
         out->longSize = (!chains && level >= 3) ? 8192u : 0u;
         out->tileLog = 9;
@@ -98,41 +91,25 @@ size_t qzstd_hip_workspace_bytes(int level, uint32_t nBlocks, uint32_t maxBlockL
 {
     qzstd_hip_profile_t p;
     if (maxBlockLen > QZSTD_HIP_BLOCK_MAX || qzstd_hip_profile_for_level(level, maxBlockLen, &p)) return 0;
-#ifndef QZ_PLAIN_DEFER
-#define QZ_PLAIN_DEFER 1 /* csrc/qzstd_kernels.hip must agree */
-#endif
-#ifndef QZ_REP_DEFER
-#define QZ_REP_DEFER 1
-#endif
     if (!p.chainDepth) /* one word per position (the plain parse only uses the front of every 64: its starts) + the windows' start masks, 8 B per 64 positions */
-        return (p.repWin ? QZ_REP_DEFER != 0 : QZ_PLAIN_DEFER != 0) ? (size_t)nBlocks * ((((size_t)maxBlockLen + 511u) & ~(size_t)511u) / 8u * 33u) : 0;
+        return (size_t)nBlocks * ((((size_t)maxBlockLen + 511u) & ~(size_t)511u) / 8u * 33u);
     return (size_t)nBlocks * (((size_t)maxBlockLen + 511u) & ~(size_t)511u) * (4u * QZSTD_HIP_CHAIN_ENTRY_LINKS + 4u); /* a chain entry of QZSTD_HIP_CHAIN_ENTRY_LINKS links + the first link again, dense */
 }
-
-#ifndef QZ_RING
-#define QZ_RING 32768u
-#endif
-#ifndef QZ_PARSE_LAG
-#define QZ_PARSE_LAG 2u /* csrc/qzstd_kernels.hip must agree (make variant passes XFLAGS to both); 3 / 4: the decoupled parse wave experiment of round 6 */
-#endif
-#define QZ_RING_BYTES (QZ_RING + 128u) /* ring of recent block bytes + wrap mirror (csrc/qzstd_kernels.hip: kRing) */
 
 /* LDS per workgroup: independent of the block size — 72 560 B at levels 1-2 (two workgroups per CU) */
 size_t qzstd_hip_lds_bytes(int level, uint32_t maxBlockLen)
 {
     qzstd_hip_profile_t p;
-    size_t need, lag;
+    size_t need;
+    const size_t lag = 2u; /* tiles between matching and emission (csrc/qzstd_kernels.hip: kLagT) */
     if (maxBlockLen > QZSTD_HIP_BLOCK_MAX || qzstd_hip_profile_for_level(level, maxBlockLen, &p)) return 0;
-    /* tiles between matching and emission (csrc/qzstd_kernels.hip: kLagT): the decoupled parse wave of levels 1-4 keeps QZ_PARSE_LAG tiles of
-     * parse words and emission records; the chain levels and the repeat-aware parse run it in lock-step with the matchers: 2 */
-    lag = (p.chainDepth || p.repWin) ? 2u : QZ_PARSE_LAG;
-    need = (size_t)QZ_RING_BYTES
+    need = (size_t)QZ_RING + QZSTD_HIP_RING_MIRROR
            + 4u * p.tableSize        /* hash table                                    */
            + 4u * p.longSize         /* 8-byte-key table (levels >= 3)                */
            + (4u << p.tileLog)     /* tile-local near table / the current tile's chain links (levels >= 5) */
            + lag * ((4u << p.tileLog) + 32u) /* per-position parse words (+ override spill), `lag` tiles in flight */
            + lag * ((1u << p.tileLog) >> 6) * 32u /* per-window emission records, as many tiles */
            + (p.chainDepth ? (4u << p.tileLog) : 0u) /* chain levels: slot | tag of the tile's positions, for the insert wave */
-           + QZ_LDS_CTRL + QZ_LDS_SVC;
-    return need <= QZ_LDS_MAX ? need : 0;
+           + QZSTD_HIP_LDS_BASE + QZSTD_HIP_LDS_CTRL + QZSTD_HIP_LDS_SVC;
+    return need <= QZSTD_HIP_LDS_MAX ? need : 0;
 }

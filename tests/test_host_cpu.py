@@ -132,6 +132,12 @@ def test_lds_budget_fits_gfx950(plugin):
     assert plugin.lib.qzstd_hip_lds_bytes(1, 131072) * 2 <= 163840
     assert plugin.lib.qzstd_hip_lds_bytes(2, 32768) * 2 <= 163840
     assert plugin.lib.qzstd_hip_lds_bytes(3, 131072) > 81920
+    # the exact budgets: the layout numbers behind them are shared with the kernels (include/qzstd_hip.h)
+    want = {1: 72560, 2: 72560, 3: 138096, 4: 138096}
+    for level in range(1, 13):
+        for rep in (0, 0x100):
+            for blk in (32768, 131072):
+                assert plugin.lib.qzstd_hip_lds_bytes(level | rep, blk) == want.get(level, 65392), (level, rep, blk)
 
 
 def test_sequence_bound_matches_libzstd(plugin, zstd):

@@ -501,9 +501,10 @@ class ServiceLane:
             self.cnt[k] = 0
         self.epoch = self.epoch % 0xFFFFFF + 1
         work = None
-        if self.plug.profile(level, self.BLOCK_MAX).chainDepth:  # a chain level: the request carries a chain scratch
-            if not self.dwork:
-                self.dwork = self.L.qzstd_hip_malloc(self.device, self.BLOCK_MAX * (8 * 4 + 4) + 32 * 5888 * 4)  # QZSTD_HIP_SVC_WORK_BYTES: one scratch per request
+        prof = self.plug.profile(level, self.BLOCK_MAX)
+        if prof.chainDepth:  # a chain level: the request carries a chain scratch
+            if not self.dwork:  # QZSTD_HIP_SVC_WORK_BYTES: one scratch per request, one head table (QZ_CHAIN_TABLE = the chain levels' tableSize) per item
+                self.dwork = self.L.qzstd_hip_malloc(self.device, self.BLOCK_MAX * (8 * 4 + 4) + 32 * prof.tableSize * 4)
                 assert self.dwork, self.plug.err()
             work = self.dwork
         rq = SvcReq(self.hsrc, self.dsrc, self.hseq, self.hcnt, n, item_bytes, nit, cap, self.slot, self.epoch, work)
