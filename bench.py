@@ -22,6 +22,11 @@ launch stream; achieved = algorithmic bytes (block bytes read once + 16 B per se
 Further legs (side keys): `unchanged_callers` (nothing announced), `announced` (benchmark tool -H2), `e2e_ceiling_replay`,
 `cpu_libzstd_1_5` / `cpu_libzstd_1_4`, `pcie_pipeline`, `kernel_other_levels`, the other BASELINE levels end to end,
 `product_multi_gpu`, the oracle port on one core (`cpu_oracle_port`).
+
+A plain run (`--gpus N --steps K --warmup W`, with or without --dump-outputs) measures `value` and nothing else: it sets up, warms up,
+times the K passes, writes its outputs and prints the line, whose `roofline` and `cpu_baseline` are null.  `--full` adds the roofline
+block and every side leg above (`--no-cpu` then leaves out the CPU and side legs but keeps the roofline block); `--kernel-only` runs the
+roofline block alone.
 """
 from __future__ import annotations
 
@@ -71,7 +76,9 @@ def parse():
     ap.add_argument("--block", type=int, default=131072)
     ap.add_argument("--blocks", type=int, default=8192, help="blocks per GPU per step (8192 x 128 KiB = 1 GiB)")
     ap.add_argument("--corpus", default="system", help="system | text | mix | weblog | mixed_entropy | /path/to/file")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline / end-to-end legs")
+    ap.add_argument("--full", action="store_true", help="besides `value`, the roofline block (K timed launches of the dominant kernel, resident "
+                    "input) and every side leg: CPU baselines, other levels and shapes, the PCIe pipeline, the product's multi-GPU path")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline / end-to-end side legs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--e2e-seconds", type=float, default=5.5, help="continuous load per first-class end-to-end side leg")
     ap.add_argument("--e2e-blocks", type=int, default=8192, help="chunks per GPU per step of the timed ZSTD_compress2 leg (8192 x 128 KiB = 1 GiB: BASELINE configs[1])")
@@ -145,9 +152,12 @@ def slim_line(out: dict, details_file: str | None) -> dict:
     line["config"]["cpu_binding_rank0"] = {k: v if not isinstance(v, str) else _short(v, 80) for k, v in (cfg.get("cpu_binding_rank0") or {}).items()}
     line["config"]["producer_errors"] = (out.get("e2e", {}).get("producer_errors") or {}).get("total")
     line["config"]["roundtrip_sampled"] = out.get("e2e", {}).get("roundtrip_sampled")
-    line["roofline"] = {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms_avg",
-                                               "algorithmic_bytes_per_launch", "launches_timed")}
-    line["roofline"]["launch_workload"] = _short(rf.get("launch_workload", ""), 160)
+    if rf:
+        line["roofline"] = {k: rf.get(k) for k in ("bound", "achieved", "peak", "unit", "frac", "traffic", "kernel", "kernel_ms_avg",
+                                                   "algorithmic_bytes_per_launch", "launches_timed")}
+        line["roofline"]["launch_workload"] = _short(rf.get("launch_workload", ""), 160)
+    else:
+        line["roofline"] = None  # (a plain run: the roofline block needs --full)
     if cb:
         line["cpu_baseline"] = {k: cb.get(k) for k in ("value", "unit", "cores", "kind", "same_bytes_as_value", "sw_ratio_on_sample",
                                                        "sw_ratio_on_value_bytes") if k in cb}
@@ -787,24 +797,28 @@ def main():
     data, prov = load_corpus(a.corpus, size + S.weak_offset(size, world, world - 1))
     shard = data[off:off + size]
 
-    dev = torch.device("cuda", local)
-    d_src = torch.empty(size + 64, dtype=torch.uint8, device=dev)
-    d_src[:size].copy_(torch.frombuffer(bytearray(shard), dtype=torch.uint8))
-    stride = B.sequence_bound(block)
-    d_seqs = torch.empty((nb * stride, 4), dtype=torch.int32, device=dev)
-    d_cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
-    desc = (B.HipBlock * nb)()
-    for i in range(nb):
-        desc[i].srcOff = i * block
-        desc[i].seqOff = i * stride
-        desc[i].srcLen = block
-        desc[i].seqCap = stride
-    d_desc = torch.empty(C.sizeof(desc), dtype=torch.uint8, device=dev)
-    d_desc.copy_(torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8))
-    work = L.qzstd_hip_workspace_bytes(level, nb, block)  # levels >= 6: hash chains in device memory
-    d_work = torch.empty(max(work, 4), dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    stream = torch.cuda.current_stream()
+    # the dominant kernel over the whole batch, input resident in HBM: --full and --kernel-only time it (the `roofline` block); a plain run
+    # launches it only for the kernel arrays of --dump-outputs
+    roofline = a.full or a.kernel_only
+    if roofline or a.dump_outputs:
+        dev = torch.device("cuda", local)
+        d_src = torch.empty(size + 64, dtype=torch.uint8, device=dev)
+        d_src[:size].copy_(torch.frombuffer(bytearray(shard), dtype=torch.uint8))
+        stride = B.sequence_bound(block)
+        d_seqs = torch.empty((nb * stride, 4), dtype=torch.int32, device=dev)
+        d_cnt = torch.zeros(nb, dtype=torch.int32, device=dev)
+        desc = (B.HipBlock * nb)()
+        for i in range(nb):
+            desc[i].srcOff = i * block
+            desc[i].seqOff = i * stride
+            desc[i].srcLen = block
+            desc[i].seqCap = stride
+        d_desc = torch.empty(C.sizeof(desc), dtype=torch.uint8, device=dev)
+        d_desc.copy_(torch.frombuffer(bytearray(bytes(desc)), dtype=torch.uint8))
+        work = L.qzstd_hip_workspace_bytes(level, nb, block)  # levels >= 6: hash chains in device memory
+        d_work = torch.empty(max(work, 4), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        stream = torch.cuda.current_stream()
 
     def step():
         rc = L.qzstd_hip_find_sequences(local, C.c_void_p(stream.cuda_stream), level, C.c_void_p(d_src.data_ptr()),
@@ -813,25 +827,29 @@ def main():
         if rc != 0:
             raise RuntimeError(plug.err())
 
-    # ---- the dominant kernel, resident input, one HIP event pair per launch on the launch stream: the `roofline` block
-    for _ in range(max(a.warmup, 1)):
-        step()
-    torch.cuda.synchronize()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
-    tk0 = time.perf_counter()
-    ev[0].record(stream)
-    for k in range(a.steps):
-        step()
-        ev[k + 1].record(stream)  # HIP events on the launch stream: per-launch kernel time
-    torch.cuda.synchronize()
-    kern_wall = time.perf_counter() - tk0
-    kern_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(a.steps)]
-    kern_avg_ms = sum(kern_ms) / len(kern_ms)
-    kern_avg_ms_slowest = S.reduce_max_seconds(kern_avg_ms, dist if world > 1 else None, None)  # (a MAX over ranks, whatever the unit)
+    if roofline:
+        # ---- the dominant kernel, resident input, one HIP event pair per launch on the launch stream: the `roofline` block
+        for _ in range(max(a.warmup, 1)):
+            step()
+        torch.cuda.synchronize()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(a.steps + 1)]
+        tk0 = time.perf_counter()
+        ev[0].record(stream)
+        for k in range(a.steps):
+            step()
+            ev[k + 1].record(stream)  # HIP events on the launch stream: per-launch kernel time
+        torch.cuda.synchronize()
+        kern_wall = time.perf_counter() - tk0
+        kern_ms = [ev[k].elapsed_time(ev[k + 1]) for k in range(a.steps)]
+        kern_avg_ms = sum(kern_ms) / len(kern_ms)
+        kern_avg_ms_slowest = S.reduce_max_seconds(kern_avg_ms, dist if world > 1 else None, None)  # (a MAX over ranks, whatever the unit)
 
-    cnt = d_cnt.cpu().numpy().astype("uint32")
-    n_err = int((cnt == 0xFFFFFFFF).sum())
-    seq_total = int(cnt[cnt != 0xFFFFFFFF].sum())
+        cnt = d_cnt.cpu().numpy().astype("uint32")
+        n_err = int((cnt == 0xFFFFFFFF).sum())
+        seq_total = int(cnt[cnt != 0xFFFFFFFF].sum())
+    elif a.dump_outputs:
+        step()  # (once: a launch's results do not depend on the launches before it, so these are what the last of K would leave)
+        torch.cuda.synchronize()
     dumped = kernel_outputs(d_cnt, d_seqs, stride) if a.dump_outputs and rank == 0 else None
 
     if a.kernel_only:
@@ -873,8 +891,9 @@ def main():
     # ---- the software path over THE SAME BYTES, the same chunking, the same thread pool (round-5 verdict: cpu_baseline was timed on the first
     # 32 MiB of the corpus while `value` ran over all of it): QZSTD_frontCompress with useProducer = 0 — ZSTD_compress2 per chunk, plugin
     # unregistered, libzstd's own match-finder — over e2e_buf, once with as many threads as usable cores and once with `value`'s thread count
+    side_legs = a.full and not a.no_cpu
     sw_same = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if rank == 0 and world == 1 and side_legs:
         sw_same = []
         for t in sorted({max(1, min(int(host_cpu_budget()[1]), 128)), e2e_threads}):
             try:
@@ -892,9 +911,6 @@ def main():
     if rank == 0:
         total_bytes = len(e2e_buf) * world * a.steps
         value = total_bytes / wall / 1e6
-        alg_bytes = size + 16 * seq_total  # per launch: block bytes read once + 16 B per sequence written
-        achieved = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
-        traffic, traffic_src = profiled_traffic(nb, block) if level == 1 else (None, None)
         srt = sorted(per_pass)
         served_by_gpu = e2e_info["producer_errors"]["total"] == 0 and e2e_info["roundtrip_sampled"] == "PASS"
         out = {
@@ -915,21 +931,25 @@ def main():
                         pass_s_max=round(srt[-1], 4),
                         MBps_median_pass_this_rank=round(len(e2e_buf) / srt[len(srt) // 2] / 1e6, 1),
                         ratio=round(len(e2e_buf) / max(e2e_info["csize"], 1), 4)),
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
-                         "kernel": "qzstd_find_sequences_kernel", "kernel_ms_avg": round(kern_avg_ms, 3), "launches_timed": a.steps,
-                         "launch_workload": "level-%d, %d KiB blocks, %d blocks (%.2f GiB) per launch, input resident in HBM" % (level, block >> 10, nb, size / 2 ** 30),
-                         "algorithmic_bytes_per_launch": alg_bytes,
-                         "kernel_input_MBps": round(size / (kern_avg_ms * 1e-3) / 1e6, 1),
-                         "kernel_input_MBps_wall": round(size * a.steps / kern_wall / 1e6, 1),
-                         "kernel_input_MBps_all_gpus": round(world * size / (kern_avg_ms_slowest * 1e-3) / 1e6, 1),
-                         "input_read_frac_of_peak": round(size / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-                         "note": "the resident-input kernel rate (rounds 1-3: `value`); the metric above is bounded by host cores x libzstd's "
-                                 "entropy stage (so is its scaling over GPUs: the ranks share the host's cores), this is what the GPU side delivers: "
-                                 "kernel_input_MBps_all_gpus = ranks x bytes per launch / the slowest rank's average launch"},
-            "sequences_per_block": round(seq_total / max(nb - n_err, 1), 1), "error_blocks": n_err,
         }
-        if not a.no_cpu and world == 1 and level == 1 and block == 131072:
+        if roofline:
+            alg_bytes = size + 16 * seq_total  # per launch: block bytes read once + 16 B per sequence written
+            achieved = alg_bytes / (kern_avg_ms * 1e-3) / 1e9
+            traffic, traffic_src = profiled_traffic(nb, block) if level == 1 else (None, None)
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": traffic_src,
+                               "kernel": "qzstd_find_sequences_kernel", "kernel_ms_avg": round(kern_avg_ms, 3), "launches_timed": a.steps,
+                               "launch_workload": "level-%d, %d KiB blocks, %d blocks (%.2f GiB) per launch, input resident in HBM" % (level, block >> 10, nb, size / 2 ** 30),
+                               "algorithmic_bytes_per_launch": alg_bytes,
+                               "kernel_input_MBps": round(size / (kern_avg_ms * 1e-3) / 1e6, 1),
+                               "kernel_input_MBps_wall": round(size * a.steps / kern_wall / 1e6, 1),
+                               "kernel_input_MBps_all_gpus": round(world * size / (kern_avg_ms_slowest * 1e-3) / 1e6, 1),
+                               "input_read_frac_of_peak": round(size / (kern_avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
+                               "note": "the resident-input kernel rate (rounds 1-3: `value`); the metric above is bounded by host cores x libzstd's "
+                                       "entropy stage (so is its scaling over GPUs: the ranks share the host's cores), this is what the GPU side delivers: "
+                                       "kernel_input_MBps_all_gpus = ranks x bytes per launch / the slowest rank's average launch"}
+            out["sequences_per_block"], out["error_blocks"] = round(seq_total / max(nb - n_err, 1), 1), n_err
+        if side_legs and world == 1 and level == 1 and block == 131072:
             # the other BASELINE levels through the same entry point, resident input, HIP events (side keys, not the metric):
             # config 3's level 6 on 128 KiB blocks, config 4's level 12 on 32 KiB web-log blocks
             def side_kernel(lv, blk, nblk, src_bytes, host_results=0):
@@ -996,7 +1016,7 @@ def main():
             out["kernel_results_over_pcie_level1"] = {"device_memory": side_kernel(level, block, 2048, shard),
                                                       "pinned_host_16_byte_entries": side_kernel(level, block, 2048, shard, 16),
                                                       "pinned_host_packed_entries": side_kernel(level, block, 2048, shard, 8)}
-        if not a.no_cpu and world == 1:  # CPU legs on rank 0 at N=1 only (bench contract)
+        if side_legs and world == 1:  # CPU legs on rank 0 at N=1 only (bench contract)
             import tempfile
             ncpu, quota = host_cpu_budget()
             out["host"] = {"logical_cpus": ncpu, "usable_cores": round(quota, 1),
@@ -1203,7 +1223,7 @@ def main():
             os.unlink(fname)
         if "cpu_baseline" in out and out["cpu_baseline"].get("value"):
             out["vs_cpu_baseline"] = round(out["value"] / out["cpu_baseline"]["value"], 3)
-        if not a.no_cpu:
+        if side_legs:
             # ---- the product's multi-GPU path (rank 0, after the timed region; the other ranks wait at the barrier below): ONE process,
             # every visible gfx950 device — the announcement split of QZSTD_hintSource (contiguous block ranges, one per GPU, per-GPU streams,
             # results gathered in the announcement's pinned host buffers) and the PCIe-inclusive pipeline on every GPU at once

@@ -71,6 +71,33 @@ def test_slim_line_sheds_optional_keys_instead_of_failing(monkeypatch):
     assert "box_ceilings_GBps" not in line
 
 
+def test_plain_run_line_keeps_the_contract_keys_without_the_side_legs():
+    """a plain run (no --full) times `value` and nothing else: its line still carries every contract key, `roofline` and `cpu_baseline`
+    null, and the headline keys as measured"""
+    import bench
+    out = {k: v for k, v in canned().items() if k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
+                                                      "scaling", "vs_baseline", "dtype", "data", "config", "e2e")}
+    line = bench.slim_line(out, "bench_details.json")
+    s = json.dumps(line)
+    assert len(s) < 4096 and json.loads(s) == line
+    assert set(TOP) <= set(line) and set(line) <= set(TOP) | set(EXTRA)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["vs_cpu_baseline"] is None
+    assert all(k in line["config"] for k in CONFIG)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert line[k] == out[k], k
+
+
+def test_side_legs_need_full(monkeypatch):
+    """--full is off by default: `bench.py --gpus 1 --steps N --warmup W` is a plain run"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and not a.no_cpu and not a.kernel_only and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu"])
+    a = bench.parse()
+    assert a.full and a.no_cpu
+
+
 def test_write_details_names_a_file(tmp_path, monkeypatch):
     import bench
     monkeypatch.setattr(bench, "ROOT", str(tmp_path))

@@ -27,7 +27,7 @@ def test_two_rank_bench_both_ranks_on_gpu0(gpu_plugin):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-cpu",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full", "--no-cpu",
            "--blocks", "256", "--e2e-blocks", "256"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
@@ -53,7 +53,7 @@ def test_single_rank_bench_stdout_is_exactly_the_line_of_record(gpu_plugin):
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu", "--blocks", "512",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--blocks", "512",
                           "--e2e-blocks", "512"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
     lines = [x for x in out.stdout.splitlines() if x.strip()]
@@ -65,3 +65,24 @@ def test_single_rank_bench_stdout_is_exactly_the_line_of_record(gpu_plugin):
     assert line["n_gpus"] == 1 and line["config"]["libzstd_fast_build"] is True and line["config"]["producer_errors"] == 0
     assert line["roofline"]["frac"] > 0 and line["roofline"]["peak"] == 8000.0
     assert os.path.isfile(os.path.join(ROOT, line["details_file"]))
+
+
+@pytest.mark.gpu
+def test_single_rank_plain_bench_times_the_metric_alone(gpu_plugin):
+    """N = 1 without --full: the headline and nothing else — one line on stdout with the contract's keys, no roofline block, no CPU legs"""
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--blocks", "512",
+                          "--e2e-blocks", "512"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+    assert out.returncode == 0, (out.stdout + out.stderr)[-3000:]
+    lines = [x for x in out.stdout.splitlines() if x.strip()]
+    assert len(lines) == 1 and len(lines[0]) < 4096, out.stdout[:500]
+    line = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data",
+              "config", "roofline", "cpu_baseline", "vs_cpu_baseline", "details_file"):
+        assert k in line, k
+    assert line["n_gpus"] == 1 and line["steps"] == 2 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["unit"] == "MB/s" and line["higher_is_better"] is True and line["dtype"] == "u8"
+    assert line["config"]["producer_errors"] == 0 and line["config"]["roundtrip_sampled"] == "PASS"
+    assert line["roofline"] is None and line["cpu_baseline"] is None
