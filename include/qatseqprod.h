@@ -86,18 +86,19 @@ void QZSTD_freeSeqProdState(void *sequenceProducerState);
  *
  * The producer API is synchronous per block, which would leave 255 of the 256 CUs idle.
  * When the caller is about to run ZSTD_compress2 over a contiguous buffer it may tell
- * the state first; the plugin then match-finds the whole buffer in one batched launch
+ * the state first; the plugin then match-finds the whole buffer in batched launches
  * and serves the following qatSequenceProducer() callbacks whose (src, srcSize) lie on
  * the announced block grid from that result.  Purely an optimisation: callbacks that do
  * not match the hint take the normal single-block path.  `blockSize` is the block grid
  * (131072 for plain ZSTD_compress2; the frame/chunk size when each chunk is its own
  * frame; 1024 .. 131072, a multiple of 16; at most 16 MiB per call).  Returns 0 when the hint was accepted, -1 otherwise.
  *
- * The call is asynchronous: it copies at most 16 MiB into pinned memory, queues the
- * transfers and the launches, and returns.  A state holds four announcements (two until round 4), so a caller
+ * The call is asynchronous: it copies at most 16 MiB into pinned memory — a batch area that the announcements
+ * of every state of the process share — and returns; the batch goes out as one launch together with whatever
+ * else it collected (QZSTD_HIP_HINT_BATCHES launches in flight per GPU).  A state holds four announcements (two until round 4), so a caller
  * announces segments k+1 .. k+3 at most and compresses segment k; a fifth replaces the oldest.  On a node with several GPUs the
- * blocks of one announcement are split into contiguous ranges, one per GPU, each on its own
- * stream; every kernel writes its results into the announcement's pinned host buffers
+ * blocks of one announcement are split into contiguous ranges, one per GPU, each staged into that GPU's batch;
+ * every kernel writes its results into the batch area's pinned host buffers
  * (QZSTD_HIP_SPLIT=n limits the split to n GPUs, 1 keeps it on the state's own GPU).
  *
  * Streaming callers (ZSTD_compressStream2 with small feeds, the zstd CLI): libzstd hands the producer blocks out

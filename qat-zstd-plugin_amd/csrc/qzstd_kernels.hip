@@ -2628,11 +2628,11 @@ static int probe_lds_order(int device, int physDev)
 static void probe_devices()
 {
     int n = 0;
-    /* Announcements run on one stream per slot; the runtime folds its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and launches
-     * of different streams that share a queue run one after the other — four 32-block launches at a time leave the GPU mostly idle and the
-     * announcing threads waiting (batch front-end, 16 threads, level 1: 12.5 GB/s with 4 queues, 14.6 with 8, 18.3 with 16, 17.1 with 24).
-     * The variable is read when the runtime starts, so it only helps when this is the process's first HIP call; a value the
-     * environment already carries is left alone.  QZSTD_HIP_HW_QUEUES=0 leaves the runtime's default. */
+    /* The runtime folds its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and launches of different streams that share a queue run
+     * one after the other.  Announcements no longer depend on it (they go out as a few large launches on the announcement batcher's own
+     * streams, host/qatseqprod.c); the per-block paths' slot streams still do.  The variable is read when the runtime starts, so it only takes
+     * effect when this is the process's first HIP call; a value the environment already carries is left alone.  QZSTD_HIP_HW_QUEUES=0 leaves
+     * the runtime's default. */
     {
         const char *q = getenv("QZSTD_HIP_HW_QUEUES");
         const int want = q && *q ? atoi(q) : 16;

@@ -90,11 +90,8 @@ typedef struct {
     unsigned int *hCount; /* pinned */
     unsigned int *dCount;
     size_t seqCap;
-    /* grow-only buffers of the batched (announced) path */
-    unsigned char *dBatchSrc; size_t dBatchSrcCap;
-    /* launch scratch (hash chains of levels >= 5), grow-only: one block / an announced batch */
+    /* launch scratch (hash chains of levels >= 5), grow-only */
     void *dWork; size_t dWorkCap;
-    void *dBatchWork; size_t dBatchWorkCap;
     /* buffers of the resident service's requests (qzstd_hip_service_submit), created on first use: the staged block, its
      * device twin, QZ_SVC_ITEMS_MAX result regions and count words — the words are what the caller polls */
     unsigned char *vSrc;   /* pinned */
@@ -193,42 +190,43 @@ typedef struct {
     int svcSpinSet;                /* QZSTD_HIP_SERVICE_SPIN_US was given: no adapting */
     int liveStates;                /* producer states alive (one per CCtx, i.e. per calling thread): more of them than usable cores = the callers
                                     * oversubscribe the cores, and a caller that waits for the GPU should give its core away at once */
-    int hintFlags;                 /* QZSTD_HIP_HINT_FLAGS (default 1): an announcement's launch is complete when its blocks' count words are in (0: when
-                                    * the runtime says its stream is idle) */
+    struct QZSTD_Batcher_S *hb;    /* announcement batchers, one per device */
+    int hintBatches;               /* QZSTD_HIP_HINT_BATCHES (default 4): batch streams per device, i.e. announcement launches in flight */
+    unsigned int gen;              /* device layer generation: parts of an earlier start refer to nothing */
     int hintCompact;               /* QZSTD_HIP_HINT_COMPACT (default 1): announcements' result entries are packed — 8 bytes with a 12-bit tag */
     int stageNt;                   /* QZSTD_HIP_STAGE_NT (default 1): announcements are staged with streaming stores (qzStageCopy) */
-    int hintDirect;                /* QZSTD_HIP_HINT_DIRECT: 0 (default) an announcement's staging copy goes to device memory by a copy kernel on the
+    int hintDirect;                /* QZSTD_HIP_HINT_DIRECT: 0 (default) a batch's staging copy goes to device memory by a copy kernel on the
                                     * launch's stream; 1 the match-finder reads the pinned staging copy itself; 2 that at the levels without
-                                    * chains only; 3 the copy by hipMemcpyAsync (rounds 1-3).  Batch front-end, 16 threads, 2 MiB claims, GB/s:
-                                    * level 1 21.4 / 18.5 / 18.5 / 12-14, level 3 18.6 / 15.7 (the kernel takes 0.72 ms per launch out of device
-                                    * memory, 0.96 ms over the bus; hipMemcpyAsync holds the caller 0.8-1.1 ms per 4 MiB) */
+                                    * chains only; 3 the copy by hipMemcpyAsync (rounds 1-3).  Batch front-end, 16 threads, 2 MiB claims, GB/s
+                                    * (one launch per claim, 16 hardware queues): level 1 21.4 / 18.5 / 18.5 / 12-14, level 3 18.6 / 15.7 (the
+                                    * kernel takes 0.72 ms per launch out of device memory, 0.96 ms over the bus; hipMemcpyAsync holds the caller
+                                    * 0.8-1.1 ms per 4 MiB) */
 } QZSTD_Process_T;
 
 static QZSTD_Process_T gProc = { .status = QZSTD_FAIL, .coalesce = 1, .timeoutMs = QZ_DEFAULT_TIMEOUT_MS, .splitBlocks = 1, .service = 1,
                                  .svcItemBytes = 4096, .svcSpinUs = 400, .mutex = PTHREAD_MUTEX_INITIALIZER, .numa = 1, .numaThreadNode = -1,
-                                 .hintFlags = 1 };
+                                 .hintBatches = 4 };
 
-/* One announced buffer: staged in pinned memory, match-found asynchronously — split into contiguous block ranges, one
- * per GPU, each on a slot's stream — results (count + the first QZ_HINT_PITCH sequences of every block) written by
- * the kernels straight into the announcement's pinned host buffers. */
+/* One announced buffer: its blocks are staged into the batch areas of the announcement batcher (below) — split into contiguous
+ * block ranges, one per GPU — and match-found there; a callback is served from the area its block went to. */
 #define QZ_HINT_MAX_BYTES ((size_t)16 << 20)
 #define QZ_HINT_PITCH ((size_t)16384) /* blocks with more sequences take the per-block path */
-#define QZ_HINT_PARTS 8
-#define QZ_COUNT_PENDING 0xFFFFFFFDu /* an announced block's count word until its workgroup publishes it (gProc.hintFlags) */
+#define QZ_HINT_PARTS 16 /* block ranges of an announcement: one per GPU, more where a range does not fit one batch area */
+#define QZ_COUNT_PENDING 0xFFFFFFFDu /* an announced block's count word until its workgroup publishes it */
 #define QZ_HINTS 4 /* announcements a state keeps: a ring (QZSTD_hintSource) */
 #define QZ_CONTENT_LOOKUP_BLOCKS 256u /* announcements with more grid blocks are matched by address only */
 typedef struct {
-    int st;   /* 0 none, 1 in flight on the GPU (slot held), 2 ready, 3 failed */
-    int slot; /* index of the slot held while in flight */
+    int st;   /* 0 none, 1 in a batch (issued or not), 2 ready, 3 failed */
+    int dev, area;       /* the batch area of device dev that holds its blocks */
+    unsigned int first;  /* index of block b0 in that area */
+    unsigned int gen;    /* gProc.gen when it was staged */
     size_t b0, b1; /* block range [b0, b1) of the announcement */
-    size_t seen;   /* flags: every block below this one has published its count */
-    int flags;     /* completion by the blocks' count words (gProc.hintFlags), not by the stream */
+    size_t seen;   /* every block below this one has published its count */
 } QZSTD_Part_T;
 
 typedef struct {
     int st;   /* 0 empty, 1 announced (parts in flight or ready) */
     int touched; /* a callback was served from it */
-    unsigned int epoch; /* count-word completion: the mark (24 bits, never 0) every entry of THIS announcement carries in its fourth word */
     int stable;  /* QZSTD_HINT_STABLE: the announcer holds the bytes still until their callbacks have come (no memcmp per callback) */
     unsigned int seq;   /* the state's announcement number (QZSTD_Session_T.hintSeq): callbacks look at the newest announcement first */
     size_t servedUpTo;  /* grid blocks below this one have been served: a STABLE announcement serves every block once, going forward */
@@ -238,35 +236,92 @@ typedef struct {
     const unsigned char *base;
     size_t size, block, nb;
     int level;
-    unsigned char *hSrc;      /* pinned staging copy of the buffer */
     size_t pitch;             /* result entries per block: min(QZ_HINT_PITCH, ZSTD_sequenceBound(block)) */
     unsigned long long *keys; /* per grid block: size + first / last 8 bytes folded (content look-up for streaming callers) */
     size_t keysCap;
-    ZSTD_Sequence *hSeqs;     /* pinned, nb x pitch */
-    unsigned int *hCount;     /* pinned */
-    qzstd_hip_block_t *hDesc; /* pinned */
-    void *dvSeqs, *dvCount, *dvDesc; /* device-side addresses of the three: the kernels use them directly */
-    void *dvSrc;                     /* ... and of hSrc (QZSTD_HIP_HINT_DIRECT: the kernel reads the staging copy itself) */
-    const void *dvOf[4];             /* the host buffers the four were asked for: asked again only when a buffer was replaced (the
-                                      * runtime's look-up takes its global lock: ~0.5 ms per call with 16 announcing threads) */
-    size_t hSrcCap, hSeqsCap, hCountCap, hDescCap; /* bytes */
-    int nStuck, stuckSlot[QZ_HINT_PARTS]; /* slots whose wait timed out: a kernel may still read and write the buffers above */
     int noAddr; /* a newer announcement names (some of) these addresses: this one no longer serves by address, only by verified content */
-    int packedLast; /* the form of the entries the result area held last (1 packed, 0 sixteen-byte): a change of form (the device layer restarted with
-                     * another QZSTD_HIP_HINT_COMPACT) wipes it, as a lap of the epochs does */
 } QZSTD_Hint_T;
 
-/* Pinned buffers of an announcement that a timed-out kernel may still read (hSrc, hDesc) and write (hSeqs, hCount): the
- * announcement gets fresh ones, these are parked here — never reused, scrubbed or freed — until the streams of the slots
- * involved have drained (round-2 ADVICE: a late kernel must not write into the next announcement's results). */
+/*
+ * Announcement batcher (one per GPU): the "group commit" of the coalescer above, applied to announcements.  Announced block ranges of
+ * every state of the process go into a few large launches instead of one launch per announcement: launches of different streams that
+ * the runtime folds onto one hardware queue run one after the other, so with one launch per 2 MiB claim the GPU held as many claims as
+ * there were hardware queues (4 by default: 64 of 512 workgroup slots at level 1).
+ *
+ * A batch AREA is pinned host memory for up to QZ_HB_BLOCKS blocks: their staged bytes, descriptors, count words and result entries.
+ * An announcer reserves room in the OPEN area, stages its bytes and descriptors there itself, and the last one to finish staging issues
+ * the area when one of the batcher's QZSTD_HIP_HINT_BATCHES streams is free (its last launch has published every count word): one
+ * copy-in of the area's bytes and one launch of its blocks.  While every stream is busy the open area keeps collecting; it is issued
+ * by the next announcer or callback that finds a stream free — or, when it is full, holds another level or grid, or a callback or a
+ * drop needs one of its blocks, at once, behind the previous launch of a stream.  No timers, no host thread of its own.
+ * An area is reused when every part in it has been consumed, dropped or failed; its entries carry a 12-bit tag (24 bits unpacked)
+ * that changes with every use, and the area is wiped when the tag starts over.  A wait that times out fails every part of the area;
+ * its buffers are parked (QZSTD_Orphan_T) when the last part lets go, its stream is quarantined until it drains.
+ */
+#define QZ_HB_STREAMS_MAX 32
+#define QZ_HB_AREAS 256                                 /* areas per GPU, given buffers on first use (32 MiB of pinned memory each): an area
+                                                         * lives until the slowest claim in it is consumed — about 2.4 per announcing thread at
+                                                         * level 1 (41 for 17 threads); past the last one a range takes the per-block path */
+#define QZ_HB_BLOCKS 256u                               /* blocks per area, i.e. per launch at most (grids finer than 32 KiB) */
+#define QZ_HB_SRC_BYTES ((size_t)16 << 20)              /* staged bytes per area: 128 blocks of 128 KiB.  An area fills up when every stream is
+                                                         * busy and then goes behind a busy one: 64 blocks per area held 3 hardware queues to
+                                                         * 70 workgroups in flight and 17.8 GB/s at level 1 */
+#define QZ_HB_ENTRIES ((size_t)128 * QZ_HINT_PITCH)     /* result entries per area: 128 blocks at the widest pitch */
+enum { QZ_AREA_FREE = 0, QZ_AREA_OPEN, QZ_AREA_ISSUING, QZ_AREA_ISSUED };
+typedef struct {
+    int st;
+    int level;          /* the level (with flags) and the grid of every block in it: one launch, one profile */
+    size_t block;
+    unsigned int nBlocks, seen; /* descriptors in use; every block below `seen` has published its count */
+    size_t srcUsed, entUsed;    /* staged bytes, result entries reserved */
+    int staging;        /* announcers still copying into it */
+    int parts;          /* parts that still refer to it */
+    int stream;         /* the batch stream it was issued on */
+    int stuck;          /* a wait for it timed out */
+    int wipe;           /* its tag started over: the opener wipes its result area (qzAreaOpen) */
+    int sealed;         /* full, or a range of another level or grid came: it takes no more parts, and goes out as soon as its staging is done */
+    unsigned int lap;   /* the tag of its entries */
+    unsigned char *hSrc;      /* pinned, QZ_HB_SRC_BYTES */
+    qzstd_hip_block_t *hDesc; /* pinned, QZ_HB_BLOCKS */
+    unsigned int *hCount;     /* pinned, coherent, QZ_HB_BLOCKS */
+    void *hSeqs;              /* pinned, coherent, QZ_HB_ENTRIES packed (8-byte) or sixteen-byte entries */
+    size_t seqsCap;           /* bytes */
+    void *dvSrc, *dvDesc, *dvCount, *dvSeqs; /* their device-side addresses */
+} QZSTD_Area_T;
+
+typedef struct {
+    void *stream;
+    unsigned char *dSrc;      /* device, QZ_HB_SRC_BYTES: the copy-in's destination */
+    void *dWork; size_t dWorkCap; /* launch scratch (levels >= 5), grow-only */
+    int last;                 /* area issued last on it, -1 none */
+    int issuing;              /* a thread is queueing a launch on it */
+    int stuck;                /* a wait timed out: not used before it has drained */
+} QZSTD_BStream_T;
+
+typedef struct QZSTD_Batcher_S {
+    int device;
+    pthread_mutex_t mu;
+    pthread_cond_t cv;        /* an area's staging or a stream's issue has finished */
+    int open;                 /* the area taking parts, -1 none */
+    int pending;              /* the open area holds blocks (read without the lock by callbacks) */
+    int nextStream;
+    QZSTD_BStream_T str[QZ_HB_STREAMS_MAX];
+    QZSTD_Area_T area[QZ_HB_AREAS];
+    unsigned long launches, blocks, areas; /* event log / test hook: launches, blocks launched, areas given buffers */
+} QZSTD_Batcher_T;
+
+/* Pinned buffers of a batch area that a timed-out kernel may still read (hSrc, hDesc) and write (hSeqs, hCount): the area gets fresh
+ * ones, these are parked here — never reused, scrubbed or freed — until the stream it ran on has drained (round-2 ADVICE: a late
+ * kernel must not write into the next announcement's results). */
 typedef struct QZSTD_Orphan_S {
     struct QZSTD_Orphan_S *next;
     void *buf[4];
     size_t srcCap;
-    int nSlots, slot[QZ_HINT_PARTS];
+    int device;
+    void *stream;
 } QZSTD_Orphan_T;
 static QZSTD_Orphan_T *qzOrphans;
-static unsigned long qzOrphanCount; /* test hook / log: announcements whose buffers were parked */
+static unsigned long qzOrphanCount; /* test hook / log: areas whose buffers were parked */
 static pthread_mutex_t qzOrphanMu = PTHREAD_MUTEX_INITIALIZER;
 
 /* Per-CCtx state (opaque to the caller). */
@@ -283,11 +338,12 @@ typedef struct {
     unsigned long servedFromBatch, servedSync, servedService;
     unsigned long fail[QZ_CAUSE_N]; /* callbacks that returned the error code, by cause ([0] = all of them) */
     unsigned long redoneAlone;      /* blocks too dense for a batch's result area, redone on a slot of their own (not errors) */
-    unsigned long hintCalls, hintStageNs, hintQueueNs, hintWaitNs, hintCopyCallNs, hintLaunchCallNs, hintPrepNs, hintDropNs; /* event log only */
+    unsigned long hintCalls, hintStageNs, hintWaitNs, hintCopyCallNs, hintLaunchCallNs, hintPrepNs, hintDropNs; /* event log only */
 } QZSTD_Session_T;
 
 #define QZ_HINT_STALE_MISSES 16u /* an announcement that was used and then missed this often is dropped */
 static void qzReapOrphans(int force);
+static void qzFreeBatcher(QZSTD_Batcher_T *bt);
 static size_t qzFailed(QZSTD_Session_T *s, int cause);
 static void *qzGrowDev(int dev, void *old, size_t *cap, size_t need);
 static int qzUsableCores(void);
@@ -349,9 +405,7 @@ static void qzFreeSlot(QZSTD_Slot_T *s)
     qzstd_hip_free(s->device, s->dSeqs);
     qzstd_hip_free(s->device, s->dDesc);
     qzstd_hip_free(s->device, s->dCount);
-    qzstd_hip_free(s->device, s->dBatchSrc);
     qzstd_hip_free(s->device, s->dWork);
-    qzstd_hip_free(s->device, s->dBatchWork);
     if (s->vSrc) memset(s->vSrc, 0, QZSTD_HIP_BLOCK_MAX + 64); /* staged caller data: scrubbed before the pages go back */
     qzstd_hip_host_free(s->vSrc);
     qzstd_hip_host_free(s->vSeqs);
@@ -405,9 +459,8 @@ static int qzPickHint(void)
     return (int)(__sync_fetch_and_add(&gProc.anyNext, 1u) & 0x3FFFFFFFu);
 }
 
-/* lazy per-slot setup, first use only (reference: QZSTD_allocInstMem, :685-822); `full` also creates the buffers of the
- * one-block path (an announced batch only needs the stream and the grow-only batch buffers) */
-static int qzSetupSlot(QZSTD_Slot_T *s, int full)
+/* lazy per-slot setup, first use only (reference: QZSTD_allocInstMem, :685-822) */
+static int qzSetupSlot(QZSTD_Slot_T *s)
 {
     if (!s->stream) {
         s->stream = qzstd_hip_stream_create(s->device);
@@ -416,7 +469,7 @@ static int qzSetupSlot(QZSTD_Slot_T *s, int full)
             return QZSTD_FAIL;
         }
     }
-    if (!full || s->ready) return QZSTD_OK;
+    if (s->ready) return QZSTD_OK;
     s->seqCap = qzstd_hip_sequence_bound(QZSTD_HIP_BLOCK_MAX);
     s->hSrc = (unsigned char *)qzHostAlloc(QZSTD_HIP_BLOCK_MAX + 64, s->device, 0);
     s->hSeqs = (ZSTD_Sequence *)qzHostAlloc(s->seqCap * sizeof(ZSTD_Sequence), s->device, 0);
@@ -808,6 +861,15 @@ static int qzBuildSlots(void)
             pthread_cond_init(&gProc.coal[i].batch[b].cvDone, NULL);
         }
     }
+    gProc.hb = (QZSTD_Batcher_T *)calloc((size_t)nDev, sizeof(QZSTD_Batcher_T));
+    if (!gProc.hb) return QZSTD_FAIL;
+    for (i = 0; i < nDev; i++) {
+        gProc.hb[i].device = i;
+        gProc.hb[i].open = -1;
+        pthread_mutex_init(&gProc.hb[i].mu, NULL);
+        pthread_cond_init(&gProc.hb[i].cv, NULL);
+        for (b = 0; b < QZ_HB_STREAMS_MAX; b++) gProc.hb[i].str[b].last = -1;
+    }
     return QZSTD_OK;
 }
 
@@ -828,10 +890,11 @@ int QZSTD_startQatDevice(void)
         gProc.svcItemBytes = qzEnvInt("QZSTD_HIP_SERVICE_ITEM", 4096, 4096, (int)QZSTD_HIP_BLOCK_MAX) & ~4095;
         gProc.svcSpinUs = qzEnvInt("QZSTD_HIP_SERVICE_SPIN_US", 400, 0, 1000000);
         gProc.svcSpinSet = getenv("QZSTD_HIP_SERVICE_SPIN_US") != NULL;
-        gProc.hintFlags = qzEnvInt("QZSTD_HIP_HINT_FLAGS", 1, 0, 1);
         /* announcements: PACKED result entries (qzstd_hip.h: QZSTD_HIP_MARK_COMPACT) — 8 bytes per sequence over PCIe instead of 16 (round 6: the
-         * level-1 kernel ran at the bus's write rate); needs the count-word completion (every entry certifies itself).  0 = 16-byte entries (A/B) */
-        gProc.hintCompact = gProc.hintFlags ? qzEnvInt("QZSTD_HIP_HINT_COMPACT", 1, 0, 1) : 0;
+         * level-1 kernel ran at the bus's write rate).  0 = 16-byte entries (A/B) */
+        gProc.hintCompact = qzEnvInt("QZSTD_HIP_HINT_COMPACT", 1, 0, 1);
+        /* announcement launches in flight per GPU (the batcher's streams): the runtime's default hardware queue count */
+        gProc.hintBatches = qzEnvInt("QZSTD_HIP_HINT_BATCHES", 4, 1, QZ_HB_STREAMS_MAX);
         gProc.stageNt = qzEnvInt("QZSTD_HIP_STAGE_NT", 1, 0, 1);
         gProc.hintDirect = qzEnvInt("QZSTD_HIP_HINT_DIRECT", 0, 0, 3);
         (void)qzUsableCores(); /* (read once here, under the process mutex: the waits only load it) */
@@ -857,9 +920,15 @@ void QZSTD_stopQatDevice(void)
     for (i = 0; i < gProc.numDevices; i++) (void)qzstd_hip_service_stop(i); /* the resident kernels leave before anything is freed */
     if (gProc.slots) {
         for (i = 0; i < gProc.numSlots; i++) qzFreeSlot(&gProc.slots[i]); /* waits (bounded) for each stream */
-        qzReapOrphans(1);
         free(gProc.slots);
     }
+    if (gProc.hb) {
+        for (i = 0; i < gProc.numDevices; i++) qzFreeBatcher(&gProc.hb[i]); /* waits (bounded) for each stream */
+        free(gProc.hb);
+    }
+    gProc.hb = NULL;
+    qzReapOrphans(1); /* (after the bounded waits for the streams the parked areas' kernels ran on) */
+    gProc.gen++; /* parts staged so far refer to nothing any more */
     if (gProc.coal) {
         for (i = 0; i < gProc.numDevices; i++) qzFreeCoalescer(&gProc.coal[i]);
         free(gProc.coal);
@@ -914,14 +983,8 @@ static void qzReapOrphans(int force)
     pthread_mutex_lock(&qzOrphanMu);
     for (pp = &qzOrphans; *pp; ) {
         QZSTD_Orphan_T *o = *pp;
-        int k, busy = 0;
-        for (k = 0; k < o->nSlots && !force; k++) {
-            const int i = o->slot[k];
-            if (gProc.slots && i >= 0 && i < gProc.numSlots && gProc.slots[i].stream &&
-                qzstd_hip_stream_query(gProc.slots[i].device, gProc.slots[i].stream) != 0)
-                busy = 1;
-        }
-        if (busy) { pp = &o->next; continue; }
+        int k;
+        if (!force && o->stream && qzstd_hip_stream_query(o->device, o->stream) != 0) { pp = &o->next; continue; }
         if (o->buf[0]) memset(o->buf[0], 0, o->srcCap);
         for (k = 0; k < 4; k++) qzstd_hip_host_free(o->buf[k]);
         *pp = o->next;
@@ -930,35 +993,50 @@ static void qzReapOrphans(int force)
     pthread_mutex_unlock(&qzOrphanMu);
 }
 
-/* the announcement's buffers may still be in use by a kernel that timed out: park them, the announcement starts afresh */
-static void qzOrphanHint(QZSTD_Hint_T *h)
+/* the area's buffers may still be in use by a kernel that timed out on `stream`: park them, the area starts afresh at its next use */
+static void qzOrphanArea(QZSTD_Area_T *a, int dev, void *stream)
 {
     QZSTD_Orphan_T *o = (QZSTD_Orphan_T *)calloc(1, sizeof(*o));
-    int k;
     if (o) { /* (no memory for the list node: the buffers are leaked rather than freed under a running kernel) */
-        o->buf[0] = h->hSrc; o->buf[1] = h->hSeqs; o->buf[2] = h->hCount; o->buf[3] = h->hDesc;
-        o->srcCap = h->hSrcCap;
-        o->nSlots = h->nStuck;
-        for (k = 0; k < h->nStuck; k++) o->slot[k] = h->stuckSlot[k];
+        o->buf[0] = a->hSrc; o->buf[1] = a->hSeqs; o->buf[2] = a->hCount; o->buf[3] = a->hDesc;
+        o->srcCap = QZ_HB_SRC_BYTES;
+        o->device = dev;
+        o->stream = stream;
         pthread_mutex_lock(&qzOrphanMu);
         o->next = qzOrphans;
         qzOrphans = o;
         qzOrphanCount++;
         pthread_mutex_unlock(&qzOrphanMu);
     }
-    h->hSrc = NULL; h->hSeqs = NULL; h->hCount = NULL; h->hDesc = NULL;
-    h->dvSeqs = h->dvCount = h->dvDesc = h->dvSrc = NULL;
-    h->hSrcCap = h->hSeqsCap = h->hCountCap = h->hDescCap = 0;
-    h->nStuck = 0;
-    QZ_LOG(1, "an announcement's buffers are parked until a timed-out stream drains\n");
+    a->hSrc = NULL; a->hSeqs = NULL; a->hCount = NULL; a->hDesc = NULL;
+    a->dvSeqs = a->dvCount = a->dvDesc = a->dvSrc = NULL;
+    a->seqsCap = 0;
+    QZ_LOG(1, "device %d: a batch area's buffers are parked until a timed-out stream drains\n", dev);
 }
 #ifdef QZ_TEST_HOOKS /* the mock build of tests/test_host_mock.py only: never in the release library */
 unsigned long qzstd_test_orphans(void) { return qzOrphanCount; }
-void qzstd_test_set_hint_epochs(void *state, unsigned int e) /* the state's next announcements get epoch e + 1 (the 24-bit wrap) */
+void qzstd_test_set_area_tags(unsigned int e) /* the next use of every batch area, every GPU, gets tag e + 1 (the wrap) */
 {
-    QZSTD_Session_T *s = (QZSTD_Session_T *)state;
-    int k;
-    for (k = 0; s && k < QZ_HINTS; k++) s->hint[k].epoch = e & 0xFFFFFFu;
+    int d, k;
+    for (d = 0; gProc.hb && d < gProc.numDevices; d++) {
+        pthread_mutex_lock(&gProc.hb[d].mu);
+        for (k = 0; k < QZ_HB_AREAS; k++) gProc.hb[d].area[k].lap = e & 0xFFFFFFu;
+        pthread_mutex_unlock(&gProc.hb[d].mu);
+    }
+}
+/* the hook's name from the time announcements kept their own result areas and epochs (tests/test_host_mock.py calls it): the tags now belong to
+ * the batch areas, which every state shares, so `state` names nothing and every area's tag moves */
+void qzstd_test_set_hint_epochs(void *state, unsigned int e)
+{
+    (void)state;
+    qzstd_test_set_area_tags(e);
+}
+unsigned long qzstd_test_hint_launches(void) /* announcement launches since the device layer started, every GPU */
+{
+    unsigned long n = 0;
+    int d;
+    for (d = 0; gProc.hb && d < gProc.numDevices; d++) n += __atomic_load_n(&gProc.hb[d].launches, __ATOMIC_RELAXED);
+    return n;
 }
 void qzstd_test_set_service_epochs(unsigned int e) /* every slot's next service request gets epoch e + 1 (the 24-bit wrap) */
 {
@@ -1038,13 +1116,394 @@ static int qzTakePacked(ZSTD_Sequence *dst, const unsigned long long *q, size_t 
     return 0;
 }
 
-/* Completion of an announcement's launch WITHOUT the runtime (round 4): every workgroup publishes its block's count word — in the
- * announcement's pinned, coherent result area — with a system-scope release after all of its result stores (csrc/qzstd_kernels.hip,
+/* ---------------------------------------------------------------- announcement batcher -- */
+
+static void qzStageCopy(unsigned char *dst, const unsigned char *src, size_t n);
+
+/* every block of the area has published its count (called with the batcher's lock held) */
+static int qzAreaDone(QZSTD_Area_T *a)
+{
+    if (!a->hCount) return 1;
+    while (a->seen < a->nBlocks && __atomic_load_n(&a->hCount[a->seen], __ATOMIC_ACQUIRE) != QZ_COUNT_PENDING) a->seen++;
+    return a->seen >= a->nBlocks;
+}
+
+/* a stream a launch may be queued on: nobody is queueing on it and it is not quarantined (a drained one is back in service) */
+static int qzStreamUsable(QZSTD_Batcher_T *bt, int k)
+{
+    QZSTD_BStream_T *q = &bt->str[k];
+    if (q->issuing) return 0;
+    if (q->stuck) {
+        if (qzStillStuck(bt->device, q->stream, &q->stuck)) return 0;
+        q->last = -1; /* drained: whatever ran on it is over */
+    }
+    return 1;
+}
+
+/* free = usable, and its last launch has published every count word (not hipStreamQuery: see qzBlocksWait) */
+static int qzStreamFree(QZSTD_Batcher_T *bt, int k)
+{
+    QZSTD_BStream_T *q = &bt->str[k];
+    QZSTD_Area_T *a;
+    if (!qzStreamUsable(bt, k)) return 0;
+    if (q->last < 0) return 1;
+    a = &bt->area[q->last];
+    if (a->st != QZ_AREA_ISSUED || a->stream != k || qzAreaDone(a)) { q->last = -1; return 1; }
+    return 0;
+}
+
+/* an area's pinned buffers, allocated WITHOUT the batcher's lock (pinned allocations take milliseconds) into `a`: next to the GPU of
+ * the state that needs it first (`home`), as an announcement's own buffers were — the socket of the announcing threads, which stage
+ * into it.  0 on success */
+static int qzAreaAlloc(QZSTD_Area_T *a, int dev, int home)
+{
+    const size_t seqs = QZ_HB_ENTRIES * (gProc.hintCompact ? 8u : sizeof(ZSTD_Sequence));
+    memset(a, 0, sizeof(*a));
+    a->hSrc = (unsigned char *)qzHostAlloc(QZ_HB_SRC_BYTES, home, 0);
+    a->hDesc = (qzstd_hip_block_t *)qzHostAlloc(QZ_HB_BLOCKS * sizeof(qzstd_hip_block_t), home, 0);
+    a->hCount = (unsigned int *)qzHostAlloc(QZ_HB_BLOCKS * sizeof(unsigned int), home, 1);
+    a->hSeqs = qzHostAlloc(seqs, home, 1);
+    /* entries certify themselves by the area's tag, and fresh pinned pages may hold anything: tag 0 is never valid, the area starts wiped */
+    if (a->hSeqs) memset(a->hSeqs, 0, seqs);
+    a->dvSrc = a->hSrc ? qzstd_hip_host_device_ptr(a->hSrc) : NULL;
+    a->dvDesc = a->hDesc ? qzstd_hip_host_device_ptr(a->hDesc) : NULL;
+    a->dvCount = a->hCount ? qzstd_hip_host_device_ptr(a->hCount) : NULL;
+    a->dvSeqs = a->hSeqs ? qzstd_hip_host_device_ptr(a->hSeqs) : NULL;
+    if (!a->dvSrc || !a->dvDesc || !a->dvCount || !a->dvSeqs) {
+        QZ_LOG(1, "device %d: no pinned memory for a batch area: %s\n", dev, qzstd_hip_last_error());
+        qzstd_hip_host_free(a->hSrc); qzstd_hip_host_free(a->hDesc); qzstd_hip_host_free(a->hCount); qzstd_hip_host_free(a->hSeqs);
+        memset(a, 0, sizeof(*a));
+        return -1;
+    }
+    a->seqsCap = seqs;
+    return 0;
+}
+
+/* a free area that has its buffers becomes the open one (lock held); its index, -2 if the free areas have no buffers yet, -1 if there
+ * is no free area */
+static int qzAreaOpen(QZSTD_Batcher_T *bt, int level, size_t block)
+{
+    QZSTD_Area_T *a;
+    int k, bare = 0;
+    for (k = 0; k < QZ_HB_AREAS && !(bt->area[k].st == QZ_AREA_FREE && bt->area[k].hSrc); k++) bare |= bt->area[k].st == QZ_AREA_FREE;
+    if (k >= QZ_HB_AREAS) return bare ? -2 : -1;
+    a = &bt->area[k];
+    a->lap = (a->lap + 1u) & (gProc.hintCompact ? 0xFFFu : 0xFFFFFFu);
+    a->staging = a->parts = 0;
+    a->wipe = a->sealed = 0;
+    if (a->lap == 0u) {
+        /* the tag (12 bits packed, 24 unpacked) starts over: an entry no use of the last lap overwrote would show a valid tag again.
+         * Nothing runs on the area here (every part of its last use let go): its result area is wiped once per lap — by the opener,
+         * outside the lock, counted as one more stager so that the area is not issued before the wipe is done (qzBatchAdd) */
+        a->lap = 1u;
+        a->wipe = 1;
+        a->staging = 1;
+    }
+    a->st = QZ_AREA_OPEN;
+    a->level = level;
+    a->block = block;
+    a->nBlocks = a->seen = 0;
+    a->srcUsed = a->entUsed = 0;
+    a->stream = -1;
+    a->stuck = 0;
+    bt->open = k;
+    return k;
+}
+
+/* every part of the area has let go (lock held): parked if a wait for it timed out, free again either way */
+static void qzAreaRetire(QZSTD_Batcher_T *bt, int ai)
+{
+    QZSTD_Area_T *a = &bt->area[ai];
+    int k;
+    if (a->stuck) qzOrphanArea(a, bt->device, a->stream >= 0 ? bt->str[a->stream].stream : NULL);
+    for (k = 0; k < QZ_HB_STREAMS_MAX; k++)
+        if (bt->str[k].last == ai && !bt->str[k].stuck) bt->str[k].last = -1;
+    a->st = QZ_AREA_FREE;
+}
+
+/* one copy-in of the area's staged bytes and one launch of its blocks, on stream q (lock NOT held); 0 on success */
+static int qzLaunchArea(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, QZSTD_Area_T *a, QZSTD_BStream_T *q)
+{
+    const int dev = bt->device;
+    const size_t work = qzstd_hip_workspace_bytes(a->level, a->nBlocks, (unsigned int)a->block);
+    unsigned long t0;
+    int direct, rc;
+    if (!q->stream && !(q->stream = qzstd_hip_stream_create(dev))) return -1;
+    if (work && !(q->dWork = qzGrowDev(dev, q->dWork, &q->dWorkCap, work))) return -1;
+    direct = gProc.hintDirect == 1 || (gProc.hintDirect == 2 && work == 0); /* (A/B switch, see hintDirect) */
+    if (!direct) {
+        if (!q->dSrc && !(q->dSrc = (unsigned char *)qzstd_hip_malloc(dev, QZ_HB_SRC_BYTES))) return -1;
+        t0 = qzNowNs();
+        /* the staging copy goes to device memory by a copy kernel on the stream (qzstd_hip_copy_in says why not by the runtime's copy) */
+        rc = gProc.hintDirect != 3 ? qzstd_hip_copy_in(dev, q->stream, q->dSrc, a->dvSrc, a->srcUsed)
+                                   : qzstd_hip_memcpy_h2d(dev, q->stream, q->dSrc, a->hSrc, a->srcUsed);
+        if (s) s->hintCopyCallNs += qzNowNs() - t0;
+        if (rc) return -1;
+    }
+    t0 = qzNowNs();
+    rc = qzstd_hip_find_sequences(dev, q->stream, a->level, direct ? a->dvSrc : q->dSrc, (const qzstd_hip_block_t *)a->dvDesc, a->nBlocks,
+                                  (unsigned int)a->block, a->dvSeqs, (unsigned int *)a->dvCount, q->dWork, q->dWorkCap);
+    if (s) s->hintLaunchCallNs += qzNowNs() - t0;
+    if (rc) return -1;
+    __atomic_fetch_add(&gProc.devBlocks[dev][0], (unsigned long)a->nBlocks, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&bt->launches, 1ul, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&bt->blocks, (unsigned long)a->nBlocks, __ATOMIC_RELAXED);
+    return 0;
+}
+
+/* Issue a collecting area (lock held; held again on return): area `want`, or the open one when want < 0.  Not forced: only once its
+ * staging is done and on a FREE stream, else it keeps collecting.  Forced (a callback or a drop needs its blocks) or sealed (full, or
+ * another level or grid came): once its staging is done it is queued behind the launch of a busy stream if no stream is free; forced,
+ * the caller waits for that staging. */
+static void qzIssueOpen(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, int force, int want)
+{
+    const int n = gProc.hintBatches;
+    for (;;) {
+        const int ai = want >= 0 ? want : bt->open;
+        QZSTD_Area_T *a;
+        int k, pick = -1, busy = 0, rc, go;
+        unsigned int b;
+        if (ai < 0) return;
+        a = &bt->area[ai];
+        if (a->st != QZ_AREA_OPEN || a->nBlocks == 0) return; /* (issued meanwhile, or nothing in it yet) */
+        if (a->staging > 0) {
+            if (!force) return; /* the last announcer to finish staging comes back here */
+            pthread_cond_wait(&bt->cv, &bt->mu);
+            continue;
+        }
+        go = force || a->sealed;
+        for (k = 0; k < n && pick < 0; k++)
+            if (qzStreamFree(bt, (bt->nextStream + k) % n)) pick = (bt->nextStream + k) % n;
+        for (k = 0; k < n && pick < 0 && go; k++) {
+            const int j = (bt->nextStream + k) % n;
+            if (bt->str[j].issuing) busy = 1;
+            else if (qzStreamUsable(bt, j)) pick = j;
+        }
+        if (pick < 0 && !go) return;
+        if (pick < 0 && busy) { /* another thread is queueing on the only usable streams: after it */
+            pthread_cond_wait(&bt->cv, &bt->mu);
+            continue;
+        }
+        if (bt->open == ai) {
+            bt->open = -1;
+            __atomic_store_n(&bt->pending, 0, __ATOMIC_RELAXED);
+        }
+        if (pick < 0) { /* every stream is quarantined: nothing will run these blocks, their callbacks take the per-block path */
+            for (b = 0; b < a->nBlocks; b++) a->hCount[b] = QZSTD_HIP_NSEQ_ERROR;
+            a->st = QZ_AREA_ISSUED;
+            QZ_LOG(1, "device %d: every batch stream is quarantined; a batch of %u blocks is not queued\n", bt->device, a->nBlocks);
+            if (a->parts == 0) qzAreaRetire(bt, ai);
+            return;
+        }
+        bt->nextStream = (pick + 1) % n;
+        a->st = QZ_AREA_ISSUING;
+        a->stream = pick;
+        bt->str[pick].issuing = 1;
+        pthread_mutex_unlock(&bt->mu);
+        rc = qzLaunchArea(s, bt, a, &bt->str[pick]);
+        pthread_mutex_lock(&bt->mu);
+        if (rc) { /* never launched: nothing will publish these */
+            for (b = 0; b < a->nBlocks; b++) a->hCount[b] = QZSTD_HIP_NSEQ_ERROR;
+            QZ_LOG(1, "device %d: a batch of announced blocks is not queued: %s\n", bt->device, qzstd_hip_last_error());
+        }
+        a->st = QZ_AREA_ISSUED;
+        bt->str[pick].issuing = 0;
+        bt->str[pick].last = ai;
+        pthread_cond_broadcast(&bt->cv);
+        if (a->parts == 0) qzAreaRetire(bt, ai);
+        return;
+    }
+}
+
+/* a caller passing by (a callback, a waiter) issues the open area if a stream has become free */
+static void qzBatchPoke(QZSTD_Session_T *s, QZSTD_Batcher_T *bt)
+{
+    if (!__atomic_load_n(&bt->pending, __ATOMIC_RELAXED) || pthread_mutex_trylock(&bt->mu) != 0) return;
+    qzIssueOpen(s, bt, 0, -1);
+    pthread_mutex_unlock(&bt->mu);
+}
+
+/* blocks of announcement h that fit area a from block b on, at most `want` */
+static size_t qzAreaFit(const QZSTD_Area_T *a, const QZSTD_Hint_T *h, size_t want)
+{
+    size_t n = QZ_HB_BLOCKS - a->nBlocks, bySrc, byEnt;
+    bySrc = (QZ_HB_SRC_BYTES - a->srcUsed) / h->block; /* (a range is padded to 64 bytes: both ends of the room are multiples of 64, so n blocks
+                                                       * that fit unpadded fit padded) */
+    byEnt = (QZ_HB_ENTRIES - a->entUsed) / h->pitch;
+    if (n > bySrc) n = bySrc;
+    if (n > byEnt) n = byEnt;
+    return n < want ? n : want;
+}
+
+/* the opener's wipe of an area it staged nothing into (lock NOT held) */
+static void qzWipeArea(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, int ai)
+{
+    QZSTD_Area_T *a = &bt->area[ai];
+    memset(a->hSeqs, 0, a->seqsCap);
+    pthread_mutex_lock(&bt->mu);
+    if (--a->staging == 0) {
+        pthread_cond_broadcast(&bt->cv);
+        qzIssueOpen(s, bt, 0, ai);
+    }
+    pthread_mutex_unlock(&bt->mu);
+}
+
+/* Stage blocks [b0, b1) of announcement h into device dev's batcher, as one part per area they go to.  Blocks that find no room (no
+ * free area, no part left) get a failed part: their callbacks take the per-block path. */
+static void qzBatchAdd(QZSTD_Session_T *s, QZSTD_Hint_T *h, int dev, size_t b0, size_t b1, const unsigned char *src, int level, int stable)
+{
+    QZSTD_Batcher_T *bt = &gProc.hb[dev];
+    size_t b = b0;
+    while (b < b1 && h->nParts < QZ_HINT_PARTS) {
+        QZSTD_Part_T *pt = &h->part[h->nParts];
+        QZSTD_Area_T *a;
+        size_t n, j, srcOff, entOff, bytes;
+        unsigned int first;
+        int ai, wipe;
+        pthread_mutex_lock(&bt->mu);
+        ai = bt->open;
+        if (ai >= 0) {
+            a = &bt->area[ai];
+            if (a->nBlocks > 0 && (a->level != level || a->block != h->block || qzAreaFit(a, h, b1 - b) < b1 - b)) {
+                /* another level or grid (one launch = one profile), or too full for this range: it goes as it is — sealed, so that the
+                 * last of its stagers issues it, and this range opens the next area without waiting for them */
+                a->sealed = 1;
+                bt->open = -1;
+                __atomic_store_n(&bt->pending, 0, __ATOMIC_RELAXED);
+                if (a->staging == 0) qzIssueOpen(s, bt, 0, ai);
+                pthread_mutex_unlock(&bt->mu);
+                continue;
+            }
+            a->level = level; /* (an empty open area takes this range's level and grid) */
+            a->block = h->block;
+        } else if ((ai = qzAreaOpen(bt, level, h->block)) == -2) {
+            /* the free areas have no buffers yet: made here, outside the lock, and given to one of them */
+            QZSTD_Area_T fresh;
+            int k;
+            pthread_mutex_unlock(&bt->mu);
+            if (qzAreaAlloc(&fresh, dev, s->slotHint % gProc.numDevices) != 0) break;
+            pthread_mutex_lock(&bt->mu);
+            for (k = 0; k < QZ_HB_AREAS && !(bt->area[k].st == QZ_AREA_FREE && !bt->area[k].hSrc); k++) {}
+            if (k < QZ_HB_AREAS) {
+                const unsigned int lap = bt->area[k].lap;
+                bt->area[k] = fresh;
+                bt->area[k].lap = lap;
+                bt->areas++;
+                fresh.hSrc = NULL;
+            }
+            pthread_mutex_unlock(&bt->mu);
+            if (fresh.hSrc) { /* (another thread filled the last bare one meanwhile) */
+                qzstd_hip_host_free(fresh.hSrc); qzstd_hip_host_free(fresh.hDesc); qzstd_hip_host_free(fresh.hCount); qzstd_hip_host_free(fresh.hSeqs);
+            }
+            continue;
+        } else if (ai < 0) {
+            pthread_mutex_unlock(&bt->mu);
+            QZ_LOG(1, "device %d: no batch area free for an announcement\n", dev);
+            break;
+        }
+        a = &bt->area[ai];
+        wipe = a->wipe; /* (this thread opened it at the end of a lap: the wipe is its job) */
+        a->wipe = 0;
+        n = qzAreaFit(a, h, b1 - b);
+        if (n == 0 || (n < b1 - b && h->nParts == QZ_HINT_PARTS - 1)) { /* (the last part: the rest as a failed one) */
+            pthread_mutex_unlock(&bt->mu);
+            if (wipe) qzWipeArea(s, bt, ai);
+            break;
+        }
+        bytes = ((b + n) * h->block < h->size ? (b + n) * h->block : h->size) - b * h->block;
+        first = a->nBlocks;
+        srcOff = a->srcUsed;
+        entOff = a->entUsed;
+        a->nBlocks += (unsigned int)n;
+        a->srcUsed += (bytes + 63) & ~(size_t)63;
+        a->entUsed += n * h->pitch;
+        a->staging++;
+        a->parts++;
+        __atomic_store_n(&bt->pending, 1, __ATOMIC_RELAXED);
+        pthread_mutex_unlock(&bt->mu);
+
+        if (wipe) memset(a->hSeqs, 0, a->seqsCap);
+        /* pinned staging (reference: the staging memcpy, :1222-1227).  Streaming stores where the host will not read the copy back: a verified
+         * announcement compares every callback's block with it (measured with the copy streamed out: -2 ... -4 %), a STABLE one only samples (+1.5 %) */
+        if (stable) qzStageCopy(a->hSrc + srcOff, src + b * h->block, bytes);
+        else memcpy(a->hSrc + srcOff, src + b * h->block, bytes);
+        /* descriptors: results go straight into the area's pinned result area, h->pitch entries per block; a block with more sequences
+         * reports an error and is redone by the per-block path when its callback comes */
+        for (j = 0; j < n; j++) {
+            const size_t o = (b + j) * h->block, len = h->size - o < h->block ? h->size - o : h->block;
+            qzstd_hip_block_t *d = &a->hDesc[first + j];
+            const size_t ent = entOff + j * h->pitch;
+            d->srcOff = srcOff + j * h->block;
+            d->seqOff = gProc.hintCompact ? ent / 2u : ent; /* (sixteen-byte units; the pitch is even) */
+            d->srcLen = (unsigned int)len;
+            d->seqCap = (unsigned int)h->pitch;
+            d->parseFrom = 0;
+            d->mark = gProc.hintCompact ? (a->lap | QZSTD_HIP_MARK_COMPACT) : a->lap; /* every entry certifies itself, see qzTakeMarked */
+            a->hCount[first + j] = QZ_COUNT_PENDING; /* until its workgroup says otherwise */
+            if (h->keys && h->nb <= h->keysCap) h->keys[b + j] = len >= 16 ? qzBlockKey(a->hSrc + d->srcOff, len) : 0ull;
+        }
+        pt->st = 1;
+        pt->dev = dev;
+        pt->area = ai;
+        pt->first = first;
+        pt->gen = gProc.gen;
+        pt->b0 = pt->seen = b;
+        pt->b1 = b + n;
+        h->nParts++;
+        b += n;
+
+        pthread_mutex_lock(&bt->mu);
+        a->staging -= 1 + wipe;
+        if (a->staging == 0) {
+            pthread_cond_broadcast(&bt->cv);
+            qzIssueOpen(s, bt, 0, ai); /* the last one out issues it if a stream is free */
+        }
+        pthread_mutex_unlock(&bt->mu);
+    }
+    if (b < b1 && h->nParts < QZ_HINT_PARTS) {
+        QZSTD_Part_T *pt = &h->part[h->nParts++];
+        pt->st = 3;
+        pt->area = -1;
+        pt->b0 = pt->seen = b;
+        pt->b1 = b1;
+    }
+}
+
+/* the area and the index in it of block b of h; NULL when no part holds it (or the device layer has restarted since) */
+static QZSTD_Area_T *qzHintBlock(const QZSTD_Hint_T *h, size_t b, unsigned int *idx)
+{
+    int k;
+    for (k = 0; k < h->nParts; k++) {
+        const QZSTD_Part_T *pt = &h->part[k];
+        if (b < pt->b0 || b >= pt->b1) continue;
+        if (pt->area < 0 || pt->gen != gProc.gen || !gProc.hb) return NULL;
+        *idx = pt->first + (unsigned int)(b - pt->b0);
+        return &gProc.hb[pt->dev].area[pt->area];
+    }
+    return NULL;
+}
+
+/* the staged copy of blocks [b, e) equals p: 1 equal, 0 different, -1 not all of them are staged */
+static int qzHintSame(const QZSTD_Hint_T *h, size_t b, size_t e, const unsigned char *p)
+{
+    size_t bi;
+    for (bi = b; bi < e; bi++) {
+        unsigned int idx;
+        const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
+        if (!a || !a->hSrc) return -1;
+        if (memcmp(a->hSrc + a->hDesc[idx].srcOff, p + (bi - b) * h->block, a->hDesc[idx].srcLen) != 0) return 0;
+    }
+    return 1;
+}
+
+/* Completion of an announced launch WITHOUT the runtime (round 4): every workgroup publishes its block's count word — in the batch
+ * area's pinned, coherent result area — with a system-scope release after all of its result stores (csrc/qzstd_kernels.hip,
  * qzstd_find_sequences_kernel), and the words start out as QZ_COUNT_PENDING.  A callback waits for ITS blocks only, by reading memory.
  * (hipStreamQuery on one of 48 streams folded onto 16 hardware queues waits for whatever was queued behind the launch it asks about:
  * with the stream waits a worker of the batch front-end spent 30 % of its time waiting for launches that had long finished.)
- * Blocks [b0, b1): 0 = all published, 1 = not within the time-out. */
-static int qzBlocksWait(const QZSTD_Hint_T *h, size_t b0, size_t b1)
+ * Count words [i0, i1): 0 = all published, 1 = not within the time-out.  A waiter passing by issues its batcher's open area when a
+ * stream has become free. */
+static int qzBlocksWait(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, const unsigned int *cnt, size_t i0, size_t i1)
 {
     const unsigned long t0 = qzNowNs(), limit = (unsigned long)gProc.timeoutMs * 1000000ul;
     /* 50 us of polling, then naps: a waiting caller does not burn a core others could entropy-code on; with far more callers than
@@ -1052,11 +1511,11 @@ static int qzBlocksWait(const QZSTD_Hint_T *h, size_t b0, size_t b1)
      * Decided once, at the first miss (round-4 ADVICE: not by how long the first scan happened to take) */
     unsigned long spinNs = 50000ul;
     int decided = 0;
-    size_t b = b0;
+    size_t i = i0;
     for (;;) {
         unsigned long el;
-        while (b < b1 && __atomic_load_n(&h->hCount[b], __ATOMIC_ACQUIRE) != QZ_COUNT_PENDING) b++;
-        if (b >= b1) return 0;
+        while (i < i1 && __atomic_load_n(&cnt[i], __ATOMIC_ACQUIRE) != QZ_COUNT_PENDING) i++;
+        if (i >= i1) return 0;
         if (!decided) { /* at the first miss, whenever that is */
             decided = 1;
             if (2 * __atomic_load_n(&gProc.liveStates, __ATOMIC_RELAXED) > 3 * qzUsableCores()) spinNs = 0ul;
@@ -1064,44 +1523,98 @@ static int qzBlocksWait(const QZSTD_Hint_T *h, size_t b0, size_t b1)
         el = qzNowNs() - t0;
         if (el > limit) {
             qzCause = QZ_CAUSE_TIMEOUT;
-            QZ_LOG(1, "announcement: block %zu still not published after %d ms\n", b, gProc.timeoutMs);
+            QZ_LOG(1, "announcement: a block is still not published after %d ms\n", gProc.timeoutMs);
             return 1;
         }
         if (el > spinNs) {
             const struct timespec nap = { 0, el < 20000000ul ? 20000l : 200000l };
+            qzBatchPoke(s, bt);
             nanosleep(&nap, NULL);
         }
     }
 }
 
-/* wait for one part of an announcement and give its slot back; the part becomes ready (2) or failed (3) */
-static void qzPartFinish(QZSTD_Hint_T *h, QZSTD_Part_T *pt)
+/* Wait for blocks [w0, w1) of part pt (announcement block numbers), issuing its batch first if it is still collecting.  0 = there;
+ * -1 = the part failed (3): a wait for its batch timed out — which fails every part of the batch — or the device layer restarted. */
+static int qzPartWait(QZSTD_Session_T *s, QZSTD_Part_T *pt, size_t w0, size_t w1)
 {
-    if (pt->st != 1) return;
-    if (gProc.slots && pt->slot >= 0 && pt->slot < gProc.numSlots) {
-        QZSTD_Slot_T *sl = &gProc.slots[pt->slot];
-        const int w = pt->flags ? qzBlocksWait(h, pt->seen > pt->b0 ? pt->seen : pt->b0, pt->b1) : qzWait(sl->device, sl->stream);
-        if (w == 0) pt->seen = pt->b1;
-        if (w == 1) sl->stuck = 1; /* the slot is given back, but nobody uses it before its stream has drained */
-        if (w != 0 && h->nStuck < QZ_HINT_PARTS) h->stuckSlot[h->nStuck++] = pt->slot; /* ... and the kernel may still use h's buffers */
-        qzReleaseSlot(pt->slot);
-        pt->st = w == 0 ? 2 : 3;
-        if (w != 0) QZ_LOG(1, "announced batch failed: %s\n", qzstd_hip_last_error());
-    } else {
-        pt->st = 3;
+    QZSTD_Batcher_T *bt;
+    QZSTD_Area_T *a;
+    int stuck;
+    if (pt->st != 1) return pt->st == 2 ? 0 : -1;
+    if (pt->gen != gProc.gen || !gProc.hb) { pt->st = 3; pt->area = -1; return -1; }
+    bt = &gProc.hb[pt->dev];
+    a = &bt->area[pt->area];
+    if (w0 < pt->seen) w0 = pt->seen;
+    pthread_mutex_lock(&bt->mu);
+    if (a->st == QZ_AREA_OPEN) qzIssueOpen(s, bt, 1, pt->area); /* (nothing strands in a batch that is still collecting) */
+    stuck = a->stuck;
+    pthread_mutex_unlock(&bt->mu);
+    if (!stuck && (w0 >= w1 || qzBlocksWait(s, bt, a->hCount, pt->first + (w0 - pt->b0), pt->first + (w1 - pt->b0)) == 0)) {
+        while (pt->seen < pt->b1 && __atomic_load_n(&a->hCount[pt->first + (pt->seen - pt->b0)], __ATOMIC_ACQUIRE) != QZ_COUNT_PENDING) pt->seen++;
+        if (pt->seen >= pt->b1) pt->st = 2;
+        return 0;
     }
+    pthread_mutex_lock(&bt->mu);
+    if (!a->stuck) {
+        a->stuck = 1; /* its kernel may still read and write the area: parked when the last part lets go */
+        if (a->stream >= 0) bt->str[a->stream].stuck = 1; /* not used before it has drained */
+        QZ_LOG(1, "device %d: a batch of %u announced blocks timed out: %s\n", bt->device, a->nBlocks, qzstd_hip_last_error());
+    }
+    pthread_mutex_unlock(&bt->mu);
+    pt->st = 3;
+    return -1;
 }
 
-/* drop an announcement: wait for what is still in flight (its buffers are about to be reused or freed) */
+/* the part lets go of its area (waited for, or failed) */
+static void qzPartRelease(QZSTD_Part_T *pt)
+{
+    if (pt->st != 0 && pt->area >= 0 && pt->gen == gProc.gen && gProc.hb) {
+        QZSTD_Batcher_T *bt = &gProc.hb[pt->dev];
+        pthread_mutex_lock(&bt->mu);
+        if (--bt->area[pt->area].parts == 0 && bt->area[pt->area].st == QZ_AREA_ISSUED) qzAreaRetire(bt, pt->area);
+        pthread_mutex_unlock(&bt->mu);
+    }
+    pt->area = -1;
+    pt->st = 0;
+}
+
+/* drop an announcement: wait for what is still in flight (or in a batch still collecting: issued first), then let go of the areas */
 static void qzHintDrop(QZSTD_Hint_T *h)
 {
     int k;
-    for (k = 0; k < h->nParts; k++) qzPartFinish(h, &h->part[k]);
-    if (h->nStuck) qzOrphanHint(h);
+    for (k = 0; k < h->nParts; k++) {
+        if (h->part[k].st == 1) (void)qzPartWait(NULL, &h->part[k], h->part[k].b0, h->part[k].b1);
+        qzPartRelease(&h->part[k]);
+    }
     h->nParts = 0;
     h->st = 0;
     h->touched = 0;
     h->misses = 0;
+}
+
+static void qzFreeBatcher(QZSTD_Batcher_T *bt)
+{
+    int k;
+    QZ_LOG(2, "device %d: %lu announced block(s) in %lu launch(es), %lu batch area(s)\n", bt->device, bt->blocks, bt->launches, bt->areas);
+    for (k = 0; k < QZ_HB_STREAMS_MAX; k++) {
+        QZSTD_BStream_T *q = &bt->str[k];
+        if (q->stream) (void)qzstd_hip_stream_wait(bt->device, q->stream, (unsigned)gProc.timeoutMs);
+        qzstd_hip_free(bt->device, q->dSrc);
+        qzstd_hip_free(bt->device, q->dWork);
+    }
+    for (k = 0; k < QZ_HB_AREAS; k++) {
+        QZSTD_Area_T *a = &bt->area[k];
+        if (a->hSrc) memset(a->hSrc, 0, QZ_HB_SRC_BYTES); /* staged caller data: scrubbed before the pages go back */
+        qzstd_hip_host_free(a->hSrc);
+        qzstd_hip_host_free(a->hDesc);
+        qzstd_hip_host_free(a->hCount);
+        qzstd_hip_host_free(a->hSeqs);
+    }
+    for (k = 0; k < QZ_HB_STREAMS_MAX; k++)
+        if (bt->str[k].stream) qzstd_hip_stream_destroy(bt->device, bt->str[k].stream);
+    pthread_mutex_destroy(&bt->mu);
+    pthread_cond_destroy(&bt->cv);
 }
 
 void QZSTD_freeSeqProdState(void *sequenceProducerState)
@@ -1111,18 +1624,11 @@ void QZSTD_freeSeqProdState(void *sequenceProducerState)
     if (!s) return;
     __atomic_fetch_sub(&gProc.liveStates, 1, __ATOMIC_RELAXED);
     QZ_LOG(2, "state %p: %lu block(s) served from announcements, %lu per "
-              "block; %lu hint(s), timers from the 9th on: drop %.2f ms, buffers %.2f ms, staging %.2f ms, queueing %.2f ms (%.2f ms of it in the copy call, %.2f in the launch call), waited %.2f ms for the GPU\n", (void *)s,
+              "block; %lu hint(s), timers from the 9th on: drop %.2f ms, buffers %.2f ms, staging and queueing %.2f ms (%.2f ms in copy calls, %.2f in launch calls), waited %.2f ms for the GPU\n", (void *)s,
            s->servedFromBatch, s->servedSync, s->hintCalls, s->hintDropNs / 1e6, s->hintPrepNs / 1e6, s->hintStageNs / 1e6,
-           s->hintQueueNs / 1e6, s->hintCopyCallNs / 1e6, s->hintLaunchCallNs / 1e6, s->hintWaitNs / 1e6);
+           s->hintCopyCallNs / 1e6, s->hintLaunchCallNs / 1e6, s->hintWaitNs / 1e6);
     for (k = 0; k < QZ_HINTS; k++) {
         qzHintDrop(&s->hint[k]);
-        /* the staged copies are the caller's data (for a guess: bytes it never handed over): scrubbed before the
-         * pinned pages go back to the allocator */
-        if (s->hint[k].hSrc) memset(s->hint[k].hSrc, 0, s->hint[k].hSrcCap);
-        qzstd_hip_host_free(s->hint[k].hSrc);
-        qzstd_hip_host_free(s->hint[k].hSeqs);
-        qzstd_hip_host_free(s->hint[k].hCount);
-        qzstd_hip_host_free(s->hint[k].hDesc);
         free(s->hint[k].keys);
     }
     free(s);
@@ -1466,7 +1972,7 @@ static size_t qzSlotBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, s
             continue;
         }
         if (dev < 0) s->slotHint = i;
-        if (qzSetupSlot(sl, 1) == QZSTD_OK) rc = qzRunBlock(sl, outSeqs, outSeqsCapacity, src, srcSize, level);
+        if (qzSetupSlot(sl) == QZSTD_OK) rc = qzRunBlock(sl, outSeqs, outSeqsCapacity, src, srcSize, level);
         QZ_LOG(2, "block %zu B level %d -> %zu sequences (slot %d, device %d)\n", srcSize, level & 0xFF, rc, i, sl->device);
         qzReleaseSlot(i);
         return rc;
@@ -1493,6 +1999,10 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
     if (!s || !outSeqs || !src || srcSize > QZSTD_HIP_BLOCK_MAX || outSeqsCapacity < 3) return qzFailed(s, QZ_CAUSE_GUARD);
     if (!qzDeviceUsable(s)) return qzFailed(s, QZ_CAUSE_DEVICE_DOWN);
     qzCause = QZ_CAUSE_RUNTIME; /* until a failing site below says otherwise */
+    if (gProc.hb) { /* a batch collecting while every stream was busy goes out with the first caller that finds one free */
+        int d;
+        for (d = 0; d < gProc.numDevices; d++) qzBatchPoke(s, &gProc.hb[d]);
+    }
 
     /* Served from an announcement?  (src, srcSize) must start on an announced block grid and
      * cover one or more whole blocks of it: libzstd 1.5.7 cuts multi-block frames into blocks of 32..128 KiB at 32 KiB
@@ -1514,8 +2024,8 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
         for (oi = 0; oi < n; oi++) {
             QZSTD_Hint_T *h = &s->hint[order[oi]];
             const unsigned char *p = (const unsigned char *)src;
-            size_t rel, b, e, covered = 0;
-            int pi, ok = 1, byAddr = 0;
+            size_t rel, b, e, covered = 0, held = 0;
+            int pi, ok = 1, byAddr = 0, same = 1;
             k = order[oi];
             if (h->st == 0) continue; /* (dropped further up in this loop) */
             if (h->level != compressionLevel) continue;
@@ -1524,7 +2034,7 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
                 b = rel / h->block;
                 byAddr = 1;
                 if (rel % h->block != 0 || b >= h->nb) continue; /* off the grid (libzstd 1.5.7 pre-splits multi-block frames at 32 KiB steps): not served from here */
-                for (e = b; e < h->nb && covered < srcSize; e++) covered += h->hDesc[e].srcLen;
+                for (e = b; e < h->nb && covered < srcSize; e++) covered += h->size - e * h->block < h->block ? h->size - e * h->block : h->block;
                 if (covered != srcSize || e - b > 8) {
                     QZ_LOG(3, "announcement %d: block %zu+%zu does not fit the grid (%zu)\n", k, rel, srcSize, h->block);
                     continue;
@@ -1536,8 +2046,9 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
                     qzHintDrop(h);
                     continue;
                 }
-                /* verified: every callback; STABLE: every 16th block served, a sampled check of the announcer's promise (QZSTD_hintBroken) */
-                if ((!h->stable || (++s->stableSampler & 15u) == 0u) && memcmp(h->hSrc + rel, src, srcSize) != 0) {
+                /* verified: every callback; STABLE: every 16th block served, a sampled check of the announcer's promise (QZSTD_hintBroken).
+                 * (A block that was never staged — its part found no room — is not served; that says nothing about the caller's bytes) */
+                if ((!h->stable || (++s->stableSampler & 15u) == 0u) && (same = qzHintSame(h, b, e, p)) == 0) {
                     QZ_LOG(h->stable ? 1 : 2, "announcement %d: the buffer changed after it was announced%s; dropped\n", k,
                            h->stable ? " although it was announced with QZSTD_HINT_STABLE" : "");
                     if (h->stable) s->stableBroken++;
@@ -1553,56 +2064,51 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
                 if (srcSize < 16 || h->nb > QZ_CONTENT_LOOKUP_BLOCKS || !h->keys) continue;
                 key = qzBlockKey((const unsigned char *)src, srcSize);
                 for (b = 0; b < h->nb; b++)
-                    if (h->keys[b] == key && h->hDesc[b].srcLen == srcSize && memcmp(h->hSrc + b * h->block, src, srcSize) == 0) break;
+                    if (h->keys[b] == key && (h->size - b * h->block < h->block ? h->size - b * h->block : h->block) == srcSize &&
+                        qzHintSame(h, b, b + 1, p) == 1) break;
                 if (b >= h->nb) continue;
                 rel = b * h->block;
                 e = b + 1;
             }
-            /* the parts that hold these blocks: wait for them (usually long done) */
+            if (same < 0) ok = 0;
+            /* the parts that hold these blocks: wait for this callback's blocks (usually long done) */
             for (pi = 0; pi < h->nParts; pi++) {
                 QZSTD_Part_T *pt = &h->part[pi];
-                if (pt->b1 <= b || pt->b0 >= e) continue;
-                if (pt->st == 1 && pt->flags) {
-                    /* this callback's blocks only; the slot goes back once the part's last block is in */
-                    const size_t w0b = b > pt->b0 ? b : pt->b0, w1b = e < pt->b1 ? e : pt->b1;
-                    const unsigned long w0 = qzNowNs();
-                    if (qzBlocksWait(h, w0b, w1b) != 0) {
-                        qzPartFinish(h, pt); /* (times out again at once: the same block is still pending) -> failed, slot quarantined */
-                    } else {
-                        if (pt->seen < pt->b0) pt->seen = pt->b0;
-                        while (pt->seen < pt->b1 && __atomic_load_n(&h->hCount[pt->seen], __ATOMIC_ACQUIRE) != QZ_COUNT_PENDING) pt->seen++;
-                        if (pt->seen >= pt->b1) qzPartFinish(h, pt);
-                    }
-                    s->hintWaitNs += qzNowNs() - w0;
-                    if (pt->st == 3) ok = 0;
-                    continue;
-                }
+                const size_t w0b = b > pt->b0 ? b : pt->b0, w1b = e < pt->b1 ? e : pt->b1;
+                if (w0b >= w1b) continue;
+                held += w1b - w0b;
                 if (pt->st == 1) {
                     const unsigned long w0 = qzNowNs();
-                    qzPartFinish(h, pt);
+                    (void)qzPartWait(s, pt, w0b, w1b);
                     s->hintWaitNs += qzNowNs() - w0;
                 }
-                if (pt->st != 2) ok = 0;
+                if (pt->st != 1 && pt->st != 2) ok = 0;
             }
+            if (held != e - b) ok = 0;
             if (ok) {
                 const int last = rel + srcSize >= h->size;
                 size_t total = 1, carry = 0, out = 0, bi;
                 int usable = 1;
                 for (bi = b; bi < e; bi++) {
-                    const size_t count = h->hCount[bi];
+                    unsigned int idx;
+                    const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
+                    const size_t count = a ? a->hCount[idx] : QZSTD_HIP_NSEQ_ERROR;
                     if (count == QZSTD_HIP_NSEQ_ERROR || count == 0 || count > h->pitch) { usable = 0; break; }
                     total += count - 1;
                 }
                 if (usable && total < outSeqsCapacity - 1) {
                     for (bi = b; bi < e; bi++) {
+                        unsigned int idx;
+                        const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
+                        const qzstd_hip_block_t *d = &a->hDesc[idx];
+                        const size_t count = a->hCount[idx];
                         const ZSTD_Sequence *q;
-                        const size_t count = h->hCount[bi];
-                        if (h->hDesc[bi].mark & QZSTD_HIP_MARK_COMPACT) {
+                        if (d->mark & QZSTD_HIP_MARK_COMPACT) {
                             /* packed entries (8 bytes, 12-bit tag): unpacked into the caller's array as they are taken */
-                            const unsigned long long *q8 = (const unsigned long long *)(const void *)((const unsigned char *)h->hSeqs + bi * h->pitch * 8u);
+                            const unsigned long long *q8 = (const unsigned long long *)a->hSeqs + d->seqOff * 2u;
                             ZSTD_Sequence dl;
-                            if (qzTakePacked(count > 1 ? outSeqs + out : NULL, q8, count - 1, h->hDesc[bi].mark & 0xFFFu) != 0 ||
-                                qzTakePacked(&dl, q8 + count - 1, 1, h->hDesc[bi].mark & 0xFFFu) != 0) {
+                            if (qzTakePacked(count > 1 ? outSeqs + out : NULL, q8, count - 1, d->mark & 0xFFFu) != 0 ||
+                                qzTakePacked(&dl, q8 + count - 1, 1, d->mark & 0xFFFu) != 0) {
                                 QZ_LOG(1, "announcement: entries of block %zu did not arrive within %d ms of their count\n", bi, gProc.timeoutMs);
                                 usable = 0;
                                 break;
@@ -1615,16 +2121,15 @@ size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, 
                             carry += dl.litLength; /* the block's delimiter: its trailing literals */
                             continue;
                         }
-                        q = h->hSeqs + bi * h->pitch;
+                        q = (const ZSTD_Sequence *)a->hSeqs + d->seqOff;
                         /* completed by its count word: the entries certify themselves one by one (the last one, the delimiter, too) */
-                        if (h->hDesc[bi].mark != 0u && (qzTakeMarked(count > 1 ? outSeqs + out : NULL, q, count - 1, h->hDesc[bi].mark) != 0 ||
-                                                        qzTakeMarked(NULL, q + count - 1, 1, h->hDesc[bi].mark) != 0)) {
+                        if (qzTakeMarked(count > 1 ? outSeqs + out : NULL, q, count - 1, d->mark) != 0 ||
+                            qzTakeMarked(NULL, q + count - 1, 1, d->mark) != 0) {
                             QZ_LOG(1, "announcement: entries of block %zu did not arrive within %d ms of their count\n", bi, gProc.timeoutMs);
                             usable = 0;
                             break;
                         }
                         if (count > 1) {
-                            if (h->hDesc[bi].mark == 0u) memcpy(outSeqs + out, q, (count - 1) * sizeof(ZSTD_Sequence));
                             outSeqs[out].litLength += (unsigned int)carry;
                             out += count - 1;
                             carry = 0;
@@ -1706,24 +2211,7 @@ static void qzStageCopy(unsigned char *dst, const unsigned char *src, size_t n)
     if (i < n) memcpy(dst + i, src + i, n - i);
 }
 
-/* grow-only buffers: returns the (possibly new) pointer, NULL on failure */
-static void *qzGrowHostC(void *old, size_t *cap, size_t need, int dev, int coherent)
-{
-    void *p;
-    if (old && *cap >= need) return old;
-    if (old) memset(old, 0, *cap); /* staged caller data: scrubbed before the pages go back */
-    qzstd_hip_host_free(old);
-    p = qzHostAlloc(need, dev, coherent); /* next to the state's own GPU (the first of the GPUs an announcement is split across) */
-    /* a result area completed by count words: its entries certify themselves by the announcement's epoch, and fresh pinned pages may
-     * hold anything — entries of another announcement's earlier life included, whose epochs count from 1 like everybody's.  Mark 0 is
-     * never valid: the area starts out wiped */
-    if (p && coherent) memset(p, 0, need);
-    *cap = p ? need : 0;
-    return p;
-}
-
-static void *qzGrowHost(void *old, size_t *cap, size_t need, int dev) { return qzGrowHostC(old, cap, need, dev, 0); }
-
+/* grow-only device buffers: returns the (possibly new) pointer, NULL on failure */
 static void *qzGrowDev(int dev, void *old, size_t *cap, size_t need)
 {
     void *p;
@@ -1778,95 +2266,14 @@ void QZSTD_hintStats(void *sequenceProducerState, unsigned long stats[4])
     stats[3] = s ? s->hintWaitNs / 1000 : 0;
 }
 
-/* queue blocks [b0, b1) of announcement h on a slot of device `dev` (any device when dev < 0); 0 on success */
-static int qzLaunchPart(QZSTD_Session_T *s, QZSTD_Hint_T *h, QZSTD_Part_T *pt, size_t b0, size_t b1, int dev, int level,
-                        int mayWait)
-{
-    QZSTD_Slot_T *sl;
-    const size_t o0 = b0 * h->block;
-    const size_t bytes = ((b1 * h->block < h->size ? b1 * h->block : h->size) - o0 + 63) & ~(size_t)63;
-    size_t b;
-    int i, tries, direct = 0;
-    pt->st = 0;
-    for (tries = 0; ; tries++) {
-        /* a state's announcements start their sweep four rows apart from the next state's (a state has up to four in flight): each state
-         * keeps to its own few slots, whose streams then exist after its first announcements (a stream is created at a slot's first use:
-         * with sweeps that all start in the same corner the slots in use kept drifting and streams were still being created ten passes in) */
-        const int nd = gProc.numDevices, rows = gProc.numSlots / (nd > 0 ? nd : 1);
-        const int row = rows > 0 ? ((s->slotHint / nd) * QZ_HINTS) % rows : 0;
-        i = qzTryGrabSlot(row * nd + s->slotHint % nd + tries * nd, dev);
-        if (i < 0 && mayWait) {
-            /* every slot is busy: give back what this state still holds, then wait for one */
-            int k, j;
-            for (k = 0; k < QZ_HINTS; k++)
-                for (j = 0; j < s->hint[k].nParts; j++)
-                    if (&s->hint[k] != h) qzPartFinish(&s->hint[k], &s->hint[k].part[j]);
-            i = qzGrabSlot(s->slotHint, dev);
-        }
-        if (i < 0) return -1;
-        sl = &gProc.slots[i];
-        if (!(sl->stream && qzStillStuck(sl->device, sl->stream, &sl->stuck))) break;
-        qzReleaseSlot(i); /* quarantined after a time-out: try another one */
-        if (tries >= 8) return -1;
-    }
-    if (dev < 0) s->slotHint = i;
-    if (qzSetupSlot(sl, 0) != QZSTD_OK) goto fail;
-    {
-        const size_t work = qzstd_hip_workspace_bytes(level, (unsigned int)(b1 - b0), (unsigned int)h->block);
-        if (work) sl->dBatchWork = qzGrowDev(sl->device, sl->dBatchWork, &sl->dBatchWorkCap, work);
-        if (work && !sl->dBatchWork) goto fail;
-        /* (A/B switch, see hintDirect) */
-        direct = h->dvSrc != NULL && (gProc.hintDirect == 1 || (gProc.hintDirect == 2 && work == 0));
-    }
-    if (!direct) {
-        sl->dBatchSrc = (unsigned char *)qzGrowDev(sl->device, sl->dBatchSrc, &sl->dBatchSrcCap, bytes);
-        if (!sl->dBatchSrc) goto fail;
-    }
-    for (b = b0; b < b1; b++) h->hDesc[b].srcOff = b * h->block - o0; /* relative to this part's first byte */
-    /* everything below is queued on the slot's stream */
-    if (!direct) {
-        const unsigned long t0 = qzNowNs();
-        /* the staging copy goes to device memory by a copy kernel on the stream (qzstd_hip_copy_in says why not by the runtime's copy) */
-        const int rc = h->dvSrc && gProc.hintDirect != 3 ? qzstd_hip_copy_in(sl->device, sl->stream, sl->dBatchSrc, (const unsigned char *)h->dvSrc + o0, bytes)
-                                                         : qzstd_hip_memcpy_h2d(sl->device, sl->stream, sl->dBatchSrc, h->hSrc + o0, bytes);
-        s->hintCopyCallNs += qzNowNs() - t0;
-        if (rc) { if (qzWait(sl->device, sl->stream) == 1) sl->stuck = 1; goto fail; }
-    }
-    {
-        const unsigned char *dsrc = direct ? (const unsigned char *)h->dvSrc + o0 : sl->dBatchSrc;
-        const unsigned long t0 = qzNowNs();
-        const int rc = qzstd_hip_find_sequences(sl->device, sl->stream, level, dsrc, (const qzstd_hip_block_t *)h->dvDesc + b0,
-                                                (unsigned int)(b1 - b0), (unsigned int)h->block, h->dvSeqs, (unsigned int *)h->dvCount + b0,
-                                                sl->dBatchWork, sl->dBatchWorkCap);
-        s->hintLaunchCallNs += qzNowNs() - t0;
-        if (rc) {
-            if (qzWait(sl->device, sl->stream) == 1) sl->stuck = 1;
-            goto fail;
-        }
-    }
-    __atomic_fetch_add(&gProc.devBlocks[sl->device][0], (unsigned long)(b1 - b0), __ATOMIC_RELAXED);
-    pt->st = 1; /* in flight; the slot stays ours until qzPartFinish() */
-    pt->slot = i;
-    pt->b0 = b0;
-    pt->b1 = b1;
-    pt->seen = b0;
-    pt->flags = gProc.hintFlags;
-    return 0;
-fail:
-    for (b = b0; b < b1; b++) h->hCount[b] = QZSTD_HIP_NSEQ_ERROR; /* never launched: nothing will publish these */
-    QZ_LOG(1, "announcement not queued: %s\n", qzstd_hip_last_error());
-    qzReleaseSlot(i);
-    return -1;
-}
-
-/* Stage a buffer, queue its match-finding and remember it in *h (asynchronous, see QZSTD_hintSource).  The blocks
- * are split into contiguous ranges, one per GPU (reference analogue: instances interleaved across devices,
- * src/qatseqprod.c:601-630), each on its own slot and stream; the results land in the announcement's pinned buffers.
- * Returns the bytes announced, 0 if none. */
+/* Stage a buffer into the announcement batchers and remember it in *h (asynchronous, see QZSTD_hintSource).  The blocks are split
+ * into contiguous ranges, one per GPU (reference analogue: instances interleaved across devices, src/qatseqprod.c:601-630), each
+ * staged into its GPU's open batch area and launched with whatever else that batch collects; the results land in the area's pinned
+ * buffers.  Returns the bytes announced, 0 if none. */
 static size_t qzAnnounce(QZSTD_Session_T *s, QZSTD_Hint_T *h, const void *src, size_t srcSize, size_t blockSize,
                          int compressionLevel, int stable)
 {
-    size_t nb, blocksBytes, srcBytes;
+    size_t nb;
     unsigned long tq, tp;
     int parts, k, firstDev;
 
@@ -1878,70 +2285,22 @@ static size_t qzAnnounce(QZSTD_Session_T *s, QZSTD_Hint_T *h, const void *src, s
     /* a fine grid means many blocks: the result area is sized by what a block of that size can produce at most */
     h->pitch = qzstd_hip_sequence_bound(blockSize) < QZ_HINT_PITCH ? qzstd_hip_sequence_bound(blockSize) : QZ_HINT_PITCH;
     h->pitch = (h->pitch + 1u) & ~(size_t)1; /* (even: a block's region of packed entries is pitch / 2 sixteen-byte units long) */
-    blocksBytes = nb * sizeof(qzstd_hip_block_t);
-    srcBytes = (srcSize + 63) & ~(size_t)63;
 
     if (s->slotHint < 0) s->slotHint = qzPickHint(); /* the state's own GPU: sticky from its first use */
     firstDev = s->slotHint % gProc.numDevices;
     tp = qzNowNs();
-    h->hSrc = (unsigned char *)qzGrowHost(h->hSrc, &h->hSrcCap, srcBytes, firstDev);
-    h->hDesc = (qzstd_hip_block_t *)qzGrowHost(h->hDesc, &h->hDescCap, blocksBytes, firstDev);
-    h->hCount = (unsigned int *)qzGrowHostC(h->hCount, &h->hCountCap, nb * sizeof(unsigned int), firstDev, gProc.hintFlags);
-    h->hSeqs = (ZSTD_Sequence *)qzGrowHostC(h->hSeqs, &h->hSeqsCap, nb * h->pitch * (gProc.hintCompact ? 8u : sizeof(ZSTD_Sequence)), firstDev, gProc.hintFlags); /* (packed entries: 8 bytes) */
-    if (!h->hSrc || !h->hDesc || !h->hCount || !h->hSeqs) return 0;
-    if (h->dvOf[0] != h->hDesc || !h->dvDesc) { h->dvDesc = qzstd_hip_host_device_ptr(h->hDesc); h->dvOf[0] = h->hDesc; }
-    if (h->dvOf[1] != h->hCount || !h->dvCount) { h->dvCount = qzstd_hip_host_device_ptr(h->hCount); h->dvOf[1] = h->hCount; }
-    if (h->dvOf[2] != h->hSeqs || !h->dvSeqs) { h->dvSeqs = qzstd_hip_host_device_ptr(h->hSeqs); h->dvOf[2] = h->hSeqs; }
-    if (h->dvOf[3] != h->hSrc || !h->dvSrc) { h->dvSrc = qzstd_hip_host_device_ptr(h->hSrc); h->dvOf[3] = h->hSrc; }
-    if (!h->dvDesc || !h->dvCount || !h->dvSeqs) return 0;
+    if (nb <= QZ_CONTENT_LOOKUP_BLOCKS && h->keysCap < nb) {
+        free(h->keys);
+        h->keys = (unsigned long long *)malloc(nb * sizeof(*h->keys));
+        h->keysCap = h->keys ? nb : 0;
+    }
     s->hintPrepNs += qzNowNs() - tp;
-
-    tq = qzNowNs();
-    /* pinned staging (reference: the staging memcpy, :1222-1227).  Streaming stores where the host will not read the copy back: a verified
-     * announcement compares every callback's block with it (measured with the copy streamed out: -2 ... -4 %), a STABLE one only samples (+1.5 %) */
-    if (stable) qzStageCopy(h->hSrc, (const unsigned char *)src, srcSize);
-    else memcpy(h->hSrc, src, srcSize);
-    s->hintStageNs += qzNowNs() - tq;
     tq = qzNowNs();
     h->base = (const unsigned char *)src;
     h->size = srcSize;
     h->block = blockSize;
     h->level = compressionLevel;
     h->nb = nb;
-    h->epoch = (h->epoch + 1u) & (gProc.hintCompact ? 0xFFFu : 0xFFFFFFu);
-    if (h->packedLast != gProc.hintCompact) { h->epoch = 0u; h->packedLast = gProc.hintCompact; } /* (entries of the other form mean nothing as marks) */
-    if (h->epoch == 0u) {
-        /* the epoch (24 bits; 12 as the tag of packed entries) starts over: an entry that no announcement of the last lap overwrote would show a
-         * mark that is valid again.  Nothing of this announcement's buffers is in flight here (qzHintDrop above): wipe the result area once per
-         * lap (packed: 2 MiB every 4 095 announcements) */
-        memset(h->hSeqs, 0, h->hSeqsCap);
-        h->epoch = 1u;
-    }
-    if (nb <= QZ_CONTENT_LOOKUP_BLOCKS) {
-        if (h->keysCap < nb) {
-            free(h->keys);
-            h->keys = (unsigned long long *)malloc(nb * sizeof(*h->keys));
-            h->keysCap = h->keys ? nb : 0;
-        }
-    }
-    {
-        /* descriptors of every block (also of ranges that cannot be queued: the callbacks' grid arithmetic reads them).
-         * Results go straight into the pinned buffer, QZ_HINT_PITCH entries per block: a block with more sequences
-         * reports an error and is redone by the per-block path when its callback comes */
-        size_t b;
-        for (b = 0; b < nb; b++) {
-            const size_t o = b * blockSize;
-            h->hDesc[b].srcOff = o;
-            h->hDesc[b].seqOff = gProc.hintCompact ? b * (h->pitch / 2u) : b * h->pitch; /* (sixteen-byte units) */
-            h->hDesc[b].srcLen = (unsigned int)(srcSize - o < blockSize ? srcSize - o : blockSize);
-            h->hDesc[b].seqCap = (unsigned int)h->pitch;
-            h->hDesc[b].parseFrom = 0;
-            h->hDesc[b].mark = gProc.hintFlags ? (gProc.hintCompact ? (h->epoch | QZSTD_HIP_MARK_COMPACT) : h->epoch) : 0u; /* (count-word completion: every entry certifies itself, see qzTakeMarked) */
-            h->hCount[b] = gProc.hintFlags ? QZ_COUNT_PENDING : QZSTD_HIP_NSEQ_ERROR; /* until a kernel says otherwise */
-            if (h->keys && nb <= h->keysCap && nb <= QZ_CONTENT_LOOKUP_BLOCKS)
-                h->keys[b] = h->hDesc[b].srcLen >= 16 ? qzBlockKey(h->hSrc + o, h->hDesc[b].srcLen) : 0ull;
-        }
-    }
     /* contiguous block ranges, one per GPU, starting at this state's own GPU; a range is worth a launch from 4 blocks */
     parts = gProc.split;
     if ((size_t)parts > nb / 4) parts = nb / 4 ? (int)(nb / 4) : 1;
@@ -1949,13 +2308,7 @@ static size_t qzAnnounce(QZSTD_Session_T *s, QZSTD_Hint_T *h, const void *src, s
     for (k = 0; k < parts; k++) {
         const size_t b0 = nb * (size_t)k / (size_t)parts, b1 = nb * (size_t)(k + 1) / (size_t)parts;
         const int dev = parts > 1 ? (firstDev + k) % gProc.numDevices : firstDev;
-        if (qzLaunchPart(s, h, &h->part[h->nParts], b0, b1, dev, compressionLevel | gProc.levelFlags, 1) != 0) {
-            /* that range could not be queued: its callbacks take the per-block path */
-            h->part[h->nParts].st = 3;
-            h->part[h->nParts].b0 = b0;
-            h->part[h->nParts].b1 = b1;
-        }
-        h->nParts++;
+        qzBatchAdd(s, h, dev, b0, b1, (const unsigned char *)src, compressionLevel | gProc.levelFlags, stable);
     }
     h->st = 1;
     h->touched = 0;
@@ -1963,7 +2316,7 @@ static size_t qzAnnounce(QZSTD_Session_T *s, QZSTD_Hint_T *h, const void *src, s
     h->stable = 0;
     h->servedUpTo = 0;
     h->seq = ++s->hintSeq;
-    s->hintQueueNs += qzNowNs() - tq;
+    s->hintStageNs += qzNowNs() - tq; /* (staging and queueing are one step now: an announcer stages straight into its batch) */
     return srcSize;
 }
 
@@ -2017,7 +2370,7 @@ int QZSTD_hintSourceEx(void *sequenceProducerState, const void *src, size_t srcS
     h->noAddr = 0;
     s->hintCalls++;
     if (s->hintCalls == 8) /* the event log's timers: steady state only (the first announcements allocate pinned buffers and create streams) */
-        s->hintStageNs = s->hintQueueNs = s->hintWaitNs = s->hintCopyCallNs = s->hintLaunchCallNs = s->hintPrepNs = s->hintDropNs = 0;
+        s->hintStageNs = s->hintWaitNs = s->hintCopyCallNs = s->hintLaunchCallNs = s->hintPrepNs = s->hintDropNs = 0;
     return 0;
 }
 

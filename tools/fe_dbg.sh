@@ -11,8 +11,6 @@ run() { echo "== seg ${SEG:-4} threads ${T:-16} L${LV:-1} ${BUF:-} $*"; env "$@"
 if [ $# -gt 0 ]; then for CFG in "$@"; do eval "$CFG"; done; exit 0; fi
 SEG=2 run QZSTD_FRONT_AHEAD=2
 SEG=2 run QZSTD_FRONT_AHEAD=2 QZSTD_HIP_HINT_DIRECT=0
-SEG=2 run QZSTD_FRONT_AHEAD=2 QZSTD_HIP_HINT_FLAGS=0
-SEG=2 run QZSTD_FRONT_AHEAD=2 QZSTD_HIP_HINT_FLAGS=0 QZSTD_HIP_HINT_DIRECT=0
 ROWS=3
 SEG=4 run QZSTD_FRONT_AHEAD=1
 SEG=4 run QZSTD_FRONT_AHEAD=2
