@@ -25,6 +25,9 @@
  *     :88, :1140-1152
  *
  * No QAT / icp_sal / cpa symbol is used or emulated.
+ *
+ * Sections, each using only what stands above it: types, helpers, take / join, slots, coalescer, service, announcement batcher,
+ * announcements, lifecycle, producer (guards -> serve from an announcement -> service -> coalescer -> slot).
  */
 #ifndef _GNU_SOURCE
 #define _GNU_SOURCE /* SYS_getcpu, sched_getaffinity */
@@ -342,11 +345,8 @@ typedef struct {
 } QZSTD_Session_T;
 
 #define QZ_HINT_STALE_MISSES 16u /* an announcement that was used and then missed this often is dropped */
-static void qzReapOrphans(int force);
-static void qzFreeBatcher(QZSTD_Batcher_T *bt);
-static size_t qzFailed(QZSTD_Session_T *s, int cause);
-static void *qzGrowDev(int dev, void *old, size_t *cap, size_t need);
-static int qzUsableCores(void);
+
+/* ---------------------------------------------------------------- helpers -------- */
 
 /* cheap fingerprint of a block: its size and its first and last 8 bytes (a candidate is always verified with memcmp) */
 static unsigned long long qzBlockKey(const unsigned char *p, size_t n)
@@ -369,6 +369,43 @@ static unsigned long qzNowNs(void)
     return (unsigned long)ts.tv_sec * 1000000000ul + (unsigned long)ts.tv_nsec;
 }
 
+static int qzEnvInt(const char *name, int dflt, int lo, int hi)
+{
+    const char *v = getenv(name);
+    long x;
+    if (!v || !*v) return dflt;
+    x = strtol(v, NULL, 10);
+    if (x < lo) x = lo;
+    if (x > hi) x = hi;
+    return (int)x;
+}
+
+/* the cores this process may use: its affinity mask, capped by a cgroup CPU quota (cpu.max) */
+static int qzUsableCores(void)
+{
+    static int cached; /* written once with the same value by whoever gets here first (QZSTD_startQatDevice does, under the process mutex) */
+    int n = 0;
+    cpu_set_t set;
+    FILE *f;
+    if ((n = __atomic_load_n(&cached, __ATOMIC_RELAXED)) != 0) return n;
+    n = 0;
+    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);
+    if (n <= 0) n = (int)sysconf(_SC_NPROCESSORS_ONLN);
+    f = fopen("/sys/fs/cgroup/cpu.max", "re");
+    if (f) {
+        char q[32] = "";
+        long per = 0;
+        if (fscanf(f, "%31s %ld", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) {
+            const long quota = (atol(q) + per - 1) / per;
+            if (quota > 0 && quota < n) n = (int)quota;
+        }
+        fclose(f);
+    }
+    n = n > 0 ? n : 1;
+    __atomic_store_n(&cached, n, __ATOMIC_RELAXED);
+    return n;
+}
+
 /* Bounded wait for a stream (reference: the polling loop with its 2 s limit, src/qatseqprod.c:1261-1285).
  * 0 = everything queued on the stream is done, 1 = timed out (the work is still running: the caller must not touch
  * the buffers involved and marks their owner as stuck), -1 = the runtime reported an error. */
@@ -378,6 +415,14 @@ static int qzWait(int dev, void *stream)
     if (r == 1) { qzCause = QZ_CAUSE_TIMEOUT; QZ_LOG(1, "device %d: request timed out after %d ms\n", dev, gProc.timeoutMs); }
     if (r < 0) { qzCause = QZ_CAUSE_RUNTIME; QZ_LOG(1, "device %d: %s\n", dev, qzstd_hip_last_error()); }
     return r;
+}
+
+/* the same for a wait whose time-out quarantines the stream's owner: *stuck is set, the owner is not reused until the stream drains */
+static int qzWaitOrQuarantine(int dev, void *stream, int *stuck)
+{
+    const int w = qzWait(dev, stream);
+    if (w == 1) *stuck = 1;
+    return w;
 }
 
 /* A stream that timed out is quarantined; it becomes usable again once a non-blocking query finds it drained. */
@@ -392,32 +437,65 @@ static int qzStillStuck(int dev, void *stream, int *stuck)
     return 1;
 }
 
-/* ---------------------------------------------------------------- slots ---------- */
-
-static void qzFreeSlot(QZSTD_Slot_T *s)
+/* grow-only device buffers: returns the (possibly new) pointer, NULL on failure */
+static void *qzGrowDev(int dev, void *old, size_t *cap, size_t need)
 {
-    if (s->stream) (void)qzstd_hip_stream_wait(s->device, s->stream, (unsigned)gProc.timeoutMs);
-    qzstd_hip_host_free(s->hSrc);
-    qzstd_hip_host_free(s->hSeqs);
-    qzstd_hip_host_free(s->hDesc);
-    qzstd_hip_host_free(s->hCount);
-    qzstd_hip_free(s->device, s->dSrc);
-    qzstd_hip_free(s->device, s->dSeqs);
-    qzstd_hip_free(s->device, s->dDesc);
-    qzstd_hip_free(s->device, s->dCount);
-    qzstd_hip_free(s->device, s->dWork);
-    if (s->vSrc) memset(s->vSrc, 0, QZSTD_HIP_BLOCK_MAX + 64); /* staged caller data: scrubbed before the pages go back */
-    qzstd_hip_host_free(s->vSrc);
-    qzstd_hip_host_free(s->vSeqs);
-    qzstd_hip_host_free(s->vCount);
-    qzstd_hip_free(s->device, s->vdSrc);
-    qzstd_hip_free(s->device, s->vdWork);
-    if (s->stream) qzstd_hip_stream_destroy(s->device, s->stream);
-    {
-        const int dev = s->device;
-        memset(s, 0, sizeof(*s));
-        s->device = dev;
+    void *p;
+    if (old && *cap >= need) return old;
+    qzstd_hip_free(dev, old);
+    p = qzstd_hip_malloc(dev, need);
+    *cap = p ? need : 0;
+    return p;
+}
+
+/* free and forget: a pinned buffer, a device buffer (NULL: nothing to free) */
+#define QZ_HOST_FREE(p) do { qzstd_hip_host_free(p); (p) = NULL; } while (0)
+#define QZ_DEV_FREE(dev, p) do { qzstd_hip_free(dev, p); (p) = NULL; } while (0)
+
+/* The staging copy of an announcement (reference: the memcpy into DMA memory, :1222-1227): caller's bytes -> pinned buffer the GPU reads over the
+ * bus.  For a STABLE announcement nobody on the host reads the copy again soon (a sampled memcmp at most), so it goes out with STREAMING stores: no
+ * read-for-ownership of the destination lines and no 2 MiB of a thread's cache spent on bytes only the GPU wants — with 16 threads staging at
+ * once the copies share the socket's memory bandwidth, a third of which the ordinary stores' line fills took.  QZSTD_HIP_STAGE_NT=0: memcpy. */
+static void qzStageCopy(unsigned char *dst, const unsigned char *src, size_t n)
+{
+    size_t i = 0;
+    if (!gProc.stageNt || n < 4096 || ((uintptr_t)dst & 15u)) { memcpy(dst, src, n); return; }
+    for (; i + 64 <= n; i += 64) {
+        const __m128i a = _mm_loadu_si128((const __m128i *)(const void *)(src + i)), b = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 16)),
+                      c = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 32)), d = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 48));
+        _mm_stream_si128((__m128i *)(void *)(dst + i), a);
+        _mm_stream_si128((__m128i *)(void *)(dst + i + 16), b);
+        _mm_stream_si128((__m128i *)(void *)(dst + i + 32), c);
+        _mm_stream_si128((__m128i *)(void *)(dst + i + 48), d);
     }
+    _mm_sfence(); /* streaming stores are weakly ordered: before anything that tells the GPU the bytes are there */
+    if (i < n) memcpy(dst + i, src + i, n - i);
+}
+
+/* shared by the producer and the hint: is the device usable?  Counts failures and
+ * re-probes every QZ_RETRY_INTERVAL_BLOCKS-th block (reference :1140-1152). */
+static int qzDeviceUsable(QZSTD_Session_T *s)
+{
+    if (gProc.status == QZSTD_OK) return 1;
+    s->failOffloadCnt++;
+    if (s->failOffloadCnt >= QZ_RETRY_INTERVAL_BLOCKS) {
+        s->failOffloadCnt = 0;
+        if (QZSTD_startQatDevice() == QZSTD_OK) return 1;
+        QZ_LOG(1, "tried to restart the device, but failed\n");
+        return 0;
+    }
+    QZ_LOG(1, "the device was not successfully started\n");
+    return 0;
+}
+
+/* a callback is about to return the error code: count it by cause (QZSTD_failStats) */
+static size_t qzFailed(QZSTD_Session_T *s, int cause)
+{
+    if (s) {
+        s->fail[0]++;
+        s->fail[cause > 0 && cause < QZ_CAUSE_N ? cause : QZ_CAUSE_RUNTIME]++;
+    }
+    return ZSTD_SEQUENCE_PRODUCER_ERROR;
 }
 
 /* ---- NUMA placement ---- */
@@ -457,6 +535,136 @@ static int qzPickHint(void)
         }
     }
     return (int)(__sync_fetch_and_add(&gProc.anyNext, 1u) & 0x3FFFFFFFu);
+}
+
+/* ---------------------------------------------------------------- take / join ---- */
+
+/* A result area is completed by count words: the count says how many entries there are, not that they have all arrived — they are stored
+ * by other waves than the count and nothing orders them on their ways to host memory (measured in round 3 on the resident service: under
+ * load an item's last entries land up to microseconds after its count).  So every entry certifies ITSELF: it is ONE store that carries
+ * its request's epoch or its area's tag (qzstd_hip_block_t.mark) and is taken when it shows it, by one of the two takers below.  Their
+ * time-out counts from t0 (the service: its submit time) or, t0 == 0, from the first late entry (announcements).  One more round: */
+static inline int qzSpinExpired(unsigned *spins, unsigned long t0)
+{
+    __builtin_ia32_pause();
+    __asm__ volatile("" ::: "memory"); /* (a fresh load every time round) */
+    return (++*spins & 1023u) == 0u && qzNowNs() - t0 > (unsigned long)gProc.timeoutMs * 1000000ul;
+}
+
+/* Takes n 16-byte entries: one aligned load per entry (it arrived as one store), taken when its fourth word shows the epoch; the mark is
+ * masked out of the copy (the pinned area keeps it: marks of an earlier lap are wiped when the epoch or tag starts over).  *covered +=
+ * the literal and match lengths of the entries taken, added up in the same pass.  0 = taken, 1 = not within the time-out. */
+static int qzTakeMarked(ZSTD_Sequence *dst, const ZSTD_Sequence *q, size_t n, unsigned int epoch, unsigned long t0, size_t *covered)
+{
+    const __m128i keep = _mm_set_epi32(0, -1, -1, -1);
+    __m128i acc = _mm_setzero_si128();
+    size_t j;
+    for (j = 0; j < n; j++) {
+        __m128i v;
+        unsigned spins = 0;
+        while (v = _mm_load_si128((const __m128i *)(const void *)(q + j)), (unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(v, 12)) != epoch) {
+            if (!t0) t0 = qzNowNs(); /* not there yet: rare */
+            if (qzSpinExpired(&spins, t0)) return 1;
+        }
+        _mm_storeu_si128((__m128i *)(void *)(dst + j), _mm_and_si128(v, keep));
+        acc = _mm_add_epi32(acc, v); /* literal and match lengths add up in lanes 1 and 2 (a block is 128 KiB at most) */
+    }
+    *covered += (size_t)(unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(acc, 4)) + (unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(acc, 8));
+    return 0;
+}
+
+/* The same for PACKED entries (qzstd_hip.h: QZSTD_HIP_MARK_COMPACT): one 8-byte load per entry (it arrived as one store), taken when its top 12
+ * bits show the tag, unpacked into the caller's ZSTD_Sequence array. */
+static int qzTakePacked(ZSTD_Sequence *dst, const unsigned long long *q, size_t n, unsigned int tag, unsigned long t0)
+{
+    const __m128i m17 = _mm_set_epi32(0, 0x1FFFF, 0, 0x1FFFF), m18 = _mm_set_epi32(0, 0x3FFFF, 0, 0x3FFFF);
+    size_t j = 0;
+    while (j < n) {
+        if (j + 2 <= n && !((uintptr_t)(q + j) & 15u)) { /* two entries per step: the usual case, both there (an ALIGNED 16-byte load: each
+                                                           * 8-byte half is one of the kernel's stores, never torn) */
+            const __m128i v = _mm_load_si128((const __m128i *)(const void *)(q + j));
+            const __m128i t = _mm_srli_epi64(v, 52);
+            if ((unsigned int)_mm_cvtsi128_si32(t) == tag && (unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(t, 8)) == tag) {
+                const __m128i ol = _mm_or_si128(_mm_and_si128(v, m17), _mm_slli_epi64(_mm_and_si128(_mm_srli_epi64(v, 17), m18), 32)); /* off0 lit0 off1 lit1 */
+                const __m128i ml = _mm_and_si128(_mm_srli_epi64(v, 35), m17);                                                          /* ml0  0    ml1  0    */
+                _mm_storeu_si128((__m128i *)(void *)(dst + j), _mm_unpacklo_epi64(ol, ml));
+                _mm_storeu_si128((__m128i *)(void *)(dst + j + 1), _mm_unpackhi_epi64(ol, ml));
+                j += 2;
+                continue;
+            }
+        }
+        {
+            unsigned long long v;
+            unsigned spins = 0;
+            while (v = __atomic_load_n(&q[j], __ATOMIC_RELAXED), QZSTD_HIP_PACKED_TAG(v) != tag) {
+                if (!t0) t0 = qzNowNs(); /* not there yet: rare */
+                if (qzSpinExpired(&spins, t0)) return 1;
+            }
+            dst[j].offset = QZSTD_HIP_PACKED_OFF(v);
+            dst[j].litLength = QZSTD_HIP_PACKED_LIT(v);
+            dst[j].matchLength = QZSTD_HIP_PACKED_ML(v);
+            dst[j].rep = 0;
+            j++;
+        }
+    }
+    return 0;
+}
+
+/* Joining independently parsed lists — segments of a batched block, items of a service request, announced grid blocks.  Every piece is
+ * count >= 1 entries, the last one its delimiter {0, trailing literals, 0, 0}: all but the delimiter are copied, the pending trailing
+ * literals go to the first copied entry, the delimiter's are carried on (a delimiter-only piece only adds to the carry); one delimiter
+ * closes the list.  The caller applies its capacity rule BEFORE it appends a piece.  covered: literal + match lengths of the 16-byte
+ * entries taken, delimiters included (the service's adds-up check). */
+typedef struct { ZSTD_Sequence *dst; size_t out, carry, covered; } QZSTD_Join_T;
+
+/* Appends one piece in the form its descriptor's mark names: 0 = complete in ordinary memory (a launch's results after the stream wait);
+ * QZSTD_HIP_MARK_COMPACT | tag = packed entries; else 16-byte entries that show the mark (an epoch or tag of at most 24 bits: bit 31 is
+ * never set in one).  Marked and packed entries are taken as they certify themselves, the delimiter too; 1 = not within the time-out. */
+static int qzJoinPiece(QZSTD_Join_T *j, const void *q, size_t count, unsigned int mark, unsigned long t0)
+{
+    ZSTD_Sequence *dst = j->dst + j->out, dl;
+    const size_t carry = j->carry;
+    if (mark == 0u) {
+        memcpy(dst, q, (count - 1) * sizeof(ZSTD_Sequence));
+        dl = ((const ZSTD_Sequence *)q)[count - 1];
+    } else if (mark & QZSTD_HIP_MARK_COMPACT) {
+        const unsigned long long *q8 = (const unsigned long long *)q;
+        if (qzTakePacked(dst, q8, count - 1, mark & 0xFFFu, t0) != 0 || qzTakePacked(&dl, q8 + count - 1, 1, mark & 0xFFFu, t0) != 0) return 1;
+    } else {
+        const ZSTD_Sequence *q16 = (const ZSTD_Sequence *)q;
+        if (qzTakeMarked(dst, q16, count - 1, mark, t0, &j->covered) != 0 || qzTakeMarked(&dl, q16 + count - 1, 1, mark, t0, &j->covered) != 0) return 1;
+    }
+    if (count > 1) {
+        dst->litLength += (unsigned int)carry;
+        j->out += count - 1;
+        j->carry = 0;
+    }
+    j->carry += dl.litLength;
+    return 0;
+}
+
+/* closes the joined list with its delimiter; returns the sequence count */
+static size_t qzJoinFinish(QZSTD_Join_T *j)
+{
+    j->dst[j->out].offset = 0; j->dst[j->out].litLength = (unsigned int)j->carry;
+    j->dst[j->out].matchLength = 0; j->dst[j->out].rep = 0;
+    return ++j->out;
+}
+
+/* ---------------------------------------------------------------- slots ---------- */
+
+static void qzFreeSlot(QZSTD_Slot_T *s)
+{
+    const int dev = s->device;
+    if (s->stream) (void)qzstd_hip_stream_wait(dev, s->stream, (unsigned)gProc.timeoutMs);
+    if (s->vSrc) memset(s->vSrc, 0, QZSTD_HIP_BLOCK_MAX + 64); /* staged caller data: scrubbed before the pages go back */
+    QZ_HOST_FREE(s->hSrc); QZ_HOST_FREE(s->hSeqs); QZ_HOST_FREE(s->hDesc); QZ_HOST_FREE(s->hCount);
+    QZ_HOST_FREE(s->vSrc); QZ_HOST_FREE(s->vSeqs); QZ_HOST_FREE(s->vCount);
+    QZ_DEV_FREE(dev, s->dSrc); QZ_DEV_FREE(dev, s->dSeqs); QZ_DEV_FREE(dev, s->dDesc); QZ_DEV_FREE(dev, s->dCount); QZ_DEV_FREE(dev, s->dWork);
+    QZ_DEV_FREE(dev, s->vdSrc); QZ_DEV_FREE(dev, s->vdWork);
+    if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
+    memset(s, 0, sizeof(*s));
+    s->device = dev;
 }
 
 /* lazy per-slot setup, first use only (reference: QZSTD_allocInstMem, :685-822) */
@@ -530,21 +738,89 @@ static void qzReleaseSlot(int i)
     __sync_lock_release(&gProc.slots[i].lock);
 }
 
+/* one block, synchronously, on a slot */
+static size_t qzRunBlock(QZSTD_Slot_T *sl, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
+                         size_t srcSize, int level)
+{
+    const size_t cap = outSeqsCapacity < sl->seqCap ? outSeqsCapacity : sl->seqCap;
+    size_t first, count;
+    memcpy(sl->hSrc, src, srcSize); /* staging copy, reference :1223 */
+    sl->hDesc->srcOff = 0;
+    sl->hDesc->seqOff = 0;
+    sl->hDesc->srcLen = (unsigned int)srcSize;
+    sl->hDesc->seqCap = (unsigned int)cap;
+    sl->hDesc->parseFrom = 0;
+    sl->hDesc->mark = 0;
+    {
+        const size_t work = qzstd_hip_workspace_bytes(level, 1, (unsigned int)srcSize);
+        if (work) sl->dWork = qzGrowDev(sl->device, sl->dWork, &sl->dWorkCap, work);
+        if (work && !sl->dWork) goto fail;
+    }
+    if (qzstd_hip_memcpy_h2d(sl->device, sl->stream, sl->dSrc, sl->hSrc, (srcSize + 15) & ~(size_t)15) ||
+        qzstd_hip_memcpy_h2d(sl->device, sl->stream, sl->dDesc, sl->hDesc, sizeof(*sl->hDesc)) ||
+        qzstd_hip_find_sequences(sl->device, sl->stream, level, sl->dSrc, sl->dDesc, 1, (unsigned int)srcSize,
+                                 sl->dSeqs, sl->dCount, sl->dWork, sl->dWorkCap))
+        goto fail;
+    first = cap < QZ_FIRST_COPY_SEQS ? cap : QZ_FIRST_COPY_SEQS;
+    if (qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hCount, sl->dCount, sizeof(unsigned int)) ||
+        qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hSeqs, sl->dSeqs, first * sizeof(ZSTD_Sequence)))
+        goto fail;
+    if (qzWaitOrQuarantine(sl->device, sl->stream, &sl->stuck) != 0) goto fail;
+    count = *sl->hCount;
+    if (count == QZSTD_HIP_NSEQ_ERROR || count == 0 || count >= outSeqsCapacity - 1) {
+        QZ_LOG(1, "sequence count %zu does not fit capacity %zu\n", count, outSeqsCapacity);
+        qzCause = QZ_CAUSE_CAPACITY;
+        return ZSTD_SEQUENCE_PRODUCER_ERROR; /* reference :1318-1322 */
+    }
+    if (count > first) {
+        if (qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hSeqs + first, sl->dSeqs + first,
+                                 (count - first) * sizeof(ZSTD_Sequence)))
+            goto fail;
+        if (qzWaitOrQuarantine(sl->device, sl->stream, &sl->stuck) != 0) goto fail;
+    }
+    memcpy(outSeqs, sl->hSeqs, count * sizeof(ZSTD_Sequence));
+    return count;
+fail:
+    QZ_LOG(1, "device request failed: %s\n", qzstd_hip_last_error());
+    return ZSTD_SEQUENCE_PRODUCER_ERROR;
+}
+
+/* one block on a slot of its own (QZSTD_HIP_COALESCE=0, and blocks too dense for a batch) */
+static size_t qzSlotBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
+                          size_t srcSize, int level)
+{
+    size_t rc = ZSTD_SEQUENCE_PRODUCER_ERROR;
+    int tries;
+    for (tries = 0; tries < 4; tries++) {
+        const int i = qzGrabSlot(s->slotHint + tries * gProc.numDevices, dev);
+        QZSTD_Slot_T *sl;
+        if (i < 0) {
+            QZ_LOG(1, "failed to grab a slot\n");
+            return ZSTD_SEQUENCE_PRODUCER_ERROR;
+        }
+        sl = &gProc.slots[i];
+        if (sl->stream && qzStillStuck(sl->device, sl->stream, &sl->stuck)) { /* quarantined: try the next one */
+            qzReleaseSlot(i);
+            continue;
+        }
+        if (dev < 0) s->slotHint = i;
+        if (qzSetupSlot(sl) == QZSTD_OK) rc = qzRunBlock(sl, outSeqs, outSeqsCapacity, src, srcSize, level);
+        QZ_LOG(2, "block %zu B level %d -> %zu sequences (slot %d, device %d)\n", srcSize, level & 0xFF, rc, i, sl->device);
+        qzReleaseSlot(i);
+        return rc;
+    }
+    return rc;
+}
+
 /* ---------------------------------------------------------------- coalescer ------ */
 
 static void qzFreeBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
 {
     if (bt->stream) (void)qzstd_hip_stream_wait(c->device, bt->stream, (unsigned)gProc.timeoutMs);
-    qzstd_hip_host_free(bt->hSrc);
-    qzstd_hip_host_free(bt->hSeqs);
-    qzstd_hip_host_free(bt->hDesc);
-    qzstd_hip_host_free(bt->hCount);
-    qzstd_hip_free(c->device, bt->dSrc);
-    qzstd_hip_free(c->device, bt->dWork);
+    QZ_HOST_FREE(bt->hSrc); QZ_HOST_FREE(bt->hSeqs); QZ_HOST_FREE(bt->hDesc); QZ_HOST_FREE(bt->hCount);
+    QZ_DEV_FREE(c->device, bt->dSrc); QZ_DEV_FREE(c->device, bt->dWork);
     if (bt->stream) qzstd_hip_stream_destroy(c->device, bt->stream);
-    bt->hSrc = NULL; bt->hSeqs = NULL; bt->hDesc = NULL; bt->hCount = NULL; bt->dSrc = NULL; bt->dWork = NULL;
-    bt->dWorkCap = 0; bt->stream = NULL; bt->dvSeqs = bt->dvDesc = bt->dvCount = NULL;
-    bt->ready = 0;
+    bt->dWorkCap = 0; bt->stream = NULL; bt->dvSeqs = bt->dvDesc = bt->dvCount = NULL; bt->ready = 0;
 }
 
 static void qzFreeCoalescer(QZSTD_Coalescer_T *c)
@@ -582,11 +858,52 @@ static int qzSetupBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
     return QZSTD_OK;
 }
 
-/* the leader's job: one launch per level present in the batch (called WITHOUT c->mu held).
- * Lone-request latency: at the levels whose profile allows it (segLog: no match crosses a 32 KiB boundary) a block goes
- * to the GPU as up to four SEGMENT work items — each workgroup inserts the block before its segment into its tables and
- * parses its segment only — which finish in about 40 % of the time one workgroup needs for the whole block; the
- * caller joins the segments' sequence lists (identical to the whole block's list by construction). */
+/* How a batch's launch cuts request ri into work items (the service has its own rule, on purpose: qzSvcQueue): r->nSeg descriptors from
+ * bt->hDesc[k] on; returns the next free one.  Lone-request latency: at the levels whose profile allows it (segLog: no match crosses a
+ * 32 KiB boundary) a block goes as SEGMENT work items — each workgroup inserts the block before its segment into its tables and parses
+ * its segment only — which finish in about 40 % of the time of the whole block; the caller joins the segments' sequence lists. */
+static int qzPlanSegments(QZSTD_Batch_T *bt, int ri, int k)
+{
+    QZSTD_Req_T *r = &bt->req[ri];
+    const int n = bt->n;
+    qzstd_hip_profile_t pf;
+    /* a full batch fills the GPU as it is: segment items then only repeat the insert work of the block before them
+     * (and, at the chain levels, multiply the scratch); they pay for batches that leave CUs idle */
+    size_t seg = 0, segsMax = !gProc.splitBlocks ? 1 : (n * 32 <= QZ_SPLIT_ITEMS_MAX ? 32 : (n * 8 <= QZ_SPLIT_ITEMS_MAX ? 8 : 1));
+    int sg;
+    r->nSeg = 1;
+    r->dense = 0;
+    if (segsMax > 1 && qzstd_hip_profile_for_level(r->level, r->srcSize, &pf) == 0 && pf.segLog) {
+        /* chain levels: every item of a LAUNCH links the block before it in a scratch of its own (20 B per position of the whole
+         * block: the workgroups of a launch do not start in order, so they cannot share one as the service's items do) — 32 items
+         * per block would grow the batch's grow-only scratch to 32 x 2.6 MB per caller; eight keep most of the latency gain */
+        if (pf.chainDepth && segsMax > 8) segsMax = 8;
+        seg = (size_t)1 << pf.segLog;
+        while ((r->srcSize + seg - 1) / seg > segsMax) seg *= 2; /* whole segments per item */
+        if (r->srcSize > seg) r->nSeg = (int)((r->srcSize + seg - 1) / seg);
+    }
+    r->segPitch = (unsigned int)(QZ_BATCH_PITCH / (size_t)r->nSeg);
+    for (sg = 0; sg < r->nSeg; sg++, k++) {
+        qzstd_hip_block_t *d = &bt->hDesc[k];
+        d->srcOff = (size_t)ri * QZ_SRC_STRIDE;
+        d->mark = 0;
+        if (r->nSeg == 1) {
+            d->seqOff = (size_t)ri * QZ_BATCH_PITCH;
+            d->srcLen = (unsigned int)r->srcSize;
+            d->seqCap = (unsigned int)(r->cap < QZ_BATCH_PITCH ? r->cap : QZ_BATCH_PITCH);
+            d->parseFrom = 0;
+        } else { /* segment sg: the block up to the segment's end, parsed from the segment's start */
+            const size_t end = (size_t)(sg + 1) * seg;
+            d->seqOff = (size_t)ri * QZ_BATCH_PITCH + (size_t)sg * r->segPitch;
+            d->srcLen = (unsigned int)(end < r->srcSize ? end : r->srcSize);
+            d->seqCap = r->segPitch;
+            d->parseFrom = (unsigned int)((size_t)sg * seg);
+        }
+    }
+    return k;
+}
+
+/* the leader's job: one launch per level present in the batch (called WITHOUT c->mu held) */
 static void qzRunBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
 {
     const int n = bt->n, dev = c->device;
@@ -598,43 +915,8 @@ static void qzRunBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
         order[j] = i;
     }
     for (j = 0; j < n; j++) {
-        QZSTD_Req_T *r = &bt->req[order[j]];
-        qzstd_hip_profile_t pf;
-        size_t seg = 0;
-        int sg;
-        r->nSeg = 1;
-        r->dense = 0;
-        /* a full batch fills the GPU as it is: segment items then only repeat the insert work of the block before them
-         * (and, at the chain levels, multiply the scratch); they pay for batches that leave CUs idle */
-        size_t segsMax = !gProc.splitBlocks ? 1 : (n * 32 <= QZ_SPLIT_ITEMS_MAX ? 32 : (n * 8 <= QZ_SPLIT_ITEMS_MAX ? 8 : 1));
-        if (segsMax > 1 && qzstd_hip_profile_for_level(r->level, r->srcSize, &pf) == 0 && pf.segLog) {
-            /* chain levels: every item of a LAUNCH links the block before it in a scratch of its own (20 B per position of the whole
-             * block: the workgroups of a launch do not start in order, so they cannot share one as the service's items do) — 32 items
-             * per block would grow the batch's grow-only scratch to 32 x 2.6 MB per caller; eight keep most of the latency gain */
-            if (pf.chainDepth && segsMax > 8) segsMax = 8;
-            seg = (size_t)1 << pf.segLog;
-            while ((r->srcSize + seg - 1) / seg > segsMax) seg *= 2; /* whole segments per item */
-            if (r->srcSize > seg) r->nSeg = (int)((r->srcSize + seg - 1) / seg);
-        }
-        r->segPitch = (unsigned int)(QZ_BATCH_PITCH / (size_t)r->nSeg);
         first[j] = k;
-        for (sg = 0; sg < r->nSeg; sg++, k++) {
-            qzstd_hip_block_t *d = &bt->hDesc[k];
-            d->srcOff = (size_t)order[j] * QZ_SRC_STRIDE;
-            d->mark = 0;
-            if (r->nSeg == 1) {
-                d->seqOff = (size_t)order[j] * QZ_BATCH_PITCH;
-                d->srcLen = (unsigned int)r->srcSize;
-                d->seqCap = (unsigned int)(r->cap < QZ_BATCH_PITCH ? r->cap : QZ_BATCH_PITCH);
-                d->parseFrom = 0;
-            } else { /* segment sg: the block up to the segment's end, parsed from the segment's start */
-                const size_t end = (size_t)(sg + 1) * seg;
-                d->seqOff = (size_t)order[j] * QZ_BATCH_PITCH + (size_t)sg * r->segPitch;
-                d->srcLen = (unsigned int)(end < r->srcSize ? end : r->srcSize);
-                d->seqCap = r->segPitch;
-                d->parseFrom = (unsigned int)((size_t)sg * seg);
-            }
-        }
+        k = qzPlanSegments(bt, order[j], k);
     }
     /* one copy in, one launch per level, one wait: the kernel reads the descriptors from and writes the sequences and
      * counts to this batch's pinned host buffers directly (posted PCIe writes while it runs), which takes two
@@ -651,11 +933,8 @@ static void qzRunBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
         }
         k1 = g1 < n ? first[g1] : k;
         work = qzstd_hip_workspace_bytes(level, (unsigned int)(k1 - k0), maxLen);
-        if (work > bt->dWorkCap && launches) { /* the scratch is about to be replaced: what runs on it has to finish first */
-            const int w = qzWait(dev, bt->stream);
-            if (w == 1) bt->stuck = 1;
-            failed = w != 0;
-        }
+        /* the scratch is about to be replaced: what runs on it has to finish first */
+        if (work > bt->dWorkCap && launches) failed = qzWaitOrQuarantine(dev, bt->stream, &bt->stuck) != 0;
         if (work && !failed) bt->dWork = qzGrowDev(dev, bt->dWork, &bt->dWorkCap, work);
         failed = failed || (work && !bt->dWork) ||
                  qzstd_hip_find_sequences(dev, bt->stream, level, bt->dSrc, (const qzstd_hip_block_t *)bt->dvDesc + k0,
@@ -665,12 +944,9 @@ static void qzRunBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
         g0 = g1;
     }
     /* whatever was queued — the copy, the launches of earlier level groups — has to be off the stream before the batch's
-     * buffers are handed back, also when a later step failed (round-2 ADVICE) */
-    if (!bt->stuck) {
-        const int w = qzWait(dev, bt->stream);
-        if (w == 1) bt->stuck = 1; /* the kernel may still write into this batch's buffers: quarantined */
-        failed = failed || w != 0;
-    }
+     * buffers are handed back, also when a later step failed (round-2 ADVICE); after a time-out the kernel may still write
+     * into this batch's buffers: quarantined */
+    if (!bt->stuck && qzWaitOrQuarantine(dev, bt->stream, &bt->stuck) != 0) failed = 1;
     {
         const int cause = bt->stuck ? QZ_CAUSE_TIMEOUT : QZ_CAUSE_RUNTIME;
         for (j = 0; j < n; j++) bt->req[j].cause = cause;
@@ -697,9 +973,6 @@ static void qzRunBatch(QZSTD_Coalescer_T *c, QZSTD_Batch_T *bt)
     c->blocks += (unsigned long)n;
     __atomic_fetch_add(&gProc.devBlocks[dev][1], (unsigned long)n, __ATOMIC_RELAXED);
 }
-
-static size_t qzSlotBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
-                          size_t srcSize, int level);
 
 /* one block through the coalescer of device `dev`; returns the sequence count or the error code */
 static size_t qzCoalescedBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
@@ -772,23 +1045,10 @@ static size_t qzCoalescedBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSe
         if (r->nSeg == 1) {
             memcpy(outSeqs, bt->hSeqs + (size_t)i * QZ_BATCH_PITCH, rc * sizeof(ZSTD_Sequence));
         } else { /* join the segments: the trailing literals of one flow into the first sequence of the next */
-            size_t out = 0, carry = 0;
+            QZSTD_Join_T jn = { outSeqs, 0, 0, 0 };
             int sg;
-            for (sg = 0; sg < r->nSeg; sg++) {
-                const ZSTD_Sequence *q = bt->hSeqs + (size_t)i * QZ_BATCH_PITCH + (size_t)sg * r->segPitch;
-                const size_t count = r->segCnt[sg];
-                if (count > 1) {
-                    memcpy(outSeqs + out, q, (count - 1) * sizeof(ZSTD_Sequence));
-                    outSeqs[out].litLength += (unsigned int)carry;
-                    out += count - 1;
-                    carry = 0;
-                }
-                carry += q[count - 1].litLength;
-            }
-            outSeqs[out].offset = 0;
-            outSeqs[out].litLength = (unsigned int)carry;
-            outSeqs[out].matchLength = 0;
-            outSeqs[out].rep = 0;
+            for (sg = 0; sg < r->nSeg; sg++) (void)qzJoinPiece(&jn, bt->hSeqs + (size_t)i * QZ_BATCH_PITCH + (size_t)sg * r->segPitch, r->segCnt[sg], 0u, 0ul);
+            (void)qzJoinFinish(&jn); /* (its count is rc: the leader added the segments up for the capacity rule) */
         }
     }
     dense = rc == ZSTD_SEQUENCE_PRODUCER_ERROR && bt->req[i].dense && !bt->stuck;
@@ -809,172 +1069,239 @@ static size_t qzCoalescedBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSe
     return rc;
 }
 
-/* ---------------------------------------------------------------- lifecycle ------ */
+/* ---------------------------------------------------------------- service -------- */
 
-static int qzEnvInt(const char *name, int dflt, int lo, int hi)
+/* buffers of a slot's service requests, first use only; 0 on success (a failure frees what was created) */
+static int qzSetupSlotService(QZSTD_Slot_T *sl)
 {
-    const char *v = getenv(name);
-    long x;
-    if (!v || !*v) return dflt;
-    x = strtol(v, NULL, 10);
-    if (x < lo) x = lo;
-    if (x > hi) x = hi;
-    return (int)x;
+    if (sl->vSrc) return 0;
+    sl->vSrc = (unsigned char *)qzHostAlloc(QZSTD_HIP_BLOCK_MAX + 64, sl->device, 1);
+    sl->vSeqs = (ZSTD_Sequence *)qzHostAlloc(QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence), sl->device, 1);
+    if (sl->vSeqs) memset(sl->vSeqs, 0, QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence)); /* (fresh pinned pages may hold marked entries of an earlier life) */
+    sl->vCount = (unsigned int *)qzHostAlloc(QZ_SVC_ITEMS_MAX * sizeof(unsigned int), sl->device, 1);
+    sl->vdSrc = (unsigned char *)qzstd_hip_malloc(sl->device, QZSTD_HIP_BLOCK_MAX + 64);
+    if (!sl->vSrc || !sl->vSeqs || !sl->vCount || !sl->vdSrc) {
+        QZ_LOG(1, "service buffers of a slot on device %d: %s\n", sl->device, qzstd_hip_last_error());
+        QZ_HOST_FREE(sl->vSrc); QZ_HOST_FREE(sl->vSeqs); QZ_HOST_FREE(sl->vCount); QZ_DEV_FREE(sl->device, sl->vdSrc);
+        return -1;
+    }
+    memset(sl->vCount, 0xFF, QZ_SVC_ITEMS_MAX * sizeof(unsigned int)); /* "arrived": nothing is outstanding */
+    sl->vItems = 0;
+    return 0;
 }
 
-/* Enumerate GPUs and lay the slots out round-robin across them, so that threads whose
- * hints are consecutive land on different devices (reference: the instance shuffle of
- * QZSTD_getAndShuffleInstance, :601-630). */
-static int qzBuildSlots(void)
+/* levels >= 5 (exact hash chains): their service requests carry a chain scratch (a launch's scratch is sized by qzstd_hip_workspace_bytes at every level) */
+static int qzIsChainLevel(int level)
 {
-    int nDev = qzstd_hip_device_count();
-    int perDev, i, b, maxDev;
-    if (nDev <= 0) return QZSTD_FAIL;
-    maxDev = qzEnvInt("QZSTD_HIP_MAX_DEVICES", QZ_MAX_DEVICES, 1, QZ_MAX_DEVICES);
-    if (nDev > maxDev) nDev = maxDev;
-    perDev = qzEnvInt("QZSTD_HIP_SLOTS", QZ_DEFAULT_SLOTS_PER_DEVICE, 1, QZ_MAX_SLOTS / nDev);
-    gProc.slots = (QZSTD_Slot_T *)calloc((size_t)nDev * perDev, sizeof(QZSTD_Slot_T));
-    if (!gProc.slots) return QZSTD_FAIL;
-    gProc.numDevices = nDev;
-    gProc.numSlots = nDev * perDev;
-    memset(gProc.devBlocks, 0, sizeof(gProc.devBlocks));
-    for (i = 0; i < gProc.numSlots; i++) gProc.slots[i].device = i % nDev;
-    gProc.numa = qzEnvInt("QZSTD_HIP_NUMA", 1, 0, 1);
-    gProc.numaThreadNode = qzEnvInt("QZSTD_HIP_NUMA_NODE", -1, -1, 1023);
-    memset(gProc.nodeNext, 0, sizeof(gProc.nodeNext));
-    gProc.anyNext = 0;
-    for (i = 0; i < nDev && i < QZ_MAX_DEVICES; i++) {
-        gProc.devNode[i] = qzstd_hip_device_numa_node(i);
-        QZ_LOG(2, "device %d: host NUMA node %d\n", i, gProc.devNode[i]);
+    qzstd_hip_profile_t p;
+    return qzstd_hip_profile_for_level(level, QZSTD_HIP_BLOCK_MAX, &p) == 0 && p.chainDepth != 0;
+}
+
+/* one request to the resident service, from the grab of its slot to its answer */
+typedef struct {
+    QZSTD_Slot_T *sl;
+    int slot, level;
+    qzstd_hip_svc_req_t rq;
+    unsigned long t0, spinNs; /* when the polling began (the time-out counts from here); how long it stays busy before it naps */
+} QZSTD_SvcCall_T;
+enum { QZ_SVC_DONE = 0, QZ_SVC_TIMED_OUT, QZ_SVC_REJECTED, QZ_SVC_WRONG }; /* how a queued request ended (qzSvcCollect) */
+
+/* Grab a slot of device `dev`, make it ready (buffers, count words, epoch, the request), stage the block and queue the request.
+ * 0 = queued, c holds the slot; -1 = not now (no slot free, its last request still outstanding, no memory, the service does not take
+ * the request): nothing is held. */
+static int qzSvcQueue(QZSTD_SvcCall_T *c, int hint, int dev, const void *src, size_t srcSize, int level)
+{
+    const size_t pad = ((srcSize + 15) & ~(size_t)15) - srcSize;
+    QZSTD_Slot_T *sl;
+    qzstd_hip_svc_req_t *rq = &c->rq;
+    size_t itemBytes = (size_t)gProc.svcItemBytes, nItems, k;
+    int rc, progressive;
+    while ((srcSize + itemBytes - 1) / itemBytes > QZ_SVC_ITEMS_MAX) itemBytes *= 2; /* (the launch path's rule differs: qzPlanSegments) */
+    nItems = (srcSize + itemBytes - 1) / itemBytes;
+    c->level = level;
+    c->slot = qzTryGrabSlot(hint, dev);
+    if (c->slot < 0) return -1;
+    sl = c->sl = &gProc.slots[c->slot];
+    if (sl->vStuck) { /* a request of this slot timed out: usable again once every count word of it has arrived */
+        for (k = 0; k < sl->vItems; k++)
+            if (__atomic_load_n(&sl->vCount[k], __ATOMIC_ACQUIRE) == 0u) goto notNow;
+        sl->vStuck = 0;
     }
-    gProc.coalesce = qzEnvInt("QZSTD_HIP_COALESCE", 1, 0, 1);
-    gProc.split = qzEnvInt("QZSTD_HIP_SPLIT", nDev < QZ_HINT_PARTS ? nDev : QZ_HINT_PARTS, 1, nDev < QZ_HINT_PARTS ? nDev : QZ_HINT_PARTS);
-    gProc.coal = (QZSTD_Coalescer_T *)calloc((size_t)nDev, sizeof(QZSTD_Coalescer_T));
-    if (!gProc.coal) return QZSTD_FAIL;
-    for (i = 0; i < nDev; i++) {
-        gProc.coal[i].device = i;
-        gProc.coal[i].open = -1;
-        pthread_mutex_init(&gProc.coal[i].mu, NULL);
-        pthread_cond_init(&gProc.coal[i].cvOpen, NULL);
-        for (b = 0; b < QZ_BATCHES; b++) {
-            pthread_cond_init(&gProc.coal[i].batch[b].cvLead, NULL);
-            pthread_cond_init(&gProc.coal[i].batch[b].cvDone, NULL);
+    if (qzSetupSlotService(sl) != 0) goto notNow;
+    /* progressive staging (qzstd_hip.h, round 5): where the workers look at a count word before they read its slice, the request is queued
+     * FIRST and the block is copied into the pinned buffer behind it, slice by slice — the staging copy (13 us for 128 KiB) then overlaps
+     * the request's way to the first worker (8 us) instead of standing in front of it */
+    progressive = qzstd_hip_service_progressive(sl->device) == 1;
+    if (!progressive) {
+        memcpy(sl->vSrc, src, srcSize); /* staging copy, reference :1223 */
+        memset(sl->vSrc + srcSize, 0, pad);
+    }
+    for (k = 0; k < nItems; k++) sl->vCount[k] = progressive ? QZSTD_HIP_NSEQ_STAGING : 0u;
+    sl->vItems = (unsigned int)nItems;
+    sl->vEpoch = (sl->vEpoch + 1u) & 0xFFFFFFu;
+    if (sl->vEpoch == 0u) {
+        /* the 24-bit epoch starts over: an entry that no request of the last 2^24 overwrote would show a mark that is valid again.
+         * The slot is ours and its previous request is complete (every count word in): wipe the result area once per lap. */
+        memset(sl->vSeqs, 0, QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence));
+        sl->vEpoch = 1u;
+    }
+    rq->hSrc = sl->vSrc; rq->dSrc = sl->vdSrc; rq->hSeqs = sl->vSeqs; rq->hCount = sl->vCount;
+    rq->srcLen = (uint32_t)srcSize; rq->itemBytes = (uint32_t)itemBytes; rq->nItems = (uint32_t)nItems;
+    rq->seqCapPerItem = (uint32_t)(QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP / nItems); /* the slot's whole result area, shared out */
+    rq->slot = (uint32_t)c->slot; rq->epoch = sl->vEpoch;
+    rq->dWork = NULL;
+    rc = 0;
+    if (qzIsChainLevel(level)) { /* every item links the block before it in its own scratch */
+        if (!sl->vdWork) sl->vdWork = qzstd_hip_malloc(sl->device, QZSTD_HIP_SVC_WORK_BYTES);
+        rq->dWork = sl->vdWork;
+        rc = sl->vdWork == NULL; /* (no scratch: as a request the service does not take) */
+    }
+    if (rc == 0) rc = qzstd_hip_service_submit(sl->device, level, rq);
+    if (rc != 0) { /* > 0: the level is not served, the service is down or busy with another level; < 0: an error */
+        memset(sl->vCount, 0xFF, nItems * sizeof(unsigned int)); /* nothing outstanding */
+        if (rc < 0) QZ_LOG(1, "service request not queued: %s\n", qzstd_hip_last_error());
+        goto notNow; /* the launch path may still work */
+    }
+    for (k = 0; progressive && k < nItems; k++) {
+        const size_t from = k * itemBytes, upTo = (k + 1) * itemBytes < srcSize ? (k + 1) * itemBytes : srcSize;
+        unsigned int expect = QZSTD_HIP_NSEQ_STAGING;
+        memcpy(sl->vSrc + from, (const unsigned char *)src + from, upTo - from);
+        if (k + 1 == nItems) memset(sl->vSrc + srcSize, 0, pad);
+        /* "slice k is in": only a word that still says STAGING (a request the dispatcher handed back has REJECTED there) */
+        (void)__atomic_compare_exchange_n(&sl->vCount[k], &expect, 0u, 0, __ATOMIC_RELEASE, __ATOMIC_RELAXED);
+    }
+    return 0;
+notNow:
+    qzReleaseSlot(c->slot);
+    return -1;
+}
+
+/* Wait for count word k to leave 0; 1 = not within the time-out, or the service has left for good.  `naps`: the policy for an item being
+ * worked on — busy for spinNs, then naps, every 1024 polls a poke (the service may have left with this request in its ring: it is
+ * launched again; or for good: another request timed out).  Without: busy all the way (words of one wave store). */
+static int qzSvcWordWait(const QZSTD_SvcCall_T *c, size_t k, int naps)
+{
+    const unsigned int *word = &c->sl->vCount[k];
+    unsigned polls = 0;
+    while (__atomic_load_n(word, __ATOMIC_ACQUIRE) == 0u) {
+        __builtin_ia32_pause();
+        if ((++polls & (naps ? 63u : 1023u)) == 0u) {
+            const unsigned long dt = qzNowNs() - c->t0;
+            if (dt > (unsigned long)gProc.timeoutMs * 1000000ul) return 1;
+            if (!naps) continue;
+            if ((polls & 1023u) == 0u && qzstd_hip_service_poke(c->sl->device, c->level) == 2 && __atomic_load_n(word, __ATOMIC_ACQUIRE) == 0u) return 1;
+            if (dt > c->spinNs) { const struct timespec nap = { 0, dt < 20000000ul ? 5000 : 200000 }; nanosleep(&nap, NULL); }
         }
     }
-    gProc.hb = (QZSTD_Batcher_T *)calloc((size_t)nDev, sizeof(QZSTD_Batcher_T));
-    if (!gProc.hb) return QZSTD_FAIL;
-    for (i = 0; i < nDev; i++) {
-        gProc.hb[i].device = i;
-        gProc.hb[i].open = -1;
-        pthread_mutex_init(&gProc.hb[i].mu, NULL);
-        pthread_cond_init(&gProc.hb[i].cv, NULL);
-        for (b = 0; b < QZ_HB_STREAMS_MAX; b++) gProc.hb[i].str[b].last = -1;
-    }
-    return QZSTD_OK;
+    return 0;
 }
 
-int QZSTD_startQatDevice(void)
+/* Poll the count words in item order — the items finish roughly in that order (the later, the more history in front of it) — and JOIN
+ * every item's list as it arrives: by the time the last item is in, the rest of the block's list stands.  Returns QZ_SVC_*. */
+static int qzSvcCollect(QZSTD_SvcCall_T *c, QZSTD_Join_T *j, size_t outSeqsCapacity)
 {
-    int status;
-    pthread_mutex_lock(&gProc.mutex);
-    {
-        const char *dbg = getenv("QZSTD_HIP_DEBUG");
-        const char *rep = getenv("QZSTD_HIP_EXT_REPCODES");
-        if (dbg && *dbg) qzLogLevel = atoi(dbg);
-        /* the caller promises ZSTD_c_searchForExternalRepcodes = enable on its CCtx (libzstd's default only
-         * from level 10): repeat-offset aware sequences at every level */
-        gProc.levelFlags = (rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0;
-        gProc.timeoutMs = qzEnvInt("QZSTD_HIP_TIMEOUT_MS", QZ_DEFAULT_TIMEOUT_MS, 1, 600000);
-        gProc.splitBlocks = qzEnvInt("QZSTD_HIP_SPLIT_BLOCKS", 1, 0, 1);
-        gProc.service = qzEnvInt("QZSTD_HIP_SERVICE", 1, 0, 1);
-        gProc.svcItemBytes = qzEnvInt("QZSTD_HIP_SERVICE_ITEM", 4096, 4096, (int)QZSTD_HIP_BLOCK_MAX) & ~4095;
-        gProc.svcSpinUs = qzEnvInt("QZSTD_HIP_SERVICE_SPIN_US", 400, 0, 1000000);
-        gProc.svcSpinSet = getenv("QZSTD_HIP_SERVICE_SPIN_US") != NULL;
-        /* announcements: PACKED result entries (qzstd_hip.h: QZSTD_HIP_MARK_COMPACT) — 8 bytes per sequence over PCIe instead of 16 (round 6: the
-         * level-1 kernel ran at the bus's write rate).  0 = 16-byte entries (A/B) */
-        gProc.hintCompact = qzEnvInt("QZSTD_HIP_HINT_COMPACT", 1, 0, 1);
-        /* announcement launches in flight per GPU (the batcher's streams): the runtime's default hardware queue count */
-        gProc.hintBatches = qzEnvInt("QZSTD_HIP_HINT_BATCHES", 4, 1, QZ_HB_STREAMS_MAX);
-        gProc.stageNt = qzEnvInt("QZSTD_HIP_STAGE_NT", 1, 0, 1);
-        gProc.hintDirect = qzEnvInt("QZSTD_HIP_HINT_DIRECT", 0, 0, 3);
-        (void)qzUsableCores(); /* (read once here, under the process mutex: the waits only load it) */
-    }
-    if (gProc.status == QZSTD_FAIL) {
-        /* runtime up? (reference: QZSTD_salUserStart, :498-527) */
-        gProc.status = qzstd_hip_device_count() > 0 ? QZSTD_STARTED : QZSTD_FAIL;
-        if (gProc.status == QZSTD_FAIL) QZ_LOG(2, "no usable HIP device: %s\n", qzstd_hip_last_error());
-    }
-    if (gProc.status == QZSTD_STARTED) {
-        gProc.status = qzBuildSlots() == QZSTD_OK ? QZSTD_OK : QZSTD_STARTED;
-    }
-    QZ_LOG(2, "start: status %d, %d device(s), %d slot(s)\n", gProc.status, gProc.numDevices, gProc.numSlots);
-    status = gProc.status;
-    pthread_mutex_unlock(&gProc.mutex);
-    return status;
-}
-
-void QZSTD_stopQatDevice(void)
-{
-    int i;
-    pthread_mutex_lock(&gProc.mutex);
-    for (i = 0; i < gProc.numDevices; i++) (void)qzstd_hip_service_stop(i); /* the resident kernels leave before anything is freed */
-    if (gProc.slots) {
-        for (i = 0; i < gProc.numSlots; i++) qzFreeSlot(&gProc.slots[i]); /* waits (bounded) for each stream */
-        free(gProc.slots);
-    }
-    if (gProc.hb) {
-        for (i = 0; i < gProc.numDevices; i++) qzFreeBatcher(&gProc.hb[i]); /* waits (bounded) for each stream */
-        free(gProc.hb);
-    }
-    gProc.hb = NULL;
-    qzReapOrphans(1); /* (after the bounded waits for the streams the parked areas' kernels ran on) */
-    gProc.gen++; /* parts staged so far refer to nothing any more */
-    if (gProc.coal) {
-        for (i = 0; i < gProc.numDevices; i++) qzFreeCoalescer(&gProc.coal[i]);
-        free(gProc.coal);
-    }
-    gProc.coal = NULL;
-    gProc.slots = NULL;
-    gProc.numSlots = 0;
-    gProc.numDevices = 0;
-    gProc.status = QZSTD_FAIL;
-    pthread_mutex_unlock(&gProc.mutex);
-}
-
-/* the cores this process may use: its affinity mask, capped by a cgroup CPU quota (cpu.max) */
-static int qzUsableCores(void)
-{
-    static int cached; /* written once with the same value by whoever gets here first (QZSTD_startQatDevice does, under the process mutex) */
-    int n = 0;
-    cpu_set_t set;
-    FILE *f;
-    if ((n = __atomic_load_n(&cached, __ATOMIC_RELAXED)) != 0) return n;
-    n = 0;
-    if (sched_getaffinity(0, sizeof(set), &set) == 0) n = CPU_COUNT(&set);
-    if (n <= 0) n = (int)sysconf(_SC_NPROCESSORS_ONLN);
-    f = fopen("/sys/fs/cgroup/cpu.max", "re");
-    if (f) {
-        char q[32] = "";
-        long per = 0;
-        if (fscanf(f, "%31s %ld", q, &per) == 2 && strcmp(q, "max") != 0 && per > 0) {
-            const long quota = (atol(q) + per - 1) / per;
-            if (quota > 0 && quota < n) n = (int)quota;
+    const QZSTD_Slot_T *sl = c->sl;
+    size_t k, m;
+    int wrong = 0;
+    c->t0 = qzNowNs();
+    /* how long a waiting caller polls before it naps: with a core per caller polling is free and a nap costs its wake-up (level 1, 16 threads on
+     * 16 cores: 12.7 GB/s polling 400 us, 10.5 napping at once); with more callers than cores a poller keeps another caller's entropy stage
+     * off the core (32 threads: 9.5 GB/s polling 400 us, 14.2-14.6 polling 10 us or not at all; 48 threads: 5.6 against 15.1-15.5) */
+    c->spinNs = (unsigned long)gProc.svcSpinUs * 1000ul;
+    if (!gProc.svcSpinSet && __atomic_load_n(&gProc.liveStates, __ATOMIC_RELAXED) > qzUsableCores()) c->spinNs = 10000ul;
+    for (k = 0; k < c->rq.nItems; k++) {
+        unsigned int cnt;
+        if (qzSvcWordWait(c, k, 1)) return QZ_SVC_TIMED_OUT;
+        if (wrong) continue; /* (after a wrong item the rest is only waited for: the slot's buffers are in use until every count is in) */
+        cnt = sl->vCount[k];
+        if (cnt == QZSTD_HIP_NSEQ_REJECTED) {
+            /* handed back whole: nothing of it was queued.  The dispatcher writes all nItems words with one wave store, but stores
+             * to pinned host memory can land microseconds apart: the slot is given back only when every word is in — a word
+             * landing later would be read by the slot's NEXT request as its own (round-3 ADVICE) */
+            for (m = k + 1; m < c->rq.nItems; m++)
+                if (qzSvcWordWait(c, m, 0)) return QZ_SVC_TIMED_OUT;
+            return QZ_SVC_REJECTED;
         }
-        fclose(f);
+        if (cnt == QZSTD_HIP_NSEQ_ERROR || cnt > c->rq.seqCapPerItem || j->out + cnt >= outSeqsCapacity - 1) { wrong = 1; continue; } /* capacity rule, reference :1318-1322 */
+        if (qzJoinPiece(j, sl->vSeqs + k * c->rq.seqCapPerItem, cnt, c->rq.epoch, c->t0) != 0) return QZ_SVC_TIMED_OUT; /* (entries later than t0 + the limit) */
     }
-    n = n > 0 ? n : 1;
-    __atomic_store_n(&cached, n, __ATOMIC_RELAXED);
-    return n;
+    return wrong ? QZ_SVC_WRONG : QZ_SVC_DONE;
 }
 
-void *QZSTD_createSeqProdState(void)
+/* the request was not answered within the time-out: what the service says about itself */
+static void qzSvcLogTimeout(const QZSTD_SvcCall_T *c)
 {
-    QZSTD_Session_T *s = (QZSTD_Session_T *)calloc(1, sizeof(QZSTD_Session_T));
-    if (!s) return NULL;
-    s->slotHint = -1;
-    __atomic_fetch_add(&gProc.liveStates, 1, __ATOMIC_RELAXED);
-    return s;
+    unsigned long in[8] = { 0 }, dg[8] = { 0 };
+    (void)qzstd_hip_service_info(c->sl->device, in);
+    (void)qzstd_hip_service_debug(c->sl->device, dg);
+    QZ_LOG(1, "device %d: service request not answered after %lu ms (limit %d; service: %lu launch(es), %lu request(s), state %lu; dispatcher: %lu poll(s), "
+              "%lu request(s) taken, %lu item(s) queued; workers: %lu started, %lu item(s) picked up, %lu finished, %lu gave up on a slice; ring: %lu "
+              "consumed, %lu reserved, quit %lu, frozen %lu; this request: %zu item(s), level %#x)\n",
+           c->sl->device, (qzNowNs() - c->t0) / 1000000ul, gProc.timeoutMs, in[0], in[1], in[4], dg[0], dg[1], dg[2], dg[3], dg[4], dg[5], in[6], dg[6],
+           dg[7] & 0x1FFFFFFFFFFFFFFFul, dg[7] >> 62, (dg[7] >> 61) & 1ul, (size_t)c->rq.nItems, (unsigned)c->level);
 }
+
+/* the answer does not add up to the block — which item: every item's own list adds up to its range */
+static void qzSvcLogSum(const QZSTD_SvcCall_T *c, size_t sum, size_t srcSize)
+{
+    const QZSTD_Slot_T *sl = c->sl;
+    const size_t nItems = c->rq.nItems, itemBytes = c->rq.itemBytes;
+    size_t k;
+    QZ_LOG(1, "service result does not add up: %zu of %zu bytes\n", sum, srcSize);
+    for (k = 0; k < nItems; k++) {
+        const ZSTD_Sequence *q = sl->vSeqs + k * c->rq.seqCapPerItem;
+        const size_t from = k * itemBytes, upTo = (k + 1) * itemBytes < srcSize ? (k + 1) * itemBytes : srcSize;
+        size_t isum = 0, j;
+        for (j = 0; j < sl->vCount[k] && j < c->rq.seqCapPerItem; j++) isum += (size_t)q[j].litLength + q[j].matchLength;
+        if (isum != upTo - from) QZ_LOG(1, "  item %zu of %zu: %u sequences cover %zu of %zu bytes\n", k, nItems, sl->vCount[k], isum, upTo - from);
+    }
+}
+
+/* One block through the resident service (qzstd_hip_service_submit): no launch, no stream — one 64-byte request goes into the service's
+ * ring, workgroups that are already resident parse the block as up to 32 work items (runs of whole segments) and write sequences and,
+ * last, the counts into this slot's pinned memory.  Reference shape: synchronous submit + poll of one request on one DC instance,
+ * src/qatseqprod.c:1243-1272.  Returns the count, the error code, or QZ_NOT_SERVED: the caller then takes the launch path. */
+static size_t qzServiceBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
+                             size_t srcSize, int level)
+{
+    QZSTD_SvcCall_T c;
+    QZSTD_Join_T j = { outSeqs, 0, 0, 0 };
+    size_t out;
+    int end;
+    if (!gProc.service || srcSize == 0 || qzSvcQueue(&c, s->slotHint, dev, src, srcSize, level) != 0) return QZ_NOT_SERVED;
+    end = qzSvcCollect(&c, &j, outSeqsCapacity);
+    if (end == QZ_SVC_TIMED_OUT) { /* reference: the 2 s poll limit, :1261-1285 */
+        qzSvcLogTimeout(&c);
+        c.sl->vStuck = 1;
+        qzstd_hip_service_mark_broken(c.sl->device);
+        qzReleaseSlot(c.slot);
+        /* the resident kernels are asked to leave and are not used again; THIS block is not lost: it goes through the batches
+         * (whose own wait has the same limit: a device that is really wedged then returns the error, reference :1261-1285) */
+        s->redoneAlone++;
+        return QZ_NOT_SERVED;
+    }
+    if (end != QZ_SVC_DONE) {
+        qzReleaseSlot(c.slot);
+        if (end == QZ_SVC_REJECTED) return QZ_NOT_SERVED;
+        qzCause = QZ_CAUSE_CAPACITY; /* QZ_SVC_WRONG */
+        return ZSTD_SEQUENCE_PRODUCER_ERROR;
+    }
+    out = qzJoinFinish(&j);
+    qzReleaseSlot(c.slot);
+    /* what arrived has to add up to the block (a wrong result must never reach libzstd, which does not validate sequences by
+     * default): the lengths were added up on the way */
+    if (j.covered != srcSize) {
+        qzSvcLogSum(&c, j.covered, srcSize);
+        qzstd_hip_service_mark_broken(c.sl->device);
+        qzCause = QZ_CAUSE_RUNTIME;
+        return ZSTD_SEQUENCE_PRODUCER_ERROR;
+    }
+    s->servedService++;
+    __atomic_fetch_add(&gProc.devBlocks[c.sl->device][2], 1ul, __ATOMIC_RELAXED);
+    return out;
+}
+
+/* ---------------------------------------------------------------- announcement batcher -- */
 
 /* frees (force) or tries to free the parked buffers whose streams have drained; scrubs the staged caller data first */
 static void qzReapOrphans(int force)
@@ -1013,112 +1340,6 @@ static void qzOrphanArea(QZSTD_Area_T *a, int dev, void *stream)
     a->seqsCap = 0;
     QZ_LOG(1, "device %d: a batch area's buffers are parked until a timed-out stream drains\n", dev);
 }
-#ifdef QZ_TEST_HOOKS /* the mock build of tests/test_host_mock.py only: never in the release library */
-unsigned long qzstd_test_orphans(void) { return qzOrphanCount; }
-void qzstd_test_set_area_tags(unsigned int e) /* the next use of every batch area, every GPU, gets tag e + 1 (the wrap) */
-{
-    int d, k;
-    for (d = 0; gProc.hb && d < gProc.numDevices; d++) {
-        pthread_mutex_lock(&gProc.hb[d].mu);
-        for (k = 0; k < QZ_HB_AREAS; k++) gProc.hb[d].area[k].lap = e & 0xFFFFFFu;
-        pthread_mutex_unlock(&gProc.hb[d].mu);
-    }
-}
-/* the hook's name from the time announcements kept their own result areas and epochs (tests/test_host_mock.py calls it): the tags now belong to
- * the batch areas, which every state shares, so `state` names nothing and every area's tag moves */
-void qzstd_test_set_hint_epochs(void *state, unsigned int e)
-{
-    (void)state;
-    qzstd_test_set_area_tags(e);
-}
-unsigned long qzstd_test_hint_launches(void) /* announcement launches since the device layer started, every GPU */
-{
-    unsigned long n = 0;
-    int d;
-    for (d = 0; gProc.hb && d < gProc.numDevices; d++) n += __atomic_load_n(&gProc.hb[d].launches, __ATOMIC_RELAXED);
-    return n;
-}
-void qzstd_test_set_service_epochs(unsigned int e) /* every slot's next service request gets epoch e + 1 (the 24-bit wrap) */
-{
-    int i;
-    for (i = 0; gProc.slots && i < gProc.numSlots; i++) gProc.slots[i].vEpoch = e & 0xFFFFFFu;
-}
-#endif
-
-/* Takes n entries of a result area that is completed by count words: the count says how many entries there are, not that they have all
- * arrived — they are stored by other waves than the count and nothing orders them on their ways to host memory (measured in round 3 on
- * the resident service: under load an item's last entries land up to microseconds after its count).  Every entry is ONE 16-byte store
- * that carries the announcement's epoch in its fourth word (qzstd_hip_block_t.mark): an entry is taken when it shows it; the mark is
- * masked out of the copy.  dst may be NULL (the entries are only waited for).  0 = taken, 1 = not within the time-out. */
-static int qzTakeMarked(ZSTD_Sequence *dst, const ZSTD_Sequence *q, size_t n, unsigned int epoch)
-{
-    const __m128i keep = _mm_set_epi32(0, -1, -1, -1);
-    unsigned long t0 = 0;
-    size_t j;
-    for (j = 0; j < n; j++) {
-        __m128i v = _mm_load_si128((const __m128i *)(const void *)(q + j));
-        if ((unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(v, 12)) != epoch) { /* not there yet: rare */
-            unsigned spins = 0;
-            if (!t0) t0 = qzNowNs();
-            do {
-                __builtin_ia32_pause();
-                __asm__ volatile("" ::: "memory"); /* (a fresh load every time round) */
-                if ((++spins & 1023u) == 0u && qzNowNs() - t0 > (unsigned long)gProc.timeoutMs * 1000000ul) return 1;
-                v = _mm_load_si128((const __m128i *)(const void *)(q + j));
-            } while ((unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(v, 12)) != epoch);
-        }
-        if (dst) _mm_storeu_si128((__m128i *)(void *)(dst + j), _mm_and_si128(v, keep));
-    }
-    return 0;
-}
-
-/* The same for PACKED entries (qzstd_hip.h: QZSTD_HIP_MARK_COMPACT): one 8-byte load per entry (it arrived as one store), taken when its top 12
- * bits show the tag, unpacked into the caller's ZSTD_Sequence array.  *covered += literal + match lengths of the entries taken (dst != NULL). */
-static int qzTakePacked(ZSTD_Sequence *dst, const unsigned long long *q, size_t n, unsigned int tag)
-{
-    const __m128i m17 = _mm_set_epi32(0, 0x1FFFF, 0, 0x1FFFF), m18 = _mm_set_epi32(0, 0x3FFFF, 0, 0x3FFFF);
-    unsigned long t0 = 0;
-    size_t j = 0;
-    while (j < n) {
-        if (dst && j + 2 <= n && !((uintptr_t)(q + j) & 15u)) { /* two entries per step: the usual case, both there (an ALIGNED 16-byte load: each
-                                                                  * 8-byte half is one of the kernel's stores, never torn) */
-            const __m128i v = _mm_load_si128((const __m128i *)(const void *)(q + j));
-            const __m128i t = _mm_srli_epi64(v, 52);
-            if ((unsigned int)_mm_cvtsi128_si32(t) == tag && (unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(t, 8)) == tag) {
-                const __m128i ol = _mm_or_si128(_mm_and_si128(v, m17), _mm_slli_epi64(_mm_and_si128(_mm_srli_epi64(v, 17), m18), 32)); /* off0 lit0 off1 lit1 */
-                const __m128i ml = _mm_and_si128(_mm_srli_epi64(v, 35), m17);                                                          /* ml0  0    ml1  0    */
-                _mm_storeu_si128((__m128i *)(void *)(dst + j), _mm_unpacklo_epi64(ol, ml));
-                _mm_storeu_si128((__m128i *)(void *)(dst + j + 1), _mm_unpackhi_epi64(ol, ml));
-                j += 2;
-                continue;
-            }
-        }
-        {
-            unsigned long long v = __atomic_load_n(&q[j], __ATOMIC_RELAXED);
-            if (QZSTD_HIP_PACKED_TAG(v) != tag) { /* not there yet: rare */
-                unsigned spins = 0;
-                if (!t0) t0 = qzNowNs();
-                do {
-                    __builtin_ia32_pause();
-                    if ((++spins & 1023u) == 0u && qzNowNs() - t0 > (unsigned long)gProc.timeoutMs * 1000000ul) return 1;
-                    v = __atomic_load_n(&q[j], __ATOMIC_RELAXED);
-                } while (QZSTD_HIP_PACKED_TAG(v) != tag);
-            }
-            if (dst) {
-                dst[j].offset = QZSTD_HIP_PACKED_OFF(v);
-                dst[j].litLength = QZSTD_HIP_PACKED_LIT(v);
-                dst[j].matchLength = QZSTD_HIP_PACKED_ML(v);
-                dst[j].rep = 0;
-            }
-            j++;
-        }
-    }
-    return 0;
-}
-
-/* ---------------------------------------------------------------- announcement batcher -- */
-
-static void qzStageCopy(unsigned char *dst, const unsigned char *src, size_t n);
 
 /* every block of the area has published its count (called with the batcher's lock held) */
 static int qzAreaDone(QZSTD_Area_T *a)
@@ -1171,7 +1392,7 @@ static int qzAreaAlloc(QZSTD_Area_T *a, int dev, int home)
     a->dvSeqs = a->hSeqs ? qzstd_hip_host_device_ptr(a->hSeqs) : NULL;
     if (!a->dvSrc || !a->dvDesc || !a->dvCount || !a->dvSeqs) {
         QZ_LOG(1, "device %d: no pinned memory for a batch area: %s\n", dev, qzstd_hip_last_error());
-        qzstd_hip_host_free(a->hSrc); qzstd_hip_host_free(a->hDesc); qzstd_hip_host_free(a->hCount); qzstd_hip_host_free(a->hSeqs);
+        QZ_HOST_FREE(a->hSrc); QZ_HOST_FREE(a->hDesc); QZ_HOST_FREE(a->hCount); QZ_HOST_FREE(a->hSeqs);
         memset(a, 0, sizeof(*a));
         return -1;
     }
@@ -1251,6 +1472,12 @@ static int qzLaunchArea(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, QZSTD_Area_T *a
     return 0;
 }
 
+/* nothing will publish the area's count words (it is not queued): its blocks' callbacks take the per-block path */
+static void qzAreaFailCounts(QZSTD_Area_T *a)
+{
+    memset(a->hCount, 0xFF, a->nBlocks * sizeof(unsigned int)); /* QZSTD_HIP_NSEQ_ERROR, every word */
+}
+
 /* Issue a collecting area (lock held; held again on return): area `want`, or the open one when want < 0.  Not forced: only once its
  * staging is done and on a FREE stream, else it keeps collecting.  Forced (a callback or a drop needs its blocks) or sealed (full, or
  * another level or grid came): once its staging is done it is queued behind the launch of a busy stream if no stream is free; forced,
@@ -1262,7 +1489,6 @@ static void qzIssueOpen(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, int force, int 
         const int ai = want >= 0 ? want : bt->open;
         QZSTD_Area_T *a;
         int k, pick = -1, busy = 0, rc, go;
-        unsigned int b;
         if (ai < 0) return;
         a = &bt->area[ai];
         if (a->st != QZ_AREA_OPEN || a->nBlocks == 0) return; /* (issued meanwhile, or nothing in it yet) */
@@ -1288,8 +1514,8 @@ static void qzIssueOpen(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, int force, int 
             bt->open = -1;
             __atomic_store_n(&bt->pending, 0, __ATOMIC_RELAXED);
         }
-        if (pick < 0) { /* every stream is quarantined: nothing will run these blocks, their callbacks take the per-block path */
-            for (b = 0; b < a->nBlocks; b++) a->hCount[b] = QZSTD_HIP_NSEQ_ERROR;
+        if (pick < 0) { /* every stream is quarantined: nothing will run these blocks */
+            qzAreaFailCounts(a);
             a->st = QZ_AREA_ISSUED;
             QZ_LOG(1, "device %d: every batch stream is quarantined; a batch of %u blocks is not queued\n", bt->device, a->nBlocks);
             if (a->parts == 0) qzAreaRetire(bt, ai);
@@ -1302,8 +1528,8 @@ static void qzIssueOpen(QZSTD_Session_T *s, QZSTD_Batcher_T *bt, int force, int 
         pthread_mutex_unlock(&bt->mu);
         rc = qzLaunchArea(s, bt, a, &bt->str[pick]);
         pthread_mutex_lock(&bt->mu);
-        if (rc) { /* never launched: nothing will publish these */
-            for (b = 0; b < a->nBlocks; b++) a->hCount[b] = QZSTD_HIP_NSEQ_ERROR;
+        if (rc) { /* never launched */
+            qzAreaFailCounts(a);
             QZ_LOG(1, "device %d: a batch of announced blocks is not queued: %s\n", bt->device, qzstd_hip_last_error());
         }
         a->st = QZ_AREA_ISSUED;
@@ -1393,7 +1619,7 @@ static void qzBatchAdd(QZSTD_Session_T *s, QZSTD_Hint_T *h, int dev, size_t b0, 
             }
             pthread_mutex_unlock(&bt->mu);
             if (fresh.hSrc) { /* (another thread filled the last bare one meanwhile) */
-                qzstd_hip_host_free(fresh.hSrc); qzstd_hip_host_free(fresh.hDesc); qzstd_hip_host_free(fresh.hCount); qzstd_hip_host_free(fresh.hSeqs);
+                QZ_HOST_FREE(fresh.hSrc); QZ_HOST_FREE(fresh.hDesc); QZ_HOST_FREE(fresh.hCount); QZ_HOST_FREE(fresh.hSeqs);
             }
             continue;
         } else if (ai < 0) {
@@ -1600,16 +1826,12 @@ static void qzFreeBatcher(QZSTD_Batcher_T *bt)
     for (k = 0; k < QZ_HB_STREAMS_MAX; k++) {
         QZSTD_BStream_T *q = &bt->str[k];
         if (q->stream) (void)qzstd_hip_stream_wait(bt->device, q->stream, (unsigned)gProc.timeoutMs);
-        qzstd_hip_free(bt->device, q->dSrc);
-        qzstd_hip_free(bt->device, q->dWork);
+        QZ_DEV_FREE(bt->device, q->dSrc); QZ_DEV_FREE(bt->device, q->dWork);
     }
     for (k = 0; k < QZ_HB_AREAS; k++) {
         QZSTD_Area_T *a = &bt->area[k];
         if (a->hSrc) memset(a->hSrc, 0, QZ_HB_SRC_BYTES); /* staged caller data: scrubbed before the pages go back */
-        qzstd_hip_host_free(a->hSrc);
-        qzstd_hip_host_free(a->hDesc);
-        qzstd_hip_host_free(a->hCount);
-        qzstd_hip_host_free(a->hSeqs);
+        QZ_HOST_FREE(a->hSrc); QZ_HOST_FREE(a->hDesc); QZ_HOST_FREE(a->hCount); QZ_HOST_FREE(a->hSeqs);
     }
     for (k = 0; k < QZ_HB_STREAMS_MAX; k++)
         if (bt->str[k].stream) qzstd_hip_stream_destroy(bt->device, bt->str[k].stream);
@@ -1617,653 +1839,151 @@ static void qzFreeBatcher(QZSTD_Batcher_T *bt)
     pthread_cond_destroy(&bt->cv);
 }
 
-void QZSTD_freeSeqProdState(void *sequenceProducerState)
-{
-    QZSTD_Session_T *s = (QZSTD_Session_T *)sequenceProducerState;
-    int k;
-    if (!s) return;
-    __atomic_fetch_sub(&gProc.liveStates, 1, __ATOMIC_RELAXED);
-    QZ_LOG(2, "state %p: %lu block(s) served from announcements, %lu per "
-              "block; %lu hint(s), timers from the 9th on: drop %.2f ms, buffers %.2f ms, staging and queueing %.2f ms (%.2f ms in copy calls, %.2f in launch calls), waited %.2f ms for the GPU\n", (void *)s,
-           s->servedFromBatch, s->servedSync, s->hintCalls, s->hintDropNs / 1e6, s->hintPrepNs / 1e6, s->hintStageNs / 1e6,
-           s->hintCopyCallNs / 1e6, s->hintLaunchCallNs / 1e6, s->hintWaitNs / 1e6);
-    for (k = 0; k < QZ_HINTS; k++) {
-        qzHintDrop(&s->hint[k]);
-        free(s->hint[k].keys);
-    }
-    free(s);
-}
-
-/* ---------------------------------------------------------------- hot path ------- */
-
-/* shared by the producer and the hint: is the device usable?  Counts failures and
- * re-probes every QZ_RETRY_INTERVAL_BLOCKS-th block (reference :1140-1152). */
-static int qzDeviceUsable(QZSTD_Session_T *s)
-{
-    if (gProc.status == QZSTD_OK) return 1;
-    s->failOffloadCnt++;
-    if (s->failOffloadCnt >= QZ_RETRY_INTERVAL_BLOCKS) {
-        s->failOffloadCnt = 0;
-        if (QZSTD_startQatDevice() == QZSTD_OK) return 1;
-        QZ_LOG(1, "tried to restart the device, but failed\n");
-        return 0;
-    }
-    QZ_LOG(1, "the device was not successfully started\n");
-    return 0;
-}
-
-/* a callback is about to return the error code: count it by cause (QZSTD_failStats) */
-static size_t qzFailed(QZSTD_Session_T *s, int cause)
-{
-    if (s) {
-        s->fail[0]++;
-        s->fail[cause > 0 && cause < QZ_CAUSE_N ? cause : QZ_CAUSE_RUNTIME]++;
-    }
-    return ZSTD_SEQUENCE_PRODUCER_ERROR;
-}
-
-/* one block, synchronously, on a slot */
-static size_t qzRunBlock(QZSTD_Slot_T *sl, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
-                         size_t srcSize, int level)
-{
-    const size_t cap = outSeqsCapacity < sl->seqCap ? outSeqsCapacity : sl->seqCap;
-    size_t first, count;
-    int w;
-    memcpy(sl->hSrc, src, srcSize); /* staging copy, reference :1223 */
-    sl->hDesc->srcOff = 0;
-    sl->hDesc->seqOff = 0;
-    sl->hDesc->srcLen = (unsigned int)srcSize;
-    sl->hDesc->seqCap = (unsigned int)cap;
-    sl->hDesc->parseFrom = 0;
-    sl->hDesc->mark = 0;
-    {
-        const size_t work = qzstd_hip_workspace_bytes(level, 1, (unsigned int)srcSize);
-        if (work) sl->dWork = qzGrowDev(sl->device, sl->dWork, &sl->dWorkCap, work);
-        if (work && !sl->dWork) goto fail;
-    }
-    if (qzstd_hip_memcpy_h2d(sl->device, sl->stream, sl->dSrc, sl->hSrc, (srcSize + 15) & ~(size_t)15) ||
-        qzstd_hip_memcpy_h2d(sl->device, sl->stream, sl->dDesc, sl->hDesc, sizeof(*sl->hDesc)) ||
-        qzstd_hip_find_sequences(sl->device, sl->stream, level, sl->dSrc, sl->dDesc, 1, (unsigned int)srcSize,
-                                 sl->dSeqs, sl->dCount, sl->dWork, sl->dWorkCap))
-        goto fail;
-    first = cap < QZ_FIRST_COPY_SEQS ? cap : QZ_FIRST_COPY_SEQS;
-    if (qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hCount, sl->dCount, sizeof(unsigned int)) ||
-        qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hSeqs, sl->dSeqs, first * sizeof(ZSTD_Sequence)))
-        goto fail;
-    w = qzWait(sl->device, sl->stream);
-    if (w == 1) sl->stuck = 1;
-    if (w != 0) goto fail;
-    count = *sl->hCount;
-    if (count == QZSTD_HIP_NSEQ_ERROR || count == 0 || count >= outSeqsCapacity - 1) {
-        QZ_LOG(1, "sequence count %zu does not fit capacity %zu\n", count, outSeqsCapacity);
-        qzCause = QZ_CAUSE_CAPACITY;
-        return ZSTD_SEQUENCE_PRODUCER_ERROR; /* reference :1318-1322 */
-    }
-    if (count > first) {
-        if (qzstd_hip_memcpy_d2h(sl->device, sl->stream, sl->hSeqs + first, sl->dSeqs + first,
-                                 (count - first) * sizeof(ZSTD_Sequence)))
-            goto fail;
-        w = qzWait(sl->device, sl->stream);
-        if (w == 1) sl->stuck = 1;
-        if (w != 0) goto fail;
-    }
-    memcpy(outSeqs, sl->hSeqs, count * sizeof(ZSTD_Sequence));
-    return count;
-fail:
-    QZ_LOG(1, "device request failed: %s\n", qzstd_hip_last_error());
-    return ZSTD_SEQUENCE_PRODUCER_ERROR;
-}
-
-/* buffers of a slot's service requests, first use only; 0 on success (a failure frees what was created) */
-static int qzSetupSlotService(QZSTD_Slot_T *sl)
-{
-    if (sl->vSrc) return 0;
-    sl->vSrc = (unsigned char *)qzHostAlloc(QZSTD_HIP_BLOCK_MAX + 64, sl->device, 1);
-    sl->vSeqs = (ZSTD_Sequence *)qzHostAlloc(QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence), sl->device, 1);
-    if (sl->vSeqs) memset(sl->vSeqs, 0, QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence)); /* (fresh pinned pages may hold marked entries of an earlier life) */
-    sl->vCount = (unsigned int *)qzHostAlloc(QZ_SVC_ITEMS_MAX * sizeof(unsigned int), sl->device, 1);
-    sl->vdSrc = (unsigned char *)qzstd_hip_malloc(sl->device, QZSTD_HIP_BLOCK_MAX + 64);
-    if (!sl->vSrc || !sl->vSeqs || !sl->vCount || !sl->vdSrc) {
-        QZ_LOG(1, "service buffers of a slot on device %d: %s\n", sl->device, qzstd_hip_last_error());
-        qzstd_hip_host_free(sl->vSrc); qzstd_hip_host_free(sl->vSeqs); qzstd_hip_host_free(sl->vCount);
-        qzstd_hip_free(sl->device, sl->vdSrc);
-        sl->vSrc = NULL; sl->vSeqs = NULL; sl->vCount = NULL; sl->vdSrc = NULL;
-        return -1;
-    }
-    memset(sl->vCount, 0xFF, QZ_SVC_ITEMS_MAX * sizeof(unsigned int)); /* "arrived": nothing is outstanding */
-    sl->vItems = 0;
-    return 0;
-}
-
-/*
- * One block through the resident service (qzstd_hip_service_submit): no launch, no stream — the block is staged in the slot's
- * pinned buffer, one 64-byte request goes into the service's ring, workgroups that are already resident parse the block as
- * up to 32 work items (runs of whole segments) and write sequences and, last, the counts into this slot's pinned memory;
- * the caller polls those count words and joins the items' lists (the same join as the batch path's segments).
- * Reference shape: synchronous submit + poll of one request on one DC instance, src/qatseqprod.c:1243-1272.
- * Returns the count, the error code, or QZ_NOT_SERVED (no slot free right now, the level is not served, the service is
- * down or busy with another level): the caller then takes the launch path.
- */
-/* levels >= 5 (exact hash chains): their service requests carry a chain scratch (a launch's scratch is sized by qzstd_hip_workspace_bytes at every level) */
-static int qzIsChainLevel(int level)
-{
-    qzstd_hip_profile_t p;
-    return qzstd_hip_profile_for_level(level, QZSTD_HIP_BLOCK_MAX, &p) == 0 && p.chainDepth != 0;
-}
-
-static size_t qzServiceBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
-                             size_t srcSize, int level)
-{
-    QZSTD_Slot_T *sl;
-    qzstd_hip_svc_req_t rq;
-    size_t itemBytes, nItems, k, out = 0, carry = 0, covered = 0;
-    unsigned long t0, spinNs, limitNs;
-    int i, rc, rejected = 0, bad = 0, wrong = 0, progressive;
-
-    if (!gProc.service || srcSize == 0) return QZ_NOT_SERVED;
-    itemBytes = (size_t)gProc.svcItemBytes;
-    while ((srcSize + itemBytes - 1) / itemBytes > QZ_SVC_ITEMS_MAX) itemBytes *= 2;
-    nItems = (srcSize + itemBytes - 1) / itemBytes;
-    i = qzTryGrabSlot(s->slotHint, dev);
-    if (i < 0) return QZ_NOT_SERVED;
-    sl = &gProc.slots[i];
-    if (sl->vStuck) { /* a request of this slot timed out: usable again once every count word of it has arrived */
-        for (k = 0; k < sl->vItems; k++)
-            if (__atomic_load_n(&sl->vCount[k], __ATOMIC_ACQUIRE) == 0u) { qzReleaseSlot(i); return QZ_NOT_SERVED; }
-        sl->vStuck = 0;
-    }
-    if (qzSetupSlotService(sl) != 0) { qzReleaseSlot(i); return QZ_NOT_SERVED; }
-
-    /* progressive staging (qzstd_hip.h, round 5): where the workers look at a count word before they read its slice, the request is queued
-     * FIRST and the block is copied into the pinned buffer behind it, slice by slice — the staging copy (13 us for 128 KiB) then overlaps
-     * the request's way to the first worker (8 us) instead of standing in front of it */
-    progressive = qzstd_hip_service_progressive(sl->device) == 1;
-    if (!progressive) {
-        memcpy(sl->vSrc, src, srcSize); /* staging copy, reference :1223 */
-        memset(sl->vSrc + srcSize, 0, ((srcSize + 15) & ~(size_t)15) - srcSize);
-    }
-    for (k = 0; k < nItems; k++) sl->vCount[k] = progressive ? QZSTD_HIP_NSEQ_STAGING : 0u;
-    sl->vItems = (unsigned int)nItems;
-    sl->vEpoch = (sl->vEpoch + 1u) & 0xFFFFFFu;
-    if (sl->vEpoch == 0u) {
-        /* the 24-bit epoch starts over: an entry that no request of the last 2^24 overwrote would show a mark that is valid again.
-         * The slot is ours and its previous request is complete (every count word in): wipe the result area once per lap. */
-        memset(sl->vSeqs, 0, QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP * sizeof(ZSTD_Sequence));
-        sl->vEpoch = 1u;
-    }
-    rq.hSrc = sl->vSrc; rq.dSrc = sl->vdSrc; rq.hSeqs = sl->vSeqs; rq.hCount = sl->vCount;
-    rq.srcLen = (uint32_t)srcSize; rq.itemBytes = (uint32_t)itemBytes; rq.nItems = (uint32_t)nItems;
-    rq.seqCapPerItem = (uint32_t)(QZ_SVC_ITEMS_MAX * QZ_SVC_ITEM_CAP / nItems); /* the slot's whole result area, shared out */
-    rq.slot = (uint32_t)i; rq.epoch = sl->vEpoch;
-    rq.dWork = NULL;
-    if (qzIsChainLevel(level)) { /* every item links the block before it in its own scratch */
-        if (!sl->vdWork) sl->vdWork = qzstd_hip_malloc(sl->device, QZSTD_HIP_SVC_WORK_BYTES);
-        if (!sl->vdWork) {
-            memset(sl->vCount, 0xFF, nItems * sizeof(unsigned int));
-            qzReleaseSlot(i);
-            return QZ_NOT_SERVED;
-        }
-        rq.dWork = sl->vdWork;
-    }
-    rc = qzstd_hip_service_submit(sl->device, level, &rq);
-    if (rc != 0) {
-        memset(sl->vCount, 0xFF, nItems * sizeof(unsigned int)); /* nothing outstanding */
-        qzReleaseSlot(i);
-        if (rc > 0) return QZ_NOT_SERVED;
-        QZ_LOG(1, "service request not queued: %s\n", qzstd_hip_last_error());
-        return QZ_NOT_SERVED; /* the launch path may still work */
-    }
-    if (progressive) {
-        for (k = 0; k < nItems; k++) {
-            const size_t from = k * itemBytes, upTo = (k + 1) * itemBytes < srcSize ? (k + 1) * itemBytes : srcSize;
-            unsigned int expect = QZSTD_HIP_NSEQ_STAGING;
-            memcpy(sl->vSrc + from, (const unsigned char *)src + from, upTo - from);
-            if (k + 1 == nItems) memset(sl->vSrc + srcSize, 0, ((srcSize + 15) & ~(size_t)15) - srcSize);
-            /* "slice k is in": only a word that still says STAGING (a request the dispatcher handed back has REJECTED there) */
-            (void)__atomic_compare_exchange_n(&sl->vCount[k], &expect, 0u, 0, __ATOMIC_RELEASE, __ATOMIC_RELAXED);
-        }
-    }
-    /* poll the count words in item order — the items finish roughly in that order (the later, the more history in front of it) — and
-     * JOIN every item's list as it arrives (the trailing literals of one flow into the first sequence of the next): by the time the
-     * last item is in, the rest of the block's list stands.  Busy for svcSpinUs, then naps. */
-    t0 = qzNowNs();
-    /* how long a waiting caller polls before it naps: with a core per caller polling is free and a nap costs its wake-up (level 1, 16 threads on
-     * 16 cores: 12.7 GB/s polling 400 us, 10.5 napping at once); with more callers than cores a poller keeps another caller's entropy stage
-     * off the core (32 threads: 9.5 GB/s polling 400 us, 14.2-14.6 polling 10 us or not at all; 48 threads: 5.6 against 15.1-15.5) */
-    spinNs = (unsigned long)gProc.svcSpinUs * 1000ul;
-    if (!gProc.svcSpinSet && __atomic_load_n(&gProc.liveStates, __ATOMIC_RELAXED) > qzUsableCores()) spinNs = 10000ul;
-    limitNs = (unsigned long)gProc.timeoutMs * 1000000ul;
-    for (k = 0; k < nItems; k++) {
-        unsigned polls = 0;
-        while (__atomic_load_n(&sl->vCount[k], __ATOMIC_ACQUIRE) == 0u) {
-            __builtin_ia32_pause();
-            if ((++polls & 63u) == 0u) {
-                const unsigned long dt = qzNowNs() - t0;
-                if (dt > limitNs) { bad = 1; break; }
-                /* the service may have left with this request in its ring: it is launched again; or for good (another request timed out) */
-                if ((polls & 1023u) == 0u && qzstd_hip_service_poke(sl->device, level) == 2 && __atomic_load_n(&sl->vCount[k], __ATOMIC_ACQUIRE) == 0u) { bad = 1; break; }
-                if (dt > spinNs) { const struct timespec nap = { 0, dt < 20000000ul ? 5000 : 200000 }; nanosleep(&nap, NULL); }
-            }
-        }
-        if (bad) break;
-        if (!wrong) { /* (after a wrong item the rest is only waited for: the slot's buffers are in use until every count is in) */
-            const unsigned int cnt = sl->vCount[k];
-            const ZSTD_Sequence *q = sl->vSeqs + k * rq.seqCapPerItem;
-            if (cnt == QZSTD_HIP_NSEQ_REJECTED) {
-                /* handed back whole: nothing of it was queued.  The dispatcher writes all nItems words with one wave store, but stores
-                 * to pinned host memory can land microseconds apart: the slot is given back only when every word is in — a word
-                 * landing later would be read by the slot's NEXT request as its own (round-3 ADVICE) */
-                size_t m;
-                rejected = 1;
-                for (m = k + 1; m < nItems && !bad; m++) {
-                    unsigned spins = 0;
-                    while (__atomic_load_n(&sl->vCount[m], __ATOMIC_ACQUIRE) == 0u) {
-                        __builtin_ia32_pause();
-                        if ((++spins & 1023u) == 0u && qzNowNs() - t0 > limitNs) { bad = 1; break; }
-                    }
-                }
-                break;
-            }
-            if (cnt == QZSTD_HIP_NSEQ_ERROR || cnt > rq.seqCapPerItem || out + cnt >= outSeqsCapacity - 1) { wrong = 1; continue; } /* capacity rule, reference :1318-1322 */
-            /* The count says how many entries there are, not that they are all there: the entries are stored by eight waves, the
-             * count by a ninth, and on their ways to host memory nothing orders the one behind the others (measured: under load an
-             * item's last entries arrive up to microseconds after its count).  Every entry is ONE 16-byte store that carries the
-             * request's epoch in its fourth word (qzstd_hip_block_t.mark): an entry is taken when it shows it. */
-            {   /* one aligned 16-byte load per entry (it arrived as one store), the mark checked here and masked out of the copy (the pinned
-                 * area keeps it: marks of an earlier lap of the 24-bit epoch are wiped when the epoch starts over, above) */
-                const __m128i keep = _mm_set_epi32(0, -1, -1, -1);
-                __m128i acc = _mm_setzero_si128();
-                size_t j;
-                for (j = 0; j < cnt; j++) {
-                    __m128i v = _mm_load_si128((const __m128i *)(const void *)(q + j));
-                    if ((unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(v, 12)) != rq.epoch) { /* not there yet: rare */
-                        unsigned spins = 0;
-                        do {
-                            __builtin_ia32_pause();
-                            __asm__ volatile("" ::: "memory"); /* (a fresh load every time round) */
-                            if ((++spins & 1023u) == 0u && qzNowNs() - t0 > limitNs) { bad = 1; break; }
-                            v = _mm_load_si128((const __m128i *)(const void *)(q + j));
-                        } while ((unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(v, 12)) != rq.epoch);
-                        if (bad) break;
-                    }
-                    if (j + 1 < cnt) _mm_storeu_si128((__m128i *)(void *)(outSeqs + out + j), _mm_and_si128(v, keep));
-                    acc = _mm_add_epi32(acc, v); /* literal and match lengths add up in lanes 1 and 2 (a block is 128 KiB at most) */
-                }
-                if (bad) break;
-                covered += (size_t)(unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(acc, 4)) + (unsigned int)_mm_cvtsi128_si32(_mm_srli_si128(acc, 8));
-                if (cnt > 1) outSeqs[out].litLength += (unsigned int)carry;
-            }
-            if (cnt > 1) {
-                out += cnt - 1;
-                carry = 0;
-            }
-            carry += q[cnt - 1].litLength;
-        }
-    }
-    if (bad) { /* reference: the 2 s poll limit, :1261-1285 */
-        {
-            unsigned long in[8] = { 0 }, dg[8] = { 0 };
-            (void)qzstd_hip_service_info(sl->device, in);
-            (void)qzstd_hip_service_debug(sl->device, dg);
-            QZ_LOG(1, "device %d: service request not answered after %lu ms (limit %d; service: %lu launch(es), %lu request(s), state %lu; dispatcher: %lu poll(s), "
-                      "%lu request(s) taken, %lu item(s) queued; workers: %lu started, %lu item(s) picked up, %lu finished, %lu gave up on a slice; ring: %lu "
-                      "consumed, %lu reserved, quit %lu, frozen %lu; this request: %zu item(s), level %#x)\n",
-                   sl->device, (qzNowNs() - t0) / 1000000ul, gProc.timeoutMs, in[0], in[1], in[4], dg[0], dg[1], dg[2], dg[3], dg[4], dg[5], in[6], dg[6],
-                   dg[7] & 0x1FFFFFFFFFFFFFFFul, dg[7] >> 62, (dg[7] >> 61) & 1ul, nItems, (unsigned)level);
-        }
-        sl->vStuck = 1;
-        qzstd_hip_service_mark_broken(sl->device);
-        qzReleaseSlot(i);
-        /* the resident kernels are asked to leave and are not used again; THIS block is not lost: it goes through the batches
-         * (whose own wait has the same limit: a device that is really wedged then returns the error, reference :1261-1285) */
-        s->redoneAlone++;
-        return QZ_NOT_SERVED;
-    }
-    if (rejected) { qzReleaseSlot(i); return QZ_NOT_SERVED; }
-    if (wrong) {
-        qzReleaseSlot(i);
-        qzCause = QZ_CAUSE_CAPACITY;
-        return ZSTD_SEQUENCE_PRODUCER_ERROR;
-    }
-    outSeqs[out].offset = 0;
-    outSeqs[out].litLength = (unsigned int)carry;
-    outSeqs[out].matchLength = 0;
-    outSeqs[out].rep = 0;
-    out++;
-    qzReleaseSlot(i);
-    {   /* what arrived has to add up to the block (a wrong result must never reach libzstd, which does not validate sequences by
-         * default): the lengths were added up on the way */
-        const size_t sum = covered;
-        if (sum != srcSize) {
-            QZ_LOG(1, "service result does not add up: %zu of %zu bytes\n", sum, srcSize);
-            for (k = 0; k < nItems; k++) { /* which item: every item's own list adds up to its range */
-                const ZSTD_Sequence *q = sl->vSeqs + k * rq.seqCapPerItem;
-                const size_t from = k * itemBytes, upTo = (k + 1) * itemBytes < srcSize ? (k + 1) * itemBytes : srcSize;
-                size_t isum = 0, j;
-                for (j = 0; j < sl->vCount[k] && j < rq.seqCapPerItem; j++) isum += (size_t)q[j].litLength + q[j].matchLength;
-                if (isum != upTo - from) QZ_LOG(1, "  item %zu of %zu: %u sequences cover %zu of %zu bytes\n", k, nItems, sl->vCount[k], isum, upTo - from);
-            }
-            qzstd_hip_service_mark_broken(sl->device);
-            qzCause = QZ_CAUSE_RUNTIME;
-            return ZSTD_SEQUENCE_PRODUCER_ERROR;
-        }
-    }
-    s->servedService++;
-    __atomic_fetch_add(&gProc.devBlocks[sl->device][2], 1ul, __ATOMIC_RELAXED);
-    return out;
-}
-
-/* one block on a slot of its own (QZSTD_HIP_COALESCE=0, and blocks too dense for a batch) */
-static size_t qzSlotBlock(QZSTD_Session_T *s, int dev, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, const void *src,
-                          size_t srcSize, int level)
-{
-    size_t rc = ZSTD_SEQUENCE_PRODUCER_ERROR;
-    int tries;
-    for (tries = 0; tries < 4; tries++) {
-        const int i = qzGrabSlot(s->slotHint + tries * gProc.numDevices, dev);
-        QZSTD_Slot_T *sl;
-        if (i < 0) {
-            QZ_LOG(1, "failed to grab a slot\n");
-            return ZSTD_SEQUENCE_PRODUCER_ERROR;
-        }
-        sl = &gProc.slots[i];
-        if (sl->stream && qzStillStuck(sl->device, sl->stream, &sl->stuck)) { /* quarantined: try the next one */
-            qzReleaseSlot(i);
-            continue;
-        }
-        if (dev < 0) s->slotHint = i;
-        if (qzSetupSlot(sl) == QZSTD_OK) rc = qzRunBlock(sl, outSeqs, outSeqsCapacity, src, srcSize, level);
-        QZ_LOG(2, "block %zu B level %d -> %zu sequences (slot %d, device %d)\n", srcSize, level & 0xFF, rc, i, sl->device);
-        qzReleaseSlot(i);
-        return rc;
-    }
-    return rc;
-}
-
-size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity,
-                           const void *src, size_t srcSize, const void *dict, size_t dictSize,
-                           int compressionLevel, size_t windowSize)
-{
-    QZSTD_Session_T *s = (QZSTD_Session_T *)sequenceProducerState;
-    size_t rc = ZSTD_SEQUENCE_PRODUCER_ERROR;
-
-    /* guards, reference :1123-1137 */
-    if (windowSize < (srcSize < 32 * 1024 ? srcSize : 32 * 1024) || dictSize > 0 || dict) {
-        QZ_LOG(2, "window %zu too small for block %zu, or dictionary given (%zu)\n", windowSize, srcSize, dictSize);
-        return qzFailed(s, QZ_CAUSE_GUARD);
-    }
-    if (compressionLevel < QZ_LEVEL_MIN || compressionLevel > QZ_LEVEL_MAX) {
-        QZ_LOG(1, "only levels 1-12 can be offloaded, got %d\n", compressionLevel);
-        return qzFailed(s, QZ_CAUSE_GUARD);
-    }
-    if (!s || !outSeqs || !src || srcSize > QZSTD_HIP_BLOCK_MAX || outSeqsCapacity < 3) return qzFailed(s, QZ_CAUSE_GUARD);
-    if (!qzDeviceUsable(s)) return qzFailed(s, QZ_CAUSE_DEVICE_DOWN);
-    qzCause = QZ_CAUSE_RUNTIME; /* until a failing site below says otherwise */
-    if (gProc.hb) { /* a batch collecting while every stream was busy goes out with the first caller that finds one free */
-        int d;
-        for (d = 0; d < gProc.numDevices; d++) qzBatchPoke(s, &gProc.hb[d]);
-    }
-
-    /* Served from an announcement?  (src, srcSize) must start on an announced block grid and
-     * cover one or more whole blocks of it: libzstd 1.5.7 cuts multi-block frames into blocks of 32..128 KiB at 32 KiB
-     * steps, so a finer grid serves several sizes — independently parsed neighbours are simply concatenated, the trailing literals of
-     * one block flowing into the first sequence of the next.  The bytes of the callback must still
-     * equal the staged copy the sequences were computed from (the caller may have reused or changed the buffer
-     * since the announcement): one memcmp per callback, a mismatch drops the announcement — unless the announcer promised to hold
-     * the bytes still (QZSTD_HINT_STABLE); such an announcement serves every block ONCE, going forward: a block asked for a second time
-     * ends it (round-4 ADVICE).  The newest announcement is looked at first: an older
-     * one that names the same addresses never shadows it. */
-    {
-        int order[QZ_HINTS], n = 0, oi, k;
-        for (k = 0; k < QZ_HINTS; k++) { /* live announcements, newest first (insertion sort of at most four) */
-            int j = n++;
-            if (s->hint[k].st == 0) { n--; continue; }
-            while (j > 0 && (int)(s->hint[order[j - 1]].seq - s->hint[k].seq) < 0) { order[j] = order[j - 1]; j--; }
-            order[j] = k;
-        }
-        for (oi = 0; oi < n; oi++) {
-            QZSTD_Hint_T *h = &s->hint[order[oi]];
-            const unsigned char *p = (const unsigned char *)src;
-            size_t rel, b, e, covered = 0, held = 0;
-            int pi, ok = 1, byAddr = 0, same = 1;
-            k = order[oi];
-            if (h->st == 0) continue; /* (dropped further up in this loop) */
-            if (h->level != compressionLevel) continue;
-            if (!h->noAddr && p >= h->base && p + srcSize <= h->base + h->size) { /* by address: the callback names announced memory */
-                rel = (size_t)(p - h->base);
-                b = rel / h->block;
-                byAddr = 1;
-                if (rel % h->block != 0 || b >= h->nb) continue; /* off the grid (libzstd 1.5.7 pre-splits multi-block frames at 32 KiB steps): not served from here */
-                for (e = b; e < h->nb && covered < srcSize; e++) covered += h->size - e * h->block < h->block ? h->size - e * h->block : h->block;
-                if (covered != srcSize || e - b > 8) {
-                    QZ_LOG(3, "announcement %d: block %zu+%zu does not fit the grid (%zu)\n", k, rel, srcSize, h->block);
-                    continue;
-                }
-                if (h->stable && b < h->servedUpTo) {
-                    /* a block of a STABLE announcement asked for a second time: the buffer is being used again (a new job over the
-                     * same memory whose last callbacks never came) — nothing vouches for its bytes any more */
-                    QZ_LOG(2, "announcement %d: block %zu asked for again; dropped\n", k, b);
-                    qzHintDrop(h);
-                    continue;
-                }
-                /* verified: every callback; STABLE: every 16th block served, a sampled check of the announcer's promise (QZSTD_hintBroken).
-                 * (A block that was never staged — its part found no room — is not served; that says nothing about the caller's bytes) */
-                if ((!h->stable || (++s->stableSampler & 15u) == 0u) && (same = qzHintSame(h, b, e, p)) == 0) {
-                    QZ_LOG(h->stable ? 1 : 2, "announcement %d: the buffer changed after it was announced%s; dropped\n", k,
-                           h->stable ? " although it was announced with QZSTD_HINT_STABLE" : "");
-                    if (h->stable) s->stableBroken++;
-                    qzHintDrop(h);
-                    continue;
-                }
-            } else {
-                /* by content: a streaming caller (ZSTD_compressStream2 with small feeds, the zstd CLI) announces the buffer it
-                 * read into, but libzstd hands the producer blocks out of its OWN window buffer.  An announced grid block with
-                 * the same size, the same first and last 8 bytes and — verified — the same bytes serves such a callback
-                 * just as well (the sequences depend on nothing but the block's bytes). */
-                unsigned long long key;
-                if (srcSize < 16 || h->nb > QZ_CONTENT_LOOKUP_BLOCKS || !h->keys) continue;
-                key = qzBlockKey((const unsigned char *)src, srcSize);
-                for (b = 0; b < h->nb; b++)
-                    if (h->keys[b] == key && (h->size - b * h->block < h->block ? h->size - b * h->block : h->block) == srcSize &&
-                        qzHintSame(h, b, b + 1, p) == 1) break;
-                if (b >= h->nb) continue;
-                rel = b * h->block;
-                e = b + 1;
-            }
-            if (same < 0) ok = 0;
-            /* the parts that hold these blocks: wait for this callback's blocks (usually long done) */
-            for (pi = 0; pi < h->nParts; pi++) {
-                QZSTD_Part_T *pt = &h->part[pi];
-                const size_t w0b = b > pt->b0 ? b : pt->b0, w1b = e < pt->b1 ? e : pt->b1;
-                if (w0b >= w1b) continue;
-                held += w1b - w0b;
-                if (pt->st == 1) {
-                    const unsigned long w0 = qzNowNs();
-                    (void)qzPartWait(s, pt, w0b, w1b);
-                    s->hintWaitNs += qzNowNs() - w0;
-                }
-                if (pt->st != 1 && pt->st != 2) ok = 0;
-            }
-            if (held != e - b) ok = 0;
-            if (ok) {
-                const int last = rel + srcSize >= h->size;
-                size_t total = 1, carry = 0, out = 0, bi;
-                int usable = 1;
-                for (bi = b; bi < e; bi++) {
-                    unsigned int idx;
-                    const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
-                    const size_t count = a ? a->hCount[idx] : QZSTD_HIP_NSEQ_ERROR;
-                    if (count == QZSTD_HIP_NSEQ_ERROR || count == 0 || count > h->pitch) { usable = 0; break; }
-                    total += count - 1;
-                }
-                if (usable && total < outSeqsCapacity - 1) {
-                    for (bi = b; bi < e; bi++) {
-                        unsigned int idx;
-                        const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
-                        const qzstd_hip_block_t *d = &a->hDesc[idx];
-                        const size_t count = a->hCount[idx];
-                        const ZSTD_Sequence *q;
-                        if (d->mark & QZSTD_HIP_MARK_COMPACT) {
-                            /* packed entries (8 bytes, 12-bit tag): unpacked into the caller's array as they are taken */
-                            const unsigned long long *q8 = (const unsigned long long *)a->hSeqs + d->seqOff * 2u;
-                            ZSTD_Sequence dl;
-                            if (qzTakePacked(count > 1 ? outSeqs + out : NULL, q8, count - 1, d->mark & 0xFFFu) != 0 ||
-                                qzTakePacked(&dl, q8 + count - 1, 1, d->mark & 0xFFFu) != 0) {
-                                QZ_LOG(1, "announcement: entries of block %zu did not arrive within %d ms of their count\n", bi, gProc.timeoutMs);
-                                usable = 0;
-                                break;
-                            }
-                            if (count > 1) {
-                                outSeqs[out].litLength += (unsigned int)carry;
-                                out += count - 1;
-                                carry = 0;
-                            }
-                            carry += dl.litLength; /* the block's delimiter: its trailing literals */
-                            continue;
-                        }
-                        q = (const ZSTD_Sequence *)a->hSeqs + d->seqOff;
-                        /* completed by its count word: the entries certify themselves one by one (the last one, the delimiter, too) */
-                        if (qzTakeMarked(count > 1 ? outSeqs + out : NULL, q, count - 1, d->mark) != 0 ||
-                            qzTakeMarked(NULL, q + count - 1, 1, d->mark) != 0) {
-                            QZ_LOG(1, "announcement: entries of block %zu did not arrive within %d ms of their count\n", bi, gProc.timeoutMs);
-                            usable = 0;
-                            break;
-                        }
-                        if (count > 1) {
-                            outSeqs[out].litLength += (unsigned int)carry;
-                            out += count - 1;
-                            carry = 0;
-                        }
-                        carry += q[count - 1].litLength; /* the block's delimiter: its trailing literals */
-                    }
-                }
-                if (usable && total < outSeqsCapacity - 1) {
-                    outSeqs[out].offset = 0;
-                    outSeqs[out].litLength = (unsigned int)carry;
-                    outSeqs[out].matchLength = 0;
-                    outSeqs[out].rep = 0;
-                    out++;
-                    s->servedFromBatch++;
-                    h->touched = 1;
-                    h->misses = 0;
-                    if (byAddr && e > h->servedUpTo) h->servedUpTo = e; /* (a block served by content says nothing about where the announcer is) */
-                    if (last && byAddr) qzHintDrop(h); /* last block consumed */
-                    return out;
-                }
-            }
-            /* announced but not served (a failed or timed-out part, a block with too many sequences): the per-block path takes THIS
-             * block; the announcement lives on for its other blocks unless this was the last one.  (Round 5 ended a STABLE announcement
-             * here, waiting for every launch still in flight: one dense block — more sequences than the result pitch holds — then cost
-             * the rest of a 2-4 MiB claim its announcement, a cliff on short-match data (round-5 ADVICE).  Its life is bounded without
-             * that: QZSTD_dropHints at the end of the announcer's job, the asked-twice rule above, the overlap rule of QZSTD_hintSourceEx.) */
-            if (byAddr && rel + srcSize >= h->size) qzHintDrop(h);
-            else if (byAddr && e > h->servedUpTo) h->servedUpTo = e;
-            break;
-        }
-        /* nothing to serve from.  Announcements the caller has walked away from (used, then missed again and again)
-         * are dropped, so that they do not serve stale positions */
-        for (k = 0; k < QZ_HINTS; k++) {
-            QZSTD_Hint_T *h = &s->hint[k];
-            if (h->st != 0 && (h->touched || h->noAddr) && ++h->misses > QZ_HINT_STALE_MISSES) {
-                QZ_LOG(2, "announcement %d: abandoned by the caller; dropped\n", k);
-                qzHintDrop(h);
-            }
-        }
-    }
-
-    /* sticky device per state: a GPU of the calling thread's socket if there is one, states spread round-robin (qzPickHint) */
-    if (s->slotHint < 0) s->slotHint = qzPickHint();
-    rc = qzServiceBlock(s, s->slotHint % gProc.numDevices, outSeqs, outSeqsCapacity, src, srcSize, compressionLevel | gProc.levelFlags);
-    if (rc != QZ_NOT_SERVED) {
-        QZ_LOG(2, "block %zu B level %d -> %zu sequences (service, device %d)\n", srcSize, compressionLevel, rc, s->slotHint % gProc.numDevices);
-    } else if (gProc.coalesce) {
-        rc = qzCoalescedBlock(s, s->slotHint % gProc.numDevices, outSeqs, outSeqsCapacity, src, srcSize,
-                              compressionLevel | gProc.levelFlags);
-        QZ_LOG(2, "block %zu B level %d -> %zu sequences (coalesced, device %d)\n", srcSize, compressionLevel, rc,
-               s->slotHint % gProc.numDevices);
-    } else {
-        rc = qzSlotBlock(s, -1, outSeqs, outSeqsCapacity, src, srcSize, compressionLevel | gProc.levelFlags);
-    }
-    if (rc != ZSTD_SEQUENCE_PRODUCER_ERROR) s->servedSync++;
-    else (void)qzFailed(s, qzCause);
-    return rc;
-}
-
 /* ---------------------------------------------------------------- announcements -- */
 
-/* The staging copy of an announcement (reference: the memcpy into DMA memory, :1222-1227): caller's bytes -> pinned buffer the GPU reads over the
- * bus.  For a STABLE announcement nobody on the host reads the copy again soon (a sampled memcmp at most), so it goes out with STREAMING stores: no
- * read-for-ownership of the destination lines and no 2 MiB of a thread's cache spent on bytes only the GPU wants — with 16 threads staging at
- * once the copies share the socket's memory bandwidth, a third of which the ordinary stores' line fills took.  QZSTD_HIP_STAGE_NT=0: memcpy. */
-static void qzStageCopy(unsigned char *dst, const unsigned char *src, size_t n)
+/* Serving a callback from an announcement: (src, srcSize) must start on an announced block grid and cover one or more whole blocks of it
+ * (libzstd 1.5.7 cuts multi-block frames into blocks of 32..128 KiB at 32 KiB steps, so a finer grid serves several sizes: neighbours are
+ * joined).  Its bytes must still equal the staged copy the sequences were computed from: one memcmp per callback, a mismatch drops the
+ * announcement — unless the announcer promised to hold them still (QZSTD_HINT_STABLE): then every block is served ONCE, going forward. */
+
+/* the state's live announcements, newest first (an older one that names the same addresses never shadows a newer one); returns how many */
+static int qzHintOrder(const QZSTD_Session_T *s, int order[QZ_HINTS])
 {
-    size_t i = 0;
-    if (!gProc.stageNt || n < 4096 || ((uintptr_t)dst & 15u)) { memcpy(dst, src, n); return; }
-    for (; i + 64 <= n; i += 64) {
-        const __m128i a = _mm_loadu_si128((const __m128i *)(const void *)(src + i)), b = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 16)),
-                      c = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 32)), d = _mm_loadu_si128((const __m128i *)(const void *)(src + i + 48));
-        _mm_stream_si128((__m128i *)(void *)(dst + i), a);
-        _mm_stream_si128((__m128i *)(void *)(dst + i + 16), b);
-        _mm_stream_si128((__m128i *)(void *)(dst + i + 32), c);
-        _mm_stream_si128((__m128i *)(void *)(dst + i + 48), d);
+    int n = 0, k;
+    for (k = 0; k < QZ_HINTS; k++) { /* insertion sort of at most four */
+        int j = n;
+        if (s->hint[k].st == 0) continue;
+        while (j > 0 && (int)(s->hint[order[j - 1]].seq - s->hint[k].seq) < 0) { order[j] = order[j - 1]; j--; }
+        order[j] = k;
+        n++;
     }
-    _mm_sfence(); /* streaming stores are weakly ordered: before anything that tells the GPU the bytes are there */
-    if (i < n) memcpy(dst + i, src + i, n - i);
+    return n;
 }
 
-/* grow-only device buffers: returns the (possibly new) pointer, NULL on failure */
-static void *qzGrowDev(int dev, void *old, size_t *cap, size_t need)
+/* the grid blocks [b, e) of announcement h that a callback asks for; rel: its offset in the announced buffer; byAddr: found by address */
+typedef struct { QZSTD_Hint_T *h; size_t b, e, rel; int byAddr; } QZSTD_HintHit_T;
+
+/* Does announcement k hold the callback's bytes?  0 = not here (another level, off its grid, unknown content, or dropped here: a STABLE
+ * block asked for again, bytes that changed); else *hit says where: 1 = all staged, -1 = not all of them (a part found no room). */
+static int qzHintFind(QZSTD_Session_T *s, int k, const unsigned char *p, size_t srcSize, int level, QZSTD_HintHit_T *hit)
 {
-    void *p;
-    if (old && *cap >= need) return old;
-    qzstd_hip_free(dev, old);
-    p = qzstd_hip_malloc(dev, need);
-    *cap = p ? need : 0;
-    return p;
+    QZSTD_Hint_T *h = &s->hint[k];
+    size_t b, e, covered = 0;
+    int same = 1;
+    if (h->st == 0 || h->level != level) return 0;
+    hit->h = h;
+    hit->byAddr = !h->noAddr && p >= h->base && p + srcSize <= h->base + h->size;
+    if (hit->byAddr) { /* by address: the callback names announced memory */
+        hit->rel = (size_t)(p - h->base);
+        b = hit->rel / h->block;
+        if (hit->rel % h->block != 0 || b >= h->nb) return 0; /* off the grid (libzstd 1.5.7 pre-splits multi-block frames at 32 KiB steps): not served from here */
+        for (e = b; e < h->nb && covered < srcSize; e++) covered += h->size - e * h->block < h->block ? h->size - e * h->block : h->block;
+        if (covered != srcSize || e - b > 8) {
+            QZ_LOG(3, "announcement %d: block %zu+%zu does not fit the grid (%zu)\n", k, hit->rel, srcSize, h->block);
+            return 0;
+        }
+        if (h->stable && b < h->servedUpTo) {
+            /* a block of a STABLE announcement asked for a second time: the buffer is being used again (a new job over the
+             * same memory whose last callbacks never came) — nothing vouches for its bytes any more */
+            QZ_LOG(2, "announcement %d: block %zu asked for again; dropped\n", k, b);
+            qzHintDrop(h);
+            return 0;
+        }
+        /* verified: every callback; STABLE: every 16th block served, a sampled check of the announcer's promise (QZSTD_hintBroken) */
+        if ((!h->stable || (++s->stableSampler & 15u) == 0u) && (same = qzHintSame(h, b, e, p)) == 0) {
+            QZ_LOG(h->stable ? 1 : 2, "announcement %d: the buffer changed after it was announced%s; dropped\n", k,
+                   h->stable ? " although it was announced with QZSTD_HINT_STABLE" : "");
+            if (h->stable) s->stableBroken++;
+            qzHintDrop(h);
+            return 0;
+        }
+    } else {
+        /* by content: a streaming caller (ZSTD_compressStream2 with small feeds, the zstd CLI) announces the buffer it
+         * read into, but libzstd hands the producer blocks out of its OWN window buffer.  An announced grid block with
+         * the same size, the same first and last 8 bytes and — verified — the same bytes serves such a callback
+         * just as well (the sequences depend on nothing but the block's bytes). */
+        unsigned long long key;
+        if (srcSize < 16 || h->nb > QZ_CONTENT_LOOKUP_BLOCKS || !h->keys) return 0;
+        key = qzBlockKey(p, srcSize);
+        for (b = 0; b < h->nb; b++)
+            if (h->keys[b] == key && (h->size - b * h->block < h->block ? h->size - b * h->block : h->block) == srcSize &&
+                qzHintSame(h, b, b + 1, p) == 1) break;
+        if (b >= h->nb) return 0;
+        hit->rel = b * h->block;
+        e = b + 1;
+    }
+    hit->b = b; hit->e = e;
+    return same < 0 ? -1 : 1;
 }
 
-int QZSTD_deviceStats(int device, unsigned long stats[4])
+/* Serve the callback from the blocks found (ok: all of them were staged).  Returns the sequence count, 0 when they cannot be served (a
+ * failed or timed-out part, a block with too many sequences): the per-block path then takes THIS block. */
+static size_t qzHintServe(QZSTD_Session_T *s, const QZSTD_HintHit_T *hit, int ok, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity, size_t srcSize)
+{
+    QZSTD_Hint_T *h = hit->h;
+    const size_t b = hit->b, e = hit->e;
+    const int last = hit->byAddr && hit->rel + srcSize >= h->size; /* (a block served by content says nothing about where the announcer is) */
+    QZSTD_Join_T j = { outSeqs, 0, 0, 0 };
+    size_t held = 0, total = 1, bi;
+    int pi;
+    for (pi = 0; pi < h->nParts; pi++) { /* the parts that hold these blocks */
+        QZSTD_Part_T *pt = &h->part[pi];
+        const size_t w0b = b > pt->b0 ? b : pt->b0, w1b = e < pt->b1 ? e : pt->b1;
+        if (w0b >= w1b) continue;
+        held += w1b - w0b;
+        if (pt->st == 1) {
+            const unsigned long w0 = qzNowNs();
+            (void)qzPartWait(s, pt, w0b, w1b);
+            s->hintWaitNs += qzNowNs() - w0;
+        }
+        if (pt->st != 1 && pt->st != 2) ok = 0;
+    }
+    if (held != e - b) ok = 0;
+    for (bi = b; bi < e && ok; bi++) { /* the capacity rule (reference :1318-1322), before anything is copied */
+        unsigned int idx;
+        const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
+        const size_t count = a ? a->hCount[idx] : QZSTD_HIP_NSEQ_ERROR;
+        if (count == QZSTD_HIP_NSEQ_ERROR || count == 0 || count > h->pitch) { ok = 0; break; }
+        total += count - 1;
+    }
+    if (total >= outSeqsCapacity - 1) ok = 0;
+    for (bi = b; bi < e && ok; bi++) { /* completed by its count word: a block's entries certify themselves one by one */
+        unsigned int idx;
+        const QZSTD_Area_T *a = qzHintBlock(h, bi, &idx);
+        const qzstd_hip_block_t *d = &a->hDesc[idx];
+        if (qzJoinPiece(&j, (const unsigned char *)a->hSeqs + d->seqOff * 16u, a->hCount[idx], d->mark, 0ul) != 0) { /* (seqOff: sixteen-byte units) */
+            QZ_LOG(1, "announcement: entries of block %zu did not arrive within %d ms of their count\n", bi, gProc.timeoutMs);
+            ok = 0;
+        }
+    }
+    if (hit->byAddr && e > h->servedUpTo) h->servedUpTo = e;
+    if (!ok) {
+        /* announced but not served: the announcement lives on for its other blocks unless this was the last one.  (Round 5 ended a
+         * STABLE announcement here, waiting for every launch still in flight: one dense block — more sequences than the result pitch
+         * holds — then cost the rest of a 2-4 MiB claim its announcement, a cliff on short-match data (round-5 ADVICE).  Its life is
+         * bounded without that: QZSTD_dropHints at the end of the announcer's job, the asked-twice rule, the overlap rule of
+         * QZSTD_hintSourceEx.) */
+        if (last) qzHintDrop(h);
+        return 0;
+    }
+    s->servedFromBatch++;
+    h->touched = 1;
+    h->misses = 0;
+    if (last) qzHintDrop(h); /* last block consumed */
+    return qzJoinFinish(&j);
+}
+
+/* announcements the caller has walked away from (used, then missed again and again) are dropped, so that they do not serve stale positions */
+static void qzHintReapStale(QZSTD_Session_T *s)
 {
     int k;
-    if (stats) for (k = 0; k < 4; k++) stats[k] = 0;
-    if (stats && device >= 0 && device < gProc.numDevices && device < QZ_MAX_DEVICES)
-    {
-        for (k = 0; k < 3; k++) stats[k] = __atomic_load_n(&gProc.devBlocks[device][k], __ATOMIC_RELAXED);
-        stats[3] = (unsigned long)(gProc.devNode[device] + 1); /* host NUMA node of the GPU + 1 (0 = unknown) */
+    for (k = 0; k < QZ_HINTS; k++) {
+        QZSTD_Hint_T *h = &s->hint[k];
+        if (h->st != 0 && (h->touched || h->noAddr) && ++h->misses > QZ_HINT_STALE_MISSES) {
+            QZ_LOG(2, "announcement %d: abandoned by the caller; dropped\n", k);
+            qzHintDrop(h);
+        }
     }
-    return gProc.numDevices;
-}
-
-void QZSTD_failStats(void *sequenceProducerState, unsigned long stats[8])
-{
-    const QZSTD_Session_T *s = (const QZSTD_Session_T *)sequenceProducerState;
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 8; k++) stats[k] = 0;
-    if (!s) return;
-    stats[0] = s->fail[0];
-    stats[1] = s->fail[QZ_CAUSE_GUARD];
-    stats[2] = s->fail[QZ_CAUSE_DEVICE_DOWN];
-    stats[3] = s->fail[QZ_CAUSE_TIMEOUT];
-    stats[4] = s->fail[QZ_CAUSE_CAPACITY];
-    stats[5] = s->fail[QZ_CAUSE_RUNTIME];
-    stats[6] = s->redoneAlone;
-    stats[7] = s->servedService;
-}
-
-unsigned long QZSTD_hintBroken(void *sequenceProducerState)
-{
-    return sequenceProducerState ? ((const QZSTD_Session_T *)sequenceProducerState)->stableBroken : 0ul;
-}
-
-void QZSTD_hintStats(void *sequenceProducerState, unsigned long stats[4])
-{
-    const QZSTD_Session_T *s = (const QZSTD_Session_T *)sequenceProducerState;
-    if (!stats) return;
-    stats[0] = s ? s->servedFromBatch : 0;
-    stats[1] = s ? s->servedSync : 0;
-    stats[2] = s ? s->hintCalls : 0;
-    stats[3] = s ? s->hintWaitNs / 1000 : 0;
 }
 
 /* Stage a buffer into the announcement batchers and remember it in *h (asynchronous, see QZSTD_hintSource).  The blocks are split
@@ -2389,4 +2109,280 @@ void QZSTD_dropHints(void *sequenceProducerState)
     if (!s) return;
     for (k = 0; k < QZ_HINTS; k++)
         if (s->hint[k].st != 0) qzHintDrop(&s->hint[k]);
+}
+
+/* ---------------------------------------------------------------- lifecycle ------ */
+
+/* Enumerate GPUs and lay the slots out round-robin across them, so that threads whose
+ * hints are consecutive land on different devices (reference: the instance shuffle of
+ * QZSTD_getAndShuffleInstance, :601-630). */
+static int qzBuildSlots(void)
+{
+    int nDev = qzstd_hip_device_count();
+    int perDev, i, b, maxDev;
+    if (nDev <= 0) return QZSTD_FAIL;
+    maxDev = qzEnvInt("QZSTD_HIP_MAX_DEVICES", QZ_MAX_DEVICES, 1, QZ_MAX_DEVICES);
+    if (nDev > maxDev) nDev = maxDev;
+    perDev = qzEnvInt("QZSTD_HIP_SLOTS", QZ_DEFAULT_SLOTS_PER_DEVICE, 1, QZ_MAX_SLOTS / nDev);
+    gProc.slots = (QZSTD_Slot_T *)calloc((size_t)nDev * perDev, sizeof(QZSTD_Slot_T));
+    if (!gProc.slots) return QZSTD_FAIL;
+    gProc.numDevices = nDev;
+    gProc.numSlots = nDev * perDev;
+    memset(gProc.devBlocks, 0, sizeof(gProc.devBlocks));
+    for (i = 0; i < gProc.numSlots; i++) gProc.slots[i].device = i % nDev;
+    gProc.numa = qzEnvInt("QZSTD_HIP_NUMA", 1, 0, 1);
+    gProc.numaThreadNode = qzEnvInt("QZSTD_HIP_NUMA_NODE", -1, -1, 1023);
+    memset(gProc.nodeNext, 0, sizeof(gProc.nodeNext));
+    gProc.anyNext = 0;
+    for (i = 0; i < nDev && i < QZ_MAX_DEVICES; i++) {
+        gProc.devNode[i] = qzstd_hip_device_numa_node(i);
+        QZ_LOG(2, "device %d: host NUMA node %d\n", i, gProc.devNode[i]);
+    }
+    gProc.coalesce = qzEnvInt("QZSTD_HIP_COALESCE", 1, 0, 1);
+    gProc.split = qzEnvInt("QZSTD_HIP_SPLIT", nDev < QZ_HINT_PARTS ? nDev : QZ_HINT_PARTS, 1, nDev < QZ_HINT_PARTS ? nDev : QZ_HINT_PARTS);
+    gProc.coal = (QZSTD_Coalescer_T *)calloc((size_t)nDev, sizeof(QZSTD_Coalescer_T));
+    if (!gProc.coal) return QZSTD_FAIL;
+    for (i = 0; i < nDev; i++) {
+        gProc.coal[i].device = i;
+        gProc.coal[i].open = -1;
+        pthread_mutex_init(&gProc.coal[i].mu, NULL);
+        pthread_cond_init(&gProc.coal[i].cvOpen, NULL);
+        for (b = 0; b < QZ_BATCHES; b++) {
+            pthread_cond_init(&gProc.coal[i].batch[b].cvLead, NULL);
+            pthread_cond_init(&gProc.coal[i].batch[b].cvDone, NULL);
+        }
+    }
+    gProc.hb = (QZSTD_Batcher_T *)calloc((size_t)nDev, sizeof(QZSTD_Batcher_T));
+    if (!gProc.hb) return QZSTD_FAIL;
+    for (i = 0; i < nDev; i++) {
+        gProc.hb[i].device = i;
+        gProc.hb[i].open = -1;
+        pthread_mutex_init(&gProc.hb[i].mu, NULL);
+        pthread_cond_init(&gProc.hb[i].cv, NULL);
+        for (b = 0; b < QZ_HB_STREAMS_MAX; b++) gProc.hb[i].str[b].last = -1;
+    }
+    return QZSTD_OK;
+}
+
+int QZSTD_startQatDevice(void)
+{
+    int status;
+    pthread_mutex_lock(&gProc.mutex);
+    {
+        const char *dbg = getenv("QZSTD_HIP_DEBUG");
+        const char *rep = getenv("QZSTD_HIP_EXT_REPCODES");
+        if (dbg && *dbg) qzLogLevel = atoi(dbg);
+        /* the caller promises ZSTD_c_searchForExternalRepcodes = enable on its CCtx (libzstd's default only
+         * from level 10): repeat-offset aware sequences at every level */
+        gProc.levelFlags = (rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0;
+        gProc.timeoutMs = qzEnvInt("QZSTD_HIP_TIMEOUT_MS", QZ_DEFAULT_TIMEOUT_MS, 1, 600000);
+        gProc.splitBlocks = qzEnvInt("QZSTD_HIP_SPLIT_BLOCKS", 1, 0, 1);
+        gProc.service = qzEnvInt("QZSTD_HIP_SERVICE", 1, 0, 1);
+        gProc.svcItemBytes = qzEnvInt("QZSTD_HIP_SERVICE_ITEM", 4096, 4096, (int)QZSTD_HIP_BLOCK_MAX) & ~4095;
+        gProc.svcSpinUs = qzEnvInt("QZSTD_HIP_SERVICE_SPIN_US", 400, 0, 1000000);
+        gProc.svcSpinSet = getenv("QZSTD_HIP_SERVICE_SPIN_US") != NULL;
+        /* announcements: PACKED result entries (qzstd_hip.h: QZSTD_HIP_MARK_COMPACT) — 8 bytes per sequence over PCIe instead of 16 (round 6: the
+         * level-1 kernel ran at the bus's write rate).  0 = 16-byte entries (A/B) */
+        gProc.hintCompact = qzEnvInt("QZSTD_HIP_HINT_COMPACT", 1, 0, 1);
+        /* announcement launches in flight per GPU (the batcher's streams): the runtime's default hardware queue count */
+        gProc.hintBatches = qzEnvInt("QZSTD_HIP_HINT_BATCHES", 4, 1, QZ_HB_STREAMS_MAX);
+        gProc.stageNt = qzEnvInt("QZSTD_HIP_STAGE_NT", 1, 0, 1);
+        gProc.hintDirect = qzEnvInt("QZSTD_HIP_HINT_DIRECT", 0, 0, 3);
+        (void)qzUsableCores(); /* (read once here, under the process mutex: the waits only load it) */
+    }
+    if (gProc.status == QZSTD_FAIL) {
+        /* runtime up? (reference: QZSTD_salUserStart, :498-527) */
+        gProc.status = qzstd_hip_device_count() > 0 ? QZSTD_STARTED : QZSTD_FAIL;
+        if (gProc.status == QZSTD_FAIL) QZ_LOG(2, "no usable HIP device: %s\n", qzstd_hip_last_error());
+    }
+    if (gProc.status == QZSTD_STARTED) {
+        gProc.status = qzBuildSlots() == QZSTD_OK ? QZSTD_OK : QZSTD_STARTED;
+    }
+    QZ_LOG(2, "start: status %d, %d device(s), %d slot(s)\n", gProc.status, gProc.numDevices, gProc.numSlots);
+    status = gProc.status;
+    pthread_mutex_unlock(&gProc.mutex);
+    return status;
+}
+
+void QZSTD_stopQatDevice(void)
+{
+    int i;
+    pthread_mutex_lock(&gProc.mutex);
+    for (i = 0; i < gProc.numDevices; i++) (void)qzstd_hip_service_stop(i); /* the resident kernels leave before anything is freed */
+    if (gProc.slots) {
+        for (i = 0; i < gProc.numSlots; i++) qzFreeSlot(&gProc.slots[i]); /* waits (bounded) for each stream */
+        free(gProc.slots);
+    }
+    if (gProc.hb) {
+        for (i = 0; i < gProc.numDevices; i++) qzFreeBatcher(&gProc.hb[i]); /* waits (bounded) for each stream */
+        free(gProc.hb);
+    }
+    gProc.hb = NULL;
+    qzReapOrphans(1); /* (after the bounded waits for the streams the parked areas' kernels ran on) */
+    gProc.gen++; /* parts staged so far refer to nothing any more */
+    if (gProc.coal) {
+        for (i = 0; i < gProc.numDevices; i++) qzFreeCoalescer(&gProc.coal[i]);
+        free(gProc.coal);
+    }
+    gProc.coal = NULL;
+    gProc.slots = NULL;
+    gProc.numSlots = 0;
+    gProc.numDevices = 0;
+    gProc.status = QZSTD_FAIL;
+    pthread_mutex_unlock(&gProc.mutex);
+}
+
+void *QZSTD_createSeqProdState(void)
+{
+    QZSTD_Session_T *s = (QZSTD_Session_T *)calloc(1, sizeof(QZSTD_Session_T));
+    if (!s) return NULL;
+    s->slotHint = -1;
+    __atomic_fetch_add(&gProc.liveStates, 1, __ATOMIC_RELAXED);
+    return s;
+}
+
+void QZSTD_freeSeqProdState(void *sequenceProducerState)
+{
+    QZSTD_Session_T *s = (QZSTD_Session_T *)sequenceProducerState;
+    int k;
+    if (!s) return;
+    __atomic_fetch_sub(&gProc.liveStates, 1, __ATOMIC_RELAXED);
+    QZ_LOG(2, "state %p: %lu block(s) served from announcements, %lu per "
+              "block; %lu hint(s), timers from the 9th on: drop %.2f ms, buffers %.2f ms, staging and queueing %.2f ms (%.2f ms in copy calls, %.2f in launch calls), waited %.2f ms for the GPU\n", (void *)s,
+           s->servedFromBatch, s->servedSync, s->hintCalls, s->hintDropNs / 1e6, s->hintPrepNs / 1e6, s->hintStageNs / 1e6,
+           s->hintCopyCallNs / 1e6, s->hintLaunchCallNs / 1e6, s->hintWaitNs / 1e6);
+    for (k = 0; k < QZ_HINTS; k++) {
+        qzHintDrop(&s->hint[k]);
+        free(s->hint[k].keys);
+    }
+    free(s);
+}
+
+int QZSTD_deviceStats(int device, unsigned long stats[4])
+{
+    int k;
+    if (stats) for (k = 0; k < 4; k++) stats[k] = 0;
+    if (stats && device >= 0 && device < gProc.numDevices && device < QZ_MAX_DEVICES)
+    {
+        for (k = 0; k < 3; k++) stats[k] = __atomic_load_n(&gProc.devBlocks[device][k], __ATOMIC_RELAXED);
+        stats[3] = (unsigned long)(gProc.devNode[device] + 1); /* host NUMA node of the GPU + 1 (0 = unknown) */
+    }
+    return gProc.numDevices;
+}
+
+void QZSTD_failStats(void *sequenceProducerState, unsigned long stats[8])
+{
+    const QZSTD_Session_T *s = (const QZSTD_Session_T *)sequenceProducerState;
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 8; k++) stats[k] = 0;
+    if (!s) return;
+    stats[0] = s->fail[0];
+    stats[1] = s->fail[QZ_CAUSE_GUARD];
+    stats[2] = s->fail[QZ_CAUSE_DEVICE_DOWN];
+    stats[3] = s->fail[QZ_CAUSE_TIMEOUT];
+    stats[4] = s->fail[QZ_CAUSE_CAPACITY];
+    stats[5] = s->fail[QZ_CAUSE_RUNTIME];
+    stats[6] = s->redoneAlone;
+    stats[7] = s->servedService;
+}
+
+unsigned long QZSTD_hintBroken(void *sequenceProducerState)
+{
+    return sequenceProducerState ? ((const QZSTD_Session_T *)sequenceProducerState)->stableBroken : 0ul;
+}
+
+void QZSTD_hintStats(void *sequenceProducerState, unsigned long stats[4])
+{
+    const QZSTD_Session_T *s = (const QZSTD_Session_T *)sequenceProducerState;
+    if (!stats) return;
+    stats[0] = s ? s->servedFromBatch : 0;
+    stats[1] = s ? s->servedSync : 0;
+    stats[2] = s ? s->hintCalls : 0;
+    stats[3] = s ? s->hintWaitNs / 1000 : 0;
+}
+
+#ifdef QZ_TEST_HOOKS /* the mock build of tests/test_host_mock.py only: never in the release library */
+unsigned long qzstd_test_orphans(void) { return qzOrphanCount; }
+void qzstd_test_set_area_tags(unsigned int e) /* the next use of every batch area, every GPU, gets tag e + 1 (the wrap) */
+{
+    int d, k;
+    for (d = 0; gProc.hb && d < gProc.numDevices; d++) {
+        pthread_mutex_lock(&gProc.hb[d].mu);
+        for (k = 0; k < QZ_HB_AREAS; k++) gProc.hb[d].area[k].lap = e & 0xFFFFFFu;
+        pthread_mutex_unlock(&gProc.hb[d].mu);
+    }
+}
+/* the hook's name from the time announcements kept their own result areas and epochs (tests/test_host_mock.py calls it): the tags now belong to
+ * the batch areas, which every state shares, so `state` names nothing and every area's tag moves */
+void qzstd_test_set_hint_epochs(void *state, unsigned int e)
+{
+    (void)state;
+    qzstd_test_set_area_tags(e);
+}
+unsigned long qzstd_test_hint_launches(void) /* announcement launches since the device layer started, every GPU */
+{
+    unsigned long n = 0;
+    int d;
+    for (d = 0; gProc.hb && d < gProc.numDevices; d++) n += __atomic_load_n(&gProc.hb[d].launches, __ATOMIC_RELAXED);
+    return n;
+}
+void qzstd_test_set_service_epochs(unsigned int e) /* every slot's next service request gets epoch e + 1 (the 24-bit wrap) */
+{
+    int i;
+    for (i = 0; gProc.slots && i < gProc.numSlots; i++) gProc.slots[i].vEpoch = e & 0xFFFFFFu;
+}
+#endif
+
+/* ---------------------------------------------------------------- producer ------- */
+
+size_t qatSequenceProducer(void *sequenceProducerState, ZSTD_Sequence *outSeqs, size_t outSeqsCapacity,
+                           const void *src, size_t srcSize, const void *dict, size_t dictSize,
+                           int compressionLevel, size_t windowSize)
+{
+    QZSTD_Session_T *s = (QZSTD_Session_T *)sequenceProducerState;
+    size_t rc;
+    int order[QZ_HINTS], n, oi, dev, found;
+
+    /* guards, reference :1123-1137 */
+    if (windowSize < (srcSize < 32 * 1024 ? srcSize : 32 * 1024) || dictSize > 0 || dict) {
+        QZ_LOG(2, "window %zu too small for block %zu, or dictionary given (%zu)\n", windowSize, srcSize, dictSize);
+        return qzFailed(s, QZ_CAUSE_GUARD);
+    }
+    if (compressionLevel < QZ_LEVEL_MIN || compressionLevel > QZ_LEVEL_MAX) {
+        QZ_LOG(1, "only levels 1-12 can be offloaded, got %d\n", compressionLevel);
+        return qzFailed(s, QZ_CAUSE_GUARD);
+    }
+    if (!s || !outSeqs || !src || srcSize > QZSTD_HIP_BLOCK_MAX || outSeqsCapacity < 3) return qzFailed(s, QZ_CAUSE_GUARD);
+    if (!qzDeviceUsable(s)) return qzFailed(s, QZ_CAUSE_DEVICE_DOWN);
+    qzCause = QZ_CAUSE_RUNTIME; /* until a failing site below says otherwise */
+    /* a batch collecting while every stream was busy goes out with the first caller that finds one free */
+    for (dev = 0; gProc.hb && dev < gProc.numDevices; dev++) qzBatchPoke(s, &gProc.hb[dev]);
+
+    /* served from an announcement?  The first one that holds the block decides: what it cannot serve, the per-block path takes */
+    n = qzHintOrder(s, order);
+    for (oi = 0; oi < n; oi++) {
+        QZSTD_HintHit_T hit;
+        if ((found = qzHintFind(s, order[oi], (const unsigned char *)src, srcSize, compressionLevel, &hit)) == 0) continue;
+        rc = qzHintServe(s, &hit, found > 0, outSeqs, outSeqsCapacity, srcSize);
+        if (rc != 0) return rc;
+        break;
+    }
+    qzHintReapStale(s); /* nothing to serve from */
+
+    /* sticky device per state: a GPU of the calling thread's socket if there is one, states spread round-robin (qzPickHint) */
+    if (s->slotHint < 0) s->slotHint = qzPickHint();
+    dev = s->slotHint % gProc.numDevices;
+    rc = qzServiceBlock(s, dev, outSeqs, outSeqsCapacity, src, srcSize, compressionLevel | gProc.levelFlags);
+    if (rc != QZ_NOT_SERVED) {
+        QZ_LOG(2, "block %zu B level %d -> %zu sequences (service, device %d)\n", srcSize, compressionLevel, rc, dev);
+    } else if (gProc.coalesce) {
+        rc = qzCoalescedBlock(s, dev, outSeqs, outSeqsCapacity, src, srcSize, compressionLevel | gProc.levelFlags);
+        QZ_LOG(2, "block %zu B level %d -> %zu sequences (coalesced, device %d)\n", srcSize, compressionLevel, rc, dev);
+    } else {
+        rc = qzSlotBlock(s, -1, outSeqs, outSeqsCapacity, src, srcSize, compressionLevel | gProc.levelFlags);
+    }
+    if (rc != ZSTD_SEQUENCE_PRODUCER_ERROR) s->servedSync++;
+    else (void)qzFailed(s, qzCause);
+    return rc;
 }

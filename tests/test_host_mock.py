@@ -858,6 +858,27 @@ def test_service_coarser_items_and_other_levels(mock, zstd, oracle):
         L.qzstd_mock_service_level(0)
 
 
+def test_service_joins_delimiter_only_items(mock, zstd, oracle):
+    """The join's edge: a work item that holds no match is nothing but its delimiter — it copies nothing and only carries its literals
+    on to the first sequence of the next item that has one.  A block whose sixth and seventh 4 KiB are incompressible goes through the
+    service as 32 items of 4 KiB: two delimiter-only items in a row between non-empty ones (the oracle's own segment parse says so), and
+    the joined list is still the whole block's."""
+    import random
+    chunk, item = 131072, 4096
+    text = K.by_name("system", chunk, seed=5)
+    data = text[:5 * item] + random.Random(11).randbytes(2 * item) + text[7 * item:]
+    prof = oracle.profile(1, chunk)
+    counts = [oracle.find(prof, data[:(k + 1) * item], parse_from=k * item)[0] for k in range(4, 8)]
+    assert counts[1] == 1 and counts[2] == 1 and counts[0] > 1 and counts[3] > 1, counts
+    buf = (C.c_char * len(data)).from_buffer_copy(data)
+    with restarted(mock, QZSTD_HIP_SERVICE_ITEM="4096"):
+        st = mock.lib.QZSTD_createSeqProdState()
+        assert frames_of(zstd, mock.producer_addr, st, C.addressof(buf), chunk, chunk, 1) == oracle_frames(zstd, oracle, data, chunk, 1)
+        fs = fail_stats(mock, st)
+        mock.lib.QZSTD_freeSeqProdState(st)
+    assert fs[0] == 0 and fs[7] == 1, fs
+
+
 @pytest.mark.parametrize("level,chunk", [(1, 131072), (2, 100001), (6, 131072), (12, 32768), (1, 5000)])
 def test_service_progressive_staging(mock, zstd, oracle, level, chunk):
     """round 5 (include/qzstd_hip.h: QZSTD_HIP_NSEQ_STAGING): where the device layer's workers look at a count word before they read
