@@ -18,7 +18,8 @@ extern "C" {
  * read before the work queued on it so far completes.  Returns the frame count or (size_t)-1.  Blocks until done; d_src must stay
  * valid and unchanged until then.
  *
- * The GPU match-finds the input in parts of whole chunks (at most 64 MiB) and packs each part's sequences and literal bytes into one
+ * The GPU match-finds the input in parts of whole chunks (at most 64 MiB; a part that is not 16-byte aligned throughout is copied to
+ * library memory first) and packs each part's sequences and literal bytes into one
  * dense arena (qzstd_hip_compact) that comes back in one copy; the workers build the frames from it with
  * ZSTD_compressSequencesAndLiterals (explicit block delimiters, one 128 KiB block per delimiter) while the GPU works on the next
  * parts.  A frame with a block libzstd would store raw, or a failed block, is built from its raw bytes, copied back.  Errors that return before
@@ -30,6 +31,27 @@ size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSi
  * a matcher error, or a libzstd without ZSTD_compressSequencesAndLiterals), [2] bytes copied device->host, [3] bytes of input of the calls
  * that succeeded */
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4]);
+
+/* A batch of device buffers of any sizes and alignments, wherever the allocator put them (a checkpoint's tensors, column buffers), in ONE
+ * call.  Buffer i becomes frames firstFrame[i] .. firstFrame[i + 1] - 1, cut every chunkSize bytes OF THAT BUFFER (an empty buffer yields
+ * none): byte for byte the frames QZSTD_frontCompressDevice(f, bufs[i].d_ptr, bufs[i].size, ...) produces, whatever its neighbours are.
+ * Frame c at dst + c * QZSTD_frontFrameStride(), its size in frameSizes[c]; firstFrame (nBufs + 1 entries) may be NULL.  The GPU's parts are
+ * filled across buffer boundaries (at most 64 MiB of input each, whole frames): thousands of small buffers share one descriptor upload,
+ * one gather launch (qzstd_hip_gather: the part's frames copied to 16-aligned places of library memory), one match-finder launch, one
+ * compaction, one arena copy and one job of the workers.  `stream`, blocking and the validity of the buffers: as QZSTD_frontCompressDevice.
+ * Returns the frame count (0 for no buffers or empty ones: no GPU is touched) or (size_t)-1.  Errors that return before anything is
+ * queued: dst below frames x stride, a front created with useProducer = 0, bufs NULL with nBufs > 0, a NULL buffer of a size above 0, a
+ * buffer whose first or last byte is not device memory, buffers of different devices, a call while another one runs on this front, a
+ * device layer without qzstd_hip_gather.  QZSTD_frontDeviceStats counts a batch as the single calls: [3] grows by the sum of the sizes. */
+typedef struct {
+    const void *d_ptr; /* device address, any alignment */
+    size_t size;       /* bytes, may be 0 */
+} QZSTD_DeviceBuf;
+/* frames the batch yields: the sum over i of ceil(size_i / chunkSize) — what dst (x QZSTD_frontFrameStride()) and frameSizes must hold;
+ * (size_t)-1 for f NULL or bufs NULL with nBufs > 0 */
+size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs);
+size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream,
+                                      void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame);
 
 #if defined(__cplusplus)
 }

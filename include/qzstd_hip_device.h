@@ -1,6 +1,7 @@
 /*
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
- * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy and the compaction kernel.
+ * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
+ * (QZSTD_frontCompressDeviceBatch).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -47,6 +48,29 @@ typedef struct {
 size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks);
 int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
                       const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work, size_t workBytes);
+
+/*
+ * Gather: ONE launch copies every row — nRows byte ranges anywhere in device memory, at any alignment — to its place in a staging buffer
+ * and writes `pad` zero bytes behind it, so that a part made of many buffers lies in 16-aligned pieces as the match-finder reads them.
+ * Work is divided by bytes of the stage (16 KiB per workgroup, the row of every 16-byte word found by a binary search over dstOff), not by
+ * rows: rows of one byte and rows of a MiB in one launch keep the device equally busy.  Stores are aligned 16-byte stores; loads are aligned
+ * 16-byte loads of the words that overlap [src, src + len) and of no other word, shifted into place in registers.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous) and must stay unchanged until the stream has passed the call; the
+ * launcher checks it and uploads it to d_rows, device scratch of nRows entries.  Refused (< 0) before anything is queued: a null
+ * rows, d_rows or d_stage, d_stage not 16-aligned, a dstOff or a len + pad that is no multiple of 16, a null src with len > 0, a row
+ * that ends past stageBytes, rows that are not in ascending stage order or overlap there (dstOff[i] >= dstOff[i-1] + len[i-1] + pad[i-1]),
+ * a stage span of 64 GiB or more (the kernel counts 16-byte words in 32 bits).  Stage bytes between rows are left as they are.
+ * No row may overlap the stage in memory.  nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t src;    /* device address of the row's first byte, any alignment */
+    uint64_t dstOff; /* byte offset in d_stage, a multiple of 16 */
+    uint32_t len;    /* bytes to copy, may be 0 */
+    uint32_t pad;    /* zero bytes written behind them; len + pad is a multiple of 16 */
+} qzstd_hip_gather_row_t;
+int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
+                     void *d_stage, size_t stageBytes);
 
 #if defined(__cplusplus)
 }

@@ -3612,3 +3612,92 @@ int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_h
 }
 
 } /* extern "C" */
+
+/* ---------------------------------------------------------------- gather (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kGatherT = 256u;               /* threads per workgroup */
+constexpr uint32_t kGatherWords = 4u * kGatherT;  /* 16-byte words of the stage per workgroup: 16 KiB */
+
+/* the last row of [lo, hi] whose first word is at or before word w (lo when there is none) */
+__device__ inline uint32_t gather_row_of(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t lo, uint32_t hi, uint32_t w)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if ((uint32_t)(rows[mid].dstOff >> 4) <= w) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+/* one workgroup per 16 KiB of the stage between the first row's start and the last row's end; a lane takes every 256th word.  The rows that
+ * reach into the workgroup's piece are found once (two searches over all rows), a word's own row by a search among those: no step at all
+ * inside a long row, at most ten where 1024 one-word rows share the piece */
+__global__ __launch_bounds__(kGatherT) void qzstd_gather_kernel(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t nRows, uint32_t firstWord,
+                                                                uint32_t endWord, uint4 *__restrict__ stage)
+{
+    __shared__ uint32_t span[2];
+    const uint32_t w0 = firstWord + blockIdx.x * kGatherWords;
+    const uint32_t wEnd = endWord - w0 < kGatherWords ? endWord : w0 + kGatherWords;
+    if (threadIdx.x == 0) {
+        span[0] = gather_row_of(rows, 0u, nRows - 1u, w0);
+        span[1] = gather_row_of(rows, span[0], nRows - 1u, wEnd - 1u);
+    }
+    __syncthreads();
+    const uint32_t rLo = span[0], rHi = span[1];
+    for (uint32_t w = w0 + threadIdx.x; w < wEnd; w += kGatherT) {
+        const qzstd_hip_gather_row_t row = rows[gather_row_of(rows, rLo, rHi, w)];
+        const uint64_t o = ((uint64_t)w << 4) - row.dstOff; /* the word's first byte in its row (wraps to a huge value in front of row 0) */
+        if (o >= (uint64_t)row.len + row.pad) continue;     /* between two rows: not ours to write */
+        uint64_t o0 = 0, o1 = 0;
+        if (o < row.len) {
+            const uint64_t a = row.src + o;
+            const uint32_t sh = (uint32_t)a & 15u;
+            const uint32_t valid = row.len - o < 16u ? (uint32_t)(row.len - o) : 16u; /* payload bytes of this word */
+            const uint4 *p = reinterpret_cast<const uint4 *>(a - sh);
+            /* the aligned word that holds byte a, and the next one only when payload of this word lies in it */
+            const uint4 l = p[0];
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh + valid > 16u) h = p[1];
+            const uint64_t l0 = l.x | (uint64_t)l.y << 32, l1 = l.z | (uint64_t)l.w << 32, h0 = h.x | (uint64_t)h.y << 32, h1 = h.z | (uint64_t)h.w << 32;
+            /* {h1 h0 l1 l0} >> 8 * sh: whole 64-bit halves first, then the bytes */
+            const bool half = (sh & 8u) != 0u;
+            const uint32_t bits = (sh & 7u) * 8u;
+            const uint64_t a0 = half ? l1 : l0, a1 = half ? h0 : l1, a2 = half ? h1 : h0;
+            o0 = bits ? (a0 >> bits) | (a1 << (64u - bits)) : a0;
+            o1 = bits ? (a1 >> bits) | (a2 << (64u - bits)) : a1;
+            if (valid < 16u) { /* the row's last word: zero behind the payload (what the shift brought in lies inside the aligned words read) */
+                o1 = valid > 8u ? o1 & ((1ull << ((valid - 8u) * 8u)) - 1ull) : 0ull;
+                if (valid < 8u) o0 &= (1ull << (valid * 8u)) - 1ull;
+            }
+        }
+        stage[w] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
+                                void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_gather: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_gather_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_gather: dstOff or len + pad not a multiple of 16");
+        if (r.len && !r.src) return fail_msg("qzstd_hip_gather: null source");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_gather: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_gather: a row ends past stageBytes");
+        end = r.dstOff + ext;
+    }
+    /* 16-byte words in 32 bits, with room for a workgroup's last step */
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_gather: stage span too large");
+    const uint32_t firstWord = (uint32_t)(rows[0].dstOff >> 4), endWord = (uint32_t)(end >> 4);
+    if (endWord == firstWord) return 0; /* nothing but empty rows */
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (gather rows)");
+    const uint32_t groups = (endWord - firstWord + kGatherWords - 1u) / kGatherWords;
+    hipLaunchKernelGGL(qzstd_gather_kernel, dim3(groups), dim3(kGatherT), 0, (hipStream_t)stream, d_rows, nRows, firstWord, endWord,
+                       static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_gather_kernel");
+    return 0;
+}

@@ -337,7 +337,9 @@ void QZSTD_freeFront(QZSTD_Front *f)
 
 /* ---------------------------------------------------------------- device-resident input -- */
 /*
- * QZSTD_frontCompressDevice: the input is cut into PARTS of whole chunks (at most QF_PART_BYTES).  Per part, on one of two device slots:
+ * QZSTD_frontCompressDevice / QZSTD_frontCompressDeviceBatch: every buffer is cut into frames of chunkSize (the per-frame table, QF_DevFrame) and
+ * the frames, across buffer boundaries, into PARTS of whole frames (at most QF_PART_BYTES of input).  A part that is one buffer's 16-aligned
+ * chunks is read where it lies; any other is gathered into the slot's stage first (qzstd_hip_gather).  Per part, on one of two device slots:
  * the match-finder (qzstd_hip_find_sequences), the compaction (qzstd_hip_compact: packed entries + literal bytes in one dense arena), the
  * arena's headers and then the arena itself D2H into pinned memory.  The workers entropy-code part k straight from its arena
  * (ZSTD_compressSequencesAndLiterals) while the GPU works on parts k + 1 and k + 2.  The calling thread does the GPU side.
@@ -356,6 +358,8 @@ extern size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks) __attribute__(
 extern int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
                              const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work,
                              size_t workBytes) __attribute__((weak));
+extern int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
+                            void *d_stage, size_t stageBytes) __attribute__((weak));
 
 #define QF_PART_BYTES ((size_t)64 << 20)
 #define QF_DEV_WAIT_MS 60000u
@@ -387,7 +391,9 @@ static void qfResolveSeqApi(void)
 /* one device slot: a part's buffers, device and pinned */
 struct QF_DevSlot_s {
     void *stream;
-    unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned blocks, when the caller's buffer cannot be read in place */
+    unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned frames, when the caller's buffers cannot be read in place */
+    qzstd_hip_gather_row_t *hRows; size_t hRowsCap; /* the gather's rows, one per frame (pinned), and their device copy */
+    void *dRows; size_t dRowsCap;
     qzstd_hip_block_t *hDesc; size_t hDescCap;
     void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
     size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
@@ -396,20 +402,36 @@ struct QF_DevSlot_s {
     const unsigned char *hLit; size_t litTotal; /* the arena's literal bytes, in hArena */
 };
 
+/* one frame of a device job (the per-frame table, built once per call): where its bytes lie and which blocks of its part are its own */
+typedef struct {
+    size_t off, len; /* offset in its buffer, length (chunkSize, or what is left of the buffer) */
+    size_t b0;       /* first block in its part */
+    uint32_t buf;    /* owning buffer */
+    uint32_t nb;     /* blocks: ceil(len / 128 KiB) */
+} QF_DevFrame;
+
+/* a part: frames [f0, f1) of the job, matched in one launch */
+typedef struct {
+    size_t f0, f1, nb, bytes;
+    int run; /* the frames are consecutive chunks of ONE buffer: readable in place when aligned, stageable by 2D copies */
+} QF_DevRange;
+
 struct QF_DevPart_s {
-    const unsigned char *dSrc;  /* the caller's buffer (the raw-bytes path reads its chunks from there) */
-    size_t c0, c1;              /* chunks of the job */
-    size_t nb, bpc;             /* blocks, blocks per chunk */
+    const QZSTD_DeviceBuf *bufs; /* the caller's buffers (the raw-bytes path reads a frame from its own) */
+    const QF_DevFrame *frames;   /* the job's table */
+    size_t f0, f1;               /* frames of the job */
+    size_t nb;                   /* blocks */
     const QF_DevSlot *slot;
     int dev;
 };
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
-    void *d[] = { s->dStage, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena };
+    void *d[] = { s->dStage, s->dRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
+    if (s->hRows) qzstd_hip_host_free(s->hRows);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
     if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
     free(s->blkSeq);
@@ -446,23 +468,64 @@ static int qfGrowH(void **p, size_t *cap, size_t need)
 
 typedef struct {
     QZSTD_Front *f;
-    const unsigned char *dSrc;
-    size_t srcSize, partChunks, bpc;
+    const QZSTD_DeviceBuf *bufs;
+    const QF_DevFrame *frames; /* the per-frame table: frame c of the job */
+    const QF_DevRange *parts;
+    size_t nParts, blk;        /* blk: the launches' largest block, min(chunkSize, 128 KiB) */
     int dev, level;
 } QF_DevJob;
 
-/* queues part p (chunks [c0, c1)) on slot s: staging copy if needed, match-finder, compaction.  Device side only: the slot's pinned
- * arena may still be read by the workers (the part fetched from it before) */
-static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1)
+static size_t qfPad16(size_t n) { return (n + 15u) & ~(size_t)15u; }
+
+/* stages a part's frames at 16-aligned offsets of the slot's stage, zero bytes behind each (the matcher reads 16-aligned blocks and up to
+ * the next multiple of 16 past each).  One gather launch when the device layer has it; else — a run of one buffer's chunks only — a memset
+ * and up to two 2D copies (the last chunk alone when it is short) */
+static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, size_t stageBytes)
 {
-    const size_t chunk = j->f->p.chunkSize, off = c0 * chunk, end = c1 * chunk < j->srcSize ? c1 * chunk : j->srcSize;
-    const size_t blk = chunk < QZSTD_HIP_BLOCK_MAX ? chunk : QZSTD_HIP_BLOCK_MAX;
-    const size_t pitch = (chunk + 15u) & ~(size_t)15u; /* chunk c of the part at c * pitch when staged */
-    const int inPlace = ((uintptr_t)(j->dSrc + off) & 15u) == 0 && (chunk & 15u) == 0 && ((end - off) & 15u) == 0;
-    const size_t nb = (c1 - c0 - 1) * j->bpc + ((end - (c1 - 1) * chunk) + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    const QF_DevFrame *f0 = &j->frames[pr->f0];
+    const size_t nf = pr->f1 - pr->f0;
+    void *stage = s->dStage;
+    if (qfGrowD(j->dev, &stage, &s->stageCap, stageBytes)) return -1;
+    s->dStage = (unsigned char *)stage;
+    if (qzstd_hip_gather) {
+        void *h = s->hRows;
+        size_t c, so = 0;
+        if (nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
+        s->hRows = (qzstd_hip_gather_row_t *)h;
+        if (qfGrowD(j->dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
+        for (c = 0; c < nf; c++) {
+            qzstd_hip_gather_row_t *r = &s->hRows[c];
+            if (f0[c].len > 0xFFFFFFE0u) return -1; /* (a row's length and padding are 32-bit) */
+            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->dstOff = so;
+            r->len = (uint32_t)f0[c].len;
+            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
+            so += qfPad16(f0[c].len);
+        }
+        return qzstd_hip_gather(j->dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_gather_row_t *)s->dRows, s->dStage, stageBytes);
+    }
+    if (!pr->run) return -1;
+    {
+        const size_t chunk = j->f->p.chunkSize, pitch = qfPad16(chunk), full = pr->bytes / chunk, tail = pr->bytes - full * chunk;
+        const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
+        if (qzstd_hip_memset(j->dev, s->stream, s->dStage, 0, stageBytes)) return -1;
+        if (full && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage, pitch, base, chunk, chunk, full)) return -1;
+        if (tail && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
+    }
+    return 0;
+}
+
+/* queues a part on slot s: staging if needed, match-finder, compaction.  Device side only: the slot's pinned arena may still be read by
+ * the workers (the part fetched from it before) */
+static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
+{
+    const QF_DevFrame *f0 = &j->frames[pr->f0];
+    const size_t nf = pr->f1 - pr->f0, nb = pr->nb, blk = j->blk;
     const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
-    const unsigned char *base = j->dSrc + off;
-    size_t c, b = 0, seqCapTotal = 0;
+    const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
+    /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
+    const int inPlace = pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
+    size_t c, b = 0, so = 0, seqCapTotal = 0;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
     {
@@ -470,40 +533,34 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1)
         if (qfGrowH(&h, &s->hDescCap, nb * sizeof(qzstd_hip_block_t))) return -1;
         s->hDesc = (qzstd_hip_block_t *)h;
     }
-    for (c = c0; c < c1; c++) {
-        const size_t co = c * chunk, ce = co + chunk < j->srcSize ? co + chunk : j->srcSize;
+    for (c = 0; c < nf; c++) {
+        const size_t at = inPlace ? f0[c].off - f0->off : so; /* the frame's first byte from the launch's base */
         size_t o;
-        for (o = co; o < ce; o += QZSTD_HIP_BLOCK_MAX, b++) {
+        if (f0[c].b0 != b) return -1;
+        for (o = 0; o < f0[c].len; o += QZSTD_HIP_BLOCK_MAX, b++) {
             qzstd_hip_block_t *d = &s->hDesc[b];
-            d->srcLen = (uint32_t)(ce - o < QZSTD_HIP_BLOCK_MAX ? ce - o : QZSTD_HIP_BLOCK_MAX);
-            d->srcOff = inPlace ? o - off : (c - c0) * pitch + (o - co);
+            d->srcLen = (uint32_t)(f0[c].len - o < QZSTD_HIP_BLOCK_MAX ? f0[c].len - o : QZSTD_HIP_BLOCK_MAX);
+            d->srcOff = at + o;
             d->seqOff = b * capPad;
             d->seqCap = (uint32_t)cap;
             d->parseFrom = 0;
             d->mark = 0;
             seqCapTotal += cap;
         }
+        so += qfPad16(f0[c].len);
     }
     if (b != nb) return -1;
     if (!s->stream && !(s->stream = qzstd_hip_stream_create(dev))) return -1;
     {
         const size_t work = qzstd_hip_workspace_bytes(j->level, (uint32_t)nb, (uint32_t)blk);
-        const size_t arena = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb) + 8u * seqCapTotal + (end - off);
+        const size_t arena = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb) + 8u * seqCapTotal + pr->bytes;
         if (qfGrowD(dev, &s->dDesc, &s->dDescCap, nb * sizeof(qzstd_hip_block_t)) || qfGrowD(dev, &s->dSeqs, &s->dSeqsCap, nb * capPad * 16u) ||
             qfGrowD(dev, &s->dCount, &s->dCountCap, nb * 4u) || qfGrowD(dev, &s->dWork, &s->dWorkCap, work) ||
             qfGrowD(dev, &s->dCWork, &s->dCWorkCap, qzstd_hip_compact_workspace_bytes((uint32_t)nb)) || qfGrowD(dev, &s->dArena, &s->dArenaCap, arena))
             return -1;
     }
     if (!inPlace) {
-        /* the matcher reads 16-aligned blocks and up to the next multiple of 16 past each: the part's chunks go to pitch-aligned rows of
-         * library memory (one 2D copy; the last chunk alone when it is short), zero bytes behind every chunk */
-        const size_t full = (end - off) / chunk, tail = (end - off) - full * chunk;
-        void *stage = s->dStage;
-        if (qfGrowD(dev, &stage, &s->stageCap, (c1 - c0) * pitch + 16u)) return -1;
-        s->dStage = (unsigned char *)stage;
-        if (qzstd_hip_memset(dev, s->stream, s->dStage, 0, (c1 - c0) * pitch + 16u)) return -1;
-        if (full && qzstd_hip_memcpy2d_d2d(dev, s->stream, s->dStage, pitch, base, chunk, chunk, full)) return -1;
-        if (tail && qzstd_hip_memcpy2d_d2d(dev, s->stream, s->dStage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
+        if (qfStagePart(j, s, pr, so + 16u)) return -1;
         base = s->dStage;
     }
     if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dDesc, s->hDesc, nb * sizeof(qzstd_hip_block_t)) ||
@@ -516,16 +573,15 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1)
 }
 
 /* waits for a queued part, brings its arena back (one D2H) and fills the per-block offsets; -> the part for the workers */
-static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1, QF_DevPart *out)
+static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, QF_DevPart *out)
 {
-    const size_t end = c1 * j->f->p.chunkSize < j->srcSize ? c1 * j->f->p.chunkSize : j->srcSize;
-    const size_t nb = (c1 - c0 - 1) * j->bpc + ((end - (c1 - 1) * j->f->p.chunkSize) + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    const size_t nb = pr->nb;
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb);
     const qzstd_hip_compact_hdr_t *hdr;
     size_t b, seqs = 0, lits = 0, bytes;
     if (s->hArenaCap < eo) {
         void *h = s->hArena;
-        if (qfGrowH(&h, &s->hArenaCap, eo + (end - c0 * j->f->p.chunkSize) + ((end - c0 * j->f->p.chunkSize) >> 2) + QF_LIT_SLACK)) return -1;
+        if (qfGrowH(&h, &s->hArenaCap, eo + pr->bytes + (pr->bytes >> 2) + QF_LIT_SLACK)) return -1;
         s->hArena = (unsigned char *)h;
     }
     if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
@@ -563,11 +619,11 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, size_t c0, size_t c1, 
     s->hLit = s->hArena + eo + 8u * seqs;
     s->litTotal = lits;
     __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes), __ATOMIC_RELAXED);
-    out->dSrc = j->dSrc;
-    out->c0 = c0;
-    out->c1 = c1;
+    out->bufs = j->bufs;
+    out->frames = j->frames;
+    out->f0 = pr->f0;
+    out->f1 = pr->f1;
     out->nb = nb;
-    out->bpc = j->bpc;
     out->slot = s;
     out->dev = j->dev;
     return 0;
@@ -593,14 +649,14 @@ static int qfStoresRawBlock(const unsigned char *fr, size_t frSize, size_t n)
     return 0;
 }
 
-/* chunk c of the part in progress -> frame */
+/* frame c of the part in progress -> zstd frame */
 static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
 {
     const QF_DevPart *pt = f->part;
     const QF_DevSlot *s = pt->slot;
-    const size_t cg = pt->c0 + c, off = cg * f->p.chunkSize;
-    const size_t n = f->srcSize - off < f->p.chunkSize ? f->srcSize - off : f->p.chunkSize;
-    const size_t b0 = c * pt->bpc, b1 = b0 + pt->bpc < pt->nb ? b0 + pt->bpc : pt->nb;
+    const size_t cg = pt->f0 + c;
+    const QF_DevFrame *fm = &pt->frames[cg];
+    const size_t n = fm->len, b0 = fm->b0, b1 = b0 + fm->nb;
     const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(pt->nb);
     const unsigned long long *ent = (const unsigned long long *)(const void *)(s->hArena + eo);
@@ -654,9 +710,9 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         w->rawDev = pt->dev;
         if (!w->raw || !w->rawStream) return -1;
     }
-    if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, pt->dSrc + off, n)) return -1;
+    if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, (const unsigned char *)pt->bufs[fm->buf].d_ptr + fm->off, n)) return -1;
     if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
-        /* the copy still reads d_src: the call must not return before it is done */
+        /* the copy still reads the caller's buffer: the call must not return before it is done */
         (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
         return -1;
     }
@@ -679,87 +735,158 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     return 0;
 }
 
-size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSize, void *stream, void *dst, size_t dstCapacity,
-                                 size_t *frameSizes)
+size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs)
+{
+    size_t i, n = 0;
+    if (!f || (nBufs && !bufs)) return (size_t)-1;
+    for (i = 0; i < nBufs; i++) n += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+    return n;
+}
+
+/* the per-frame table and the parts of a job.  A part takes whole frames, across buffer boundaries, until the next one would take its input
+ * past partBytes or its blocks past four times the blocks of a part of full ones (a block costs the device the same scratch whatever its
+ * length); at least one frame. */
+static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, size_t nFrames, size_t partBytes, size_t blk,
+                        QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
+{
+    const size_t chunk = f->p.chunkSize, maxBlocks = 4u * (partBytes / blk ? partBytes / blk : 1u);
+    QF_DevFrame *fr = (QF_DevFrame *)malloc(nFrames * sizeof(*fr));
+    QF_DevRange *pt = (QF_DevRange *)malloc(nFrames * sizeof(*pt)), *cur = NULL;
+    size_t i, c = 0, nParts = 0;
+    if (!fr || !pt) { free(fr); free(pt); return -1; }
+    for (i = 0; i < nBufs; i++) {
+        size_t off;
+        for (off = 0; off < bufs[i].size; off += chunk, c++) {
+            const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
+            const size_t nb = (len + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+            if (!cur || cur->bytes + len > partBytes || cur->nb + nb > maxBlocks) {
+                cur = &pt[nParts++];
+                cur->f0 = c;
+                cur->nb = cur->bytes = 0;
+                cur->run = 1;
+            } else if (fr[c - 1].buf != (uint32_t)i) {
+                cur->run = 0;
+            }
+            fr[c].off = off;
+            fr[c].len = len;
+            fr[c].b0 = cur->nb;
+            fr[c].buf = (uint32_t)i;
+            fr[c].nb = (uint32_t)nb;
+            cur->f1 = c + 1;
+            cur->nb += nb;
+            cur->bytes += len;
+        }
+    }
+    if (c != nFrames) { free(fr); free(pt); return -1; }
+    *framesOut = fr;
+    *partsOut = pt;
+    *nPartsOut = nParts;
+    return 0;
+}
+
+/* both device entry points.  batch: the call needs the gather (frames of several buffers in one part); the single-buffer call stages a part it
+ * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not */
+static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, int batch, void *stream, void *dst, size_t dstCapacity,
+                               size_t *frameSizes, size_t *firstFrame)
 {
     QF_DevJob j;
     QF_DevSlot *slot;
     QF_DevPart part[2];
+    QF_DevFrame *frames = NULL;
+    QF_DevRange *parts = NULL;
     void *ev = NULL;
-    size_t nChunks, nParts, k;
+    size_t nFrames, nParts = 0, k, i, total = 0;
     int rc = 0;
     /* host-side checks: nothing has touched a GPU when one of them fails */
-    if (!f || (!d_src && srcSize) || !dst || !frameSizes || !f->p.useProducer) return (size_t)-1;
-    nChunks = (srcSize + f->p.chunkSize - 1) / f->p.chunkSize;
-    if (dstCapacity / f->stride < nChunks) return (size_t)-1;
+    if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    for (i = 0; i < nBufs; i++)
+        if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+    nFrames = QZSTD_frontDeviceBatchFrames(f, bufs, nBufs);
+    if (dstCapacity / f->stride < nFrames) return (size_t)-1;
     if (!qzstd_hip_pointer_device || !qzstd_hip_compact || !qzstd_hip_compact_workspace_bytes || !qzstd_hip_event_create ||
-        !qzstd_hip_event_record || !qzstd_hip_stream_wait_event || !qzstd_hip_event_destroy || !qzstd_hip_memcpy2d_d2d)
+        !qzstd_hip_event_record || !qzstd_hip_stream_wait_event || !qzstd_hip_event_destroy || !qzstd_hip_memcpy2d_d2d ||
+        (batch && !qzstd_hip_gather))
         return (size_t)-1; /* a device layer without the device-input entry points */
-    if (nChunks == 0) return 0;
-    j.dev = qzstd_hip_pointer_device(d_src);
-    if (j.dev < 0 || qzstd_hip_pointer_device((const unsigned char *)d_src + srcSize - 1) != j.dev) return (size_t)-1;
-    pthread_mutex_lock(&f->mu);
-    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-    f->devBusy = 1;
-    pthread_mutex_unlock(&f->mu);
+    j.dev = -1;
+    for (i = 0; i < nBufs; i++) {
+        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
+        int d;
+        if (!bufs[i].size) continue;
+        d = qzstd_hip_pointer_device(p);
+        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (j.dev >= 0 && d != j.dev)) return (size_t)-1;
+        j.dev = d;
+        total += bufs[i].size;
+    }
+    if (nFrames) {
+        pthread_mutex_lock(&f->mu);
+        if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+        f->devBusy = 1;
+        pthread_mutex_unlock(&f->mu);
+    }
+    if (firstFrame) {
+        size_t c = 0;
+        for (i = 0; i < nBufs; i++) {
+            firstFrame[i] = c;
+            c += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+        }
+        firstFrame[nBufs] = c;
+    }
+    if (nFrames == 0) return 0;
     pthread_once(&qfSeqOnce, qfResolveSeqApi);
 
     j.f = f;
-    j.dSrc = (const unsigned char *)d_src;
-    j.srcSize = srcSize;
-    j.bpc = (f->p.chunkSize + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+    j.bufs = bufs;
+    j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes per part (rounded down to whole chunks, at least one), default 64 MiB */
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
         const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        j.partChunks = want / f->p.chunkSize ? want / f->p.chunkSize : 1;
+        rc = qfPlanDevice(f, bufs, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
     }
+    j.frames = frames;
+    j.parts = parts;
+    j.nParts = nParts;
     {
         const char *rep = getenv("QZSTD_HIP_EXT_REPCODES"); /* the producer path's level flags (QZSTD_startQatDevice) */
         j.level = f->p.level | ((rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0);
     }
-    nParts = (nChunks + j.partChunks - 1) / j.partChunks;
     memset(part, 0, sizeof(part));
     /* the slots stay with the front between calls (allocating and freeing pinned and device memory costs more than a part takes) */
     if (f->devSlot && f->devSlotDev != j.dev) qfDevSlotsFree(f);
     if (!f->devSlot && !(f->devSlot = (QF_DevSlot *)calloc(2, sizeof(QF_DevSlot)))) rc = -1;
     f->devSlotDev = j.dev;
     slot = f->devSlot;
-    /* the library's streams wait for what the caller queued on `stream` so far: the work that produced d_src */
-    for (k = 0; k < 2 && rc == 0; k++)
+    /* the library's streams wait for what the caller queued on `stream` so far: the work that produced the buffers */
+    for (k = 0; slot && k < 2 && rc == 0; k++)
         if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(j.dev))) rc = -1;
     if (rc == 0 && !(ev = qzstd_hip_event_create(j.dev))) rc = -1;
     if (rc == 0 && (qzstd_hip_event_record(j.dev, ev, stream) || qzstd_hip_stream_wait_event(j.dev, slot[0].stream, ev) ||
                     qzstd_hip_stream_wait_event(j.dev, slot[1].stream, ev)))
         rc = -1;
-#define QF_PART_C0(p) ((p) * j.partChunks)
-#define QF_PART_C1(p) ((p) * j.partChunks + j.partChunks < nChunks ? (p) * j.partChunks + j.partChunks : nChunks)
     /* two parts on the GPU ahead of the one being entropy-coded: part p lives on slot p % 2 from its queueing to its fetch */
-    for (k = 0; k < 2 && k < nParts && rc == 0; k++) rc = qfQueuePart(&j, &slot[k], QF_PART_C0(k), QF_PART_C1(k));
-    if (rc == 0) rc = qfFetchPart(&j, &slot[0], QF_PART_C0(0), QF_PART_C1(0), &part[0]);
+    for (k = 0; k < 2 && k < nParts && rc == 0; k++) rc = qfQueuePart(&j, &slot[k], &parts[k]);
+    if (rc == 0) rc = qfFetchPart(&j, &slot[0], &parts[0], &part[0]);
     for (k = 0; k < nParts && rc == 0; k++) {
         int failed;
         /* slot k % 2 is fetched: its device side takes part k + 2 while the workers read its pinned arena — not the device buffers */
         if (k + 2 < nParts) {
-            if ((rc = qfQueuePart(&j, &slot[k % 2], QF_PART_C0(k + 2), QF_PART_C1(k + 2))) != 0) break;
+            if ((rc = qfQueuePart(&j, &slot[k % 2], &parts[k + 2])) != 0) break;
         }
         pthread_mutex_lock(&f->mu);
         f->part = &part[k % 2];
         f->src = NULL;
-        f->srcSize = srcSize;
+        f->srcSize = 0;
         f->dst = (unsigned char *)dst;
         f->sizes = frameSizes;
-        failed = qfRunJobLocked(f, part[k % 2].c1 - part[k % 2].c0);
+        failed = qfRunJobLocked(f, part[k % 2].f1 - part[k % 2].f0);
         f->part = NULL;
         pthread_mutex_unlock(&f->mu);
         if (failed) { rc = -1; break; }
         if (k + 1 < nParts) {
             /* the next part's arena into the other slot (its last reader was the job of part k - 1) */
-            rc = qfFetchPart(&j, &slot[(k + 1) % 2], QF_PART_C0(k + 1), QF_PART_C1(k + 1), &part[(k + 1) % 2]);
+            rc = qfFetchPart(&j, &slot[(k + 1) % 2], &parts[k + 1], &part[(k + 1) % 2]);
         }
     }
-#undef QF_PART_C0
-#undef QF_PART_C1
-    /* nothing the library queued may still read d_src when the call returns: a bounded wait first, then an unbounded one */
+    /* nothing the library queued may still read the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
     for (k = 0; slot && k < 2; k++) {
         if (!slot[k].stream) continue;
         if (qzstd_hip_stream_wait(j.dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
@@ -768,11 +895,28 @@ size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSi
         }
     }
     if (ev) qzstd_hip_event_destroy(j.dev, ev);
-    if (rc == 0) __atomic_fetch_add(&f->devStats[3], (unsigned long long)srcSize, __ATOMIC_RELAXED);
+    free(frames);
+    free(parts);
+    if (rc == 0) __atomic_fetch_add(&f->devStats[3], (unsigned long long)total, __ATOMIC_RELAXED);
     pthread_mutex_lock(&f->mu);
     f->devBusy = 0;
     pthread_mutex_unlock(&f->mu);
-    return rc == 0 ? nChunks : (size_t)-1;
+    return rc == 0 ? nFrames : (size_t)-1;
+}
+
+size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSize, void *stream, void *dst, size_t dstCapacity,
+                                 size_t *frameSizes)
+{
+    QZSTD_DeviceBuf one;
+    one.d_ptr = d_src;
+    one.size = srcSize;
+    return qfCompressDevice(f, &one, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
+}
+
+size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, void *dst, size_t dstCapacity,
+                                      size_t *frameSizes, size_t *firstFrame)
+{
+    return qfCompressDevice(f, bufs, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])

@@ -8,6 +8,14 @@ sized once, one untimed pass of each way comes first, frames are read out of the
 byte, frames that took the raw-bytes fallback, compressed sizes, whether both ways give the same frames.
 
   python tools/device_bench.py --gib 1 --reps 3 [--levels 1,6,12]
+
+--batch: a LIST of tensors, N GiB in total from the same corpus, in three mixes — (a) tensors of 128 KiB, (b) sizes log-uniform between
+4 KiB and 64 MiB from a fixed seed, each tensor its own allocation, (c) one tensor — and three ways, library calls timed, every run listed:
+  batch  one QZSTD_frontCompressDeviceBatch call (skipped, "n/a", on a library without it: the other two ways measure an older build)
+  loop   one QZSTD_frontCompressDevice call per tensor
+  cat    torch.cat + one QZSTD_frontCompressDevice call, the cat inside the window (mixes a and b)
+
+  python tools/device_bench.py --batch --gib 1 --reps 3 [--levels 1,6,12] [--ways batch,loop,cat] [--mixes a_128k,b_loguniform,c_one]
 """
 import argparse
 import json
@@ -23,14 +31,91 @@ import qz_corpus as K  # noqa: E402
 torch = D.torch
 
 
+def batch_mixes(size: int):
+    """-> {mix: [tensor sizes]}, each summing to `size`"""
+    import numpy as np
+    rng = np.random.default_rng(2024)
+    b, left = [], size
+    while left > 0:
+        n = min(left, int(np.exp(rng.uniform(np.log(4096), np.log(64 << 20)))))
+        b.append(n)
+        left -= n
+    return {"a_128k": [131072] * (size // 131072), "b_loguniform": b, "c_one": [size]}
+
+
+def batch_main(a):
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    size = int(a.gib * (1 << 30))
+    data = K.by_name("system", size)
+    has_batch = hasattr(lib, "QZSTD_frontCompressDeviceBatch")
+    ways = [w for w in a.ways.split(",") if w != "batch" or has_batch]
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "timed": "library calls (+ torch.cat for `cat`), every run of %d" % a.reps,
+           "batch_call_present": has_batch, "mixes": {}}
+    for mix, sizes in batch_mixes(size).items():
+        if mix not in a.mixes.split(","):
+            continue
+        tensors, o = [], 0
+        for n in sizes:  # each tensor an allocation of its own
+            tensors.append(torch.frombuffer(bytearray(data[o:o + n]), dtype=torch.uint8).to("cuda:0"))
+            o += n
+        torch.cuda.synchronize()
+        res = out["mixes"][mix] = {"tensors": len(sizes), "levels": {}}
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            try:
+                stream = torch.cuda.current_stream().cuda_stream
+                pairs = [(t.data_ptr(), t.numel()) for t in tensors]
+                n_frames = sum((n + a.chunk - 1) // a.chunk for n in sizes)
+                fr.reserve_frames(max(n_frames, (size + a.chunk - 1) // a.chunk))
+
+                def batch_pass():
+                    return fr.call_device_batch(bufs, nb, nf, stream)[0] == nf
+
+                def loop_pass():
+                    return all(fr.call_device(p, n, stream)[0] == (n + a.chunk - 1) // a.chunk for p, n in pairs)
+
+                def cat_pass():
+                    whole = torch.cat(tensors)
+                    return fr.call_device(whole.data_ptr(), size, stream)[0] == (size + a.chunk - 1) // a.chunk
+
+                passes = {"batch": batch_pass, "loop": loop_pass, "cat": cat_pass}
+                if has_batch:
+                    bufs, nb, nf = fr.batch(pairs)
+                use = [w for w in ways if not (w == "cat" and len(sizes) == 1)]
+                runs = {w: [] for w in use}
+                for w in use:  # untimed: the device slots, the pinned arenas, first touch of the destination
+                    assert passes[w](), w
+                for _ in range(a.reps):
+                    for w in use:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        ok = passes[w]()
+                        dt = time.perf_counter() - t0
+                        assert ok, "%s pass failed" % w
+                        runs[w].append(round(size / dt / 1e9, 3))
+                res["levels"][str(level)] = {w + "_gbps": runs[w] for w in use}
+            finally:
+                fr.close()
+        del tensors
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--ways", default="batch,loop,cat")
+    ap.add_argument("--mixes", default="a_128k,b_loguniform,c_one")
     ap.add_argument("--gib", type=float, default=1.0)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.batch:
+        return batch_main(a)
     B.Zstd()
     B.Plugin()
     lib = B.Front().lib

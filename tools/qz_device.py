@@ -1,5 +1,6 @@
 """ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
-QZSTD_frontDeviceStats) and compress_tensor() for a contiguous GPU tensor of any dtype.
+QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats), compress_tensor() for a contiguous GPU tensor of any dtype and compress_tensors()
+for a list of them in one call.
 
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
 import ctypes as C
@@ -17,6 +18,16 @@ import qz_bind as B  # noqa: E402
 ERROR = C.c_size_t(-1).value
 
 
+class DeviceBuf(C.Structure):
+    """QZSTD_DeviceBuf"""
+    _fields_ = [("d_ptr", C.c_void_p), ("size", C.c_size_t)]
+
+
+class GatherRow(C.Structure):
+    """qzstd_hip_gather_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32)]
+
+
 def bind(F):
     """the front-end's C surface, the device entry points included, on a loaded library"""
     F.QZSTD_createFront.restype = C.c_void_p
@@ -28,6 +39,12 @@ def bind(F):
     F.QZSTD_frontCompressDevice.restype = C.c_size_t
     F.QZSTD_frontCompressDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
                                             C.POINTER(C.c_size_t)]
+    if hasattr(F, "QZSTD_frontCompressDeviceBatch"):  # (absent from an older library: tools/device_bench.py measures one)
+        F.QZSTD_frontDeviceBatchFrames.restype = C.c_size_t
+        F.QZSTD_frontDeviceBatchFrames.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_size_t]
+        F.QZSTD_frontCompressDeviceBatch.restype = C.c_size_t
+        F.QZSTD_frontCompressDeviceBatch.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                     C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
     F.QZSTD_frontDeviceStats.restype = None
     F.QZSTD_frontDeviceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     F.QZSTD_freeFront.argtypes = [C.c_void_p]
@@ -67,10 +84,48 @@ class DeviceFront:
                                                   len(self._dst), sizes), sizes
 
     def _buffers(self, size: int):
-        n = (size + self.chunk - 1) // self.chunk
+        return self._frame_buffers((size + self.chunk - 1) // self.chunk)
+
+    def _frame_buffers(self, n: int):
         if self._dst is None or len(self._dst) < max(n, 1) * self.stride:
             self._dst = C.create_string_buffer(max(n, 1) * self.stride)
         return n, (C.c_size_t * max(n, 1))()
+
+    def batch(self, ptrs_and_sizes):
+        """-> (QZSTD_DeviceBuf array, its length, frames the batch yields) for [(device address, bytes), ...]"""
+        bufs = (DeviceBuf * max(len(ptrs_and_sizes), 1))()
+        for i, (p, n) in enumerate(ptrs_and_sizes):
+            bufs[i].d_ptr, bufs[i].size = p or None, n
+        return bufs, len(ptrs_and_sizes), self.lib.QZSTD_frontDeviceBatchFrames(self.f, bufs, len(ptrs_and_sizes))
+
+    def reserve_frames(self, n: int):
+        """size the destination for n frames once (timed loops)"""
+        self._frame_buffers(n)
+
+    def call_device_batch(self, bufs, n_bufs: int, n_frames: int, stream: int | None = None):
+        """QZSTD_frontCompressDeviceBatch alone on a prepared array (batch()) -> (return value, sizes); frames stay in the destination"""
+        _, sizes = self._frame_buffers(n_frames)
+        return self.lib.QZSTD_frontCompressDeviceBatch(self.f, bufs, n_bufs, C.c_void_p(stream or None), self._dst, len(self._dst), sizes,
+                                                       None), sizes
+
+    def compress_device_batch_raw(self, ptrs_and_sizes, stream: int | None = None, dst_capacity: int | None = None):
+        """-> (return value of QZSTD_frontCompressDeviceBatch, per buffer its list of frames or None, firstFrame as a list)"""
+        bufs, nb, n = self.batch(ptrs_and_sizes)
+        _, sizes = self._frame_buffers(n)
+        first = (C.c_size_t * (nb + 1))()
+        cap = len(self._dst) if dst_capacity is None else dst_capacity
+        r = self.lib.QZSTD_frontCompressDeviceBatch(self.f, bufs, nb, C.c_void_p(stream or None), self._dst, cap, sizes, first)
+        if r != n:
+            return r, None, list(first)
+        fr = self._frames(n, sizes)
+        return r, [fr[first[i]:first[i + 1]] for i in range(nb)], list(first)
+
+    def compress_device_batch(self, ptrs_and_sizes, stream: int | None = None) -> list:
+        """frames of every buffer of [(device address, bytes), ...], a list of lists: one QZSTD_frontCompressDeviceBatch call"""
+        r, frames, _ = self.compress_device_batch_raw(ptrs_and_sizes, stream)
+        if frames is None:
+            raise RuntimeError("QZSTD_frontCompressDeviceBatch failed (%d)" % (r if r != ERROR else -1))
+        return frames
 
     def _frames(self, n, sizes):
         raw = self._dst.raw
@@ -119,6 +174,24 @@ def compress_tensor(front: DeviceFront, t, stream=None) -> list:
         stream = torch.cuda.current_stream(t.device)
     handle = getattr(stream, "cuda_stream", stream)
     return front.compress_device(t.data_ptr(), t.numel() * t.element_size(), handle)
+
+
+def compress_tensors(front: DeviceFront, tensors, stream=None) -> list:
+    """per tensor the frames of its bytes, all tensors in ONE call (QZSTD_frontCompressDeviceBatch): contiguous GPU tensors of any dtypes
+    and sizes, views with a storage offset included, all on one device.  `stream`: the torch.cuda.Stream (or raw hipStream_t) that
+    produced them; default: the current stream of their device."""
+    tensors = list(tensors)
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous():
+            raise ValueError("compress_tensors: contiguous GPU tensors")
+        if t.device != tensors[0].device:
+            raise ValueError("compress_tensors: tensors on one device")
+    if not tensors:
+        return []
+    if stream is None:
+        stream = torch.cuda.current_stream(tensors[0].device)
+    handle = getattr(stream, "cuda_stream", stream)
+    return front.compress_device_batch([(t.data_ptr(), t.numel() * t.element_size()) for t in tensors], handle)
 
 
 def reference_frames(zstd, oracle, data: bytes, chunk: int, level: int, ext_rep: bool = False) -> list:
