@@ -163,12 +163,24 @@ int qzstd_hip_memcpy2d_d2h(int device, void *stream, void *dst, size_t dpitch, c
  *   d_src     input bytes; block i occupies [srcOff_i, srcOff_i + srcLen_i); the buffer
  *             must stay readable up to the next multiple of 16 past each block end
  *   d_blocks  nBlocks descriptors
- *   d_seqs    ZSTD_Sequence array; block i writes entries [seqOff_i, seqOff_i + count_i)
+ *   d_seqs    ZSTD_Sequence array; block i writes entries [seqOff_i, seqOff_i + count_i) and nothing else: the rest of
+ *             its region, its neighbours' regions (production lays them exactly adjacent) and whatever lies between
+ *             or behind them keep their bytes.  A block that reports QZSTD_HIP_NSEQ_ERROR may have written anywhere
+ *             inside its own region [seqOff_i, seqOff_i + seqCap_i) and nowhere else; a block that is REFUSED (a
+ *             parseFrom that is no segment boundary, a srcLen that does not fit the scratch regions of a launch
+ *             that said a smaller maxBlockLen — at every level) writes nothing at all
  *   d_nseq    per block: number of sequences INCLUDING the trailing-literals delimiter
  *             (what qatSequenceProducer returns, src/qatseqprod.c:1090,:1323), or
- *             QZSTD_HIP_NSEQ_ERROR when count >= seqCap-1 (src/qatseqprod.c:1318)
+ *             QZSTD_HIP_NSEQ_ERROR when count >= seqCap-1 (src/qatseqprod.c:1318) — evaluated without the
+ *             subtraction: a seqCap of 0 or 1 (outside the contract of qzstd_hip_block_t.seqCap, but descriptors
+ *             live in device memory where no launcher can look) is an error and writes nothing behind the region.
+ *             Every block's word is written unconditionally, exactly once; the words need NOT be zeroed before a
+ *             launch (no launch path of the plugin does; announcements preset QZSTD_HIP_NSEQ_ERROR and poll), and
+ *             nothing behind the nBlocks words is touched
  *   d_work    device scratch of at least qzstd_hip_workspace_bytes(level, nBlocks, maxBlockLen)
- *             bytes, private to this launch until it completes: REQUIRED AT EVERY LEVEL since
+ *             bytes, private to this launch until it completes — no byte behind that size is touched, and what the
+ *             scratch held before (an earlier launch's words at any level: production's is grow-only) does not
+ *             matter —: REQUIRED AT EVERY LEVEL since
  *             round 6 (levels >= 5 keep their hash chains there; below them a launch leaves one
  *             parse word per position there and parses after its tile loop, eight 4 KiB segments
  *             at a time: 4 bytes per position)

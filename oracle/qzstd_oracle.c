@@ -426,7 +426,7 @@ static size_t qzo_parse_rep(const qzo_profile_t *pf, const uint8_t *src, uint32_
         floor = pf->segLog ? (q >> pf->segLog) << pf->segLog : 0u; /* never backwards across the start of q's segment */
         if (floor < anchor) floor = anchor;
         while (b < pf->backExt && q - b > floor && q - off - b > 0 && src[q - b - 1] == src[q - off - b - 1]) b++;
-        if (ns + 1 >= cap - 1) return QZO_ERROR; /* src/qatseqprod.c:1073-1076 */
+        if (ns + 2 >= cap) return QZO_ERROR; /* src/qatseqprod.c:1073-1076 (ns + 1 >= cap - 1, written so that a cap of 0 cannot wrap) */
         out[ns].offset = off;
         out[ns].litLength = q - b - anchor;
         out[ns].matchLength = L + b;
@@ -435,12 +435,14 @@ static size_t qzo_parse_rep(const qzo_profile_t *pf, const uint8_t *src, uint32_
         if (off != rep[0]) { rep[1] = rep[0]; rep[0] = off; }
         cur = anchor = q + L;
     }
-    out[ns].offset = 0; /* trailing literals delimiter, src/qatseqprod.c:1037-1045 */
-    out[ns].litLength = n - anchor;
-    out[ns].matchLength = 0;
-    out[ns].rep = 0;
+    if (ns < cap) { /* trailing literals delimiter, src/qatseqprod.c:1037-1045: never behind the region */
+        out[ns].offset = 0;
+        out[ns].litLength = n - anchor;
+        out[ns].matchLength = 0;
+        out[ns].rep = 0;
+    }
     ns++;
-    if (ns >= cap - 1) ns = QZO_ERROR; /* src/qatseqprod.c:1318 */
+    if (ns + 1 >= cap) ns = QZO_ERROR; /* src/qatseqprod.c:1318 (ns >= cap - 1, written so that a cap of 0 cannot wrap) */
     return ns;
 }
 
@@ -493,7 +495,7 @@ size_t qzo_find_sequences_from(const qzo_profile_t *pf, const uint8_t *src, size
         floor = pf->segLog ? (p >> pf->segLog) << pf->segLog : 0u;
         if (floor < anchor) floor = anchor;
         while (b < pf->backExt && p - b > floor && q - b > 0 && src[p - b - 1] == src[q - b - 1]) b++;
-        if (ns + 1 >= cap - 1) { ns = QZO_ERROR; goto done; } /* src/qatseqprod.c:1073-1076 */
+        if (ns + 2 >= cap) { ns = QZO_ERROR; goto done; } /* src/qatseqprod.c:1073-1076 (ns + 1 >= cap - 1, written so that a cap of 0 cannot wrap) */
         out[ns].offset = off;
         out[ns].litLength = p - b - anchor;
         out[ns].matchLength = L + b;
@@ -502,13 +504,15 @@ size_t qzo_find_sequences_from(const qzo_profile_t *pf, const uint8_t *src, size
         p += L;
         anchor = p;
     }
-    /* trailing literals delimiter, src/qatseqprod.c:1037-1045 */
-    out[ns].offset = 0;
-    out[ns].litLength = n - anchor;
-    out[ns].matchLength = 0;
-    out[ns].rep = 0;
+    /* trailing literals delimiter, src/qatseqprod.c:1037-1045: never behind the region */
+    if (ns < cap) {
+        out[ns].offset = 0;
+        out[ns].litLength = n - anchor;
+        out[ns].matchLength = 0;
+        out[ns].rep = 0;
+    }
     ns++;
-    if (ns >= cap - 1) ns = QZO_ERROR; /* src/qatseqprod.c:1318 */
+    if (ns + 1 >= cap) ns = QZO_ERROR; /* src/qatseqprod.c:1318 (ns >= cap - 1, written so that a cap of 0 cannot wrap) */
 done:
     free(cand); free(tbl); free(near); free(tblL); free(chain);
     return ns;

@@ -990,6 +990,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     }
     if (NEAR && n > kRing) return QZSTD_HIP_NSEQ_ERROR; /* a descriptor longer than the launch's maxBlockLen: refused, never compared from a ring that lost its bytes */
     if (DEFER && args.pwWords != 0u && ((n + kTile - 1u) & ~(kTile - 1u)) > args.pwWords) return QZSTD_HIP_NSEQ_ERROR; /* ... nor parsed out of a scratch region it does not fit (uniform: before the first barrier) */
+    if (DEFER && CHAIN && args.chainEntries != 0u && ((n + kTile - 1u) & ~(kTile - 1u)) * kEQ > args.chainEntries) return QZSTD_HIP_NSEQ_ERROR; /* ... nor, at the chain levels, linked in chain entries that lie in its neighbour's region or behind the workspace */
 
     /* ---- LDS layout (qzstd_hip_lds_bytes(): 72 560 B at levels 1-2, 65 392 B at levels 5-12 = two workgroups per CU; 138 096 B at levels 3-4) ---- */
     /* The workgroup's LDS is addressed from an integer constant, not from the `smem` symbol: the dynamic allocation starts at
@@ -1456,7 +1457,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = nseqEnd + 1u;
         if (lane == 0 && nseqEnd < blk.seqCap) store_entry(out, nseqEnd, 0u, n - anchorEnd, 0u, blk.mark);
-        if (count >= blk.seqCap - 1u) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318 */
+        if (count + 1u >= blk.seqCap) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318: count >= seqCap - 1, written so that a seqCap of 0 cannot wrap into a valid count */
         return count;
     }
 
@@ -2010,7 +2011,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = total + 1u;
         if (lane == 0 && total < blk.seqCap) store_entry(out, total, 0u, n - anchorEndAll, 0u, blk.mark);
-        if (count >= blk.seqCap - 1u) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318 */
+        if (count + 1u >= blk.seqCap) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318: count >= seqCap - 1, written so that a seqCap of 0 cannot wrap into a valid count */
         return count;
     }
 
@@ -2102,7 +2103,7 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
         /* delimiter {lit = tail, 0, 0}: QZSTD_decLz4s, src/qatseqprod.c:1037-1045 */
         uint32_t count = total + 1u;
         if (lane == 0 && total < blk.seqCap) store_entry(out, total, 0u, n - anchorCarry, 0u, blk.mark);
-        if (count >= blk.seqCap - 1u) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318 */
+        if (count + 1u >= blk.seqCap) count = QZSTD_HIP_NSEQ_ERROR; /* src/qatseqprod.c:1318: count >= seqCap - 1, written so that a seqCap of 0 cannot wrap into a valid count */
         return count;
     }
     return 0u; /* (not reached) */

@@ -278,9 +278,10 @@ class Oracle:
         return p
 
     def find(self, prof: OracleProfile, data: bytes, cap: int | None = None, parse_from: int = 0):
-        """sequences of a block; parse_from != 0: of the segment that starts there (data = the block up to the segment's end)"""
+        """sequences of a block; parse_from != 0: of the segment that starts there (data = the block up to the segment's end).
+        cap=None: ZSTD_sequenceBound(len(data)); a cap of 0 is passed on as 0"""
         n = len(data)
-        cap = cap or (n // 3 + 1 + n // 1024 + 1)
+        cap = sequence_bound(n) if cap is None else cap
         out = (Sequence * cap)()
         r = self.lib.qzo_find_sequences_from(C.byref(prof), data, n, parse_from, out, cap)
         return r, out
@@ -489,13 +490,17 @@ class ServiceLane:
         self.cnt = (C.c_uint32 * self.MAX_ITEMS).from_address(self.hcnt)
         self.seqs = (Sequence * (self.MAX_ITEMS * self.ITEM_CAP)).from_address(self.hseq)
 
-    def run(self, block: bytes, level: int, item_bytes: int = 4096, timeout_s: float = 5.0):
+    def run(self, block: bytes, level: int, item_bytes: int = 4096, timeout_s: float = 5.0, seq_cap: int | None = None):
+        """seq_cap: seqCapPerItem of the request (default: the whole result area shared out among the items)"""
         import time
         n = len(block)
         while -(-n // item_bytes) > self.MAX_ITEMS:
             item_bytes *= 2
         nit = -(-n // item_bytes)
         cap = self.MAX_ITEMS * self.ITEM_CAP // nit
+        if seq_cap is not None:
+            assert seq_cap <= cap
+            cap = seq_cap
         C.memmove(self.hsrc, block + bytes(16), n + 16)
         for k in range(nit):
             self.cnt[k] = 0
