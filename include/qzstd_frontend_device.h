@@ -53,6 +53,20 @@ size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf 
 size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream,
                                       void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame);
 
+/* Content checksums (RFC 8878: Content_Checksum_Flag, the low 32 bits of XXH64 of the frame's content behind its last block): off by
+ * default.  On: every frame of every call on this front carries one, and all calls still agree byte for byte — QZSTD_frontCompress runs its
+ * contexts with ZSTD_c_checksumFlag = 1; the device calls hash each part's frames ON THE GPU (qzstd_hip_xxh64, one launch per part, 8 bytes
+ * per frame device->host), set the header's flag and append the four bytes themselves, since the input never reaches the host; a frame
+ * built from its raw bytes (QZSTD_frontDeviceStats [1]) is hashed by libzstd like a host frame.  A decoder sees an ordinary frame and
+ * verifies it.  The GPU hashes a frame as one serial chain: frames far longer than 128 KiB in a part of few frames take it
+ * correspondingly long (64 MiB: 2 M steps).  With the setting on and a device layer without qzstd_hip_xxh64 the device calls return
+ * (size_t)-1 before anything is queued; QZSTD_frontCompress is not affected.
+ * Set: 0, or -1 for f NULL or while a call runs on the front.  Get: 0 / 1 (0 for f NULL). */
+int QZSTD_frontSetChecksum(QZSTD_Front *f, int on);
+int QZSTD_frontGetChecksum(const QZSTD_Front *f);
+/* since creation, frames whose checksum [0] the GPU computed, [1] libzstd computed (host calls, and device frames built from raw bytes) */
+void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2]);
+
 #if defined(__cplusplus)
 }
 #endif

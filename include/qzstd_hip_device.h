@@ -1,7 +1,7 @@
 /*
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
- * (QZSTD_frontCompressDeviceBatch).
+ * (QZSTD_frontCompressDeviceBatch) and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -71,6 +71,28 @@ typedef struct {
 } qzstd_hip_gather_row_t;
 int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
                      void *d_stage, size_t stageBytes);
+
+/*
+ * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a
+ * zstd frame stores its low 32 bits).  The rows are a part's frames where the match-finder reads them (the stage, or the caller's buffer
+ * for a part read in place): both start every frame 16-aligned, hence the alignment rule.  XXH64's four accumulators are serial chains
+ * (the rotation breaks linearity), so the parallelism is ACROSS rows: a wave takes 16 rows, four lanes per row, one lane per accumulator;
+ * rows of different lengths in a wave finish independently.  A row much longer than its neighbours is one long chain (64 MiB: 2 M steps).
+ * Loads are aligned 16-byte loads of the words that overlap [srcOff, srcOff + len) and of no other word; the bytes behind `len` in a row's
+ * last word are loaded and never looked at.  Only d_out[0 .. nRows) is written.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous) and must stay unchanged until the stream has passed the call; the
+ * launcher checks it and uploads it to d_rows, device scratch of nRows entries.  Refused (< 0) before anything is queued: a null rows,
+ * d_rows or d_out, a null d_base with a row that is not empty, a d_base that is not 16-aligned, a srcOff that is no multiple of 16.
+ * nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+#define QZSTD_HIP_XXH64_TILE 1024u /* bytes of a row the kernel fetches at a time (tests place lengths around its multiples) */
+typedef struct {
+    uint64_t srcOff; /* bytes from d_base, a multiple of 16 */
+    uint64_t len;    /* bytes to hash, may be 0 */
+} qzstd_hip_hash_row_t;
+int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
+                    qzstd_hip_hash_row_t *d_rows, uint64_t *d_out);
 
 #if defined(__cplusplus)
 }

@@ -3702,3 +3702,120 @@ extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather
     QZ_CHECK(hipGetLastError(), "launch qzstd_gather_kernel");
     return 0;
 }
+
+/* ---------------------------------------------------------------- content checksum (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kHashRows = 16u;                 /* rows per wave: four lanes each, one per XXH64 accumulator */
+constexpr uint32_t kHashTile = QZSTD_HIP_XXH64_TILE; /* bytes of a row per fetch: one whole-wave 16-byte load */
+constexpr uint32_t kHashPitch = kHashTile + 32u;    /* a row's tile in LDS: 32 bytes of padding put the eight rows of a 32-lane group on
+                                                       the 64 banks once (8 B per lane, 32 B per row and stripe) */
+constexpr uint64_t kXP1 = 0x9E3779B185EBCA87ull, kXP2 = 0xC2B2AE3D27D4EB4Full, kXP3 = 0x165667B19E3779F9ull, kXP4 = 0x85EBCA77C2B2AE63ull,
+                   kXP5 = 0x27D4EB2F165667C5ull;
+
+typedef uint32_t hash_word_t __attribute__((ext_vector_type(4))); /* one aligned 16-byte word */
+
+__device__ inline uint64_t xxh_rotl(uint64_t v, uint32_t r) { return (v << r) | (v >> (64u - r)); }
+__device__ inline uint64_t xxh_round(uint64_t acc, uint64_t in) { return xxh_rotl(acc + in * kXP2, 31u) * kXP1; }
+__device__ inline uint64_t xxh_merge(uint64_t h, uint64_t v) { return (h ^ xxh_round(0ull, v)) * kXP1 + kXP4; }
+
+/* One wave per workgroup, rows [16 * blockIdx.x, + 16).  Per step every row's next 1 KiB tile is fetched with one 16-byte load per lane
+ * (the words that overlap the row only) into registers while the tile before it, in LDS, is consumed: lane 4 r + a runs accumulator a
+ * of row r over the tile's 32-byte stripes.  The multiply chain (two 64-bit multiplies per 8 bytes and lane) sets the pace; the fetch of
+ * the next tile has a whole tile's chain to arrive.  A row ends in the step that holds byte (len & ~31): its first lane collects the
+ * four accumulators, walks the tail (8-, 4- and 1-byte steps over bytes below len only) and stores the hash.  The loop runs to the longest
+ * row of the wave; lanes of rows that are done idle. */
+__global__ __launch_bounds__(64) void qzstd_xxh64_kernel(const uint8_t *__restrict__ base, const qzstd_hip_hash_row_t *__restrict__ rows,
+                                                         uint32_t nRows, unsigned long long *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kHashRows * kHashPitch];
+    const uint32_t lane = threadIdx.x, r = lane >> 2, a = lane & 3u;
+    const uint32_t row0 = blockIdx.x * kHashRows;
+    /* the wave's rows, by uniform addresses: their offsets and 16-byte word counts are the same in every lane (scalar registers) */
+#define QZ_HASH_EACH_ROW(X, t) X(0, t) X(1, t) X(2, t) X(3, t) X(4, t) X(5, t) X(6, t) X(7, t) X(8, t) X(9, t) X(10, t) X(11, t) X(12, t) X(13, t) X(14, t) X(15, t)
+#define QZ_HASH_ROW(j, t)                                                                   \
+    const uint64_t off##j = row0 + j < nRows ? rows[row0 + j].srcOff : 0ull;               \
+    const uint64_t words##j = row0 + j < nRows ? (rows[row0 + j].len + 15u) >> 4 : 0ull;   \
+    hash_word_t next##j = { 0u, 0u, 0u, 0u };                                              \
+    nTiles = (words##j >> 6) + 1u > nTiles ? (words##j >> 6) + 1u : nTiles;
+    uint64_t nTiles = 0; /* steps of the wave: past the longest row's tail (a row of k whole tiles ends in step k, which fetches nothing) */
+    QZ_HASH_EACH_ROW(QZ_HASH_ROW, 0)
+    const uint64_t len = row0 + r < nRows ? rows[row0 + r].len : 0ull;
+    const uint64_t endTile = len / kHashTile; /* the tile that holds the row's tail; every stripe of the row lies at or before it */
+    uint64_t acc = a == 0u ? kXP1 + kXP2 : (a == 1u ? kXP2 : (a == 2u ? 0ull : 0ull - kXP1));
+    uint64_t stripesLeft = len >> 5;
+    /* tile t of row j: word t * 64 + lane of the row, when the row has it.  Sixteen named registers, not an array: the fetches must stay
+     * in flight in VGPRs across the chain below */
+#define QZ_HASH_FETCH1(j, t) \
+    if ((t) * (kHashTile / 16u) + lane < words##j) next##j = reinterpret_cast<const hash_word_t *>(base + off##j)[(t) * (kHashTile / 16u) + lane];
+#define QZ_HASH_STAGE1(j, t) \
+    if ((t) * (kHashTile / 16u) + lane < words##j) *reinterpret_cast<hash_word_t *>(&tile[j * kHashPitch + lane * 16u]) = next##j;
+#define QZ_HASH_FETCH(t) QZ_HASH_EACH_ROW(QZ_HASH_FETCH1, t)
+#define QZ_HASH_STAGE(t) QZ_HASH_EACH_ROW(QZ_HASH_STAGE1, t)
+    QZ_HASH_FETCH(0ull)
+    QZ_HASH_STAGE(0ull)
+    __syncthreads();
+    for (uint64_t t = 0; t < nTiles; t++) {
+        const bool more = t + 1u < nTiles;
+        if (more) { QZ_HASH_FETCH(t + 1u) }
+        const uint8_t *mine = &tile[r * kHashPitch];
+        const uint32_t n = stripesLeft < kHashTile / 32u ? (uint32_t)stripesLeft : kHashTile / 32u;
+        for (uint32_t s = 0; s < n; s++) acc = xxh_round(acc, *reinterpret_cast<const uint64_t *>(mine + s * 32u + a * 8u));
+        stripesLeft -= n;
+        /* (all lanes: the row's accumulators to each of its lanes) */
+        const uint64_t v1 = __shfl(acc, (int)(lane & ~3u)), v2 = __shfl(acc, (int)(lane & ~3u) + 1), v3 = __shfl(acc, (int)(lane & ~3u) + 2),
+                       v4 = __shfl(acc, (int)(lane & ~3u) + 3);
+        if (t == endTile && a == 0u && row0 + r < nRows) {
+            uint64_t h;
+            if (len >= 32u) {
+                h = xxh_rotl(v1, 1u) + xxh_rotl(v2, 7u) + xxh_rotl(v3, 12u) + xxh_rotl(v4, 18u);
+                h = xxh_merge(xxh_merge(xxh_merge(xxh_merge(h, v1), v2), v3), v4);
+            } else {
+                h = kXP5;
+            }
+            h += len;
+            uint32_t p = (uint32_t)((len & ~(uint64_t)31u) - t * kHashTile), left = (uint32_t)len & 31u;
+            for (; left >= 8u; left -= 8u, p += 8u)
+                h = xxh_rotl(h ^ xxh_round(0ull, *reinterpret_cast<const uint64_t *>(mine + p)), 27u) * kXP1 + kXP4;
+            if (left >= 4u) {
+                h = xxh_rotl(h ^ (uint64_t)*reinterpret_cast<const uint32_t *>(mine + p) * kXP1, 23u) * kXP2 + kXP3;
+                p += 4u;
+                left -= 4u;
+            }
+            for (; left; left--, p++) h = xxh_rotl(h ^ (uint64_t)mine[p] * kXP5, 11u) * kXP1;
+            h ^= h >> 33;
+            h *= kXP2;
+            h ^= h >> 29;
+            h *= kXP3;
+            h ^= h >> 32;
+            out[row0 + r] = h;
+        }
+        __syncthreads(); /* the tile is consumed: the next one may take its place */
+        if (more) { QZ_HASH_STAGE(t + 1u) }
+        __syncthreads();
+    }
+#undef QZ_HASH_EACH_ROW
+#undef QZ_HASH_ROW
+#undef QZ_HASH_FETCH1
+#undef QZ_HASH_STAGE1
+#undef QZ_HASH_FETCH
+#undef QZ_HASH_STAGE
+}
+} // namespace
+
+extern "C" int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
+                               qzstd_hip_hash_row_t *d_rows, uint64_t *d_out)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_out) return fail_msg("qzstd_hip_xxh64: null pointer");
+    if ((uintptr_t)d_base & 15u) return fail_msg("qzstd_hip_xxh64: base not 16-byte aligned");
+    for (uint32_t i = 0; i < nRows; i++) {
+        if (rows[i].srcOff & 15u) return fail_msg("qzstd_hip_xxh64: srcOff not a multiple of 16");
+        if (rows[i].len && !d_base) return fail_msg("qzstd_hip_xxh64: null base");
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (hash rows)");
+    hipLaunchKernelGGL(qzstd_xxh64_kernel, dim3((nRows + kHashRows - 1u) / kHashRows), dim3(64), 0, (hipStream_t)stream,
+                       static_cast<const uint8_t *>(d_base), d_rows, nRows, reinterpret_cast<unsigned long long *>(d_out));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_xxh64_kernel");
+    return 0;
+}

@@ -37,6 +37,7 @@ typedef struct {
     unsigned char *raw;
     void *rawStream;
     int rawDev;
+    int cksum; /* ZSTD_c_checksumFlag as last set on zc (the parameter is sticky: qfCtxChecksum) */
 } QF_Worker;
 
 typedef struct QF_DevPart_s QF_DevPart;
@@ -66,6 +67,9 @@ struct QZSTD_Front_s {
     unsigned long long devStats[4];
     QF_DevSlot *devSlot; /* two, kept from call to call (device buffers, pinned arenas, streams) for device devSlotDev */
     int devSlotDev;
+    /* content checksums (QZSTD_frontSetChecksum): the setting, and frames hashed by the GPU / by libzstd */
+    int checksum;
+    unsigned long long cksumStats[2];
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -119,6 +123,18 @@ static void qfAnnounce(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 
 static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c);
 
+/* ZSTD_c_checksumFlag on the worker's context.  The parameter outlives ZSTD_reset_session_only, so every path that builds a frame names
+ * the value it needs and no frame inherits the one before it; the context is only touched when the value changes (never, with the
+ * setting off).  Parameters cannot be set mid-frame, where a failed call may have left the context: reset first. */
+static int qfCtxChecksum(QF_Worker *w, int on)
+{
+    if (w->cksum == on) return 0;
+    (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
+    if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_checksumFlag, on))) return -1;
+    w->cksum = on;
+    return 0;
+}
+
 static int qfCompressSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 {
     size_t c;
@@ -127,6 +143,7 @@ static int qfCompressSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
             if (qfDeviceFrame(f, w, c) != 0) return -1;
         return 0;
     }
+    if (qfCtxChecksum(w, f->checksum)) return -1;
     for (c = sg->c0; c < sg->c1; c++) {
         const size_t off = c * f->p.chunkSize;
         const size_t n = f->srcSize - off < f->p.chunkSize ? f->srcSize - off : f->p.chunkSize;
@@ -134,6 +151,7 @@ static int qfCompressSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
         if (ZSTD_isError(r)) return -1;
         f->sizes[c] = r;
     }
+    if (f->checksum) __atomic_fetch_add(&f->cksumStats[1], (unsigned long long)(sg->c1 - sg->c0), __ATOMIC_RELAXED);
     return 0;
 }
 
@@ -346,6 +364,11 @@ void QZSTD_freeFront(QZSTD_Front *f)
  *
  * The new entry points of the device layer are weak references: a device layer without them (an older library, the CPU suite's mock)
  * makes QZSTD_frontCompressDevice fail and leaves the rest of the front-end as it was.
+ *
+ * Content checksums (QZSTD_frontSetChecksum): the part's frames are hashed where the match-finder reads them (qzstd_hip_xxh64, queued behind
+ * the compaction on the slot's stream), 8 bytes per frame come back with the arena's headers, and qfDeviceFrame sets the header's flag and
+ * appends the low 32 bits to a frame ZSTD_compressSequencesAndLiterals built (that function refuses ZSTD_c_checksumFlag: it never sees
+ * the content).  The raw-bytes paths have the content and let libzstd hash it.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
@@ -360,6 +383,8 @@ extern int qzstd_hip_compact(int device, void *stream, const void *d_src, const 
                              size_t workBytes) __attribute__((weak));
 extern int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
                             void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
+                           qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
 
 #define QF_PART_BYTES ((size_t)64 << 20)
 #define QF_DEV_WAIT_MS 60000u
@@ -394,6 +419,10 @@ struct QF_DevSlot_s {
     unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned frames, when the caller's buffers cannot be read in place */
     qzstd_hip_gather_row_t *hRows; size_t hRowsCap; /* the gather's rows, one per frame (pinned), and their device copy */
     void *dRows; size_t dRowsCap;
+    qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
+    void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
+    uint64_t *hHash; size_t hHashCap;
+    int hashed; /* the part queued on this slot has its frames' hashes in dHash; the part fetched from it has them in hHash */
     qzstd_hip_block_t *hDesc; size_t hDescCap;
     void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
     size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
@@ -423,15 +452,18 @@ struct QF_DevPart_s {
     size_t nb;                   /* blocks */
     const QF_DevSlot *slot;
     int dev;
+    int hashed; /* checksums on: frame c's content hash is slot->hHash[c - f0] */
 };
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
-    void *d[] = { s->dStage, s->dRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena };
+    void *d[] = { s->dStage, s->dRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
     if (s->hRows) qzstd_hip_host_free(s->hRows);
+    if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
+    if (s->hHash) qzstd_hip_host_free(s->hHash);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
     if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
     free(s->blkSeq);
@@ -473,6 +505,7 @@ typedef struct {
     const QF_DevRange *parts;
     size_t nParts, blk;        /* blk: the launches' largest block, min(chunkSize, 128 KiB) */
     int dev, level;
+    int checksum;              /* the front's setting when the call began */
 } QF_DevJob;
 
 static size_t qfPad16(size_t n) { return (n + 15u) & ~(size_t)15u; }
@@ -569,6 +602,23 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
         qzstd_hip_compact(dev, s->stream, base, (const qzstd_hip_block_t *)s->dDesc, (uint32_t)nb, s->dSeqs, (const uint32_t *)s->dCount,
                           s->dArena, s->dArenaCap, s->dCWork, s->dCWorkCap))
         return -1;
+    s->hashed = 0;
+    if (j->checksum) {
+        /* the frames' content hashes, from the bytes the match-finder was given: frame c at the offset its first block has */
+        void *h = s->hHashRows;
+        if (qfGrowH(&h, &s->hHashRowsCap, nf * sizeof(qzstd_hip_hash_row_t))) return -1;
+        s->hHashRows = (qzstd_hip_hash_row_t *)h;
+        if (qfGrowD(dev, &s->dHashRows, &s->dHashRowsCap, nf * sizeof(qzstd_hip_hash_row_t)) || qfGrowD(dev, &s->dHash, &s->dHashCap, nf * 8u))
+            return -1;
+        for (c = 0; c < nf; c++) {
+            s->hHashRows[c].srcOff = s->hDesc[f0[c].b0].srcOff;
+            s->hHashRows[c].len = f0[c].len;
+        }
+        if (nf > 0xFFFFFFFFu || qzstd_hip_xxh64(dev, s->stream, base, s->hHashRows, (uint32_t)nf, (qzstd_hip_hash_row_t *)s->dHashRows,
+                                                 (uint64_t *)s->dHash))
+            return -1;
+        s->hashed = 1;
+    }
     return 0;
 }
 
@@ -583,6 +633,13 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         void *h = s->hArena;
         if (qfGrowH(&h, &s->hArenaCap, eo + pr->bytes + (pr->bytes >> 2) + QF_LIT_SLACK)) return -1;
         s->hArena = (unsigned char *)h;
+    }
+    if (s->hashed) {
+        /* the hashes travel with the headers: one more copy per part, 8 bytes per frame, no wait of its own */
+        void *h = s->hHash;
+        if (qfGrowH(&h, &s->hHashCap, (pr->f1 - pr->f0) * 8u)) return -1;
+        s->hHash = (uint64_t *)h;
+        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHash, s->dHash, (pr->f1 - pr->f0) * 8u)) return -1;
     }
     if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
         return -1;
@@ -618,7 +675,8 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     memset(s->hArena + eo + bytes, 0, QF_LIT_SLACK);
     s->hLit = s->hArena + eo + 8u * seqs;
     s->litTotal = lits;
-    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes), __ATOMIC_RELAXED);
+    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u)), __ATOMIC_RELAXED);
+    out->hashed = s->hashed;
     out->bufs = j->bufs;
     out->frames = j->frames;
     out->f0 = pr->f0;
@@ -686,13 +744,24 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         /* (a session that ended in an error leaves the CCtx mid-frame, where parameters cannot be set: every frame starts afresh) */
         (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
         if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 1))) return -1;
-        if (qfSeqLit) {
+        if (qfSeqLit && qfCtxChecksum(w, 0) == 0) { /* (ZSTD_compressSequencesAndLiterals refuses the checksum flag) */
             /* the frame's literals straight from the arena; everything behind them (later frames' literals, the slack) is readable */
             const unsigned char *lit = s->hLit + s->blkLit[b0];
             const size_t litCap = s->litTotal - s->blkLit[b0] + QF_LIT_SLACK;
             r = qfSeqLit(w->zc, dst, f->stride, w->seqs, ns, lit, nl, litCap, n);
-            if (!ZSTD_isError(r) && !qfStoresRawBlock(dst, r, n)) {
+            if (!ZSTD_isError(r) && !qfStoresRawBlock(dst, r, n) && (!pt->hashed || r + 4u <= f->stride)) {
                 (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
+                if (pt->hashed) {
+                    /* Content_Checksum_Flag (bit 2 of the frame header descriptor) and the hash's low 32 bits behind the last block */
+                    const uint64_t h = s->hHash[c];
+                    dst[4] |= 4u;
+                    dst[r] = (unsigned char)h;
+                    dst[r + 1] = (unsigned char)(h >> 8);
+                    dst[r + 2] = (unsigned char)(h >> 16);
+                    dst[r + 3] = (unsigned char)(h >> 24);
+                    r += 4u;
+                    __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
+                }
                 f->sizes[cg] = r;
                 __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
                 return 0;
@@ -718,6 +787,9 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     }
     __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->devStats[1], 1ull, __ATOMIC_RELAXED);
+    /* libzstd has the content here and hashes it itself */
+    if (qfCtxChecksum(w, pt->hashed)) return -1;
+    if (pt->hashed) __atomic_fetch_add(&f->cksumStats[1], 1ull, __ATOMIC_RELAXED);
     if (haveSeqs && qfSeq) {
         (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
         r = qfSeq(w->zc, dst, f->stride, w->seqs, ns, w->raw, n);
@@ -807,6 +879,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size
         !qzstd_hip_event_record || !qzstd_hip_stream_wait_event || !qzstd_hip_event_destroy || !qzstd_hip_memcpy2d_d2d ||
         (batch && !qzstd_hip_gather))
         return (size_t)-1; /* a device layer without the device-input entry points */
+    if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
     j.dev = -1;
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
@@ -836,6 +909,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size
 
     j.f = f;
     j.bufs = bufs;
+    j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
         const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
@@ -924,4 +998,24 @@ void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
     int k;
     if (!stats) return;
     for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->devStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+int QZSTD_frontSetChecksum(QZSTD_Front *f, int on)
+{
+    int busy;
+    if (!f) return -1;
+    pthread_mutex_lock(&f->mu);
+    busy = f->devBusy || f->running;
+    if (!busy) f->checksum = on != 0;
+    pthread_mutex_unlock(&f->mu);
+    return busy ? -1 : 0;
+}
+
+int QZSTD_frontGetChecksum(const QZSTD_Front *f) { return f ? f->checksum : 0; }
+
+void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 2; k++) stats[k] = f ? __atomic_load_n(&f->cksumStats[k], __ATOMIC_RELAXED) : 0ull;
 }

@@ -16,6 +16,13 @@ byte, frames that took the raw-bytes fallback, compressed sizes, whether both wa
   cat    torch.cat + one QZSTD_frontCompressDevice call, the cat inside the window (mixes a and b)
 
   python tools/device_bench.py --batch --gib 1 --reps 3 [--levels 1,6,12] [--ways batch,loop,cat] [--mixes a_128k,b_loguniform,c_one]
+
+--checksum: content checksums (QZSTD_frontSetChecksum).  The legs above on one tensor — host (t.cpu() + QZSTD_frontCompress: the baseline,
+libzstd hashes), device (QZSTD_frontCompressDevice: the GPU hashes) — and batch (one QZSTD_frontCompressDeviceBatch call over the tensor's
+128 KiB pieces, each an allocation of its own), every leg with the setting off and on in the same run on the same front, every run listed;
+plus who hashed the frames and whether the device frames equal the host path's with the setting on.
+
+  python tools/device_bench.py --checksum --gib 1 --reps 3 [--levels 1,6,12] [--legs host,device,batch] [--no-compare]
 """
 import argparse
 import json
@@ -103,9 +110,82 @@ def batch_main(a):
     print(json.dumps(out))
 
 
+def checksum_main(a):
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    size = int(a.gib * (1 << 30))
+    n = (size + a.chunk - 1) // a.chunk
+    data = K.by_name("system", size)
+    t = torch.frombuffer(bytearray(data), dtype=torch.uint8).to("cuda:0")
+    del data
+    pieces = [t[o:o + 131072].clone() for o in range(0, size, 131072)]
+    torch.cuda.synchronize()
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "levels": {},
+           "timed": "library calls (+ t.cpu() for the host leg), GB/s of input, every run of %d, checksum off and on alternating" % a.reps}
+    for level in [int(x) for x in a.levels.split(",")]:
+        fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            stream = torch.cuda.current_stream().cuda_stream
+            bufs, nb, nf = fr.batch([(p.data_ptr(), p.numel()) for p in pieces])
+            fr.reserve_frames(max(n, nf))
+
+            def host_pass():
+                h = t.cpu()
+                return fr.call_host(h.data_ptr(), size)[0] == n
+
+            def device_pass():
+                return fr.call_device(t.data_ptr(), size, stream)[0] == n
+
+            def batch_pass():
+                return fr.call_device_batch(bufs, nb, nf, stream)[0] == nf
+
+            legs = [x for x in (("host", host_pass), ("device", device_pass), ("batch", batch_pass)) if x[0] in a.legs.split(",")]
+            runs = {"%s_%s_gbps" % (name, ("off", "on")[on]): [] for name, _ in legs for on in (0, 1)}
+            for on in (0, 1):  # untimed: first touch of the destination, the device slots, the pinned arenas, the hash buffers
+                assert fr.set_checksum(on) == 0
+                for name, f in legs:
+                    assert f(), name
+            c0, d2h = fr.checksum_stats(), {}
+            for _ in range(a.reps):
+                for on in (0, 1):
+                    assert fr.set_checksum(on) == 0
+                    for name, f in legs:
+                        torch.cuda.synchronize()
+                        s0 = fr.stats()
+                        t0 = time.perf_counter()
+                        ok = f()
+                        dt = time.perf_counter() - t0
+                        assert ok, "%s pass failed" % name
+                        runs["%s_%s_gbps" % (name, ("off", "on")[on])].append(round(size / dt / 1e9, 3))
+                        d2h["%s_%s" % (name, ("off", "on")[on])] = round((fr.stats()[2] - s0[2]) / size, 5)
+            c1 = fr.checksum_stats()
+            res = out["levels"][str(level)] = dict(runs)
+            res["d2h_bytes_per_input_byte"] = d2h
+            res["frames_hashed_by_gpu_per_rep"] = (c1[0] - c0[0]) // a.reps
+            res["frames_hashed_by_libzstd_per_rep"] = (c1[1] - c0[1]) // a.reps
+            if not a.no_compare:
+                fr.set_checksum(1)
+                h = t.cpu()
+                r, sizes = fr.call_host(h.data_ptr(), size)
+                frames_h = fr.frames(n, sizes)
+                r, sizes = fr.call_device(t.data_ptr(), size, stream)
+                frames_d = fr.frames(n, sizes)
+                res["frames_identical_to_host_path"] = frames_h == frames_d
+                res["frames_flagged"] = all(f[4] & 4 for f in frames_d)
+                res["compressed_on"] = sum(len(x) for x in frames_d)
+        finally:
+            fr.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", action="store_true")
+    ap.add_argument("--checksum", action="store_true")
+    ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
+    ap.add_argument("--no-compare", action="store_true", help="--checksum: skip the closing comparison of the two paths' frames (kernel traces)")
     ap.add_argument("--ways", default="batch,loop,cat")
     ap.add_argument("--mixes", default="a_128k,b_loguniform,c_one")
     ap.add_argument("--gib", type=float, default=1.0)
@@ -114,6 +194,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.checksum:
+        return checksum_main(a)
     if a.batch:
         return batch_main(a)
     B.Zstd()

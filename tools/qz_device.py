@@ -1,5 +1,5 @@
 """ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
-QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats), compress_tensor() for a contiguous GPU tensor of any dtype and compress_tensors()
+QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum), compress_tensor() for a contiguous GPU tensor of any dtype and compress_tensors()
 for a list of them in one call.
 
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
@@ -28,6 +28,11 @@ class GatherRow(C.Structure):
     _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32)]
 
 
+class HashRow(C.Structure):
+    """qzstd_hip_hash_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("srcOff", C.c_uint64), ("len", C.c_uint64)]
+
+
 def bind(F):
     """the front-end's C surface, the device entry points included, on a loaded library"""
     F.QZSTD_createFront.restype = C.c_void_p
@@ -48,6 +53,13 @@ def bind(F):
     F.QZSTD_frontDeviceStats.restype = None
     F.QZSTD_frontDeviceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     F.QZSTD_freeFront.argtypes = [C.c_void_p]
+    if hasattr(F, "QZSTD_frontSetChecksum"):  # (absent from an older library)
+        F.QZSTD_frontSetChecksum.restype = C.c_int
+        F.QZSTD_frontSetChecksum.argtypes = [C.c_void_p, C.c_int]
+        F.QZSTD_frontGetChecksum.restype = C.c_int
+        F.QZSTD_frontGetChecksum.argtypes = [C.c_void_p]
+        F.QZSTD_frontChecksumStats.restype = None
+        F.QZSTD_frontChecksumStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -157,6 +169,19 @@ class DeviceFront:
     def stats(self) -> list:
         st = (C.c_ulonglong * 4)()
         self.lib.QZSTD_frontDeviceStats(self.f, st)
+        return list(st)
+
+    def set_checksum(self, on) -> int:
+        """QZSTD_frontSetChecksum: content checksums in every frame of the calls that follow -> 0, or -1 while a call runs"""
+        return self.lib.QZSTD_frontSetChecksum(self.f, 1 if on else 0)
+
+    def get_checksum(self) -> int:
+        return self.lib.QZSTD_frontGetChecksum(self.f)
+
+    def checksum_stats(self) -> list:
+        """frames whose checksum [0] the GPU computed, [1] libzstd computed"""
+        st = (C.c_ulonglong * 2)()
+        self.lib.QZSTD_frontChecksumStats(self.f, st)
         return list(st)
 
     def close(self):
