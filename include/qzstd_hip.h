@@ -1,6 +1,6 @@
 /*
  * qzstd_hip.h — thin C ABI between the plain-C plugin (host/qatseqprod.c) and the
- * CDNA4 / gfx950 HIP side (csrc/qzstd_kernels.hip).  extern "C", plain pointers and
+ * CDNA4 / gfx950 HIP side (csrc/qzstd_runtime.hip, csrc/qzstd_kernels.hip).  extern "C", plain pointers and
  * sizes, no C++ / torch types.
  *
  * Which reference interface each entry point replaces (the reference reaches its

@@ -2,7 +2,7 @@
 
 The product is the C library in ``lib/`` (``libqatseqprod.so`` / ``.a``; public headers in
 ``../include``): plain-C host code (``host/qatseqprod.c``) over a thin HIP C ABI
-(``csrc/qzstd_kernels.hip``).  This Python package is only a loader for tests / bench /
+(``csrc/qzstd_runtime.hip``, ``csrc/qzstd_kernels.hip``, ``csrc/qzstd_device_input.hip``).  This Python package is only a loader for tests / bench /
 the driver's build check; it adds no behaviour of its own and has no CPU fallback.
 """
 import ctypes

@@ -1,0 +1,395 @@
+/*
+ * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
+ * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, and the XXH64 content
+ * checksum.  They use nothing of the match-finder (qzstd_kernels.hip).
+ */
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "qzstd_hip.h"
+#include "qzstd_hip_device.h"
+#include "qzstd_hip_internal.h"
+
+/* ---------------------------------------------------------------- device-resident input: compaction ---------- */
+/*
+ * qzstd_hip_compact (include/qzstd_hip_device.h): a launch's ZSTD_Sequence entries (16 B each, in device memory) and the literal bytes they
+ * name, packed densely into one arena — 8-byte entries (QZSTD_HIP_PACK, tag 0) and the literals back to back — so that one D2H copy of
+ * about 0.64 B per input byte (level 1, text) gives libzstd everything ZSTD_compressSequencesAndLiterals needs.  Three kernels:
+ *   count  one workgroup per block: checks the block's entries and sums their literal bytes -> header {count, litBytes}
+ *   scan   one workgroup: exclusive prefix sums of entries and literal bytes over the blocks, the arena's capacity check
+ *   emit   one workgroup per block: packs the entries and copies the literal runs, a chunk of kCompactT entries at a time (the
+ *          destination and source offsets of the runs are a scan of litLength and litLength + matchLength over the chunk in LDS)
+ * A block is emitted only when its entries cover exactly [0, srcLen): every literal read lies inside [srcOff, srcOff + srcLen).
+ */
+namespace {
+constexpr uint32_t kCompactT = 512u; /* threads per workgroup of the count and emit kernels, entries per chunk of the emit kernel */
+
+/* block-wide inclusive scan of one 64-bit value per thread (kCompactT threads); `red` holds kCompactT / 64 partials */
+__device__ inline unsigned long long compact_scan(unsigned long long v, unsigned long long *red, unsigned long long *total)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const unsigned long long o = __shfl_up(v, d);
+        if (lane >= d) v += o;
+    }
+    if (lane == 63u) red[wave] = v;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+    for (uint32_t w = 0; w < kCompactT / 64u; w++) {
+        const unsigned long long r = red[w];
+        if (w < wave) before += r;
+        all += r;
+    }
+    __syncthreads(); /* red is reused by the next call */
+    *total = all;
+    return v + before;
+}
+
+__global__ __launch_bounds__(kCompactT) void qzstd_compact_count_kernel(const qzstd_hip_block_t *__restrict__ blocks, const uint4 *__restrict__ seqs,
+                                                                        const uint32_t *__restrict__ nseq, qzstd_hip_compact_hdr_t *__restrict__ hdr)
+{
+    __shared__ unsigned long long red[kCompactT / 64u];
+    const qzstd_hip_block_t bk = blocks[blockIdx.x];
+    const uint32_t count = nseq[blockIdx.x];
+    bool ok = count != QZSTD_HIP_NSEQ_ERROR && count >= 1u && count <= bk.seqCap && (bk.mark & QZSTD_HIP_MARK_COMPACT) == 0u;
+    unsigned long long lit = 0, cover = 0, bad = 0;
+    if (ok) {
+        const uint4 *q = seqs + bk.seqOff;
+        for (uint32_t i = threadIdx.x; i < count; i += kCompactT) {
+            const uint4 s = q[i]; /* x offset, y litLength, z matchLength */
+            lit += s.y;
+            cover += (unsigned long long)s.y + s.z;
+            /* the packed fields: offset 17 bits, litLength 18, matchLength 17; the last entry is the delimiter */
+            if (s.x >= (1u << 17) || s.y > (1u << 17) || s.z >= (1u << 17) || (i + 1u == count && (s.x | s.z) != 0u)) bad++;
+        }
+    }
+    unsigned long long t;
+    (void)compact_scan(lit, red, &lit);
+    (void)compact_scan(cover, red, &cover);
+    (void)compact_scan(bad, red, &t);
+    if (threadIdx.x == 0) {
+        ok = ok && t == 0 && cover == bk.srcLen;
+        hdr[blockIdx.x].count = ok ? count : QZSTD_HIP_NSEQ_ERROR;
+        hdr[blockIdx.x].litBytes = ok ? (uint32_t)lit : 0u;
+    }
+}
+
+/* work: [0, 8n) first entry of each block, [8n, 16n) first literal byte of each block, then {entries, literal bytes} in total */
+__global__ __launch_bounds__(kCompactT) void qzstd_compact_scan_kernel(qzstd_hip_compact_hdr_t *__restrict__ hdr, uint32_t n,
+                                                                       unsigned long long *__restrict__ work, unsigned long long cap)
+{
+    __shared__ unsigned long long red[kCompactT / 64u];
+    unsigned long long *seqBase = work, *litBase = work + n, *totals = work + 2u * (size_t)n;
+    unsigned long long carryAll = 0, carrySeq = 0, carryLit = 0;
+    for (uint32_t c = 0; c < n; c += kCompactT) {
+        const uint32_t b = c + threadIdx.x;
+        qzstd_hip_compact_hdr_t h = { QZSTD_HIP_NSEQ_ERROR, 0u };
+        if (b < n) h = hdr[b];
+        const unsigned long long cnt = h.count == QZSTD_HIP_NSEQ_ERROR ? 0ull : h.count;
+        unsigned long long tAll, tSeq, tLit;
+        /* the arena's bytes up to the end of this block (entries and literals both counted): the blocks that do not fit are a suffix */
+        const unsigned long long endAll = carryAll + compact_scan(8ull * cnt + h.litBytes, red, &tAll);
+        const bool fits = endAll <= cap;
+        const unsigned long long keepCnt = fits ? cnt : 0ull, keepLit = fits ? h.litBytes : 0ull;
+        const unsigned long long inSeq = compact_scan(keepCnt, red, &tSeq), inLit = compact_scan(keepLit, red, &tLit);
+        if (b < n) {
+            seqBase[b] = carrySeq + inSeq - keepCnt;
+            litBase[b] = carryLit + inLit - keepLit;
+            if (!fits && h.count != QZSTD_HIP_NSEQ_ERROR) { h.count = QZSTD_HIP_NSEQ_ERROR; h.litBytes = 0u; hdr[b] = h; }
+        }
+        carryAll += tAll;
+        carrySeq += tSeq;
+        carryLit += tLit;
+    }
+    if (threadIdx.x == 0) { totals[0] = carrySeq; totals[1] = carryLit; }
+}
+
+__global__ __launch_bounds__(kCompactT) void qzstd_compact_emit_kernel(const uint8_t *__restrict__ src, const qzstd_hip_block_t *__restrict__ blocks,
+                                                                       const uint4 *__restrict__ seqs, const qzstd_hip_compact_hdr_t *__restrict__ hdr,
+                                                                       const unsigned long long *__restrict__ work, uint32_t n, uint8_t *__restrict__ arena)
+{
+    __shared__ unsigned long long red[kCompactT / 64u];
+    __shared__ uint32_t dStart[kCompactT + 1u], sStart[kCompactT];
+    const qzstd_hip_compact_hdr_t h = hdr[blockIdx.x];
+    if (h.count == QZSTD_HIP_NSEQ_ERROR) return;
+    const qzstd_hip_block_t bk = blocks[blockIdx.x];
+    const unsigned long long seqBase = work[blockIdx.x], litBase = work[n + blockIdx.x], totalSeq = work[2u * (size_t)n];
+    const size_t entriesOff = QZSTD_HIP_COMPACT_ENTRIES_OFF(n);
+    unsigned long long *outSeq = reinterpret_cast<unsigned long long *>(arena + entriesOff) + seqBase;
+    uint8_t *outLit = arena + entriesOff + 8ull * totalSeq + litBase;
+    const uint8_t *in = src + bk.srcOff;
+    const uint4 *q = seqs + bk.seqOff;
+    uint32_t dCarry = 0, sCarry = 0; /* literal bytes and covered bytes of the chunks before */
+    for (uint32_t c = 0; c < h.count; c += kCompactT) {
+        const uint32_t i = c + threadIdx.x;
+        uint4 s = make_uint4(0u, 0u, 0u, 0u);
+        if (i < h.count) {
+            s = q[i];
+            outSeq[i] = QZSTD_HIP_PACK(s.x, s.y, s.z, 0u);
+        }
+        unsigned long long tLit, tCov;
+        const uint32_t dEnd = (uint32_t)compact_scan(s.y, red, &tLit), sEnd = (uint32_t)compact_scan((unsigned long long)s.y + s.z, red, &tCov);
+        dStart[threadIdx.x] = dEnd - s.y;
+        sStart[threadIdx.x] = sCarry + sEnd - s.y - s.z;
+        if (threadIdx.x == 0) dStart[kCompactT] = (uint32_t)tLit;
+        __syncthreads();
+        /* the chunk's literal bytes [0, tLit): four consecutive bytes per lane, the run found by a binary search over dStart.  Byte stores:
+         * the runs start anywhere in the source and the destination.  Measured at level 1 (ms per GiB, the emit kernel): bytes 2.17 - 2.39; aligned
+         * dword stores of gathered bytes 2.50; aligned 16-byte stores 4.65 — a chunk's ~1.7 KiB of literals then keeps a quarter of the lanes
+         * busy, each with sixteen dependent byte loads.  Wider stores do not make it faster */
+        const uint32_t lits = (uint32_t)tLit;
+        for (uint32_t j = threadIdx.x * 4u; j < lits; j += kCompactT * 4u) {
+            uint32_t lo = 0, hi = kCompactT; /* the last run e with dStart[e] <= j */
+            while (hi - lo > 1u) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (dStart[mid] <= j) lo = mid; else hi = mid;
+            }
+            uint32_t e = lo;
+            for (uint32_t k = 0; k < 4u && j + k < lits; k++) {
+                while (j + k >= dStart[e + 1u]) e++;
+                outLit[dCarry + j + k] = in[sStart[e] + (j + k - dStart[e])];
+            }
+        }
+        dCarry += lits;
+        sCarry += (uint32_t)tCov;
+        __syncthreads(); /* dStart / sStart are rewritten by the next chunk */
+    }
+}
+} // namespace
+
+extern "C" {
+
+size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks) { return (size_t)nBlocks * 16u + 16u; }
+
+int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
+                      const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work, size_t workBytes)
+{
+    if (nBlocks == 0) return 0;
+    if (!d_src || !d_blocks || !d_seqs || !d_nseq || !d_arena || !d_work) return fail_msg("qzstd_hip_compact: null pointer");
+    if (workBytes < qzstd_hip_compact_workspace_bytes(nBlocks) || ((uintptr_t)d_work & 7u) || ((uintptr_t)d_arena & 15u))
+        return fail_msg("qzstd_hip_compact: workspace too small, or workspace / arena not aligned");
+    if (arenaBytes < QZSTD_HIP_COMPACT_ENTRIES_OFF(nBlocks)) return fail_msg("qzstd_hip_compact: arena smaller than its headers");
+    QZ_SET_DEVICE(device);
+    const hipStream_t s = (hipStream_t)stream;
+    auto *hdr = static_cast<qzstd_hip_compact_hdr_t *>(d_arena);
+    auto *work = static_cast<unsigned long long *>(d_work);
+    const auto *seqs = static_cast<const uint4 *>(d_seqs);
+    hipLaunchKernelGGL(qzstd_compact_count_kernel, dim3(nBlocks), dim3(kCompactT), 0, s, d_blocks, seqs, d_nseq, hdr);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_count_kernel");
+    hipLaunchKernelGGL(qzstd_compact_scan_kernel, dim3(1), dim3(kCompactT), 0, s, hdr, nBlocks, work,
+                       (unsigned long long)(arenaBytes - QZSTD_HIP_COMPACT_ENTRIES_OFF(nBlocks)));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_scan_kernel");
+    hipLaunchKernelGGL(qzstd_compact_emit_kernel, dim3(nBlocks), dim3(kCompactT), 0, s, static_cast<const uint8_t *>(d_src), d_blocks, seqs, hdr,
+                       work, nBlocks, static_cast<uint8_t *>(d_arena));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_emit_kernel");
+    return 0;
+}
+
+} /* extern "C" */
+
+/* ---------------------------------------------------------------- gather (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kGatherT = 256u;               /* threads per workgroup */
+constexpr uint32_t kGatherWords = 4u * kGatherT;  /* 16-byte words of the stage per workgroup: 16 KiB */
+
+/* the last row of [lo, hi] whose first word is at or before word w (lo when there is none) */
+__device__ inline uint32_t gather_row_of(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t lo, uint32_t hi, uint32_t w)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if ((uint32_t)(rows[mid].dstOff >> 4) <= w) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+/* one workgroup per 16 KiB of the stage between the first row's start and the last row's end; a lane takes every 256th word.  The rows that
+ * reach into the workgroup's piece are found once (two searches over all rows), a word's own row by a search among those: no step at all
+ * inside a long row, at most ten where 1024 one-word rows share the piece */
+__global__ __launch_bounds__(kGatherT) void qzstd_gather_kernel(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t nRows, uint32_t firstWord,
+                                                                uint32_t endWord, uint4 *__restrict__ stage)
+{
+    __shared__ uint32_t span[2];
+    const uint32_t w0 = firstWord + blockIdx.x * kGatherWords;
+    const uint32_t wEnd = endWord - w0 < kGatherWords ? endWord : w0 + kGatherWords;
+    if (threadIdx.x == 0) {
+        span[0] = gather_row_of(rows, 0u, nRows - 1u, w0);
+        span[1] = gather_row_of(rows, span[0], nRows - 1u, wEnd - 1u);
+    }
+    __syncthreads();
+    const uint32_t rLo = span[0], rHi = span[1];
+    for (uint32_t w = w0 + threadIdx.x; w < wEnd; w += kGatherT) {
+        const qzstd_hip_gather_row_t row = rows[gather_row_of(rows, rLo, rHi, w)];
+        const uint64_t o = ((uint64_t)w << 4) - row.dstOff; /* the word's first byte in its row (wraps to a huge value in front of row 0) */
+        if (o >= (uint64_t)row.len + row.pad) continue;     /* between two rows: not ours to write */
+        uint64_t o0 = 0, o1 = 0;
+        if (o < row.len) {
+            const uint64_t a = row.src + o;
+            const uint32_t sh = (uint32_t)a & 15u;
+            const uint32_t valid = row.len - o < 16u ? (uint32_t)(row.len - o) : 16u; /* payload bytes of this word */
+            const uint4 *p = reinterpret_cast<const uint4 *>(a - sh);
+            /* the aligned word that holds byte a, and the next one only when payload of this word lies in it */
+            const uint4 l = p[0];
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh + valid > 16u) h = p[1];
+            const uint64_t l0 = l.x | (uint64_t)l.y << 32, l1 = l.z | (uint64_t)l.w << 32, h0 = h.x | (uint64_t)h.y << 32, h1 = h.z | (uint64_t)h.w << 32;
+            /* {h1 h0 l1 l0} >> 8 * sh: whole 64-bit halves first, then the bytes */
+            const bool half = (sh & 8u) != 0u;
+            const uint32_t bits = (sh & 7u) * 8u;
+            const uint64_t a0 = half ? l1 : l0, a1 = half ? h0 : l1, a2 = half ? h1 : h0;
+            o0 = bits ? (a0 >> bits) | (a1 << (64u - bits)) : a0;
+            o1 = bits ? (a1 >> bits) | (a2 << (64u - bits)) : a1;
+            if (valid < 16u) { /* the row's last word: zero behind the payload (what the shift brought in lies inside the aligned words read) */
+                o1 = valid > 8u ? o1 & ((1ull << ((valid - 8u) * 8u)) - 1ull) : 0ull;
+                if (valid < 8u) o0 &= (1ull << (valid * 8u)) - 1ull;
+            }
+        }
+        stage[w] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
+                                void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_gather: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_gather_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_gather: dstOff or len + pad not a multiple of 16");
+        if (r.len && !r.src) return fail_msg("qzstd_hip_gather: null source");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_gather: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_gather: a row ends past stageBytes");
+        end = r.dstOff + ext;
+    }
+    /* 16-byte words in 32 bits, with room for a workgroup's last step */
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_gather: stage span too large");
+    const uint32_t firstWord = (uint32_t)(rows[0].dstOff >> 4), endWord = (uint32_t)(end >> 4);
+    if (endWord == firstWord) return 0; /* nothing but empty rows */
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (gather rows)");
+    const uint32_t groups = (endWord - firstWord + kGatherWords - 1u) / kGatherWords;
+    hipLaunchKernelGGL(qzstd_gather_kernel, dim3(groups), dim3(kGatherT), 0, (hipStream_t)stream, d_rows, nRows, firstWord, endWord,
+                       static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_gather_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- content checksum (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kHashRows = 16u;                 /* rows per wave: four lanes each, one per XXH64 accumulator */
+constexpr uint32_t kHashTile = QZSTD_HIP_XXH64_TILE; /* bytes of a row per fetch: one whole-wave 16-byte load */
+constexpr uint32_t kHashPitch = kHashTile + 32u;    /* a row's tile in LDS: 32 bytes of padding put the eight rows of a 32-lane group on
+                                                       the 64 banks once (8 B per lane, 32 B per row and stripe) */
+constexpr uint64_t kXP1 = 0x9E3779B185EBCA87ull, kXP2 = 0xC2B2AE3D27D4EB4Full, kXP3 = 0x165667B19E3779F9ull, kXP4 = 0x85EBCA77C2B2AE63ull,
+                   kXP5 = 0x27D4EB2F165667C5ull;
+
+typedef uint32_t hash_word_t __attribute__((ext_vector_type(4))); /* one aligned 16-byte word */
+
+__device__ inline uint64_t xxh_rotl(uint64_t v, uint32_t r) { return (v << r) | (v >> (64u - r)); }
+__device__ inline uint64_t xxh_round(uint64_t acc, uint64_t in) { return xxh_rotl(acc + in * kXP2, 31u) * kXP1; }
+__device__ inline uint64_t xxh_merge(uint64_t h, uint64_t v) { return (h ^ xxh_round(0ull, v)) * kXP1 + kXP4; }
+
+/* One wave per workgroup, rows [16 * blockIdx.x, + 16).  Per step every row's next 1 KiB tile is fetched with one 16-byte load per lane
+ * (the words that overlap the row only) into registers while the tile before it, in LDS, is consumed: lane 4 r + a runs accumulator a
+ * of row r over the tile's 32-byte stripes.  The multiply chain (two 64-bit multiplies per 8 bytes and lane) sets the pace; the fetch of
+ * the next tile has a whole tile's chain to arrive.  A row ends in the step that holds byte (len & ~31): its first lane collects the
+ * four accumulators, walks the tail (8-, 4- and 1-byte steps over bytes below len only) and stores the hash.  The loop runs to the longest
+ * row of the wave; lanes of rows that are done idle. */
+__global__ __launch_bounds__(64) void qzstd_xxh64_kernel(const uint8_t *__restrict__ base, const qzstd_hip_hash_row_t *__restrict__ rows,
+                                                         uint32_t nRows, unsigned long long *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t tile[kHashRows * kHashPitch];
+    const uint32_t lane = threadIdx.x, r = lane >> 2, a = lane & 3u;
+    const uint32_t row0 = blockIdx.x * kHashRows;
+    /* the wave's rows, by uniform addresses: their offsets and 16-byte word counts are the same in every lane (scalar registers) */
+#define QZ_HASH_EACH_ROW(X, t) X(0, t) X(1, t) X(2, t) X(3, t) X(4, t) X(5, t) X(6, t) X(7, t) X(8, t) X(9, t) X(10, t) X(11, t) X(12, t) X(13, t) X(14, t) X(15, t)
+#define QZ_HASH_ROW(j, t)                                                                   \
+    const uint64_t off##j = row0 + j < nRows ? rows[row0 + j].srcOff : 0ull;               \
+    const uint64_t words##j = row0 + j < nRows ? (rows[row0 + j].len + 15u) >> 4 : 0ull;   \
+    hash_word_t next##j = { 0u, 0u, 0u, 0u };                                              \
+    nTiles = (words##j >> 6) + 1u > nTiles ? (words##j >> 6) + 1u : nTiles;
+    uint64_t nTiles = 0; /* steps of the wave: past the longest row's tail (a row of k whole tiles ends in step k, which fetches nothing) */
+    QZ_HASH_EACH_ROW(QZ_HASH_ROW, 0)
+    const uint64_t len = row0 + r < nRows ? rows[row0 + r].len : 0ull;
+    const uint64_t endTile = len / kHashTile; /* the tile that holds the row's tail; every stripe of the row lies at or before it */
+    uint64_t acc = a == 0u ? kXP1 + kXP2 : (a == 1u ? kXP2 : (a == 2u ? 0ull : 0ull - kXP1));
+    uint64_t stripesLeft = len >> 5;
+    /* tile t of row j: word t * 64 + lane of the row, when the row has it.  Sixteen named registers, not an array: the fetches must stay
+     * in flight in VGPRs across the chain below */
+#define QZ_HASH_FETCH1(j, t) \
+    if ((t) * (kHashTile / 16u) + lane < words##j) next##j = reinterpret_cast<const hash_word_t *>(base + off##j)[(t) * (kHashTile / 16u) + lane];
+#define QZ_HASH_STAGE1(j, t) \
+    if ((t) * (kHashTile / 16u) + lane < words##j) *reinterpret_cast<hash_word_t *>(&tile[j * kHashPitch + lane * 16u]) = next##j;
+#define QZ_HASH_FETCH(t) QZ_HASH_EACH_ROW(QZ_HASH_FETCH1, t)
+#define QZ_HASH_STAGE(t) QZ_HASH_EACH_ROW(QZ_HASH_STAGE1, t)
+    QZ_HASH_FETCH(0ull)
+    QZ_HASH_STAGE(0ull)
+    __syncthreads();
+    for (uint64_t t = 0; t < nTiles; t++) {
+        const bool more = t + 1u < nTiles;
+        if (more) { QZ_HASH_FETCH(t + 1u) }
+        const uint8_t *mine = &tile[r * kHashPitch];
+        const uint32_t n = stripesLeft < kHashTile / 32u ? (uint32_t)stripesLeft : kHashTile / 32u;
+        for (uint32_t s = 0; s < n; s++) acc = xxh_round(acc, *reinterpret_cast<const uint64_t *>(mine + s * 32u + a * 8u));
+        stripesLeft -= n;
+        /* (all lanes: the row's accumulators to each of its lanes) */
+        const uint64_t v1 = __shfl(acc, (int)(lane & ~3u)), v2 = __shfl(acc, (int)(lane & ~3u) + 1), v3 = __shfl(acc, (int)(lane & ~3u) + 2),
+                       v4 = __shfl(acc, (int)(lane & ~3u) + 3);
+        if (t == endTile && a == 0u && row0 + r < nRows) {
+            uint64_t h;
+            if (len >= 32u) {
+                h = xxh_rotl(v1, 1u) + xxh_rotl(v2, 7u) + xxh_rotl(v3, 12u) + xxh_rotl(v4, 18u);
+                h = xxh_merge(xxh_merge(xxh_merge(xxh_merge(h, v1), v2), v3), v4);
+            } else {
+                h = kXP5;
+            }
+            h += len;
+            uint32_t p = (uint32_t)((len & ~(uint64_t)31u) - t * kHashTile), left = (uint32_t)len & 31u;
+            for (; left >= 8u; left -= 8u, p += 8u)
+                h = xxh_rotl(h ^ xxh_round(0ull, *reinterpret_cast<const uint64_t *>(mine + p)), 27u) * kXP1 + kXP4;
+            if (left >= 4u) {
+                h = xxh_rotl(h ^ (uint64_t)*reinterpret_cast<const uint32_t *>(mine + p) * kXP1, 23u) * kXP2 + kXP3;
+                p += 4u;
+                left -= 4u;
+            }
+            for (; left; left--, p++) h = xxh_rotl(h ^ (uint64_t)mine[p] * kXP5, 11u) * kXP1;
+            h ^= h >> 33;
+            h *= kXP2;
+            h ^= h >> 29;
+            h *= kXP3;
+            h ^= h >> 32;
+            out[row0 + r] = h;
+        }
+        __syncthreads(); /* the tile is consumed: the next one may take its place */
+        if (more) { QZ_HASH_STAGE(t + 1u) }
+        __syncthreads();
+    }
+#undef QZ_HASH_EACH_ROW
+#undef QZ_HASH_ROW
+#undef QZ_HASH_FETCH1
+#undef QZ_HASH_STAGE1
+#undef QZ_HASH_FETCH
+#undef QZ_HASH_STAGE
+}
+} // namespace
+
+extern "C" int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
+                               qzstd_hip_hash_row_t *d_rows, uint64_t *d_out)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_out) return fail_msg("qzstd_hip_xxh64: null pointer");
+    if ((uintptr_t)d_base & 15u) return fail_msg("qzstd_hip_xxh64: base not 16-byte aligned");
+    for (uint32_t i = 0; i < nRows; i++) {
+        if (rows[i].srcOff & 15u) return fail_msg("qzstd_hip_xxh64: srcOff not a multiple of 16");
+        if (rows[i].len && !d_base) return fail_msg("qzstd_hip_xxh64: null base");
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (hash rows)");
+    hipLaunchKernelGGL(qzstd_xxh64_kernel, dim3((nRows + kHashRows - 1u) / kHashRows), dim3(64), 0, (hipStream_t)stream,
+                       static_cast<const uint8_t *>(d_base), d_rows, nRows, reinterpret_cast<unsigned long long *>(d_out));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_xxh64_kernel");
+    return 0;
+}

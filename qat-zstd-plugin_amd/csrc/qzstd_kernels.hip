@@ -1,6 +1,7 @@
 /*
  * qzstd_kernels.hip — the block-level ZSTD sequence producer's match-finder for
- * AMD Instinct MI355X (CDNA4, gfx950), plus the thin C ABI of include/qzstd_hip.h.
+ * AMD Instinct MI355X (CDNA4, gfx950) and its resident service, plus their part of the C ABI of include/qzstd_hip.h
+ * (the rest: qzstd_runtime.hip; the kernels for device-resident input: qzstd_device_input.hip).
  *
  * What it replaces: the reference hands each <=128 KiB block to QAT silicon
  * (cpaDcCompressData2, /root/reference/src/qatseqprod.c:1245) and then parses the
@@ -59,11 +60,9 @@
 #include <mutex>
 #include <sched.h>
 #include <time.h>
-#include <sys/syscall.h>
-#include <unistd.h>
 
 #include "qzstd_hip.h"
-#include "qzstd_hip_device.h"
+#include "qzstd_hip_internal.h"
 
 /* Round 6: "progress-inverse priority" (QZ_PRIO, below the chain levels).  The issue arbiter serves the OLDER waves of a SIMD first, so waves 4-7 of a
  * workgroup reach every barrier last and run the end of every interval alone, with nobody to hide their latencies behind
@@ -2482,25 +2481,6 @@ __global__ __launch_bounds__(kThreads) void qzstd_probe_lds_order(uint32_t *bad)
     if (wrong) atomicAdd(bad, wrong);
 }
 
-thread_local char g_err[256] = "";
-
-int fail(const char *what, hipError_t e)
-{
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return -1;
-}
-int fail_msg(const char *what)
-{
-    snprintf(g_err, sizeof(g_err), "%s", what);
-    return -1;
-}
-
-#define QZ_CHECK(call, what)                       \
-    do {                                           \
-        hipError_t e_ = (call);                    \
-        if (e_ != hipSuccess) return fail(what, e_); \
-    } while (0)
-
 /* ---- the resident service: host-side state (the kernels: qzstd_service_worker / qzstd_service_dispatcher above) ---- */
 struct Service {
     std::mutex mu; /* set-up, launches, stops */
@@ -2566,35 +2546,46 @@ int svc_stop_locked(Service &s, unsigned waitMs)
     return 0;
 }
 
-/* before memory is freed: hipFree / hipHostFree wait for every stream, which a resident kernel never lets finish */
-struct SvcFreeze {
-    SvcFreeze()
-    {
-        g_svcFreeze.fetch_add(1);
-        for (int d = 0; d < 64; d++) {
-            Service &s = g_svc[d];
-            if (!s.hs) continue;
-            std::lock_guard<std::mutex> g(s.mu);
-            (void)svc_stop_locked(s, 2000);
-        }
-    }
-    ~SvcFreeze() { g_svcFreeze.fetch_sub(1); }
-};
+/* ---- the one map from a search profile to a kernel variant ----
+ * The eight legal searches as <HAS_LONG, REP, CHAIN, TURNS>, in the order variant_index() counts them; X's last argument is NEAR for the
+ * launch kernels and MULTI for the service workers. */
+#define QZ_SEARCHES(X, last)                                                                                    \
+    X(false, false, false, false, last), X(false, true, false, false, last), /* 0 tables only (level 1) */       \
+    X(false, false, false, true, last), X(false, true, false, true, last),   /* 1 turns (level 2) */             \
+    X(false, false, true, true, last), X(false, true, true, true, last),     /* 2 chain + turns (levels >= 5) */ \
+    X(true, false, false, false, last), X(true, true, false, false, last)    /* 3 second table (levels 3-4) */
+#define QZ_K(L, R, C, T, N) reinterpret_cast<const void *>(qzstd_find_sequences_kernel<L, R, C, T, N>)
+#define QZ_W(L, R, C, T, M) reinterpret_cast<const void *>(qzstd_service_worker<L, R, C, T, M>)
+const void *const kLaunchKernels[16] = { QZ_SEARCHES(QZ_K, false), QZ_SEARCHES(QZ_K, true) };
+const void *const kWorkers[8] = { QZ_SEARCHES(QZ_W, false) }; /* (the multi-level worker is not a variant of the profile: svc_launch_locked) */
+#undef QZ_K
+#undef QZ_W
+#undef QZ_SEARCHES
+
+/* index into kLaunchKernels (nearK: every block of the launch fits the ring) and, with nearK false, into kWorkers.  A profile asks for one
+ * search: chains exclude the second table and the second table excludes turns (qzstd_hip_find_sequences refuses anything else). */
+int variant_index(const qzstd_hip_profile_t &p, bool nearK)
+{
+    const int search = p.chainDepth ? 2 : (p.longSize ? 3 : (p.subTileLog ? 1 : 0));
+    return (nearK ? 8 : 0) + 2 * search + (p.repWin ? 1 : 0);
+}
 
 } // namespace
 
-extern "C" {
+/* before memory is freed: hipFree / hipHostFree wait for every stream, which a resident kernel never lets finish */
+SvcFreeze::SvcFreeze()
+{
+    g_svcFreeze.fetch_add(1);
+    for (int d = 0; d < 64; d++) {
+        Service &s = g_svc[d];
+        if (!s.hs) continue;
+        std::lock_guard<std::mutex> g(s.mu);
+        (void)svc_stop_locked(s, 2000);
+    }
+}
+SvcFreeze::~SvcFreeze() { g_svcFreeze.fetch_sub(1); }
 
-const char *qzstd_hip_last_error(void) { return g_err; }
-
-/* The library carries one code object (gfx950).  Only devices that can run it are counted, and the `device` argument
- * of every entry point indexes that filtered list (reference: instance discovery keeps only usable DC instances,
- * /root/reference/src/qatseqprod.c:529-600). */
-static std::once_flag g_devOnce;
-static int g_devCount = -1;
-static int g_devMap[64];
-static int g_devReplicas = 1; /* QZSTD_HIP_REPLICATE_DEVICES (test only): logical devices per physical one */
-static int g_ldsOrdered[64]; /* per device: -1 not probed yet, 0 no, 1 yes (probe_lds_order) */
+static int g_ldsOrdered[64]; /* per device: 0 not probed yet, 1 no, 2 yes (probe_lds_order) */
 static std::mutex g_probeMu;
 
 /* runs qzstd_probe_lds_order once per device; any failure of the probe itself counts as "no" (the ballot path needs nothing).
@@ -2602,14 +2593,14 @@ static std::mutex g_probeMu;
  * exist: the probe allocates and frees device memory, and hipFree waits for every stream of the device, so running it lazily
  * from a launch (under the device's service mutex, as rounds 2-3 did) could wait for as long as per-block requests kept a
  * service of another level alive, with the mutex held (round-3 ADVICE, medium).  Later calls only read the verdict. */
-static int probe_lds_order(int device, int physDev)
+int probe_lds_order(int device, int physDev)
 {
     {
         const int known = __atomic_load_n(&g_ldsOrdered[device], __ATOMIC_ACQUIRE);
-        if (known >= 0) return known;
+        if (known > 0) return known - 1;
     }
     std::lock_guard<std::mutex> g(g_probeMu);
-    if (g_ldsOrdered[device] >= 0) return g_ldsOrdered[device];
+    if (g_ldsOrdered[device] > 0) return g_ldsOrdered[device] - 1;
     int verdict = 0;
     const char *force = getenv("QZSTD_HIP_ORDERED_LDS"); /* 0 = never use the single-instruction insert */
     uint32_t *dBad = nullptr, hBad = 1u;
@@ -2622,296 +2613,11 @@ static int probe_lds_order(int device, int physDev)
         (void)hipFree(dBad);
     }
     (void)hipGetLastError();
-    __atomic_store_n(&g_ldsOrdered[device], verdict, __ATOMIC_RELEASE);
+    __atomic_store_n(&g_ldsOrdered[device], verdict + 1, __ATOMIC_RELEASE);
     return verdict;
 }
 
-static void probe_devices()
-{
-    int n = 0;
-    /* The runtime folds its streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and launches of different streams that share a queue run
-     * one after the other.  Announcements no longer depend on it (they go out as a few large launches on the announcement batcher's own
-     * streams, host/qatseqprod.c); the per-block paths' slot streams still do.  The variable is read when the runtime starts, so it only takes
-     * effect when this is the process's first HIP call; a value the environment already carries is left alone.  QZSTD_HIP_HW_QUEUES=0 leaves
-     * the runtime's default. */
-    {
-        const char *q = getenv("QZSTD_HIP_HW_QUEUES");
-        const int want = q && *q ? atoi(q) : 16;
-        if (want > 0 && want <= 64) {
-            char buf[16];
-            snprintf(buf, sizeof(buf), "%d", want);
-            (void)setenv("GPU_MAX_HW_QUEUES", buf, 0);
-        }
-    }
-    hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess) { fail("hipGetDeviceCount", e); (void)hipGetLastError(); g_devCount = -1; return; }
-    g_devCount = 0;
-    for (int d = 0; d < 64; d++) g_ldsOrdered[d] = -1;
-    for (int d = 0; d < n && g_devCount < 64; d++) {
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, d) != hipSuccess) { (void)hipGetLastError(); continue; }
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) continue; /* no code object for it */
-        g_devMap[g_devCount++] = d;
-    }
-    if (g_devCount == 0) fail_msg("no gfx950 device among the visible HIP devices");
-    /* TEST ONLY — QZSTD_HIP_REPLICATE_DEVICES=k lists every physical device k times: the library then sees k x n LOGICAL devices, each with
-     * its own streams, batches, pinned buffers and resident service, and the host's split of an announcement into per-GPU ranges, its state
-     * placement and QZSTD_deviceStats run over several devices on a box that has one GPU (round-5 verdict: the N > 1 path had only ever run
-     * against tests/mock/mock_hip.c).  Replicas share the physical GPU's CUs and LDS: no speed to be had, and resident services of two replicas
-     * compete for the same CUs (the tests give each service half the CUs: QZSTD_HIP_SERVICE_WORKERS). */
-    {
-        const char *r = getenv("QZSTD_HIP_REPLICATE_DEVICES");
-        const int k = r && *r ? atoi(r) : 1;
-        const int n0 = g_devCount;
-        for (int c = 1; c < k && c < 64; c++)
-            for (int d = 0; d < n0 && g_devCount < 64; d++) g_devMap[g_devCount++] = g_devMap[d];
-        if (n0 > 0 && g_devCount > n0) g_devReplicas = g_devCount / n0;
-    }
-    for (int d = 0; d < g_devCount; d++) (void)probe_lds_order(d, g_devMap[d]); /* now: nothing is resident yet (see probe_lds_order) */
-}
-
-static inline int phys(int device)
-{
-    std::call_once(g_devOnce, probe_devices);
-    return device >= 0 && device < g_devCount ? g_devMap[device] : -1;
-}
-
-#define QZ_SET_DEVICE(device)                                            \
-    do {                                                                 \
-        const int pd_ = phys(device);                                    \
-        if (pd_ < 0) return fail_msg("device index out of range");       \
-        QZ_CHECK(hipSetDevice(pd_), "hipSetDevice");                     \
-    } while (0)
-
-int qzstd_hip_device_count(void)
-{
-    std::call_once(g_devOnce, probe_devices);
-    return g_devCount;
-}
-
-int qzstd_hip_device_name(int device, char *buf, size_t bufLen)
-{
-    hipDeviceProp_t prop;
-    if (phys(device) < 0) return fail_msg("device index out of range");
-    QZ_CHECK(hipGetDeviceProperties(&prop, phys(device)), "hipGetDeviceProperties");
-    if (buf && bufLen) snprintf(buf, bufLen, "%s (%s, %d CUs, %zu KiB LDS/WG)", prop.name, prop.gcnArchName,
-                                prop.multiProcessorCount, prop.sharedMemPerBlock >> 10);
-    return 0;
-}
-
-void *qzstd_hip_malloc(int device, size_t bytes)
-{
-    void *p = nullptr;
-    if (phys(device) < 0 || hipSetDevice(phys(device)) != hipSuccess) return nullptr;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e != hipSuccess) { fail("hipMalloc", e); return nullptr; }
-    return p;
-}
-
-void qzstd_hip_free(int device, void *dptr)
-{
-    if (!dptr) return;
-    SvcFreeze frozen; /* hipFree waits for every stream of the device: the resident service has to leave first */
-    if (phys(device) >= 0 && hipSetDevice(phys(device)) == hipSuccess) (void)hipFree(dptr);
-}
-
-void *qzstd_hip_host_alloc(size_t bytes)
-{
-    void *p = nullptr;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped);
-    if (e != hipSuccess) { fail("hipHostMalloc", e); return nullptr; }
-    return p;
-}
-
-void *qzstd_hip_host_device_ptr(void *hptr)
-{
-    void *d = nullptr;
-    if (!hptr) return nullptr;
-    hipError_t e = hipHostGetDevicePointer(&d, hptr, 0);
-    if (e != hipSuccess) { fail("hipHostGetDevicePointer", e); return nullptr; }
-    return d;
-}
-
-void *qzstd_hip_host_alloc_coherent(size_t bytes)
-{
-    void *p = nullptr;
-    hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped | hipHostMallocCoherent);
-    if (e != hipSuccess) { fail("hipHostMalloc(coherent)", e); return nullptr; }
-    return p;
-}
-
-/* The GPU's host NUMA node: the runtime's attribute first, the PCI function's sysfs entry second */
-int qzstd_hip_device_numa_node(int device)
-{
-    const int pd = phys(device);
-    if (pd < 0) return -1;
-    int node = -1;
-    if (hipDeviceGetAttribute(&node, hipDeviceAttributeHostNumaId, pd) == hipSuccess && node >= 0) return node;
-    (void)hipGetLastError();
-    char bus[32] = "", path[96];
-    if (hipDeviceGetPCIBusId(bus, (int)sizeof(bus), pd) != hipSuccess) { (void)hipGetLastError(); return -1; }
-    for (char *c = bus; *c; c++) if (*c >= 'A' && *c <= 'F') *c = (char)(*c - 'A' + 'a'); /* sysfs spells the address in lower case */
-    snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/numa_node", bus);
-    FILE *f = fopen(path, "r");
-    if (!f) return -1;
-    if (fscanf(f, "%d", &node) != 1) node = -1;
-    fclose(f);
-    return node;
-}
-
-/* Pinned host memory on a NUMA node: hipHostMallocNumaUser makes the runtime allocate under the CALLING THREAD's memory policy, so
- * the policy is set to "prefer `node`" around the call (raw system calls: no libnuma in the image) and put back afterwards.  A
- * process that may not set a policy (seccomp, containers without CAP_SYS_NICE for other nodes) gets the memory anyway, unplaced. */
-void *qzstd_hip_host_alloc_on_node(size_t bytes, int node, int coherent)
-{
-    const unsigned flags = hipHostMallocPortable | hipHostMallocMapped | (coherent ? hipHostMallocCoherent : 0u);
-    void *p = nullptr;
-    if (node >= 0 && node < 1024) {
-        unsigned long want[16] = { 0 }, old[16] = { 0 };
-        int oldMode = 0;
-        want[node / (8 * sizeof(unsigned long))] = 1ul << (node % (8 * sizeof(unsigned long)));
-        const bool got = syscall(SYS_get_mempolicy, &oldMode, old, (unsigned long)(8 * sizeof(old)), nullptr, 0ul) == 0;
-        if (got && syscall(SYS_set_mempolicy, 1 /* MPOL_PREFERRED */, want, (unsigned long)(8 * sizeof(want))) == 0) {
-            const hipError_t e = hipHostMalloc(&p, bytes, flags | hipHostMallocNumaUser);
-            (void)syscall(SYS_set_mempolicy, oldMode, oldMode == 0 /* MPOL_DEFAULT takes no mask */ ? nullptr : old,
-                          oldMode == 0 ? 0ul : (unsigned long)(8 * sizeof(old)));
-            if (e == hipSuccess) return p;
-            (void)hipGetLastError();
-            p = nullptr;
-        }
-    }
-    const hipError_t e = hipHostMalloc(&p, bytes, flags);
-    if (e != hipSuccess) { fail(coherent ? "hipHostMalloc(coherent)" : "hipHostMalloc", e); return nullptr; }
-    return p;
-}
-
-int qzstd_hip_host_node_of(const void *hptr)
-{
-    int node = -1;
-    if (!hptr) return -1;
-    if (syscall(SYS_get_mempolicy, &node, nullptr, 0ul, hptr, 3ul /* MPOL_F_NODE | MPOL_F_ADDR */) != 0) return -1;
-    return node;
-}
-
-void qzstd_hip_host_free(void *hptr)
-{
-    if (!hptr) return;
-    SvcFreeze frozen; /* hipHostFree waits for the device's streams too */
-    (void)hipHostFree(hptr);
-}
-
-void *qzstd_hip_stream_create(int device)
-{
-    hipStream_t s = nullptr;
-    if (phys(device) < 0 || hipSetDevice(phys(device)) != hipSuccess) return nullptr;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e != hipSuccess) { fail("hipStreamCreate", e); return nullptr; }
-    return (void *)s;
-}
-
-void qzstd_hip_stream_destroy(int device, void *stream)
-{
-    if (stream && phys(device) >= 0 && hipSetDevice(phys(device)) == hipSuccess) (void)hipStreamDestroy((hipStream_t)stream);
-}
-
-int qzstd_hip_stream_sync(int device, void *stream)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipStreamSynchronize((hipStream_t)stream), "hipStreamSynchronize");
-    return 0;
-}
-
-int qzstd_hip_stream_query(int device, void *stream)
-{
-    QZ_SET_DEVICE(device);
-    hipError_t e = hipStreamQuery((hipStream_t)stream);
-    if (e == hipSuccess) return 0;
-    if (e == hipErrorNotReady) return 1;
-    return fail("hipStreamQuery", e);
-}
-
-int qzstd_hip_stream_wait(int device, void *stream, unsigned timeoutMs)
-{
-    QZ_SET_DEVICE(device);
-    /* poll instead of hipStreamSynchronize: a wedged kernel must not take the calling thread with it.  Busy polls for
-     * the first QZSTD_HIP_SPIN_US microseconds (default 50), then naps between polls so
-     * that a waiting caller does not burn a core other callers could entropy-code on (QZSTD_HIP_NAP_US, default 20) */
-    static const long long spinUs = [] { const char *v = getenv("QZSTD_HIP_SPIN_US"); return v ? atoll(v) : 50ll; }();
-    static const long napNs = [] { const char *v = getenv("QZSTD_HIP_NAP_US"); return (v ? atol(v) : 20l) * 1000l; }();
-    struct timespec t0, t;
-    clock_gettime(CLOCK_MONOTONIC, &t0);
-    for (;;) {
-        const hipError_t e = hipStreamQuery((hipStream_t)stream);
-        if (e == hipSuccess) return 0;
-        if (e != hipErrorNotReady) return fail("hipStreamQuery", e);
-        clock_gettime(CLOCK_MONOTONIC, &t);
-        const long long us = (long long)(t.tv_sec - t0.tv_sec) * 1000000ll + (t.tv_nsec - t0.tv_nsec) / 1000;
-        if (us >= (long long)timeoutMs * 1000ll) {
-            snprintf(g_err, sizeof(g_err), "stream still busy after %u ms", timeoutMs);
-            return 1;
-        }
-        if (us < spinUs) continue;
-        if (napNs <= 0) sched_yield();
-        else { const struct timespec nap = { 0, us < 20000 ? napNs : 200000l }; nanosleep(&nap, nullptr); }
-    }
-}
-
-int qzstd_hip_memcpy_h2d(int device, void *stream, void *dst, const void *src, size_t bytes)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D");
-    return 0;
-}
-
-/* pinned host memory -> device memory by a KERNEL on the stream: 16 bytes per lane and step, every wave streaming its own 16 KiB stripes.
- * For the staging copies of announcements (host/qatseqprod.c, qzLaunchPart): hipMemcpyAsync holds the calling thread for 0.8-1.1 ms per 4 MiB
- * when 16 threads announce (the runtime's copy path and its locks); a launch costs 10-30 us, and the copy then runs at the bus's rate in front
- * of the match-finder on the same stream.  src_dev = the DEVICE address of the pinned buffer (qzstd_hip_host_device_ptr); bytes a multiple
- * of 16, both addresses 16-byte aligned. */
-}
-namespace {
-__global__ __launch_bounds__(256) void qzstd_copy_in_kernel(uint4 *__restrict__ dst, const uint4 *__restrict__ src, uint32_t n16)
-{
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n16; i += gridDim.x * 256u) dst[i] = src[i];
-}
-}
 extern "C" {
-int qzstd_hip_copy_in(int device, void *stream, void *dst, const void *src_dev, size_t bytes)
-{
-    if (bytes == 0) return 0;
-    if (!dst || !src_dev || (bytes & 15u) || ((uintptr_t)dst & 15u) || ((uintptr_t)src_dev & 15u) || bytes > ((size_t)1 << 34))
-        return fail_msg("qzstd_hip_copy_in: null, unaligned or oversized");
-    QZ_SET_DEVICE(device);
-    const uint32_t n16 = (uint32_t)(bytes >> 4);
-    uint32_t groups = (n16 + 1023u) / 1024u; /* four steps per lane */
-    if (groups > 1024u) groups = 1024u;
-    hipLaunchKernelGGL(qzstd_copy_in_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, static_cast<uint4 *>(dst), static_cast<const uint4 *>(src_dev), n16);
-    QZ_CHECK(hipGetLastError(), "launch qzstd_copy_in_kernel");
-    return 0;
-}
-
-int qzstd_hip_memcpy_d2h(int device, void *stream, void *dst, const void *src, size_t bytes)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream), "hipMemcpyAsync D2H");
-    return 0;
-}
-
-int qzstd_hip_memset(int device, void *stream, void *dst, int value, size_t bytes)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemsetAsync(dst, value, bytes, (hipStream_t)stream), "hipMemsetAsync");
-    return 0;
-}
-
-int qzstd_hip_memcpy2d_d2h(int device, void *stream, void *dst, size_t dpitch, const void *src, size_t spitch,
-                           size_t width, size_t height)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToHost, (hipStream_t)stream),
-             "hipMemcpy2DAsync D2H");
-    return 0;
-}
 
 int qzstd_hip_find_sequences(int device, void *stream, int level, const void *d_src,
                              const qzstd_hip_block_t *d_blocks, uint32_t nBlocks, uint32_t maxBlockLen,
@@ -2946,16 +2652,6 @@ int qzstd_hip_find_sequences(int device, void *stream, int level, const void *d_
         big = big || sv.wide;
         if (sv.hs && __atomic_load_n(&sv.hs->state, __ATOMIC_ACQUIRE) != 0u && lds + sv.lds > kLdsPerCu) (void)svc_stop_locked(sv, 2000);
     }
-    /* [near][long][rep][chain/turns: 0 none, 1 turns, 2 chain + turns] */
-#define QZ_K(L, R, C, T, N) reinterpret_cast<const void *>(qzstd_find_sequences_kernel<L, R, C, T, N>)
-    static const void *const variants[2][2][2][3] = {
-        { { { QZ_K(false, false, false, false, false), QZ_K(false, false, false, true, false), QZ_K(false, false, true, true, false) },
-            { QZ_K(false, true, false, false, false), QZ_K(false, true, false, true, false), QZ_K(false, true, true, true, false) } },
-          { { QZ_K(true, false, false, false, false), nullptr, nullptr }, { QZ_K(true, true, false, false, false), nullptr, nullptr } } },
-        { { { QZ_K(false, false, false, false, true), QZ_K(false, false, false, true, true), QZ_K(false, false, true, true, true) },
-            { QZ_K(false, true, false, false, true), QZ_K(false, true, false, true, true), QZ_K(false, true, true, true, true) } },
-          { { QZ_K(true, false, false, false, true), nullptr, nullptr }, { QZ_K(true, true, false, false, true), nullptr, nullptr } } } };
-#undef QZ_K
     /* the LDS a variant may ask for is a per-function, per-device attribute (process-wide, not per thread): raise it
      * once per device to the most any level needs and never lower it */
     {
@@ -2969,11 +2665,9 @@ int qzstd_hip_find_sequences(int device, void *stream, int level, const void *d_
                 const size_t b = qzstd_hip_lds_bytes(l, QZSTD_HIP_BLOCK_MAX);
                 if (b > most) most = b;
             }
-            for (int v = 0; v < 24; v++) {
-                const void *f = variants[v / 12][(v / 6) % 2][(v / 3) % 2][v % 3];
-                if (f) QZ_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most),
-                                "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-            }
+            for (const void *f : kLaunchKernels)
+                QZ_CHECK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)most),
+                         "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
             attrDone[device] = true;
         }
     }
@@ -3012,10 +2706,8 @@ int qzstd_hip_find_sequences(int device, void *stream, int level, const void *d_
 #endif
     const dim3 grid(nBlocks), wg(kThreads);
     /* every block of the launch fits the ring: the kernels without a device-memory side of the compares (NEAR) */
-    const int nearK = maxBlockLen <= kRing ? 1 : 0;
-    const void *kernel = variants[nearK][a.prof.longSize ? 1 : 0][a.prof.repWin ? 1 : 0][a.prof.chainDepth ? 2 : (a.prof.subTileLog ? 1 : 0)];
+    const void *kernel = kLaunchKernels[variant_index(a.prof, maxBlockLen <= kRing)];
     void *kargs[1] = { &a };
-    if (!kernel) return fail_msg("qzstd_hip_find_sequences: unsupported profile (no kernel variant)");
     /* below the chain levels the kernels take the slot as a shift of the hash and mix at most three bytes behind the fourth through a 24-bit product */
     if (!a.prof.chainDepth && ((a.prof.tableSize & (a.prof.tableSize - 1u)) != 0u || (a.prof.longSize & (a.prof.longSize - 1u)) != 0u || a.prof.hashBytes > 7u))
         return fail_msg("qzstd_hip_find_sequences: unsupported profile (tables below the chain levels are powers of two, hashBytes <= 7)");
@@ -3044,11 +2736,7 @@ int qzstd_hip_occupancy(int device, int level)
     if (qzstd_hip_profile_for_level(level, QZSTD_HIP_BLOCK_MAX, &p)) return fail_msg("qzstd_hip_occupancy: bad level");
     const size_t lds = qzstd_hip_lds_bytes(level, QZSTD_HIP_BLOCK_MAX);
     QZ_SET_DEVICE(device);
-    const void *k;
-    if (p.chainDepth) k = p.repWin ? reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, true, true, true, false>) : reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, false, true, true, false>);
-    else if (p.longSize) k = p.repWin ? reinterpret_cast<const void *>(qzstd_find_sequences_kernel<true, true, false, false, false>) : reinterpret_cast<const void *>(qzstd_find_sequences_kernel<true, false, false, false, false>);
-    else if (p.subTileLog) k = p.repWin ? reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, true, false, true, false>) : reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, false, false, true, false>);
-    else k = p.repWin ? reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, true, false, false, false>) : reinterpret_cast<const void *>(qzstd_find_sequences_kernel<false, false, false, false, false>);
+    const void *k = kLaunchKernels[variant_index(p, false)]; /* answers for the non-NEAR kernel, whatever block lengths a launch would have */
     (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     int n = 0;
     QZ_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k, kThreads, lds), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
@@ -3060,16 +2748,8 @@ int qzstd_hip_occupancy(int device, int level)
 /* ---------------------------------------------------------------- the resident service (host side) ---------- */
 namespace {
 
-const void *svc_worker_variant(const qzstd_hip_profile_t &p)
-{
-#define QZ_W(L, R, C, T) reinterpret_cast<const void *>(qzstd_service_worker<L, R, C, T, false>)
-    if (p.chainDepth) return p.repWin ? QZ_W(false, true, true, true) : QZ_W(false, false, true, true);
-    if (p.longSize) return p.repWin ? QZ_W(true, true, false, false) : QZ_W(true, false, false, false); /* levels 3-4: a worker fills its CU's LDS
-                                                                                                         * (see Service::wide) */
-    if (p.repWin) return p.subTileLog ? QZ_W(false, true, false, true) : QZ_W(false, true, false, false);
-    return p.subTileLog ? QZ_W(false, false, false, true) : QZ_W(false, false, false, false);
-#undef QZ_W
-}
+/* (levels 3-4: a worker fills its CU's LDS, see Service::wide) */
+const void *svc_worker_variant(const qzstd_hip_profile_t &p) { return kWorkers[variant_index(p, false)]; }
 
 /* index of a level (optionally | QZSTD_HIP_LEVEL_REPCODES) in the table of profiles: the host side of svc_profile_index */
 int svc_level_index(int level)
@@ -3387,435 +3067,3 @@ int qzstd_hip_service_debug(int device, unsigned long out[8])
 }
 
 } /* extern "C" */
-
-/* ---------------------------------------------------------------- device-resident input: compaction ---------- */
-/*
- * qzstd_hip_compact (include/qzstd_hip_device.h): a launch's ZSTD_Sequence entries (16 B each, in device memory) and the literal bytes they
- * name, packed densely into one arena — 8-byte entries (QZSTD_HIP_PACK, tag 0) and the literals back to back — so that one D2H copy of
- * about 0.64 B per input byte (level 1, text) gives libzstd everything ZSTD_compressSequencesAndLiterals needs.  Three kernels:
- *   count  one workgroup per block: checks the block's entries and sums their literal bytes -> header {count, litBytes}
- *   scan   one workgroup: exclusive prefix sums of entries and literal bytes over the blocks, the arena's capacity check
- *   emit   one workgroup per block: packs the entries and copies the literal runs, a chunk of kCompactT entries at a time (the
- *          destination and source offsets of the runs are a scan of litLength and litLength + matchLength over the chunk in LDS)
- * A block is emitted only when its entries cover exactly [0, srcLen): every literal read lies inside [srcOff, srcOff + srcLen).
- */
-namespace {
-constexpr uint32_t kCompactT = 512u; /* threads per workgroup of the count and emit kernels, entries per chunk of the emit kernel */
-
-/* block-wide inclusive scan of one 64-bit value per thread (kCompactT threads); `red` holds kCompactT / 64 partials */
-__device__ inline unsigned long long compact_scan(unsigned long long v, unsigned long long *red, unsigned long long *total)
-{
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    for (uint32_t d = 1; d < 64u; d <<= 1) {
-        const unsigned long long o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    if (lane == 63u) red[wave] = v;
-    __syncthreads();
-    unsigned long long before = 0, all = 0;
-    for (uint32_t w = 0; w < kCompactT / 64u; w++) {
-        const unsigned long long r = red[w];
-        if (w < wave) before += r;
-        all += r;
-    }
-    __syncthreads(); /* red is reused by the next call */
-    *total = all;
-    return v + before;
-}
-
-__global__ __launch_bounds__(kCompactT) void qzstd_compact_count_kernel(const qzstd_hip_block_t *__restrict__ blocks, const uint4 *__restrict__ seqs,
-                                                                        const uint32_t *__restrict__ nseq, qzstd_hip_compact_hdr_t *__restrict__ hdr)
-{
-    __shared__ unsigned long long red[kCompactT / 64u];
-    const qzstd_hip_block_t bk = blocks[blockIdx.x];
-    const uint32_t count = nseq[blockIdx.x];
-    bool ok = count != QZSTD_HIP_NSEQ_ERROR && count >= 1u && count <= bk.seqCap && (bk.mark & QZSTD_HIP_MARK_COMPACT) == 0u;
-    unsigned long long lit = 0, cover = 0, bad = 0;
-    if (ok) {
-        const uint4 *q = seqs + bk.seqOff;
-        for (uint32_t i = threadIdx.x; i < count; i += kCompactT) {
-            const uint4 s = q[i]; /* x offset, y litLength, z matchLength */
-            lit += s.y;
-            cover += (unsigned long long)s.y + s.z;
-            /* the packed fields: offset 17 bits, litLength 18, matchLength 17; the last entry is the delimiter */
-            if (s.x >= (1u << 17) || s.y > (1u << 17) || s.z >= (1u << 17) || (i + 1u == count && (s.x | s.z) != 0u)) bad++;
-        }
-    }
-    unsigned long long t;
-    (void)compact_scan(lit, red, &lit);
-    (void)compact_scan(cover, red, &cover);
-    (void)compact_scan(bad, red, &t);
-    if (threadIdx.x == 0) {
-        ok = ok && t == 0 && cover == bk.srcLen;
-        hdr[blockIdx.x].count = ok ? count : QZSTD_HIP_NSEQ_ERROR;
-        hdr[blockIdx.x].litBytes = ok ? (uint32_t)lit : 0u;
-    }
-}
-
-/* work: [0, 8n) first entry of each block, [8n, 16n) first literal byte of each block, then {entries, literal bytes} in total */
-__global__ __launch_bounds__(kCompactT) void qzstd_compact_scan_kernel(qzstd_hip_compact_hdr_t *__restrict__ hdr, uint32_t n,
-                                                                       unsigned long long *__restrict__ work, unsigned long long cap)
-{
-    __shared__ unsigned long long red[kCompactT / 64u];
-    unsigned long long *seqBase = work, *litBase = work + n, *totals = work + 2u * (size_t)n;
-    unsigned long long carryAll = 0, carrySeq = 0, carryLit = 0;
-    for (uint32_t c = 0; c < n; c += kCompactT) {
-        const uint32_t b = c + threadIdx.x;
-        qzstd_hip_compact_hdr_t h = { QZSTD_HIP_NSEQ_ERROR, 0u };
-        if (b < n) h = hdr[b];
-        const unsigned long long cnt = h.count == QZSTD_HIP_NSEQ_ERROR ? 0ull : h.count;
-        unsigned long long tAll, tSeq, tLit;
-        /* the arena's bytes up to the end of this block (entries and literals both counted): the blocks that do not fit are a suffix */
-        const unsigned long long endAll = carryAll + compact_scan(8ull * cnt + h.litBytes, red, &tAll);
-        const bool fits = endAll <= cap;
-        const unsigned long long keepCnt = fits ? cnt : 0ull, keepLit = fits ? h.litBytes : 0ull;
-        const unsigned long long inSeq = compact_scan(keepCnt, red, &tSeq), inLit = compact_scan(keepLit, red, &tLit);
-        if (b < n) {
-            seqBase[b] = carrySeq + inSeq - keepCnt;
-            litBase[b] = carryLit + inLit - keepLit;
-            if (!fits && h.count != QZSTD_HIP_NSEQ_ERROR) { h.count = QZSTD_HIP_NSEQ_ERROR; h.litBytes = 0u; hdr[b] = h; }
-        }
-        carryAll += tAll;
-        carrySeq += tSeq;
-        carryLit += tLit;
-    }
-    if (threadIdx.x == 0) { totals[0] = carrySeq; totals[1] = carryLit; }
-}
-
-__global__ __launch_bounds__(kCompactT) void qzstd_compact_emit_kernel(const uint8_t *__restrict__ src, const qzstd_hip_block_t *__restrict__ blocks,
-                                                                       const uint4 *__restrict__ seqs, const qzstd_hip_compact_hdr_t *__restrict__ hdr,
-                                                                       const unsigned long long *__restrict__ work, uint32_t n, uint8_t *__restrict__ arena)
-{
-    __shared__ unsigned long long red[kCompactT / 64u];
-    __shared__ uint32_t dStart[kCompactT + 1u], sStart[kCompactT];
-    const qzstd_hip_compact_hdr_t h = hdr[blockIdx.x];
-    if (h.count == QZSTD_HIP_NSEQ_ERROR) return;
-    const qzstd_hip_block_t bk = blocks[blockIdx.x];
-    const unsigned long long seqBase = work[blockIdx.x], litBase = work[n + blockIdx.x], totalSeq = work[2u * (size_t)n];
-    const size_t entriesOff = QZSTD_HIP_COMPACT_ENTRIES_OFF(n);
-    unsigned long long *outSeq = reinterpret_cast<unsigned long long *>(arena + entriesOff) + seqBase;
-    uint8_t *outLit = arena + entriesOff + 8ull * totalSeq + litBase;
-    const uint8_t *in = src + bk.srcOff;
-    const uint4 *q = seqs + bk.seqOff;
-    uint32_t dCarry = 0, sCarry = 0; /* literal bytes and covered bytes of the chunks before */
-    for (uint32_t c = 0; c < h.count; c += kCompactT) {
-        const uint32_t i = c + threadIdx.x;
-        uint4 s = make_uint4(0u, 0u, 0u, 0u);
-        if (i < h.count) {
-            s = q[i];
-            outSeq[i] = QZSTD_HIP_PACK(s.x, s.y, s.z, 0u);
-        }
-        unsigned long long tLit, tCov;
-        const uint32_t dEnd = (uint32_t)compact_scan(s.y, red, &tLit), sEnd = (uint32_t)compact_scan((unsigned long long)s.y + s.z, red, &tCov);
-        dStart[threadIdx.x] = dEnd - s.y;
-        sStart[threadIdx.x] = sCarry + sEnd - s.y - s.z;
-        if (threadIdx.x == 0) dStart[kCompactT] = (uint32_t)tLit;
-        __syncthreads();
-        /* the chunk's literal bytes [0, tLit): four consecutive bytes per lane, the run found by a binary search over dStart.  Byte stores:
-         * the runs start anywhere in the source and the destination.  Measured at level 1 (ms per GiB, the emit kernel): bytes 2.17 - 2.39; aligned
-         * dword stores of gathered bytes 2.50; aligned 16-byte stores 4.65 — a chunk's ~1.7 KiB of literals then keeps a quarter of the lanes
-         * busy, each with sixteen dependent byte loads.  Wider stores do not make it faster */
-        const uint32_t lits = (uint32_t)tLit;
-        for (uint32_t j = threadIdx.x * 4u; j < lits; j += kCompactT * 4u) {
-            uint32_t lo = 0, hi = kCompactT; /* the last run e with dStart[e] <= j */
-            while (hi - lo > 1u) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if (dStart[mid] <= j) lo = mid; else hi = mid;
-            }
-            uint32_t e = lo;
-            for (uint32_t k = 0; k < 4u && j + k < lits; k++) {
-                while (j + k >= dStart[e + 1u]) e++;
-                outLit[dCarry + j + k] = in[sStart[e] + (j + k - dStart[e])];
-            }
-        }
-        dCarry += lits;
-        sCarry += (uint32_t)tCov;
-        __syncthreads(); /* dStart / sStart are rewritten by the next chunk */
-    }
-}
-} // namespace
-
-extern "C" {
-
-int qzstd_hip_pointer_device(const void *p)
-{
-    if (!p) return -1;
-    const int n = qzstd_hip_device_count();
-    if (n <= 0) return -1;
-    hipPointerAttribute_t a;
-    memset(&a, 0, sizeof(a));
-    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return -1; } /* memory the runtime does not know: host */
-    if (a.type != hipMemoryTypeDevice || a.isManaged) return -1;
-    for (int d = 0; d < n; d++)
-        if (g_devMap[d] == a.device) return d;
-    return -1;
-}
-
-void *qzstd_hip_event_create(int device)
-{
-    hipEvent_t e = nullptr;
-    if (phys(device) < 0 || hipSetDevice(phys(device)) != hipSuccess) return nullptr;
-    const hipError_t r = hipEventCreateWithFlags(&e, hipEventDisableTiming);
-    if (r != hipSuccess) { fail("hipEventCreate", r); return nullptr; }
-    return (void *)e;
-}
-
-void qzstd_hip_event_destroy(int device, void *event)
-{
-    if (event && phys(device) >= 0 && hipSetDevice(phys(device)) == hipSuccess) (void)hipEventDestroy((hipEvent_t)event);
-}
-
-int qzstd_hip_event_record(int device, void *event, void *stream)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipEventRecord((hipEvent_t)event, (hipStream_t)stream), "hipEventRecord");
-    return 0;
-}
-
-int qzstd_hip_stream_wait_event(int device, void *stream, void *event)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)event, 0), "hipStreamWaitEvent");
-    return 0;
-}
-
-int qzstd_hip_memcpy2d_d2d(int device, void *stream, void *dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t height)
-{
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpy2DAsync(dst, dpitch, src, spitch, width, height, hipMemcpyDeviceToDevice, (hipStream_t)stream), "hipMemcpy2DAsync D2D");
-    return 0;
-}
-
-size_t qzstd_hip_compact_workspace_bytes(uint32_t nBlocks) { return (size_t)nBlocks * 16u + 16u; }
-
-int qzstd_hip_compact(int device, void *stream, const void *d_src, const qzstd_hip_block_t *d_blocks, uint32_t nBlocks,
-                      const void *d_seqs, const uint32_t *d_nseq, void *d_arena, size_t arenaBytes, void *d_work, size_t workBytes)
-{
-    if (nBlocks == 0) return 0;
-    if (!d_src || !d_blocks || !d_seqs || !d_nseq || !d_arena || !d_work) return fail_msg("qzstd_hip_compact: null pointer");
-    if (workBytes < qzstd_hip_compact_workspace_bytes(nBlocks) || ((uintptr_t)d_work & 7u) || ((uintptr_t)d_arena & 15u))
-        return fail_msg("qzstd_hip_compact: workspace too small, or workspace / arena not aligned");
-    if (arenaBytes < QZSTD_HIP_COMPACT_ENTRIES_OFF(nBlocks)) return fail_msg("qzstd_hip_compact: arena smaller than its headers");
-    QZ_SET_DEVICE(device);
-    const hipStream_t s = (hipStream_t)stream;
-    auto *hdr = static_cast<qzstd_hip_compact_hdr_t *>(d_arena);
-    auto *work = static_cast<unsigned long long *>(d_work);
-    const auto *seqs = static_cast<const uint4 *>(d_seqs);
-    hipLaunchKernelGGL(qzstd_compact_count_kernel, dim3(nBlocks), dim3(kCompactT), 0, s, d_blocks, seqs, d_nseq, hdr);
-    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_count_kernel");
-    hipLaunchKernelGGL(qzstd_compact_scan_kernel, dim3(1), dim3(kCompactT), 0, s, hdr, nBlocks, work,
-                       (unsigned long long)(arenaBytes - QZSTD_HIP_COMPACT_ENTRIES_OFF(nBlocks)));
-    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_scan_kernel");
-    hipLaunchKernelGGL(qzstd_compact_emit_kernel, dim3(nBlocks), dim3(kCompactT), 0, s, static_cast<const uint8_t *>(d_src), d_blocks, seqs, hdr,
-                       work, nBlocks, static_cast<uint8_t *>(d_arena));
-    QZ_CHECK(hipGetLastError(), "launch qzstd_compact_emit_kernel");
-    return 0;
-}
-
-} /* extern "C" */
-
-/* ---------------------------------------------------------------- gather (include/qzstd_hip_device.h) -- */
-namespace {
-constexpr uint32_t kGatherT = 256u;               /* threads per workgroup */
-constexpr uint32_t kGatherWords = 4u * kGatherT;  /* 16-byte words of the stage per workgroup: 16 KiB */
-
-/* the last row of [lo, hi] whose first word is at or before word w (lo when there is none) */
-__device__ inline uint32_t gather_row_of(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t lo, uint32_t hi, uint32_t w)
-{
-    while (lo < hi) {
-        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-        if ((uint32_t)(rows[mid].dstOff >> 4) <= w) lo = mid; else hi = mid - 1u;
-    }
-    return lo;
-}
-
-/* one workgroup per 16 KiB of the stage between the first row's start and the last row's end; a lane takes every 256th word.  The rows that
- * reach into the workgroup's piece are found once (two searches over all rows), a word's own row by a search among those: no step at all
- * inside a long row, at most ten where 1024 one-word rows share the piece */
-__global__ __launch_bounds__(kGatherT) void qzstd_gather_kernel(const qzstd_hip_gather_row_t *__restrict__ rows, uint32_t nRows, uint32_t firstWord,
-                                                                uint32_t endWord, uint4 *__restrict__ stage)
-{
-    __shared__ uint32_t span[2];
-    const uint32_t w0 = firstWord + blockIdx.x * kGatherWords;
-    const uint32_t wEnd = endWord - w0 < kGatherWords ? endWord : w0 + kGatherWords;
-    if (threadIdx.x == 0) {
-        span[0] = gather_row_of(rows, 0u, nRows - 1u, w0);
-        span[1] = gather_row_of(rows, span[0], nRows - 1u, wEnd - 1u);
-    }
-    __syncthreads();
-    const uint32_t rLo = span[0], rHi = span[1];
-    for (uint32_t w = w0 + threadIdx.x; w < wEnd; w += kGatherT) {
-        const qzstd_hip_gather_row_t row = rows[gather_row_of(rows, rLo, rHi, w)];
-        const uint64_t o = ((uint64_t)w << 4) - row.dstOff; /* the word's first byte in its row (wraps to a huge value in front of row 0) */
-        if (o >= (uint64_t)row.len + row.pad) continue;     /* between two rows: not ours to write */
-        uint64_t o0 = 0, o1 = 0;
-        if (o < row.len) {
-            const uint64_t a = row.src + o;
-            const uint32_t sh = (uint32_t)a & 15u;
-            const uint32_t valid = row.len - o < 16u ? (uint32_t)(row.len - o) : 16u; /* payload bytes of this word */
-            const uint4 *p = reinterpret_cast<const uint4 *>(a - sh);
-            /* the aligned word that holds byte a, and the next one only when payload of this word lies in it */
-            const uint4 l = p[0];
-            uint4 h = make_uint4(0u, 0u, 0u, 0u);
-            if (sh + valid > 16u) h = p[1];
-            const uint64_t l0 = l.x | (uint64_t)l.y << 32, l1 = l.z | (uint64_t)l.w << 32, h0 = h.x | (uint64_t)h.y << 32, h1 = h.z | (uint64_t)h.w << 32;
-            /* {h1 h0 l1 l0} >> 8 * sh: whole 64-bit halves first, then the bytes */
-            const bool half = (sh & 8u) != 0u;
-            const uint32_t bits = (sh & 7u) * 8u;
-            const uint64_t a0 = half ? l1 : l0, a1 = half ? h0 : l1, a2 = half ? h1 : h0;
-            o0 = bits ? (a0 >> bits) | (a1 << (64u - bits)) : a0;
-            o1 = bits ? (a1 >> bits) | (a2 << (64u - bits)) : a1;
-            if (valid < 16u) { /* the row's last word: zero behind the payload (what the shift brought in lies inside the aligned words read) */
-                o1 = valid > 8u ? o1 & ((1ull << ((valid - 8u) * 8u)) - 1ull) : 0ull;
-                if (valid < 8u) o0 &= (1ull << (valid * 8u)) - 1ull;
-            }
-        }
-        stage[w] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
-    }
-}
-} // namespace
-
-extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
-                                void *d_stage, size_t stageBytes)
-{
-    if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_gather: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_gather_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_gather: dstOff or len + pad not a multiple of 16");
-        if (r.len && !r.src) return fail_msg("qzstd_hip_gather: null source");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_gather: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_gather: a row ends past stageBytes");
-        end = r.dstOff + ext;
-    }
-    /* 16-byte words in 32 bits, with room for a workgroup's last step */
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_gather: stage span too large");
-    const uint32_t firstWord = (uint32_t)(rows[0].dstOff >> 4), endWord = (uint32_t)(end >> 4);
-    if (endWord == firstWord) return 0; /* nothing but empty rows */
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (gather rows)");
-    const uint32_t groups = (endWord - firstWord + kGatherWords - 1u) / kGatherWords;
-    hipLaunchKernelGGL(qzstd_gather_kernel, dim3(groups), dim3(kGatherT), 0, (hipStream_t)stream, d_rows, nRows, firstWord, endWord,
-                       static_cast<uint4 *>(d_stage));
-    QZ_CHECK(hipGetLastError(), "launch qzstd_gather_kernel");
-    return 0;
-}
-
-/* ---------------------------------------------------------------- content checksum (include/qzstd_hip_device.h) -- */
-namespace {
-constexpr uint32_t kHashRows = 16u;                 /* rows per wave: four lanes each, one per XXH64 accumulator */
-constexpr uint32_t kHashTile = QZSTD_HIP_XXH64_TILE; /* bytes of a row per fetch: one whole-wave 16-byte load */
-constexpr uint32_t kHashPitch = kHashTile + 32u;    /* a row's tile in LDS: 32 bytes of padding put the eight rows of a 32-lane group on
-                                                       the 64 banks once (8 B per lane, 32 B per row and stripe) */
-constexpr uint64_t kXP1 = 0x9E3779B185EBCA87ull, kXP2 = 0xC2B2AE3D27D4EB4Full, kXP3 = 0x165667B19E3779F9ull, kXP4 = 0x85EBCA77C2B2AE63ull,
-                   kXP5 = 0x27D4EB2F165667C5ull;
-
-typedef uint32_t hash_word_t __attribute__((ext_vector_type(4))); /* one aligned 16-byte word */
-
-__device__ inline uint64_t xxh_rotl(uint64_t v, uint32_t r) { return (v << r) | (v >> (64u - r)); }
-__device__ inline uint64_t xxh_round(uint64_t acc, uint64_t in) { return xxh_rotl(acc + in * kXP2, 31u) * kXP1; }
-__device__ inline uint64_t xxh_merge(uint64_t h, uint64_t v) { return (h ^ xxh_round(0ull, v)) * kXP1 + kXP4; }
-
-/* One wave per workgroup, rows [16 * blockIdx.x, + 16).  Per step every row's next 1 KiB tile is fetched with one 16-byte load per lane
- * (the words that overlap the row only) into registers while the tile before it, in LDS, is consumed: lane 4 r + a runs accumulator a
- * of row r over the tile's 32-byte stripes.  The multiply chain (two 64-bit multiplies per 8 bytes and lane) sets the pace; the fetch of
- * the next tile has a whole tile's chain to arrive.  A row ends in the step that holds byte (len & ~31): its first lane collects the
- * four accumulators, walks the tail (8-, 4- and 1-byte steps over bytes below len only) and stores the hash.  The loop runs to the longest
- * row of the wave; lanes of rows that are done idle. */
-__global__ __launch_bounds__(64) void qzstd_xxh64_kernel(const uint8_t *__restrict__ base, const qzstd_hip_hash_row_t *__restrict__ rows,
-                                                         uint32_t nRows, unsigned long long *__restrict__ out)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t tile[kHashRows * kHashPitch];
-    const uint32_t lane = threadIdx.x, r = lane >> 2, a = lane & 3u;
-    const uint32_t row0 = blockIdx.x * kHashRows;
-    /* the wave's rows, by uniform addresses: their offsets and 16-byte word counts are the same in every lane (scalar registers) */
-#define QZ_HASH_EACH_ROW(X, t) X(0, t) X(1, t) X(2, t) X(3, t) X(4, t) X(5, t) X(6, t) X(7, t) X(8, t) X(9, t) X(10, t) X(11, t) X(12, t) X(13, t) X(14, t) X(15, t)
-#define QZ_HASH_ROW(j, t)                                                                   \
-    const uint64_t off##j = row0 + j < nRows ? rows[row0 + j].srcOff : 0ull;               \
-    const uint64_t words##j = row0 + j < nRows ? (rows[row0 + j].len + 15u) >> 4 : 0ull;   \
-    hash_word_t next##j = { 0u, 0u, 0u, 0u };                                              \
-    nTiles = (words##j >> 6) + 1u > nTiles ? (words##j >> 6) + 1u : nTiles;
-    uint64_t nTiles = 0; /* steps of the wave: past the longest row's tail (a row of k whole tiles ends in step k, which fetches nothing) */
-    QZ_HASH_EACH_ROW(QZ_HASH_ROW, 0)
-    const uint64_t len = row0 + r < nRows ? rows[row0 + r].len : 0ull;
-    const uint64_t endTile = len / kHashTile; /* the tile that holds the row's tail; every stripe of the row lies at or before it */
-    uint64_t acc = a == 0u ? kXP1 + kXP2 : (a == 1u ? kXP2 : (a == 2u ? 0ull : 0ull - kXP1));
-    uint64_t stripesLeft = len >> 5;
-    /* tile t of row j: word t * 64 + lane of the row, when the row has it.  Sixteen named registers, not an array: the fetches must stay
-     * in flight in VGPRs across the chain below */
-#define QZ_HASH_FETCH1(j, t) \
-    if ((t) * (kHashTile / 16u) + lane < words##j) next##j = reinterpret_cast<const hash_word_t *>(base + off##j)[(t) * (kHashTile / 16u) + lane];
-#define QZ_HASH_STAGE1(j, t) \
-    if ((t) * (kHashTile / 16u) + lane < words##j) *reinterpret_cast<hash_word_t *>(&tile[j * kHashPitch + lane * 16u]) = next##j;
-#define QZ_HASH_FETCH(t) QZ_HASH_EACH_ROW(QZ_HASH_FETCH1, t)
-#define QZ_HASH_STAGE(t) QZ_HASH_EACH_ROW(QZ_HASH_STAGE1, t)
-    QZ_HASH_FETCH(0ull)
-    QZ_HASH_STAGE(0ull)
-    __syncthreads();
-    for (uint64_t t = 0; t < nTiles; t++) {
-        const bool more = t + 1u < nTiles;
-        if (more) { QZ_HASH_FETCH(t + 1u) }
-        const uint8_t *mine = &tile[r * kHashPitch];
-        const uint32_t n = stripesLeft < kHashTile / 32u ? (uint32_t)stripesLeft : kHashTile / 32u;
-        for (uint32_t s = 0; s < n; s++) acc = xxh_round(acc, *reinterpret_cast<const uint64_t *>(mine + s * 32u + a * 8u));
-        stripesLeft -= n;
-        /* (all lanes: the row's accumulators to each of its lanes) */
-        const uint64_t v1 = __shfl(acc, (int)(lane & ~3u)), v2 = __shfl(acc, (int)(lane & ~3u) + 1), v3 = __shfl(acc, (int)(lane & ~3u) + 2),
-                       v4 = __shfl(acc, (int)(lane & ~3u) + 3);
-        if (t == endTile && a == 0u && row0 + r < nRows) {
-            uint64_t h;
-            if (len >= 32u) {
-                h = xxh_rotl(v1, 1u) + xxh_rotl(v2, 7u) + xxh_rotl(v3, 12u) + xxh_rotl(v4, 18u);
-                h = xxh_merge(xxh_merge(xxh_merge(xxh_merge(h, v1), v2), v3), v4);
-            } else {
-                h = kXP5;
-            }
-            h += len;
-            uint32_t p = (uint32_t)((len & ~(uint64_t)31u) - t * kHashTile), left = (uint32_t)len & 31u;
-            for (; left >= 8u; left -= 8u, p += 8u)
-                h = xxh_rotl(h ^ xxh_round(0ull, *reinterpret_cast<const uint64_t *>(mine + p)), 27u) * kXP1 + kXP4;
-            if (left >= 4u) {
-                h = xxh_rotl(h ^ (uint64_t)*reinterpret_cast<const uint32_t *>(mine + p) * kXP1, 23u) * kXP2 + kXP3;
-                p += 4u;
-                left -= 4u;
-            }
-            for (; left; left--, p++) h = xxh_rotl(h ^ (uint64_t)mine[p] * kXP5, 11u) * kXP1;
-            h ^= h >> 33;
-            h *= kXP2;
-            h ^= h >> 29;
-            h *= kXP3;
-            h ^= h >> 32;
-            out[row0 + r] = h;
-        }
-        __syncthreads(); /* the tile is consumed: the next one may take its place */
-        if (more) { QZ_HASH_STAGE(t + 1u) }
-        __syncthreads();
-    }
-#undef QZ_HASH_EACH_ROW
-#undef QZ_HASH_ROW
-#undef QZ_HASH_FETCH1
-#undef QZ_HASH_STAGE1
-#undef QZ_HASH_FETCH
-#undef QZ_HASH_STAGE
-}
-} // namespace
-
-extern "C" int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
-                               qzstd_hip_hash_row_t *d_rows, uint64_t *d_out)
-{
-    if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_out) return fail_msg("qzstd_hip_xxh64: null pointer");
-    if ((uintptr_t)d_base & 15u) return fail_msg("qzstd_hip_xxh64: base not 16-byte aligned");
-    for (uint32_t i = 0; i < nRows; i++) {
-        if (rows[i].srcOff & 15u) return fail_msg("qzstd_hip_xxh64: srcOff not a multiple of 16");
-        if (rows[i].len && !d_base) return fail_msg("qzstd_hip_xxh64: null base");
-    }
-    QZ_SET_DEVICE(device);
-    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (hash rows)");
-    hipLaunchKernelGGL(qzstd_xxh64_kernel, dim3((nRows + kHashRows - 1u) / kHashRows), dim3(64), 0, (hipStream_t)stream,
-                       static_cast<const uint8_t *>(d_base), d_rows, nRows, reinterpret_cast<unsigned long long *>(d_out));
-    QZ_CHECK(hipGetLastError(), "launch qzstd_xxh64_kernel");
-    return 0;
-}

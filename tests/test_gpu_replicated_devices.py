@@ -3,7 +3,7 @@
 `north_star`: "the batch shards across the 8 GPUs of one node with per-GPU HIP streams and host-side gather (no RCCL)"; the reference's
 analogue is the instance spread of /root/reference/src/qatseqprod.c:601-630, :1156-1162.  Until now QZSTD_hintSource's cut of an
 announcement into per-GPU block ranges, the placement of states over the GPUs and one resident service per device had only run against
-tests/mock/mock_hip.c: the GPU boxes have one MI355X.  QZSTD_HIP_REPLICATE_DEVICES=2 (test only, csrc/qzstd_kernels.hip: probe_devices)
+tests/mock/mock_hip.c: the GPU boxes have one MI355X.  QZSTD_HIP_REPLICATE_DEVICES=2 (test only, csrc/qzstd_runtime.hip: probe_devices)
 lists the physical GPU twice, so the library sees two LOGICAL devices — own streams, own pinned buffers, own batches, own resident
 service each — and the whole path runs on real HIP.  Everything has to come out as with one device: frames byte-identical to libzstd's
 frames from the ORACLE's sequences, no producer error, and BOTH devices have to have served blocks (QZSTD_deviceStats).
