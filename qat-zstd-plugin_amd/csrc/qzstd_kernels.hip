@@ -71,6 +71,34 @@
  * (profiles/r06_ab_small_steps.txt): level 1 11.91 -> 11.78 ms per GiB (-1.1 %), level 3 10.47 -> 10.31 (-1.6 %). */
 #define QZ_PRIO(n) do { if (!CHAIN) __builtin_amdgcn_s_setprio(n); } while (0)
 
+/* Knobs of the A/B builds (make variant XFLAGS="-D..."), each with the measurement it rests on */
+#ifndef QZ_PARSE_SPLIT
+#define QZ_PARSE_SPLIT 3 /* the parse wave of qz_item: windows parsed in interval 1 (the short one), the rest in interval 2 (A/B builds) */
+#endif
+#ifndef QZ_LINKS_PER_STEP
+#define QZ_LINKS_PER_STEP 4 /* the chain walk: links of an entry tested together; measured: 2 -> 4 another -1 to -2.6 % at levels 5-12 (76 VGPRs: still two workgroups per CU) */
+#endif
+/* Two workgroups of nine waves per CU put five waves on two of the four SIMDs: the kernel must fit five waves' registers into a
+ * SIMD's 512.  (A/B builds: QZ_WAVES_PER_EU=7 caps them for three workgroups per CU — measured in round 4 with a smaller head table:
+ * the runtime reports three resident, 768 blocks take 1.56 x the time of 512: the third workgroup buys nothing.) */
+#ifndef QZ_WAVES_PER_EU
+#define QZ_WAVES_PER_EU 5
+#endif
+#define QZ_OCCUPANCY __attribute__((amdgpu_waves_per_eu(QZ_WAVES_PER_EU)))
+
+/* profiling build (-DQZ_DEBUG_DUMP): per-wave cycle counts inside qz_item, dumped behind the item's result entries (tools/gpu_debug.py).  Each macro adds
+ * the cycles since the wave's previous lap to an accumulator and expects the wave's clock under a fixed name: QZ_PLAP the parse wave's (tQ), QZ_LAP a
+ * matcher wave's (tP), QZ_CLAP(k) phase k of the chain walk (dC[k], tC) */
+#ifdef QZ_DEBUG_DUMP
+#define QZ_PLAP(acc) { const u64 tN = __builtin_amdgcn_s_memtime(); acc += tN - tQ; tQ = tN; }
+#define QZ_LAP(acc) { const u64 tN = __builtin_amdgcn_s_memtime(); acc += tN - tP; tP = tN; }
+#define QZ_CLAP(k) { const u64 tN = __builtin_amdgcn_s_memtime(); dC[k] += tN - tC; tC = tN; }
+#else
+#define QZ_PLAP(acc)
+#define QZ_LAP(acc)
+#define QZ_CLAP(k)
+#endif
+
 namespace {
 
 constexpr int kMatchWaves = 8;
@@ -1388,15 +1416,9 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     if (!matcher) {
         /* ---------------- the parse wave (DEFER = false): its own scalar loop, same barrier cadence ---------------- */
         if (!QZ_ABLATED(32u)) __builtin_amdgcn_s_setprio(3); /* the serial critical path: win issue arbitration on its SIMD */
-#ifndef QZ_PARSE_SPLIT
-#define QZ_PARSE_SPLIT 3 /* windows parsed in interval 1 (the short one), the rest in interval 2 (A/B builds) */
-#endif
         constexpr uint32_t kSplit = QZ_PARSE_SPLIT;
 #ifdef QZ_DEBUG_DUMP
         u64 pI1 = 0, pW1 = 0, pI2 = 0, pW2 = 0, tQ = __builtin_amdgcn_s_memtime();
-#define QZ_PLAP(acc) { const u64 tN = __builtin_amdgcn_s_memtime(); acc += tN - tQ; tQ = tN; }
-#else
-#define QZ_PLAP(acc)
 #endif
         uint32_t nseqEnd, anchorEnd;
         if (REP) {
@@ -1485,13 +1507,8 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
     uint32_t rp = ring_dw((itBegin << kTileLog) + tid) << 2 | (tid & 3u); /* ring offset of the own position, advanced by one tile per iteration */
 #ifdef QZ_DEBUG_DUMP
     u64 dI1 = 0, dW1 = 0, dI2 = 0, dW2 = 0, tP = __builtin_amdgcn_s_memtime();
-#define QZ_LAP(acc) { const u64 tN = __builtin_amdgcn_s_memtime(); acc += tN - tP; tP = tN; }
     /* chain walk, by phase: 0 entry build, 1 next-entry fetch issued, 2 four-byte tests, 3 heads + extensions, 4 wait for the next entry, 5 steps */
     u64 dC[6] = { 0, 0, 0, 0, 0, 0 }, tC = 0;
-#define QZ_CLAP(k) { const u64 tN = __builtin_amdgcn_s_memtime(); dC[k] += tN - tC; tC = tN; }
-#else
-#define QZ_LAP(acc)
-#define QZ_CLAP(k)
 #endif
 
     /* Start flags and parse words of one tile from every position's candidate (cl = capped length, off = offset).  Below the chain levels this
@@ -1700,9 +1717,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
                      * BEFORE the earlier ones (a weaker test, still a necessary condition: they survive a little more often), all
                      * tests are one round trip, all heads another; the updates follow in link order, so the result is
                      * the sequential one. */
-#ifndef QZ_LINKS_PER_STEP
-#define QZ_LINKS_PER_STEP 4 /* measured: 2 -> 4 another -1 to -2.6 % at levels 5-12 (76 VGPRs: still two workgroups per CU) */
-#endif
                     constexpr int kG = QZ_LINKS_PER_STEP;
                     QZ_CLAP(1)
 #pragma unroll
@@ -2109,13 +2123,6 @@ __device__ __forceinline__ uint32_t qz_item(const LaunchArgs &args, const qzstd_
 }
 
 /* one launch, one work item per workgroup (the batch paths) */
-/* Two workgroups of nine waves per CU put five waves on two of the four SIMDs: the kernel must fit five waves' registers into a
- * SIMD's 512.  (A/B builds: QZ_WAVES_PER_EU=7 caps them for three workgroups per CU — measured in round 4 with a smaller head table:
- * the runtime reports three resident, 768 blocks take 1.56 x the time of 512: the third workgroup buys nothing.) */
-#ifndef QZ_WAVES_PER_EU
-#define QZ_WAVES_PER_EU 5
-#endif
-#define QZ_OCCUPANCY __attribute__((amdgpu_waves_per_eu(QZ_WAVES_PER_EU)))
 /* NEAR: every block of the launch fits the ring (maxBlockLen <= kRing: BASELINE config 4's 32 KiB blocks) — nothing the ring held is
  * ever overwritten, every source is compared from LDS, and the device-memory side of every compare is compiled out */
 template <bool HAS_LONG, bool REP, bool CHAIN, bool TURNS, bool NEAR>
