@@ -67,6 +67,32 @@ int QZSTD_frontGetChecksum(const QZSTD_Front *f);
 /* since creation, frames whose checksum [0] the GPU computed, [1] libzstd computed (host calls, and device frames built from raw bytes) */
 void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2]);
 
+/* Byte grouping for typed data (include/qzstd_bytegroup.h): elemSize 2, 4 or 8 makes every device call on this front build its frames from
+ * the BYTE-GROUPED content of each chunk — byte 0 of every element, then byte 1 of every element, ... (per frame: n = frame length /
+ * elemSize elements, the remainder behind the planes, unchanged) — with a block per plane from 4096 elements on
+ * (QZSTD_byteGroupBlocks): the sign/exponent bytes of bf16 / fp16 / fp32 weights are skewed and the mantissa bytes noise, and a block of
+ * their own gives each its own entropy tables.  1 (the default): off, every frame byte for byte what it was.  The grouping happens on the
+ * GPU while a part is staged (qzstd_hip_group): no extra pass, no host copy.  A frame is an ordinary zstd frame OF THE GROUPED CONTENT: the
+ * element size is not stored in it — the caller keeps it — and the layout follows from the frame's content size and elemSize alone; a
+ * reader decodes the frame and calls QZSTD_byteUngroup.  Checksums (QZSTD_frontSetChecksum) cover the grouped content, which is what a decoder
+ * verifies.  Frame counts, strides and QZSTD_frontDeviceBatchFrames are unchanged.
+ * A grouped frame whose content libzstd needs (a block it stores raw — a mantissa plane — is the rule here) gets it rebuilt on the host
+ * from the frame's own sequences and literals, already in the arena: no second device->host copy.  Only a frame with a block the matcher
+ * failed has the caller's bytes copied back and grouped on the host; that frame is built by ZSTD_compress2 and is any valid frame of the
+ * grouped content.  QZSTD_frontDeviceStats [1] counts rebuilt frames too (frames that were not built from sequences + literals).
+ * With a setting above 1 QZSTD_frontCompress returns (size_t)-1 (the host path cannot cut blocks per plane, and one front does not
+ * produce two layouts), and with a device layer without qzstd_hip_group the device calls return (size_t)-1 before anything is queued.
+ * Set: 0, or -1 for f NULL, an elemSize other than 1, 2, 4, 8, or while a call runs on the front.  Get: the setting (1 for f NULL). */
+int QZSTD_frontSetByteGroup(QZSTD_Front *f, unsigned elemSize);
+unsigned QZSTD_frontGetByteGroup(const QZSTD_Front *f);
+/* QZSTD_frontCompressDeviceBatch with an element size per buffer (a checkpoint mixes bf16 weights and fp32 norms): elemSizes[i] is 1, 2, 4
+ * or 8, or 0 for the front's setting; NULL means all 0.  Any other value: (size_t)-1 before anything is queued. */
+size_t QZSTD_frontCompressDeviceBatchTyped(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs,
+                                           void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame);
+/* since creation, byte-grouped frames (element size above 1) built from [0] sequences + literals, [1] content rebuilt from the arena,
+ * [2] content copied back from the device and grouped on the host */
+void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3]);
+
 #if defined(__cplusplus)
 }
 #endif

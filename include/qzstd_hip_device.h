@@ -73,6 +73,32 @@ int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *row
                      void *d_stage, size_t stageBytes);
 
 /*
+ * Byte-grouping gather: the gather with a per-row element size.  A row's `len` bytes land in the stage in the byte-grouped layout of
+ * include/qzstd_bytegroup.h for k = elem — n = len / elem; byte j of elements 0 .. n-1 at [j * n, (j + 1) * n) of the row; the len - n * elem
+ * tail bytes behind them, unchanged — and `pad` zero bytes follow.  elem = 1 rows give exactly what qzstd_hip_gather gives.
+ *
+ * A workgroup takes 16 KiB of ONE row's source (an element range) across all `elem` planes: the source is read once (aligned 16-byte loads
+ * of the words that overlap [src, src + len) and of no other word, shifted into place in registers), split into the planes in LDS, and every
+ * stage word — a 16-byte word of the stage belongs to the plane and element range of its FIRST byte — leaves with one aligned 16-byte
+ * store by one lane.  The owner of a word that reaches into the next element range, the next plane, the tail or the padding fetches those
+ * few bytes itself.  No atomics, no read-modify-write of the stage; stage bytes between rows are left as they are.  Rows of one byte and
+ * rows of many MiB go in one launch.
+ *
+ * `rows`, d_rows, the refusals before anything is queued, nRows == 0 and asynchrony: as qzstd_hip_gather, plus an `elem` outside
+ * {1, 2, 4, 8} and a `reserved` that is not 0.
+ */
+typedef struct {
+    uint64_t src;      /* device address of the row's first byte, any alignment */
+    uint64_t dstOff;   /* byte offset in d_stage, a multiple of 16 */
+    uint32_t len;      /* bytes to copy, may be 0 */
+    uint32_t pad;      /* zero bytes written behind them; len + pad is a multiple of 16 */
+    uint32_t elem;     /* element size: 1, 2, 4 or 8 */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_group_row_t;
+int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
+                    void *d_stage, size_t stageBytes);
+
+/*
  * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a
  * zstd frame stores its low 32 bits).  The rows are a part's frames where the match-finder reads them (the stage, or the caller's buffer
  * for a part read in place): both start every frame 16-aligned, hence the alignment rule.  XXH64's four accumulators are serial chains

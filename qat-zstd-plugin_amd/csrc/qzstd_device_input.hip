@@ -1,7 +1,7 @@
 /*
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
- * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, and the XXH64 content
- * checksum.  They use nothing of the match-finder (qzstd_kernels.hip).
+ * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
+ * gather for typed rows, and the XXH64 content checksum.  They use nothing of the match-finder (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
 
@@ -274,6 +274,201 @@ extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather
     hipLaunchKernelGGL(qzstd_gather_kernel, dim3(groups), dim3(kGatherT), 0, (hipStream_t)stream, d_rows, nRows, firstWord, endWord,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_gather_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- byte-grouping gather (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kGroupT = 256u;                    /* threads per workgroup */
+constexpr uint32_t kGroupTileLog = 14u;               /* source bytes of one row per workgroup: 16 KiB, 16 KiB / elem elements */
+constexpr uint32_t kGroupTile = 1u << kGroupTileLog;
+constexpr uint32_t kGroupSlack = 32u;                 /* bytes behind each plane in LDS: a stage word's two aligned 16-byte reads stay inside */
+constexpr uint32_t kGroupLds = kGroupTile + 8u * kGroupSlack;
+
+/* Workgroup v of the launch's numbering is tile v - start(r) of row r, start(r) = (dstOff >> 14) + r: strictly ascending in r, and a row's
+ * tiles (at most ceil((len + pad) / 16 KiB)) end before the next row's start, so the launcher needs no prefix sums over the rows.  A
+ * workgroup whose number falls behind its row's last tile has nothing to do. */
+__device__ inline uint64_t group_row_start(const qzstd_hip_group_row_t *__restrict__ rows, uint32_t r)
+{
+    return (rows[r].dstOff >> kGroupTileLog) + r;
+}
+
+/* byte p of the row's grouped layout (0 from len on), by one aligned 16-byte load of the word that holds its source byte */
+__device__ inline uint64_t group_byte(const qzstd_hip_group_row_t &row, uint32_t n, uint32_t kLog, uint64_t p)
+{
+    if (p >= row.len) return 0ull;
+    uint64_t s = p;
+    if (p < ((uint64_t)n << kLog)) {
+        const uint32_t j = (uint32_t)p / n; /* (p < len: 32 bits) */
+        s = ((uint64_t)((uint32_t)p - j * n) << kLog) + j;
+    }
+    const uint64_t a = row.src + s;
+    const uint32_t sh = (uint32_t)a & 15u;
+    const uint4 v = *reinterpret_cast<const uint4 *>(a - sh);
+    const uint32_t d = sh < 8u ? (sh < 4u ? v.x : v.y) : (sh < 12u ? v.z : v.w);
+    return (d >> ((sh & 3u) * 8u)) & 0xFFu;
+}
+
+/* {h, l} >> 8 * sh, its low 16 bytes: whole 64-bit halves first, then the bytes (the gather's shift) */
+__device__ inline void group_shift(const uint4 l, const uint4 h, uint32_t sh, uint64_t *o0, uint64_t *o1)
+{
+    const uint64_t l0 = l.x | (uint64_t)l.y << 32, l1 = l.z | (uint64_t)l.w << 32, h0 = h.x | (uint64_t)h.y << 32, h1 = h.z | (uint64_t)h.w << 32;
+    const bool half = (sh & 8u) != 0u;
+    const uint32_t bits = (sh & 7u) * 8u;
+    const uint64_t a0 = half ? l1 : l0, a1 = half ? h0 : l1, a2 = half ? h1 : h0;
+    *o0 = bits ? (a0 >> bits) | (a1 << (64u - bits)) : a0;
+    *o1 = bits ? (a1 >> bits) | (a2 << (64u - bits)) : a1;
+}
+
+/* bytes [from, 16) of the stage word at row offset o, fetched one by one: the few bytes of a word that lie outside its owner's tile */
+__device__ inline void group_patch(const qzstd_hip_group_row_t &row, uint32_t n, uint32_t kLog, uint64_t o, uint32_t from, uint64_t *o0, uint64_t *o1)
+{
+    *o1 = from > 8u ? *o1 & ((1ull << ((from - 8u) * 8u)) - 1ull) : 0ull;
+    if (from < 8u) *o0 = from ? *o0 & ((1ull << (from * 8u)) - 1ull) : 0ull;
+    if (o + from >= row.len) return; /* padding only */
+    for (uint32_t i = from; i < 16u; i++) {
+        const uint64_t b = group_byte(row, n, kLog, o + i);
+        if (i < 8u) *o0 |= b << (i * 8u); else *o1 |= b << ((i - 8u) * 8u);
+    }
+}
+
+/* the 16 source bytes {o1, o0} = 16 / K elements: byte j of each into plane j of the tile in LDS, at the elements' place (word w of the tile) */
+template <uint32_t K> __device__ inline void group_split(uint64_t o0, uint64_t o1, uint8_t *lds, uint32_t w)
+{
+    constexpr uint32_t per = 16u / K, pitch = kGroupTile / K + kGroupSlack;
+    if constexpr (K == 1u) {
+        *reinterpret_cast<uint4 *>(lds + w * 16u) = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+    } else {
+#pragma unroll
+        for (uint32_t j = 0; j < K; j++) {
+            uint64_t v = 0;
+#pragma unroll
+            for (uint32_t e = 0; e < per; e++) {
+                const uint32_t i = e * K + j;
+                v |= (((i < 8u ? o0 >> (i * 8u) : o1 >> ((i - 8u) * 8u))) & 0xFFull) << (e * 8u);
+            }
+            uint8_t *at = lds + j * pitch + w * per;
+            if constexpr (per == 8u) *reinterpret_cast<uint64_t *>(at) = v;
+            else if constexpr (per == 4u) *reinterpret_cast<uint32_t *>(at) = (uint32_t)v;
+            else *reinterpret_cast<uint16_t *>(at) = (uint16_t)v;
+        }
+    }
+}
+
+/* One workgroup per tile: elements [e0, e0 + tileElems) of one row, 16 KiB of its source.
+ *   A  every lane takes the tile's source 16 bytes at a time (aligned loads shifted into place, as the gather's), splits them by byte
+ *      position and writes the pieces to the tile's planes in LDS: the source crosses the memory system once for all planes
+ *   B  per plane, every stage word whose first byte is one of the tile's elements is read back from LDS (two aligned 16-byte reads shifted
+ *      by the plane's offset in its stage word), completed with single bytes where it reaches past the tile, and stored
+ *   and the row's last tile writes the words that start in the tail or the padding. */
+__global__ __launch_bounds__(kGroupT) void qzstd_group_kernel(const qzstd_hip_group_row_t *__restrict__ rows, uint32_t nRows, uint64_t firstTile,
+                                                               uint4 *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
+    __shared__ uint32_t which;
+    const uint64_t v = firstTile + blockIdx.x;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (group_row_start(rows, mid) <= v) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_group_row_t row = rows[r];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kGroupTile >> kLog;
+    const uint64_t ext = (uint64_t)row.len + row.pad;
+    const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (ext ? 1ull : 0ull);
+    const uint64_t t = v - ((row.dstOff >> kGroupTileLog) + r);
+    if (t >= tiles) return; /* (the whole workgroup) */
+    const uint32_t e0 = (uint32_t)t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint32_t tileBytes = tileElems << kLog;
+    const uint64_t srcTile = row.src + ((uint64_t)e0 << kLog);
+
+    for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kGroupT) {
+        const uint64_t a = srcTile + w * 16u;
+        const uint32_t sh = (uint32_t)a & 15u;
+        const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+        const uint4 *p = reinterpret_cast<const uint4 *>(a - sh);
+        /* the aligned word that holds byte a, and the next one only when bytes of the tile lie in it */
+        const uint4 l = p[0];
+        uint4 h = make_uint4(0u, 0u, 0u, 0u);
+        if (sh + valid > 16u) h = p[1];
+        uint64_t o0, o1;
+        group_shift(l, h, sh, &o0, &o1);
+        switch (kLog) {
+        case 0u: group_split<1u>(o0, o1, lds, w); break;
+        case 1u: group_split<2u>(o0, o1, lds, w); break;
+        case 2u: group_split<4u>(o0, o1, lds, w); break;
+        default: group_split<8u>(o0, o1, lds, w); break;
+        }
+    }
+    __syncthreads();
+
+    uint4 *out = stage + (row.dstOff >> 4);
+    for (uint32_t j = 0; j < (1u << kLog); j++) {
+        const uint64_t planeAt = (uint64_t)j * n + e0; /* row offset of the tile's first element in plane j */
+        const uint32_t aj = (uint32_t)planeAt & 15u;
+        const uint8_t *base = lds + j * (tileMax + kGroupSlack);
+        /* c: offset from the stage word that holds planeAt; that word itself belongs here only when it starts at planeAt */
+        for (uint32_t c = (aj ? 16u : 0u) + threadIdx.x * 16u; c < aj + tileElems; c += kGroupT * 16u) {
+            const uint32_t x0 = c - aj, q = x0 & ~15u, sh = x0 & 15u;
+            const uint32_t valid = tileElems - x0 < 16u ? tileElems - x0 : 16u;
+            const uint64_t o = planeAt + x0;
+            const uint4 l = *reinterpret_cast<const uint4 *>(base + q);
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh) h = *reinterpret_cast<const uint4 *>(base + q + 16u);
+            uint64_t o0, o1;
+            group_shift(l, h, sh, &o0, &o1);
+            if (valid < 16u) group_patch(row, n, kLog, o, valid, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+    if (t + 1u == tiles) {
+        const uint64_t tailAt = ((((uint64_t)n << kLog) + 15u) & ~(uint64_t)15u);
+        for (uint64_t o = tailAt + threadIdx.x * 16u; o < ext; o += kGroupT * 16u) {
+            uint64_t o0 = 0, o1 = 0;
+            group_patch(row, n, kLog, o, 0u, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
+                               void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_group_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
+            return fail_msg("qzstd_hip_group: elem not 1, 2, 4 or 8, or reserved not 0");
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group: dstOff or len + pad not a multiple of 16");
+        if (r.len && !r.src) return fail_msg("qzstd_hip_group: null source");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_group: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group: a row ends past stageBytes");
+        end = r.dstOff + ext;
+        if (ext) { /* the row's tiles in the launch's numbering (qzstd_group_kernel) */
+            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
+            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group rows)");
+    hipLaunchKernelGGL(qzstd_group_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+                       static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_group_kernel");
     return 0;
 }
 

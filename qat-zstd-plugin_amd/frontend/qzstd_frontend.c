@@ -11,6 +11,8 @@
 #include "qzstd_frontend_device.h"
 
 #include "qatseqprod.h"
+#include "qzstd_bytegroup.h"
+#include "qzstd_bytegroup_internal.h"
 #include "qzstd_hip_device.h"
 
 #include <dlfcn.h>
@@ -20,6 +22,8 @@
 #include <string.h>
 
 extern int zstdshim_ok(void) __attribute__((weak)); /* tools/zstdshim, when that is the libzstd in the process; else absent */
+
+typedef char qf_seq_layout_is_qzbg[sizeof(ZSTD_Sequence) == QZBG_ENTRY_WORDS * sizeof(unsigned) ? 1 : -1]; /* qzbgRebuild reads the workers' ZSTD_Sequence arrays */
 
 #define QF_NONE ((size_t)-1)
 #define QF_HINT_MAX ((size_t)16 << 20)
@@ -38,6 +42,10 @@ typedef struct {
     void *rawStream;
     int rawDev;
     int cksum; /* ZSTD_c_checksumFlag as last set on zc (the parameter is sticky: qfCtxChecksum) */
+    /* byte-grouped frames: the frame's block ends, and the caller's bytes of a frame that could not be rebuilt (pinned, as raw) */
+    size_t *ends;
+    size_t endsCap;
+    unsigned char *back;
 } QF_Worker;
 
 typedef struct QF_DevPart_s QF_DevPart;
@@ -70,6 +78,9 @@ struct QZSTD_Front_s {
     /* content checksums (QZSTD_frontSetChecksum): the setting, and frames hashed by the GPU / by libzstd */
     int checksum;
     unsigned long long cksumStats[2];
+    /* byte grouping (QZSTD_frontSetByteGroup): the element size of the device calls (1: off), and grouped frames by how they were built */
+    unsigned group;
+    unsigned long long groupStats[3];
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -210,6 +221,7 @@ QZSTD_Front *QZSTD_createFront(const QZSTD_FrontParams *p)
     f = (QZSTD_Front *)calloc(1, sizeof(*f));
     if (!f) return NULL;
     f->p = *p;
+    f->group = 1u;
     /* measured on MI355X + 16 cores: 2 MiB where the entropy stage sets the pace (levels 1-4), 4 MiB claims of one size where the match-finder does */
     seg = p->segmentBytes ? p->segmentBytes : ((size_t)(p->level >= 5 ? 4 : 2) << 20);
     /* ... and at the chain levels at most 64 chunks per claim (round 5): a claim is one launch, its blocks one workgroup each — level 12 on 32 KiB
@@ -276,6 +288,7 @@ size_t QZSTD_frontCompress(QZSTD_Front *f, const void *src, size_t srcSize, void
     size_t nChunks;
     int failed;
     if (!f || (!src && srcSize) || !dst || !frameSizes) return (size_t)-1;
+    if (f->group > 1u) return (size_t)-1; /* the host path cannot cut a block per plane: no second layout from one front */
     nChunks = (srcSize + f->p.chunkSize - 1) / f->p.chunkSize;
     if (nChunks == 0) return 0;
     if (dstCapacity / f->stride < nChunks) return (size_t)-1;
@@ -342,6 +355,8 @@ void QZSTD_freeFront(QZSTD_Front *f)
         if (w->zc) ZSTD_freeCCtx(w->zc);
         if (w->state) QZSTD_freeSeqProdState(w->state);
         free(w->seqs);
+        free(w->ends);
+        if (w->back) qzstd_hip_host_free(w->back);
         if (w->raw) qzstd_hip_host_free(w->raw);
         if (w->rawStream) qzstd_hip_stream_destroy(w->rawDev, w->rawStream);
     }
@@ -369,6 +384,12 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * the compaction on the slot's stream), 8 bytes per frame come back with the arena's headers, and qfDeviceFrame sets the header's flag and
  * appends the low 32 bits to a frame ZSTD_compressSequencesAndLiterals built (that function refuses ZSTD_c_checksumFlag: it never sees
  * the content).  The raw-bytes paths have the content and let libzstd hash it.
+ *
+ * Byte grouping (QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped): a frame with an element size k > 1 is staged by
+ * qzstd_hip_group instead — its bytes arrive in the layout of include/qzstd_bytegroup.h — and its blocks are those of QZSTD_byteGroupBlocks:
+ * a block per plane, so that the skewed exponent plane and the noisy mantissa plane of float data get entropy tables of their own.
+ * Everything behind the staging (match-finder, compaction, hash, arena) sees an ordinary part whose frames have unusual block lengths.
+ * A frame that needs its content on the host (a raw block: the common case here) rebuilds it from its own entries and literals.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
@@ -383,6 +404,8 @@ extern int qzstd_hip_compact(int device, void *stream, const void *d_src, const 
                              size_t workBytes) __attribute__((weak));
 extern int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
                             void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
+                           void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
                            qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
 
@@ -419,6 +442,9 @@ struct QF_DevSlot_s {
     unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned frames, when the caller's buffers cannot be read in place */
     qzstd_hip_gather_row_t *hRows; size_t hRowsCap; /* the gather's rows, one per frame (pinned), and their device copy */
     void *dRows; size_t dRowsCap;
+    qzstd_hip_group_row_t *hGroupRows; size_t hGroupRowsCap; /* a part with byte-grouped frames: qzstd_hip_group's rows instead */
+    void *dGroupRows; size_t dGroupRowsCap;
+    size_t *ends; size_t endsCap; /* the block ends of the frame whose descriptors are being written */
     qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
     void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
     uint64_t *hHash; size_t hHashCap;
@@ -436,13 +462,15 @@ typedef struct {
     size_t off, len; /* offset in its buffer, length (chunkSize, or what is left of the buffer) */
     size_t b0;       /* first block in its part */
     uint32_t buf;    /* owning buffer */
-    uint32_t nb;     /* blocks: ceil(len / 128 KiB) */
+    uint32_t nb;     /* blocks: QZSTD_byteGroupBlocks(len, k) — ceil(len / 128 KiB) for k = 1 */
+    uint32_t k;      /* element size of the byte-grouped layout; 1: the bytes as they are */
 } QF_DevFrame;
 
 /* a part: frames [f0, f1) of the job, matched in one launch */
 typedef struct {
     size_t f0, f1, nb, bytes;
     int run; /* the frames are consecutive chunks of ONE buffer: readable in place when aligned, stageable by 2D copies */
+    int grouped; /* a frame with k > 1 among them: staged by qzstd_hip_group, never read in place */
 } QF_DevRange;
 
 struct QF_DevPart_s {
@@ -457,11 +485,13 @@ struct QF_DevPart_s {
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
-    void *d[] = { s->dStage, s->dRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
+    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
     if (s->hRows) qzstd_hip_host_free(s->hRows);
+    if (s->hGroupRows) qzstd_hip_host_free(s->hGroupRows);
+    free(s->ends);
     if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
     if (s->hHash) qzstd_hip_host_free(s->hHash);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
@@ -520,6 +550,26 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     void *stage = s->dStage;
     if (qfGrowD(j->dev, &stage, &s->stageCap, stageBytes)) return -1;
     s->dStage = (unsigned char *)stage;
+    if (pr->grouped) {
+        /* the gather's rows with each frame's element size: the frames arrive in the byte-grouped layout */
+        void *h = s->hGroupRows;
+        size_t c, so = 0;
+        if (!qzstd_hip_group || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
+        s->hGroupRows = (qzstd_hip_group_row_t *)h;
+        if (qfGrowD(j->dev, &s->dGroupRows, &s->dGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
+        for (c = 0; c < nf; c++) {
+            qzstd_hip_group_row_t *r = &s->hGroupRows[c];
+            if (f0[c].len > 0xFFFFFFE0u) return -1;
+            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->dstOff = so;
+            r->len = (uint32_t)f0[c].len;
+            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
+            r->elem = f0[c].k;
+            r->reserved = 0;
+            so += qfPad16(f0[c].len);
+        }
+        return qzstd_hip_group(j->dev, s->stream, s->hGroupRows, (uint32_t)nf, (qzstd_hip_group_row_t *)s->dGroupRows, s->dStage, stageBytes);
+    }
     if (qzstd_hip_gather) {
         void *h = s->hRows;
         size_t c, so = 0;
@@ -557,7 +607,7 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
     const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
     /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
-    const int inPlace = pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
+    const int inPlace = !pr->grouped && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
     size_t c, b = 0, so = 0, seqCapTotal = 0;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
@@ -568,11 +618,19 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     }
     for (c = 0; c < nf; c++) {
         const size_t at = inPlace ? f0[c].off - f0->off : so; /* the frame's first byte from the launch's base */
-        size_t o;
+        size_t o = 0, e;
         if (f0[c].b0 != b) return -1;
-        for (o = 0; o < f0[c].len; o += QZSTD_HIP_BLOCK_MAX, b++) {
+        /* one descriptor per block of the frame's rule: every 128 KiB, and for a byte-grouped frame a block per plane first */
+        if (s->endsCap < f0[c].nb) {
+            free(s->ends);
+            s->ends = (size_t *)malloc(f0[c].nb * sizeof(size_t));
+            s->endsCap = s->ends ? f0[c].nb : 0;
+            if (!s->ends) return -1;
+        }
+        if (QZSTD_byteGroupBlocks(f0[c].len, f0[c].k, s->ends, s->endsCap) != f0[c].nb) return -1;
+        for (e = 0; e < f0[c].nb; o = s->ends[e], e++, b++) {
             qzstd_hip_block_t *d = &s->hDesc[b];
-            d->srcLen = (uint32_t)(f0[c].len - o < QZSTD_HIP_BLOCK_MAX ? f0[c].len - o : QZSTD_HIP_BLOCK_MAX);
+            d->srcLen = (uint32_t)(s->ends[e] - o);
             d->srcOff = at + o;
             d->seqOff = b * capPad;
             d->seqCap = (uint32_t)cap;
@@ -687,19 +745,19 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     return 0;
 }
 
-/* 1 when the frame ZSTD_compressSequencesAndLiterals built for n source bytes holds a Compressed block that libzstd stores raw — that
- * function cannot, ZSTD_compressSequences does when the body does not beat the block's source (min(128 KiB, what is left) bytes) by
+/* 1 when the frame ZSTD_compressSequencesAndLiterals built holds a Compressed block that libzstd stores raw — that
+ * function cannot, ZSTD_compressSequences does when the body does not beat the block's source (ends[k] - ends[k - 1] bytes: the frame's own block lengths) by
  * ZSTD_minGain = (srcSize >> 6) + 2 bytes.  That is the gain of every strategy below btultra; above it the gain is smaller, and a frame
  * this catches without need takes the raw-bytes path and comes out the same.  Walks the frame header (descriptor: single segment,
  * dictionary ID and content size fields) and the 3-byte block headers. */
-static int qfStoresRawBlock(const unsigned char *fr, size_t frSize, size_t n)
+static int qfStoresRawBlock(const unsigned char *fr, size_t frSize, const size_t *ends, size_t nEnds)
 {
     static const unsigned char didBytes[4] = { 0, 1, 2, 4 }, fcsBytes[4] = { 0, 2, 4, 8 };
     const unsigned fhd = fr[4], single = (fhd >> 5) & 1u;
     size_t pos = 5 + !single + didBytes[fhd & 3u] + ((fhd >> 6) == 0 ? single : fcsBytes[fhd >> 6]), k;
-    for (k = 0; pos + 3 <= frSize; k++) {
+    for (k = 0; pos + 3 <= frSize && k < nEnds; k++) {
         const unsigned h = fr[pos] | (unsigned)fr[pos + 1] << 8 | (unsigned)fr[pos + 2] << 16;
-        const size_t body = h >> 3, src = n - k * QZSTD_HIP_BLOCK_MAX < QZSTD_HIP_BLOCK_MAX ? n - k * QZSTD_HIP_BLOCK_MAX : QZSTD_HIP_BLOCK_MAX;
+        const size_t body = h >> 3, src = ends[k] - (k ? ends[k - 1] : 0);
         if (((h >> 1) & 3u) == 2u && body + (src >> 6) + 2 >= src) return 1;
         pos += 3 + (((h >> 1) & 3u) == 1u ? 1 : body);
         if (h & 1u) break; /* Last_Block */
@@ -719,11 +777,25 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(pt->nb);
     const unsigned long long *ent = (const unsigned long long *)(const void *)(s->hArena + eo);
     size_t b, ns = 0, nl = 0, k, r = 0;
-    int failedBlock = 0, haveSeqs = 0;
+    int failedBlock = 0, haveSeqs = 0, maybeRle = 0;
+    const int grouped = fm->k > 1u;
     unsigned char *dst = f->dst + cg * f->stride;
+    /* the frame's block ends (every 128 KiB; a byte-grouped frame's planes first) */
+    if (w->endsCap < fm->nb) {
+        free(w->ends);
+        w->ends = (size_t *)malloc(fm->nb * sizeof(size_t));
+        w->endsCap = w->ends ? fm->nb : 0;
+        if (!w->ends) return -1;
+    }
+    if (QZSTD_byteGroupBlocks(n, fm->k, w->ends, w->endsCap) != fm->nb) return -1;
     for (b = b0; b < b1; b++) {
         if (hdr[b].count == QZSTD_HIP_NSEQ_ERROR) failedBlock = 1;
         else { ns += hdr[b].count; nl += hdr[b].litBytes; }
+        /* A plane of one value (the high bytes of small integers) is a block ZSTD_compressSequences may store as RLE — never the frame's
+         * first block, and only one of fewer than 4 sequences and fewer than 10 literal bytes (ZSTD_maybeRLE) — which
+         * ZSTD_compressSequencesAndLiterals cannot: it has no content to look at.  Such a frame is built from its content, like one with
+         * a raw block.  (Byte-grouped frames only: the frames of ungrouped input stay what they were.) */
+        if (grouped && b > b0 && hdr[b].count != QZSTD_HIP_NSEQ_ERROR && hdr[b].count < 5u && hdr[b].litBytes < 10u) maybeRle = 1;
     }
     if (!failedBlock) {
         const unsigned long long *q = ent + s->blkSeq[b0];
@@ -744,12 +816,12 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         /* (a session that ended in an error leaves the CCtx mid-frame, where parameters cannot be set: every frame starts afresh) */
         (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
         if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 1))) return -1;
-        if (qfSeqLit && qfCtxChecksum(w, 0) == 0) { /* (ZSTD_compressSequencesAndLiterals refuses the checksum flag) */
+        if (qfSeqLit && !maybeRle && qfCtxChecksum(w, 0) == 0) { /* (ZSTD_compressSequencesAndLiterals refuses the checksum flag) */
             /* the frame's literals straight from the arena; everything behind them (later frames' literals, the slack) is readable */
             const unsigned char *lit = s->hLit + s->blkLit[b0];
             const size_t litCap = s->litTotal - s->blkLit[b0] + QF_LIT_SLACK;
             r = qfSeqLit(w->zc, dst, f->stride, w->seqs, ns, lit, nl, litCap, n);
-            if (!ZSTD_isError(r) && !qfStoresRawBlock(dst, r, n) && (!pt->hashed || r + 4u <= f->stride)) {
+            if (!ZSTD_isError(r) && !qfStoresRawBlock(dst, r, w->ends, fm->nb) && (!pt->hashed || r + 4u <= f->stride)) {
                 (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
                 if (pt->hashed) {
                     /* Content_Checksum_Flag (bit 2 of the frame header descriptor) and the hash's low 32 bits behind the last block */
@@ -764,6 +836,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
                 }
                 f->sizes[cg] = r;
                 __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
+                if (grouped) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
                 return 0;
             }
         }
@@ -779,13 +852,32 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         w->rawDev = pt->dev;
         if (!w->raw || !w->rawStream) return -1;
     }
-    if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, (const unsigned char *)pt->bufs[fm->buf].d_ptr + fm->off, n)) return -1;
-    if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
-        /* the copy still reads the caller's buffer: the call must not return before it is done */
-        (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
-        return -1;
+    /* A byte-grouped frame's content is not what the caller's buffer holds, and in grouped mode this is the common path (a mantissa plane is
+     * noise: a raw block).  The arena has everything: the frame's own entries and literals, executed, ARE the grouped content — no second
+     * device->host copy, and no look at the stage, which may hold the part after next by now */
+    if (grouped && haveSeqs &&
+        qzbgRebuild(w->raw, n, ns ? &w->seqs[0].offset : NULL, ns, s->hLit + s->blkLit[b0], nl, w->ends, fm->nb) == 0) {
+        __atomic_fetch_add(&f->groupStats[1], 1ull, __ATOMIC_RELAXED);
+    } else {
+        unsigned char *to = w->raw;
+        if (grouped) {
+            /* a failed block (or entries that do not rebuild): the caller's bytes come back and are grouped here; no sequences are used */
+            if (!w->back && !(w->back = (unsigned char *)qzstd_hip_host_alloc(f->p.chunkSize))) return -1;
+            to = w->back;
+            haveSeqs = 0;
+        }
+        if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, to, (const unsigned char *)pt->bufs[fm->buf].d_ptr + fm->off, n)) return -1;
+        if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
+            /* the copy still reads the caller's buffer: the call must not return before it is done */
+            (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
+            return -1;
+        }
+        __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
+        if (grouped) {
+            if (QZSTD_byteGroup(w->raw, w->back, n, fm->k) != n) return -1;
+            __atomic_fetch_add(&f->groupStats[2], 1ull, __ATOMIC_RELAXED);
+        }
     }
-    __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->devStats[1], 1ull, __ATOMIC_RELAXED);
     /* libzstd has the content here and hashes it itself */
     if (qfCtxChecksum(w, pt->hashed)) return -1;
@@ -818,8 +910,8 @@ size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf 
 /* the per-frame table and the parts of a job.  A part takes whole frames, across buffer boundaries, until the next one would take its input
  * past partBytes or its blocks past four times the blocks of a part of full ones (a block costs the device the same scratch whatever its
  * length); at least one frame. */
-static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, size_t nFrames, size_t partBytes, size_t blk,
-                        QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
+static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, unsigned group, size_t nBufs,
+                        size_t nFrames, size_t partBytes, size_t blk, QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
 {
     const size_t chunk = f->p.chunkSize, maxBlocks = 4u * (partBytes / blk ? partBytes / blk : 1u);
     QF_DevFrame *fr = (QF_DevFrame *)malloc(nFrames * sizeof(*fr));
@@ -827,15 +919,17 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_
     size_t i, c = 0, nParts = 0;
     if (!fr || !pt) { free(fr); free(pt); return -1; }
     for (i = 0; i < nBufs; i++) {
+        const unsigned k = elemSizes && elemSizes[i] ? elemSizes[i] : group;
         size_t off;
         for (off = 0; off < bufs[i].size; off += chunk, c++) {
             const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
-            const size_t nb = (len + QZSTD_HIP_BLOCK_MAX - 1) / QZSTD_HIP_BLOCK_MAX;
+            const size_t nb = QZSTD_byteGroupBlocks(len, k, NULL, 0);
             if (!cur || cur->bytes + len > partBytes || cur->nb + nb > maxBlocks) {
                 cur = &pt[nParts++];
                 cur->f0 = c;
                 cur->nb = cur->bytes = 0;
                 cur->run = 1;
+                cur->grouped = 0;
             } else if (fr[c - 1].buf != (uint32_t)i) {
                 cur->run = 0;
             }
@@ -844,6 +938,8 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_
             fr[c].b0 = cur->nb;
             fr[c].buf = (uint32_t)i;
             fr[c].nb = (uint32_t)nb;
+            fr[c].k = k;
+            if (k > 1u) cur->grouped = 1;
             cur->f1 = c + 1;
             cur->nb += nb;
             cur->bytes += len;
@@ -858,8 +954,8 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_
 
 /* both device entry points.  batch: the call needs the gather (frames of several buffers in one part); the single-buffer call stages a part it
  * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not */
-static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, int batch, void *stream, void *dst, size_t dstCapacity,
-                               size_t *frameSizes, size_t *firstFrame)
+static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, int batch, void *stream,
+                               void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
     QF_DevJob j;
     QF_DevSlot *slot;
@@ -868,11 +964,19 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size
     QF_DevRange *parts = NULL;
     void *ev = NULL;
     size_t nFrames, nParts = 0, k, i, total = 0;
-    int rc = 0;
+    unsigned group;
+    int rc = 0, anyGrouped = 0;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
         if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+    /* each buffer's element size: its own entry, or (0, or no array) the front's setting */
+    group = f->group;
+    for (i = 0; i < nBufs; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : group;
+        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
+        if (e > 1u) anyGrouped = 1;
+    }
     nFrames = QZSTD_frontDeviceBatchFrames(f, bufs, nBufs);
     if (dstCapacity / f->stride < nFrames) return (size_t)-1;
     if (!qzstd_hip_pointer_device || !qzstd_hip_compact || !qzstd_hip_compact_workspace_bytes || !qzstd_hip_event_create ||
@@ -880,6 +984,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size
         (batch && !qzstd_hip_gather))
         return (size_t)-1; /* a device layer without the device-input entry points */
     if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
+    if (anyGrouped && !qzstd_hip_group) return (size_t)-1;  /* byte grouping wanted and a device layer that cannot group */
     j.dev = -1;
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
@@ -914,7 +1019,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size
     {
         const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
         const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        rc = qfPlanDevice(f, bufs, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
+        rc = qfPlanDevice(f, bufs, elemSizes, group, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
     }
     j.frames = frames;
     j.parts = parts;
@@ -984,13 +1089,19 @@ size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSi
     QZSTD_DeviceBuf one;
     one.d_ptr = d_src;
     one.size = srcSize;
-    return qfCompressDevice(f, &one, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
+    return qfCompressDevice(f, &one, NULL, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
 }
 
 size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, void *dst, size_t dstCapacity,
                                       size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, NULL, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+}
+
+size_t QZSTD_frontCompressDeviceBatchTyped(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream,
+                                           void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
+{
+    return qfCompressDevice(f, bufs, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
@@ -1019,3 +1130,27 @@ void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2])
     if (!stats) return;
     for (k = 0; k < 2; k++) stats[k] = f ? __atomic_load_n(&f->cksumStats[k], __ATOMIC_RELAXED) : 0ull;
 }
+
+int QZSTD_frontSetByteGroup(QZSTD_Front *f, unsigned elemSize)
+{
+    int busy;
+    if (!f || (elemSize != 1u && elemSize != 2u && elemSize != 4u && elemSize != 8u)) return -1;
+    pthread_mutex_lock(&f->mu);
+    busy = f->devBusy || f->running;
+    if (!busy) f->group = elemSize;
+    pthread_mutex_unlock(&f->mu);
+    return busy ? -1 : 0;
+}
+
+unsigned QZSTD_frontGetByteGroup(const QZSTD_Front *f) { return f ? f->group : 1u; }
+
+void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 3; k++) stats[k] = f ? __atomic_load_n(&f->groupStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+/* The byte-grouped layout, its block rule and qzbgRebuild: a source of their own, free of HIP and libzstd (the tests build it alone), and
+ * part of this translation unit so that the front-end stays ONE source to whoever builds it. */
+#include "qzstd_bytegroup.c"

@@ -23,6 +23,19 @@ libzstd hashes), device (QZSTD_frontCompressDevice: the GPU hashes) — and batc
 plus who hashed the frames and whether the device frames equal the host path's with the setting on.
 
   python tools/device_bench.py --checksum --gib 1 --reps 3 [--levels 1,6,12] [--legs host,device,batch] [--no-compare]
+
+--group: byte grouping (QZSTD_frontSetByteGroup) on typed data — an N GiB bf16 tensor and an N GiB fp32 one of N(0, 0.02) weights (drawn on the
+GPU from a fixed seed).  Four legs, every run listed, grouping off and on alternating in one run:
+  off    QZSTD_frontCompressDevice, the setting 1
+  on     QZSTD_frontCompressDevice, the setting the element size (grouped on the GPU while staging, a block per plane)
+  torch  what a caller can do without the feature: a torch byte transposition of every frame on the GPU, then QZSTD_frontCompressDevice
+         with the setting 1 (grouped content, blocks every 128 KiB); the transposition is inside the window
+  host   t.cpu() + numpy grouping of every frame + QZSTD_frontCompress
+plus compressed sizes, the share of grouped frames by how they were built (QZSTD_frontByteGroupStats) and bytes device->host per input byte.
+--kernels: one untimed `on` pass per element size 2, 4, 8 (the same bytes seen as bf16, fp32, int64) and one `off` pass of an unaligned
+view (gathered) at level 1 and nothing else: the run to put under rocprofv3.
+
+  python tools/device_bench.py --group --gib 1 --reps 3 [--levels 1,6,12] [--legs off,on,torch,host] [--kernels]
 """
 import argparse
 import json
@@ -180,8 +193,90 @@ def checksum_main(a):
     print(json.dumps(out))
 
 
+def group_main(a):
+    import numpy as np
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    size = int(a.gib * (1 << 30)) & ~(a.chunk - 1)
+    n = size // a.chunk
+    torch.manual_seed(0)
+    if a.kernels:
+        t = (torch.randn(size // 2 + 8, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8)
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            stream = torch.cuda.current_stream().cuda_stream
+            for k in (2, 4, 8):
+                assert fr.set_byte_group(k) == 0 and fr.call_device(t.data_ptr(), size, stream)[0] == n
+            assert fr.set_byte_group(1) == 0 and fr.call_device(t.data_ptr() + 1, size, stream)[0] == n  # (unaligned: every part gathered)
+        finally:
+            fr.close()
+        print(json.dumps({"bytes": size, "passes": "group k=2, k=4, k=8, then gather; level 1; %d parts each" % (size >> 26)}))
+        return
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "data": {},
+           "timed": "library calls (+ the torch transposition / t.cpu() and numpy grouping), GB/s of input, every run of %d, legs alternating" % a.reps}
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        t = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt)
+        torch.cuda.synchronize()
+        res = out["data"][kind] = {"elem": k, "levels": {}}
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            try:
+                fr.reserve(size)
+                stream = torch.cuda.current_stream().cuda_stream
+
+                def off_pass():
+                    fr.set_byte_group(1)
+                    return fr.call_device(t.data_ptr(), size, stream)
+
+                def on_pass():
+                    fr.set_byte_group(k)
+                    return fr.call_device(t.data_ptr(), size, stream)
+
+                def torch_pass():
+                    fr.set_byte_group(1)
+                    g = t.view(torch.uint8).view(n, a.chunk // k, k).transpose(1, 2).contiguous()
+                    return fr.call_device(g.data_ptr(), size, stream)
+
+                def host_pass():
+                    fr.set_byte_group(1)
+                    h = t.cpu().view(torch.uint8).numpy().reshape(n, a.chunk // k, k)
+                    g = np.ascontiguousarray(h.transpose(0, 2, 1))
+                    return fr.call_host(g.ctypes.data, size)
+
+                legs = [x for x in (("off", off_pass), ("on", on_pass), ("torch", torch_pass), ("host", host_pass)) if x[0] in a.legs.split(",")]
+                cell = {name + "_gbps": [] for name, _ in legs}
+                for name, f in legs:  # untimed: first touch of the destination, the device slots, the pinned arenas
+                    r, sizes = f()
+                    assert r == n, name
+                    cell["compressed_" + name] = sum(sizes[c] for c in range(n))
+                g0 = fr.byte_group_stats()
+                for _ in range(a.reps):
+                    for name, f in legs:
+                        torch.cuda.synchronize()
+                        s0 = fr.stats()
+                        t0 = time.perf_counter()
+                        r, _ = f()
+                        dt_s = time.perf_counter() - t0
+                        assert r == n, "%s pass failed" % name
+                        cell[name + "_gbps"].append(round(size / dt_s / 1e9, 3))
+                        cell["d2h_bytes_per_input_byte_" + name] = round((fr.stats()[2] - s0[2]) / size, 4)
+                g1 = fr.byte_group_stats()
+                cell["grouped_frames_share"] = dict(zip(("sequences_and_literals", "rebuilt", "copied_back"),
+                                                        [round((x - y) / max(sum(g1) - sum(g0), 1), 4) for x, y in zip(g1, g0)]))
+                res["levels"][str(level)] = cell
+            finally:
+                fr.close()
+        del t
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--group", action="store_true")
+    ap.add_argument("--kernels", action="store_true", help="--group: the passes to trace, nothing timed")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--checksum", action="store_true")
     ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
@@ -194,6 +289,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.group:
+        if a.legs == "host,device,batch":
+            a.legs = "off,on,torch,host"
+        return group_main(a)
     if a.checksum:
         return checksum_main(a)
     if a.batch:

@@ -1,6 +1,8 @@
 """ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
-QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum), compress_tensor() for a contiguous GPU tensor of any dtype and compress_tensors()
-for a list of them in one call.
+QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped),
+compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
+each tensor's element size) and restore_tensor() for the way back; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
+ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
 
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
 import ctypes as C
@@ -26,6 +28,12 @@ class DeviceBuf(C.Structure):
 class GatherRow(C.Structure):
     """qzstd_hip_gather_row_t (include/qzstd_hip_device.h)"""
     _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class GroupRow(C.Structure):
+    """qzstd_hip_group_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32), ("elem", C.c_uint32),
+                ("reserved", C.c_uint32)]
 
 
 class HashRow(C.Structure):
@@ -60,7 +68,69 @@ def bind(F):
         F.QZSTD_frontGetChecksum.argtypes = [C.c_void_p]
         F.QZSTD_frontChecksumStats.restype = None
         F.QZSTD_frontChecksumStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontSetByteGroup"):  # (absent from an older library)
+        F.QZSTD_frontSetByteGroup.restype = C.c_int
+        F.QZSTD_frontSetByteGroup.argtypes = [C.c_void_p, C.c_uint]
+        F.QZSTD_frontGetByteGroup.restype = C.c_uint
+        F.QZSTD_frontGetByteGroup.argtypes = [C.c_void_p]
+        F.QZSTD_frontByteGroupStats.restype = None
+        F.QZSTD_frontByteGroupStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_frontCompressDeviceBatchTyped.restype = C.c_size_t
+        F.QZSTD_frontCompressDeviceBatchTyped.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                          C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        bind_bytegroup(F)
     return F
+
+
+def bind_bytegroup(L):
+    """include/qzstd_bytegroup.h on a loaded library (libqzstdfront, or qzstd_bytegroup.c built alone)"""
+    for fn in (L.QZSTD_byteGroup, L.QZSTD_byteUngroup):
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint]
+    L.QZSTD_byteGroupBlocks.restype = C.c_size_t
+    L.QZSTD_byteGroupBlocks.argtypes = [C.c_size_t, C.c_uint, C.POINTER(C.c_size_t), C.c_size_t]
+    return L
+
+
+_bytegroup_lib = None
+
+
+def _bg(lib):
+    global _bytegroup_lib
+    if lib is not None:
+        return lib
+    if _bytegroup_lib is None:
+        _bytegroup_lib = bind_bytegroup(B.Front().lib)
+    return _bytegroup_lib
+
+
+def _regroup(fn, data: bytes, k: int) -> bytes:
+    src = C.create_string_buffer(bytes(data), max(len(data), 1))
+    dst = C.create_string_buffer(max(len(data), 1))
+    if fn(dst, src, len(data), k) != len(data):
+        raise ValueError("element size %r: 1, 2, 4 or 8" % (k,))
+    return dst.raw[:len(data)]
+
+
+def group_bytes(data: bytes, k: int, lib=None) -> bytes:
+    """QZSTD_byteGroup: one frame's bytes in the byte-grouped layout for element size k"""
+    return _regroup(_bg(lib).QZSTD_byteGroup, data, k)
+
+
+def ungroup_bytes(data: bytes, k: int, lib=None) -> bytes:
+    """QZSTD_byteUngroup: the inverse of group_bytes"""
+    return _regroup(_bg(lib).QZSTD_byteUngroup, data, k)
+
+
+def group_blocks(n: int, k: int, lib=None) -> list:
+    """QZSTD_byteGroupBlocks: the block ends of a grouped frame of n bytes"""
+    L = _bg(lib)
+    cnt = L.QZSTD_byteGroupBlocks(n, k, None, 0)
+    if cnt == ERROR:
+        raise ValueError("element size %r: 1, 2, 4 or 8" % (k,))
+    ends = (C.c_size_t * max(cnt, 1))()
+    assert L.QZSTD_byteGroupBlocks(n, k, ends, cnt) == cnt
+    return list(ends[:cnt])
 
 
 class DeviceFront:
@@ -132,6 +202,25 @@ class DeviceFront:
         fr = self._frames(n, sizes)
         return r, [fr[first[i]:first[i + 1]] for i in range(nb)], list(first)
 
+    def compress_device_batch_typed_raw(self, ptrs_and_sizes, elem_sizes, stream: int | None = None):
+        """QZSTD_frontCompressDeviceBatchTyped -> (return value, per buffer its list of frames or None); elem_sizes: one of 0 (the front's
+        setting), 1, 2, 4, 8 per buffer, or None"""
+        bufs, nb, n = self.batch(ptrs_and_sizes)
+        _, sizes = self._frame_buffers(n)
+        first = (C.c_size_t * (nb + 1))()
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        r = self.lib.QZSTD_frontCompressDeviceBatchTyped(self.f, bufs, es, nb, C.c_void_p(stream or None), self._dst, len(self._dst), sizes, first)
+        if r != n:
+            return r, None
+        fr = self._frames(n, sizes)
+        return r, [fr[first[i]:first[i + 1]] for i in range(nb)]
+
+    def compress_device_batch_typed(self, ptrs_and_sizes, elem_sizes, stream: int | None = None) -> list:
+        r, frames = self.compress_device_batch_typed_raw(ptrs_and_sizes, elem_sizes, stream)
+        if frames is None:
+            raise RuntimeError("QZSTD_frontCompressDeviceBatchTyped failed (%d)" % (r if r != ERROR else -1))
+        return frames
+
     def compress_device_batch(self, ptrs_and_sizes, stream: int | None = None) -> list:
         """frames of every buffer of [(device address, bytes), ...], a list of lists: one QZSTD_frontCompressDeviceBatch call"""
         r, frames, _ = self.compress_device_batch_raw(ptrs_and_sizes, stream)
@@ -184,6 +273,20 @@ class DeviceFront:
         self.lib.QZSTD_frontChecksumStats(self.f, st)
         return list(st)
 
+    def set_byte_group(self, k: int) -> int:
+        """QZSTD_frontSetByteGroup: the element size (1: off, 2, 4, 8) of every device call that follows -> 0, or -1 (another value, or
+        while a call runs)"""
+        return self.lib.QZSTD_frontSetByteGroup(self.f, k)
+
+    def get_byte_group(self) -> int:
+        return self.lib.QZSTD_frontGetByteGroup(self.f)
+
+    def byte_group_stats(self) -> list:
+        """byte-grouped frames built from [0] sequences + literals, [1] rebuilt content, [2] copied-back content"""
+        st = (C.c_ulonglong * 3)()
+        self.lib.QZSTD_frontByteGroupStats(self.f, st)
+        return list(st)
+
     def close(self):
         if self.f:
             self.lib.QZSTD_freeFront(self.f)
@@ -201,10 +304,18 @@ def compress_tensor(front: DeviceFront, t, stream=None) -> list:
     return front.compress_device(t.data_ptr(), t.numel() * t.element_size(), handle)
 
 
-def compress_tensors(front: DeviceFront, tensors, stream=None) -> list:
+def element_group(t) -> int:
+    """the byte-group element size of a tensor: its element size when that is 2, 4 or 8, else 1"""
+    return t.element_size() if t.element_size() in (2, 4, 8) else 1
+
+
+def compress_tensors(front: DeviceFront, tensors, stream=None, group=None) -> list:
     """per tensor the frames of its bytes, all tensors in ONE call (QZSTD_frontCompressDeviceBatch): contiguous GPU tensors of any dtypes
     and sizes, views with a storage offset included, all on one device.  `stream`: the torch.cuda.Stream (or raw hipStream_t) that
-    produced them; default: the current stream of their device."""
+    produced them; default: the current stream of their device.  group="dtype": every tensor byte-grouped by its own element size
+    (QZSTD_frontCompressDeviceBatchTyped; restore_tensor() undoes it); None: the front's setting."""
+    if group not in (None, "dtype"):
+        raise ValueError("compress_tensors: group is None or \"dtype\"")
     tensors = list(tensors)
     for t in tensors:
         if not t.is_cuda or not t.is_contiguous():
@@ -216,7 +327,27 @@ def compress_tensors(front: DeviceFront, tensors, stream=None) -> list:
     if stream is None:
         stream = torch.cuda.current_stream(tensors[0].device)
     handle = getattr(stream, "cuda_stream", stream)
-    return front.compress_device_batch([(t.data_ptr(), t.numel() * t.element_size()) for t in tensors], handle)
+    bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
+    if group == "dtype":
+        return front.compress_device_batch_typed(bufs, [element_group(t) for t in tensors], handle)
+    return front.compress_device_batch(bufs, handle)
+
+
+def restore_tensor(frames, dtype, shape, k: int, device=None, zstd=None, lib=None):
+    """the tensor whose byte-grouped frames (element size k, as compress_tensors(group="dtype") built them) these are: every frame decoded
+    on the host, ungrouped (the layout follows from the frame's content size and k), the bytes uploaded to `device`"""
+    import math
+    z = zstd or B.Zstd()
+    left = math.prod(shape) * torch.empty((), dtype=dtype).element_size()
+    out = bytearray()
+    for fr in frames:
+        content = z.decompress(fr, left)
+        out += ungroup_bytes(content, k, lib)
+        left -= len(content)
+    if left != 0:
+        raise ValueError("restore_tensor: the frames hold %d bytes fewer than the shape needs" % left)
+    t = torch.frombuffer(out, dtype=torch.uint8).view(dtype).reshape(shape) if out else torch.empty(shape, dtype=dtype)
+    return t.to(device) if device is not None else t.clone()
 
 
 def reference_frames(zstd, oracle, data: bytes, chunk: int, level: int, ext_rep: bool = False) -> list:
@@ -235,3 +366,79 @@ def reference_frames(zstd, oracle, data: bytes, chunk: int, level: int, ext_rep:
     finally:
         zstd.free(zc)
         del prof
+
+
+def typed_corpus(kind: str, nbytes: int, seed: int = 0) -> bytes:
+    """seeded typed data, nbytes of it: "bf16" / "fp16" / "fp32" N(0, 0.02) weights, "ids32" Zipf token ids (int32), "ids64" ascending
+    ids (int64, random small steps)"""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    if kind in ("bf16", "fp16", "fp32"):
+        size = {"bf16": 2, "fp16": 2, "fp32": 4}[kind]
+        w = rng.normal(0.0, 0.02, (nbytes + size - 1) // size).astype(np.float32)
+        if kind == "bf16":
+            raw = (w.view(np.uint32) >> 16).astype(np.uint16).tobytes()
+        else:
+            raw = w.astype(np.float16).tobytes() if kind == "fp16" else w.tobytes()
+    elif kind == "ids32":
+        raw = np.minimum(rng.zipf(1.2, (nbytes + 3) // 4), 50000).astype(np.int32).tobytes()
+    elif kind == "ids64":
+        raw = np.cumsum(rng.integers(1, 40, (nbytes + 7) // 8)).astype(np.int64).tobytes()
+    else:
+        raise ValueError(kind)
+    return raw[:nbytes]
+
+
+def blocks_with_cuts(n: int, k: int, cut: bool) -> list:
+    """block ends of a grouped frame of n bytes with the plane cuts forced on or off, whatever QZSTD_BYTEGROUP_CUT_MIN says (measurements)"""
+    pieces = [((j * (n // k)) & ~15) for j in range(1, k)] if cut and k > 1 else []
+    ends, start = [], 0
+    for piece_end in pieces + [n]:
+        while start < piece_end:
+            start = min(start + 131072, piece_end)
+            ends.append(start)
+    return ends
+
+
+def reference_frames_grouped(zstd, oracle, data: bytes, chunk: int, level: int, k: int, checksum: bool = False, lib=None,
+                             counts: dict | None = None, cut: bool | None = None) -> list:
+    """what the device calls must produce with element size k: per frame (chunk) group_bytes, the ORACLE's sequences for each block of
+    group_blocks (every block matched on its own, the last entry its delimiter), then ZSTD_compressSequences with explicit block delimiters
+    and sequence validation on a context with the workers' parameters (the level; checksum: ZSTD_c_checksumFlag).  counts: a dict that
+    receives "blocks" and "entries" (sequences, delimiters included) of all frames; cut: None for the library's block rule, True / False to
+    force the plane cuts on / off (measurements: blocks_with_cuts)"""
+    L = zstd.lib
+    L.ZSTD_compressSequences.restype = C.c_size_t
+    L.ZSTD_compressSequences.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(B.Sequence), C.c_size_t, C.c_void_p, C.c_size_t]
+    blk = min(chunk, 131072)
+    prof = oracle.profile(level, blk)
+    cap = B.sequence_bound(blk)
+    # (a producer is registered, as on the workers' contexts, though ZSTD_compressSequences never calls it: with one, libzstd's validation
+    # admits matches of 3 bytes at every level, which the chain levels' profiles produce)
+    zc = zstd.cctx(level, producer=oracle.producer_addr, state=None, fallback=True, validate=True, checksumFlag=1 if checksum else 0)
+    zstd.set(zc, 1008, 1)  # ZSTD_c_blockDelimiters = ZSTD_sf_explicitBlockDelimiters
+    out = []
+    try:
+        dst = C.create_string_buffer(L.ZSTD_compressBound(chunk))
+        for o in range(0, len(data), chunk):
+            g = group_bytes(data[o:o + chunk], k, lib)
+            seqs, start = [], 0
+            for end in (group_blocks(len(g), k, lib) if cut is None else blocks_with_cuts(len(g), k, cut)):
+                n, sq = oracle.find(prof, g[start:end], cap=cap)
+                if n == B.SEQ_ERROR:
+                    raise RuntimeError("the oracle failed a block")
+                seqs += [(s.offset, s.litLength, s.matchLength, 0) for s in sq[:n]]
+                start = end
+                if counts is not None:
+                    counts["blocks"] = counts.get("blocks", 0) + 1
+                    counts["entries"] = counts.get("entries", 0) + n
+            arr = (B.Sequence * max(len(seqs), 1))(*seqs)
+            src = C.create_string_buffer(g, max(len(g), 1))
+            L.ZSTD_CCtx_reset(zc, 1)  # ZSTD_reset_session_only
+            r = L.ZSTD_compressSequences(zc, dst, len(dst), arr, len(seqs), src, len(g))
+            if zstd.is_error(r):
+                raise RuntimeError("ZSTD_compressSequences: " + zstd.err(r))
+            out.append(dst.raw[:r])
+    finally:
+        zstd.free(zc)
+    return out
