@@ -1,6 +1,6 @@
 /*
  * qzstd_frontend_device.h — the batch front-end's way in for DEVICE-RESIDENT input (a GPU tensor, any HIP allocation): the input is
- * never copied to the host; exported by libqzstdfront next to the calls of qzstd_frontend.h, which includes this header (its own
+ * never copied to the host — and the way back, frames restored into device buffers; exported by libqzstdfront next to the calls of qzstd_frontend.h, which includes this header (its own
  * declarations stay what they were).
  */
 #ifndef QZSTD_FRONTEND_DEVICE_H
@@ -74,7 +74,8 @@ void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2]);
  * their own gives each its own entropy tables.  1 (the default): off, every frame byte for byte what it was.  The grouping happens on the
  * GPU while a part is staged (qzstd_hip_group): no extra pass, no host copy.  A frame is an ordinary zstd frame OF THE GROUPED CONTENT: the
  * element size is not stored in it — the caller keeps it — and the layout follows from the frame's content size and elemSize alone; a
- * reader decodes the frame and calls QZSTD_byteUngroup.  Checksums (QZSTD_frontSetChecksum) cover the grouped content, which is what a decoder
+ * reader either hands the frames to QZSTD_frontRestoreDeviceBatchTyped with the same element sizes (below: decoded by the front's workers,
+ * ungrouped on the GPU), or decodes a frame itself and calls QZSTD_byteUngroup on the host.  Checksums (QZSTD_frontSetChecksum) cover the grouped content, which is what a decoder
  * verifies.  Frame counts, strides and QZSTD_frontDeviceBatchFrames are unchanged.
  * A grouped frame whose content libzstd needs (a block it stores raw — a mantissa plane — is the rule here) gets it rebuilt on the host
  * from the frame's own sequences and literals, already in the arena: no second device->host copy.  Only a frame with a block the matcher
@@ -92,6 +93,45 @@ size_t QZSTD_frontCompressDeviceBatchTyped(QZSTD_Front *f, const QZSTD_DeviceBuf
 /* since creation, byte-grouped frames (element size above 1) built from [0] sequences + literals, [1] content rebuilt from the arena,
  * [2] content copied back from the device and grouped on the host */
 void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3]);
+
+/* The way back: frames in HOST memory restored into device buffers, in ONE call.  Frame c lies at frames + c * frameStride, its size in
+ * frameSizes[c] — what the compress calls leave with frameStride = QZSTD_frontFrameStride(); with frameStride == 0 it lies at the sum of the
+ * sizes before it, which is what QZSTD_frontCompact leaves.  Buffer i receives frames firstFrame[i] .. firstFrame[i + 1] - 1 under the compress
+ * calls' own rule (ceil(size_i / chunkSize) frames, none for an empty buffer); nFrames must equal QZSTD_frontDeviceBatchFrames of the same
+ * sizes.  elemSizes: as QZSTD_frontCompressDeviceBatchTyped's (1, 2, 4, 8, or 0 for the front's setting; NULL: all 0; anything else is refused) —
+ * the values the frames were written with, which the caller keeps.
+ *
+ * A frame is ANY valid zstd frame whose content is the (byte-grouped) chunk: one of this library's, or one built by ZSTD_compress2 over
+ * QZSTD_byteGroup's output.  Every frame is decoded with capacity = the chunk's expected length and must yield exactly that; the header's
+ * content-size field is not relied on.  libzstd verifies a content checksum where a frame carries one, whatever QZSTD_frontSetChecksum says.
+ *
+ * The call is cut into parts of whole frames (at most 64 MiB of content, $QZSTD_FRONT_DEVICE_PART as on the compress side).  The front's
+ * workers, each with a ZSTD_DCtx of its own, decode a part into one of two pinned buffers kept with the front, every frame at a 16-aligned
+ * offset; one host->device copy and one qzstd_hip_ungroup launch (the frames scattered to their buffers at any alignment, the grouped layout
+ * undone on the way, exactly the buffers' bytes written) follow on a stream of the library's, while the workers decode the next part into the
+ * other buffer.  `stream`: the hipStream_t that orders the last user of the buffers (NULL = the default stream): nothing is written before
+ * the work queued on it so far completes.  Blocks until done.
+ *
+ * Returns nFrames (0 for no buffers or empty ones: no GPU is touched) or (size_t)-1.  Before anything is queued: f NULL, bufs NULL with
+ * nBufs > 0, a NULL buffer of a size above 0, a bad elemSizes entry, a wrong nFrames, frames or frameSizes NULL with nFrames > 0, a buffer
+ * whose first or last byte is not device memory, buffers of different devices, a call while another one runs on this front, a device layer
+ * without qzstd_hip_ungroup.  After work has started: a frame that does not decode, decodes to another length than its chunk's or fails its
+ * checksum — the buffers' contents are then unspecified, but nothing outside them was written, and nothing of the library's is still running
+ * on the GPU when the call returns.
+ * The restore needs nothing of the producer: a front created with useProducer = 0 (no match-finder service is started) is accepted.
+ * The compress calls, their frames and their stats are not affected. */
+typedef struct {
+    void *d_ptr; /* device address, any alignment */
+    size_t size; /* bytes, may be 0 */
+} QZSTD_DeviceOutBuf;
+size_t QZSTD_frontRestoreDeviceBatchTyped(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                          const QZSTD_DeviceOutBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream);
+/* one buffer, the front's element size (QZSTD_frontSetByteGroup) */
+size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                void *d_dst, size_t dstSize, void *stream);
+/* since creation, of the parts that were queued: [0] frames decoded, [1] bytes of content, [2] bytes copied host->device (the frames at
+ * 16-aligned offsets), [3] qzstd_hip_ungroup launches (one per part) */
+void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4]);
 
 #if defined(__cplusplus)
 }

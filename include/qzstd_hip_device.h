@@ -1,7 +1,8 @@
 /*
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
- * (QZSTD_frontCompressDeviceBatch) and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
+ * and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -97,6 +98,38 @@ typedef struct {
 } qzstd_hip_group_row_t;
 int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
                     void *d_stage, size_t stageBytes);
+
+/*
+ * Ungrouping scatter, the inverse of qzstd_hip_group: ONE launch copies every row out of a 16-aligned staging buffer to its destination
+ * anywhere in device memory and undoes the byte-grouped layout of include/qzstd_bytegroup.h on the way — for k = elem and n = len / k,
+ * dst[e * k + j] = stage[srcOff + j * n + e] for e < n, and the len - n * k tail bytes are copied unchanged.  elem = 1 rows are a plain scatter.
+ *
+ * EXACTLY the bytes [dst, dst + len) of every row are written, each once, and no other byte of device memory: the 16-byte words that lie
+ * wholly inside a row leave as aligned 16-byte stores, the up to 15 bytes in front of the first such word and behind the last as single
+ * bytes, and the destination is never read — two rows of one launch may be neighbours in memory and share a 16-byte word (tensor views
+ * packed back to back) without a race between their workgroups.  dst may have ANY alignment, also one that is no multiple of elem.
+ *
+ * A workgroup takes 16 KiB of ONE row's destination (an element range) across all `elem` planes: the plane strips of that range come from the
+ * stage into LDS (aligned 16-byte loads inside [srcOff, srcOff + pad16(len)) of the row and nowhere else; the bytes between len and
+ * pad16(len) may be loaded and are never looked at), and every destination word — it belongs to the element range of its FIRST byte — is
+ * assembled from the strips by one lane; the owner of a word that reaches into the next element range or the tail fetches those few bytes
+ * itself.  No atomics.  Rows of one byte and rows of many MiB go in one launch.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous) and must stay unchanged until the stream has passed the call; the
+ * launcher checks it and uploads it to d_rows, device scratch of nRows entries.  Refused (< 0) before anything is queued: a null rows,
+ * d_rows or d_stage, d_stage not 16-aligned, a srcOff that is no multiple of 16, an elem outside {1, 2, 4, 8}, a null dst with len > 0, a row
+ * that ends past stageBytes, rows that are not in ascending stage order or overlap there (srcOff[i] >= srcOff[i-1] + pad16(len[i-1])), a
+ * stage span of 64 GiB or more, more than 2^31 - 1 tiles between the first row's and the last row's.  Destinations that overlap each other
+ * or the stage are the caller's error and are not checked.  nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t dst;    /* device address of the row's first byte, any alignment */
+    uint64_t srcOff; /* byte offset of the row in d_stage, a multiple of 16 */
+    uint32_t len;    /* bytes, may be 0 */
+    uint32_t elem;   /* element size: 1, 2, 4 or 8; the row lies in the stage in the grouped layout for k = elem */
+} qzstd_hip_ungroup_row_t;
+int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
+                      const void *d_stage, size_t stageBytes);
 
 /*
  * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a

@@ -1,7 +1,8 @@
 /*
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
- * gather for typed rows, and the XXH64 content checksum.  They use nothing of the match-finder (qzstd_kernels.hip).
+ * gather for typed rows and the ungrouping scatter that undoes it, and the XXH64 content checksum.  They use nothing of the match-finder
+ * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
 
@@ -469,6 +470,210 @@ extern "C" int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_r
     hipLaunchKernelGGL(qzstd_group_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- ungrouping scatter (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kUngroupT = 256u;                 /* threads per workgroup */
+constexpr uint32_t kUngroupTileLog = kGroupTileLog;  /* destination bytes of one row per workgroup: 16 KiB, 16 KiB / elem elements */
+constexpr uint32_t kUngroupTile = 1u << kUngroupTileLog;
+constexpr uint32_t kUngroupSlack = 48u;              /* bytes behind each plane strip in LDS: the strip's one extra stage word (a strip starts anywhere
+                                                        in its first word) and the aligned reads of a destination word's last elements */
+constexpr uint32_t kUngroupLds = kUngroupTile + 8u * kUngroupSlack;
+
+/* byte p (< len) of the row as the destination holds it, by one aligned 16-byte load of the stage word that holds it in the grouped layout:
+ * the bytes a destination word needs from outside its owner's tile, and the bytes in front of and behind a row's whole words */
+__device__ inline uint32_t ungroup_byte(const uint8_t *__restrict__ stageRow, uint32_t n, uint32_t kLog, uint32_t p)
+{
+    uint64_t s = p;
+    if (p < ((uint64_t)n << kLog)) s = (uint64_t)(p & ((1u << kLog) - 1u)) * n + (p >> kLog);
+    const uint32_t sh = (uint32_t)s & 15u;
+    const uint4 v = *reinterpret_cast<const uint4 *>(stageRow + (s - sh));
+    const uint32_t d = sh < 8u ? (sh < 4u ? v.x : v.y) : (sh < 12u ? v.z : v.w);
+    return (d >> ((sh & 3u) * 8u)) & 0xFFu;
+}
+
+/* 16 / K bytes of a plane strip in LDS from byte `at` on (any alignment), in the low bytes of the result: aligned reads, shifted.  K = 8: the
+ * two bytes wanted and two more that nobody looks at */
+template <uint32_t K> __device__ inline uint64_t ungroup_strip(const uint8_t *strip, uint32_t at)
+{
+    if constexpr (K == 2u) {
+        const uint32_t q = at & ~7u, bits = (at & 7u) * 8u;
+        const uint64_t lo = *reinterpret_cast<const uint64_t *>(strip + q), hi = *reinterpret_cast<const uint64_t *>(strip + q + 8u);
+        return bits ? (lo >> bits) | (hi << (64u - bits)) : lo;
+    } else {
+        const uint32_t q = at & ~3u;
+        const uint64_t both = *reinterpret_cast<const uint32_t *>(strip + q) | (uint64_t)*reinterpret_cast<const uint32_t *>(strip + q + 4u) << 32;
+        return (uint32_t)(both >> ((at & 3u) * 8u));
+    }
+}
+
+/* The 16 destination bytes at row offset o (any phase inside an element), from the tile's plane strips in LDS.  Byte i of the word is byte
+ * (ph + i) % K of element o / K + (ph + i) / K, ph = o % K: plane j = (jj + ph) % K gives the word's bytes jj, jj + K, jj + 2 K, ..., which lie
+ * side by side in its strip from element o / K (+ 1 for the planes below ph) on.  Every plane is read once, 16 / K bytes wide, and the bytes are
+ * interleaved by v_perm_b32 (byte selects 0-3: the second operand, 4-7: the first), not one by one.  Plane j's strip lies at strip 0 +
+ * j * pitch and starts (j * n + e0) & 15 bytes into its first word, as it does in the stage. */
+template <uint32_t K> __device__ inline uint4 ungroup_word(const uint8_t *lds, uint32_t n, uint32_t e0, uint32_t o)
+{
+    constexpr uint32_t pitch = kUngroupTile / K + kUngroupSlack;
+    const uint32_t ph = o & (K - 1u), e = o / K - e0;
+    uint64_t q[K];
+#pragma unroll
+    for (uint32_t jj = 0; jj < K; jj++) {
+        const uint32_t j = (jj + ph) & (K - 1u);
+        const uint32_t at = (uint32_t)(((uint64_t)j * n + e0) & 15u) + e + (j < ph ? 1u : 0u);
+        q[jj] = ungroup_strip<K>(lds + j * pitch, at);
+    }
+    constexpr uint32_t lo01 = 0x05010400u, hi01 = 0x07030602u; /* {b0 a0 b1 a1}, {b2 a2 b3 a3} of perm(a, b) */
+    constexpr uint32_t lo16 = 0x05040100u, hi16 = 0x07060302u; /* {b0 b1 a0 a1}, {b2 b3 a2 a3} */
+    if constexpr (K == 2u) {
+        const uint32_t a0 = (uint32_t)q[0], a1 = (uint32_t)(q[0] >> 32), b0 = (uint32_t)q[1], b1 = (uint32_t)(q[1] >> 32);
+        return make_uint4(__builtin_amdgcn_perm(b0, a0, lo01), __builtin_amdgcn_perm(b0, a0, hi01), __builtin_amdgcn_perm(b1, a1, lo01),
+                          __builtin_amdgcn_perm(b1, a1, hi01));
+    } else if constexpr (K == 4u) {
+        const uint32_t t0 = __builtin_amdgcn_perm((uint32_t)q[1], (uint32_t)q[0], lo01), t1 = __builtin_amdgcn_perm((uint32_t)q[1], (uint32_t)q[0], hi01);
+        const uint32_t u0 = __builtin_amdgcn_perm((uint32_t)q[3], (uint32_t)q[2], lo01), u1 = __builtin_amdgcn_perm((uint32_t)q[3], (uint32_t)q[2], hi01);
+        return make_uint4(__builtin_amdgcn_perm(u0, t0, lo16), __builtin_amdgcn_perm(u0, t0, hi16), __builtin_amdgcn_perm(u1, t1, lo16),
+                          __builtin_amdgcn_perm(u1, t1, hi16));
+    } else {
+        const uint32_t a01 = __builtin_amdgcn_perm((uint32_t)q[1], (uint32_t)q[0], lo01), a23 = __builtin_amdgcn_perm((uint32_t)q[3], (uint32_t)q[2], lo01);
+        const uint32_t a45 = __builtin_amdgcn_perm((uint32_t)q[5], (uint32_t)q[4], lo01), a67 = __builtin_amdgcn_perm((uint32_t)q[7], (uint32_t)q[6], lo01);
+        return make_uint4(__builtin_amdgcn_perm(a23, a01, lo16), __builtin_amdgcn_perm(a67, a45, lo16), __builtin_amdgcn_perm(a23, a01, hi16),
+                          __builtin_amdgcn_perm(a67, a45, hi16));
+    }
+}
+
+/* K = 1: the strip is the row; two aligned 16-byte reads shifted, as the group kernel's */
+template <> __device__ inline uint4 ungroup_word<1u>(const uint8_t *lds, uint32_t n, uint32_t e0, uint32_t o)
+{
+    const uint32_t at = (e0 & 15u) + (o - e0), q = at & ~15u, sh = at & 15u;
+    const uint4 l = *reinterpret_cast<const uint4 *>(lds + q);
+    uint4 h = make_uint4(0u, 0u, 0u, 0u);
+    if (sh) h = *reinterpret_cast<const uint4 *>(lds + q + 16u);
+    uint64_t o0, o1;
+    group_shift(l, h, sh, &o0, &o1);
+    (void)n;
+    return make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+}
+
+/* A: the tile's K plane strips, stage words (aligned 16-byte loads) to LDS as they lie in the stage; B, behind the barrier: the tile's
+ * destination words, assembled and stored.  One function of the thread's index for both, so that the kernel's body reads as its two phases. */
+__device__ inline void ungroup_load(const uint8_t *__restrict__ stageRow, uint32_t n, uint32_t kLog, uint32_t e0, uint32_t tileElems, uint8_t *lds,
+                                    uint32_t tid)
+{
+    const uint32_t stripLog = kUngroupTileLog - 4u - kLog, stripWords = 1u << stripLog; /* a strip without its extra word */
+    const uint32_t pitch = (kUngroupTile >> kLog) + kUngroupSlack;
+    if (!tileElems) return;
+#pragma unroll
+    for (uint32_t u = 0; u < kUngroupTile / 16u / kUngroupT; u++) {
+        const uint32_t idx = tid + u * kUngroupT, j = idx >> stripLog, i = idx & (stripWords - 1u);
+        const uint64_t s0 = (uint64_t)j * n + e0;
+        if (i < (((uint32_t)s0 & 15u) + tileElems + 15u) >> 4)
+            *reinterpret_cast<uint4 *>(lds + j * pitch + i * 16u) = *reinterpret_cast<const uint4 *>(stageRow + ((s0 >> 4) + i) * 16u);
+    }
+    if (tid < (1u << kLog)) { /* the extra word of a full strip that does not start on a word */
+        const uint64_t s0 = (uint64_t)tid * n + e0;
+        if ((((uint32_t)s0 & 15u) + tileElems + 15u) >> 4 > stripWords)
+            *reinterpret_cast<uint4 *>(lds + tid * pitch + stripWords * 16u) = *reinterpret_cast<const uint4 *>(stageRow + ((s0 >> 4) + stripWords) * 16u);
+    }
+}
+
+__device__ inline void ungroup_store(const qzstd_hip_ungroup_row_t &row, const uint8_t *__restrict__ stageRow, uint32_t n, uint32_t kLog, uint32_t e0,
+                                     uint32_t tileElems, bool first, bool last, const uint8_t *lds, uint32_t tid)
+{
+    uint8_t *dst = reinterpret_cast<uint8_t *>(row.dst);
+    /* the row's whole destination words: `words` of them from row offset `head` on; in front of them and behind them single bytes */
+    const uint32_t lead = (uint32_t)(0u - row.dst) & 15u, head = lead < row.len ? lead : row.len;
+    const uint32_t words = (row.len - head) >> 4;
+    const uint64_t t0 = (uint64_t)e0 << kLog, lim = (uint64_t)(e0 + tileElems) << kLog; /* the tile's bytes of the row: what its strips hold */
+    const uint64_t t1 = last ? row.len : lim; /* a word belongs to the tile of its FIRST byte; the tail behind the elements to the last tile */
+    for (uint64_t i = (t0 <= head ? 0u : (t0 - head + 15u) >> 4) + tid; i < words && head + i * 16u < t1; i += kUngroupT) {
+        const uint32_t o = head + (uint32_t)i * 16u;
+        uint4 v;
+        switch (kLog) {
+        case 0u: v = ungroup_word<1u>(lds, n, e0, o); break;
+        case 1u: v = ungroup_word<2u>(lds, n, e0, o); break;
+        case 2u: v = ungroup_word<4u>(lds, n, e0, o); break;
+        default: v = ungroup_word<8u>(lds, n, e0, o); break;
+        }
+        if (lim - o < 16u) { /* the word reaches into the next tile or the tail: those bytes one by one, from the stage */
+            uint32_t d[4] = { v.x, v.y, v.z, v.w };
+            for (uint32_t b = (uint32_t)(lim - o); b < 16u; b++)
+                d[b >> 2] = (d[b >> 2] & ~(0xFFu << ((b & 3u) * 8u))) | ungroup_byte(stageRow, n, kLog, o + b) << ((b & 3u) * 8u);
+            v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        *reinterpret_cast<uint4 *>(dst + o) = v;
+    }
+    if (first && tid < head) dst[tid] = (uint8_t)ungroup_byte(stageRow, n, kLog, tid);
+    if (last) {
+        const uint32_t from = head + words * 16u;
+        if (tid < row.len - from) dst[from + tid] = (uint8_t)ungroup_byte(stageRow, n, kLog, from + tid);
+    }
+}
+
+/* One workgroup per tile: elements [e0, e0 + tileElems) of one row — 16 KiB of its destination — in the launch numbering of
+ * qzstd_group_kernel with srcOff in dstOff's place.  No destination byte is read, none is written twice, none outside [dst, dst + len). */
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_kernel(const qzstd_hip_ungroup_row_t *__restrict__ rows, uint32_t nRows, uint64_t firstTile,
+                                                                   const uint8_t *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which;
+    const uint64_t v = firstTile + blockIdx.x;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if ((rows[mid].srcOff >> kUngroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_ungroup_row_t row = rows[r];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
+    const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (row.len ? 1ull : 0ull);
+    const uint64_t t = v - ((row.srcOff >> kUngroupTileLog) + r);
+    if (t >= tiles) return; /* (the whole workgroup) */
+    const uint32_t e0 = (uint32_t)t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint8_t *stageRow = stage + row.srcOff;
+    ungroup_load(stageRow, n, kLog, e0, tileElems, lds, threadIdx.x);
+    __syncthreads();
+    ungroup_store(row, stageRow, n, kLog, e0, tileElems, t == 0, t + 1u == tiles, lds, threadIdx.x);
+}
+} // namespace
+
+extern "C" int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
+                                 const void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ungroup_row_t &r = rows[i];
+        const uint64_t ext = ((uint64_t)r.len + 15u) & ~(uint64_t)15u;
+        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup: elem not 1, 2, 4 or 8");
+        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup: srcOff not a multiple of 16");
+        if (r.len && !r.dst) return fail_msg("qzstd_hip_ungroup: null destination");
+        if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup: rows overlap in the stage or are not in ascending order");
+        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup: a row ends past stageBytes");
+        end = r.srcOff + ext;
+        if (r.len) { /* the row's tiles in the launch's numbering (qzstd_ungroup_kernel) */
+            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
+            endTile = (r.srcOff >> kUngroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].srcOff >> kUngroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup rows)");
+    hipLaunchKernelGGL(qzstd_ungroup_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+                       static_cast<const uint8_t *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_kernel");
     return 0;
 }
 

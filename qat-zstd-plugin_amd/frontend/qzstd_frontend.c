@@ -46,11 +46,14 @@ typedef struct {
     size_t *ends;
     size_t endsCap;
     unsigned char *back;
+    ZSTD_DCtx *zd; /* the restore calls' decoder, created by the worker's first restore job */
 } QF_Worker;
 
 typedef struct QF_DevPart_s QF_DevPart;
 typedef struct QF_DevSlot_s QF_DevSlot;
+typedef struct QF_RestoreSlot_s QF_RestoreSlot;
 static void qfDevSlotsFree(QZSTD_Front *f);
+static void qfRestoreSlotsFree(QZSTD_Front *f);
 
 struct QZSTD_Front_s {
     QZSTD_FrontParams p;
@@ -81,6 +84,12 @@ struct QZSTD_Front_s {
     /* byte grouping (QZSTD_frontSetByteGroup): the element size of the device calls (1: off), and grouped frames by how they were built */
     unsigned group;
     unsigned long long groupStats[3];
+    /* the restore calls (qzstd_restore.c): the part the workers decode (NULL: a compress job), the counters, and two slots kept from call to
+     * call (pinned buffer, device stage, stream) for device restoreSlotDev */
+    const struct QF_RestorePart_s *restore;
+    unsigned long long restoreStats[4];
+    QF_RestoreSlot *restoreSlot;
+    int restoreSlotDev;
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -133,6 +142,7 @@ static void qfAnnounce(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 }
 
 static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c);
+static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg);
 
 /* ZSTD_c_checksumFlag on the worker's context.  The parameter outlives ZSTD_reset_session_only, so every path that builds a frame names
  * the value it needs and no frame inherits the one before it; the context is only touched when the value changes (never, with the
@@ -149,6 +159,7 @@ static int qfCtxChecksum(QF_Worker *w, int on)
 static int qfCompressSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 {
     size_t c;
+    if (f->restore) return qfRestoreSegment(f, w, sg);
     if (f->part) {
         for (c = sg->c0; c < sg->c1; c++)
             if (qfDeviceFrame(f, w, c) != 0) return -1;
@@ -188,7 +199,7 @@ static void *qfWorker(void *arg)
                 more = qfClaim(f, claims, &q[n]);
                 if (!more) break;
                 claims++;
-                if (!bad && !f->part) qfAnnounce(f, w, &q[n]);
+                if (!bad && !f->part && !f->restore) qfAnnounce(f, w, &q[n]);
                 n++;
             }
             if (n == 0) break;
@@ -353,6 +364,7 @@ void QZSTD_freeFront(QZSTD_Front *f)
         QF_Worker *w = &f->w[t];
         if (w->ok) pthread_join(w->th, NULL);
         if (w->zc) ZSTD_freeCCtx(w->zc);
+        if (w->zd) ZSTD_freeDCtx(w->zd);
         if (w->state) QZSTD_freeSeqProdState(w->state);
         free(w->seqs);
         free(w->ends);
@@ -361,6 +373,7 @@ void QZSTD_freeFront(QZSTD_Front *f)
         if (w->rawStream) qzstd_hip_stream_destroy(w->rawDev, w->rawStream);
     }
     qfDevSlotsFree(f);
+    qfRestoreSlotsFree(f);
     free(f->w);
     pthread_mutex_destroy(&f->mu);
     pthread_cond_destroy(&f->cvWork);
@@ -1154,3 +1167,6 @@ void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3])
 /* The byte-grouped layout, its block rule and qzbgRebuild: a source of their own, free of HIP and libzstd (the tests build it alone), and
  * part of this translation unit so that the front-end stays ONE source to whoever builds it. */
 #include "qzstd_bytegroup.c"
+
+/* The restore calls: a source of their own that uses this file's types and helpers, and part of this translation unit for the same reason. */
+#include "qzstd_restore.c"

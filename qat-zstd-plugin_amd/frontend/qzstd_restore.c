@@ -1,0 +1,240 @@
+/*
+ * qzstd_restore.c — the way back of the device calls (include/qzstd_frontend_device.h: QZSTD_frontRestoreDeviceBatchTyped,
+ * QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats): zstd frames in host memory, decoded by the front's workers and scattered into device
+ * buffers, the byte-grouped layout undone on the GPU.  Part of qzstd_frontend.c's translation unit (it is included at that file's end and
+ * uses its types and helpers), so that the front-end stays ONE source to whoever builds it.
+ *
+ * The frames of a call are cut into PARTS of whole frames (at most QF_PART_BYTES of content, $QZSTD_FRONT_DEVICE_PART as on the compress
+ * side).  Per part, on one of two restore slots (pinned host buffer + device stage + stream, kept with the front between calls):
+ *   - the workers decode the part's frames into the slot's pinned buffer, every frame at a 16-aligned offset, each worker with a ZSTD_DCtx
+ *     of its own (created on first use); a frame must decode to exactly its chunk's length;
+ *   - the calling thread queues ONE host->device copy of the buffer and ONE qzstd_hip_ungroup launch (a row per frame: its destination in
+ *     the caller's buffer, its element size) on the slot's stream — and hands the workers the next part, which goes to the other slot.
+ * A slot's pinned buffer and rows are written again only after its stream has passed the copy and the launch that read them.
+ * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
+ */
+
+extern int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
+                             const void *d_stage, size_t stageBytes) __attribute__((weak));
+
+/* one frame of a restore job (the per-frame table, built once per call) */
+typedef struct {
+    const unsigned char *src; /* the frame, host memory */
+    size_t srcSize;
+    unsigned char *d_dst;     /* where its content belongs: device memory */
+    size_t len;               /* the chunk's length: what the frame must decode to */
+    size_t at;                /* offset in its part's stage, a multiple of 16 */
+    uint32_t k;               /* element size of the byte-grouped layout the content is in; 1: the bytes as they are */
+} QF_RestoreFrame;
+
+typedef struct { size_t f0, f1, bytes, stage; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames) */
+
+struct QF_RestoreSlot_s {
+    void *stream;
+    unsigned char *hStage; size_t hStageCap; /* pinned: the part's decoded frames */
+    void *dStage; size_t dStageCap;          /* their device copy, read by qzstd_hip_ungroup */
+    qzstd_hip_ungroup_row_t *hRows; size_t hRowsCap; /* a row per frame (pinned), and the device copy */
+    void *dRows; size_t dRowsCap;
+};
+
+/* the part the workers decode (QZSTD_Front.restore) */
+struct QF_RestorePart_s {
+    const QF_RestoreFrame *frames; /* the job's table */
+    size_t f0;                     /* chunk c of the workers' job is frame f0 + c */
+    unsigned char *hStage;
+};
+
+static void qfRestoreSlotsFree(QZSTD_Front *f)
+{
+    int k;
+    if (!f->restoreSlot) return;
+    for (k = 0; k < 2; k++) {
+        QF_RestoreSlot *s = &f->restoreSlot[k];
+        if (s->dStage) qzstd_hip_free(f->restoreSlotDev, s->dStage);
+        if (s->dRows) qzstd_hip_free(f->restoreSlotDev, s->dRows);
+        if (s->hStage) qzstd_hip_host_free(s->hStage);
+        if (s->hRows) qzstd_hip_host_free(s->hRows);
+        if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
+    }
+    free(f->restoreSlot);
+    f->restoreSlot = NULL;
+}
+
+/* a worker's share of a part: chunks [c0, c1) of the job are frames of f->restore */
+static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
+{
+    const struct QF_RestorePart_s *p = f->restore;
+    size_t c;
+    if (!w->zd && !(w->zd = ZSTD_createDCtx())) return -1;
+    for (c = sg->c0; c < sg->c1; c++) {
+        const QF_RestoreFrame *fr = &p->frames[p->f0 + c];
+        /* capacity = the chunk's length: a longer content is an error of libzstd's, a shorter one shows in the return value; a frame with a
+         * content checksum is verified by the decoder */
+        const size_t r = ZSTD_decompressDCtx(w->zd, p->hStage + fr->at, fr->len, fr->src, fr->srcSize);
+        if (ZSTD_isError(r) || r != fr->len) return -1;
+    }
+    return 0;
+}
+
+static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                              const QZSTD_DeviceOutBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream)
+{
+    QF_RestoreFrame *table = NULL;
+    QF_RestoreRange *parts = NULL;
+    QF_RestoreSlot *slot;
+    struct QF_RestorePart_s part;
+    void *ev = NULL;
+    size_t i, c = 0, k, nParts = 0, want = 0, partBytes, pos = 0;
+    int dev = -1, rc = 0;
+    /* host-side checks: nothing has touched a GPU when one of them fails */
+    if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    for (i = 0; i < nBufs; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
+        want += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+    }
+    if (want != nFrames || (nFrames && (!frames || !frameSizes))) return (size_t)-1;
+    if (!qzstd_hip_ungroup || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
+        !qzstd_hip_event_destroy)
+        return (size_t)-1; /* a device layer without the ungrouping scatter, or without the device-input entry points at all */
+    for (i = 0; i < nBufs; i++) {
+        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
+        int d;
+        if (!bufs[i].size) continue;
+        d = qzstd_hip_pointer_device(p);
+        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
+        dev = d;
+    }
+    if (nFrames == 0) return 0;
+    pthread_mutex_lock(&f->mu);
+    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+    f->devBusy = 1;
+    pthread_mutex_unlock(&f->mu);
+
+    {
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of content per part (whole frames, at least one), default 64 MiB */
+        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
+    }
+    table = (QF_RestoreFrame *)malloc(nFrames * sizeof(*table));
+    parts = (QF_RestoreRange *)malloc(nFrames * sizeof(*parts));
+    if (!table || !parts) rc = -1;
+    for (i = 0; i < nBufs && rc == 0; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        size_t off;
+        for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
+            const size_t len = bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize;
+            QF_RestoreRange *cur = nParts ? &parts[nParts - 1] : NULL;
+            if (len > 0xFFFFFFE0u || (cur && cur->f1 - cur->f0 >= 0xFFFFFFFFu)) { rc = -1; break; } /* (a row's length and a launch's rows are 32-bit) */
+            if (!cur || cur->bytes + len > partBytes) {
+                cur = &parts[nParts++];
+                cur->f0 = c;
+                cur->bytes = cur->stage = 0;
+            }
+            table[c].src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
+            table[c].srcSize = frameSizes[c];
+            table[c].d_dst = (unsigned char *)bufs[i].d_ptr + off;
+            table[c].len = len;
+            table[c].at = cur->stage;
+            table[c].k = e;
+            pos += frameSizes[c];
+            cur->f1 = c + 1;
+            cur->bytes += len;
+            cur->stage += qfPad16(len);
+        }
+    }
+    /* the slots stay with the front between calls, as the compress side's */
+    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
+    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
+    f->restoreSlotDev = dev;
+    slot = f->restoreSlot;
+    for (k = 0; slot && k < 2 && rc == 0; k++)
+        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
+    /* the library's streams wait for what the caller queued on `stream` so far: whatever last used the buffers */
+    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
+    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
+                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
+        rc = -1;
+    for (k = 0; k < nParts && rc == 0; k++) {
+        const QF_RestoreRange *pr = &parts[k];
+        const size_t nf = pr->f1 - pr->f0;
+        QF_RestoreSlot *s = &slot[k % 2];
+        void *h;
+        int failed;
+        /* part k - 2 was copied and scattered from this slot: its stream must have passed both before the buffers are written (or grown) */
+        if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
+        h = s->hStage;
+        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
+        s->hStage = (unsigned char *)h;
+        h = s->hRows;
+        if (rc == 0 && qfGrowH(&h, &s->hRowsCap, nf * sizeof(qzstd_hip_ungroup_row_t))) rc = -1;
+        s->hRows = (qzstd_hip_ungroup_row_t *)h;
+        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) || qfGrowD(dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_ungroup_row_t))))
+            rc = -1;
+        if (rc) break;
+        for (c = 0; c < nf; c++) {
+            const QF_RestoreFrame *fr = &table[pr->f0 + c];
+            s->hRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
+            s->hRows[c].srcOff = fr->at;
+            s->hRows[c].len = (uint32_t)fr->len;
+            s->hRows[c].elem = fr->k;
+        }
+        part.frames = table;
+        part.f0 = pr->f0;
+        part.hStage = s->hStage;
+        pthread_mutex_lock(&f->mu);
+        f->restore = &part;
+        f->src = NULL;
+        f->srcSize = 0;
+        failed = qfRunJobLocked(f, nf);
+        f->restore = NULL;
+        pthread_mutex_unlock(&f->mu);
+        if (failed) { rc = -1; break; } /* a frame that does not decode, decodes to another length or fails its checksum */
+        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage) ||
+            qzstd_hip_ungroup(dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_ungroup_row_t *)s->dRows, s->dStage, pr->stage)) {
+            rc = -1;
+            break;
+        }
+        __atomic_fetch_add(&f->restoreStats[0], (unsigned long long)nf, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)pr->bytes, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
+    }
+    /* nothing the library queued may still write the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
+    for (k = 0; slot && k < 2; k++) {
+        if (!slot[k].stream) continue;
+        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
+            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
+            rc = -1;
+        }
+    }
+    if (ev) qzstd_hip_event_destroy(dev, ev);
+    free(table);
+    free(parts);
+    pthread_mutex_lock(&f->mu);
+    f->devBusy = 0;
+    pthread_mutex_unlock(&f->mu);
+    return rc == 0 ? nFrames : (size_t)-1;
+}
+
+size_t QZSTD_frontRestoreDeviceBatchTyped(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                          const QZSTD_DeviceOutBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream)
+{
+    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, bufs, elemSizes, nBufs, stream);
+}
+
+size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames, void *d_dst,
+                                size_t dstSize, void *stream)
+{
+    QZSTD_DeviceOutBuf one;
+    one.d_ptr = d_dst;
+    one.size = dstSize;
+    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, &one, NULL, 1, stream);
+}
+
+void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->restoreStats[k], __ATOMIC_RELAXED) : 0ull;
+}

@@ -36,6 +36,17 @@ plus compressed sizes, the share of grouped frames by how they were built (QZSTD
 view (gathered) at level 1 and nothing else: the run to put under rocprofv3.
 
   python tools/device_bench.py --group --gib 1 --reps 3 [--levels 1,6,12] [--legs off,on,torch,host] [--kernels]
+
+--restore: the way back (QZSTD_frontRestoreDeviceBatchTyped) on the same typed data — N GiB of bf16 and of fp32 N(0, 0.02) weights, level-1
+frames of 128 KiB, grouped (the element size) and ungrouped (1) — into one N GiB tensor and into tensors of 128 KiB, each an allocation of
+its own.  Two legs, alternating in one run, every run listed, GB/s of restored content:
+  lib       one QZSTD_frontRestoreDeviceBatchTyped call (the front's workers decode, one H2D copy and one ungroup launch per part)
+  baseline  what a caller does today, written here: ZSTD_decompressDCtx on --threads Python threads (ctypes: the GIL is released inside
+            the calls) into pinned memory, QZSTD_byteUngroup on the same threads for grouped frames, then one copy_ per tensor
+The window holds the calls, the copies and the closing synchronize; the frames, the destinations and the pinned buffer exist before it.
+--kernels: one untimed restore per element size 1, 2, 4, 8 (the same bytes) into one tensor and nothing else: the run to put under rocprofv3.
+
+  python tools/device_bench.py --restore --gib 1 --reps 3 [--kernels]
 """
 import argparse
 import json
@@ -273,10 +284,115 @@ def group_main(a):
     print(json.dumps(out))
 
 
+def restore_main(a):
+    from concurrent.futures import ThreadPoolExecutor
+    import ctypes as C
+    z = B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    size = int(a.gib * (1 << 30)) & ~(a.chunk - 1)
+    n = size // a.chunk
+    torch.manual_seed(0)
+    stream = torch.cuda.current_stream().cuda_stream
+    if a.kernels:
+        t = (torch.randn(size // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8)
+        back = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            for k in (1, 2, 4, 8):
+                assert fr.set_byte_group(k) == 0
+                r, sizes = fr.call_device(t.data_ptr(), size, stream)
+                assert r == n
+                back.zero_()
+                assert fr.call_restore((fr._dst, fr.stride, sizes), n, fr.out_batch([(back.data_ptr(), size)]), 1, None, stream) == n
+                assert torch.equal(back, t)
+        finally:
+            fr.close()
+        print(json.dumps({"bytes": size, "passes": "restore k=1, k=2, k=4, k=8 into one tensor; %d parts each" % max(size >> 26, 1)}))
+        return
+    L = z.lib
+    L.ZSTD_createDCtx.restype = C.c_void_p
+    L.ZSTD_freeDCtx.argtypes = [C.c_void_p]
+    L.ZSTD_decompressDCtx.restype = C.c_size_t
+    L.ZSTD_decompressDCtx.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    ungroup = D.bind_bytegroup(lib).QZSTD_byteUngroup
+    pool = ThreadPoolExecutor(a.threads)
+    dctx = [L.ZSTD_createDCtx() for _ in range(a.threads)]
+    scratch = [C.create_string_buffer(a.chunk) for _ in range(a.threads)]
+    pinned = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "level": 1, "data": {},
+           "timed": "the calls, the copies and the closing synchronize; GB/s of restored content, every run of %d, legs alternating" % a.reps,
+           "baseline": "ZSTD_decompressDCtx (+ QZSTD_byteUngroup) on %d Python threads through ctypes into pinned memory, one copy_ per tensor" % a.threads}
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        t = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt).view(torch.uint8)
+        one = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+        many = [torch.empty(a.chunk, dtype=torch.uint8, device="cuda:0") for _ in range(n)]
+        shapes = {"one_tensor": [one], "tensors_of_128k": many}
+        res = out["data"][kind] = {"elem": k}
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            for label, e in (("grouped", k), ("ungrouped", 1)):
+                assert fr.set_byte_group(e) == 0
+                r, sizes = fr.call_device(t.data_ptr(), size, stream)
+                assert r == n
+                frames_at = C.addressof(fr._dst)
+                cell = res[label] = {"compressed": sum(sizes[c] for c in range(n))}
+                fsize = [sizes[c] for c in range(n)]
+                for shape, tensors in shapes.items():
+                    bufs = fr.out_batch([(x.data_ptr(), x.numel()) for x in tensors])
+                    packed = (fr._dst, fr.stride, sizes)
+
+                    def lib_pass():
+                        assert fr.call_restore(packed, n, bufs, len(tensors), None, stream) == n
+
+                    def decode(w):
+                        zd, tmp = dctx[w], scratch[w]
+                        for c in range(w * n // a.threads, (w + 1) * n // a.threads):
+                            to = pinned.data_ptr() + c * a.chunk
+                            if e == 1:
+                                assert L.ZSTD_decompressDCtx(zd, to, a.chunk, frames_at + c * fr.stride, fsize[c]) == a.chunk
+                            else:
+                                assert L.ZSTD_decompressDCtx(zd, tmp, a.chunk, frames_at + c * fr.stride, fsize[c]) == a.chunk
+                                ungroup(to, tmp, a.chunk, e)
+
+                    def baseline_pass():
+                        list(pool.map(decode, range(a.threads)))
+                        if len(tensors) == 1:
+                            tensors[0].copy_(pinned, non_blocking=True)
+                        else:
+                            for c, x in enumerate(tensors):
+                                x.copy_(pinned[c * a.chunk:(c + 1) * a.chunk], non_blocking=True)
+
+                    runs = cell[shape] = {"lib_gbps": [], "baseline_gbps": []}
+                    for name, f in (("lib", lib_pass), ("baseline", baseline_pass)):  # untimed, and checked
+                        for x in tensors:
+                            x.zero_()
+                        f()
+                        torch.cuda.synchronize()
+                        assert torch.equal(tensors[0] if len(tensors) == 1 else torch.cat(tensors), t), (kind, label, shape, name)
+                    for _ in range(a.reps):
+                        for name, f in (("lib", lib_pass), ("baseline", baseline_pass)):
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            f()
+                            torch.cuda.synchronize()
+                            runs[name + "_gbps"].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+        finally:
+            fr.close()
+        del t, one, many, shapes
+        torch.cuda.empty_cache()
+    for zd in dctx:
+        L.ZSTD_freeDCtx(zd)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--restore", action="store_true")
     ap.add_argument("--group", action="store_true")
-    ap.add_argument("--kernels", action="store_true", help="--group: the passes to trace, nothing timed")
+    ap.add_argument("--kernels", action="store_true", help="--group, --restore: the passes to trace, nothing timed")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--checksum", action="store_true")
     ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
@@ -289,6 +405,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.restore:
+        return restore_main(a)
     if a.group:
         if a.legs == "host,device,batch":
             a.legs = "off,on,torch,host"

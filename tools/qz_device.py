@@ -1,7 +1,8 @@
 """ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
-QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped),
+QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped)
+and of the way back (QZSTD_frontRestoreDeviceBatchTyped, QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats: DeviceFront.restore_batch),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
-each tensor's element size) and restore_tensor() for the way back; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
+each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
 
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
@@ -34,6 +35,16 @@ class GroupRow(C.Structure):
     """qzstd_hip_group_row_t (include/qzstd_hip_device.h)"""
     _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32), ("elem", C.c_uint32),
                 ("reserved", C.c_uint32)]
+
+
+class UngroupRow(C.Structure):
+    """qzstd_hip_ungroup_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("dst", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32)]
+
+
+class DeviceOutBuf(C.Structure):
+    """QZSTD_DeviceOutBuf"""
+    _fields_ = [("d_ptr", C.c_void_p), ("size", C.c_size_t)]
 
 
 class HashRow(C.Structure):
@@ -79,6 +90,17 @@ def bind(F):
         F.QZSTD_frontCompressDeviceBatchTyped.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                           C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         bind_bytegroup(F)
+    if hasattr(F, "QZSTD_frontRestoreDeviceBatchTyped"):  # (absent from an older library)
+        F.QZSTD_frontRestoreDeviceBatchTyped.restype = C.c_size_t
+        F.QZSTD_frontRestoreDeviceBatchTyped.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                                         C.POINTER(DeviceOutBuf), C.c_char_p, C.c_size_t, C.c_void_p]
+        F.QZSTD_frontRestoreDevice.restype = C.c_size_t
+        F.QZSTD_frontRestoreDevice.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]
+        F.QZSTD_frontRestoreStats.restype = None
+        F.QZSTD_frontRestoreStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_frontCompact.restype = C.c_size_t
+        F.QZSTD_frontCompact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t]
     return F
 
 
@@ -210,6 +232,7 @@ class DeviceFront:
         first = (C.c_size_t * (nb + 1))()
         es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
         r = self.lib.QZSTD_frontCompressDeviceBatchTyped(self.f, bufs, es, nb, C.c_void_p(stream or None), self._dst, len(self._dst), sizes, first)
+        self.last = (n, sizes)  # (restore_last: the frames where this call left them)
         if r != n:
             return r, None
         fr = self._frames(n, sizes)
@@ -287,6 +310,66 @@ class DeviceFront:
         self.lib.QZSTD_frontByteGroupStats(self.f, st)
         return list(st)
 
+    def pack_frames(self, frames, compact: bool = False):
+        """frames (a flat list of bytes) in host memory as the restore calls read them -> (buffer, frameStride, sizes array): at the
+        front's stride, as the compress calls leave them, or compact=True back to back with frameStride 0, as QZSTD_frontCompact leaves them"""
+        sizes = (C.c_size_t * max(len(frames), 1))(*[len(f) for f in frames])
+        if compact:
+            return C.create_string_buffer(b"".join(frames), max(sum(len(f) for f in frames), 1)), 0, sizes
+        stride = max([self.stride] + [len(f) for f in frames])
+        buf = C.create_string_buffer(max(len(frames), 1) * stride)
+        for c, f in enumerate(frames):
+            C.memmove(C.addressof(buf) + c * stride, f, len(f))
+        return buf, stride, sizes
+
+    def out_batch(self, ptrs_and_sizes):
+        """-> QZSTD_DeviceOutBuf array for [(device address, bytes), ...]"""
+        bufs = (DeviceOutBuf * max(len(ptrs_and_sizes), 1))()
+        for i, (p, n) in enumerate(ptrs_and_sizes):
+            bufs[i].d_ptr, bufs[i].size = p or None, n
+        return bufs
+
+    def call_restore(self, packed, n_frames: int, bufs, n_bufs: int, elem_sizes=None, stream: int | None = None):
+        """QZSTD_frontRestoreDeviceBatchTyped alone on prepared arguments (pack_frames(), out_batch()) -> its return value"""
+        buf, stride, sizes = packed
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        return self.lib.QZSTD_frontRestoreDeviceBatchTyped(self.f, buf, stride, sizes, n_frames, bufs, es, n_bufs, C.c_void_p(stream or None))
+
+    def restore_last(self, n_frames: int, sizes, ptrs_and_sizes, elem_sizes=None, stream: int | None = None, compacted: bool = False):
+        """the frames the last compress call left in the destination, restored from where they lie -> the restore's return value;
+        compacted=True: QZSTD_frontCompact first, then frameStride 0"""
+        if compacted:
+            self.lib.QZSTD_frontCompact(self.f, self._dst, sizes, n_frames)
+        return self.call_restore((self._dst, 0 if compacted else self.stride, sizes), n_frames, self.out_batch(ptrs_and_sizes),
+                                 len(ptrs_and_sizes), elem_sizes, stream)
+
+    def restore_batch_raw(self, frames_per_buffer, ptrs_and_sizes, elem_sizes=None, stream: int | None = None, compact: bool = False,
+                          n_frames: int | None = None):
+        """per buffer its list of frames (what the compress helpers return) restored into [(device address, bytes), ...] by ONE
+        QZSTD_frontRestoreDeviceBatchTyped call -> its return value (the frame count, or ERROR); elem_sizes: one of 0 (the front's
+        setting), 1, 2, 4, 8 per buffer, or None; n_frames: what to pass as nFrames instead of the frames' count"""
+        flat = [f for fr in frames_per_buffer for f in fr]
+        return self.call_restore(self.pack_frames(flat, compact), len(flat) if n_frames is None else n_frames, self.out_batch(ptrs_and_sizes),
+                                 len(ptrs_and_sizes), elem_sizes, stream)
+
+    def restore_batch(self, frames_per_buffer, ptrs_and_sizes, elem_sizes=None, stream: int | None = None, compact: bool = False) -> int:
+        r = self.restore_batch_raw(frames_per_buffer, ptrs_and_sizes, elem_sizes, stream, compact)
+        if r != sum(len(fr) for fr in frames_per_buffer):
+            raise RuntimeError("QZSTD_frontRestoreDeviceBatchTyped failed (%d)" % (r if r != ERROR else -1))
+        return r
+
+    def restore_device_raw(self, frames, d_dst: int, size: int, stream: int | None = None, compact: bool = False):
+        """QZSTD_frontRestoreDevice: one buffer's frames, the front's element size -> its return value"""
+        buf, stride, sizes = self.pack_frames(list(frames), compact)
+        return self.lib.QZSTD_frontRestoreDevice(self.f, buf, stride, sizes, len(frames), C.c_void_p(d_dst or None), size,
+                                                 C.c_void_p(stream or None))
+
+    def restore_stats(self) -> list:
+        """[0] frames decoded, [1] bytes of content, [2] bytes copied host->device, [3] ungroup launches"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontRestoreStats(self.f, st)
+        return list(st)
+
     def close(self):
         if self.f:
             self.lib.QZSTD_freeFront(self.f)
@@ -333,6 +416,24 @@ def compress_tensors(front: DeviceFront, tensors, stream=None, group=None) -> li
     return front.compress_device_batch(bufs, handle)
 
 
+def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None, group=None) -> int:
+    """the way back of compress_tensors(): per tensor its frames, restored INTO the given contiguous GPU tensors (same sizes, same `group`) in ONE
+    call (QZSTD_frontRestoreDeviceBatchTyped: decoded by the front's workers, ungrouped on the GPU) -> the frame count"""
+    if group not in (None, "dtype"):
+        raise ValueError("restore_tensors: group is None or \"dtype\"")
+    tensors = list(tensors)
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous() or t.device != tensors[0].device:
+            raise ValueError("restore_tensors: contiguous GPU tensors on one device")
+    if not tensors:
+        return 0
+    if stream is None:
+        stream = torch.cuda.current_stream(tensors[0].device)
+    handle = getattr(stream, "cuda_stream", stream)
+    bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
+    return front.restore_batch(frames_per_tensor, bufs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
+
+
 def restore_tensor(frames, dtype, shape, k: int, device=None, zstd=None, lib=None):
     """the tensor whose byte-grouped frames (element size k, as compress_tensors(group="dtype") built them) these are: every frame decoded
     on the host, ungrouped (the layout follows from the frame's content size and k), the bytes uploaded to `device`"""
@@ -348,6 +449,16 @@ def restore_tensor(frames, dtype, shape, k: int, device=None, zstd=None, lib=Non
         raise ValueError("restore_tensor: the frames hold %d bytes fewer than the shape needs" % left)
     t = torch.frombuffer(out, dtype=torch.uint8).view(dtype).reshape(shape) if out else torch.empty(shape, dtype=dtype)
     return t.to(device) if device is not None else t.clone()
+
+
+def foreign_frames(zstd, data: bytes, chunk: int, k: int, level: int = 3, checksum: bool = False, lib=None) -> list:
+    """frames a reader may meet that this library did not build: plain ZSTD_compress2 (libzstd's own match-finder, its own blocks) over the
+    byte-grouped content (group_bytes, element size k) of every chunk"""
+    zc = zstd.cctx(level, checksumFlag=1 if checksum else 0)
+    try:
+        return [zstd.compress2(zc, group_bytes(data[o:o + chunk], k, lib)) for o in range(0, len(data), chunk)]
+    finally:
+        zstd.free(zc)
 
 
 def reference_frames(zstd, oracle, data: bytes, chunk: int, level: int, ext_rep: bool = False) -> list:
