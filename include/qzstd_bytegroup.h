@@ -24,6 +24,9 @@ extern "C" {
  * k outside {1, 2, 4, 8}. */
 size_t QZSTD_byteGroup(void *dst, const void *src, size_t L, unsigned k);
 size_t QZSTD_byteUngroup(void *dst, const void *src, size_t L, unsigned k);
+/* dst[i] = a[i] ^ b[i] for i < n; dst may be a or b.  The delta frames of qzstd_frontend_device.h (QZSTD_frontCompressDeviceBatchDelta) hold the
+ * grouped layout of chunk XOR base chunk: a reader who decodes such a frame itself calls QZSTD_byteUngroup, then this with the base's bytes. */
+void QZSTD_byteXor(void *dst, const void *a, const void *b, size_t n);
 
 /* The block ends of a grouped frame of L bytes, ascending, the last one L; returns their count (ends may be NULL with cap 0 to size the
  * array; at most cap entries are written), 0 for L = 0, (size_t)-1 for a k outside {1, 2, 4, 8}.

@@ -133,6 +133,40 @@ size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frame
  * 16-aligned offsets), [3] qzstd_hip_ungroup launches (one per part) */
 void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Delta frames: the Typed calls with a BASE per buffer — the previous checkpoint's tensor, still on the device.  bases[i] is {NULL, 0} for a
+ * buffer without one, else a device address of exactly bufs[i].size bytes on the buffers' device, at any alignment; bases == NULL makes each
+ * call exactly its ...Typed counterpart.  A frame of a buffer with a base is an ordinary zstd frame whose content is the byte-grouped layout,
+ * for that buffer's element size (1 included), of chunk XOR base chunk: where the step between two checkpoints is small, that is mostly zero
+ * bytes in exactly the mantissa planes grouping cannot help.  NEITHER THE BASE NOR THE FACT THAT THERE WAS ONE IS STORED IN THE FRAME: the
+ * caller keeps both with the frames, as it keeps the element size.  A reader hands the frames to QZSTD_frontRestoreDeviceBatchDelta with the
+ * same element sizes and bases, or decodes a frame itself: decode, QZSTD_byteUngroup, QZSTD_byteXor with the base's bytes.
+ *
+ * Compress: the XOR happens while a part is staged (qzstd_hip_group_xor: one launch for all rows of a part that holds a frame with a base —
+ * such a part is always staged, never read in place): no temporary of the buffers' size, no pass of its own.  Framing, strides,
+ * QZSTD_frontDeviceBatchFrames, the per-plane block rule and checksums are the Typed call's; a checksum covers the content a decoder
+ * verifies, the delta.  Frames of buffers without a base are byte for byte what the Typed call yields, whatever their neighbours are, and a
+ * call in which no buffer has a base is the Typed call, launch for launch.  A delta frame that needs its content on the host gets it rebuilt
+ * from its own sequences and literals, like a grouped one; only a frame with a block the matcher failed has the caller's bytes AND the base's
+ * copied back (both count in QZSTD_frontDeviceStats [2]), XORed and grouped on the host, and is built by ZSTD_compress2.  The bases are only
+ * read; `stream` must order their last writer too.
+ *
+ * Restore: decoding, the pinned buffers and the host->device copy are the Typed call's; a part with a base among its rows is scattered by
+ * one qzstd_hip_ungroup_xor launch, which XORs the base back in on the way out.  bases[i].d_ptr == bufs[i].d_ptr restores IN PLACE over the
+ * previous checkpoint (every byte is read by its only writer, before it is written); a base that overlaps its buffer in any other way is
+ * the caller's error.  `stream` must order the last writer of the bases too.
+ *
+ * Both return (size_t)-1 before anything is queued for everything the Typed calls refuse, a base of another size than its buffer (a NULL one
+ * of a size above 0 included), a base whose first or last byte is not device memory or lies on another device than the buffers, and — when a
+ * base is given — a device layer without qzstd_hip_group_xor / qzstd_hip_ungroup_xor (the Typed and older calls are not affected). */
+size_t QZSTD_frontCompressDeviceBatchDelta(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
+                                           size_t nBufs, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame);
+size_t QZSTD_frontRestoreDeviceBatchDelta(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                          const QZSTD_DeviceOutBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                                          void *stream);
+/* since creation: frames with a base built from [0] sequences + literals, [1] content rebuilt from the arena, [2] both buffers copied back,
+ * XORed (and grouped) on the host; [3] frames restored onto a base */
+void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 #if defined(__cplusplus)
 }
 #endif

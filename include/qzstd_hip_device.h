@@ -2,7 +2,7 @@
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
- * and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * both also with a base XORed in (the ...Delta calls), and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -130,6 +130,49 @@ typedef struct {
 } qzstd_hip_ungroup_row_t;
 int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
                       const void *d_stage, size_t stageBytes);
+
+/*
+ * The two above with a BASE XORed in on the way (delta frames: QZSTD_frontCompressDeviceBatchDelta / QZSTD_frontRestoreDeviceBatchDelta) — no
+ * temporary of the rows' size, no pass of its own.  A row's `base` is a device address of `len` bytes, at any alignment, also one that
+ * differs from the row's src / dst mod 16; 0 = the row has no base and is handled exactly as qzstd_hip_group / qzstd_hip_ungroup handle it.
+ *
+ * qzstd_hip_group_xor: the stage receives the byte-grouped layout of src[i] ^ base[i], i < len; the padding stays zero.  The base is read
+ * under the source's own rule — aligned 16-byte loads of the words that overlap [base, base + len) and of no other word — and XORed with the
+ * source's bytes in registers before they are split into the planes; the few bytes a stage word's owner fetches singly have their base byte
+ * fetched the same way.  The base is never written; src == base is allowed (a row of zeros).  Everything else — one aligned 16-byte store
+ * per stage word, no atomics, stage bytes between rows left alone — is qzstd_hip_group's.
+ *
+ * qzstd_hip_ungroup_xor: dst[i] = ungrouped[i] ^ base[i], under every write guarantee of qzstd_hip_ungroup (exactly [dst, dst + len) written,
+ * each byte once, whole words as aligned 16-byte stores, the up to 15 bytes in front and behind singly).  The base bytes of a destination
+ * word are loaded by the lane that stores the word (one aligned load when base and dst agree mod 16, else two and a shift: the word lies
+ * inside the row, so both overlap [base, base + len)), those of a head or tail byte as single bytes by the lane that stores the byte.
+ * base == dst is therefore allowed — the update in place over a previous checkpoint: every byte is read by its only writer before it is
+ * written, and neighbours that share a 16-byte word stay free of races.  A base that overlaps its destination in any other way, or the
+ * stage, is the caller's error and is not checked.
+ *
+ * `rows`, d_rows, nRows == 0, asynchrony and the refusals before anything is queued: those of qzstd_hip_group / qzstd_hip_ungroup; no value
+ * of `base` is refused.
+ */
+typedef struct {
+    uint64_t src;      /* device address of the row's first byte, any alignment */
+    uint64_t base;     /* device address of the base's first byte, any alignment; 0 = no base */
+    uint64_t dstOff;   /* byte offset in d_stage, a multiple of 16 */
+    uint32_t len;      /* bytes, may be 0 */
+    uint32_t pad;      /* zero bytes written behind them; len + pad is a multiple of 16 */
+    uint32_t elem;     /* element size: 1, 2, 4 or 8 */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_group_xor_row_t;
+int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows, qzstd_hip_group_xor_row_t *d_rows,
+                        void *d_stage, size_t stageBytes);
+typedef struct {
+    uint64_t dst;    /* device address of the row's first byte, any alignment */
+    uint64_t base;   /* device address of the base's first byte, any alignment; 0 = no base; base == dst: update in place */
+    uint64_t srcOff; /* byte offset of the row in d_stage, a multiple of 16 */
+    uint32_t len;    /* bytes, may be 0 */
+    uint32_t elem;   /* element size: 1, 2, 4 or 8 */
+} qzstd_hip_ungroup_xor_row_t;
+int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
+                          const void *d_stage, size_t stageBytes);
 
 /*
  * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a

@@ -1,7 +1,8 @@
 /*
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
- * gather for typed rows and the ungrouping scatter that undoes it, and the XXH64 content checksum.  They use nothing of the match-finder
+ * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), and the XXH64
+ * content checksum.  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -438,6 +439,136 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_kernel(const qzstd_hip_gr
         }
     }
 }
+
+/* ---- the same with a base XORed in (qzstd_hip_group_xor).  A kernel of its own: written as one template with qzstd_group_kernel, that
+ * kernel's register allocation and instruction mix changed (profiles/device_delta_kernels.txt), and it is to stay what it was.  group_shift
+ * and group_split are shared; what looks at a row is written again for a row with a base. */
+
+/* the byte at address a, by one aligned 16-byte load of the word that holds it */
+__device__ inline uint64_t group_byte_at(uint64_t a)
+{
+    const uint32_t sh = (uint32_t)a & 15u;
+    const uint4 v = *reinterpret_cast<const uint4 *>(a - sh);
+    const uint32_t d = sh < 8u ? (sh < 4u ? v.x : v.y) : (sh < 12u ? v.z : v.w);
+    return (d >> ((sh & 3u) * 8u)) & 0xFFu;
+}
+
+/* group_byte for a row with a base: the source byte and, when the row has one, the base byte of the same row offset, each by one aligned
+ * 16-byte load, XORed */
+__device__ inline uint64_t group_xor_byte(const qzstd_hip_group_xor_row_t &row, uint32_t n, uint32_t kLog, uint64_t p)
+{
+    if (p >= row.len) return 0ull;
+    uint64_t s = p;
+    if (p < ((uint64_t)n << kLog)) {
+        const uint32_t j = (uint32_t)p / n; /* (p < len: 32 bits) */
+        s = ((uint64_t)((uint32_t)p - j * n) << kLog) + j;
+    }
+    const uint64_t b = group_byte_at(row.src + s);
+    return row.base ? b ^ group_byte_at(row.base + s) : b;
+}
+
+/* group_patch over group_xor_byte */
+__device__ inline void group_xor_patch(const qzstd_hip_group_xor_row_t &row, uint32_t n, uint32_t kLog, uint64_t o, uint32_t from, uint64_t *o0,
+                                       uint64_t *o1)
+{
+    *o1 = from > 8u ? *o1 & ((1ull << ((from - 8u) * 8u)) - 1ull) : 0ull;
+    if (from < 8u) *o0 = from ? *o0 & ((1ull << (from * 8u)) - 1ull) : 0ull;
+    if (o + from >= row.len) return; /* padding only */
+    for (uint32_t i = from; i < 16u; i++) {
+        const uint64_t b = group_xor_byte(row, n, kLog, o + i);
+        if (i < 8u) *o0 |= b << (i * 8u); else *o1 |= b << ((i - 8u) * 8u);
+    }
+}
+
+/* the 16 bytes from address a on, of which the first `valid` are wanted: the aligned word that holds byte a, and the next one only when
+ * wanted bytes lie in it, shifted into place */
+__device__ inline void group_fetch(uint64_t a, uint32_t valid, uint64_t *o0, uint64_t *o1)
+{
+    const uint32_t sh = (uint32_t)a & 15u;
+    const uint4 *p = reinterpret_cast<const uint4 *>(a - sh);
+    const uint4 l = p[0];
+    uint4 h = make_uint4(0u, 0u, 0u, 0u);
+    if (sh + valid > 16u) h = p[1];
+    group_shift(l, h, sh, o0, o1);
+}
+
+/* qzstd_group_kernel's tiles and phases.  In A the base's 16 bytes are fetched like the source's — aligned loads of the words that overlap
+ * [base, base + len) only, shifted by the base's OWN misalignment — and XORed in before the split: B sees a tile of src ^ base. */
+__global__ __launch_bounds__(kGroupT) void qzstd_group_xor_kernel(const qzstd_hip_group_xor_row_t *__restrict__ rows, uint32_t nRows,
+                                                                   uint64_t firstTile, uint4 *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
+    __shared__ uint32_t which;
+    const uint64_t v = firstTile + blockIdx.x;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_group_xor_row_t row = rows[r];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kGroupTile >> kLog;
+    const uint64_t ext = (uint64_t)row.len + row.pad;
+    const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (ext ? 1ull : 0ull);
+    const uint64_t t = v - ((row.dstOff >> kGroupTileLog) + r);
+    if (t >= tiles) return; /* (the whole workgroup) */
+    const uint32_t e0 = (uint32_t)t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint32_t tileBytes = tileElems << kLog;
+    const uint64_t srcTile = row.src + ((uint64_t)e0 << kLog), baseTile = row.base + ((uint64_t)e0 << kLog);
+
+    for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kGroupT) {
+        const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+        uint64_t o0, o1;
+        group_fetch(srcTile + w * 16u, valid, &o0, &o1);
+        if (row.base) {
+            uint64_t b0, b1;
+            group_fetch(baseTile + w * 16u, valid, &b0, &b1);
+            o0 ^= b0;
+            o1 ^= b1;
+        }
+        switch (kLog) {
+        case 0u: group_split<1u>(o0, o1, lds, w); break;
+        case 1u: group_split<2u>(o0, o1, lds, w); break;
+        case 2u: group_split<4u>(o0, o1, lds, w); break;
+        default: group_split<8u>(o0, o1, lds, w); break;
+        }
+    }
+    __syncthreads();
+
+    uint4 *out = stage + (row.dstOff >> 4);
+    for (uint32_t j = 0; j < (1u << kLog); j++) {
+        const uint64_t planeAt = (uint64_t)j * n + e0; /* row offset of the tile's first element in plane j */
+        const uint32_t aj = (uint32_t)planeAt & 15u;
+        const uint8_t *plane = lds + j * (tileMax + kGroupSlack);
+        /* c: offset from the stage word that holds planeAt; that word itself belongs here only when it starts at planeAt */
+        for (uint32_t c = (aj ? 16u : 0u) + threadIdx.x * 16u; c < aj + tileElems; c += kGroupT * 16u) {
+            const uint32_t x0 = c - aj, q = x0 & ~15u, sh = x0 & 15u;
+            const uint32_t valid = tileElems - x0 < 16u ? tileElems - x0 : 16u;
+            const uint64_t o = planeAt + x0;
+            const uint4 l = *reinterpret_cast<const uint4 *>(plane + q);
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh) h = *reinterpret_cast<const uint4 *>(plane + q + 16u);
+            uint64_t o0, o1;
+            group_shift(l, h, sh, &o0, &o1);
+            if (valid < 16u) group_xor_patch(row, n, kLog, o, valid, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+    if (t + 1u == tiles) {
+        const uint64_t tailAt = ((((uint64_t)n << kLog) + 15u) & ~(uint64_t)15u);
+        for (uint64_t o = tailAt + threadIdx.x * 16u; o < ext; o += kGroupT * 16u) {
+            uint64_t o0 = 0, o1 = 0;
+            group_xor_patch(row, n, kLog, o, 0u, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+}
 } // namespace
 
 extern "C" int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
@@ -470,6 +601,40 @@ extern "C" int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_r
     hipLaunchKernelGGL(qzstd_group_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_kernel");
+    return 0;
+}
+
+/* (qzstd_hip_group's checks and launch geometry, row for row; a row's base may be anything, 0 included) */
+extern "C" int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows,
+                                   qzstd_hip_group_xor_row_t *d_rows, void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_xor: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_group_xor_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
+            return fail_msg("qzstd_hip_group_xor: elem not 1, 2, 4 or 8, or reserved not 0");
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_xor: dstOff or len + pad not a multiple of 16");
+        if (r.len && !r.src) return fail_msg("qzstd_hip_group_xor: null source");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_group_xor: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_xor: a row ends past stageBytes");
+        end = r.dstOff + ext;
+        if (ext) {
+            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
+            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_xor: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_xor: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group xor rows)");
+    hipLaunchKernelGGL(qzstd_group_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+                       static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_group_xor_kernel");
     return 0;
 }
 
@@ -579,7 +744,17 @@ __device__ inline void ungroup_load(const uint8_t *__restrict__ stageRow, uint32
     }
 }
 
-__device__ inline void ungroup_store(const qzstd_hip_ungroup_row_t &row, const uint8_t *__restrict__ stageRow, uint32_t n, uint32_t kLog, uint32_t e0,
+/* qzstd_hip_ungroup_xor's rows carry a base address (0: none); the store phase and the kernel's body are written once for both row types
+ * (the instantiation without a base compiles to the kernel it was: profiles/device_delta_kernels.txt) */
+template <class Row> inline constexpr bool kRowHasBase = false;
+template <> inline constexpr bool kRowHasBase<qzstd_hip_ungroup_xor_row_t> = true;
+
+/* A row with a base (the XOR variant's rows): every byte leaves XORed with the base's byte of the same row offset.  The base bytes of a
+ * destination word are fetched by the lane that stores the word — one aligned 16-byte load when base and dst agree mod 16, else two and a
+ * shift; the word lies inside the row, so both loads overlap [base, base + len) — and those of a head or tail byte singly, by the lane
+ * that stores the byte: with base == dst every byte is read by its only writer, before it writes. */
+template <class Row>
+__device__ inline void ungroup_store(const Row &row, const uint8_t *__restrict__ stageRow, uint32_t n, uint32_t kLog, uint32_t e0,
                                      uint32_t tileElems, bool first, bool last, const uint8_t *lds, uint32_t tid)
 {
     uint8_t *dst = reinterpret_cast<uint8_t *>(row.dst);
@@ -603,22 +778,46 @@ __device__ inline void ungroup_store(const qzstd_hip_ungroup_row_t &row, const u
                 d[b >> 2] = (d[b >> 2] & ~(0xFFu << ((b & 3u) * 8u))) | ungroup_byte(stageRow, n, kLog, o + b) << ((b & 3u) * 8u);
             v = make_uint4(d[0], d[1], d[2], d[3]);
         }
+        if constexpr (kRowHasBase<Row>) {
+            if (row.base) {
+                const uint64_t b = row.base + o;
+                const uint32_t bsh = (uint32_t)b & 15u;
+                const uint4 *bp = reinterpret_cast<const uint4 *>(b - bsh);
+                const uint4 bl = bp[0];
+                uint4 bh = make_uint4(0u, 0u, 0u, 0u);
+                if (bsh) bh = bp[1];
+                uint64_t b0, b1;
+                group_shift(bl, bh, bsh, &b0, &b1);
+                v = make_uint4(v.x ^ (uint32_t)b0, v.y ^ (uint32_t)(b0 >> 32), v.z ^ (uint32_t)b1, v.w ^ (uint32_t)(b1 >> 32));
+            }
+        }
         *reinterpret_cast<uint4 *>(dst + o) = v;
     }
-    if (first && tid < head) dst[tid] = (uint8_t)ungroup_byte(stageRow, n, kLog, tid);
+    if (first && tid < head) {
+        uint32_t b = ungroup_byte(stageRow, n, kLog, tid);
+        if constexpr (kRowHasBase<Row>) {
+            if (row.base) b ^= reinterpret_cast<const uint8_t *>(row.base)[tid];
+        }
+        dst[tid] = (uint8_t)b;
+    }
     if (last) {
         const uint32_t from = head + words * 16u;
-        if (tid < row.len - from) dst[from + tid] = (uint8_t)ungroup_byte(stageRow, n, kLog, from + tid);
+        if (tid < row.len - from) {
+            uint32_t b = ungroup_byte(stageRow, n, kLog, from + tid);
+            if constexpr (kRowHasBase<Row>) {
+                if (row.base) b ^= reinterpret_cast<const uint8_t *>(row.base)[from + tid];
+            }
+            dst[from + tid] = (uint8_t)b;
+        }
     }
 }
 
 /* One workgroup per tile: elements [e0, e0 + tileElems) of one row — 16 KiB of its destination — in the launch numbering of
  * qzstd_group_kernel with srcOff in dstOff's place.  No destination byte is read, none is written twice, none outside [dst, dst + len). */
-__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_kernel(const qzstd_hip_ungroup_row_t *__restrict__ rows, uint32_t nRows, uint64_t firstTile,
-                                                                   const uint8_t *__restrict__ stage)
+template <class Row>
+__device__ __forceinline__ void ungroup_tile(const Row *__restrict__ rows, uint32_t nRows, uint64_t firstTile, const uint8_t *__restrict__ stage,
+                                             uint8_t *lds, uint32_t *which)
 {
-    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
-    __shared__ uint32_t which;
     const uint64_t v = firstTile + blockIdx.x;
     if (threadIdx.x == 0) {
         uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
@@ -626,11 +825,11 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_kernel(const qzstd_hi
             const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
             if ((rows[mid].srcOff >> kUngroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
         }
-        which = lo;
+        *which = lo;
     }
     __syncthreads();
-    const uint32_t r = which;
-    const qzstd_hip_ungroup_row_t row = rows[r];
+    const uint32_t r = *which;
+    const Row row = rows[r];
     const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
     const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
     const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (row.len ? 1ull : 0ull);
@@ -642,6 +841,23 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_kernel(const qzstd_hi
     ungroup_load(stageRow, n, kLog, e0, tileElems, lds, threadIdx.x);
     __syncthreads();
     ungroup_store(row, stageRow, n, kLog, e0, tileElems, t == 0, t + 1u == tiles, lds, threadIdx.x);
+}
+
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_kernel(const qzstd_hip_ungroup_row_t *__restrict__ rows, uint32_t nRows, uint64_t firstTile,
+                                                                   const uint8_t *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which;
+    ungroup_tile(rows, nRows, firstTile, stage, lds, &which);
+}
+
+/* the destination IS read here when a row's base is its destination: see ungroup_store */
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_xor_kernel(const qzstd_hip_ungroup_xor_row_t *__restrict__ rows, uint32_t nRows,
+                                                                       uint64_t firstTile, const uint8_t *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which;
+    ungroup_tile(rows, nRows, firstTile, stage, lds, &which);
 }
 } // namespace
 
@@ -674,6 +890,39 @@ extern "C" int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungro
     hipLaunchKernelGGL(qzstd_ungroup_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
                        static_cast<const uint8_t *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_kernel");
+    return 0;
+}
+
+/* (qzstd_hip_ungroup's checks and launch geometry, row for row; a row's base may be anything, 0 and the row's dst included) */
+extern "C" int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows,
+                                     qzstd_hip_ungroup_xor_row_t *d_rows, const void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_xor: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ungroup_xor_row_t &r = rows[i];
+        const uint64_t ext = ((uint64_t)r.len + 15u) & ~(uint64_t)15u;
+        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_xor: elem not 1, 2, 4 or 8");
+        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_xor: srcOff not a multiple of 16");
+        if (r.len && !r.dst) return fail_msg("qzstd_hip_ungroup_xor: null destination");
+        if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_xor: rows overlap in the stage or are not in ascending order");
+        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_xor: a row ends past stageBytes");
+        end = r.srcOff + ext;
+        if (r.len) {
+            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
+            endTile = (r.srcOff >> kUngroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup_xor: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].srcOff >> kUngroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_xor: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup xor rows)");
+    hipLaunchKernelGGL(qzstd_ungroup_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+                       static_cast<const uint8_t *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_xor_kernel");
     return 0;
 }
 

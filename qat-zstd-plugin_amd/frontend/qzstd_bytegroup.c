@@ -45,6 +45,14 @@ size_t QZSTD_byteUngroup(void *dst, const void *src, size_t L, unsigned k)
     return L;
 }
 
+void QZSTD_byteXor(void *dst, const void *a, const void *b, size_t n)
+{
+    unsigned char *d = (unsigned char *)dst;
+    const unsigned char *x = (const unsigned char *)a, *y = (const unsigned char *)b;
+    size_t i;
+    for (i = 0; i < n; i++) d[i] = (unsigned char)(x[i] ^ y[i]);
+}
+
 size_t QZSTD_byteGroupBlocks(size_t L, unsigned k, size_t *ends, size_t cap)
 {
     const size_t n = bgValid(k) ? L / k : 0;

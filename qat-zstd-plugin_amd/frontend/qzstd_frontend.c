@@ -84,6 +84,8 @@ struct QZSTD_Front_s {
     /* byte grouping (QZSTD_frontSetByteGroup): the element size of the device calls (1: off), and grouped frames by how they were built */
     unsigned group;
     unsigned long long groupStats[3];
+    /* delta frames (the ...Delta calls): frames with a base by how they were built, and frames restored onto a base */
+    unsigned long long deltaStats[4];
     /* the restore calls (qzstd_restore.c): the part the workers decode (NULL: a compress job), the counters, and two slots kept from call to
      * call (pinned buffer, device stage, stream) for device restoreSlotDev */
     const struct QF_RestorePart_s *restore;
@@ -403,6 +405,12 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * a block per plane, so that the skewed exponent plane and the noisy mantissa plane of float data get entropy tables of their own.
  * Everything behind the staging (match-finder, compaction, hash, arena) sees an ordinary part whose frames have unusual block lengths.
  * A frame that needs its content on the host (a raw block: the common case here) rebuilds it from its own entries and literals.
+ *
+ * Delta frames (QZSTD_frontCompressDeviceBatchDelta): a part with a frame whose buffer has a base is staged by ONE qzstd_hip_group_xor launch
+ * for all its rows (base 0 for the rows without one, elem = 1 rows included) and never read in place; the frame's content is the grouped
+ * layout of chunk XOR base chunk, and everything behind the staging — the hash too, which reads the stage — is untouched.  A delta frame that
+ * needs its content on the host is treated like a grouped one (qzbgRebuild, also for k = 1); only for a block the matcher failed do the
+ * caller's bytes AND the base's come back, to be XORed and grouped here.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
@@ -419,6 +427,8 @@ extern int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row
                             void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
                            void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows, qzstd_hip_group_xor_row_t *d_rows,
+                               void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
                            qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
 
@@ -457,6 +467,8 @@ struct QF_DevSlot_s {
     void *dRows; size_t dRowsCap;
     qzstd_hip_group_row_t *hGroupRows; size_t hGroupRowsCap; /* a part with byte-grouped frames: qzstd_hip_group's rows instead */
     void *dGroupRows; size_t dGroupRowsCap;
+    qzstd_hip_group_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with delta frames: qzstd_hip_group_xor's rows instead */
+    void *dXorRows; size_t dXorRowsCap;
     size_t *ends; size_t endsCap; /* the block ends of the frame whose descriptors are being written */
     qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
     void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
@@ -484,10 +496,12 @@ typedef struct {
     size_t f0, f1, nb, bytes;
     int run; /* the frames are consecutive chunks of ONE buffer: readable in place when aligned, stageable by 2D copies */
     int grouped; /* a frame with k > 1 among them: staged by qzstd_hip_group, never read in place */
+    int delta;   /* a frame of a buffer with a base among them: staged by qzstd_hip_group_xor (all its rows), never read in place */
 } QF_DevRange;
 
 struct QF_DevPart_s {
     const QZSTD_DeviceBuf *bufs; /* the caller's buffers (the raw-bytes path reads a frame from its own) */
+    const QZSTD_DeviceBuf *bases; /* the buffers' bases (d_ptr NULL: none), or NULL for a call without any */
     const QF_DevFrame *frames;   /* the job's table */
     size_t f0, f1;               /* frames of the job */
     size_t nb;                   /* blocks */
@@ -498,12 +512,13 @@ struct QF_DevPart_s {
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
-    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
+    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
     if (s->hRows) qzstd_hip_host_free(s->hRows);
     if (s->hGroupRows) qzstd_hip_host_free(s->hGroupRows);
+    if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
     free(s->ends);
     if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
     if (s->hHash) qzstd_hip_host_free(s->hHash);
@@ -544,6 +559,7 @@ static int qfGrowH(void **p, size_t *cap, size_t need)
 typedef struct {
     QZSTD_Front *f;
     const QZSTD_DeviceBuf *bufs;
+    const QZSTD_DeviceBuf *bases; /* NULL: no buffer of the call has a base */
     const QF_DevFrame *frames; /* the per-frame table: frame c of the job */
     const QF_DevRange *parts;
     size_t nParts, blk;        /* blk: the launches' largest block, min(chunkSize, 128 KiB) */
@@ -563,6 +579,28 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     void *stage = s->dStage;
     if (qfGrowD(j->dev, &stage, &s->stageCap, stageBytes)) return -1;
     s->dStage = (unsigned char *)stage;
+    if (pr->delta) {
+        /* the grouping gather's rows with each frame's base chunk (0: the frame's buffer has none): src ^ base arrives, grouped */
+        void *h = s->hXorRows;
+        size_t c, so = 0;
+        if (!qzstd_hip_group_xor || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
+        s->hXorRows = (qzstd_hip_group_xor_row_t *)h;
+        if (qfGrowD(j->dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
+        for (c = 0; c < nf; c++) {
+            qzstd_hip_group_xor_row_t *r = &s->hXorRows[c];
+            const unsigned char *base = (const unsigned char *)j->bases[f0[c].buf].d_ptr;
+            if (f0[c].len > 0xFFFFFFE0u) return -1;
+            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->base = base ? (uint64_t)(uintptr_t)(base + f0[c].off) : 0u;
+            r->dstOff = so;
+            r->len = (uint32_t)f0[c].len;
+            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
+            r->elem = f0[c].k;
+            r->reserved = 0;
+            so += qfPad16(f0[c].len);
+        }
+        return qzstd_hip_group_xor(j->dev, s->stream, s->hXorRows, (uint32_t)nf, (qzstd_hip_group_xor_row_t *)s->dXorRows, s->dStage, stageBytes);
+    }
     if (pr->grouped) {
         /* the gather's rows with each frame's element size: the frames arrive in the byte-grouped layout */
         void *h = s->hGroupRows;
@@ -620,7 +658,7 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
     const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
     /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
-    const int inPlace = !pr->grouped && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
+    const int inPlace = !pr->grouped && !pr->delta && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
     size_t c, b = 0, so = 0, seqCapTotal = 0;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
@@ -749,6 +787,7 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u)), __ATOMIC_RELAXED);
     out->hashed = s->hashed;
     out->bufs = j->bufs;
+    out->bases = j->bases;
     out->frames = j->frames;
     out->f0 = pr->f0;
     out->f1 = pr->f1;
@@ -792,6 +831,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     size_t b, ns = 0, nl = 0, k, r = 0;
     int failedBlock = 0, haveSeqs = 0, maybeRle = 0;
     const int grouped = fm->k > 1u;
+    const unsigned char *dBase = pt->bases ? (const unsigned char *)pt->bases[fm->buf].d_ptr : NULL; /* the frame's content is chunk ^ base chunk */
     unsigned char *dst = f->dst + cg * f->stride;
     /* the frame's block ends (every 128 KiB; a byte-grouped frame's planes first) */
     if (w->endsCap < fm->nb) {
@@ -850,6 +890,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
                 f->sizes[cg] = r;
                 __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
                 if (grouped) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
+                if (dBase) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
                 return 0;
             }
         }
@@ -868,12 +909,13 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     /* A byte-grouped frame's content is not what the caller's buffer holds, and in grouped mode this is the common path (a mantissa plane is
      * noise: a raw block).  The arena has everything: the frame's own entries and literals, executed, ARE the grouped content — no second
      * device->host copy, and no look at the stage, which may hold the part after next by now */
-    if (grouped && haveSeqs &&
+    if ((grouped || dBase) && haveSeqs &&
         qzbgRebuild(w->raw, n, ns ? &w->seqs[0].offset : NULL, ns, s->hLit + s->blkLit[b0], nl, w->ends, fm->nb) == 0) {
-        __atomic_fetch_add(&f->groupStats[1], 1ull, __ATOMIC_RELAXED);
+        if (grouped) __atomic_fetch_add(&f->groupStats[1], 1ull, __ATOMIC_RELAXED);
+        if (dBase) __atomic_fetch_add(&f->deltaStats[1], 1ull, __ATOMIC_RELAXED);
     } else {
         unsigned char *to = w->raw;
-        if (grouped) {
+        if (grouped || dBase) {
             /* a failed block (or entries that do not rebuild): the caller's bytes come back and are grouped here; no sequences are used */
             if (!w->back && !(w->back = (unsigned char *)qzstd_hip_host_alloc(f->p.chunkSize))) return -1;
             to = w->back;
@@ -886,9 +928,20 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             return -1;
         }
         __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
-        if (grouped) {
+        if (dBase) {
+            /* the base's bytes too (into raw, which the grouping below overwrites), XORed into the caller's */
+            if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, dBase + fm->off, n)) return -1;
+            if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
+                (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
+                return -1;
+            }
+            __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
+            QZSTD_byteXor(w->back, w->back, w->raw, n);
+            __atomic_fetch_add(&f->deltaStats[2], 1ull, __ATOMIC_RELAXED);
+        }
+        if (grouped || dBase) {
             if (QZSTD_byteGroup(w->raw, w->back, n, fm->k) != n) return -1;
-            __atomic_fetch_add(&f->groupStats[2], 1ull, __ATOMIC_RELAXED);
+            if (grouped) __atomic_fetch_add(&f->groupStats[2], 1ull, __ATOMIC_RELAXED);
         }
     }
     __atomic_fetch_add(&f->devStats[1], 1ull, __ATOMIC_RELAXED);
@@ -923,7 +976,8 @@ size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf 
 /* the per-frame table and the parts of a job.  A part takes whole frames, across buffer boundaries, until the next one would take its input
  * past partBytes or its blocks past four times the blocks of a part of full ones (a block costs the device the same scratch whatever its
  * length); at least one frame. */
-static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, unsigned group, size_t nBufs,
+static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
+                        unsigned group, size_t nBufs,
                         size_t nFrames, size_t partBytes, size_t blk, QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
 {
     const size_t chunk = f->p.chunkSize, maxBlocks = 4u * (partBytes / blk ? partBytes / blk : 1u);
@@ -942,7 +996,7 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
                 cur->f0 = c;
                 cur->nb = cur->bytes = 0;
                 cur->run = 1;
-                cur->grouped = 0;
+                cur->grouped = cur->delta = 0;
             } else if (fr[c - 1].buf != (uint32_t)i) {
                 cur->run = 0;
             }
@@ -953,6 +1007,7 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
             fr[c].nb = (uint32_t)nb;
             fr[c].k = k;
             if (k > 1u) cur->grouped = 1;
+            if (bases && bases[i].d_ptr) cur->delta = 1;
             cur->f1 = c + 1;
             cur->nb += nb;
             cur->bytes += len;
@@ -967,8 +1022,8 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
 
 /* both device entry points.  batch: the call needs the gather (frames of several buffers in one part); the single-buffer call stages a part it
  * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not */
-static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, int batch, void *stream,
-                               void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
+static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                               int batch, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
     QF_DevJob j;
     QF_DevSlot *slot;
@@ -978,11 +1033,18 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     void *ev = NULL;
     size_t nFrames, nParts = 0, k, i, total = 0;
     unsigned group;
-    int rc = 0, anyGrouped = 0;
+    int rc = 0, anyGrouped = 0, anyBase = 0;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
         if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+    /* a base is none ({NULL, 0}) or as large as its buffer; a call without any is the call without the argument */
+    for (i = 0; bases && i < nBufs; i++) {
+        if (!bases[i].d_ptr && !bases[i].size) continue;
+        if (!bases[i].d_ptr || bases[i].size != bufs[i].size) return (size_t)-1;
+        if (bases[i].size) anyBase = 1;
+    }
+    if (!anyBase) bases = NULL;
     /* each buffer's element size: its own entry, or (0, or no array) the front's setting */
     group = f->group;
     for (i = 0; i < nBufs; i++) {
@@ -998,6 +1060,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
         return (size_t)-1; /* a device layer without the device-input entry points */
     if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
     if (anyGrouped && !qzstd_hip_group) return (size_t)-1;  /* byte grouping wanted and a device layer that cannot group */
+    if (bases && !qzstd_hip_group_xor) return (size_t)-1;   /* a base given and a device layer that cannot XOR one in */
     j.dev = -1;
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
@@ -1007,6 +1070,10 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
         if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (j.dev >= 0 && d != j.dev)) return (size_t)-1;
         j.dev = d;
         total += bufs[i].size;
+        if (bases && bases[i].d_ptr) {
+            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
+            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
+        }
     }
     if (nFrames) {
         pthread_mutex_lock(&f->mu);
@@ -1027,12 +1094,13 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
 
     j.f = f;
     j.bufs = bufs;
+    j.bases = bases;
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
         const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
         const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        rc = qfPlanDevice(f, bufs, elemSizes, group, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
+        rc = qfPlanDevice(f, bufs, bases, elemSizes, group, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
     }
     j.frames = frames;
     j.parts = parts;
@@ -1102,19 +1170,25 @@ size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSi
     QZSTD_DeviceBuf one;
     one.d_ptr = d_src;
     one.size = srcSize;
-    return qfCompressDevice(f, &one, NULL, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
+    return qfCompressDevice(f, &one, NULL, NULL, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
 }
 
 size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, void *dst, size_t dstCapacity,
                                       size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, NULL, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, NULL, NULL, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 size_t QZSTD_frontCompressDeviceBatchTyped(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream,
                                            void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, NULL, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+}
+
+size_t QZSTD_frontCompressDeviceBatchDelta(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
+                                           size_t nBufs, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
+{
+    return qfCompressDevice(f, bufs, bases, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
@@ -1162,6 +1236,13 @@ void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3])
     int k;
     if (!stats) return;
     for (k = 0; k < 3; k++) stats[k] = f ? __atomic_load_n(&f->groupStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->deltaStats[k], __ATOMIC_RELAXED) : 0ull;
 }
 
 /* The byte-grouped layout, its block rule and qzbgRebuild: a source of their own, free of HIP and libzstd (the tests build it alone), and

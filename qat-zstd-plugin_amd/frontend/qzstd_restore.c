@@ -11,23 +11,29 @@
  *   - the calling thread queues ONE host->device copy of the buffer and ONE qzstd_hip_ungroup launch (a row per frame: its destination in
  *     the caller's buffer, its element size) on the slot's stream — and hands the workers the next part, which goes to the other slot.
  * A slot's pinned buffer and rows are written again only after its stream has passed the copy and the launch that read them.
+ * QZSTD_frontRestoreDeviceBatchDelta: a part with a frame whose buffer has a base is scattered by ONE qzstd_hip_ungroup_xor launch instead (base 0
+ * for the rows without one): the frames' content is chunk XOR base chunk, and the base — which may be the destination itself — is XORed back
+ * in on the way out.  Decoding, the pinned buffers and the copy are the same.
  * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
  */
 
 extern int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
                              const void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
+                                 const void *d_stage, size_t stageBytes) __attribute__((weak));
 
 /* one frame of a restore job (the per-frame table, built once per call) */
 typedef struct {
     const unsigned char *src; /* the frame, host memory */
     size_t srcSize;
     unsigned char *d_dst;     /* where its content belongs: device memory */
+    const unsigned char *d_base; /* what is XORed into it on the way there: device memory, or NULL */
     size_t len;               /* the chunk's length: what the frame must decode to */
     size_t at;                /* offset in its part's stage, a multiple of 16 */
     uint32_t k;               /* element size of the byte-grouped layout the content is in; 1: the bytes as they are */
 } QF_RestoreFrame;
 
-typedef struct { size_t f0, f1, bytes, stage; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames) */
+typedef struct { size_t f0, f1, bytes, stage, based; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames), frames with a base */
 
 struct QF_RestoreSlot_s {
     void *stream;
@@ -35,6 +41,8 @@ struct QF_RestoreSlot_s {
     void *dStage; size_t dStageCap;          /* their device copy, read by qzstd_hip_ungroup */
     qzstd_hip_ungroup_row_t *hRows; size_t hRowsCap; /* a row per frame (pinned), and the device copy */
     void *dRows; size_t dRowsCap;
+    qzstd_hip_ungroup_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with a base among its frames: qzstd_hip_ungroup_xor's rows instead */
+    void *dXorRows; size_t dXorRowsCap;
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -52,6 +60,8 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         QF_RestoreSlot *s = &f->restoreSlot[k];
         if (s->dStage) qzstd_hip_free(f->restoreSlotDev, s->dStage);
         if (s->dRows) qzstd_hip_free(f->restoreSlotDev, s->dRows);
+        if (s->dXorRows) qzstd_hip_free(f->restoreSlotDev, s->dXorRows);
+        if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
@@ -77,7 +87,7 @@ static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
 }
 
 static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
-                              const QZSTD_DeviceOutBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream)
+                              const QZSTD_DeviceOutBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs, void *stream)
 {
     QF_RestoreFrame *table = NULL;
     QF_RestoreRange *parts = NULL;
@@ -85,7 +95,7 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
     struct QF_RestorePart_s part;
     void *ev = NULL;
     size_t i, c = 0, k, nParts = 0, want = 0, partBytes, pos = 0;
-    int dev = -1, rc = 0;
+    int dev = -1, rc = 0, anyBase = 0;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
@@ -95,9 +105,17 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         want += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
     }
     if (want != nFrames || (nFrames && (!frames || !frameSizes))) return (size_t)-1;
+    /* a base is none ({NULL, 0}) or as large as its buffer; a call without any is the call without the argument */
+    for (i = 0; bases && i < nBufs; i++) {
+        if (!bases[i].d_ptr && !bases[i].size) continue;
+        if (!bases[i].d_ptr || bases[i].size != bufs[i].size) return (size_t)-1;
+        if (bases[i].size) anyBase = 1;
+    }
+    if (!anyBase) bases = NULL;
     if (!qzstd_hip_ungroup || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the ungrouping scatter, or without the device-input entry points at all */
+    if (bases && !qzstd_hip_ungroup_xor) return (size_t)-1; /* a base given and a device layer that cannot XOR one in */
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
         int d;
@@ -105,6 +123,10 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         d = qzstd_hip_pointer_device(p);
         if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
         dev = d;
+        if (bases && bases[i].d_ptr) {
+            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
+            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
+        }
     }
     if (nFrames == 0) return 0;
     pthread_mutex_lock(&f->mu);
@@ -129,11 +151,13 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             if (!cur || cur->bytes + len > partBytes) {
                 cur = &parts[nParts++];
                 cur->f0 = c;
-                cur->bytes = cur->stage = 0;
+                cur->bytes = cur->stage = cur->based = 0;
             }
             table[c].src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
             table[c].srcSize = frameSizes[c];
             table[c].d_dst = (unsigned char *)bufs[i].d_ptr + off;
+            table[c].d_base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr + off : NULL;
+            if (table[c].d_base) cur->based++;
             table[c].len = len;
             table[c].at = cur->stage;
             table[c].k = e;
@@ -171,9 +195,23 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         s->hRows = (qzstd_hip_ungroup_row_t *)h;
         if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) || qfGrowD(dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_ungroup_row_t))))
             rc = -1;
+        if (rc == 0 && pr->based) {
+            h = s->hXorRows;
+            if (qfGrowH(&h, &s->hXorRowsCap, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) rc = -1;
+            s->hXorRows = (qzstd_hip_ungroup_xor_row_t *)h;
+            if (rc == 0 && qfGrowD(dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) rc = -1;
+        }
         if (rc) break;
         for (c = 0; c < nf; c++) {
             const QF_RestoreFrame *fr = &table[pr->f0 + c];
+            if (pr->based) {
+                s->hXorRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
+                s->hXorRows[c].base = (uint64_t)(uintptr_t)fr->d_base;
+                s->hXorRows[c].srcOff = fr->at;
+                s->hXorRows[c].len = (uint32_t)fr->len;
+                s->hXorRows[c].elem = fr->k;
+                continue;
+            }
             s->hRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
             s->hRows[c].srcOff = fr->at;
             s->hRows[c].len = (uint32_t)fr->len;
@@ -191,7 +229,8 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         pthread_mutex_unlock(&f->mu);
         if (failed) { rc = -1; break; } /* a frame that does not decode, decodes to another length or fails its checksum */
         if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage) ||
-            qzstd_hip_ungroup(dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_ungroup_row_t *)s->dRows, s->dStage, pr->stage)) {
+            (pr->based ? qzstd_hip_ungroup_xor(dev, s->stream, s->hXorRows, (uint32_t)nf, (qzstd_hip_ungroup_xor_row_t *)s->dXorRows, s->dStage, pr->stage)
+                       : qzstd_hip_ungroup(dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_ungroup_row_t *)s->dRows, s->dStage, pr->stage))) {
             rc = -1;
             break;
         }
@@ -199,6 +238,7 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)pr->bytes, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)pr->based, __ATOMIC_RELAXED);
     }
     /* nothing the library queued may still write the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
     for (k = 0; slot && k < 2; k++) {
@@ -220,7 +260,14 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
 size_t QZSTD_frontRestoreDeviceBatchTyped(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
                                           const QZSTD_DeviceOutBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream)
 {
-    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, bufs, elemSizes, nBufs, stream);
+    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, bufs, NULL, elemSizes, nBufs, stream);
+}
+
+size_t QZSTD_frontRestoreDeviceBatchDelta(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                          const QZSTD_DeviceOutBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                                          void *stream)
+{
+    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, bufs, bases, elemSizes, nBufs, stream);
 }
 
 size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames, void *d_dst,
@@ -229,7 +276,7 @@ size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frame
     QZSTD_DeviceOutBuf one;
     one.d_ptr = d_dst;
     one.size = dstSize;
-    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, &one, NULL, 1, stream);
+    return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, &one, NULL, NULL, 1, stream);
 }
 
 void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4])

@@ -47,6 +47,18 @@ The window holds the calls, the copies and the closing synchronize; the frames, 
 --kernels: one untimed restore per element size 1, 2, 4, 8 (the same bytes) into one tensor and nothing else: the run to put under rocprofv3.
 
   python tools/device_bench.py --restore --gib 1 --reps 3 [--kernels]
+
+--delta: delta frames against a base (QZSTD_frontCompressDeviceBatchDelta / QZSTD_frontRestoreDeviceBatchDelta) — N GiB of bf16 and of fp32
+N(0, 0.02) weights (the base) and the same after an update drawn from N(0, 1e-5) (the new checkpoint), both on the GPU.  Two legs each way,
+alternating in one run, every run listed, GB/s of input / of restored content:
+  delta  one QZSTD_frontCompressDeviceBatchDelta call; back: one QZSTD_frontRestoreDeviceBatchDelta call in place over the base
+  torch  what a caller does today: torch.bitwise_xor into a temporary (allocated inside the window, as a caller must) +
+         QZSTD_frontCompressDeviceBatchTyped; back: QZSTD_frontRestoreDeviceBatchTyped into a temporary + bitwise_xor_ into the base
+plus compressed / input for delta + grouped and for grouped alone, and bytes device->host per input byte.
+--kernels: through the C ABI, nothing timed: qzstd_hip_group_xor and qzstd_hip_group, then qzstd_hip_ungroup_xor and qzstd_hip_ungroup, over
+the same N GiB of 128 KiB rows for each element size 1, 2, 4, 8: the run to put under rocprofv3.
+
+  python tools/device_bench.py --delta --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
 """
 import argparse
 import json
@@ -388,11 +400,150 @@ def restore_main(a):
     print(json.dumps(out))
 
 
+def delta_kernels(a, size):
+    """the four staging kernels over the same rows, per element size: qzstd_hip_group_xor / qzstd_hip_group into a stage, then
+    qzstd_hip_ungroup_xor / qzstd_hip_ungroup out of it"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_xor_kernels(plug.lib)
+    for fn in (L.qzstd_hip_group, L.qzstd_hip_ungroup):
+        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    n = size // a.chunk
+    src = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    base = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    dst = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.GroupXorRow))
+    assert d_rows and stage.data_ptr() % 16 == 0
+    want = torch.bitwise_xor(src, base)
+    try:
+        for k in (1, 2, 4, 8):
+            gx, g, ux, u = (D.GroupXorRow * n)(), (D.GroupRow * n)(), (D.UngroupXorRow * n)(), (D.UngroupRow * n)()
+            for c in range(n):
+                o = c * a.chunk
+                gx[c].src, gx[c].base, gx[c].dstOff, gx[c].len, gx[c].pad, gx[c].elem = src.data_ptr() + o, base.data_ptr() + o, o, a.chunk, 0, k
+                g[c].src, g[c].dstOff, g[c].len, g[c].pad, g[c].elem = want.data_ptr() + o, o, a.chunk, 0, k
+                ux[c].dst, ux[c].base, ux[c].srcOff, ux[c].len, ux[c].elem = dst.data_ptr() + o, base.data_ptr() + o, o, a.chunk, k
+                u[c].dst, u[c].srcOff, u[c].len, u[c].elem = dst.data_ptr() + o, o, a.chunk, k
+            torch.cuda.synchronize()
+            for fn, rows in ((L.qzstd_hip_group, g), (L.qzstd_hip_group_xor, gx)):  # both leave group(src ^ base) in the stage
+                assert fn(0, None, rows, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+                plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert L.qzstd_hip_ungroup(0, None, u, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert torch.equal(dst, want), k
+            assert L.qzstd_hip_ungroup_xor(0, None, ux, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert torch.equal(dst, src), k
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps({"bytes": size, "passes": "per element size 1, 2, 4, 8: group, group_xor, ungroup, ungroup_xor over %d rows of %d bytes" % (n, a.chunk)}))
+
+
+def delta_main(a):
+    size = int(a.gib * (1 << 30)) & ~(a.chunk - 1)
+    if a.kernels:
+        return delta_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "step": 1e-5, "data": {},
+           "timed": "the calls, the torch passes and the closing synchronize; GB/s of input (compress) and of restored content (restore), every "
+                    "run of %d, legs alternating" % a.reps,
+           "torch_leg": "bitwise_xor into a fresh temporary + QZSTD_frontCompressDeviceBatchTyped; QZSTD_frontRestoreDeviceBatchTyped into a fresh "
+                        "temporary + bitwise_xor_ into the base"}
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        base_f = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt)
+        new = (base_f.float() + torch.randn(size // k, device="cuda:0") * 1e-5).to(dt).view(torch.uint8)
+        base = base_f.view(torch.uint8)
+        work = torch.empty_like(base)  # the restore legs' "previous checkpoint": refilled from `base` before every run
+        res = out["data"][kind] = {"elem": k, "levels": {}}
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            cell = res["levels"][str(level)] = {}
+            try:
+                fr.reserve(size)
+                n = size // a.chunk
+                bufs_new, _, _ = fr.batch([(new.data_ptr(), size)])
+                bufs_base, _, _ = fr.batch([(base.data_ptr(), size)])
+                es = bytes([k]) + b"\0"
+                _, sizes = fr._frame_buffers(n)
+
+                def grouped_alone():
+                    return fr.lib.QZSTD_frontCompressDeviceBatchTyped(fr.f, bufs_new, es, 1, stream, fr._dst, len(fr._dst), sizes, None)
+
+                def delta_compress():
+                    return fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, bufs_new, bufs_base, es, 1, stream, fr._dst, len(fr._dst), sizes, None)
+
+                def torch_compress():
+                    tmp = torch.bitwise_xor(new, base)
+                    b, _, _ = fr.batch([(tmp.data_ptr(), size)])
+                    return fr.lib.QZSTD_frontCompressDeviceBatchTyped(fr.f, b, es, 1, stream, fr._dst, len(fr._dst), sizes, None)
+
+                assert grouped_alone() == n
+                cell["compressed_grouped"] = sum(sizes[c] for c in range(n))
+                assert torch_compress() == n
+                cell["compressed_torch"] = sum(sizes[c] for c in range(n))
+                s0 = fr.stats()
+                assert delta_compress() == n
+                s1 = fr.stats()
+                cell["compressed_delta"] = sum(sizes[c] for c in range(n))
+                cell["d2h_bytes_per_input_byte_delta"] = round((s1[2] - s0[2]) / size, 4)
+                cell["ratio_grouped"] = round(cell["compressed_grouped"] / size, 4)
+                cell["ratio_delta"] = round(cell["compressed_delta"] / size, 4)
+                cell["delta_frames_by_build"] = fr.delta_stats()[:3]
+                runs = {"delta_gbps": [], "torch_gbps": [], "restore_delta_gbps": [], "restore_torch_gbps": []}
+                for _ in range(a.reps):
+                    for name, f in (("delta", delta_compress), ("torch", torch_compress)):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert f() == n
+                        torch.cuda.synchronize()
+                        runs[name + "_gbps"].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+                # the way back, from the delta frames (the last compress left the torch leg's, which are the same bytes)
+                assert delta_compress() == n
+                packed = (fr._dst, fr.stride, sizes)
+                out_work = fr.out_batch([(work.data_ptr(), size)])
+                base_work, _, _ = fr.batch([(work.data_ptr(), size)])
+
+                def delta_restore():
+                    return fr.lib.QZSTD_frontRestoreDeviceBatchDelta(fr.f, packed[0], packed[1], packed[2], n, out_work, base_work, es, 1, stream)
+
+                def torch_restore():
+                    tmp = torch.empty_like(work)
+                    r = fr.call_restore(packed, n, fr.out_batch([(tmp.data_ptr(), size)]), 1, [k], stream)
+                    work.bitwise_xor_(tmp)
+                    return r
+
+                for name, f in (("delta", delta_restore), ("torch", torch_restore)):  # untimed, and checked
+                    work.copy_(base)
+                    assert f() == n
+                    torch.cuda.synchronize()
+                    assert torch.equal(work, new), (kind, level, name)
+                for _ in range(a.reps):
+                    for name, f in (("delta", delta_restore), ("torch", torch_restore)):
+                        work.copy_(base)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert f() == n
+                        torch.cuda.synchronize()
+                        runs["restore_" + name + "_gbps"].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+                cell.update(runs)
+            finally:
+                fr.close()
+        del base_f, new, base, work
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--delta", action="store_true")
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--group", action="store_true")
-    ap.add_argument("--kernels", action="store_true", help="--group, --restore: the passes to trace, nothing timed")
+    ap.add_argument("--kernels", action="store_true", help="--group, --restore, --delta: the passes to trace, nothing timed")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--checksum", action="store_true")
     ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
@@ -405,6 +556,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.delta:
+        return delta_main(a)
     if a.restore:
         return restore_main(a)
     if a.group:

@@ -1,6 +1,8 @@
 """ctypes bindings of the front-end's device-resident input (include/qzstd_frontend_device.h: QZSTD_frontCompressDevice,
 QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped)
 and of the way back (QZSTD_frontRestoreDeviceBatchTyped, QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats: DeviceFront.restore_batch),
+the delta calls against a base per buffer (QZSTD_frontCompressDeviceBatchDelta, QZSTD_frontRestoreDeviceBatchDelta, QZSTD_frontDeltaStats:
+DeviceFront.compress_device_batch_delta / restore_batch_delta),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
@@ -40,6 +42,25 @@ class GroupRow(C.Structure):
 class UngroupRow(C.Structure):
     """qzstd_hip_ungroup_row_t (include/qzstd_hip_device.h)"""
     _fields_ = [("dst", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32)]
+
+
+class GroupXorRow(C.Structure):
+    """qzstd_hip_group_xor_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("base", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32),
+                ("elem", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class UngroupXorRow(C.Structure):
+    """qzstd_hip_ungroup_xor_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("dst", C.c_uint64), ("base", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32)]
+
+
+def bind_xor_kernels(L):
+    """qzstd_hip_group_xor / qzstd_hip_ungroup_xor on a loaded device layer (libqatseqprod)"""
+    for fn in (L.qzstd_hip_group_xor, L.qzstd_hip_ungroup_xor):
+        fn.restype = C.c_int
+        fn.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    return L
 
 
 class DeviceOutBuf(C.Structure):
@@ -101,6 +122,17 @@ def bind(F):
         F.QZSTD_frontRestoreStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         F.QZSTD_frontCompact.restype = C.c_size_t
         F.QZSTD_frontCompact.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t]
+    if hasattr(F, "QZSTD_frontCompressDeviceBatchDelta"):  # (absent from an older library)
+        F.QZSTD_frontCompressDeviceBatchDelta.restype = C.c_size_t
+        F.QZSTD_frontCompressDeviceBatchDelta.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p,
+                                                          C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        F.QZSTD_frontRestoreDeviceBatchDelta.restype = C.c_size_t
+        F.QZSTD_frontRestoreDeviceBatchDelta.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t,
+                                                         C.POINTER(DeviceOutBuf), C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p]
+        F.QZSTD_frontDeltaStats.restype = None
+        F.QZSTD_frontDeltaStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_byteXor.restype = None
+        F.QZSTD_byteXor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
     return F
 
 
@@ -243,6 +275,50 @@ class DeviceFront:
         if frames is None:
             raise RuntimeError("QZSTD_frontCompressDeviceBatchTyped failed (%d)" % (r if r != ERROR else -1))
         return frames
+
+    def compress_device_batch_delta_raw(self, ptrs_and_sizes, bases, elem_sizes, stream: int | None = None):
+        """QZSTD_frontCompressDeviceBatchDelta -> (return value, per buffer its list of frames or None); bases: per buffer (device address,
+        bytes), or None / (0, 0) for a buffer without one; or None for no array at all"""
+        bufs, nb, n = self.batch(ptrs_and_sizes)
+        _, sizes = self._frame_buffers(n)
+        first = (C.c_size_t * (nb + 1))()
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        bs = None if bases is None else self.batch([b or (0, 0) for b in bases])[0]
+        r = self.lib.QZSTD_frontCompressDeviceBatchDelta(self.f, bufs, bs, es, nb, C.c_void_p(stream or None), self._dst, len(self._dst), sizes,
+                                                         first)
+        self.last = (n, sizes)
+        if r != n:
+            return r, None
+        fr = self._frames(n, sizes)
+        return r, [fr[first[i]:first[i + 1]] for i in range(nb)]
+
+    def compress_device_batch_delta(self, ptrs_and_sizes, bases, elem_sizes, stream: int | None = None) -> list:
+        r, frames = self.compress_device_batch_delta_raw(ptrs_and_sizes, bases, elem_sizes, stream)
+        if frames is None:
+            raise RuntimeError("QZSTD_frontCompressDeviceBatchDelta failed (%d)" % (r if r != ERROR else -1))
+        return frames
+
+    def restore_batch_delta_raw(self, frames_per_buffer, ptrs_and_sizes, bases, elem_sizes=None, stream: int | None = None, compact: bool = False,
+                                n_frames: int | None = None):
+        """QZSTD_frontRestoreDeviceBatchDelta: restore_batch_raw with a base per buffer (as compress_device_batch_delta_raw's) -> its return value"""
+        flat = [f for fr in frames_per_buffer for f in fr]
+        buf, stride, sizes = self.pack_frames(flat, compact)
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        bs = None if bases is None else self.batch([b or (0, 0) for b in bases])[0]
+        return self.lib.QZSTD_frontRestoreDeviceBatchDelta(self.f, buf, stride, sizes, len(flat) if n_frames is None else n_frames,
+                                                           self.out_batch(ptrs_and_sizes), bs, es, len(ptrs_and_sizes), C.c_void_p(stream or None))
+
+    def restore_batch_delta(self, frames_per_buffer, ptrs_and_sizes, bases, elem_sizes=None, stream: int | None = None, compact: bool = False) -> int:
+        r = self.restore_batch_delta_raw(frames_per_buffer, ptrs_and_sizes, bases, elem_sizes, stream, compact)
+        if r != sum(len(fr) for fr in frames_per_buffer):
+            raise RuntimeError("QZSTD_frontRestoreDeviceBatchDelta failed (%d)" % (r if r != ERROR else -1))
+        return r
+
+    def delta_stats(self) -> list:
+        """frames with a base built from [0] sequences + literals, [1] rebuilt content, [2] both buffers copied back; [3] frames restored onto a base"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontDeltaStats(self.f, st)
+        return list(st)
 
     def compress_device_batch(self, ptrs_and_sizes, stream: int | None = None) -> list:
         """frames of every buffer of [(device address, bytes), ...], a list of lists: one QZSTD_frontCompressDeviceBatch call"""
