@@ -167,6 +167,43 @@ size_t QZSTD_frontRestoreDeviceBatchDelta(QZSTD_Front *f, const void *frames, si
  * XORed (and grouped) on the host; [3] frames restored onto a base */
 void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Slices: byte ranges of the buffers AS THEY WERE WRITTEN restored into device memory — a checkpoint written by one rank layout and loaded
+ * by another (a row shard: one contiguous slice per tensor; a column shard of an [R, C] matrix: R slices of one buffer) — without a
+ * temporary of the buffers' size and without decoding the frames no slice touches.  frames / frameStride / frameSizes / nFrames are the WHOLE
+ * frame list the compress call left for bufSizes (nFrames must equal the sum of ceil(bufSizes[i] / chunkSize)); elemSizes as in the Typed
+ * call; the caller keeps the written sizes, the element sizes and which base each buffer was written against.  Slices are in ascending order
+ * and disjoint in the source: (buf, offset) must not decrease, and within one buffer offset[i] >= offset[i-1] + size[i-1].  d_base: NULL, or
+ * the SAME slice of the base the buffer was written against (`size` bytes), which may be d_dst itself: in place.
+ *
+ * Only frames that intersect a non-empty slice are decoded; the bytes of every other frame are never read (with frameStride == 0 the sizes
+ * of the other frames still are, to place the frames).  The needed frames are cut into parts of whole frames (at most
+ * $QZSTD_FRONT_DEVICE_PART bytes of content); the two restore slots, the workers' decode into the pinned buffer, the one host->device copy
+ * per part, the event pair with `stream` and the closing waits are the Typed call's; the launch is ONE qzstd_hip_ungroup_window per part,
+ * a row per piece (slice x frame): windows of the frames' content, at any byte, also inside an element of a grouped frame.
+ * QZSTD_frontRestoreStats counts the parts as before (frames decoded, their content bytes, host->device bytes, launches), and
+ * QZSTD_frontDeltaStats [3] grows by the frames restored onto a base.
+ *
+ * Returns the number of frames decoded (0 for no slices or only empty ones: no GPU is touched) or (size_t)-1.  Before anything is queued:
+ * everything the Typed call refuses that applies here, a wrong nFrames, bufSizes or slices NULL with a count above 0, a slice with
+ * buf >= nBufs or that ends past its buffer, slices out of order or overlapping, a NULL d_dst with size > 0, a destination or base whose first
+ * or last byte is not device memory or that lies on another device than the rest (destinations — or bases — of consecutive slices that follow
+ * each other in memory without a gap, a column shard's rows in one contiguous tensor, are looked up as ONE range, at its first and its last
+ * byte: what the Typed call does for a buffer), a call while another one runs on this front, a device layer without qzstd_hip_ungroup_window.  After work has started: a needed frame that does not decode, decodes to another length or fails its
+ * checksum — the rule is the Typed call's: the destinations' contents are unspecified, nothing outside them was written, and nothing of the
+ * library's is still running on the GPU when the call returns.  A front created with useProducer = 0 is accepted; the other calls do not change. */
+typedef struct {
+    size_t buf;          /* index into bufSizes: the buffer, as it was WRITTEN, that the slice is cut from */
+    size_t offset, size; /* bytes [offset, offset + size) of that buffer; any values inside it; size may be 0 */
+    void *d_dst;         /* device address that receives them, any alignment */
+    const void *d_base;  /* NULL, or the device address of `size` bytes XORed in: the SAME slice of the base the
+                            buffer was written against; may equal d_dst */
+} QZSTD_DeviceSlice;
+size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                      const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs,
+                                      const QZSTD_DeviceSlice *slices, size_t nSlices, void *stream);
+/* since creation: [0] non-empty slices restored, [1] bytes written to destinations, [2] frames decoded for them, [3] rows launched */
+void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 #if defined(__cplusplus)
 }
 #endif

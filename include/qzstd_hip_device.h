@@ -2,7 +2,8 @@
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
- * both also with a base XORed in (the ...Delta calls), and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
+ * and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -173,6 +174,47 @@ typedef struct {
 } qzstd_hip_ungroup_xor_row_t;
 int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
                           const void *d_stage, size_t stageBytes);
+
+/*
+ * Windowed ungrouping scatter (QZSTD_frontRestoreDeviceSlices): qzstd_hip_ungroup_xor for a WINDOW of a staged frame.  The frame lies at
+ * srcOff in the byte-grouped layout for k = elem (n = len / k elements, plane j at [j * n, (j + 1) * n), the len - n * k tail bytes behind
+ * the planes); with u[] its ungrouped content — u[e * k + j] = stage[srcOff + j * n + e], the tail unchanged — a row writes
+ * dst[i] = u[winOff + i] ^ base[i] for i < winLen.  Several rows may be windows of ONE frame (equal srcOff, len and elem): a column shard's
+ * pieces.  winOff and winLen are any bytes inside the frame, also mid-element.
+ *
+ * The guarantees are qzstd_hip_ungroup_xor's, for the window: EXACTLY [dst, dst + winLen) of every row is written, each byte once, and no
+ * other byte of device memory; the 16-byte destination words wholly inside the window leave as aligned 16-byte stores, the up to 15 bytes in
+ * front of the first and behind the last as single bytes; the destination is never read except as a base; two rows of one launch — two
+ * windows of the same frame included — may share a 16-byte destination word without a race; base bytes are loaded by the lane that stores
+ * them (base == dst: in place); stage loads are aligned 16-byte loads inside [srcOff, srcOff + pad16(len)) of the row's frame; no atomics.
+ *
+ * Work is divided by the FRAME's tiles (16 KiB of u[], the tail with the last tile, a frame shorter than k one tile): a row gets a workgroup
+ * per tile its window intersects, none for winLen == 0, and a destination word belongs to the tile of its first byte.  A workgroup brings into
+ * LDS only the part of each plane strip that covers its share of the window — a 2 KiB window of a 128 KiB fp32 frame fetches about 2 KiB and
+ * a word per strip, not 16 KiB.  The launcher writes tile0 (the running sum of the rows' workgroups) into the caller's rows before the upload;
+ * a workgroup finds its row by a binary search over it.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_stage, d_stage not 16-aligned, a srcOff that is no multiple of 16, an elem outside
+ * {1, 2, 4, 8}, a reserved that is not 0, winOff + winLen > len, a null dst with winLen > 0, a frame that ends past stageBytes,
+ * len > 0xFFFFFFE0, a stage span of 64 GiB or more, more than 2^31 - 1 workgroups, rows out of order: srcOff must not decrease; equal srcOff
+ * is the same frame — len and elem equal and winOff[i] >= winOff[i-1] + winLen[i-1]; a larger one must be >= srcOff[i-1] + pad16(len[i-1]).
+ * No value of `base` is refused.  nRows == 0, or every row with winLen == 0: nothing is queued, 0.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t dst;      /* device address that receives u[winOff]; any alignment */
+    uint64_t base;     /* device address of winLen bytes XORed in, any alignment; 0 = none; base == dst: in place */
+    uint64_t srcOff;   /* the FRAME's offset in d_stage, a multiple of 16 */
+    uint32_t len;      /* the FRAME's content length: fixes n and the tail */
+    uint32_t elem;     /* 1, 2, 4 or 8 */
+    uint32_t winOff;   /* first byte of u[] wanted; ANY value, also mid-element */
+    uint32_t winLen;   /* bytes written; winOff + winLen <= len; may be 0 */
+    uint32_t tile0;    /* written by the launcher: workgroups of the rows before this one */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_ungroup_win_row_t;
+int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows,
+                             qzstd_hip_ungroup_win_row_t *d_rows, const void *d_stage, size_t stageBytes);
 
 /*
  * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a

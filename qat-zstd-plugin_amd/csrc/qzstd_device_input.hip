@@ -1,8 +1,8 @@
 /*
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
- * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), and the XXH64
- * content checksum.  They use nothing of the match-finder
+ * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
+ * windows of the staged frames (slices), and the XXH64 content checksum.  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -923,6 +923,150 @@ extern "C" int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_u
     hipLaunchKernelGGL(qzstd_ungroup_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
                        static_cast<const uint8_t *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_xor_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- windowed ungrouping scatter (include/qzstd_hip_device.h) -- */
+namespace {
+/* the frame tile that owns byte p (< len) of a frame's ungrouped content: 16 KiB of the elements each, the tail with the last one */
+__host__ __device__ inline uint32_t window_tile(uint32_t p, uint32_t tiles) { return (p >> kUngroupTileLog) < tiles ? (p >> kUngroupTileLog) : tiles - 1u; }
+
+/* One workgroup per frame tile that a row's window intersects; the row of a workgroup is the last one with tile0 <= blockIdx.x (rows without
+ * a workgroup share the tile0 of the row behind them and are never that one).  Its body is written on its own and not through ungroup_tile /
+ * ungroup_store: a window has its own origin (winOff), its own clipping of the tile and its own strips, and the two whole-row kernels stay the
+ * code they were.  The pieces are shared: ungroup_load and ungroup_word take any element origin, here the first element of the workgroup's
+ * share [lo, hi) of the window instead of the tile's, so only that share's part of each plane strip comes into LDS. */
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_window_kernel(const qzstd_hip_ungroup_win_row_t *__restrict__ rows, uint32_t nRows,
+                                                                          const uint8_t *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const qzstd_hip_ungroup_win_row_t row = rows[which];
+    if (!row.winLen) return; /* (never: see above) */
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
+    const uint32_t tiles = n ? (uint32_t)(((uint64_t)n + tileMax - 1u) / tileMax) : 1u;
+    const uint32_t winEnd = row.winOff + row.winLen; /* <= len */
+    const uint32_t tFirst = window_tile(row.winOff, tiles), tLast = window_tile(winEnd - 1u, tiles);
+    const uint32_t t = tFirst + (blockIdx.x - row.tile0);
+    if (t > tLast) return; /* (the whole workgroup) */
+    /* [lo, hi): the window clipped to the tile, in bytes of the frame's content; the words whose first byte lies in it are this workgroup's */
+    const uint32_t tileLo = t << kUngroupTileLog, tileHi = t + 1u == tiles ? row.len : (t + 1u) << kUngroupTileLog;
+    const uint32_t lo = row.winOff > tileLo ? row.winOff : tileLo, hi = winEnd < tileHi ? winEnd : tileHi;
+    /* its share of the elements, [eLo, eHi): what the strips in LDS hold; none when the share lies in the tail */
+    const uint32_t eLo = (lo >> kLog) < n ? lo >> kLog : n;
+    const uint32_t eEnd = (uint32_t)(((uint64_t)hi + (1u << kLog) - 1u) >> kLog), eHi = eEnd < n ? eEnd : n;
+    const uint8_t *stageRow = stage + row.srcOff;
+    ungroup_load(stageRow, n, kLog, eLo, eHi - eLo, lds, tid);
+    __syncthreads();
+
+    uint8_t *dst = reinterpret_cast<uint8_t *>(row.dst);
+    /* the window's whole destination words: `words` of them from window offset `head` on; in front of them and behind them single bytes */
+    const uint32_t lead = (uint32_t)(0u - row.dst) & 15u, head = lead < row.winLen ? lead : row.winLen;
+    const uint32_t words = (row.winLen - head) >> 4;
+    const uint64_t lim = (uint64_t)eHi << kLog; /* the strips' end: a word that reaches past it takes those bytes from the stage, one by one */
+    const uint32_t w0 = row.winOff + head;      /* the first word's place in the frame's content */
+    for (uint64_t i = (lo <= w0 ? 0u : ((uint64_t)(lo - w0) + 15u) >> 4) + tid; i < words && (uint64_t)w0 + i * 16u < hi; i += kUngroupT) {
+        const uint32_t w = head + (uint32_t)i * 16u, o = row.winOff + w;
+        uint4 v;
+        switch (kLog) {
+        case 0u: v = ungroup_word<1u>(lds, n, eLo, o); break;
+        case 1u: v = ungroup_word<2u>(lds, n, eLo, o); break;
+        case 2u: v = ungroup_word<4u>(lds, n, eLo, o); break;
+        default: v = ungroup_word<8u>(lds, n, eLo, o); break;
+        }
+        if (lim - o < 16u) {
+            uint32_t d[4] = { v.x, v.y, v.z, v.w };
+            for (uint32_t b = (uint32_t)(lim - o); b < 16u; b++)
+                d[b >> 2] = (d[b >> 2] & ~(0xFFu << ((b & 3u) * 8u))) | ungroup_byte(stageRow, n, kLog, o + b) << ((b & 3u) * 8u);
+            v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        if (row.base) { /* the word lies inside the window, so both loads overlap [base, base + winLen) */
+            const uint64_t b = row.base + w;
+            const uint32_t bsh = (uint32_t)b & 15u;
+            const uint4 *bp = reinterpret_cast<const uint4 *>(b - bsh);
+            const uint4 bl = bp[0];
+            uint4 bh = make_uint4(0u, 0u, 0u, 0u);
+            if (bsh) bh = bp[1];
+            uint64_t b0, b1;
+            group_shift(bl, bh, bsh, &b0, &b1);
+            v = make_uint4(v.x ^ (uint32_t)b0, v.y ^ (uint32_t)(b0 >> 32), v.z ^ (uint32_t)b1, v.w ^ (uint32_t)(b1 >> 32));
+        }
+        *reinterpret_cast<uint4 *>(dst + w) = v;
+    }
+    if (t == tFirst && tid < head) {
+        uint32_t b = ungroup_byte(stageRow, n, kLog, row.winOff + tid);
+        if (row.base) b ^= reinterpret_cast<const uint8_t *>(row.base)[tid];
+        dst[tid] = (uint8_t)b;
+    }
+    if (t == tLast) {
+        const uint32_t from = head + words * 16u;
+        if (tid < row.winLen - from) {
+            uint32_t b = ungroup_byte(stageRow, n, kLog, row.winOff + from + tid);
+            if (row.base) b ^= reinterpret_cast<const uint8_t *>(row.base)[from + tid];
+            dst[from + tid] = (uint8_t)b;
+        }
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows,
+                                        qzstd_hip_ungroup_win_row_t *d_rows, const void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_window: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ungroup_win_row_t &r = rows[i];
+        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_window: elem not 1, 2, 4 or 8");
+        if (r.reserved) return fail_msg("qzstd_hip_ungroup_window: reserved not 0");
+        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_window: srcOff not a multiple of 16");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_window: frame too long");
+        if ((uint64_t)r.winOff + r.winLen > r.len) return fail_msg("qzstd_hip_ungroup_window: a window ends past its frame");
+        if (r.winLen && !r.dst) return fail_msg("qzstd_hip_ungroup_window: null destination");
+        if (i && r.srcOff == rows[i - 1].srcOff) { /* the same frame again: the next window of it */
+            if (r.len != rows[i - 1].len || r.elem != rows[i - 1].elem || r.winOff < (uint64_t)rows[i - 1].winOff + rows[i - 1].winLen)
+                return fail_msg("qzstd_hip_ungroup_window: windows of one frame differ in len or elem, overlap or are not in ascending order");
+        } else if (r.srcOff < end) {
+            return fail_msg("qzstd_hip_ungroup_window: frames overlap in the stage or are not in ascending order");
+        }
+        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_window: a frame ends past stageBytes");
+        end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
+        if (r.winLen) {
+            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
+            const uint32_t tiles = n ? (uint32_t)((n + tileMax - 1u) / tileMax) : 1u;
+            total += window_tile(r.winOff + r.winLen - 1u, tiles) - window_tile(r.winOff, tiles) + 1u;
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup_window: stage span too large");
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_window: too many tiles");
+    if (total == 0) return 0; /* nothing but empty windows */
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        qzstd_hip_ungroup_win_row_t &r = rows[i];
+        r.tile0 = (uint32_t)total;
+        if (r.winLen) {
+            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
+            const uint32_t tiles = n ? (uint32_t)((n + tileMax - 1u) / tileMax) : 1u;
+            total += window_tile(r.winOff + r.winLen - 1u, tiles) - window_tile(r.winOff, tiles) + 1u;
+        }
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup window rows)");
+    hipLaunchKernelGGL(qzstd_ungroup_window_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
+                       static_cast<const uint8_t *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_window_kernel");
     return 0;
 }
 

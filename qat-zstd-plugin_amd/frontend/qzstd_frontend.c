@@ -90,6 +90,7 @@ struct QZSTD_Front_s {
      * call (pinned buffer, device stage, stream) for device restoreSlotDev */
     const struct QF_RestorePart_s *restore;
     unsigned long long restoreStats[4];
+    unsigned long long sliceStats[4]; /* QZSTD_frontRestoreDeviceSlices: slices, bytes written, frames decoded, rows launched */
     QF_RestoreSlot *restoreSlot;
     int restoreSlotDev;
 };

@@ -14,6 +14,8 @@
  * QZSTD_frontRestoreDeviceBatchDelta: a part with a frame whose buffer has a base is scattered by ONE qzstd_hip_ungroup_xor launch instead (base 0
  * for the rows without one): the frames' content is chunk XOR base chunk, and the base — which may be the destination itself — is XORed back
  * in on the way out.  Decoding, the pinned buffers and the copy are the same.
+ * QZSTD_frontRestoreDeviceSlices (below the whole-buffer calls): byte ranges of the written buffers; only the frames they intersect are decoded,
+ * cut into parts the same way, and a part is scattered by ONE qzstd_hip_ungroup_window launch, a row per piece (slice x frame).
  * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
  */
 
@@ -21,6 +23,8 @@ extern int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_r
                              const void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
                                  const void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_win_row_t *d_rows,
+                                    const void *d_stage, size_t stageBytes) __attribute__((weak));
 
 /* one frame of a restore job (the per-frame table, built once per call) */
 typedef struct {
@@ -43,6 +47,8 @@ struct QF_RestoreSlot_s {
     void *dRows; size_t dRowsCap;
     qzstd_hip_ungroup_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with a base among its frames: qzstd_hip_ungroup_xor's rows instead */
     void *dXorRows; size_t dXorRowsCap;
+    qzstd_hip_ungroup_win_row_t *hWinRows; size_t hWinRowsCap; /* QZSTD_frontRestoreDeviceSlices: a row per piece (slice x frame) */
+    void *dWinRows; size_t dWinRowsCap;
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -62,6 +68,8 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->dRows) qzstd_hip_free(f->restoreSlotDev, s->dRows);
         if (s->dXorRows) qzstd_hip_free(f->restoreSlotDev, s->dXorRows);
         if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
+        if (s->dWinRows) qzstd_hip_free(f->restoreSlotDev, s->dWinRows);
+        if (s->hWinRows) qzstd_hip_host_free(s->hWinRows);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
@@ -277,6 +285,236 @@ size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frame
     one.d_ptr = d_dst;
     one.size = dstSize;
     return qfRestoreDevice(f, frames, frameStride, frameSizes, nFrames, &one, NULL, NULL, 1, stream);
+}
+
+/*
+ * QZSTD_frontRestoreDeviceSlices: byte ranges of the buffers as they were written, restored from the frames they intersect and from no other.
+ * The needed frames get a table of their own (frame m of the job is the m-th needed one), cut into parts as above; a part's rows are its
+ * PIECES (slice x frame, in order: all pieces of a frame follow each other, so they lie in its part), scattered by ONE
+ * qzstd_hip_ungroup_window launch.  Slots, decode, copy, events and the closing waits are qfRestoreDevice's.
+ */
+typedef struct {
+    size_t m;                    /* the needed frame it is cut from */
+    uint32_t winOff, winLen;     /* the window of that frame's content */
+    unsigned char *d_dst;
+    const unsigned char *d_base; /* or NULL */
+} QF_SlicePiece;
+typedef struct { size_t f0, f1, p0, p1, bytes, stage, based; } QF_SliceRange; /* needed frames [f0, f1) and pieces [p0, p1) */
+
+size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                      const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs,
+                                      const QZSTD_DeviceSlice *slices, size_t nSlices, void *stream)
+{
+    QF_RestoreFrame *table = NULL;
+    QF_SliceRange *parts = NULL;
+    QF_SlicePiece *pieces = NULL;
+    size_t *first = NULL;
+    QF_RestoreSlot *slot;
+    struct QF_RestorePart_s part;
+    void *ev = NULL;
+    size_t i, c, k, nParts = 0, want = 0, partBytes, nPieces = 0, nNeeded = 0, np = 0, g = 0, pos = 0, lastG = (size_t)-1, chunk;
+    unsigned long long nonEmpty = 0, written = 0;
+    int dev = -1, rc = 0;
+    /* host-side checks: nothing has touched a GPU when one of them fails */
+    if (!f || (nBufs && !bufSizes) || (nSlices && !slices) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    chunk = f->p.chunkSize;
+    for (i = 0; i < nBufs; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
+        want += bufSizes[i] / chunk + (bufSizes[i] % chunk != 0);
+    }
+    if (want != nFrames || (nFrames && (!frames || !frameSizes))) return (size_t)-1;
+    for (i = 0; i < nSlices; i++) {
+        const QZSTD_DeviceSlice *s = &slices[i];
+        if (s->buf >= nBufs || s->offset > bufSizes[s->buf] || s->size > bufSizes[s->buf] - s->offset) return (size_t)-1;
+        if (i && (s->buf < slices[i - 1].buf || (s->buf == slices[i - 1].buf && s->offset < slices[i - 1].offset + slices[i - 1].size)))
+            return (size_t)-1; /* not in ascending order, or overlapping in the source */
+        if (!s->size) continue;
+        if (!s->d_dst) return (size_t)-1;
+        nPieces += (s->offset + s->size - 1u) / chunk - s->offset / chunk + 1u;
+    }
+    if (!qzstd_hip_ungroup_window || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
+        !qzstd_hip_event_destroy)
+        return (size_t)-1; /* a device layer without the windowed scatter, or without the device-input entry points at all */
+    {
+        /* destinations (and bases) that follow each other without a gap — a column shard's rows in one contiguous tensor — are ONE range, looked
+         * up at its first and its last byte as a buffer of the Typed call is: a look-up costs some 75 ns, and a shard has 10^5 slices */
+        const unsigned char *dEnd = NULL, *bEnd = NULL;
+        for (i = 0; i < nSlices; i++) {
+            const unsigned char *p = (const unsigned char *)slices[i].d_dst, *b = (const unsigned char *)slices[i].d_base;
+            if (!slices[i].size) continue;
+            if (p != dEnd) {
+                int d;
+                if (dEnd && qzstd_hip_pointer_device(dEnd - 1) != dev) return (size_t)-1;
+                d = qzstd_hip_pointer_device(p);
+                if (d < 0 || (dev >= 0 && d != dev)) return (size_t)-1;
+                dev = d;
+            }
+            dEnd = p + slices[i].size;
+            if (b != bEnd || !b) {
+                if (bEnd && qzstd_hip_pointer_device(bEnd - 1) != dev) return (size_t)-1;
+                if (b && qzstd_hip_pointer_device(b) != dev) return (size_t)-1;
+            }
+            bEnd = b ? b + slices[i].size : NULL;
+        }
+        if (dEnd && qzstd_hip_pointer_device(dEnd - 1) != dev) return (size_t)-1;
+        if (bEnd && qzstd_hip_pointer_device(bEnd - 1) != dev) return (size_t)-1;
+    }
+    if (nPieces == 0) return 0;
+    pthread_mutex_lock(&f->mu);
+    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+    f->devBusy = 1;
+    pthread_mutex_unlock(&f->mu);
+
+    {
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART");
+        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
+    }
+    table = (QF_RestoreFrame *)malloc(nPieces * sizeof(*table)); /* (no more needed frames than pieces) */
+    parts = (QF_SliceRange *)malloc(nPieces * sizeof(*parts));
+    pieces = (QF_SlicePiece *)malloc(nPieces * sizeof(*pieces));
+    first = (size_t *)malloc((nBufs + 1u) * sizeof(*first));
+    if (!table || !parts || !pieces || !first) rc = -1;
+    for (i = 0, c = 0; i < nBufs && rc == 0; i++) {
+        first[i] = c;
+        c += bufSizes[i] / chunk + (bufSizes[i] % chunk != 0);
+    }
+    for (i = 0; i < nSlices && rc == 0; i++) {
+        const QZSTD_DeviceSlice *s = &slices[i];
+        const unsigned e = elemSizes && elemSizes[s->buf] ? elemSizes[s->buf] : f->group;
+        if (!s->size) continue;
+        nonEmpty++;
+        written += s->size;
+        for (c = s->offset / chunk; c * chunk < s->offset + s->size; c++) {
+            const size_t fg = first[s->buf] + c, off = c * chunk;
+            const size_t len = bufSizes[s->buf] - off < chunk ? bufSizes[s->buf] - off : chunk;
+            const size_t lo = s->offset > off ? s->offset : off, hi = s->offset + s->size < off + len ? s->offset + s->size : off + len;
+            QF_SliceRange *cur = nParts ? &parts[nParts - 1] : NULL;
+            QF_SlicePiece *pc = &pieces[np];
+            if (fg != lastG) { /* a frame not seen yet: the next needed one */
+                if (len > 0xFFFFFFE0u) { rc = -1; break; } /* (a row's lengths are 32-bit) */
+                if (!cur || cur->bytes + len > partBytes) {
+                    cur = &parts[nParts++];
+                    cur->f0 = nNeeded;
+                    cur->p0 = np;
+                    cur->bytes = cur->stage = cur->based = 0;
+                }
+                for (; !frameStride && g < fg; g++) pos += frameSizes[g]; /* only the sizes of the frames in between are read */
+                table[nNeeded].src = (const unsigned char *)frames + (frameStride ? fg * frameStride : pos);
+                table[nNeeded].srcSize = frameSizes[fg];
+                table[nNeeded].d_dst = NULL;
+                table[nNeeded].d_base = NULL;
+                table[nNeeded].len = len;
+                table[nNeeded].at = cur->stage;
+                table[nNeeded].k = e;
+                cur->f1 = ++nNeeded;
+                cur->bytes += len;
+                cur->stage += qfPad16(len);
+                lastG = fg;
+            }
+            if (np - cur->p0 >= 0xFFFFFFFFu) { rc = -1; break; } /* (a launch's rows are 32-bit) */
+            pc->m = nNeeded - 1u;
+            pc->winOff = (uint32_t)(lo - off);
+            pc->winLen = (uint32_t)(hi - lo);
+            pc->d_dst = (unsigned char *)s->d_dst + (lo - s->offset);
+            pc->d_base = s->d_base ? (const unsigned char *)s->d_base + (lo - s->offset) : NULL;
+            if (pc->d_base && !table[pc->m].d_base) { /* (d_base of a needed frame: only the mark that a piece of it has one) */
+                table[pc->m].d_base = pc->d_base;
+                cur->based++;
+            }
+            cur->p1 = ++np;
+        }
+    }
+    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
+    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
+    f->restoreSlotDev = dev;
+    slot = f->restoreSlot;
+    for (k = 0; slot && k < 2 && rc == 0; k++)
+        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
+    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
+    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
+                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
+        rc = -1;
+    for (k = 0; k < nParts && rc == 0; k++) {
+        const QF_SliceRange *pr = &parts[k];
+        const size_t nf = pr->f1 - pr->f0, nr = pr->p1 - pr->p0;
+        QF_RestoreSlot *s = &slot[k % 2];
+        void *h;
+        int failed;
+        if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
+        h = s->hStage;
+        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
+        s->hStage = (unsigned char *)h;
+        h = s->hWinRows;
+        if (rc == 0 && qfGrowH(&h, &s->hWinRowsCap, nr * sizeof(qzstd_hip_ungroup_win_row_t))) rc = -1;
+        s->hWinRows = (qzstd_hip_ungroup_win_row_t *)h;
+        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) ||
+                        qfGrowD(dev, &s->dWinRows, &s->dWinRowsCap, nr * sizeof(qzstd_hip_ungroup_win_row_t))))
+            rc = -1;
+        if (rc) break;
+        for (c = 0; c < nr; c++) {
+            const QF_SlicePiece *pc = &pieces[pr->p0 + c];
+            qzstd_hip_ungroup_win_row_t *r = &s->hWinRows[c];
+            r->dst = (uint64_t)(uintptr_t)pc->d_dst;
+            r->base = (uint64_t)(uintptr_t)pc->d_base;
+            r->srcOff = table[pc->m].at;
+            r->len = (uint32_t)table[pc->m].len;
+            r->elem = table[pc->m].k;
+            r->winOff = pc->winOff;
+            r->winLen = pc->winLen;
+            r->tile0 = r->reserved = 0;
+        }
+        part.frames = table;
+        part.f0 = pr->f0;
+        part.hStage = s->hStage;
+        pthread_mutex_lock(&f->mu);
+        f->restore = &part;
+        f->src = NULL;
+        f->srcSize = 0;
+        failed = qfRunJobLocked(f, nf);
+        f->restore = NULL;
+        pthread_mutex_unlock(&f->mu);
+        if (failed) { rc = -1; break; }
+        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage) ||
+            qzstd_hip_ungroup_window(dev, s->stream, s->hWinRows, (uint32_t)nr, (qzstd_hip_ungroup_win_row_t *)s->dWinRows, s->dStage, pr->stage)) {
+            rc = -1;
+            break;
+        }
+        __atomic_fetch_add(&f->restoreStats[0], (unsigned long long)nf, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)pr->bytes, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)pr->based, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->sliceStats[2], (unsigned long long)nf, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->sliceStats[3], (unsigned long long)nr, __ATOMIC_RELAXED);
+    }
+    for (k = 0; slot && k < 2; k++) {
+        if (!slot[k].stream) continue;
+        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
+            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
+            rc = -1;
+        }
+    }
+    if (rc == 0) {
+        __atomic_fetch_add(&f->sliceStats[0], nonEmpty, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->sliceStats[1], written, __ATOMIC_RELAXED);
+    }
+    if (ev) qzstd_hip_event_destroy(dev, ev);
+    free(table);
+    free(parts);
+    free(pieces);
+    free(first);
+    pthread_mutex_lock(&f->mu);
+    f->devBusy = 0;
+    pthread_mutex_unlock(&f->mu);
+    return rc == 0 ? nNeeded : (size_t)-1;
+}
+
+void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->sliceStats[k], __ATOMIC_RELAXED) : 0ull;
 }
 
 void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4])

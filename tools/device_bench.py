@@ -59,6 +59,16 @@ plus compressed / input for delta + grouped and for grouped alone, and bytes dev
 the same N GiB of 128 KiB rows for each element size 1, 2, 4, 8: the run to put under rocprofv3.
 
   python tools/device_bench.py --delta --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
+
+--slices: a resharded load (QZSTD_frontRestoreDeviceSlices) — N GiB of bf16 and of fp32 N(0, 0.02) weights as 2-D tensors with rows of 16 KiB,
+level-1 grouped frames of 128 KiB, written with and without a base.  Two legs, alternating in one run, every run listed, seconds per load,
+frames decoded, bytes host->device and torch's peak extra device memory:
+  A  one QZSTD_frontRestoreDeviceSlices call: a 1/8 row shard (one slice) and a 1/8 column shard (2 KiB of every row: a slice per row)
+  B  what a caller does today: QZSTD_frontRestoreDeviceBatchDelta of the whole tensor into a temporary, then narrow().copy_()
+--kernels: through the C ABI, nothing timed: qzstd_hip_ungroup_xor, then qzstd_hip_ungroup_window over the same N GiB stage as whole-frame
+windows and as the column shard's 2 KiB windows, for each element size 1, 2, 4, 8: the run to put under rocprofv3.
+
+  python tools/device_bench.py --slices --gib 1 --reps 3 [--kernels]
 """
 import argparse
 import json
@@ -538,8 +548,132 @@ def delta_main(a):
     print(json.dumps(out))
 
 
+def slices_kernels(a, size):
+    """through the C ABI, nothing timed, per element size 1, 2, 4, 8 over the same stage of N GiB of 128 KiB frames: qzstd_hip_ungroup_xor, then
+    qzstd_hip_ungroup_window with whole-frame windows (both with a base: the same bytes written), then qzstd_hip_ungroup_window with a column
+    shard's windows — 2 KiB of every 16 KiB of each frame, 1/8 of the bytes"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_window_kernel(D.bind_xor_kernels(plug.lib))
+    n, row, piece = size // a.chunk, 16384, 2048
+    per = a.chunk // row
+    stage = torch.randint(0, 256, (size + 16,), dtype=torch.uint8, device="cuda:0")
+    base = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    dst = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+    dst2 = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * per * C.sizeof(D.UngroupWinRow))
+    assert d_rows and stage.data_ptr() % 16 == 0
+    try:
+        for k in (1, 2, 4, 8):
+            ux, w, col = (D.UngroupXorRow * n)(), (D.UngroupWinRow * n)(), (D.UngroupWinRow * (n * per))()
+            for c in range(n):
+                o = c * a.chunk
+                ux[c].dst, ux[c].base, ux[c].srcOff, ux[c].len, ux[c].elem = dst.data_ptr() + o, base.data_ptr() + o, o, a.chunk, k
+                w[c].dst, w[c].base, w[c].srcOff, w[c].len, w[c].elem, w[c].winOff, w[c].winLen = dst2.data_ptr() + o, base.data_ptr() + o, o, a.chunk, k, 0, a.chunk
+                for j in range(per):
+                    r = col[c * per + j]
+                    r.dst, r.base, r.srcOff, r.len, r.elem = dst2.data_ptr() + (c * per + j) * piece, base.data_ptr() + (c * per + j) * piece, o, a.chunk, k
+                    r.winOff, r.winLen = j * row + 3 * piece, piece
+            torch.cuda.synchronize()
+            assert L.qzstd_hip_ungroup_xor(0, None, ux, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert L.qzstd_hip_ungroup_window(0, None, w, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert torch.equal(dst, dst2), k
+            assert L.qzstd_hip_ungroup_window(0, None, col, n * per, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            want = torch.bitwise_xor(dst, base).view(n * per, row)[:, 3 * piece:4 * piece].reshape(-1)  # (the ungrouped frames, the shard's columns)
+            assert torch.equal(torch.bitwise_xor(dst2[:n * per * piece], base[:n * per * piece]), want), k
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps({"bytes": size, "passes": "per element size 1, 2, 4, 8: ungroup_xor over %d rows of %d bytes, ungroup_window over the same as whole-frame "
+                                               "windows, ungroup_window over %d windows of %d bytes (%d bytes written)" % (n, a.chunk, n * per, piece, n * per * piece)}))
+
+
+def slices_main(a):
+    """--slices: a resharded load.  N GiB of bf16 and of fp32 weights as 2-D tensors with rows of 16 KiB, level-1 grouped frames, written with
+    and without a base; leg A: QZSTD_frontRestoreDeviceSlices of a 1/8 row shard and of a 1/8 column shard (2 KiB of every row); leg B: what a
+    caller does today — QZSTD_frontRestoreDeviceBatchDelta of the whole tensor into a temporary, then narrow().copy_()"""
+    size = int(a.gib * (1 << 30)) & ~(8 * a.chunk - 1)
+    if a.kernels:
+        return slices_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    rowb = 16384
+    R = size // rowb
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "level": 1, "rows": R, "row_bytes": rowb, "data": {},
+           "timed": "the calls, the copies and the closing synchronize; seconds per load, every run of %d, legs alternating" % a.reps,
+           "legs": "A: QZSTD_frontRestoreDeviceSlices; B: QZSTD_frontRestoreDeviceBatchDelta of the whole tensor into a temporary allocated inside "
+                   "the window, then narrow().copy_()",
+           "peak_extra_device_bytes": "torch's peak allocation above the level before the call (the temporary); the library's two device stages "
+                                      "(one part each) are the same in both legs and not included"}
+    n = size // a.chunk
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        Cc = rowb // k
+        base_f = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt)
+        new = (base_f.float() + torch.randn(size // k, device="cuda:0") * 1e-5).to(dt).view(R, Cc)
+        base = base_f.view(R, Cc)
+        res = out["data"][kind] = {"elem": k, "cells": {}}
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        try:
+            for based in (False, True):
+                fr.reserve(size)
+                _, sizes = fr._frame_buffers(n)
+                assert fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, fr.batch([(new.data_ptr(), size)])[0], fr.batch([(base.data_ptr(), size)])[0] if based else None,
+                                                                  bytes([k]) + b"\0", 1, stream, fr._dst, len(fr._dst), sizes, None) == n
+                packed = (fr._dst, fr.stride, sizes)  # the frames where the compress call left them
+                for shard, dim in (("row", 0), ("column", 1)):
+                    start, length = (R // 8 * 3, R // 8) if dim == 0 else (Cc // 8 * 3, Cc // 8)
+                    want = new.narrow(dim, start, length).contiguous()
+                    dst = torch.empty_like(want)
+                    bshard = base.narrow(dim, start, length).contiguous() if based else None
+                    sl = D.shard_slices(0, (R, Cc), k, dim, start, length, dst.data_ptr(), None if bshard is None else bshard.data_ptr())
+                    arr = fr.slice_array(sl)
+                    whole_base, _, _ = fr.batch([(base.data_ptr(), size)])
+
+                    def leg_a():
+                        return fr.call_restore_slices(packed, n, [size], [k], arr, len(sl), stream)
+
+                    def leg_b():
+                        tmp = torch.empty_like(new)
+                        r = fr.lib.QZSTD_frontRestoreDeviceBatchDelta(fr.f, packed[0], packed[1], packed[2], n, fr.out_batch([(tmp.data_ptr(), size)]),
+                                                                      whole_base if based else None, bytes([k]) + b"\0", 1, stream)
+                        dst.copy_(tmp.narrow(dim, start, length))
+                        return r
+
+                    cell = res["cells"]["%s_%s" % (shard, "base" if based else "nobase")] = {"slices": len(sl), "bytes_written": want.numel() * k}
+                    for name, f in (("A", leg_a), ("B", leg_b)):  # untimed, and checked
+                        dst.zero_()
+                        torch.cuda.synchronize()
+                        torch.cuda.reset_peak_memory_stats()
+                        m0, r0 = torch.cuda.memory_allocated(), fr.restore_stats()
+                        got = f()
+                        torch.cuda.synchronize()
+                        r1, peak = fr.restore_stats(), torch.cuda.max_memory_allocated() - m0  # (before the comparison below allocates)
+                        assert got == r1[0] - r0[0] and got != D.ERROR and torch.equal(dst, want), (kind, shard, based, name)
+                        cell[name] = {"frames_decoded": got, "h2d_bytes": r1[2] - r0[2], "peak_extra_device_bytes": peak, "seconds": []}
+                    for _ in range(a.reps):
+                        for name, f in (("A", leg_a), ("B", leg_b)):
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            f()
+                            torch.cuda.synchronize()
+                            cell[name]["seconds"].append(round(time.perf_counter() - t0, 4))
+                    del want, dst, bshard
+                del packed
+        finally:
+            fr.close()
+        del base_f, new, base
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--slices", action="store_true")
     ap.add_argument("--delta", action="store_true")
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--group", action="store_true")
@@ -556,6 +690,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.slices:
+        return slices_main(a)
     if a.delta:
         return delta_main(a)
     if a.restore:

@@ -2,7 +2,8 @@
 QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped)
 and of the way back (QZSTD_frontRestoreDeviceBatchTyped, QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats: DeviceFront.restore_batch),
 the delta calls against a base per buffer (QZSTD_frontCompressDeviceBatchDelta, QZSTD_frontRestoreDeviceBatchDelta, QZSTD_frontDeltaStats:
-DeviceFront.compress_device_batch_delta / restore_batch_delta),
+DeviceFront.compress_device_batch_delta / restore_batch_delta), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
+QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
@@ -53,6 +54,24 @@ class GroupXorRow(C.Structure):
 class UngroupXorRow(C.Structure):
     """qzstd_hip_ungroup_xor_row_t (include/qzstd_hip_device.h)"""
     _fields_ = [("dst", C.c_uint64), ("base", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32)]
+
+
+class UngroupWinRow(C.Structure):
+    """qzstd_hip_ungroup_win_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("dst", C.c_uint64), ("base", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32),
+                ("winOff", C.c_uint32), ("winLen", C.c_uint32), ("tile0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DeviceSlice(C.Structure):
+    """QZSTD_DeviceSlice (include/qzstd_frontend_device.h)"""
+    _fields_ = [("buf", C.c_size_t), ("offset", C.c_size_t), ("size", C.c_size_t), ("d_dst", C.c_void_p), ("d_base", C.c_void_p)]
+
+
+def bind_window_kernel(L):
+    """qzstd_hip_ungroup_window on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_ungroup_window.restype = C.c_int
+    L.qzstd_hip_ungroup_window.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    return L
 
 
 def bind_xor_kernels(L):
@@ -133,6 +152,12 @@ def bind(F):
         F.QZSTD_frontDeltaStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
         F.QZSTD_byteXor.restype = None
         F.QZSTD_byteXor.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]
+    if hasattr(F, "QZSTD_frontRestoreDeviceSlices"):  # (absent from an older library)
+        F.QZSTD_frontRestoreDeviceSlices.restype = C.c_size_t
+        F.QZSTD_frontRestoreDeviceSlices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t),
+                                                     C.c_char_p, C.c_size_t, C.POINTER(DeviceSlice), C.c_size_t, C.c_void_p]
+        F.QZSTD_frontSliceStats.restype = None
+        F.QZSTD_frontSliceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -440,6 +465,42 @@ class DeviceFront:
         return self.lib.QZSTD_frontRestoreDevice(self.f, buf, stride, sizes, len(frames), C.c_void_p(d_dst or None), size,
                                                  C.c_void_p(stream or None))
 
+    def slice_array(self, slices):
+        """-> QZSTD_DeviceSlice array for [(buffer index, offset, size, destination address, base address or None), ...]"""
+        arr = (DeviceSlice * max(len(slices), 1))()
+        for a, (buf, off, size, dst, base) in zip(arr, slices):
+            a.buf, a.offset, a.size, a.d_dst, a.d_base = buf, off, size, dst or None, base or None
+        return arr
+
+    def call_restore_slices(self, packed, n_frames: int, buf_sizes, elem_sizes, slice_arr, n_slices: int, stream: int | None = None):
+        """QZSTD_frontRestoreDeviceSlices alone on prepared arguments (pack_frames(), slice_array()) -> its return value"""
+        buf, stride, sizes = packed
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        bs = None if buf_sizes is None else (C.c_size_t * max(len(buf_sizes), 1))(*buf_sizes)
+        return self.lib.QZSTD_frontRestoreDeviceSlices(self.f, buf, stride, sizes, n_frames, bs, es, 0 if buf_sizes is None else len(buf_sizes),
+                                                       slice_arr, n_slices, C.c_void_p(stream or None))
+
+    def restore_slices_raw(self, frames_per_buffer, buf_sizes, elem_sizes, slices, stream: int | None = None, compact: bool = False,
+                           n_frames: int | None = None):
+        """QZSTD_frontRestoreDeviceSlices: the WHOLE frame list of the buffers as they were written (per buffer its frames; buf_sizes: the
+        written sizes), and slices [(buffer index, offset, size, destination address, base address or None), ...] in ascending order
+        -> its return value (the frames decoded, or ERROR)"""
+        flat = [f for fr in frames_per_buffer for f in fr]
+        return self.call_restore_slices(self.pack_frames(flat, compact), len(flat) if n_frames is None else n_frames, buf_sizes, elem_sizes,
+                                        None if slices is None else self.slice_array(slices), 0 if slices is None else len(slices), stream)
+
+    def restore_slices(self, frames_per_buffer, buf_sizes, elem_sizes, slices, stream: int | None = None, compact: bool = False) -> int:
+        r = self.restore_slices_raw(frames_per_buffer, buf_sizes, elem_sizes, slices, stream, compact)
+        if r == ERROR:
+            raise RuntimeError("QZSTD_frontRestoreDeviceSlices failed")
+        return r
+
+    def slice_stats(self) -> list:
+        """[0] non-empty slices restored, [1] bytes written to destinations, [2] frames decoded for them, [3] rows launched"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontSliceStats(self.f, st)
+        return list(st)
+
     def restore_stats(self) -> list:
         """[0] frames decoded, [1] bytes of content, [2] bytes copied host->device, [3] ungroup launches"""
         st = (C.c_ulonglong * 4)()
@@ -508,6 +569,50 @@ def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None,
     handle = getattr(stream, "cuda_stream", stream)
     bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
     return front.restore_batch(frames_per_tensor, bufs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
+
+
+def restore_slices(front: DeviceFront, frames, buf_sizes, elems, slices, stream=None) -> int:
+    """QZSTD_frontRestoreDeviceSlices: `frames` per buffer as the compress helpers return them (ALL of them), the buffers' written sizes and
+    element sizes, and slices [(buffer index, offset, size, destination address, base address or None), ...] in ascending order -> the number
+    of frames decoded: only those a non-empty slice intersects"""
+    return front.restore_slices(frames, buf_sizes, elems, slices, getattr(stream, "cuda_stream", stream))
+
+
+def shard_slices(index: int, shape, itemsize: int, dim: int, start: int, length: int, dst: int, base: int | None = None) -> list:
+    """the slices of rows / columns [start, start + length) along `dim` of the 2-D row-major tensor number `index` (shape [R, C], written
+    whole), into a CONTIGUOUS destination at device address dst ([length, C] for dim 0: one slice; [R, length] for dim 1: R slices); base:
+    the device address of the same shard of the base, laid out as the destination, or None"""
+    R, Cc = shape
+    if dim not in (0, 1) or start < 0 or length < 0 or start + length > (R, Cc)[dim]:
+        raise ValueError("shard_slices: [start, start + length) inside dimension 0 or 1 of a 2-D tensor")
+    if dim == 0:
+        return [(index, start * Cc * itemsize, length * Cc * itemsize, dst, base)]
+    row = length * itemsize
+    return [(index, (r * Cc + start) * itemsize, row, dst + r * row, None if base is None else base + r * row) for r in range(R)]
+
+
+def restore_shards(front: DeviceFront, frames_per_tensor, shapes, dtypes, shards, bases=None, stream=None, device="cuda:0", elems=None) -> list:
+    """a resharded load: tensors written whole by compress_tensors(group="dtype") (frames_per_tensor, their 2-D shapes and dtypes, all of them),
+    of which this loader wants shards [(tensor index, dim, start, length), ...] (ascending, at most one per tensor) -> per shard a new contiguous
+    tensor on `device`, restored by ONE QZSTD_frontRestoreDeviceSlices call; bases: per shard the same shard of the base tensor (contiguous, on
+    `device`) or None; elems: the element sizes the tensors were written with, when they are not their dtypes'"""
+    itemsizes = [torch.empty((), dtype=dt).element_size() for dt in dtypes]
+    outs, slices = [], []
+    for s, (index, dim, start, length) in enumerate(shards):
+        R, Cc = shapes[index]
+        out = torch.empty((length, Cc) if dim == 0 else (R, length), dtype=dtypes[index], device=device)
+        b = bases[s] if bases is not None else None
+        if b is not None and (not b.is_contiguous() or b.shape != out.shape or b.dtype != out.dtype or b.device != out.device):
+            raise ValueError("restore_shards: a base is the shard's shape, dtype and device, contiguous")
+        slices += shard_slices(index, shapes[index], itemsizes[index], dim, start, length, out.data_ptr(), None if b is None else b.data_ptr())
+        outs.append(out)
+    if stream is None:
+        stream = torch.cuda.current_stream(torch.device(device))
+    sizes = [sh[0] * sh[1] * it for sh, it in zip(shapes, itemsizes)]
+    if elems is None:
+        elems = [it if it in (2, 4, 8) else 1 for it in itemsizes]
+    restore_slices(front, frames_per_tensor, sizes, elems, slices, stream)
+    return outs
 
 
 def restore_tensor(frames, dtype, shape, k: int, device=None, zstd=None, lib=None):
