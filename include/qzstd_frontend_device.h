@@ -167,6 +167,40 @@ size_t QZSTD_frontRestoreDeviceBatchDelta(QZSTD_Front *f, const void *frames, si
  * XORed (and grouped) on the host; [3] frames restored onto a base */
 void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Delta skip: chunks EQUAL to their base chunk — a frozen backbone, frozen embeddings, buffers, an evaluation-only interval — found on the GPU
+ * and skipped.  Off by default; with the setting off every call is launch for launch and byte for byte what it was.
+ *
+ * Compress (QZSTD_frontCompressDeviceBatchDelta with a base given; a call without any base and every other call are not affected): after
+ * the host-side checks and the wait for `stream`, ONE qzstd_hip_diff launch compares every frame of every buffer that has a base with its
+ * base chunk (2 bytes read per content byte), the flags come back in one copy (4 bytes per compared frame, not counted in
+ * QZSTD_frontDeviceStats [2]) and a bounded wait follows.  A frame found equal is left out of the parts — it is not staged, matched,
+ * compacted, copied back or entropy-coded, and a part of 64 MiB holds 64 MiB of changed input; when every frame of the call is equal no part
+ * is queued at all.  Its frame is written by the library itself, THE CANONICAL ZERO FRAME of the chunk's length L: magic, a frame header
+ * descriptor with Single_Segment and the smallest Frame_Content_Size field that holds L, RLE_Blocks of the byte 0 cut every 128 KiB from the
+ * frame's start (the per-plane block rule does not apply: the content is zeros whatever the element size), Last_Block on the final one, and
+ * with QZSTD_frontSetChecksum on the Content_Checksum_Flag and the low 32 bits of XXH64 (seed 0) of L zero bytes, computed on the host:
+ * 10 - 13 bytes and 4 per further 128 KiB.  It is an ordinary zstd frame whose content is L zero bytes, the delta of an unchanged chunk:
+ * the caller keeps nothing new, and any decoder reads it.  Frames of changed chunks are byte for byte the frames the setting-off call yields;
+ * frames of buffers without a base are never compared and never skipped, zeros or not; frameSizes, firstFrame, strides and the return value
+ * are unchanged.  QZSTD_frontDeviceStats [3] counts skipped input too; its [0] and [1], QZSTD_frontDeltaStats and QZSTD_frontByteGroupStats
+ * do not count skipped frames.  With the setting on, a base given and a device layer without qzstd_hip_diff the call returns (size_t)-1
+ * before anything is queued.
+ *
+ * Restore (QZSTD_frontRestoreDeviceBatchDelta): a frame of a buffer with a base whose bytes equal the canonical zero frame of its chunk's
+ * length (with or without the checksum field) is recognised: it is not decoded and takes no room in the pinned buffer, the copy or the
+ * stage.  In place (bases[i].d_ptr == bufs[i].d_ptr) nothing at all happens for it; otherwise consecutive recognised frames of one buffer
+ * become ONE device->device copy from base to destination (a wholly frozen tensor: a single copy).  The parts are packed from the remaining
+ * frames; when none remains no part is queued.  QZSTD_frontRestoreStats counts only what was decoded and copied, QZSTD_frontDeltaStats [3]
+ * only frames scattered onto a base.  With the setting off such a frame is decoded like any other — it is a valid frame.
+ * QZSTD_frontRestoreDeviceSlices and QZSTD_frontRestoreDeviceBatchTyped do not look for zero frames: they decode one as the ordinary frame it is.
+ *
+ * Set: 0, or -1 for f NULL or while a call runs on the front.  Get: 0 / 1 (0 for f NULL). */
+int QZSTD_frontSetDeltaSkip(QZSTD_Front *f, int on);
+int QZSTD_frontGetDeltaSkip(const QZSTD_Front *f);
+/* since creation: [0] frames compared with their base chunk, [1] of them found equal and written as zero frames (nothing staged, matched or
+ * entropy-coded), [2] bytes compared, [3] zero frames recognised by a restore (not decoded, nothing copied host->device) */
+void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 /* Slices: byte ranges of the buffers AS THEY WERE WRITTEN restored into device memory — a checkpoint written by one rank layout and loaded
  * by another (a row shard: one contiguous slice per tensor; a column shard of an [R, C] matrix: R slices of one buffer) — without a
  * temporary of the buffers' size and without decoding the frames no slice touches.  frames / frameStride / frameSizes / nFrames are the WHOLE

@@ -3,7 +3,7 @@
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
  * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
- * and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * the comparison of rows with their bases (QZSTD_frontSetDeltaSkip), and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -215,6 +215,30 @@ typedef struct {
 } qzstd_hip_ungroup_win_row_t;
 int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows,
                              qzstd_hip_ungroup_win_row_t *d_rows, const void *d_stage, size_t stageBytes);
+
+/*
+ * Comparison with a base (QZSTD_frontSetDeltaSkip): ONE launch compares every row's two byte ranges — d_flags[i] = 1 when any of the `len`
+ * bytes at a and b differ, 0 when none does; an empty row gives 0.  a and b have any alignment, also different ones mod 16; a == b is allowed.
+ *
+ * Work is divided by bytes: a workgroup per 16 KiB tile of a row, none for an empty row, so rows of one byte and rows of 64 MiB in one launch
+ * keep the device equally busy.  The launcher writes tile0 (the running sum of the rows' workgroups) into the caller's rows before the upload;
+ * a workgroup finds its row by a binary search over it.  Loads are aligned 16-byte loads of the words that overlap [a, a + len) and
+ * [b, b + len) and of no other word, each side shifted into place in registers by its own misalignment; the bytes of a row's first and last
+ * words that lie outside the range never influence the flag.  The lanes OR their XORs, a wave votes, and one lane of a wave that saw a
+ * difference stores the value 1 to d_flags[row] — an ordinary store; several waves may store the same 1.  The launcher zeroes
+ * d_flags[0 .. nRows) first (a memset on the same stream).  No atomics, no read-modify-write; nothing but d_flags[0 .. nRows) is written.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_flags, a null a or b with len > 0, len > 0xFFFFFFE0, more than 2^31 - 1 workgroups.
+ * nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t a, b;  /* device addresses of `len` bytes each, any alignment, also different mod 16; a == b allowed */
+    uint32_t len;   /* may be 0 */
+    uint32_t tile0; /* written by the launcher: workgroups of the rows before this one */
+} qzstd_hip_diff_row_t;
+int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows, uint32_t *d_flags);
 
 /*
  * Content checksum: ONE launch hashes every row — d_out[i] = XXH64, seed 0, of the `len` bytes at d_base + srcOff (the full 64-bit value; a

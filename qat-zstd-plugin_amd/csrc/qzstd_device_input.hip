@@ -2,7 +2,7 @@
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
  * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
- * windows of the staged frames (slices), and the XXH64 content checksum.  They use nothing of the match-finder
+ * windows of the staged frames (slices), the comparison of rows with their bases (delta skip), and the XXH64 content checksum.  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -1070,9 +1070,81 @@ extern "C" int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungr
     return 0;
 }
 
+/* ---------------------------------------------------------------- comparison with a base (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kDiffT = 256u;                /* threads per workgroup */
+constexpr uint32_t kDiffTileLog = kGroupTileLog; /* bytes of one row per workgroup: 16 KiB, four 16-byte words per lane */
+
+/* One workgroup per 16 KiB tile of a row; its row is the last one with tile0 <= blockIdx.x (qzstd_ungroup_window_kernel's search: rows
+ * without a tile share the tile0 of the row behind them and are never that one).  Both sides are fetched as the grouping gather fetches
+ * its source — group_fetch: the aligned word that holds the first wanted byte and the next one only when wanted bytes lie in it, shifted
+ * by that side's OWN misalignment, so the bytes in front of a and b never arrive — and the bytes behind the row's last one are masked
+ * before the lane's OR.  A wave that saw a difference stores the 1 from one lane: no atomics, the flag is never read. */
+__global__ __launch_bounds__(kDiffT) void qzstd_diff_kernel(const qzstd_hip_diff_row_t *__restrict__ rows, uint32_t nRows, uint32_t *__restrict__ flags)
+{
+    __shared__ uint32_t which;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_diff_row_t row = rows[r];
+    const uint64_t at = (uint64_t)(blockIdx.x - row.tile0) << kDiffTileLog; /* the tile's first byte in its row */
+    if (at >= row.len) return; /* (never: see above) */
+    const uint32_t tileBytes = row.len - at < (1u << kDiffTileLog) ? (uint32_t)(row.len - at) : 1u << kDiffTileLog;
+    uint64_t acc = 0;
+    for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kDiffT) {
+        const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+        uint64_t a0, a1, b0, b1;
+        group_fetch(row.a + at + w * 16u, valid, &a0, &a1);
+        group_fetch(row.b + at + w * 16u, valid, &b0, &b1);
+        a0 ^= b0;
+        a1 ^= b1;
+        if (valid < 16u) { /* the row's last word: what lies behind the row does not count */
+            a1 = valid > 8u ? a1 & ((1ull << ((valid - 8u) * 8u)) - 1ull) : 0ull;
+            if (valid < 8u) a0 &= (1ull << (valid * 8u)) - 1ull;
+        }
+        acc |= a0 | a1;
+    }
+    if (__any(acc != 0ull) && (threadIdx.x & 63u) == 0u) flags[r] = 1u;
+}
+} // namespace
+
+extern "C" int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows, uint32_t *d_flags)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_flags) return fail_msg("qzstd_hip_diff: null pointer");
+    uint64_t total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_diff_row_t &r = rows[i];
+        if (r.len && (!r.a || !r.b)) return fail_msg("qzstd_hip_diff: null row");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_diff: row too long");
+        total += ((uint64_t)r.len + (1u << kDiffTileLog) - 1u) >> kDiffTileLog;
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_diff: too many tiles");
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += ((uint64_t)rows[i].len + (1u << kDiffTileLog) - 1u) >> kDiffTileLog;
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemsetAsync(d_flags, 0, (size_t)nRows * sizeof(uint32_t), (hipStream_t)stream), "hipMemsetAsync (diff flags)");
+    if (total == 0) return 0; /* nothing but empty rows: their flags are 0 */
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (diff rows)");
+    hipLaunchKernelGGL(qzstd_diff_kernel, dim3((uint32_t)total), dim3(kDiffT), 0, (hipStream_t)stream, d_rows, nRows, d_flags);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_diff_kernel");
+    return 0;
+}
+
 /* ---------------------------------------------------------------- content checksum (include/qzstd_hip_device.h) -- */
 namespace {
-constexpr uint32_t kHashRows = 16u;                 /* rows per wave: four lanes each, one per XXH64 accumulator */
+constexpr uint32_t kHashRows = 16u;                /* rows per wave: four lanes each, one per XXH64 accumulator */
 constexpr uint32_t kHashTile = QZSTD_HIP_XXH64_TILE; /* bytes of a row per fetch: one whole-wave 16-byte load */
 constexpr uint32_t kHashPitch = kHashTile + 32u;    /* a row's tile in LDS: 32 bytes of padding put the eight rows of a 32-lane group on
                                                        the 64 banks once (8 B per lane, 32 B per row and stripe) */

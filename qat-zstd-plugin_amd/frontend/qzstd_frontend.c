@@ -86,6 +86,9 @@ struct QZSTD_Front_s {
     unsigned long long groupStats[3];
     /* delta frames (the ...Delta calls): frames with a base by how they were built, and frames restored onto a base */
     unsigned long long deltaStats[4];
+    /* delta skip (QZSTD_frontSetDeltaSkip): the setting, and frames compared / found equal, bytes compared, zero frames a restore recognised */
+    int deltaSkip;
+    unsigned long long skipStats[4];
     /* the restore calls (qzstd_restore.c): the part the workers decode (NULL: a compress job), the counters, and two slots kept from call to
      * call (pinned buffer, device stage, stream) for device restoreSlotDev */
     const struct QF_RestorePart_s *restore;
@@ -412,6 +415,10 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * layout of chunk XOR base chunk, and everything behind the staging — the hash too, which reads the stage — is untouched.  A delta frame that
  * needs its content on the host is treated like a grouped one (qzbgRebuild, also for k = 1); only for a block the matcher failed do the
  * caller's bytes AND the base's come back, to be XORed and grouped here.
+ *
+ * Delta skip (QZSTD_frontSetDeltaSkip): before the parts are planned, ONE qzstd_hip_diff launch finds the frames of based buffers whose chunk
+ * equals its base chunk (qfDiffPass); they get the canonical zero frame, written here, and are left out of the per-frame table — a table
+ * entry carries its frame's index in the call — so nothing above ever sees them.  With the setting off, or without a base, nothing changes.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
@@ -432,6 +439,8 @@ extern int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_x
                                void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
                            qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
+extern int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows,
+                          uint32_t *d_flags) __attribute__((weak));
 
 #define QF_PART_BYTES ((size_t)64 << 20)
 #define QF_DEV_WAIT_MS 60000u
@@ -474,6 +483,9 @@ struct QF_DevSlot_s {
     qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
     void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
     uint64_t *hHash; size_t hHashCap;
+    qzstd_hip_diff_row_t *hDiffRows; size_t hDiffRowsCap; /* delta skip: a row per compared frame (pinned), the device copy, the flags on both sides */
+    void *dDiffRows, *dDiffFlags; size_t dDiffRowsCap, dDiffFlagsCap;
+    uint32_t *hDiffFlags; size_t hDiffFlagsCap;
     int hashed; /* the part queued on this slot has its frames' hashes in dHash; the part fetched from it has them in hHash */
     qzstd_hip_block_t *hDesc; size_t hDescCap;
     void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
@@ -487,6 +499,7 @@ struct QF_DevSlot_s {
 typedef struct {
     size_t off, len; /* offset in its buffer, length (chunkSize, or what is left of the buffer) */
     size_t b0;       /* first block in its part */
+    size_t idx;      /* its index in the call: dst + idx * stride, frameSizes[idx] (the table leaves out the frames a delta skip found equal) */
     uint32_t buf;    /* owning buffer */
     uint32_t nb;     /* blocks: QZSTD_byteGroupBlocks(len, k) — ceil(len / 128 KiB) for k = 1 */
     uint32_t k;      /* element size of the byte-grouped layout; 1: the bytes as they are */
@@ -513,7 +526,8 @@ struct QF_DevPart_s {
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
-    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash };
+    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
+                  s->dDiffRows, s->dDiffFlags };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
@@ -523,6 +537,8 @@ static void qfSlotFree(int dev, QF_DevSlot *s)
     free(s->ends);
     if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
     if (s->hHash) qzstd_hip_host_free(s->hHash);
+    if (s->hDiffRows) qzstd_hip_host_free(s->hDiffRows);
+    if (s->hDiffFlags) qzstd_hip_host_free(s->hDiffFlags);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
     if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
     free(s->blkSeq);
@@ -833,7 +849,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     int failedBlock = 0, haveSeqs = 0, maybeRle = 0;
     const int grouped = fm->k > 1u;
     const unsigned char *dBase = pt->bases ? (const unsigned char *)pt->bases[fm->buf].d_ptr : NULL; /* the frame's content is chunk ^ base chunk */
-    unsigned char *dst = f->dst + cg * f->stride;
+    unsigned char *dst = f->dst + fm->idx * f->stride;
     /* the frame's block ends (every 128 KiB; a byte-grouped frame's planes first) */
     if (w->endsCap < fm->nb) {
         free(w->ends);
@@ -888,7 +904,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
                     r += 4u;
                     __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
                 }
-                f->sizes[cg] = r;
+                f->sizes[fm->idx] = r;
                 __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
                 if (grouped) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
                 if (dBase) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
@@ -954,7 +970,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         r = qfSeq(w->zc, dst, f->stride, w->seqs, ns, w->raw, n);
         if (!ZSTD_isError(r)) {
             (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
-            f->sizes[cg] = r;
+            f->sizes[fm->idx] = r;
             return 0;
         }
     }
@@ -962,7 +978,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
     r = ZSTD_compress2(w->zc, dst, f->stride, w->raw, n);
     if (ZSTD_isError(r)) return -1;
-    f->sizes[cg] = r;
+    f->sizes[fm->idx] = r;
     return 0;
 }
 
@@ -976,15 +992,17 @@ size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf 
 
 /* the per-frame table and the parts of a job.  A part takes whole frames, across buffer boundaries, until the next one would take its input
  * past partBytes or its blocks past four times the blocks of a part of full ones (a block costs the device the same scratch whatever its
- * length); at least one frame. */
+ * length); at least one frame.  equal: NULL, or per frame of the call 1 for a frame found equal to its base chunk (QZSTD_frontSetDeltaSkip):
+ * it is left out of the table and of the parts, so frame m of the table is frame fr[m].idx of the call, and the frames around it are not
+ * consecutive chunks. */
 static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
-                        unsigned group, size_t nBufs,
+                        unsigned group, size_t nBufs, const unsigned char *equal,
                         size_t nFrames, size_t partBytes, size_t blk, QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
 {
     const size_t chunk = f->p.chunkSize, maxBlocks = 4u * (partBytes / blk ? partBytes / blk : 1u);
     QF_DevFrame *fr = (QF_DevFrame *)malloc(nFrames * sizeof(*fr));
     QF_DevRange *pt = (QF_DevRange *)malloc(nFrames * sizeof(*pt)), *cur = NULL;
-    size_t i, c = 0, nParts = 0;
+    size_t i, c = 0, m = 0, nParts = 0;
     if (!fr || !pt) { free(fr); free(pt); return -1; }
     for (i = 0; i < nBufs; i++) {
         const unsigned k = elemSizes && elemSizes[i] ? elemSizes[i] : group;
@@ -992,24 +1010,26 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
         for (off = 0; off < bufs[i].size; off += chunk, c++) {
             const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
             const size_t nb = QZSTD_byteGroupBlocks(len, k, NULL, 0);
+            if (equal && equal[c]) continue;
             if (!cur || cur->bytes + len > partBytes || cur->nb + nb > maxBlocks) {
                 cur = &pt[nParts++];
-                cur->f0 = c;
+                cur->f0 = m;
                 cur->nb = cur->bytes = 0;
                 cur->run = 1;
                 cur->grouped = cur->delta = 0;
-            } else if (fr[c - 1].buf != (uint32_t)i) {
+            } else if (fr[m - 1].buf != (uint32_t)i || fr[m - 1].off + chunk != off) {
                 cur->run = 0;
             }
-            fr[c].off = off;
-            fr[c].len = len;
-            fr[c].b0 = cur->nb;
-            fr[c].buf = (uint32_t)i;
-            fr[c].nb = (uint32_t)nb;
-            fr[c].k = k;
+            fr[m].off = off;
+            fr[m].len = len;
+            fr[m].b0 = cur->nb;
+            fr[m].idx = c;
+            fr[m].buf = (uint32_t)i;
+            fr[m].nb = (uint32_t)nb;
+            fr[m].k = k;
             if (k > 1u) cur->grouped = 1;
             if (bases && bases[i].d_ptr) cur->delta = 1;
-            cur->f1 = c + 1;
+            cur->f1 = ++m;
             cur->nb += nb;
             cur->bytes += len;
         }
@@ -1018,6 +1038,165 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
     *framesOut = fr;
     *partsOut = pt;
     *nPartsOut = nParts;
+    return 0;
+}
+
+/* ---- delta skip (QZSTD_frontSetDeltaSkip): chunks equal to their base chunk are found on the GPU before the parts are planned, and the
+ * library writes their frames itself */
+
+/* XXH64, seed 0, of len zero bytes: the reference algorithm with every input lane 0 (no buffer of zeros is needed) */
+static uint64_t qfRotl64(uint64_t v, unsigned r) { return (v << r) | (v >> (64u - r)); }
+static uint64_t qfXxh64Zeros(size_t len)
+{
+    const uint64_t P1 = 0x9E3779B185EBCA87ull, P2 = 0xC2B2AE3D27D4EB4Full, P3 = 0x165667B19E3779F9ull, P4 = 0x85EBCA77C2B2AE63ull,
+                   P5 = 0x27D4EB2F165667C5ull;
+    size_t n = len;
+    uint64_t h = P5;
+    if (len >= 32u) {
+        uint64_t v[4];
+        unsigned i;
+        v[0] = P1 + P2; v[1] = P2; v[2] = 0; v[3] = 0ull - P1;
+        for (; n >= 32u; n -= 32u)
+            for (i = 0; i < 4u; i++) v[i] = qfRotl64(v[i], 31) * P1; /* round(acc, 0) */
+        h = qfRotl64(v[0], 1) + qfRotl64(v[1], 7) + qfRotl64(v[2], 12) + qfRotl64(v[3], 18);
+        for (i = 0; i < 4u; i++) h = (h ^ (qfRotl64(v[i] * P2, 31) * P1)) * P1 + P4;
+    }
+    h += (uint64_t)len;
+    for (; n >= 8u; n -= 8u) h = qfRotl64(h, 27) * P1 + P4; /* h ^= round(0, 0) = 0 */
+    if (n >= 4u) { h = qfRotl64(h, 23) * P2 + P3; n -= 4u; }
+    for (; n; n--) h = qfRotl64(h, 11) * P1;
+    h ^= h >> 33; h *= P2; h ^= h >> 29; h *= P3; h ^= h >> 32;
+    return h;
+}
+
+/* the checksum field of a zero frame: computed once per distinct length while one length follows itself (a buffer's full chunks), and the
+ * length of a full chunk is kept apart from the tails' */
+typedef struct { size_t len[2]; uint32_t low[2]; } QF_ZeroHash;
+static uint32_t qfZeroHash(QF_ZeroHash *z, size_t chunk, size_t len)
+{
+    const int k = len == chunk ? 0 : 1;
+    if (z->len[k] != len) {
+        z->low[k] = (uint32_t)qfXxh64Zeros(len);
+        z->len[k] = len;
+    }
+    return z->low[k];
+}
+
+/* bytes the canonical zero frame of a chunk of len bytes takes at most (8-byte content size, checksum) */
+static size_t qfZeroFrameBound(size_t len) { return 4u + 1u + 8u + 4u * ((len + 131071u) / 131072u) + 4u; }
+
+/* THE CANONICAL ZERO FRAME of a chunk of len > 0 bytes, without its checksum field: magic, a frame header descriptor with Single_Segment and
+ * the smallest Frame_Content_Size field that holds len (and Content_Checksum_Flag when `checksum`), RLE_Blocks of the byte 0 cut every
+ * 128 KiB from the frame's start, Last_Block on the final one.  -> bytes written (out holds qfZeroFrameBound(len)) */
+static size_t qfZeroFrameBody(unsigned char *out, size_t len, int checksum)
+{
+    const unsigned long long L = (unsigned long long)len;
+    const unsigned code = L <= 255u ? 0u : (L <= 65791u ? 1u : (L <= 0xFFFFFFFFull ? 2u : 3u)), fcs = code == 0u ? 1u : 1u << code;
+    const unsigned long long v = code == 1u ? L - 256u : L;
+    size_t pos = 0, left = len;
+    unsigned i;
+    out[pos++] = 0x28; out[pos++] = 0xB5; out[pos++] = 0x2F; out[pos++] = 0xFD;
+    out[pos++] = (unsigned char)(code << 6 | 0x20u | (checksum ? 4u : 0u));
+    for (i = 0; i < fcs; i++) out[pos++] = (unsigned char)(v >> (8u * i));
+    while (left) {
+        const size_t n = left < 131072u ? left : 131072u;
+        const unsigned h = (unsigned)(n << 3) | 2u | (left == n ? 1u : 0u); /* Block_Size (the regenerated size), RLE_Block, Last_Block */
+        out[pos++] = (unsigned char)h; out[pos++] = (unsigned char)(h >> 8); out[pos++] = (unsigned char)(h >> 16);
+        out[pos++] = 0;
+        left -= n;
+    }
+    return pos;
+}
+
+/* the whole frame: with `checksum` the low 32 bits of XXH64 of len zero bytes behind the last block */
+static size_t qfZeroFrame(unsigned char *out, size_t len, int checksum, QF_ZeroHash *z, size_t chunk)
+{
+    size_t pos = qfZeroFrameBody(out, len, checksum);
+    if (checksum) {
+        const uint32_t h = qfZeroHash(z, chunk, len);
+        out[pos++] = (unsigned char)h; out[pos++] = (unsigned char)(h >> 8); out[pos++] = (unsigned char)(h >> 16); out[pos++] = (unsigned char)(h >> 24);
+    }
+    return pos;
+}
+
+/* 1 when the frame is byte for byte the canonical zero frame of a chunk of len bytes, with or without the checksum field (the frame's own
+ * flag says which); scratch holds qfZeroFrameBound(len) */
+static int qfIsZeroFrame(const unsigned char *fr, size_t frSize, size_t len, unsigned char *scratch, QF_ZeroHash *z, size_t chunk)
+{
+    const int ck = frSize > 4u && (fr[4] & 4u) != 0u;
+    size_t body;
+    if (frSize < 10u || frSize > qfZeroFrameBound(len)) return 0;
+    body = qfZeroFrameBody(scratch, len, ck);
+    if (frSize != body + (ck ? 4u : 0u) || memcmp(fr, scratch, body) != 0) return 0;
+    if (ck) {
+        const uint32_t h = qfZeroHash(z, chunk, len);
+        const unsigned char want[4] = { (unsigned char)h, (unsigned char)(h >> 8), (unsigned char)(h >> 16), (unsigned char)(h >> 24) };
+        if (memcmp(fr + body, want, 4) != 0) return 0;
+    }
+    return 1;
+}
+
+/* The pre-pass of a delta call with the setting on: ONE qzstd_hip_diff launch on the slot's stream (which already waits for the caller's),
+ * a row per frame of every buffer that has a base, the flags back in one copy, a bounded wait.  equal[c] (nFrames entries) becomes 1 for a
+ * frame whose chunk equals its base chunk — its canonical zero frame is written to dst here and its size to frameSizes — and 0 for every
+ * other frame, those of buffers without a base included: they are never compared. */
+static int qfDiffPass(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, size_t nBufs,
+                      size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes)
+{
+    const size_t chunk = f->p.chunkSize;
+    QF_ZeroHash z;
+    size_t i, off, c = 0, rows = 0, r = 0, nEqual = 0;
+    unsigned long long bytes = 0;
+    void *h;
+    memset(equal, 0, nFrames);
+    memset(&z, 0, sizeof(z));
+    for (i = 0; i < nBufs; i++)
+        if (bases[i].d_ptr) rows += bufs[i].size / chunk + (bufs[i].size % chunk != 0);
+    if (rows == 0) return 0;
+    if (rows > 0xFFFFFFFFu || chunk > 0xFFFFFFE0u) return -1; /* (a launch's rows and a row's length are 32-bit) */
+    if (qfZeroFrameBound(chunk) > f->stride) return -1;
+    h = s->hDiffRows;
+    if (qfGrowH(&h, &s->hDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t))) return -1;
+    s->hDiffRows = (qzstd_hip_diff_row_t *)h;
+    h = s->hDiffFlags;
+    if (qfGrowH(&h, &s->hDiffFlagsCap, rows * sizeof(uint32_t))) return -1;
+    s->hDiffFlags = (uint32_t *)h;
+    if (qfGrowD(dev, &s->dDiffRows, &s->dDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t)) ||
+        qfGrowD(dev, &s->dDiffFlags, &s->dDiffFlagsCap, rows * sizeof(uint32_t)))
+        return -1;
+    for (i = 0; i < nBufs; i++) {
+        if (!bases[i].d_ptr) continue;
+        for (off = 0; off < bufs[i].size; off += chunk, r++) {
+            qzstd_hip_diff_row_t *row = &s->hDiffRows[r];
+            row->a = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
+            row->b = (uint64_t)(uintptr_t)((const unsigned char *)bases[i].d_ptr + off);
+            row->len = (uint32_t)(bufs[i].size - off < chunk ? bufs[i].size - off : chunk);
+            row->tile0 = 0;
+            bytes += row->len;
+        }
+    }
+    if (qzstd_hip_diff(dev, s->stream, s->hDiffRows, (uint32_t)rows, (qzstd_hip_diff_row_t *)s->dDiffRows, (uint32_t *)s->dDiffFlags) ||
+        qzstd_hip_memcpy_d2h(dev, s->stream, s->hDiffFlags, s->dDiffFlags, rows * sizeof(uint32_t)))
+        return -1;
+    if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
+        (void)qzstd_hip_stream_sync(dev, s->stream); /* the launch still reads the caller's buffers */
+        return -1;
+    }
+    for (i = 0, r = 0; i < nBufs; i++) {
+        const size_t nf = bufs[i].size / chunk + (bufs[i].size % chunk != 0);
+        if (bases[i].d_ptr) {
+            for (off = 0; off < nf; off++, r++) {
+                if (s->hDiffFlags[r]) continue;
+                equal[c + off] = 1;
+                frameSizes[c + off] = qfZeroFrame(dst + (c + off) * f->stride, s->hDiffRows[r].len, f->checksum, &z, chunk);
+                nEqual++;
+            }
+        }
+        c += nf;
+    }
+    __atomic_fetch_add(&f->skipStats[0], (unsigned long long)rows, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->skipStats[1], (unsigned long long)nEqual, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->skipStats[2], bytes, __ATOMIC_RELAXED);
     return 0;
 }
 
@@ -1034,7 +1213,8 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     void *ev = NULL;
     size_t nFrames, nParts = 0, k, i, total = 0;
     unsigned group;
-    int rc = 0, anyGrouped = 0, anyBase = 0;
+    unsigned char *equal = NULL;
+    int rc = 0, anyGrouped = 0, anyBase = 0, skip;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
@@ -1062,6 +1242,8 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
     if (anyGrouped && !qzstd_hip_group) return (size_t)-1;  /* byte grouping wanted and a device layer that cannot group */
     if (bases && !qzstd_hip_group_xor) return (size_t)-1;   /* a base given and a device layer that cannot XOR one in */
+    skip = bases && f->deltaSkip;
+    if (skip && !qzstd_hip_diff) return (size_t)-1;         /* delta skip wanted and a device layer that cannot compare */
     j.dev = -1;
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
@@ -1099,14 +1281,6 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
-        const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        rc = qfPlanDevice(f, bufs, bases, elemSizes, group, nBufs, nFrames, want, j.blk, &frames, &parts, &nParts);
-    }
-    j.frames = frames;
-    j.parts = parts;
-    j.nParts = nParts;
-    {
         const char *rep = getenv("QZSTD_HIP_EXT_REPCODES"); /* the producer path's level flags (QZSTD_startQatDevice) */
         j.level = f->p.level | ((rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0);
     }
@@ -1123,9 +1297,23 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (rc == 0 && (qzstd_hip_event_record(j.dev, ev, stream) || qzstd_hip_stream_wait_event(j.dev, slot[0].stream, ev) ||
                     qzstd_hip_stream_wait_event(j.dev, slot[1].stream, ev)))
         rc = -1;
-    /* two parts on the GPU ahead of the one being entropy-coded: part p lives on slot p % 2 from its queueing to its fetch */
+    /* delta skip: the chunks equal to their base chunk are found first and get their zero frames; the parts are planned without them */
+    if (rc == 0 && skip) {
+        if (!(equal = (unsigned char *)malloc(nFrames))) rc = -1;
+        else rc = qfDiffPass(f, &slot[0], j.dev, bufs, bases, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes);
+    }
+    if (rc == 0) {
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
+        const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
+        rc = qfPlanDevice(f, bufs, bases, elemSizes, group, nBufs, equal, nFrames, want, j.blk, &frames, &parts, &nParts);
+    }
+    j.frames = frames;
+    j.parts = parts;
+    j.nParts = nParts;
+    /* two parts on the GPU ahead of the one being entropy-coded: part p lives on slot p % 2 from its queueing to its fetch (no part at all
+     * when every frame of the call was equal to its base: nothing is staged, matched, copied or handed to the workers) */
     for (k = 0; k < 2 && k < nParts && rc == 0; k++) rc = qfQueuePart(&j, &slot[k], &parts[k]);
-    if (rc == 0) rc = qfFetchPart(&j, &slot[0], &parts[0], &part[0]);
+    if (rc == 0 && nParts) rc = qfFetchPart(&j, &slot[0], &parts[0], &part[0]);
     for (k = 0; k < nParts && rc == 0; k++) {
         int failed;
         /* slot k % 2 is fetched: its device side takes part k + 2 while the workers read its pinned arena — not the device buffers */
@@ -1158,6 +1346,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (ev) qzstd_hip_event_destroy(j.dev, ev);
     free(frames);
     free(parts);
+    free(equal);
     if (rc == 0) __atomic_fetch_add(&f->devStats[3], (unsigned long long)total, __ATOMIC_RELAXED);
     pthread_mutex_lock(&f->mu);
     f->devBusy = 0;
@@ -1244,6 +1433,26 @@ void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4])
     int k;
     if (!stats) return;
     for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->deltaStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+int QZSTD_frontSetDeltaSkip(QZSTD_Front *f, int on)
+{
+    int busy;
+    if (!f) return -1;
+    pthread_mutex_lock(&f->mu);
+    busy = f->devBusy || f->running;
+    if (!busy) f->deltaSkip = on != 0;
+    pthread_mutex_unlock(&f->mu);
+    return busy ? -1 : 0;
+}
+
+int QZSTD_frontGetDeltaSkip(const QZSTD_Front *f) { return f ? f->deltaSkip : 0; }
+
+void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->skipStats[k], __ATOMIC_RELAXED) : 0ull;
 }
 
 /* The byte-grouped layout, its block rule and qzbgRebuild: a source of their own, free of HIP and libzstd (the tests build it alone), and

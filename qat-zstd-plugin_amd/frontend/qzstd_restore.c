@@ -13,7 +13,9 @@
  * A slot's pinned buffer and rows are written again only after its stream has passed the copy and the launch that read them.
  * QZSTD_frontRestoreDeviceBatchDelta: a part with a frame whose buffer has a base is scattered by ONE qzstd_hip_ungroup_xor launch instead (base 0
  * for the rows without one): the frames' content is chunk XOR base chunk, and the base — which may be the destination itself — is XORed back
- * in on the way out.  Decoding, the pinned buffers and the copy are the same.
+ * in on the way out.  Decoding, the pinned buffers and the copy are the same.  With QZSTD_frontSetDeltaSkip on, a frame of a based buffer that
+ * IS the canonical zero frame of its chunk's length (qfIsZeroFrame, qzstd_frontend.c) is left out of the table and the parts: in place
+ * nothing happens for it, otherwise a run of such frames is one device->device copy from the base.
  * QZSTD_frontRestoreDeviceSlices (below the whole-buffer calls): byte ranges of the written buffers; only the frames they intersect are decoded,
  * cut into parts the same way, and a part is scattered by ONE qzstd_hip_ungroup_window launch, a row per piece (slice x frame).
  * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
@@ -38,6 +40,7 @@ typedef struct {
 } QF_RestoreFrame;
 
 typedef struct { size_t f0, f1, bytes, stage, based; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames), frames with a base */
+typedef struct { unsigned char *d_dst; const unsigned char *d_src; size_t len; } QF_ZeroRun; /* consecutive recognised zero frames of one buffer: base -> destination */
 
 struct QF_RestoreSlot_s {
     void *stream;
@@ -99,11 +102,14 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
 {
     QF_RestoreFrame *table = NULL;
     QF_RestoreRange *parts = NULL;
+    QF_ZeroRun *runs = NULL; /* delta skip: what the recognised zero frames leave to do, a device->device copy per run */
+    unsigned char *scratch = NULL;
+    QF_ZeroHash zh;
     QF_RestoreSlot *slot;
     struct QF_RestorePart_s part;
     void *ev = NULL;
-    size_t i, c = 0, k, nParts = 0, want = 0, partBytes, pos = 0;
-    int dev = -1, rc = 0, anyBase = 0;
+    size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nRuns = 0, nZero = 0;
+    int dev = -1, rc = 0, anyBase = 0, skip;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
@@ -149,28 +155,51 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
     table = (QF_RestoreFrame *)malloc(nFrames * sizeof(*table));
     parts = (QF_RestoreRange *)malloc(nFrames * sizeof(*parts));
     if (!table || !parts) rc = -1;
+    /* delta skip: a frame of a buffer with a base that IS the canonical zero frame of its chunk's length says "equal to the base" — it is not
+     * decoded and gets no place in the table (frame m of the table is the m-th remaining one), in the pinned buffer or in the stage */
+    skip = bases && f->deltaSkip && qzstd_hip_memcpy2d_d2d;
+    memset(&zh, 0, sizeof(zh));
+    if (skip && rc == 0) {
+        runs = (QF_ZeroRun *)malloc(nFrames * sizeof(*runs));
+        scratch = (unsigned char *)malloc(qfZeroFrameBound(f->p.chunkSize));
+        if (!runs || !scratch) rc = -1;
+    }
     for (i = 0; i < nBufs && rc == 0; i++) {
         const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
-        size_t off;
-        for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
+        const unsigned char *base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr : NULL;
+        size_t off, lastZero = nFrames; /* the last recognised frame of this buffer (nFrames: none yet) */
+        for (off = 0; off < bufs[i].size; off += f->p.chunkSize, pos += frameSizes[c], c++) {
             const size_t len = bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize;
+            const unsigned char *src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
             QF_RestoreRange *cur = nParts ? &parts[nParts - 1] : NULL;
+            if (skip && base && qfIsZeroFrame(src, frameSizes[c], len, scratch, &zh, f->p.chunkSize)) {
+                nZero++;
+                if (base == (const unsigned char *)bufs[i].d_ptr) continue; /* in place: the chunk is what it shall be */
+                if (lastZero == c - 1u) {
+                    runs[nRuns - 1].len += len; /* consecutive chunks: one copy */
+                } else {
+                    runs[nRuns].d_dst = (unsigned char *)bufs[i].d_ptr + off;
+                    runs[nRuns].d_src = base + off;
+                    runs[nRuns++].len = len;
+                }
+                lastZero = c;
+                continue;
+            }
             if (len > 0xFFFFFFE0u || (cur && cur->f1 - cur->f0 >= 0xFFFFFFFFu)) { rc = -1; break; } /* (a row's length and a launch's rows are 32-bit) */
             if (!cur || cur->bytes + len > partBytes) {
                 cur = &parts[nParts++];
-                cur->f0 = c;
+                cur->f0 = m;
                 cur->bytes = cur->stage = cur->based = 0;
             }
-            table[c].src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
-            table[c].srcSize = frameSizes[c];
-            table[c].d_dst = (unsigned char *)bufs[i].d_ptr + off;
-            table[c].d_base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr + off : NULL;
-            if (table[c].d_base) cur->based++;
-            table[c].len = len;
-            table[c].at = cur->stage;
-            table[c].k = e;
-            pos += frameSizes[c];
-            cur->f1 = c + 1;
+            table[m].src = src;
+            table[m].srcSize = frameSizes[c];
+            table[m].d_dst = (unsigned char *)bufs[i].d_ptr + off;
+            table[m].d_base = base ? base + off : NULL;
+            if (table[m].d_base) cur->based++;
+            table[m].len = len;
+            table[m].at = cur->stage;
+            table[m].k = e;
+            cur->f1 = ++m;
             cur->bytes += len;
             cur->stage += qfPad16(len);
         }
@@ -187,6 +216,16 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
     if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
                     qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
         rc = -1;
+    /* the recognised frames that are not restored in place: base -> destination, one copy per run of consecutive chunks (a wholly frozen
+     * tensor: one copy; a run above 1 GiB is cut there, below the 2D copy's largest pitch), on the slots' streams in turn; the destinations
+     * are no other frame's */
+    for (k = 0; k < nRuns && rc == 0; k++) {
+        size_t at;
+        for (at = 0; at < runs[k].len && rc == 0; at += (size_t)1 << 30) {
+            const size_t n = runs[k].len - at < ((size_t)1 << 30) ? runs[k].len - at : (size_t)1 << 30;
+            if (qzstd_hip_memcpy2d_d2d(dev, slot[k % 2].stream, runs[k].d_dst + at, n, runs[k].d_src + at, n, n, 1)) rc = -1;
+        }
+    }
     for (k = 0; k < nParts && rc == 0; k++) {
         const QF_RestoreRange *pr = &parts[k];
         const size_t nf = pr->f1 - pr->f0;
@@ -257,8 +296,11 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         }
     }
     if (ev) qzstd_hip_event_destroy(dev, ev);
+    if (rc == 0) __atomic_fetch_add(&f->skipStats[3], (unsigned long long)nZero, __ATOMIC_RELAXED);
     free(table);
     free(parts);
+    free(runs);
+    free(scratch);
     pthread_mutex_lock(&f->mu);
     f->devBusy = 0;
     pthread_mutex_unlock(&f->mu);

@@ -69,6 +69,16 @@ frames decoded, bytes host->device and torch's peak extra device memory:
 windows and as the column shard's 2 KiB windows, for each element size 1, 2, 4, 8: the run to put under rocprofv3.
 
   python tools/device_bench.py --slices --gib 1 --reps 3 [--kernels]
+
+--skip: delta skip (QZSTD_frontSetDeltaSkip) — N GiB of bf16 N(0, 0.02) weights as 64 tensors against their bases; a share p of 0, 0.5, 0.9
+and 1 of the tensors is identical to its base and the rest has taken the delta leg's N(0, 1e-5) update.  Levels 1 and 6, the setting off and
+on alternating in one run, every run listed: the delta compress call, the delta restore in place over a copy of the bases and into fresh
+tensors (off: the setting-off call's frames, the setting off; on: the setting-on call's frames, the setting on); GB/s of input, compressed
+bytes, bytes device->host and host->device per input byte.
+--kernels: through the C ABI, nothing timed: qzstd_hip_diff over N GiB of 128 KiB rows (equal, different, and b at another alignment than
+a), then qzstd_hip_group_xor over the same rows: the run to put under rocprofv3.
+
+  python tools/device_bench.py --skip --gib 1 --reps 3 [--levels 1,6] [--kernels]
 """
 import argparse
 import json
@@ -671,8 +681,144 @@ def slices_main(a):
     print(json.dumps(out))
 
 
+def skip_kernels(a, size):
+    """through the C ABI, nothing timed: qzstd_hip_diff over N GiB of 128 KiB rows (equal rows, rows that differ, and a and b at different
+    alignments mod 16), and qzstd_hip_group_xor over the same rows for element size 2: the run to put under rocprofv3"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_diff_kernel(D.bind_xor_kernels(plug.lib))
+    n = size // a.chunk
+    src = torch.randint(0, 256, (size + 16,), dtype=torch.uint8, device="cuda:0")
+    same = src.clone()
+    other = torch.randint(0, 256, (size + 16,), dtype=torch.uint8, device="cuda:0")
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    flags = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.GroupXorRow))
+    assert d_rows and stage.data_ptr() % 16 == 0
+    try:
+        for name, b, skew, want in (("equal", same, 0, 0), ("different", other, 0, 1), ("equal, b 7 bytes off", same, 7, 0)):
+            rows = (D.DiffRow * n)()
+            if skew:
+                b = torch.empty_like(same)
+                b[skew:] = same[:-skew]
+            for c in range(n):
+                rows[c].a, rows[c].b, rows[c].len = src.data_ptr() + c * a.chunk, b.data_ptr() + skew + c * a.chunk, a.chunk
+            torch.cuda.synchronize()
+            assert L.qzstd_hip_diff(0, None, rows, n, d_rows, flags.data_ptr()) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert bool((flags == want).all()), name
+        gx = (D.GroupXorRow * n)()
+        for c in range(n):
+            o = c * a.chunk
+            gx[c].src, gx[c].base, gx[c].dstOff, gx[c].len, gx[c].pad, gx[c].elem = src.data_ptr() + o, other.data_ptr() + o, o, a.chunk, 0, 2
+        assert L.qzstd_hip_group_xor(0, None, gx, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+        plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps({"bytes": size, "passes": "qzstd_hip_diff over %d rows of %d bytes: equal, different, equal with b 7 bytes off; then qzstd_hip_group_xor "
+                                               "(element size 2) over the same rows" % (n, a.chunk)}))
+
+
+def skip_main(a):
+    """--skip: delta skip (QZSTD_frontSetDeltaSkip) on a checkpoint of which a share did not change"""
+    import ctypes as C
+    size = int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1)
+    if a.kernels:
+        return skip_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    nt, per = 64, size // 64
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "tensors": nt, "tensor_bytes": per, "step": 1e-5, "dtype": "bf16", "cells": {},
+           "timed": "the calls and the closing synchronize; GB/s of input (compress) and of restored content (restore), every run of %d, the setting "
+                    "off and on alternating; restore: off = the setting-off call's frames restored with the setting off, on = the setting-on call's "
+                    "frames restored with the setting on; in place over a copy of the bases (refilled outside the window) and into fresh tensors" % a.reps,
+           "d2h": "QZSTD_frontDeviceStats [2] per input byte; the on leg's flags (4 bytes per compared frame) are listed apart as flag_bytes"}
+    bases = [(torch.randn(per // 2, device="cuda:0") * 0.02).to(torch.bfloat16) for _ in range(nt)]
+    stepped = [(b.float() + torch.randn(per // 2, device="cuda:0") * 1e-5).to(torch.bfloat16) for b in bases]
+    work = [torch.empty_like(b) for b in bases]
+    fresh = [torch.empty_like(b) for b in bases]
+    n = size // a.chunk
+    for share in (0.0, 0.5, 0.9, 1.0):
+        frozen = [int((i + 1) * share) > int(i * share) for i in range(nt)]  # evenly spread
+        new = [b if fz else s for b, s, fz in zip(bases, stepped, frozen)]
+        assert all(fz or not torch.equal(x, b) for x, b, fz in zip(new, bases, frozen))
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            cell = out["cells"]["p=%g,level=%d" % (share, level)] = {"frozen_tensors": sum(frozen)}
+            try:
+                fr.reserve(size)
+                es = bytes([2] * nt) + b"\0"
+                bufs_new, _, _ = fr.batch([(x.data_ptr(), per) for x in new])
+                bufs_base, _, _ = fr.batch([(x.data_ptr(), per) for x in bases])
+                bufs_work, _, _ = fr.batch([(x.data_ptr(), per) for x in work])
+                out_work = fr.out_batch([(x.data_ptr(), per) for x in work])
+                out_fresh = fr.out_batch([(x.data_ptr(), per) for x in fresh])
+                _, sizes = fr._frame_buffers(n)
+                kept = {}
+
+                def compress(on):
+                    assert fr.set_delta_skip(on) == 0
+                    return fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, bufs_new, bufs_base, es, nt, stream, fr._dst, len(fr._dst), sizes, None)
+
+                def restore(on, in_place):
+                    buf, sz = kept[on]
+                    assert fr.set_delta_skip(on) == 0
+                    return fr.lib.QZSTD_frontRestoreDeviceBatchDelta(fr.f, buf, fr.stride, sz, n, out_work if in_place else out_fresh,
+                                                                     bufs_work if in_place else bufs_base, es, nt, stream)
+
+                for on in (0, 1):  # untimed: the slots, and what each setting leaves
+                    s0, k0 = fr.stats(), fr.delta_skip_stats()
+                    assert compress(on) == n
+                    s1, k1 = fr.stats(), fr.delta_skip_stats()
+                    tag = "on" if on else "off"
+                    cell["compressed_" + tag] = sum(sizes[c] for c in range(n))
+                    cell["d2h_bytes_per_input_byte_" + tag] = round((s1[2] - s0[2]) / size, 5)
+                    if on:
+                        cell["flag_bytes"] = 4 * (k1[0] - k0[0])
+                        cell["frames_compared_equal"] = [k1[0] - k0[0], k1[1] - k0[1]]
+                    buf = C.create_string_buffer(n * fr.stride)
+                    C.memmove(buf, fr._dst, n * fr.stride)
+                    kept[on] = (buf, (C.c_size_t * n)(*sizes[:n]))
+                runs = {"compress_off_gbps": [], "compress_on_gbps": [], "restore_in_place_off_gbps": [], "restore_in_place_on_gbps": [],
+                        "restore_fresh_off_gbps": [], "restore_fresh_on_gbps": []}
+                for _ in range(a.reps):
+                    for on in (0, 1):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert compress(on) == n
+                        torch.cuda.synchronize()
+                        runs["compress_%s_gbps" % ("on" if on else "off")].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+                for in_place in (True, False):
+                    where = "in_place" if in_place else "fresh"
+                    for on in (0, 1):  # untimed, and checked
+                        for w, b in zip(work, bases):
+                            w.copy_(b)
+                        r0 = fr.restore_stats()
+                        assert restore(on, in_place) == n
+                        torch.cuda.synchronize()
+                        cell["h2d_bytes_per_input_byte_%s_%s" % (where, "on" if on else "off")] = round((fr.restore_stats()[2] - r0[2]) / size, 5)
+                        assert all(torch.equal(g, x) for g, x in zip(work if in_place else fresh, new)), (share, level, where, on)
+                    for _ in range(a.reps):
+                        for on in (0, 1):
+                            for w, b in zip(work, bases):
+                                w.copy_(b)
+                            torch.cuda.synchronize()
+                            t0 = time.perf_counter()
+                            assert restore(on, in_place) == n
+                            torch.cuda.synchronize()
+                            runs["restore_%s_%s_gbps" % (where, "on" if on else "off")].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+                cell.update(runs)
+            finally:
+                fr.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--skip", action="store_true")
     ap.add_argument("--slices", action="store_true")
     ap.add_argument("--delta", action="store_true")
     ap.add_argument("--restore", action="store_true")
@@ -690,6 +836,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.skip:
+        if a.levels == "1,6,12":
+            a.levels = "1,6"
+        return skip_main(a)
     if a.slices:
         return slices_main(a)
     if a.delta:

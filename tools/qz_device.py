@@ -2,7 +2,8 @@
 QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, QZSTD_frontSetByteGroup, QZSTD_frontCompressDeviceBatchTyped)
 and of the way back (QZSTD_frontRestoreDeviceBatchTyped, QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats: DeviceFront.restore_batch),
 the delta calls against a base per buffer (QZSTD_frontCompressDeviceBatchDelta, QZSTD_frontRestoreDeviceBatchDelta, QZSTD_frontDeltaStats:
-DeviceFront.compress_device_batch_delta / restore_batch_delta), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
+DeviceFront.compress_device_batch_delta / restore_batch_delta), delta skip (QZSTD_frontSetDeltaSkip, QZSTD_frontDeltaSkipStats:
+DeviceFront.set_delta_skip / delta_skip_stats; qzstd_hip_diff's row, binding and numpy reference; zero_frame()), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
 QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
@@ -60,6 +61,49 @@ class UngroupWinRow(C.Structure):
     """qzstd_hip_ungroup_win_row_t (include/qzstd_hip_device.h)"""
     _fields_ = [("dst", C.c_uint64), ("base", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32),
                 ("winOff", C.c_uint32), ("winLen", C.c_uint32), ("tile0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DiffRow(C.Structure):
+    """qzstd_hip_diff_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("a", C.c_uint64), ("b", C.c_uint64), ("len", C.c_uint32), ("tile0", C.c_uint32)]
+
+
+def bind_diff_kernel(L):
+    """qzstd_hip_diff on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_diff.restype = C.c_int
+    L.qzstd_hip_diff.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    return L
+
+
+def diff_flags_ref(pairs):
+    """what qzstd_hip_diff must leave in d_flags: per (a, b) — two numpy uint8 arrays of one length — 1 when any byte differs, else 0"""
+    import numpy as np
+    return np.array([1 if len(a) and not np.array_equal(a, b) else 0 for a, b in pairs], dtype=np.uint32)
+
+
+def diff_tile0_ref(lens):
+    """the tile0 the launcher writes: workgroups (16 KiB tiles) of the rows before each one"""
+    out, total = [], 0
+    for n in lens:
+        out.append(total)
+        total += (n + 16383) >> 14
+    return out
+
+
+def zero_frame(n: int, checksum: bool = False) -> bytes:
+    """THE CANONICAL ZERO FRAME of a chunk of n > 0 bytes (include/qzstd_frontend_device.h, QZSTD_frontSetDeltaSkip), without its checksum
+    field: magic, Single_Segment with the smallest Frame_Content_Size field that holds n (Content_Checksum_Flag when `checksum`), RLE blocks
+    of the byte 0 every 128 KiB, Last_Block on the final one.  With `checksum` the caller appends XXH64(n zero bytes) & 0xFFFFFFFF, little-endian"""
+    code = 0 if n <= 255 else (1 if n <= 65791 else (2 if n <= 0xFFFFFFFF else 3))
+    out = bytearray(b"\x28\xb5\x2f\xfd")
+    out.append(code << 6 | 0x20 | (4 if checksum else 0))
+    out += (n - 256 if code == 1 else n).to_bytes((1, 2, 4, 8)[code], "little")
+    left = n
+    while left:
+        b = min(left, 131072)
+        out += (b << 3 | 2 | (1 if b == left else 0)).to_bytes(3, "little") + b"\0"
+        left -= b
+    return bytes(out)
 
 
 class DeviceSlice(C.Structure):
@@ -158,6 +202,13 @@ def bind(F):
                                                      C.c_char_p, C.c_size_t, C.POINTER(DeviceSlice), C.c_size_t, C.c_void_p]
         F.QZSTD_frontSliceStats.restype = None
         F.QZSTD_frontSliceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontSetDeltaSkip"):  # (absent from an older library)
+        F.QZSTD_frontSetDeltaSkip.restype = C.c_int
+        F.QZSTD_frontSetDeltaSkip.argtypes = [C.c_void_p, C.c_int]
+        F.QZSTD_frontGetDeltaSkip.restype = C.c_int
+        F.QZSTD_frontGetDeltaSkip.argtypes = [C.c_void_p]
+        F.QZSTD_frontDeltaSkipStats.restype = None
+        F.QZSTD_frontDeltaSkipStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -343,6 +394,21 @@ class DeviceFront:
         """frames with a base built from [0] sequences + literals, [1] rebuilt content, [2] both buffers copied back; [3] frames restored onto a base"""
         st = (C.c_ulonglong * 4)()
         self.lib.QZSTD_frontDeltaStats(self.f, st)
+        return list(st)
+
+    def set_delta_skip(self, on) -> int:
+        """QZSTD_frontSetDeltaSkip: the delta calls that follow find chunks equal to their base chunk on the GPU and skip them -> 0, or -1
+        while a call runs"""
+        return self.lib.QZSTD_frontSetDeltaSkip(self.f, 1 if on else 0)
+
+    def get_delta_skip(self) -> int:
+        return self.lib.QZSTD_frontGetDeltaSkip(self.f)
+
+    def delta_skip_stats(self) -> list:
+        """[0] frames compared with their base chunk, [1] of them found equal (written as zero frames), [2] bytes compared, [3] zero frames
+        a restore recognised"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontDeltaSkipStats(self.f, st)
         return list(st)
 
     def compress_device_batch(self, ptrs_and_sizes, stream: int | None = None) -> list:
