@@ -238,6 +238,38 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
 /* since creation: [0] non-empty slices restored, [1] bytes written to destinations, [2] frames decoded for them, [3] rows launched */
 void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Verify: do the frames just written reproduce the tensors that are on the device NOW — asked before the previous checkpoint is dropped?  A
+ * delta frame is only as good as the base it is applied to and the element size it is ungrouped with, and neither is in the frame; a content
+ * checksum covers the grouped delta, not the tensor.  A mistake in the caller's bookkeeping (another base, another element size, frames in
+ * another order) and a tensor that changed while the compress call ran both pass libzstd's check and fail this one.
+ *
+ * The arguments are QZSTD_frontRestoreDeviceBatchDelta's, with bufs CONST: the live tensors, compared and never written.  bases == NULL (or no
+ * base among them) makes the call the Typed counterpart.  Per part the restore's slots and the workers' decode are used as they are; then ONE
+ * host->device copy, ONE qzstd_hip_ungroup_cmp launch (the frames ungrouped, XORed with their base chunks and compared with the live chunks in
+ * registers: nothing is stored but one word per 16 KiB) and one device->host copy of those words.  No temporary of the buffers' size exists,
+ * and nothing on the device but the library's own stage and result buffers is written.  bases[i].d_ptr == bufs[i].d_ptr is accepted and
+ * compares the frames' content with zero.  With QZSTD_frontSetDeltaSkip on, a frame of a based buffer that is the canonical zero frame of its
+ * chunk's length is not decoded and takes no room in the pinned buffer or the copy: its live chunk is compared with its base chunk directly,
+ * by the same launch (a call whose frames are all such frames still launches); with the setting off it is decoded like any other frame.
+ *
+ * Returns the NUMBER OF FRAMES THAT DIFFER — 0: the checkpoint reproduces the tensors — or (size_t)-1.  firstDiff (nFrames entries, or NULL):
+ * firstDiff[c] is QZSTD_VERIFY_SAME, or the lowest byte offset inside frame c's chunk at which the restored value differs from the live one.
+ * Blocks until done.  `stream` must order the last writer of the tensors and of the bases.
+ * (size_t)-1 before anything is queued: everything QZSTD_frontRestoreDeviceBatchDelta refuses (the nFrames rule, element sizes, pointers that
+ * are not device memory of one device, a call while another one runs on this front; a front created with useProducer = 0 is accepted), and a
+ * device layer without qzstd_hip_ungroup_cmp — every other call is served by such a layer as before.  After work has started: a frame that
+ * does not decode, decodes to another length or fails its checksum; with firstDiff given at least the frame a worker stopped at then holds
+ * QZSTD_VERIFY_UNDECODED, the other entries are unspecified, and nothing of the library's is still running on the GPU when the call returns.
+ * QZSTD_frontRestoreStats, QZSTD_frontDeltaStats and QZSTD_frontDeltaSkipStats do not count this call. */
+#define QZSTD_VERIFY_SAME      ((size_t)-1)
+#define QZSTD_VERIFY_UNDECODED ((size_t)-2)
+size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                    const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                                    void *stream, size_t *firstDiff /* nFrames entries, or NULL */);
+/* since creation, of the parts that were queued: [0] frames compared, [1] of them differing, [2] content bytes compared, [3] qzstd_hip_ungroup_cmp
+ * launches (one per part) */
+void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 #if defined(__cplusplus)
 }
 #endif

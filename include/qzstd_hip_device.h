@@ -3,7 +3,8 @@
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
  * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
- * the comparison of rows with their bases (QZSTD_frontSetDeltaSkip), and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
+ * and the content-checksum kernel (QZSTD_frontSetChecksum).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -215,6 +216,50 @@ typedef struct {
 } qzstd_hip_ungroup_win_row_t;
 int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows,
                              qzstd_hip_ungroup_win_row_t *d_rows, const void *d_stage, size_t stageBytes);
+
+/*
+ * Ungrouping comparison (QZSTD_frontVerifyDeviceBatch): qzstd_hip_ungroup_xor with its store replaced by a comparison — does a staged frame,
+ * ungrouped and XORed with its base, reproduce the LIVE bytes at `ref`?  With u[] the frame's ungrouped content exactly as qzstd_hip_ungroup
+ * defines it (u[e * k + j] = stage[srcOff + j * n + e] for k = elem, n = len / k; the len - n * k tail bytes unchanged), and u[] all zeros for a
+ * ZERO row (flags bit 0: a recognised canonical zero frame — the stage is not read and srcOff not looked at), a row MATCHES when
+ * u[i] ^ base[i] == ref[i] for every i < len; base 0 means no XOR.  ref == base is allowed (u[] is compared with zero).
+ *
+ * Work is divided as in the window and diff kernels: a workgroup per 16 KiB tile of u[] — QZSTD_HIP_CMP_TILES(len, elem) of them: the tail
+ * goes with the last tile, a frame shorter than elem is one tile, an empty row has none.  The launcher writes tile0 (the running sum of the
+ * rows' workgroups) into the caller's rows before the upload; a workgroup finds its row by a binary search over it.  Every workgroup stores
+ * ONE word: d_tiles[tile0 + t] = QZSTD_HIP_CMP_SAME when its share of the row matches, else the lowest differing row offset i it saw; the
+ * host takes the first entry of a row that is not QZSTD_HIP_CMP_SAME.  d_tiles holds the sum of the rows' QZSTD_HIP_CMP_TILES words.
+ *
+ * No atomics, no memset; nothing but d_tiles[0 .. total tiles) is written — ref, base and the stage are only read.  ref and base are read
+ * with aligned 16-byte loads of the words that overlap [p, p + len) and of no other word, each shifted into place by its own misalignment;
+ * stage loads are aligned 16-byte loads inside [srcOff, srcOff + pad16(len)) of the row; the bytes of a first or last word that lie outside
+ * the row never influence the result; every byte of [0, len) is compared by some lane.  The lowest differing offset of a tile is found with
+ * a wave min and one LDS step across the four waves.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_tiles, a null d_stage with a row that is neither ZERO nor empty, d_stage not 16-aligned, an
+ * elem outside {1, 2, 4, 8}, a flags bit other than bit 0, a null ref with len > 0, len > 0xFFFFFFE0, more than 2^31 - 1 workgroups, and for
+ * the rows that are not ZERO: a srcOff that is no multiple of 16, a frame that ends past stageBytes, frames out of ascending stage order or
+ * overlapping (srcOff >= the previous such row's srcOff + pad16(len)).  No value of `base` is refused.  nRows == 0, or only empty rows:
+ * nothing is queued, 0.  Asynchronous on `stream`.
+ */
+#define QZSTD_HIP_CMP_SAME 0xFFFFFFFFu
+#define QZSTD_HIP_CMP_ZERO 1u /* flags bit 0 */
+/* workgroups of a row = its words in d_tiles */
+#define QZSTD_HIP_CMP_TILES(len, elem)                                                                                    \
+    ((uint64_t)(len) / (elem) ? ((uint64_t)(len) / (elem) + 16384u / (elem) - 1u) / (16384u / (elem)) : (uint64_t)((len) ? 1u : 0u))
+typedef struct {
+    uint64_t ref;    /* device address of the `len` live bytes to compare with, any alignment */
+    uint64_t base;   /* device address of `len` bytes XORed in first, any alignment, also another one mod 16 than ref; 0 = none */
+    uint64_t srcOff; /* the frame's offset in d_stage, a multiple of 16 (not looked at for a ZERO row) */
+    uint32_t len;    /* content bytes, may be 0 */
+    uint32_t elem;   /* 1, 2, 4 or 8: the grouped layout the frame lies in */
+    uint32_t flags;  /* QZSTD_HIP_CMP_ZERO: the frame's content is `len` zero bytes and the stage is not read; other bits 0 */
+    uint32_t tile0;  /* written by the launcher: workgroups of the rows before this one */
+} qzstd_hip_ungroup_cmp_row_t;
+int qzstd_hip_ungroup_cmp(int device, void *stream, qzstd_hip_ungroup_cmp_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_cmp_row_t *d_rows,
+                          const void *d_stage, size_t stageBytes, uint32_t *d_tiles);
 
 /*
  * Comparison with a base (QZSTD_frontSetDeltaSkip): ONE launch compares every row's two byte ranges — d_flags[i] = 1 when any of the `len`

@@ -2,7 +2,7 @@
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
  * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
- * windows of the staged frames (slices), the comparison of rows with their bases (delta skip), and the XXH64 content checksum.  They use nothing of the match-finder
+ * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), and the XXH64 content checksum.  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -1070,9 +1070,152 @@ extern "C" int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungr
     return 0;
 }
 
+/* ---------------------------------------------------------------- ungrouping comparison (include/qzstd_hip_device.h) -- */
+namespace {
+constexpr uint32_t kCmpSame = 0xFFFFFFFFu; /* a tile word: nothing differs */
+
+/* the first `valid` (1 .. 16) of the 16 bytes {o1, o0}; the others become 0 */
+__device__ inline void cmp_mask(uint32_t valid, uint64_t *o0, uint64_t *o1)
+{
+    if (valid >= 16u) return;
+    *o1 = valid > 8u ? *o1 & ((1ull << ((valid - 8u) * 8u)) - 1ull) : 0ull;
+    if (valid < 8u) *o0 &= (1ull << (valid * 8u)) - 1ull;
+}
+
+/* qzstd_ungroup_xor_kernel with its store replaced by a comparison.  One workgroup per 16 KiB tile of a frame's ungrouped content u[] (the tail
+ * with the last tile, a frame shorter than an element one tile); its row is the last one with tile0 <= blockIdx.x (qzstd_ungroup_window_kernel's
+ * search).  Phase A is ungroup_load: the tile's plane strips, stage to LDS — nothing for a ZERO row, whose u[] is zeros and whose stage is
+ * never read.  Phase B walks the tile's bytes [t0, t1) of u[] in 16-byte steps FROM THE TILE'S START (nothing is stored, so no side's
+ * alignment has to be met): a lane assembles u's 16 bytes with ungroup_word, takes the few bytes behind the strips' end — the tail — singly
+ * from the stage (ungroup_byte), fetches base and ref as the comparison with a base fetches its sides (group_fetch: the aligned words that
+ * overlap the wanted bytes only, each shifted by its OWN misalignment), masks what lies behind the row's last byte, and keeps the lowest
+ * row offset whose byte differs.  A wave min (xor shuffles), one LDS step across the four waves, and thread 0 stores the tile's ONE word. */
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_kernel(const qzstd_hip_ungroup_cmp_row_t *__restrict__ rows, uint32_t nRows,
+                                                                       const uint8_t *__restrict__ stage, uint32_t *__restrict__ tilesOut)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which;
+    __shared__ uint32_t red[kUngroupT / 64u];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const qzstd_hip_ungroup_cmp_row_t row = rows[which];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
+    const uint32_t tiles = n ? (uint32_t)(((uint64_t)n + tileMax - 1u) / tileMax) : (row.len ? 1u : 0u);
+    const uint32_t t = blockIdx.x - row.tile0;
+    if (t >= tiles) return; /* (the whole workgroup; never: rows without a tile share the tile0 of the row behind them) */
+    const bool zero = (row.flags & 1u) != 0u;
+    const uint32_t e0 = t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint8_t *stageRow = stage + row.srcOff;
+    if (!zero) ungroup_load(stageRow, n, kLog, e0, tileElems, lds, tid); /* (row is the workgroup's: the branch is uniform) */
+    __syncthreads();
+
+    const uint32_t t0 = e0 << kLog, lim = (e0 + tileElems) << kLog; /* the tile's bytes of u[]: what its strips hold (len <= 0xFFFFFFE0) */
+    const uint32_t t1 = t + 1u == tiles ? row.len : lim;           /* the tail behind the elements goes with the last tile */
+    uint32_t first = kCmpSame;
+    for (uint32_t rel = tid * 16u; rel < t1 - t0; rel += kUngroupT * 16u) { /* (t1 - t0 <= 16 KiB + 7: no wrap near 4 GiB) */
+        const uint32_t o = t0 + rel, valid = t1 - o < 16u ? t1 - o : 16u;
+        uint64_t u0 = 0ull, u1 = 0ull;
+        if (!zero) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (o < lim) {
+                switch (kLog) {
+                case 0u: v = ungroup_word<1u>(lds, n, e0, o); break;
+                case 1u: v = ungroup_word<2u>(lds, n, e0, o); break;
+                case 2u: v = ungroup_word<4u>(lds, n, e0, o); break;
+                default: v = ungroup_word<8u>(lds, n, e0, o); break;
+                }
+            }
+            if (lim - o < valid || o >= lim) { /* the word reaches into the tail: those bytes one by one, from the stage */
+                uint32_t d[4] = { v.x, v.y, v.z, v.w };
+                for (uint32_t b = o < lim ? lim - o : 0u; b < valid; b++)
+                    d[b >> 2] = (d[b >> 2] & ~(0xFFu << ((b & 3u) * 8u))) | ungroup_byte(stageRow, n, kLog, o + b) << ((b & 3u) * 8u);
+                v = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+            u0 = v.x | (uint64_t)v.y << 32;
+            u1 = v.z | (uint64_t)v.w << 32;
+        }
+        uint64_t r0, r1;
+        group_fetch(row.ref + o, valid, &r0, &r1);
+        u0 ^= r0;
+        u1 ^= r1;
+        if (row.base) {
+            uint64_t b0, b1;
+            group_fetch(row.base + o, valid, &b0, &b1);
+            u0 ^= b0;
+            u1 ^= b1;
+        }
+        cmp_mask(valid, &u0, &u1); /* the row's last word: what lies behind the row, in the strips' slack and in memory, does not count */
+        if (u0 | u1) {
+            const uint32_t at = o + (u0 ? (uint32_t)__builtin_ctzll(u0) >> 3 : 8u + ((uint32_t)__builtin_ctzll(u1) >> 3));
+            first = at < first ? at : first; /* (a lane's offsets ascend: only its first one is kept) */
+        }
+    }
+#pragma unroll
+    for (uint32_t d = 32u; d; d >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)first, (int)d, 64);
+        first = other < first ? other : first;
+    }
+    if ((tid & 63u) == 0u) red[tid >> 6] = first;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t m = red[0];
+#pragma unroll
+        for (uint32_t w = 1; w < kUngroupT / 64u; w++) m = red[w] < m ? red[w] : m;
+        tilesOut[blockIdx.x] = m;
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_ungroup_cmp(int device, void *stream, qzstd_hip_ungroup_cmp_row_t *rows, uint32_t nRows,
+                                     qzstd_hip_ungroup_cmp_row_t *d_rows, const void *d_stage, size_t stageBytes, uint32_t *d_tiles)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_cmp: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ungroup_cmp_row_t &r = rows[i];
+        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_cmp: elem not 1, 2, 4 or 8");
+        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return fail_msg("qzstd_hip_ungroup_cmp: unknown flags");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_cmp: frame too long");
+        if (r.len && !r.ref) return fail_msg("qzstd_hip_ungroup_cmp: null ref");
+        if (!(r.flags & QZSTD_HIP_CMP_ZERO)) { /* a ZERO row's srcOff is not looked at */
+            if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_cmp: srcOff not a multiple of 16");
+            if (r.len && !d_stage) return fail_msg("qzstd_hip_ungroup_cmp: null stage");
+            if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_cmp: frames overlap in the stage or are not in ascending order");
+            if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_cmp: a frame ends past stageBytes");
+            end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
+        }
+        total += QZSTD_HIP_CMP_TILES(r.len, r.elem);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_cmp: too many tiles");
+    if (total == 0) return 0; /* nothing but empty rows */
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_CMP_TILES(rows[i].len, rows[i].elem);
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup cmp rows)");
+    hipLaunchKernelGGL(qzstd_ungroup_cmp_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
+                       static_cast<const uint8_t *>(d_stage), d_tiles);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_cmp_kernel");
+    return 0;
+}
+
 /* ---------------------------------------------------------------- comparison with a base (include/qzstd_hip_device.h) -- */
 namespace {
-constexpr uint32_t kDiffT = 256u;                /* threads per workgroup */
+constexpr uint32_t kDiffT = 256u;               /* threads per workgroup */
 constexpr uint32_t kDiffTileLog = kGroupTileLog; /* bytes of one row per workgroup: 16 KiB, four 16-byte words per lane */
 
 /* One workgroup per 16 KiB tile of a row; its row is the last one with tile0 <= blockIdx.x (qzstd_ungroup_window_kernel's search: rows

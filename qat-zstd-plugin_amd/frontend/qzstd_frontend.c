@@ -96,6 +96,7 @@ struct QZSTD_Front_s {
     unsigned long long sliceStats[4]; /* QZSTD_frontRestoreDeviceSlices: slices, bytes written, frames decoded, rows launched */
     QF_RestoreSlot *restoreSlot;
     int restoreSlotDev;
+    unsigned long long verifyStats[4]; /* QZSTD_frontVerifyDeviceBatch: frames compared, of them differing, bytes compared, launches */
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -1461,3 +1462,6 @@ void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4])
 
 /* The restore calls: a source of their own that uses this file's types and helpers, and part of this translation unit for the same reason. */
 #include "qzstd_restore.c"
+
+/* The verify call: the restore's slots and decode with a comparison in the scatter's place; included the same way. */
+#include "qzstd_verify.c"

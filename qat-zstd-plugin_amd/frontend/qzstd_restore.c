@@ -18,6 +18,8 @@
  * nothing happens for it, otherwise a run of such frames is one device->device copy from the base.
  * QZSTD_frontRestoreDeviceSlices (below the whole-buffer calls): byte ranges of the written buffers; only the frames they intersect are decoded,
  * cut into parts the same way, and a part is scattered by ONE qzstd_hip_ungroup_window launch, a row per piece (slice x frame).
+ * QZSTD_frontVerifyDeviceBatch (qzstd_verify.c, included behind this file) uses the same slots and the same decode, and compares where these
+ * calls scatter.
  * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
  */
 
@@ -52,6 +54,11 @@ struct QF_RestoreSlot_s {
     void *dXorRows; size_t dXorRowsCap;
     qzstd_hip_ungroup_win_row_t *hWinRows; size_t hWinRowsCap; /* QZSTD_frontRestoreDeviceSlices: a row per piece (slice x frame) */
     void *dWinRows; size_t dWinRowsCap;
+    qzstd_hip_ungroup_cmp_row_t *hCmpRows; size_t hCmpRowsCap; /* QZSTD_frontVerifyDeviceBatch (qzstd_verify.c): a row per frame, */
+    void *dCmpRows; size_t dCmpRowsCap;
+    void *dTiles; size_t dTilesCap;                            /* the launch's tile words and their pinned copy, */
+    uint32_t *hTiles; size_t hTilesCap;
+    size_t pending;                                            /* and the part (+ 1) whose tile words are on their way; 0: none */
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -59,6 +66,7 @@ struct QF_RestorePart_s {
     const QF_RestoreFrame *frames; /* the job's table */
     size_t f0;                     /* chunk c of the workers' job is frame f0 + c */
     unsigned char *hStage;
+    unsigned char *bad; /* NULL, or a byte per frame of the table: set to 1 for the frame a worker stopped at (QZSTD_frontVerifyDeviceBatch) */
 };
 
 static void qfRestoreSlotsFree(QZSTD_Front *f)
@@ -73,6 +81,10 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
         if (s->dWinRows) qzstd_hip_free(f->restoreSlotDev, s->dWinRows);
         if (s->hWinRows) qzstd_hip_host_free(s->hWinRows);
+        if (s->dCmpRows) qzstd_hip_free(f->restoreSlotDev, s->dCmpRows);
+        if (s->hCmpRows) qzstd_hip_host_free(s->hCmpRows);
+        if (s->dTiles) qzstd_hip_free(f->restoreSlotDev, s->dTiles);
+        if (s->hTiles) qzstd_hip_host_free(s->hTiles);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
@@ -92,7 +104,10 @@ static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
         /* capacity = the chunk's length: a longer content is an error of libzstd's, a shorter one shows in the return value; a frame with a
          * content checksum is verified by the decoder */
         const size_t r = ZSTD_decompressDCtx(w->zd, p->hStage + fr->at, fr->len, fr->src, fr->srcSize);
-        if (ZSTD_isError(r) || r != fr->len) return -1;
+        if (ZSTD_isError(r) || r != fr->len) {
+            if (p->bad) p->bad[p->f0 + c] = 1;
+            return -1;
+        }
     }
     return 0;
 }
@@ -267,6 +282,7 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         part.frames = table;
         part.f0 = pr->f0;
         part.hStage = s->hStage;
+        part.bad = NULL;
         pthread_mutex_lock(&f->mu);
         f->restore = &part;
         f->src = NULL;
@@ -509,6 +525,7 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
         part.frames = table;
         part.f0 = pr->f0;
         part.hStage = s->hStage;
+        part.bad = NULL;
         pthread_mutex_lock(&f->mu);
         f->restore = &part;
         f->src = NULL;

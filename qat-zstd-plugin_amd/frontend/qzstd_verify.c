@@ -1,0 +1,271 @@
+/*
+ * qzstd_verify.c — QZSTD_frontVerifyDeviceBatch / QZSTD_frontVerifyStats (include/qzstd_frontend_device.h): do the frames a compress call
+ * left reproduce the tensors that are on the device NOW?  The restore with a comparison in the scatter's place: nothing of the caller's is
+ * written, no temporary of the buffers' size exists, and the answer says where the first difference of every frame lies.  Part of
+ * qzstd_frontend.c's translation unit, included behind qzstd_restore.c, whose slots (QF_RestoreSlot), part type and workers' decode
+ * (qfRestoreSegment) it uses.
+ *
+ * The call's frames are cut into parts of whole frames, at most QF_PART_BYTES ($QZSTD_FRONT_DEVICE_PART) of DECODED content each.  Per part,
+ * on one of the two restore slots: the workers decode its frames into the pinned buffer; the calling thread queues the host->device copy,
+ * ONE qzstd_hip_ungroup_cmp launch (a row per frame: the live chunk, its base chunk, the frame's place in the stage) and the device->host
+ * copy of the launch's tile words (4 bytes per 16 KiB), and hands the workers the next part.  A slot's tile words are read when its stream
+ * has passed them: before the slot is used again, and behind the last part.  With QZSTD_frontSetDeltaSkip on, a frame of a based buffer
+ * that IS the canonical zero frame of its chunk's length (qfIsZeroFrame) is not decoded and takes no room in the pinned buffer or the
+ * copy: it is a ZERO row of the part it falls into — live chunk and base chunk are compared directly — and a part may consist of such rows
+ * alone (no job, no copy; the launch reads no stage).
+ */
+
+extern int qzstd_hip_ungroup_cmp(int device, void *stream, qzstd_hip_ungroup_cmp_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_cmp_row_t *d_rows,
+                                 const void *d_stage, size_t stageBytes, uint32_t *d_tiles) __attribute__((weak));
+
+/* one frame of the call: the row it becomes */
+typedef struct {
+    const unsigned char *d_ref;  /* the live chunk */
+    const unsigned char *d_base; /* its base chunk, or NULL */
+    size_t len;
+    size_t m;                    /* its frame in the decode table; (size_t)-1: a ZERO row, not decoded */
+    uint32_t k;
+} QF_VerifyRow;
+
+/* frames [c0, c1) of the call, of them decoded [f0, f1) of the table: decoded content bytes, stage bytes, compared bytes (ZERO rows too), tile words */
+typedef struct { size_t c0, c1, f0, f1, bytes, stage, compared, tiles; } QF_VerifyRange;
+
+/* the tile words of the part a slot last ran (its stream has passed them): per frame the first one that is not "same" */
+static void qfVerifyHarvest(QZSTD_Front *f, QF_RestoreSlot *s, const QF_VerifyRange *parts, const QF_VerifyRow *rows, size_t *firstDiff, size_t *nDiff)
+{
+    const QF_VerifyRange *pr;
+    size_t c, t = 0, differing = 0;
+    if (!s->pending) return;
+    pr = &parts[s->pending - 1u];
+    s->pending = 0;
+    for (c = pr->c0; c < pr->c1; c++) {
+        const size_t n = (size_t)QZSTD_HIP_CMP_TILES(rows[c].len, rows[c].k);
+        size_t i, at = QZSTD_VERIFY_SAME;
+        for (i = 0; i < n; i++)
+            if (s->hTiles[t + i] != QZSTD_HIP_CMP_SAME) { at = s->hTiles[t + i]; break; }
+        t += n;
+        if (firstDiff) firstDiff[c] = at;
+        if (at != QZSTD_VERIFY_SAME) differing++;
+    }
+    *nDiff += differing;
+    __atomic_fetch_add(&f->verifyStats[1], (unsigned long long)differing, __ATOMIC_RELAXED);
+}
+
+size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                    const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                                    void *stream, size_t *firstDiff)
+{
+    QF_RestoreFrame *table = NULL; /* the frames that are decoded */
+    size_t *callOf = NULL;         /* their numbers in the call */
+    unsigned char *bad = NULL;     /* the ones a worker stopped at */
+    QF_VerifyRow *rows = NULL;     /* every frame of the call */
+    QF_VerifyRange *parts = NULL;
+    unsigned char *scratch = NULL;
+    QF_ZeroHash zh;
+    QF_RestoreSlot *slot;
+    struct QF_RestorePart_s part;
+    void *ev = NULL;
+    size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nDiff = 0;
+    int dev = -1, rc = 0, anyBase = 0, skip;
+    /* host-side checks, the restore's: nothing has touched a GPU when one of them fails */
+    if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    for (i = 0; i < nBufs; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
+        want += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+    }
+    if (want != nFrames || (nFrames && (!frames || !frameSizes))) return (size_t)-1;
+    for (i = 0; bases && i < nBufs; i++) {
+        if (!bases[i].d_ptr && !bases[i].size) continue;
+        if (!bases[i].d_ptr || bases[i].size != bufs[i].size) return (size_t)-1;
+        if (bases[i].size) anyBase = 1;
+    }
+    if (!anyBase) bases = NULL;
+    if (!qzstd_hip_ungroup_cmp || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
+        !qzstd_hip_event_destroy)
+        return (size_t)-1; /* a device layer without the ungrouping comparison, or without the device-input entry points at all */
+    for (i = 0; i < nBufs; i++) {
+        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
+        int d;
+        if (!bufs[i].size) continue;
+        d = qzstd_hip_pointer_device(p);
+        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
+        dev = d;
+        if (bases && bases[i].d_ptr) {
+            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
+            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
+        }
+    }
+    if (nFrames == 0) return 0;
+    pthread_mutex_lock(&f->mu);
+    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+    f->devBusy = 1;
+    pthread_mutex_unlock(&f->mu);
+
+    {
+        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART");
+        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
+    }
+    skip = bases && f->deltaSkip;
+    memset(&zh, 0, sizeof(zh));
+    table = (QF_RestoreFrame *)malloc(nFrames * sizeof(*table));
+    callOf = (size_t *)malloc(nFrames * sizeof(*callOf));
+    bad = (unsigned char *)calloc(nFrames, 1);
+    rows = (QF_VerifyRow *)malloc(nFrames * sizeof(*rows));
+    parts = (QF_VerifyRange *)malloc(nFrames * sizeof(*parts));
+    if (skip) scratch = (unsigned char *)malloc(qfZeroFrameBound(f->p.chunkSize));
+    if (!table || !callOf || !bad || !rows || !parts || (skip && !scratch)) rc = -1;
+    for (i = 0; i < nBufs && rc == 0; i++) {
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        const unsigned char *base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr : NULL;
+        size_t off;
+        for (off = 0; off < bufs[i].size; off += f->p.chunkSize, pos += frameSizes[c], c++) {
+            const size_t len = bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize;
+            const unsigned char *src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
+            const int zero = skip && base && qfIsZeroFrame(src, frameSizes[c], len, scratch, &zh, f->p.chunkSize);
+            QF_VerifyRange *cur = nParts ? &parts[nParts - 1] : NULL;
+            if (len > 0xFFFFFFE0u) { rc = -1; break; } /* (a row's length is 32-bit) */
+            /* a part ends where another decoded frame would not fit, where its launch's rows are 32-bit, and where its tile words are */
+            if (!cur || (!zero && cur->bytes + len > partBytes) || cur->c1 - cur->c0 >= 0xFFFFFFFFu ||
+                cur->tiles + (size_t)QZSTD_HIP_CMP_TILES(len, e) > 0x7FFFFFFFu) {
+                cur = &parts[nParts++];
+                cur->c0 = c;
+                cur->f0 = cur->f1 = m;
+                cur->bytes = cur->stage = cur->compared = cur->tiles = 0;
+            }
+            rows[c].d_ref = (const unsigned char *)bufs[i].d_ptr + off;
+            rows[c].d_base = base ? base + off : NULL;
+            rows[c].len = len;
+            rows[c].k = e;
+            rows[c].m = (size_t)-1;
+            if (!zero) {
+                table[m].src = src;
+                table[m].srcSize = frameSizes[c];
+                table[m].d_dst = NULL;
+                table[m].d_base = NULL;
+                table[m].len = len;
+                table[m].at = cur->stage;
+                table[m].k = e;
+                callOf[m] = c;
+                rows[c].m = m;
+                cur->f1 = ++m;
+                cur->bytes += len;
+                cur->stage += qfPad16(len);
+            }
+            cur->c1 = c + 1u;
+            cur->compared += len;
+            cur->tiles += (size_t)QZSTD_HIP_CMP_TILES(len, e);
+        }
+    }
+    /* the restore's slots, kept with the front between calls */
+    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
+    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
+    f->restoreSlotDev = dev;
+    slot = f->restoreSlot;
+    for (k = 0; slot && k < 2 && rc == 0; k++)
+        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
+    /* the library's streams wait for what the caller queued on `stream` so far: whatever last wrote the tensors and the bases */
+    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
+    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
+                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
+        rc = -1;
+    for (k = 0; k < nParts && rc == 0; k++) {
+        const QF_VerifyRange *pr = &parts[k];
+        const size_t nf = pr->f1 - pr->f0, nr = pr->c1 - pr->c0;
+        QF_RestoreSlot *s = &slot[k % 2];
+        void *h;
+        /* part k - 2 ran on this slot: its stream must have passed the copy, the launch and the tile words' way back before they are read
+         * and the buffers written (or grown) */
+        if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
+        qfVerifyHarvest(f, s, parts, rows, firstDiff, &nDiff);
+        h = s->hStage;
+        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
+        s->hStage = (unsigned char *)h;
+        h = s->hCmpRows;
+        if (rc == 0 && qfGrowH(&h, &s->hCmpRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_row_t))) rc = -1;
+        s->hCmpRows = (qzstd_hip_ungroup_cmp_row_t *)h;
+        h = s->hTiles;
+        if (rc == 0 && qfGrowH(&h, &s->hTilesCap, pr->tiles * sizeof(uint32_t))) rc = -1;
+        s->hTiles = (uint32_t *)h;
+        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) ||
+                        qfGrowD(dev, &s->dCmpRows, &s->dCmpRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_row_t)) ||
+                        qfGrowD(dev, &s->dTiles, &s->dTilesCap, pr->tiles * sizeof(uint32_t))))
+            rc = -1;
+        if (rc) break;
+        for (c = 0; c < nr; c++) {
+            const QF_VerifyRow *vr = &rows[pr->c0 + c];
+            qzstd_hip_ungroup_cmp_row_t *r = &s->hCmpRows[c];
+            r->ref = (uint64_t)(uintptr_t)vr->d_ref;
+            r->base = (uint64_t)(uintptr_t)vr->d_base;
+            r->srcOff = vr->m == (size_t)-1 ? 0u : table[vr->m].at;
+            r->len = (uint32_t)vr->len;
+            r->elem = vr->k;
+            r->flags = vr->m == (size_t)-1 ? QZSTD_HIP_CMP_ZERO : 0u;
+            r->tile0 = 0;
+        }
+        if (nf) {
+            int failed;
+            part.frames = table;
+            part.f0 = pr->f0;
+            part.hStage = s->hStage;
+            part.bad = bad;
+            pthread_mutex_lock(&f->mu);
+            f->restore = &part;
+            f->src = NULL;
+            f->srcSize = 0;
+            failed = qfRunJobLocked(f, nf);
+            f->restore = NULL;
+            pthread_mutex_unlock(&f->mu);
+            if (failed) { /* a frame that does not decode, decodes to another length or fails its checksum */
+                for (c = pr->f0; firstDiff && c < pr->f1; c++)
+                    if (bad[c]) firstDiff[callOf[c]] = QZSTD_VERIFY_UNDECODED;
+                rc = -1;
+                break;
+            }
+            if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage)) { rc = -1; break; }
+        }
+        if (qzstd_hip_ungroup_cmp(dev, s->stream, s->hCmpRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_row_t *)s->dCmpRows, s->dStage, pr->stage,
+                                  (uint32_t *)s->dTiles) ||
+            qzstd_hip_memcpy_d2h(dev, s->stream, s->hTiles, s->dTiles, pr->tiles * sizeof(uint32_t))) {
+            rc = -1;
+            break;
+        }
+        s->pending = k + 1u;
+        __atomic_fetch_add(&f->verifyStats[0], (unsigned long long)nr, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->verifyStats[2], (unsigned long long)pr->compared, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->verifyStats[3], 1ull, __ATOMIC_RELAXED);
+    }
+    /* nothing the library queued may still run when the call returns: a bounded wait first, then an unbounded one */
+    for (k = 0; slot && k < 2; k++) {
+        if (!slot[k].stream) continue;
+        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
+            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
+            rc = -1;
+        }
+    }
+    /* the last parts' tile words, in the parts' order (part nParts - 2 ran on the other slot than the last one) */
+    for (k = 0; slot && k < 2; k++) {
+        QF_RestoreSlot *s = &slot[(nParts + k) % 2];
+        if (rc == 0) qfVerifyHarvest(f, s, parts, rows, firstDiff, &nDiff);
+        s->pending = 0;
+    }
+    if (ev) qzstd_hip_event_destroy(dev, ev);
+    free(table);
+    free(callOf);
+    free(bad);
+    free(rows);
+    free(parts);
+    free(scratch);
+    pthread_mutex_lock(&f->mu);
+    f->devBusy = 0;
+    pthread_mutex_unlock(&f->mu);
+    return rc == 0 ? nDiff : (size_t)-1;
+}
+
+void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->verifyStats[k], __ATOMIC_RELAXED) : 0ull;
+}

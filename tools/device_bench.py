@@ -79,6 +79,17 @@ bytes, bytes device->host and host->device per input byte.
 a), then qzstd_hip_group_xor over the same rows: the run to put under rocprofv3.
 
   python tools/device_bench.py --skip --gib 1 --reps 3 [--levels 1,6] [--kernels]
+
+--verify: the check before the previous checkpoint is dropped (QZSTD_frontVerifyDeviceBatch) — N GiB of bf16 and of fp32 N(0, 0.02) weights
+after an N(0, 1e-5) update against a base, written as level-1 grouped delta frames of 128 KiB; one tensor of N GiB and N x 8192 tensors of
+128 KiB; delta skip off, and on with every other chunk unchanged (p = 0.5).  Two legs, alternating in one run, every run listed, ms per
+check, bytes host->device and torch's peak extra device memory:
+  verify         one QZSTD_frontVerifyDeviceBatch call against the live tensors
+  restore_equal  what a caller does today: QZSTD_frontRestoreDeviceBatchDelta into fresh tensors + torch.equal per tensor
+--kernels: through the C ABI, nothing timed: qzstd_hip_ungroup_xor, then qzstd_hip_ungroup_cmp, ONE launch each over the same N GiB stage of
+128 KiB frames with a base, for each element size 1, 2, 4, 8: the run to put under rocprofv3.
+
+  python tools/device_bench.py --verify --gib 1 --reps 3 [--kernels]
 """
 import argparse
 import json
@@ -816,14 +827,148 @@ def skip_main(a):
     print(json.dumps(out))
 
 
+def verify_kernels(a, size):
+    """through the C ABI, nothing timed: for k = 1, 2, 4, 8 ONE qzstd_hip_ungroup_xor launch over an N GiB stage of 128 KiB frames (base XORed in,
+    a destination written) and ONE qzstd_hip_ungroup_cmp launch over the same stage and base against that destination as the live bytes —
+    every tile word must say "same"; then one launch with a bit changed.  The run to put under rocprofv3"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_cmp_kernel(D.bind_xor_kernels(plug.lib))
+    n = size // a.chunk
+    stage = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    base = torch.randint(0, 256, (size + 16,), dtype=torch.uint8, device="cuda:0")
+    dst = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    tiles = torch.empty(size >> 14, dtype=torch.int32, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.UngroupCmpRow))
+    assert d_rows and stage.data_ptr() % 16 == 0
+    try:
+        for k in (1, 2, 4, 8):
+            ux = (D.UngroupXorRow * n)()
+            cr = (D.UngroupCmpRow * n)()
+            for c in range(n):
+                o = c * a.chunk
+                ux[c].dst, ux[c].base, ux[c].srcOff, ux[c].len, ux[c].elem = dst.data_ptr() + o, base.data_ptr() + o, o, a.chunk, k
+                cr[c].ref, cr[c].base, cr[c].srcOff, cr[c].len, cr[c].elem, cr[c].flags = dst.data_ptr() + o, base.data_ptr() + o, o, a.chunk, k, 0
+            torch.cuda.synchronize()
+            assert L.qzstd_hip_ungroup_xor(0, None, ux, n, d_rows, stage.data_ptr(), size) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            tiles.fill_(7)
+            torch.cuda.synchronize()
+            assert L.qzstd_hip_ungroup_cmp(0, None, cr, n, d_rows, stage.data_ptr(), size, tiles.data_ptr()) == 0, plug.err()
+            plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+            assert bool((tiles == -1).all()), k
+        dst[5 * a.chunk + 16385] ^= 1  # (k = 8 still staged)
+        torch.cuda.synchronize()
+        assert L.qzstd_hip_ungroup_cmp(0, None, cr, n, d_rows, stage.data_ptr(), size, tiles.data_ptr()) == 0, plug.err()
+        plug.check(L.qzstd_hip_stream_sync(0, None), "sync")
+        hit = torch.nonzero(tiles != -1).flatten().tolist()
+        assert hit == [5 * (a.chunk >> 14) + 1] and int(tiles[hit[0]]) == 16385
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps({"bytes": size, "passes": "for k = 1, 2, 4, 8: qzstd_hip_ungroup_xor, then qzstd_hip_ungroup_cmp, each ONE launch over %d frames of %d "
+                                               "bytes with a base; a last qzstd_hip_ungroup_cmp launch (k = 8) with one bit changed" % (n, a.chunk)}))
+
+
+def verify_main(a):
+    """--verify: QZSTD_frontVerifyDeviceBatch against what a caller does without it — QZSTD_frontRestoreDeviceBatchDelta into fresh tensors and
+    torch.equal per tensor — on a checkpoint just written as level-1 grouped delta frames"""
+    import ctypes as C
+    size = int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1)
+    if a.kernels:
+        return verify_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "level": 1, "step": 1e-5, "reps": a.reps, "cells": {},
+           "timed": "ms per check, every run, the two legs alternating in one run: verify = QZSTD_frontVerifyDeviceBatch (firstDiff given) and the "
+                    "closing synchronize; restore_equal = torch.empty_like per tensor, the array of their addresses, QZSTD_frontRestoreDeviceBatchDelta into them, torch.equal per "
+                    "tensor (its answer read on the host), the tensors dropped",
+           "h2d": "verify: computed from the frames — the call copies pad16(len) bytes per frame that is not a recognised canonical zero frame (the "
+                  "library keeps no counter of it), plus 32 bytes per row up and 4 bytes per 16 KiB back; restore_equal: QZSTD_frontRestoreStats [2]",
+           "peak": "torch.cuda.max_memory_allocated() - memory_allocated() before the leg: torch's allocator only; the library's two restore slots "
+                   "(pinned + device stage of a part each) are the same in both legs and are not in it"}
+    for dt, tdt in (("bf16", torch.bfloat16), ("fp32", torch.float32)):
+        k = 2 if dt == "bf16" else 4
+        base = (torch.randn(size // k, device="cuda:0") * 0.02).to(tdt)
+        stepped = (base.float() + torch.randn(size // k, device="cuda:0") * 1e-5).to(tdt)
+        for layout, nt in (("one_tensor", 1), ("8192_tensors", size // a.chunk)):
+            per = size // nt
+            for share in (0.0, 0.5):
+                # p = 0.5: every other 128 KiB chunk did not change
+                new = stepped.clone()
+                if share:
+                    v, bv = new.view(n, -1), base.view(n, -1)
+                    v[::2] = bv[::2]
+                tensors = [new[i * (per // k):(i + 1) * (per // k)] for i in range(nt)]
+                bases = [base[i * (per // k):(i + 1) * (per // k)] for i in range(nt)]
+                fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+                cell = out["cells"]["%s,%s,skip=%s" % (dt, layout, "on,p=0.5" if share else "off")] = {}
+                try:
+                    fr.reserve(size)
+                    assert fr.set_delta_skip(1 if share else 0) == 0
+                    es = bytes([k] * nt) + b"\0"
+                    bufs_new, _, _ = fr.batch([(x.data_ptr(), per) for x in tensors])
+                    bufs_base, _, _ = fr.batch([(x.data_ptr(), per) for x in bases])
+                    _, sizes = fr._frame_buffers(n)
+                    assert fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, bufs_new, bufs_base, es, nt, stream, fr._dst, len(fr._dst), sizes, None) == n
+                    frames = C.create_string_buffer(n * fr.stride)
+                    C.memmove(frames, fr._dst, n * fr.stride)
+                    zero = D.zero_frame(a.chunk)
+                    n_zero = sum(1 for c in range(n) if sizes[c] == len(zero) and C.string_at(C.addressof(frames) + c * fr.stride, len(zero)) == zero) if share else 0
+                    cell["compressed"] = sum(sizes[c] for c in range(n))
+                    cell["zero_frames"] = n_zero
+                    first = (C.c_size_t * n)()
+
+                    def verify():
+                        return fr.lib.QZSTD_frontVerifyDeviceBatch(fr.f, frames, fr.stride, sizes, n, bufs_new, bufs_base, es, nt, stream, first)
+
+                    def restore_equal():
+                        fresh = [torch.empty_like(t) for t in tensors]
+                        outs = fr.out_batch([(x.data_ptr(), per) for x in fresh])
+                        assert fr.lib.QZSTD_frontRestoreDeviceBatchDelta(fr.f, frames, fr.stride, sizes, n, outs, bufs_base, es, nt, stream) == n
+                        return 0 if all(torch.equal(f, t) for f, t in zip(fresh, tensors)) else 1
+
+                    runs = {"verify_ms": [], "restore_equal_ms": [], "verify_peak_bytes": [], "restore_equal_peak_bytes": []}
+                    for name, leg in (("verify", verify), ("restore_equal", restore_equal)):  # untimed: the slots
+                        r0 = fr.restore_stats()
+                        assert leg() == 0
+                        torch.cuda.synchronize()
+                        cell[name + "_h2d_bytes"] = (n - n_zero) * a.chunk if name == "verify" else fr.restore_stats()[2] - r0[2]
+                    for _ in range(a.reps):
+                        for name, leg in (("verify", verify), ("restore_equal", restore_equal)):
+                            torch.cuda.synchronize()
+                            torch.cuda.reset_peak_memory_stats()
+                            m0 = torch.cuda.memory_allocated()
+                            t0 = time.perf_counter()
+                            assert leg() == 0
+                            torch.cuda.synchronize()
+                            runs[name + "_ms"].append(round((time.perf_counter() - t0) * 1e3, 2))
+                            runs[name + "_peak_bytes"].append(torch.cuda.max_memory_allocated() - m0)
+                    cell.update(runs)
+                    # the answer is worth something: one bit of the live data, found at its place
+                    new.view(torch.uint8)[3 * a.chunk + 16385] ^= 1
+                    torch.cuda.synchronize()
+                    assert verify() == 1 and first[3] == 16385 and restore_equal() == 1
+                    cell["verify_stats"] = fr.verify_stats()
+                finally:
+                    fr.close()
+                del tensors, bases, new
+        del base, stepped
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--verify", action="store_true")
     ap.add_argument("--skip", action="store_true")
     ap.add_argument("--slices", action="store_true")
     ap.add_argument("--delta", action="store_true")
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--group", action="store_true")
-    ap.add_argument("--kernels", action="store_true", help="--group, --restore, --delta: the passes to trace, nothing timed")
+    ap.add_argument("--kernels", action="store_true", help="--group, --restore, --delta, --skip, --verify: the passes to trace, nothing timed")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--checksum", action="store_true")
     ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
@@ -836,6 +981,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.verify:
+        return verify_main(a)
     if a.skip:
         if a.levels == "1,6,12":
             a.levels = "1,6"

@@ -3,7 +3,9 @@ QZSTD_frontCompressDeviceBatch, QZSTD_frontDeviceStats, QZSTD_frontSetChecksum, 
 and of the way back (QZSTD_frontRestoreDeviceBatchTyped, QZSTD_frontRestoreDevice, QZSTD_frontRestoreStats: DeviceFront.restore_batch),
 the delta calls against a base per buffer (QZSTD_frontCompressDeviceBatchDelta, QZSTD_frontRestoreDeviceBatchDelta, QZSTD_frontDeltaStats:
 DeviceFront.compress_device_batch_delta / restore_batch_delta), delta skip (QZSTD_frontSetDeltaSkip, QZSTD_frontDeltaSkipStats:
-DeviceFront.set_delta_skip / delta_skip_stats; qzstd_hip_diff's row, binding and numpy reference; zero_frame()), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
+DeviceFront.set_delta_skip / delta_skip_stats; qzstd_hip_diff's row, binding and numpy reference; zero_frame()), the verify call
+(QZSTD_frontVerifyDeviceBatch, QZSTD_frontVerifyStats: DeviceFront.verify / verify_stats, verify_tensors(); qzstd_hip_ungroup_cmp's row, binding and
+numpy reference ungroup_cmp_ref()), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
 QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
@@ -88,6 +90,54 @@ def diff_tile0_ref(lens):
         out.append(total)
         total += (n + 16383) >> 14
     return out
+
+
+class UngroupCmpRow(C.Structure):
+    """qzstd_hip_ungroup_cmp_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("ref", C.c_uint64), ("base", C.c_uint64), ("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32),
+                ("flags", C.c_uint32), ("tile0", C.c_uint32)]
+
+
+CMP_SAME = 0xFFFFFFFF  # QZSTD_HIP_CMP_SAME: a tile word of a tile that matches
+CMP_ZERO = 1           # QZSTD_HIP_CMP_ZERO: flags bit 0
+VERIFY_SAME = C.c_size_t(-1).value       # QZSTD_VERIFY_SAME
+VERIFY_UNDECODED = C.c_size_t(-2).value  # QZSTD_VERIFY_UNDECODED
+
+
+def bind_cmp_kernel(L):
+    """qzstd_hip_ungroup_cmp on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_ungroup_cmp.restype = C.c_int
+    L.qzstd_hip_ungroup_cmp.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    return L
+
+
+def cmp_tiles(n: int, k: int) -> int:
+    """QZSTD_HIP_CMP_TILES: workgroups of a row = its tile words (16 KiB of the ungrouped content each, the tail with the last one)"""
+    e = n // k
+    return -(-e // (16384 // k)) if e else (1 if n else 0)
+
+
+def ungroup_cmp_ref(rows):
+    """what qzstd_hip_ungroup_cmp must leave in d_tiles: rows = [(staged frame or None for a ZERO row, base or None, ref, elem), ...], the
+    three as numpy uint8 arrays of one length -> the tile words of all rows, row after row (numpy uint32): CMP_SAME, or the lowest row
+    offset inside the tile at which ungrouped(frame) ^ base differs from ref"""
+    import numpy as np
+    out = []
+    for frame, base, ref, k in rows:
+        n = len(ref)
+        e = n // k
+        if frame is None:
+            u = np.zeros(n, dtype=np.uint8)
+        else:
+            u = np.concatenate([np.ascontiguousarray(frame[:e * k].reshape(k, e).T).reshape(-1), frame[e * k:]]) if e else frame.copy()
+        if base is not None:
+            u = u ^ base
+        tiles = cmp_tiles(n, k)
+        words = np.full(tiles, CMP_SAME, dtype=np.uint32)
+        for p in np.flatnonzero(u != ref)[::-1]:
+            words[min(int(p) >> 14, tiles - 1)] = p
+        out.append(words)
+    return np.concatenate(out) if out else np.zeros(0, dtype=np.uint32)
 
 
 def zero_frame(n: int, checksum: bool = False) -> bytes:
@@ -209,6 +259,12 @@ def bind(F):
         F.QZSTD_frontGetDeltaSkip.argtypes = [C.c_void_p]
         F.QZSTD_frontDeltaSkipStats.restype = None
         F.QZSTD_frontDeltaSkipStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontVerifyDeviceBatch"):  # (absent from an older library)
+        F.QZSTD_frontVerifyDeviceBatch.restype = C.c_size_t
+        F.QZSTD_frontVerifyDeviceBatch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(DeviceBuf),
+                                                   C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+        F.QZSTD_frontVerifyStats.restype = None
+        F.QZSTD_frontVerifyStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -567,6 +623,46 @@ class DeviceFront:
         self.lib.QZSTD_frontSliceStats(self.f, st)
         return list(st)
 
+    def call_verify(self, packed, n_frames: int, bufs, bases, n_bufs: int, elem_sizes=None, stream: int | None = None, first_diff=None):
+        """QZSTD_frontVerifyDeviceBatch alone on prepared arguments (pack_frames(), batch()[0] for the live buffers and for the bases, a
+        c_size_t array or None for firstDiff) -> its return value"""
+        buf, stride, sizes = packed
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        return self.lib.QZSTD_frontVerifyDeviceBatch(self.f, buf, stride, sizes, n_frames, bufs, bases, es, n_bufs, C.c_void_p(stream or None),
+                                                     first_diff)
+
+    def verify_raw(self, frames_per_buffer, ptrs_and_sizes, bases=None, elem_sizes=None, stream: int | None = None, compact: bool = False,
+                   n_frames: int | None = None, want_offsets: bool = True):
+        """QZSTD_frontVerifyDeviceBatch: per buffer its list of frames, compared with the LIVE buffers [(device address, bytes), ...] (bases
+        as compress_device_batch_delta_raw's) -> (return value: the number of differing frames or ERROR, firstDiff as a flat list or None)"""
+        flat = [f for fr in frames_per_buffer for f in fr]
+        first = (C.c_size_t * max(len(flat), 1))(*([7] * max(len(flat), 1))) if want_offsets else None
+        bs = None if bases is None else self.batch([b or (0, 0) for b in bases])[0]
+        r = self.call_verify(self.pack_frames(flat, compact), len(flat) if n_frames is None else n_frames, self.batch(ptrs_and_sizes)[0], bs,
+                             len(ptrs_and_sizes), elem_sizes, stream, first)
+        return r, (list(first)[:len(flat)] if want_offsets else None)
+
+    def verify(self, frames_per_buffer, ptrs_and_sizes, bases=None, elem_sizes=None, stream: int | None = None, compact: bool = False) -> list:
+        """-> [(buffer index, frame index inside the buffer, byte offset inside that frame's chunk), ...] for the frames that do NOT reproduce
+        the live buffers; []: the checkpoint is good.  Raises when the call fails (a frame that does not decode included)"""
+        r, first = self.verify_raw(frames_per_buffer, ptrs_and_sizes, bases, elem_sizes, stream, compact)
+        if r == ERROR:
+            raise RuntimeError("QZSTD_frontVerifyDeviceBatch failed")
+        out, c = [], 0
+        for i, fr in enumerate(frames_per_buffer):
+            for j in range(len(fr)):
+                if first[c] != VERIFY_SAME:
+                    out.append((i, j, first[c]))
+                c += 1
+        assert len(out) == r
+        return out
+
+    def verify_stats(self) -> list:
+        """[0] frames compared, [1] of them differing, [2] content bytes compared, [3] qzstd_hip_ungroup_cmp launches"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontVerifyStats(self.f, st)
+        return list(st)
+
     def restore_stats(self) -> list:
         """[0] frames decoded, [1] bytes of content, [2] bytes copied host->device, [3] ungroup launches"""
         st = (C.c_ulonglong * 4)()
@@ -635,6 +731,27 @@ def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None,
     handle = getattr(stream, "cuda_stream", stream)
     bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
     return front.restore_batch(frames_per_tensor, bufs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
+
+
+def verify_tensors(front: DeviceFront, frames_per_tensor, tensors, bases=None, stream=None, group=None) -> list:
+    """do the frames compress_tensors() (or a delta call against `bases`) left reproduce the tensors as they are NOW?  ONE
+    QZSTD_frontVerifyDeviceBatch call: nothing is written, no temporary of the tensors' size -> [(tensor, frame, byte offset inside the
+    frame's chunk), ...] for the frames that differ; []: safe to drop the previous checkpoint.  bases: per tensor a tensor of the same
+    byte size or None; group as compress_tensors()'s"""
+    if group not in (None, "dtype"):
+        raise ValueError("verify_tensors: group is None or \"dtype\"")
+    tensors = list(tensors)
+    for t in tensors + [b for b in (bases or []) if b is not None]:
+        if not t.is_cuda or not t.is_contiguous() or t.device != tensors[0].device:
+            raise ValueError("verify_tensors: contiguous GPU tensors on one device")
+    if not tensors:
+        return []
+    if stream is None:
+        stream = torch.cuda.current_stream(tensors[0].device)
+    handle = getattr(stream, "cuda_stream", stream)
+    bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
+    bs = None if bases is None else [None if b is None else (b.data_ptr(), b.numel() * b.element_size()) for b in bases]
+    return front.verify(frames_per_tensor, bufs, bs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
 
 
 def restore_slices(front: DeviceFront, frames, buf_sizes, elems, slices, stream=None) -> int:
