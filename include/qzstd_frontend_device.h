@@ -201,6 +201,37 @@ int QZSTD_frontGetDeltaSkip(const QZSTD_Front *f);
  * entropy-coded), [2] bytes compared, [3] zero frames recognised by a restore (not decoded, nothing copied host->device) */
 void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Plane probe, OFF by default: the noise planes of byte-grouped and delta frames are found on the GPU before a worker touches the frame, and
+ * the library writes them as Raw_Blocks itself.  With the setting off every call is launch for launch and byte for byte what it was.
+ *
+ * With it on, a part that holds a frame with an element size above 1 or with a base gets ONE more launch behind its staging
+ * (qzstd_hip_plane_cost: a byte histogram per block of the part, reduced on the device to one 32-bit word, the block's order-0 cost in
+ * bytes — include/qzstd_planecost.h), and the words come back with the part's compaction headers: 4 bytes per block, no wait of their own.
+ * A block is RAW-PREDICTED when QZSTD_planeIsRaw(cost, length, length - litBytes) holds: neither entropy coding its bytes nor its matches
+ * could save libzstd's own minimum gain.  A frame with at least one such block (and no failed block, and no plane of one value) is ASSEMBLED
+ * BY THE LIBRARY: magic and a frame header with Single_Segment and the smallest Frame_Content_Size field that holds the frame's length; per
+ * raw-predicted block a 3-byte Raw_Block header and the block's content (its literals in the arena when it has no sequences, else that block
+ * alone rebuilt from its entries); the remaining blocks, in order, from ONE ZSTD_compressSequencesAndLiterals call over their content alone,
+ * copied to their places with Last_Block set on the frame's final block only; with checksums on, the header's flag and the GPU's hash.
+ * When that call fails or yields a block libzstd would store raw, the frame takes the path it takes with the setting off.  A frame without
+ * a raw-predicted block is byte for byte the frame of the setting off.  An assembled frame is an ordinary zstd frame of the same content:
+ * the restore, slices and verify calls and any zstd decoder read it as before; it may be larger than the setting-off frame by at most
+ * (length >> 6) + 2 bytes per raw-predicted block.  Parts without a grouped or based frame are untouched whatever the setting.
+ *
+ * With the setting on, a call with such a frame and a device layer without qzstd_hip_plane_cost returns (size_t)-1 before anything is queued.
+ * QZSTD_frontDeviceStats counts an assembled frame in [0] (built from sequences and literals, nothing copied back) and the probe's words in [2];
+ * QZSTD_frontByteGroupStats [0] and QZSTD_frontDeltaStats [0] count it as they count a frame built from the arena.
+ *
+ * Set: 0, or -1 for f NULL or while a call runs on the front.  Get: 0 / 1 (0 for f NULL). */
+int QZSTD_frontSetPlaneProbe(QZSTD_Front *f, int on);
+int QZSTD_frontGetPlaneProbe(const QZSTD_Front *f);
+/* since creation: [0] blocks probed, [1] blocks written raw by the library, [2] frames assembled by the library, [3] frames with a
+ * raw-predicted block that fell back to the setting-off path */
+void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4]);
+/* QZSTD_planeCost / QZSTD_planeIsRaw of include/qzstd_planecost.h as exported functions (bindings that cannot include the header) */
+unsigned QZSTD_planeCostOf(const unsigned hist[256], unsigned len);
+int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes);
+
 /* Slices: byte ranges of the buffers AS THEY WERE WRITTEN restored into device memory — a checkpoint written by one rank layout and loaded
  * by another (a row shard: one contiguous slice per tensor; a column shard of an [R, C] matrix: R slices of one buffer) — without a
  * temporary of the buffers' size and without decoding the frames no slice touches.  frames / frameStride / frameSizes / nFrames are the WHOLE

@@ -4,7 +4,7 @@
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
  * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
  * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
- * and the content-checksum kernel (QZSTD_frontSetChecksum).
+ * the content-checksum kernel (QZSTD_frontSetChecksum), and the byte histograms' cost per block (QZSTD_frontSetPlaneProbe).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -306,6 +306,31 @@ typedef struct {
 } qzstd_hip_hash_row_t;
 int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
                     qzstd_hip_hash_row_t *d_rows, uint64_t *d_out);
+
+/*
+ * Plane cost (QZSTD_frontSetPlaneProbe): ONE launch takes the byte histogram of every row — the `len` bytes at d_base + srcOff, at ANY byte
+ * offset — and leaves ONE word per row: d_cost[i] = QZSTD_planeCost(histogram, len) of include/qzstd_planecost.h, the order-0 cost of the row in
+ * bytes, computed on the device with that header's own functions.  The rows are a part's block descriptors over the launch's base (the
+ * stage, or the caller's buffer for a part read in place); the front-end predicts Raw_Blocks from the words (QZSTD_planeIsRaw).
+ *
+ * One workgroup of 256 threads per row.  Loads are aligned 16-byte loads of the words that overlap [srcOff, srcOff + len) and of no other
+ * word; the bytes of the first and last word outside the row are never counted.  The histogram lives in LDS, in 16 copies (a lane's copy is
+ * its index mod 16, bin b of copy c at word 16 b + c) that LDS atomics fill, so that a plane of a handful of values does not serialise on
+ * one word; a reduction over the workgroup follows and one ordinary store.  No global atomics, no memset; nothing but d_cost[0 .. nRows)
+ * is written.  An empty row costs 0 and loads nothing.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous) and must stay unchanged until the stream has passed the call; the
+ * launcher checks it and uploads it to d_rows, device scratch of nRows entries.  Refused (< 0) before anything is queued: a null rows,
+ * d_rows or d_cost, a null d_base with a row that is not empty, a len above 131072 (QZSTD_PLANE_LEN_MAX), a reserved that is not 0, more
+ * than 2^31 - 1 rows.  nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t srcOff;   /* bytes from d_base, any value */
+    uint32_t len;      /* bytes, 0 .. 131072 */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_plane_row_t;
+int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                         qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost);
 
 #if defined(__cplusplus)
 }

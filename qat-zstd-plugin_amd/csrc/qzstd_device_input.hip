@@ -1401,3 +1401,87 @@ extern "C" int qzstd_hip_xxh64(int device, void *stream, const void *d_base, con
     QZ_CHECK(hipGetLastError(), "launch qzstd_xxh64_kernel");
     return 0;
 }
+
+/* ---------------------------------------------------------------- plane cost (include/qzstd_hip_device.h, qzstd_planecost.h) -- */
+#include "qzstd_planecost.h"
+
+namespace {
+constexpr uint32_t kPlaneT = 256u;      /* threads per workgroup: one per bin in the reduction, four waves to hide the loads' latency */
+constexpr uint32_t kPlaneCopies = 16u;  /* sub-histograms: bin b of copy c at word b * 16 + c — the 64 lanes of a wave that all meet ONE
+                                           bin (an exponent plane) land on 16 banks, four lanes per word, not 64 on one; the lanes of
+                                           a noise plane spread over all 64 banks.  16 KiB of LDS: eight workgroups a CU, all 32 waves */
+
+/* One workgroup per row (a block of at most 128 KiB).  The aligned 16-byte words that overlap [base + srcOff, + len) — and no other — are
+ * loaded once each, lane after lane; the bytes of the first and last word that lie outside the row are skipped, every other byte is one
+ * LDS atomic add on the lane's sub-histogram.  Then thread b sums bin b over the copies, takes its term of the cost
+ * (QZSTD_planeTerm), the terms are added across the wave (xor shuffles) and the four waves (one LDS step), and thread 0 stores the row's
+ * ONE word.  No global atomics; the output is never read. */
+__global__ __launch_bounds__(kPlaneT) void qzstd_plane_cost_kernel(const uint8_t *__restrict__ base, const qzstd_hip_plane_row_t *__restrict__ rows,
+                                                                    uint32_t *__restrict__ out)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hist[256u * kPlaneCopies];
+    __shared__ uint32_t red[kPlaneT / 64u];
+    const uint32_t tid = threadIdx.x;
+    const qzstd_hip_plane_row_t row = rows[blockIdx.x];
+    for (uint32_t i = tid; i < 256u * kPlaneCopies; i += kPlaneT) hist[i] = 0u;
+    __syncthreads();
+    const uint64_t a = (uint64_t)(uintptr_t)base + row.srcOff;
+    const uint32_t head = (uint32_t)a & 15u;
+    const uint4 *words = reinterpret_cast<const uint4 *>(a - head);
+    const uint32_t span = head + row.len;                          /* (len <= 128 KiB) */
+    const uint32_t nWords = row.len ? (span + 15u) >> 4 : 0u;      /* the last one holds byte len - 1; an empty row loads nothing */
+    uint32_t *mine = &hist[tid & (kPlaneCopies - 1u)];
+    for (uint32_t w = tid; w < nWords; w += kPlaneT) {
+        const uint4 v = words[w];
+        const uint32_t d[4] = { v.x, v.y, v.z, v.w };
+        const uint32_t lo = w ? 0u : head, hi = span - w * 16u < 16u ? span - w * 16u : 16u;
+        if (lo == 0u && hi == 16u) {
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; b++) atomicAdd(&mine[((d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu) * kPlaneCopies], 1u);
+        } else {
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; b++)
+                if (b >= lo && b < hi) atomicAdd(&mine[((d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu) * kPlaneCopies], 1u);
+        }
+    }
+    __syncthreads();
+    uint32_t c = 0u;
+    {
+        const uint4 *h = reinterpret_cast<const uint4 *>(&hist[tid * kPlaneCopies]);
+#pragma unroll
+        for (uint32_t j = 0; j < kPlaneCopies / 4u; j++) {
+            const uint4 q = h[j];
+            c += q.x + q.y + q.z + q.w;
+        }
+    }
+    uint32_t sum = QZSTD_planeTerm(c, QZSTD_planeLog2(row.len)); /* (at most len * L(len) < 2^30 in all: 32 bits hold every partial sum) */
+#pragma unroll
+    for (uint32_t s = 32u; s; s >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)s, 64);
+    if ((tid & 63u) == 0u) red[tid >> 6] = sum;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t total = red[0];
+#pragma unroll
+        for (uint32_t w = 1; w < kPlaneT / 64u; w++) total += red[w];
+        out[blockIdx.x] = QZSTD_planeCostOfSum(total);
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                                    qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_cost) return fail_msg("qzstd_hip_plane_cost: null pointer");
+    if (nRows > 0x7FFFFFFFu) return fail_msg("qzstd_hip_plane_cost: too many rows");
+    for (uint32_t i = 0; i < nRows; i++) {
+        if (rows[i].len > QZSTD_PLANE_LEN_MAX) return fail_msg("qzstd_hip_plane_cost: a row longer than 128 KiB");
+        if (rows[i].reserved) return fail_msg("qzstd_hip_plane_cost: reserved not 0");
+        if (rows[i].len && !d_base) return fail_msg("qzstd_hip_plane_cost: null base");
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (plane cost rows)");
+    hipLaunchKernelGGL(qzstd_plane_cost_kernel, dim3(nRows), dim3(kPlaneT), 0, (hipStream_t)stream, static_cast<const uint8_t *>(d_base), d_rows, d_cost);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_plane_cost_kernel");
+    return 0;
+}

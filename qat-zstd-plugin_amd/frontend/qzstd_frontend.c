@@ -14,6 +14,7 @@
 #include "qzstd_bytegroup.h"
 #include "qzstd_bytegroup_internal.h"
 #include "qzstd_hip_device.h"
+#include "qzstd_planecost.h"
 
 #include <dlfcn.h>
 #include <pthread.h>
@@ -47,6 +48,11 @@ typedef struct {
     size_t endsCap;
     unsigned char *back;
     ZSTD_DCtx *zd; /* the restore calls' decoder, created by the worker's first restore job */
+    /* plane probe: the entries and literals of a frame's blocks that are not raw-predicted, and the frame libzstd builds of them */
+    ZSTD_Sequence *subSeqs;
+    size_t subSeqsCap;
+    unsigned char *subLit, *sub;
+    size_t subLitCap, subCap;
 } QF_Worker;
 
 typedef struct QF_DevPart_s QF_DevPart;
@@ -89,6 +95,9 @@ struct QZSTD_Front_s {
     /* delta skip (QZSTD_frontSetDeltaSkip): the setting, and frames compared / found equal, bytes compared, zero frames a restore recognised */
     int deltaSkip;
     unsigned long long skipStats[4];
+    /* plane probe (QZSTD_frontSetPlaneProbe): the setting, and blocks probed / written raw here, frames assembled here / fallen back */
+    int planeProbe;
+    unsigned long long probeStats[4];
     /* the restore calls (qzstd_restore.c): the part the workers decode (NULL: a compress job), the counters, and two slots kept from call to
      * call (pinned buffer, device stage, stream) for device restoreSlotDev */
     const struct QF_RestorePart_s *restore;
@@ -375,6 +384,9 @@ void QZSTD_freeFront(QZSTD_Front *f)
         if (w->state) QZSTD_freeSeqProdState(w->state);
         free(w->seqs);
         free(w->ends);
+        free(w->subSeqs);
+        free(w->subLit);
+        free(w->sub);
         if (w->back) qzstd_hip_host_free(w->back);
         if (w->raw) qzstd_hip_host_free(w->raw);
         if (w->rawStream) qzstd_hip_stream_destroy(w->rawDev, w->rawStream);
@@ -420,6 +432,11 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * Delta skip (QZSTD_frontSetDeltaSkip): before the parts are planned, ONE qzstd_hip_diff launch finds the frames of based buffers whose chunk
  * equals its base chunk (qfDiffPass); they get the canonical zero frame, written here, and are left out of the per-frame table — a table
  * entry carries its frame's index in the call — so nothing above ever sees them.  With the setting off, or without a base, nothing changes.
+ *
+ * Plane probe (QZSTD_frontSetPlaneProbe): a part with a grouped or based frame gets ONE qzstd_hip_plane_cost launch behind its staging — a row per
+ * block descriptor over the stage, one word per block back with the compaction headers: the block's order-0 cost (include/qzstd_planecost.h).
+ * A frame with a block that QZSTD_planeIsRaw predicts raw is assembled by qfAssembleFrame — the library writes the Raw_Blocks, libzstd codes
+ * the remaining blocks once — and never entropy-coded twice.  With the setting off nothing is launched and every frame is what it was.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
@@ -442,6 +459,8 @@ extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const q
                            qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
 extern int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows,
                           uint32_t *d_flags) __attribute__((weak));
+extern int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                                qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost) __attribute__((weak));
 
 #define QF_PART_BYTES ((size_t)64 << 20)
 #define QF_DEV_WAIT_MS 60000u
@@ -488,6 +507,10 @@ struct QF_DevSlot_s {
     void *dDiffRows, *dDiffFlags; size_t dDiffRowsCap, dDiffFlagsCap;
     uint32_t *hDiffFlags; size_t hDiffFlagsCap;
     int hashed; /* the part queued on this slot has its frames' hashes in dHash; the part fetched from it has them in hHash */
+    qzstd_hip_plane_row_t *hPlaneRows; size_t hPlaneRowsCap; /* plane probe: a row per block (pinned), the device copy, the costs on both sides */
+    void *dPlaneRows, *dPlaneCost; size_t dPlaneRowsCap, dPlaneCostCap;
+    uint32_t *hPlaneCost; size_t hPlaneCostCap;
+    int probed; /* as `hashed`: the queued part's costs are in dPlaneCost; the fetched part's in hPlaneCost */
     qzstd_hip_block_t *hDesc; size_t hDescCap;
     void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
     size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
@@ -523,12 +546,14 @@ struct QF_DevPart_s {
     const QF_DevSlot *slot;
     int dev;
     int hashed; /* checksums on: frame c's content hash is slot->hHash[c - f0] */
+    int probed; /* plane probe: block b's order-0 cost is slot->hPlaneCost[b] */
+    int failSub; /* test switch ($QZSTD_FRONT_PROBE_FAIL_SUB): the assembled frames' libzstd call counts as failed */
 };
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
     void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
-                  s->dDiffRows, s->dDiffFlags };
+                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
@@ -540,6 +565,8 @@ static void qfSlotFree(int dev, QF_DevSlot *s)
     if (s->hHash) qzstd_hip_host_free(s->hHash);
     if (s->hDiffRows) qzstd_hip_host_free(s->hDiffRows);
     if (s->hDiffFlags) qzstd_hip_host_free(s->hDiffFlags);
+    if (s->hPlaneRows) qzstd_hip_host_free(s->hPlaneRows);
+    if (s->hPlaneCost) qzstd_hip_host_free(s->hPlaneCost);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
     if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
     free(s->blkSeq);
@@ -583,6 +610,8 @@ typedef struct {
     size_t nParts, blk;        /* blk: the launches' largest block, min(chunkSize, 128 KiB) */
     int dev, level;
     int checksum;              /* the front's setting when the call began */
+    int probe;                 /* plane probe: the front's setting when the call began, for a call with a grouped or based frame */
+    int failSub;               /* $QZSTD_FRONT_PROBE_FAIL_SUB (tests) */
 } QF_DevJob;
 
 static size_t qfPad16(size_t n) { return (n + 15u) & ~(size_t)15u; }
@@ -746,6 +775,26 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
             return -1;
         s->hashed = 1;
     }
+    s->probed = 0;
+    if (j->probe && (pr->grouped || pr->delta)) {
+        /* the blocks' byte histograms, reduced to their order-0 cost on the device: a row per descriptor, over the stage (such a part is
+         * never read in place) */
+        void *h = s->hPlaneRows;
+        if (qfGrowH(&h, &s->hPlaneRowsCap, nb * sizeof(qzstd_hip_plane_row_t))) return -1;
+        s->hPlaneRows = (qzstd_hip_plane_row_t *)h;
+        if (qfGrowD(dev, &s->dPlaneRows, &s->dPlaneRowsCap, nb * sizeof(qzstd_hip_plane_row_t)) ||
+            qfGrowD(dev, &s->dPlaneCost, &s->dPlaneCostCap, nb * sizeof(uint32_t)))
+            return -1;
+        for (b = 0; b < nb; b++) {
+            s->hPlaneRows[b].srcOff = s->hDesc[b].srcOff;
+            s->hPlaneRows[b].len = s->hDesc[b].srcLen;
+            s->hPlaneRows[b].reserved = 0;
+        }
+        if (qzstd_hip_plane_cost(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
+                                 (uint32_t *)s->dPlaneCost))
+            return -1;
+        s->probed = 1;
+    }
     return 0;
 }
 
@@ -767,6 +816,13 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         if (qfGrowH(&h, &s->hHashCap, (pr->f1 - pr->f0) * 8u)) return -1;
         s->hHash = (uint64_t *)h;
         if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHash, s->dHash, (pr->f1 - pr->f0) * 8u)) return -1;
+    }
+    if (s->probed) {
+        /* the blocks' costs travel with the headers as the hashes do: 4 bytes per block */
+        void *h = s->hPlaneCost;
+        if (qfGrowH(&h, &s->hPlaneCostCap, nb * sizeof(uint32_t))) return -1;
+        s->hPlaneCost = (uint32_t *)h;
+        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hPlaneCost, s->dPlaneCost, nb * sizeof(uint32_t))) return -1;
     }
     if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
         return -1;
@@ -802,8 +858,12 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     memset(s->hArena + eo + bytes, 0, QF_LIT_SLACK);
     s->hLit = s->hArena + eo + 8u * seqs;
     s->litTotal = lits;
-    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u)), __ATOMIC_RELAXED);
+    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u) +
+                                                           (s->probed ? nb * 4u : 0u)), __ATOMIC_RELAXED);
+    if (s->probed) __atomic_fetch_add(&j->f->probeStats[0], (unsigned long long)nb, __ATOMIC_RELAXED);
     out->hashed = s->hashed;
+    out->probed = s->probed;
+    out->failSub = j->failSub;
     out->bufs = j->bufs;
     out->bases = j->bases;
     out->frames = j->frames;
@@ -833,6 +893,181 @@ static int qfStoresRawBlock(const unsigned char *fr, size_t frSize, const size_t
         if (h & 1u) break; /* Last_Block */
     }
     return 0;
+}
+
+/* Magic and frame header of a frame the library writes itself (the canonical zero frame, a frame assembled around raw-predicted blocks):
+ * a frame header descriptor with Single_Segment and the smallest Frame_Content_Size field that holds len (and Content_Checksum_Flag when
+ * `checksum`), then that field.  -> bytes written, 6 .. 13 */
+static size_t qfFrameHeader(unsigned char *out, size_t len, int checksum)
+{
+    const unsigned long long L = (unsigned long long)len;
+    const unsigned code = L <= 255u ? 0u : (L <= 65791u ? 1u : (L <= 0xFFFFFFFFull ? 2u : 3u)), fcs = code == 0u ? 1u : 1u << code;
+    const unsigned long long v = code == 1u ? L - 256u : L;
+    size_t pos = 0;
+    unsigned i;
+    out[pos++] = 0x28; out[pos++] = 0xB5; out[pos++] = 0x2F; out[pos++] = 0xFD;
+    out[pos++] = (unsigned char)(code << 6 | 0x20u | (checksum ? 4u : 0u));
+    for (i = 0; i < fcs; i++) out[pos++] = (unsigned char)(v >> (8u * i));
+    return pos;
+}
+
+/* plane probe: 1 when block b of the fetched part (len bytes, its compaction header h) is raw-predicted */
+static int qfBlockIsRaw(const QF_DevSlot *s, const qzstd_hip_compact_hdr_t *h, size_t b, size_t len)
+{
+    return len <= QZSTD_PLANE_LEN_MAX && h->count != QZSTD_HIP_NSEQ_ERROR && h->litBytes <= len &&
+           QZSTD_planeIsRaw(s->hPlaneCost[b], (uint32_t)len, (uint32_t)(len - h->litBytes));
+}
+
+static int qfGrowBytes(unsigned char **p, size_t *cap, size_t need)
+{
+    if (*cap >= need && *p) return 0;
+    free(*p);
+    *p = (unsigned char *)malloc(need ? need : 1u);
+    *cap = *p ? need : 0;
+    return *p ? 0 : -1;
+}
+
+/* Plane probe: frame c of a probed part, whose entries are unpacked in w->seqs and whose block ends are w->ends, assembled by the library
+ * when at least one of its blocks is raw-predicted (QZSTD_planeIsRaw over the block's cost from the GPU, its length and its matched bytes).
+ *   raw-predicted block -> a 3-byte Raw_Block header and its content: its literals where they lie in the arena when it has no sequences,
+ *                          else that block alone executed from its own entries and literals (qzbgRebuild);
+ *   the others, in order -> ONE ZSTD_compressSequencesAndLiterals call over their content alone, into the worker's scratch; its blocks
+ *                          (header + body) are copied to their places, Last_Block rewritten.
+ * The splice is valid because an entry's offset never leaves its block (every block is matched on its own), so no Compressed block refers to
+ * bytes of a block that is not in the sub-frame, and because a Raw_Block changes neither the decoder's repeat offsets nor its entropy
+ * tables: every Compressed block meets in the spliced frame the decoder state it was coded against.
+ * -> 0: dst holds the frame and everything is counted; 1: no raw-predicted block, or the frame must take the setting-off path (counted in
+ * [3] then); -1: out of memory. */
+static int qfAssembleFrame(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, const QF_DevFrame *fm, size_t c, int maybeRle,
+                           unsigned char *dst)
+{
+    static const unsigned char didBytes[4] = { 0, 1, 2, 4 }, fcsBytes[4] = { 0, 2, 4, 8 };
+    const QF_DevSlot *s = pt->slot;
+    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const size_t n = fm->len, b0 = fm->b0, nb = fm->nb, cap = f->stride;
+    size_t e, o, nRaw = 0, subSeqs = 0, subLit = 0, subSize = 0, runs = 0, firstSub = 0, pos, sp = 0, r = 0;
+    int prevRaw = 1;
+    for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+        const size_t len = w->ends[e] - o, b = b0 + e;
+        if (qfBlockIsRaw(s, &hdr[b], b, len)) {
+            nRaw++;
+            prevRaw = 1;
+        } else {
+            if (prevRaw && !runs++) firstSub = b;
+            prevRaw = 0;
+            subSeqs += hdr[b].count;
+            subLit += hdr[b].litBytes;
+            subSize += len;
+        }
+    }
+    if (nRaw == 0) return 1;
+    if (maybeRle || (nRaw < nb && !qfSeqLit)) goto fallback;
+    if (nRaw < nb) {
+        const unsigned char *lit;
+        size_t litCap, k = 0, l = 0;
+        if (w->subSeqsCap < subSeqs) {
+            free(w->subSeqs);
+            w->subSeqs = (ZSTD_Sequence *)malloc(subSeqs * sizeof(ZSTD_Sequence));
+            w->subSeqsCap = w->subSeqs ? subSeqs : 0;
+            if (!w->subSeqs) return -1;
+        }
+        if (qfGrowBytes(&w->sub, &w->subCap, cap)) return -1;
+        /* one run of such blocks (the common case: the noise planes lie in front): its literals are read where they lie in the arena */
+        if (runs > 1 && qfGrowBytes(&w->subLit, &w->subLitCap, subLit + QF_LIT_SLACK)) return -1;
+        for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+            const size_t len = w->ends[e] - o, b = b0 + e;
+            if (qfBlockIsRaw(s, &hdr[b], b, len))
+                continue;
+            memcpy(&w->subSeqs[k], &w->seqs[s->blkSeq[b] - s->blkSeq[b0]], hdr[b].count * sizeof(ZSTD_Sequence));
+            k += hdr[b].count;
+            if (runs > 1) {
+                memcpy(w->subLit + l, s->hLit + s->blkLit[b], hdr[b].litBytes);
+                l += hdr[b].litBytes;
+            }
+        }
+        if (runs > 1) {
+            memset(w->subLit + subLit, 0, QF_LIT_SLACK);
+            lit = w->subLit;
+            litCap = subLit + QF_LIT_SLACK;
+        } else {
+            lit = s->hLit + s->blkLit[firstSub];
+            litCap = s->litTotal - s->blkLit[firstSub] + QF_LIT_SLACK;
+        }
+        (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
+        if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 1)) || qfCtxChecksum(w, 0)) goto fallback;
+        r = qfSeqLit(w->zc, w->sub, cap, w->subSeqs, subSeqs, lit, subLit, litCap, subSize);
+        if (ZSTD_isError(r) || pt->failSub || r < 6u) goto fallback;
+        /* the sub-frame's blocks, one per block handed in: none that libzstd would store raw (qfStoresRawBlock's rule), Last_Block on the
+         * final one alone, and nothing behind it */
+        {
+            const unsigned fhd = w->sub[4], single = (fhd >> 5) & 1u;
+            size_t p;
+            sp = 5 + !single + didBytes[fhd & 3u] + ((fhd >> 6) == 0 ? single : fcsBytes[fhd >> 6]);
+            p = sp;
+            k = 0;
+            for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+                const size_t len = w->ends[e] - o, b = b0 + e;
+                unsigned h, type;
+                size_t body;
+                if (qfBlockIsRaw(s, &hdr[b], b, len))
+                    continue;
+                if (p + 3 > r) goto fallback;
+                h = w->sub[p] | (unsigned)w->sub[p + 1] << 8 | (unsigned)w->sub[p + 2] << 16;
+                type = (h >> 1) & 3u;
+                body = type == 1u ? 1u : h >> 3;
+                if (type == 3u || (type == 2u && body + (len >> 6) + 2 >= len)) goto fallback;
+                if ((type == 2u ? 0u : h >> 3) != (type == 2u ? 0u : len)) goto fallback; /* a Raw or RLE block names its regenerated size */
+                k += len;
+                if (((h & 1u) != 0u) != (k == subSize)) goto fallback;
+                p += 3 + body;
+                if (p > r) goto fallback;
+            }
+            if (p != r) goto fallback;
+        }
+    }
+    /* the frame itself */
+    if (13u + 3u * nb + 4u > cap) goto fallback;
+    pos = qfFrameHeader(dst, n, pt->hashed);
+    for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+        const size_t len = w->ends[e] - o, b = b0 + e;
+        const unsigned last = e + 1 == nb ? 1u : 0u;
+        if (qfBlockIsRaw(s, &hdr[b], b, len)) {
+            const unsigned h = (unsigned)(len << 3) | last; /* Block_Size, Raw_Block, Last_Block */
+            if (pos + 3 + len + 4u > cap) goto fallback;
+            dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16);
+            if (hdr[b].count == 1u && hdr[b].litBytes == len) {
+                memcpy(dst + pos, s->hLit + s->blkLit[b], len);
+            } else if (qzbgRebuild(dst + pos, len, &w->seqs[s->blkSeq[b] - s->blkSeq[b0]].offset, hdr[b].count, s->hLit + s->blkLit[b],
+                                   hdr[b].litBytes, &len, 1) != 0) {
+                goto fallback;
+            }
+            pos += len;
+        } else {
+            const unsigned h = w->sub[sp] | (unsigned)w->sub[sp + 1] << 8 | (unsigned)w->sub[sp + 2] << 16;
+            const size_t whole = 3 + (((h >> 1) & 3u) == 1u ? 1u : h >> 3);
+            if (pos + whole + 4u > cap) goto fallback;
+            memcpy(dst + pos, w->sub + sp, whole);
+            dst[pos] = (unsigned char)((dst[pos] & ~1u) | last);
+            pos += whole;
+            sp += whole;
+        }
+    }
+    if (nRaw < nb) (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
+    if (pt->hashed) {
+        const uint64_t h = s->hHash[c];
+        dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16); dst[pos++] = (unsigned char)(h >> 24);
+        __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
+    }
+    f->sizes[fm->idx] = pos;
+    __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
+    if (fm->k > 1u) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
+    if (pt->bases && pt->bases[fm->buf].d_ptr) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->probeStats[1], (unsigned long long)nRaw, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->probeStats[2], 1ull, __ATOMIC_RELAXED);
+    return 0;
+fallback:
+    __atomic_fetch_add(&f->probeStats[3], 1ull, __ATOMIC_RELAXED);
+    return 1;
 }
 
 /* frame c of the part in progress -> zstd frame */
@@ -884,6 +1119,11 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             w->seqs[k].rep = 0;
         }
         haveSeqs = 1;
+        if (pt->probed) {
+            /* plane probe: a frame with a raw-predicted block is assembled here; every other frame goes on as with the setting off */
+            const int a = qfAssembleFrame(f, w, pt, fm, c, maybeRle, dst);
+            if (a <= 0) return a;
+        }
         /* (a session that ended in an error leaves the CCtx mid-frame, where parameters cannot be set: every frame starts afresh) */
         (void)ZSTD_CCtx_reset(w->zc, ZSTD_reset_session_only);
         if (ZSTD_isError(ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 1))) return -1;
@@ -1091,14 +1331,7 @@ static size_t qfZeroFrameBound(size_t len) { return 4u + 1u + 8u + 4u * ((len + 
  * 128 KiB from the frame's start, Last_Block on the final one.  -> bytes written (out holds qfZeroFrameBound(len)) */
 static size_t qfZeroFrameBody(unsigned char *out, size_t len, int checksum)
 {
-    const unsigned long long L = (unsigned long long)len;
-    const unsigned code = L <= 255u ? 0u : (L <= 65791u ? 1u : (L <= 0xFFFFFFFFull ? 2u : 3u)), fcs = code == 0u ? 1u : 1u << code;
-    const unsigned long long v = code == 1u ? L - 256u : L;
-    size_t pos = 0, left = len;
-    unsigned i;
-    out[pos++] = 0x28; out[pos++] = 0xB5; out[pos++] = 0x2F; out[pos++] = 0xFD;
-    out[pos++] = (unsigned char)(code << 6 | 0x20u | (checksum ? 4u : 0u));
-    for (i = 0; i < fcs; i++) out[pos++] = (unsigned char)(v >> (8u * i));
+    size_t pos = qfFrameHeader(out, len, checksum), left = len;
     while (left) {
         const size_t n = left < 131072u ? left : 131072u;
         const unsigned h = (unsigned)(n << 3) | 2u | (left == n ? 1u : 0u); /* Block_Size (the regenerated size), RLE_Block, Last_Block */
@@ -1215,7 +1448,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     size_t nFrames, nParts = 0, k, i, total = 0;
     unsigned group;
     unsigned char *equal = NULL;
-    int rc = 0, anyGrouped = 0, anyBase = 0, skip;
+    int rc = 0, anyGrouped = 0, anyBase = 0, skip, probe;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
@@ -1245,6 +1478,8 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (bases && !qzstd_hip_group_xor) return (size_t)-1;   /* a base given and a device layer that cannot XOR one in */
     skip = bases && f->deltaSkip;
     if (skip && !qzstd_hip_diff) return (size_t)-1;         /* delta skip wanted and a device layer that cannot compare */
+    probe = f->planeProbe && (anyGrouped || bases);
+    if (probe && !qzstd_hip_plane_cost) return (size_t)-1;  /* plane probe wanted and a device layer that cannot take histograms */
     j.dev = -1;
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
@@ -1280,6 +1515,8 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     j.bufs = bufs;
     j.bases = bases;
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
+    j.probe = probe;
+    j.failSub = probe && getenv("QZSTD_FRONT_PROBE_FAIL_SUB") != NULL;
     j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
         const char *rep = getenv("QZSTD_HIP_EXT_REPCODES"); /* the producer path's level flags (QZSTD_startQatDevice) */
@@ -1455,6 +1692,29 @@ void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4])
     if (!stats) return;
     for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->skipStats[k], __ATOMIC_RELAXED) : 0ull;
 }
+
+int QZSTD_frontSetPlaneProbe(QZSTD_Front *f, int on)
+{
+    int busy;
+    if (!f) return -1;
+    pthread_mutex_lock(&f->mu);
+    busy = f->devBusy || f->running;
+    if (!busy) f->planeProbe = on != 0;
+    pthread_mutex_unlock(&f->mu);
+    return busy ? -1 : 0;
+}
+
+int QZSTD_frontGetPlaneProbe(const QZSTD_Front *f) { return f ? f->planeProbe : 0; }
+
+void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->probeStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+unsigned QZSTD_planeCostOf(const unsigned hist[256], unsigned len) { return len <= QZSTD_PLANE_LEN_MAX ? QZSTD_planeCost(hist, len) : len; }
+int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { return QZSTD_planeIsRaw(cost, len, matchedBytes); }
 
 /* The byte-grouped layout, its block rule and qzbgRebuild: a source of their own, free of HIP and libzstd (the tests build it alone), and
  * part of this translation unit so that the front-end stays ONE source to whoever builds it. */

@@ -90,6 +90,16 @@ check, bytes host->device and torch's peak extra device memory:
 128 KiB frames with a base, for each element size 1, 2, 4, 8: the run to put under rocprofv3.
 
   python tools/device_bench.py --verify --gib 1 --reps 3 [--kernels]
+
+--probe: the plane probe (QZSTD_frontSetPlaneProbe) on --group's typed data — an N GiB bf16 tensor and an N GiB fp32 one of N(0, 0.02) weights,
+byte grouping on (the element size), levels 1 / 6 / 12.  Two legs, the setting off and on alternating in one run, every run listed: GB/s of
+input of QZSTD_frontCompressDevice, compressed sizes, bytes device->host per input byte, and of the setting-on frames the share the library
+assembled and the share that fell back (QZSTD_frontPlaneProbeStats [2] and [3]), blocks probed and written raw.
+--kernels: through the C ABI, timed with events around ONE launch each, every run listed as ms per GiB: qzstd_hip_group (element size 2) over
+N GiB of 128 KiB rows, and qzstd_hip_plane_cost over N GiB of 128 KiB rows of a noise plane (random bytes), of an exponent plane (the high
+bytes of bf16 N(0, 0.02) weights: a handful of values) and over the grouped stage's own 64 KiB planes as the front-end launches it.
+
+  python tools/device_bench.py --probe --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
 """
 import argparse
 import json
@@ -960,15 +970,120 @@ def verify_main(a):
     print(json.dumps(out))
 
 
+def probe_kernels(a, size):
+    """--probe --kernels: qzstd_hip_plane_cost beside qzstd_hip_group over the same N GiB, ms per GiB from events around one launch each"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_plane_kernel(D.bind_xor_kernels(plug.lib))
+    L.qzstd_hip_group.restype = C.c_int
+    L.qzstd_hip_group.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    n = size // a.chunk
+    torch.manual_seed(0)
+    w = (torch.randn(size // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8)
+    noise = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    expo = w.view(-1, 2)[:, 1].repeat(2).contiguous()  # the high bytes, twice: N GiB of exponent plane
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    cost = torch.empty(2 * n, dtype=torch.int32, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, 2 * n * C.sizeof(D.GroupRow))
+    assert d_rows and stage.data_ptr() % 16 == 0
+    gib = size / float(1 << 30)
+    out = {"bytes": size, "rows": n, "row_bytes": a.chunk, "timed": "events around one launch (rows uploaded inside), ms per GiB, every run of %d after one untimed" % a.reps}
+
+    def timed(call):
+        runs = []
+        for i in range(a.reps + 1):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record()
+            assert call() == 0, plug.err()
+            e1.record()
+            torch.cuda.synchronize()
+            if i:
+                runs.append(round(e0.elapsed_time(e1) / gib, 3))
+        return runs
+
+    try:
+        gr = (D.GroupRow * n)()
+        for c in range(n):
+            gr[c].src, gr[c].dstOff, gr[c].len, gr[c].pad, gr[c].elem = w.data_ptr() + c * a.chunk, c * a.chunk, a.chunk, 0, 2
+        out["group_k2_ms_per_gib"] = timed(lambda: L.qzstd_hip_group(0, None, gr, n, d_rows, stage.data_ptr(), size))
+        rows = (D.PlaneRow * n)(*[D.PlaneRow(c * a.chunk, a.chunk, 0) for c in range(n)])
+        out["plane_cost_noise_ms_per_gib"] = timed(lambda: L.qzstd_hip_plane_cost(0, None, noise.data_ptr(), rows, n, d_rows, cost.data_ptr()))
+        out["noise_cost_per_row"] = [int(cost[:n].min()), int(cost[:n].max())]
+        out["plane_cost_exponent_ms_per_gib"] = timed(lambda: L.qzstd_hip_plane_cost(0, None, expo.data_ptr(), rows, n, d_rows, cost.data_ptr()))
+        out["exponent_cost_per_row"] = [int(cost[:n].min()), int(cost[:n].max())]
+        half = a.chunk // 2
+        planes = (D.PlaneRow * (2 * n))(*[D.PlaneRow(c * half, half, 0) for c in range(2 * n)])
+        out["plane_cost_grouped_stage_ms_per_gib"] = timed(lambda: L.qzstd_hip_plane_cost(0, None, stage.data_ptr(), planes, 2 * n, d_rows, cost.data_ptr()))
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps(out))
+
+
+def probe_main(a):
+    """--probe: the grouped device call with the plane probe off and on"""
+    size = int(a.gib * (1 << 30)) & ~(a.chunk - 1)
+    if a.kernels:
+        return probe_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    n = size // a.chunk
+    torch.manual_seed(0)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "data": {},
+           "timed": "QZSTD_frontCompressDevice with byte grouping on, GB/s of input, every run of %d, the plane probe off and on alternating" % a.reps}
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        t = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt)
+        torch.cuda.synchronize()
+        res = out["data"][kind] = {"elem": k, "levels": {}}
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            try:
+                fr.reserve(size)
+                stream = torch.cuda.current_stream().cuda_stream
+                assert fr.set_byte_group(k) == 0
+                cell = {"off_gbps": [], "on_gbps": []}
+                for on in (0, 1):  # untimed: first touch of the destination, the device slots, the pinned arenas
+                    tag = "on" if on else "off"
+                    assert fr.set_plane_probe(on) == 0
+                    s0, p0 = fr.stats(), fr.plane_probe_stats()
+                    r, sizes = fr.call_device(t.data_ptr(), size, stream)
+                    assert r == n, tag
+                    s1, p1 = fr.stats(), fr.plane_probe_stats()
+                    cell["compressed_" + tag] = sum(sizes[c] for c in range(n))
+                    cell["d2h_bytes_per_input_byte_" + tag] = round((s1[2] - s0[2]) / size, 5)
+                    cell["frames_from_the_arena_" + tag] = round((s1[0] - s0[0]) / n, 4)
+                    if on:
+                        cell["blocks_probed_raw"] = [p1[0] - p0[0], p1[1] - p0[1]]
+                        cell["frames_assembled_share"] = round((p1[2] - p0[2]) / n, 4)
+                        cell["frames_fell_back_share"] = round((p1[3] - p0[3]) / n, 4)
+                for _ in range(a.reps):
+                    for on in (0, 1):
+                        assert fr.set_plane_probe(on) == 0
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        r, _ = fr.call_device(t.data_ptr(), size, stream)
+                        dt_s = time.perf_counter() - t0
+                        assert r == n
+                        cell["on_gbps" if on else "off_gbps"].append(round(size / dt_s / 1e9, 3))
+                res["levels"][str(level)] = cell
+            finally:
+                fr.close()
+        del t
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--probe", action="store_true")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--skip", action="store_true")
     ap.add_argument("--slices", action="store_true")
     ap.add_argument("--delta", action="store_true")
     ap.add_argument("--restore", action="store_true")
     ap.add_argument("--group", action="store_true")
-    ap.add_argument("--kernels", action="store_true", help="--group, --restore, --delta, --skip, --verify: the passes to trace, nothing timed")
+    ap.add_argument("--kernels", action="store_true", help="--group, --restore, --delta, --skip, --verify: the passes to trace, nothing timed; --probe: the two kernels timed")
     ap.add_argument("--batch", action="store_true")
     ap.add_argument("--checksum", action="store_true")
     ap.add_argument("--legs", default="host,device,batch", help="--checksum: the legs to run")
@@ -981,6 +1096,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.probe:
+        return probe_main(a)
     if a.verify:
         return verify_main(a)
     if a.skip:

@@ -7,6 +7,8 @@ DeviceFront.set_delta_skip / delta_skip_stats; qzstd_hip_diff's row, binding and
 (QZSTD_frontVerifyDeviceBatch, QZSTD_frontVerifyStats: DeviceFront.verify / verify_stats, verify_tensors(); qzstd_hip_ungroup_cmp's row, binding and
 numpy reference ungroup_cmp_ref()), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
 QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
+the plane probe (QZSTD_frontSetPlaneProbe, QZSTD_frontPlaneProbeStats: DeviceFront.set_plane_probe / plane_probe_stats; qzstd_hip_plane_cost's row and
+binding; plane_cost() / plane_is_raw(), the rule of include/qzstd_planecost.h; reference_frames_probe(): what the calls must produce with the setting on),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
@@ -90,6 +92,30 @@ def diff_tile0_ref(lens):
         out.append(total)
         total += (n + 16383) >> 14
     return out
+
+
+class PlaneRow(C.Structure):
+    """qzstd_hip_plane_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("srcOff", C.c_uint64), ("len", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def bind_plane_kernel(L):
+    """qzstd_hip_plane_cost on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_plane_cost.restype = C.c_int
+    L.qzstd_hip_plane_cost.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    return L
+
+
+def plane_cost(block: bytes, lib=None) -> int:
+    """QZSTD_planeCost (include/qzstd_planecost.h, through the front-end library's export) of a block's byte histogram: its order-0 cost in bytes"""
+    import numpy as np
+    hist = np.bincount(np.frombuffer(block, dtype=np.uint8), minlength=256).astype(np.uint32)
+    return _bg(lib).QZSTD_planeCostOf(hist.ctypes.data_as(C.POINTER(C.c_uint)), len(block))
+
+
+def plane_is_raw(cost: int, n: int, matched: int, lib=None) -> bool:
+    """QZSTD_planeIsRaw: the block (n bytes, `matched` of them covered by matches) is predicted to be a Raw_Block"""
+    return bool(_bg(lib).QZSTD_planeIsRawOf(cost, n, matched))
 
 
 class UngroupCmpRow(C.Structure):
@@ -259,6 +285,13 @@ def bind(F):
         F.QZSTD_frontGetDeltaSkip.argtypes = [C.c_void_p]
         F.QZSTD_frontDeltaSkipStats.restype = None
         F.QZSTD_frontDeltaSkipStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontSetPlaneProbe"):  # (absent from an older library)
+        F.QZSTD_frontSetPlaneProbe.restype = C.c_int
+        F.QZSTD_frontSetPlaneProbe.argtypes = [C.c_void_p, C.c_int]
+        F.QZSTD_frontGetPlaneProbe.restype = C.c_int
+        F.QZSTD_frontGetPlaneProbe.argtypes = [C.c_void_p]
+        F.QZSTD_frontPlaneProbeStats.restype = None
+        F.QZSTD_frontPlaneProbeStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     if hasattr(F, "QZSTD_frontVerifyDeviceBatch"):  # (absent from an older library)
         F.QZSTD_frontVerifyDeviceBatch.restype = C.c_size_t
         F.QZSTD_frontVerifyDeviceBatch.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(DeviceBuf),
@@ -275,6 +308,11 @@ def bind_bytegroup(L):
         fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint]
     L.QZSTD_byteGroupBlocks.restype = C.c_size_t
     L.QZSTD_byteGroupBlocks.argtypes = [C.c_size_t, C.c_uint, C.POINTER(C.c_size_t), C.c_size_t]
+    if hasattr(L, "QZSTD_planeCostOf"):  # (absent from an older library, and from qzstd_bytegroup.c built alone)
+        L.QZSTD_planeCostOf.restype = C.c_uint
+        L.QZSTD_planeCostOf.argtypes = [C.POINTER(C.c_uint), C.c_uint]
+        L.QZSTD_planeIsRawOf.restype = C.c_int
+        L.QZSTD_planeIsRawOf.argtypes = [C.c_uint, C.c_uint, C.c_uint]
     return L
 
 
@@ -465,6 +503,20 @@ class DeviceFront:
         a restore recognised"""
         st = (C.c_ulonglong * 4)()
         self.lib.QZSTD_frontDeltaSkipStats(self.f, st)
+        return list(st)
+
+    def set_plane_probe(self, on) -> int:
+        """QZSTD_frontSetPlaneProbe: the grouped and delta calls that follow find their noise planes on the GPU and write them as raw blocks
+        -> 0, or -1 while a call runs"""
+        return self.lib.QZSTD_frontSetPlaneProbe(self.f, 1 if on else 0)
+
+    def get_plane_probe(self) -> int:
+        return self.lib.QZSTD_frontGetPlaneProbe(self.f)
+
+    def plane_probe_stats(self) -> list:
+        """[0] blocks probed, [1] blocks written raw by the library, [2] frames assembled by the library, [3] frames that fell back"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontPlaneProbeStats(self.f, st)
         return list(st)
 
     def compress_device_batch(self, ptrs_and_sizes, stream: int | None = None) -> list:
@@ -914,6 +966,117 @@ def reference_frames_grouped(zstd, oracle, data: bytes, chunk: int, level: int, 
             if zstd.is_error(r):
                 raise RuntimeError("ZSTD_compressSequences: " + zstd.err(r))
             out.append(dst.raw[:r])
+    finally:
+        zstd.free(zc)
+    return out
+
+
+def frame_header(n: int, checksum: bool = False) -> bytes:
+    """magic and frame header of a frame the library writes itself: Single_Segment, the smallest Frame_Content_Size field that holds n"""
+    code = 0 if n <= 255 else (1 if n <= 65791 else (2 if n <= 0xFFFFFFFF else 3))
+    return b"\x28\xb5\x2f\xfd" + bytes([code << 6 | 0x20 | (4 if checksum else 0)]) + (n - 256 if code == 1 else n).to_bytes((1, 2, 4, 8)[code], "little")
+
+
+def frame_blocks(frame: bytes) -> list:
+    """the blocks of a zstd frame -> [(type, whole block: 3-byte header + body)], type 0 Raw, 1 RLE, 2 Compressed"""
+    fhd = frame[4]
+    single = (fhd >> 5) & 1
+    pos = 5 + (0 if single else 1) + (0, 1, 2, 4)[fhd & 3] + (single if fhd >> 6 == 0 else (0, 2, 4, 8)[fhd >> 6])
+    out = []
+    while True:
+        h = int.from_bytes(frame[pos:pos + 3], "little")
+        t = (h >> 1) & 3
+        whole = 3 + (1 if t == 1 else h >> 3)
+        out.append((t, frame[pos:pos + whole]))
+        pos += whole
+        if h & 1:
+            return out
+
+
+def reference_frames_probe(zstd, oracle, data: bytes, chunk: int, level: int, k: int, checksum: bool = False, lib=None,
+                           counts: dict | None = None) -> list:
+    """what the grouped device calls must produce with the plane probe on (QZSTD_frontSetPlaneProbe), the counterpart of
+    reference_frames_grouped: per frame the ORACLE's sequences for each block of group_blocks, the rule of include/qzstd_planecost.h over
+    each block's histogram and matched bytes, and libzstd.  A frame without a raw-predicted block — or with a plane of one value, or whose
+    sub-frame fails or holds a block libzstd would store raw — is reference_frames_grouped's frame; every other frame is assembled: the
+    library's frame header, a Raw_Block per raw-predicted block, and between them the blocks of ONE ZSTD_compressSequencesAndLiterals call
+    over the remaining blocks' entries and literals, Last_Block on the frame's final block only; with `checksum` the four bytes libzstd
+    appends to the same content.  counts: a dict that receives "blocks", "raw" (blocks written raw), "assembled", "allraw" (assembled
+    without a libzstd call: every block raw) and "fallback" (frames),
+    and "slack": the sum of (len >> 6) + 2 over the raw-predicted blocks of assembled frames"""
+    L = zstd.lib
+    L.ZSTD_compressSequencesAndLiterals.restype = C.c_size_t
+    L.ZSTD_compressSequencesAndLiterals.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(B.Sequence), C.c_size_t, C.c_void_p, C.c_size_t,
+                                                    C.c_size_t, C.c_size_t]
+    blk = min(chunk, 131072)
+    prof = oracle.profile(level, blk)
+    cap = B.sequence_bound(blk)
+    counts = counts if counts is not None else {}
+    for key in ("blocks", "raw", "assembled", "allraw", "fallback", "slack"):
+        counts.setdefault(key, 0)
+    zc = zstd.cctx(level, producer=oracle.producer_addr, state=None, fallback=True, validate=False)
+    zstd.set(zc, 1008, 1)  # ZSTD_c_blockDelimiters = ZSTD_sf_explicitBlockDelimiters
+    out = []
+    try:
+        dst = C.create_string_buffer(L.ZSTD_compressBound(chunk))
+        for o in range(0, len(data), chunk):
+            piece = data[o:o + chunk]
+            plain = reference_frames_grouped(zstd, oracle, piece, chunk, level, k, checksum=checksum, lib=lib)[0]
+            g = group_bytes(piece, k, lib)
+            blocks, start = [], 0
+            for end in group_blocks(len(g), k, lib):
+                b = g[start:end]
+                n, sq = oracle.find(prof, b, cap=cap)
+                if n == B.SEQ_ERROR:
+                    raise RuntimeError("the oracle failed a block")
+                ent = [(s.offset, s.litLength, s.matchLength, 0) for s in sq[:n]]
+                lits, p = bytearray(), 0
+                for _, ll, ml, _ in ent:
+                    lits += b[p:p + ll]
+                    p += ll + ml
+                raw = plane_is_raw(plane_cost(b, lib), len(b), len(b) - len(lits), lib)
+                blocks.append((b, ent, bytes(lits), raw))
+                start = end
+            counts["blocks"] += len(blocks)
+            n_raw = sum(1 for b in blocks if b[3])
+            if n_raw == 0:
+                out.append(plain)
+                continue
+            maybe_rle = any(len(b[1]) < 5 and len(b[2]) < 10 for b in blocks[1:]) and k > 1
+            sub = None
+            if not maybe_rle and n_raw < len(blocks):
+                ent = [e for b in blocks if not b[3] for e in b[1]]
+                lit = b"".join(b[2] for b in blocks if not b[3])
+                size = sum(len(b[0]) for b in blocks if not b[3])
+                arr = (B.Sequence * len(ent))(*ent)
+                lbuf = C.create_string_buffer(lit, len(lit) + 64)
+                L.ZSTD_CCtx_reset(zc, 1)  # ZSTD_reset_session_only
+                r = L.ZSTD_compressSequencesAndLiterals(zc, dst, len(dst), arr, len(ent), lbuf, len(lit), len(lit) + 64, size)
+                if not zstd.is_error(r):
+                    sub = frame_blocks(dst.raw[:r])
+                    lens = [len(b[0]) for b in blocks if not b[3]]
+                    if len(sub) != len(lens) or any(t == 2 and len(w) - 3 + (n >> 6) + 2 >= n for (t, w), n in zip(sub, lens)):
+                        sub = None
+            if maybe_rle or (sub is None and n_raw < len(blocks)):
+                counts["fallback"] += 1
+                out.append(plain)
+                continue
+            fr, it = bytearray(frame_header(len(g), checksum)), iter(sub or ())
+            for i, (b, _, _, raw) in enumerate(blocks):
+                last = 1 if i + 1 == len(blocks) else 0
+                if raw:
+                    fr += (len(b) << 3 | last).to_bytes(3, "little") + b
+                    counts["slack"] += (len(b) >> 6) + 2
+                else:
+                    w = bytearray(next(it)[1])
+                    w[0] = (w[0] & ~1) | last
+                    fr += w
+            if checksum:
+                fr += plain[-4:]
+            counts["raw"] += n_raw
+            counts["assembled"] += 1
+            counts["allraw"] += 1 if n_raw == len(blocks) else 0
+            out.append(bytes(fr))
     finally:
         zstd.free(zc)
     return out
