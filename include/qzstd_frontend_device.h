@@ -301,6 +301,37 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
  * launches (one per part) */
 void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Fingerprints: are the tensors that a restore brought back the tensors that were written — asked at LOAD time, weeks later, when the live
+ * tensors Verify needs are gone?  A 64-bit fingerprint (include/qzstd_fingerprint.h: parallel by construction, not XXH64, no wire format) of
+ * every chunk is taken on the GPU from the tensor's OWN bytes; the caller keeps it with the frames, 8 bytes per frame, as it keeps element
+ * sizes and bases; after any restore one call recomputes it and says which frames differ.  The fingerprint depends on the chunk's bytes and
+ * length alone — not on element size, base, level, grouping, probe or checksum settings — so a load against another base, with a swapped
+ * element size or with frames in another order, which passes every other check, fails this one.
+ *
+ * QZSTD_frontFingerprintDeviceBatch: fp[c] = QZSTD_fingerprintOf(chunk c) for the chunks as the compress calls cut frames —
+ * QZSTD_frontDeviceBatchFrames entries, the same rule per buffer, none for an empty buffer; firstFrame as in QZSTD_frontCompressDeviceBatch.
+ * Returns the frame count.  QZSTD_frontCheckDeviceBatch: the same pass, compared with expected[0 .. nFrames): returns HOW MANY FRAMES
+ * DIFFER — 0: the buffers are what was fingerprinted — and differs[c] (nFrames entries, or NULL) is 1 for those and 0 for the others.
+ *
+ * Both: the host-side pointer and device checks of QZSTD_frontCompressDeviceBatch, the library's stream waits for `stream`, ONE
+ * qzstd_hip_fingerprint launch with a row per frame pointing INTO the caller's buffers (nothing is staged, the buffers are only read: one
+ * byte read per content byte), one device->host copy of the tile digests (8 bytes per 16 KiB), a bounded wait, and the fold per frame on
+ * the calling thread.  Rows and digests live in grow-only pinned and device scratch kept with the front.  Blocks until done.  The calls work
+ * on live, restored or never-compressed tensors alike, and on any list of buffers whose chunks are the chunks that were fingerprinted.
+ * (size_t)-1 before anything is queued: everything the batch compress call refuses about bufs (a null array, a null pointer with a size,
+ * memory that is not device memory of one device), fp — or expected — NULL with frames to write or read, nFrames that is not the buffers'
+ * frame count (Check), a call while another one runs on this front, more than 2^32 - 1 frames or 2^31 - 1 tiles (32 TiB) in one call, and a
+ * device layer without qzstd_hip_fingerprint (as in the compress calls: also for a call without frames) — every other call is served by such
+ * a layer as before.  A front created with useProducer = 0 is accepted.  No buffers, or only empty ones: 0, and no GPU is touched. */
+unsigned long long QZSTD_fingerprintOf(const void *p, size_t len); /* QZSTD_fingerprint of include/qzstd_fingerprint.h, exported for bindings */
+size_t QZSTD_frontFingerprintDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, unsigned long long *fp,
+                                         size_t *firstFrame /* nBufs + 1, or NULL */);
+size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, const unsigned long long *expected,
+                                   size_t nFrames, unsigned char *differs /* nFrames entries, or NULL */);
+/* since creation, of the calls that succeeded: [0] frames fingerprinted, [1] bytes read on the device, [2] qzstd_hip_fingerprint launches,
+ * [3] frames a check found differing */
+void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 #if defined(__cplusplus)
 }
 #endif

@@ -4,7 +4,8 @@
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
  * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
  * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
- * the content-checksum kernel (QZSTD_frontSetChecksum), and the byte histograms' cost per block (QZSTD_frontSetPlaneProbe).
+ * the content-checksum kernel (QZSTD_frontSetChecksum), the byte histograms' cost per block (QZSTD_frontSetPlaneProbe), and the tile
+ * digests of the tensor fingerprints (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -331,6 +332,34 @@ typedef struct {
 } qzstd_hip_plane_row_t;
 int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
                          qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost);
+
+/*
+ * Fingerprint (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch): ONE launch digests every row — `len` bytes anywhere in device
+ * memory, at any alignment — tile by tile: d_tiles[tile0 + j] = QZSTD_fpTile of include/qzstd_fingerprint.h over the row's j-th 16 KiB (the
+ * last tile: what is left), computed on the device with that header's own functions.  The host folds a row's tile digests into its
+ * fingerprint (QZSTD_fpFold): 8 bytes per 16 KiB come back.
+ *
+ * Work is divided as in qzstd_hip_diff: a workgroup of 256 threads per 16 KiB tile of a row — QZSTD_HIP_FP_TILES(len) of them, none for an
+ * empty row — so rows of one byte and rows of 64 MiB in one launch keep the device equally busy.  The launcher writes tile0 (the running sum
+ * of the rows' workgroups) into the caller's rows before the upload; a workgroup finds its row by a binary search over it.  Loads are aligned
+ * 16-byte loads of the words that overlap [src, src + len) and of no other word, shifted into place in registers by the row's own
+ * misalignment; the bytes behind the row's last one are set to 0 before they are looked at, those in front of the first never arrive.  The
+ * lanes are folded across each wave (shuffles) and across the four waves (one LDS step), and one lane stores the tile's ONE word with an
+ * ordinary 8-byte store.  No atomics, no memset, no read-modify-write; nothing but d_tiles[0 .. sum of the rows' QZSTD_HIP_FP_TILES) is
+ * written — the rows' bytes are only read.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_tiles, a null src with len > 0, len > 0xFFFFFFE0, more than 2^31 - 1 workgroups.
+ * nRows == 0, or only empty rows: nothing is queued, 0.  Asynchronous on `stream`.
+ */
+#define QZSTD_HIP_FP_TILES(len) (((uint64_t)(len) + 16383u) >> 14)
+typedef struct {
+    uint64_t src;   /* device address of the row's first byte, any alignment */
+    uint32_t len;   /* bytes, may be 0 */
+    uint32_t tile0; /* written by the launcher: workgroups of the rows before this one */
+} qzstd_hip_fp_row_t;
+int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows, uint64_t *d_tiles);
 
 #if defined(__cplusplus)
 }

@@ -2,7 +2,7 @@
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
  * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
- * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), and the XXH64 content checksum.  They use nothing of the match-finder
+ * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), the XXH64 content checksum, the plane cost (plane probe) and the tile digests of the tensor fingerprints.  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -1483,5 +1483,95 @@ extern "C" int qzstd_hip_plane_cost(int device, void *stream, const void *d_base
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (plane cost rows)");
     hipLaunchKernelGGL(qzstd_plane_cost_kernel, dim3(nRows), dim3(kPlaneT), 0, (hipStream_t)stream, static_cast<const uint8_t *>(d_base), d_rows, d_cost);
     QZ_CHECK(hipGetLastError(), "launch qzstd_plane_cost_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- fingerprint (include/qzstd_hip_device.h, qzstd_fingerprint.h) -- */
+#include "qzstd_fingerprint.h"
+
+namespace {
+constexpr uint32_t kFpT = QZSTD_FP_LANES;       /* threads per workgroup: the definition's lanes */
+constexpr uint32_t kFpTileLog = QZSTD_FP_TILE_LOG; /* bytes of one row per workgroup: 16 KiB, four 16-byte words per lane */
+constexpr uint32_t kFpWords = (1u << kFpTileLog) / 16u / kFpT;
+static_assert(kFpT == 256u && kFpWords == 4u && kFpTileLog == kDiffTileLog, "the definition's tile: 256 lanes, four words each");
+
+/* One workgroup per 16 KiB tile of a row; its row is the last one with tile0 <= blockIdx.x (qzstd_diff_kernel's search).  Lane t fetches
+ * the tile's words t, t + 256, t + 512, t + 768 as the comparison fetches its sides — group_fetch: the aligned words that overlap the wanted
+ * bytes only, shifted by the row's OWN misalignment — all four before the first round, so that the loads are in flight together; the bytes
+ * behind the row's last one are masked to 0 (cmp_mask) before they enter a round.  Then the definition's tree: six steps inside the wave
+ * (lane t takes lane t + s by a shuffle; the lanes that are no multiple of 2 s compute a value nobody reads), one word per wave through
+ * LDS, and thread 0 does the last two steps and stores the tile's ONE word.  No atomics, nothing is read back. */
+__global__ __launch_bounds__(kFpT) void qzstd_fingerprint_kernel(const qzstd_hip_fp_row_t *__restrict__ rows, uint32_t nRows,
+                                                                 unsigned long long *__restrict__ tilesOut)
+{
+    __shared__ uint32_t which;
+    __shared__ uint64_t red[kFpT / 64u];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const qzstd_hip_fp_row_t row = rows[which];
+    const uint64_t at = (uint64_t)(blockIdx.x - row.tile0) << kFpTileLog; /* the tile's first byte in its row */
+    if (at >= row.len) return; /* (the whole workgroup; never: rows without a tile share the tile0 of the row behind them) */
+    const uint32_t tileBytes = row.len - at < (1u << kFpTileLog) ? (uint32_t)(row.len - at) : 1u << kFpTileLog;
+    uint64_t w0[kFpWords], w1[kFpWords];
+#pragma unroll
+    for (uint32_t k = 0; k < kFpWords; k++) {
+        const uint32_t w = tid + k * kFpT;
+        w0[k] = w1[k] = 0ull;
+        if (w * 16u < tileBytes) {
+            const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+            group_fetch(row.src + at + w * 16u, valid, &w0[k], &w1[k]);
+            cmp_mask(valid, &w0[k], &w1[k]); /* the row's last word: what lies behind the row reads as 0 */
+        }
+    }
+    uint64_t acc = QZSTD_fpLaneInit(tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kFpWords; k++)
+        if ((tid + k * kFpT) * 16u < tileBytes) acc = QZSTD_fpWord(acc, w0[k], w1[k]);
+#pragma unroll
+    for (uint32_t s = 1u; s < 64u; s <<= 1) {
+        const uint64_t other = __shfl_down(acc, s, 64);
+        acc = QZSTD_fpMerge(acc, other);
+    }
+    if ((tid & 63u) == 0u) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        const uint64_t a = QZSTD_fpMerge(red[0], red[1]), b = QZSTD_fpMerge(red[2], red[3]); /* s = 64 */
+        tilesOut[blockIdx.x] = QZSTD_fpMerge(a, b);                                          /* s = 128 */
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows, uint64_t *d_tiles)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_tiles) return fail_msg("qzstd_hip_fingerprint: null pointer");
+    uint64_t total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_fp_row_t &r = rows[i];
+        if (r.len && !r.src) return fail_msg("qzstd_hip_fingerprint: null row");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_fingerprint: row too long");
+        total += QZSTD_HIP_FP_TILES(r.len);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_fingerprint: too many tiles");
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_FP_TILES(rows[i].len);
+    }
+    if (total == 0) return 0; /* nothing but empty rows */
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (fingerprint rows)");
+    hipLaunchKernelGGL(qzstd_fingerprint_kernel, dim3((uint32_t)total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows,
+                       reinterpret_cast<unsigned long long *>(d_tiles));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_fingerprint_kernel");
     return 0;
 }

@@ -1,0 +1,150 @@
+/*
+ * qzstd_fingerprint.c — QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch / QZSTD_frontFingerprintStats / QZSTD_fingerprintOf
+ * (include/qzstd_frontend_device.h): a 64-bit fingerprint (include/qzstd_fingerprint.h) of every chunk of a list of device buffers, taken on
+ * the GPU from the tensors' own bytes, and the check of such buffers against fingerprints kept from an earlier call.  Part of
+ * qzstd_frontend.c's translation unit, included behind qzstd_verify.c; it uses the restore's first slot (its stream, and grow-only pinned
+ * and device scratch kept there between calls).
+ *
+ * A call is: the host-side checks of the batch compress call, the slot's stream waiting for the caller's, ONE qzstd_hip_fingerprint launch
+ * with a row per frame that points INTO the caller's buffers (nothing is staged or copied on the device), one device->host copy of the tile
+ * digests (8 bytes per 16 KiB), a bounded wait, and QZSTD_fpFold per frame on the calling thread.  Nothing of the producer or the workers is
+ * used: a front created with useProducer = 0 serves the calls.
+ */
+
+extern int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows,
+                                 uint64_t *d_tiles) __attribute__((weak));
+
+unsigned long long QZSTD_fingerprintOf(const void *p, size_t len) { return p || !len ? QZSTD_fingerprint(p, len) : 0ull; }
+
+/* both calls: fp[c] receives the fingerprint of frame c (fp may be NULL when expected is not); with `expected`, differs[c] (or NULL) says
+ * whether it is another one, and the return value counts those frames instead of all */
+static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, unsigned long long *fp, size_t *firstFrame,
+                                  const unsigned long long *expected, int check, size_t nExpected, unsigned char *differs)
+{
+    QF_RestoreSlot *s;
+    void *ev = NULL, *h;
+    size_t i, c = 0, nFrames = 0, nTiles = 0, total = 0, t = 0, nDiff = 0;
+    int dev = -1, rc = 0;
+    /* host-side checks, the batch compress call's: nothing has touched a GPU when one of them fails */
+    if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    for (i = 0; i < nBufs; i++) {
+        if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+        nFrames += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+        nTiles += (bufs[i].size / f->p.chunkSize) * (size_t)QZSTD_HIP_FP_TILES(f->p.chunkSize) + (size_t)QZSTD_HIP_FP_TILES(bufs[i].size % f->p.chunkSize);
+    }
+    if (check) {
+        if (nExpected != nFrames || (nFrames && !expected)) return (size_t)-1;
+    } else if (nFrames && !fp) {
+        return (size_t)-1;
+    }
+    if (nFrames > 0xFFFFFFFFu || nTiles > 0x7FFFFFFFu || f->p.chunkSize > 0xFFFFFFE0u) return (size_t)-1; /* (one launch: 32-bit rows and tiles) */
+    if (!qzstd_hip_fingerprint || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
+        !qzstd_hip_event_destroy)
+        return (size_t)-1; /* a device layer without the fingerprint kernel, or without the device-input entry points at all */
+    for (i = 0; i < nBufs; i++) {
+        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
+        int d;
+        if (!bufs[i].size) continue;
+        d = qzstd_hip_pointer_device(p);
+        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
+        dev = d;
+        total += bufs[i].size;
+    }
+    if (nFrames) {
+        pthread_mutex_lock(&f->mu);
+        if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
+        f->devBusy = 1;
+        pthread_mutex_unlock(&f->mu);
+    }
+    if (firstFrame) {
+        for (i = 0, c = 0; i < nBufs; i++) {
+            firstFrame[i] = c;
+            c += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+        }
+        firstFrame[nBufs] = c;
+    }
+    if (nFrames == 0) return 0;
+
+    /* the restore's slots, kept with the front between calls: the first one's stream and scratch */
+    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
+    if (!f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
+    f->restoreSlotDev = dev;
+    s = f->restoreSlot;
+    if (rc == 0 && !s->stream && !(s->stream = qzstd_hip_stream_create(dev))) rc = -1;
+    if (rc == 0) {
+        h = s->hFpRows;
+        if (qfGrowH(&h, &s->hFpRowsCap, nFrames * sizeof(qzstd_hip_fp_row_t))) rc = -1;
+        s->hFpRows = (qzstd_hip_fp_row_t *)h;
+    }
+    if (rc == 0) {
+        h = s->hFpTiles;
+        if (qfGrowH(&h, &s->hFpTilesCap, nTiles * sizeof(uint64_t))) rc = -1;
+        s->hFpTiles = (uint64_t *)h;
+    }
+    if (rc == 0 && (qfGrowD(dev, &s->dFpRows, &s->dFpRowsCap, nFrames * sizeof(qzstd_hip_fp_row_t)) ||
+                    qfGrowD(dev, &s->dFpTiles, &s->dFpTilesCap, nTiles * sizeof(uint64_t))))
+        rc = -1;
+    /* the slot's stream waits for what the caller queued on `stream` so far: whatever last wrote the buffers */
+    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
+    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, s->stream, ev))) rc = -1;
+    if (rc == 0) {
+        for (i = 0, c = 0; i < nBufs; i++) {
+            size_t off;
+            for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
+                qzstd_hip_fp_row_t *r = &s->hFpRows[c];
+                r->src = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
+                r->len = (uint32_t)(bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
+                r->tile0 = 0;
+            }
+        }
+        if (qzstd_hip_fingerprint(dev, s->stream, s->hFpRows, (uint32_t)nFrames, (qzstd_hip_fp_row_t *)s->dFpRows, (uint64_t *)s->dFpTiles) ||
+            qzstd_hip_memcpy_d2h(dev, s->stream, s->hFpTiles, s->dFpTiles, nTiles * sizeof(uint64_t)))
+            rc = -1;
+    }
+    /* nothing the library queued may still read the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
+    if (s && s->stream && qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
+        (void)qzstd_hip_stream_sync(dev, s->stream);
+        rc = -1;
+    }
+    for (c = 0; c < nFrames && rc == 0; c++) {
+        const size_t n = (size_t)QZSTD_HIP_FP_TILES(s->hFpRows[c].len);
+        const unsigned long long v = QZSTD_fpFold(s->hFpTiles + t, n, s->hFpRows[c].len);
+        t += n;
+        if (fp) fp[c] = v;
+        if (check) {
+            const int d = v != expected[c];
+            if (differs) differs[c] = (unsigned char)d;
+            nDiff += (size_t)d;
+        }
+    }
+    if (ev) qzstd_hip_event_destroy(dev, ev);
+    if (rc == 0) {
+        __atomic_fetch_add(&f->fpStats[0], (unsigned long long)nFrames, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->fpStats[1], (unsigned long long)total, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->fpStats[2], 1ull, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->fpStats[3], (unsigned long long)nDiff, __ATOMIC_RELAXED);
+    }
+    pthread_mutex_lock(&f->mu);
+    f->devBusy = 0;
+    pthread_mutex_unlock(&f->mu);
+    return rc ? (size_t)-1 : (check ? nDiff : nFrames);
+}
+
+size_t QZSTD_frontFingerprintDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, unsigned long long *fp,
+                                         size_t *firstFrame)
+{
+    return qfFingerprintDevice(f, bufs, nBufs, stream, fp, firstFrame, NULL, 0, 0, NULL);
+}
+
+size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, const unsigned long long *expected,
+                                   size_t nFrames, unsigned char *differs)
+{
+    return qfFingerprintDevice(f, bufs, nBufs, stream, NULL, NULL, expected, 1, nFrames, differs);
+}
+
+void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->fpStats[k], __ATOMIC_RELAXED) : 0ull;
+}

@@ -15,6 +15,7 @@
 #include "qzstd_bytegroup_internal.h"
 #include "qzstd_hip_device.h"
 #include "qzstd_planecost.h"
+#include "qzstd_fingerprint.h"
 
 #include <dlfcn.h>
 #include <pthread.h>
@@ -106,6 +107,7 @@ struct QZSTD_Front_s {
     QF_RestoreSlot *restoreSlot;
     int restoreSlotDev;
     unsigned long long verifyStats[4]; /* QZSTD_frontVerifyDeviceBatch: frames compared, of them differing, bytes compared, launches */
+    unsigned long long fpStats[4];     /* the fingerprint calls: frames fingerprinted, bytes read on the device, launches, frames a check found differing */
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -1725,3 +1727,6 @@ int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { ret
 
 /* The verify call: the restore's slots and decode with a comparison in the scatter's place; included the same way. */
 #include "qzstd_verify.c"
+
+/* The fingerprint calls: one launch over the caller's own buffers, on the restore's first slot; included the same way. */
+#include "qzstd_fingerprint.c"

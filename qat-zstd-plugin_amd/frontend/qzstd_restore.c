@@ -59,6 +59,10 @@ struct QF_RestoreSlot_s {
     void *dTiles; size_t dTilesCap;                            /* the launch's tile words and their pinned copy, */
     uint32_t *hTiles; size_t hTilesCap;
     size_t pending;                                            /* and the part (+ 1) whose tile words are on their way; 0: none */
+    qzstd_hip_fp_row_t *hFpRows; size_t hFpRowsCap;            /* the fingerprint calls (qzstd_fingerprint.c, slot 0 only): a row per frame, */
+    void *dFpRows; size_t dFpRowsCap;
+    void *dFpTiles; size_t dFpTilesCap;                        /* the launch's tile digests and their pinned copy */
+    uint64_t *hFpTiles; size_t hFpTilesCap;
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -85,6 +89,10 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->hCmpRows) qzstd_hip_host_free(s->hCmpRows);
         if (s->dTiles) qzstd_hip_free(f->restoreSlotDev, s->dTiles);
         if (s->hTiles) qzstd_hip_host_free(s->hTiles);
+        if (s->dFpRows) qzstd_hip_free(f->restoreSlotDev, s->dFpRows);
+        if (s->hFpRows) qzstd_hip_host_free(s->hFpRows);
+        if (s->dFpTiles) qzstd_hip_free(f->restoreSlotDev, s->dFpTiles);
+        if (s->hFpTiles) qzstd_hip_host_free(s->hFpTiles);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);

@@ -100,6 +100,18 @@ N GiB of 128 KiB rows, and qzstd_hip_plane_cost over N GiB of 128 KiB rows of a 
 bytes of bf16 N(0, 0.02) weights: a handful of values) and over the grouped stage's own 64 KiB planes as the front-end launches it.
 
   python tools/device_bench.py --probe --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
+
+--fingerprint: the load-time check (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch) — N GiB of bf16 N(0, 0.02) weights as one
+tensor and as N x 8192 tensors of 128 KiB.  Three legs, alternating in one run, every run listed, ms per call (the call and the closing
+synchronize):
+  fingerprint  one QZSTD_frontFingerprintDeviceBatch call
+  host_hash    what a caller can do today: t.cpu() per tensor and XXH64 (python-xxhash) of every 128 KiB chunk on --threads threads
+  verify       QZSTD_frontVerifyDeviceBatch of the same tensors' level-1 grouped frames: the only other end-to-end check, which needs the live tensors
+then, in the same run, the kernels through the C ABI with events around ONE launch each over N GiB of 128 KiB rows, the three alternating:
+qzstd_hip_fingerprint, qzstd_hip_diff (two sides) and qzstd_hip_xxh64, ms per GiB.  --kernels: those kernel legs alone (also the run to put
+under rocprofv3).
+
+  python tools/device_bench.py --fingerprint --gib 1 --reps 3 [--kernels]
 """
 import argparse
 import json
@@ -1074,8 +1086,168 @@ def probe_main(a):
     print(json.dumps(out))
 
 
+def fingerprint_kernels(a, size, out):
+    """qzstd_hip_fingerprint beside qzstd_hip_diff and qzstd_hip_xxh64 IN ONE RUN: ONE launch each over the same N GiB as rows of 128 KiB, ms per
+    GiB from events around the launch (rows uploaded inside), the three alternating, every run listed after one untimed round"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_fingerprint_kernel(D.bind_diff_kernel(plug.lib))
+    L.qzstd_hip_xxh64.restype = C.c_int
+    L.qzstd_hip_xxh64.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    n = size // a.chunk
+    torch.manual_seed(0)
+    src = (torch.randn(size // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8)
+    same = src.clone()
+    tiles = torch.empty(size >> 14, dtype=torch.int64, device="cuda:0")
+    flags = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    hashes = torch.empty(n, dtype=torch.int64, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.DiffRow))
+    assert d_rows and src.data_ptr() % 16 == 0
+    gib = size / float(1 << 30)
+    fp_rows, diff_rows, hash_rows = (D.FpRow * n)(), (D.DiffRow * n)(), (D.HashRow * n)()
+    for c in range(n):
+        o = c * a.chunk
+        fp_rows[c].src, fp_rows[c].len = src.data_ptr() + o, a.chunk
+        diff_rows[c].a, diff_rows[c].b, diff_rows[c].len = src.data_ptr() + o, same.data_ptr() + o, a.chunk
+        hash_rows[c].srcOff, hash_rows[c].len = o, a.chunk
+    legs = (("fingerprint", lambda: L.qzstd_hip_fingerprint(0, None, fp_rows, n, d_rows, tiles.data_ptr())),
+            ("diff", lambda: L.qzstd_hip_diff(0, None, diff_rows, n, d_rows, flags.data_ptr())),
+            ("xxh64", lambda: L.qzstd_hip_xxh64(0, None, src.data_ptr(), hash_rows, n, d_rows, hashes.data_ptr())))
+    # the same three over the FIRST 64 MiB only (512 rows): a part of the compress calls, the launch size the checksum kernel's 4.7 ms per GiB
+    # was measured at (profiles/device_checksum_kernels.txt: 16 such launches a GiB)
+    m = min(n, (64 << 20) // a.chunk)
+    part = (("fingerprint", lambda: L.qzstd_hip_fingerprint(0, None, fp_rows, m, d_rows, tiles.data_ptr())),
+            ("diff", lambda: L.qzstd_hip_diff(0, None, diff_rows, m, d_rows, flags.data_ptr())),
+            ("xxh64", lambda: L.qzstd_hip_xxh64(0, None, src.data_ptr(), hash_rows, m, d_rows, hashes.data_ptr())))
+    runs = {name: [] for name, _ in legs}
+    part_runs = {name: [] for name, _ in part}
+    try:
+        for which, into, scale in ((legs, runs, gib), (part, part_runs, 1.0)):
+            for i in range(a.reps + 1):
+                for name, call in which:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    assert call() == 0, plug.err()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i:
+                        into[name].append(round(e0.elapsed_time(e1) / scale, 3))
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    assert not bool(flags.any())
+    # the digests are worth something: the first and the last row against the plain-C function
+    host = src[:a.chunk].cpu().numpy().tobytes(), src[size - a.chunk:].cpu().numpy().tobytes()
+    per = a.chunk >> 14
+    lib = B.Front().lib
+    for row, data in ((0, host[0]), (n - 1, host[1])):
+        got = D.fp_fold_ref([v & 0xFFFFFFFFFFFFFFFF for v in tiles[row * per:(row + 1) * per].tolist()], a.chunk)
+        assert got == D.fingerprint_of(data, lib=lib), row
+    out["kernels"] = {"rows": n, "row_bytes": a.chunk, "fingerprint_ms_per_gib": runs["fingerprint"], "diff_ms_per_gib": runs["diff"],
+                      "xxh64_ms_per_gib": runs["xxh64"],
+                      "part_rows": m, "part_fingerprint_ms_per_launch": part_runs["fingerprint"], "part_diff_ms_per_launch": part_runs["diff"],
+                      "part_xxh64_ms_per_launch": part_runs["xxh64"],
+                      "part": "the same three launches over the first %d rows only (%d MiB: one part of a compress call), ms per LAUNCH" % (m, m * a.chunk >> 20),
+                      "timed": "events around ONE launch each (rows uploaded inside) over the same %d rows of %d bytes, ms per GiB of rows, the three "
+                               "alternating in one run, every run of %d after one untimed round; diff reads two sides (2 bytes per content byte)" % (n, a.chunk, a.reps)}
+
+
+def fingerprint_main(a):
+    """--fingerprint: QZSTD_frontFingerprintDeviceBatch against what a caller can do today — t.cpu() and a host hash of the chunks on --threads
+    threads — and beside QZSTD_frontVerifyDeviceBatch, the only existing end-to-end check, on N GiB of bf16 as one tensor and as tensors of
+    128 KiB; then the kernel beside qzstd_hip_diff and qzstd_hip_xxh64 in the same run.  --kernels: the kernel legs alone"""
+    import ctypes as C
+    from concurrent.futures import ThreadPoolExecutor
+    import xxhash
+    size = int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "reps": a.reps, "dtype": "bf16"}
+    if a.kernels:
+        fingerprint_kernels(a, size, out)
+        return print(json.dumps(out))
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out["timed"] = ("ms per call, every run, the legs alternating in one run; the window holds the call and the closing synchronize: fingerprint = "
+                    "QZSTD_frontFingerprintDeviceBatch; host_hash = t.cpu() per tensor and xxhash.xxh64 of every %d-byte chunk on %d threads (the "
+                    "module releases the GIL); verify = QZSTD_frontVerifyDeviceBatch of level-1 grouped frames of the same tensors against "
+                    "them (it needs the LIVE tensors: no load-time check)" % (a.chunk, a.threads))
+    out["cells"] = {}
+    whole = (torch.randn(size // 2, device="cuda:0") * 0.02).to(torch.bfloat16)
+    pool = ThreadPoolExecutor(a.threads)
+    for layout, nt in (("one_tensor", 1), ("%d_tensors" % n, n)):
+        per = size // nt
+        tensors = [whole[i * (per // 2):(i + 1) * (per // 2)] for i in range(nt)]
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        cell = out["cells"][layout] = {}
+        try:
+            fr.reserve(size)
+            bufs, _, frames_n = fr.batch([(x.data_ptr(), per) for x in tensors])
+            assert frames_n == n
+            fp = (C.c_ulonglong * n)()
+            es = bytes([2] * nt) + b"\0"
+            _, sizes = fr._frame_buffers(n)
+            assert fr.lib.QZSTD_frontCompressDeviceBatchTyped(fr.f, bufs, es, nt, stream, fr._dst, len(fr._dst), sizes, None) == n
+            frames = C.create_string_buffer(n * fr.stride)
+            C.memmove(frames, fr._dst, n * fr.stride)
+
+            def fingerprint():
+                return fr.lib.QZSTD_frontFingerprintDeviceBatch(fr.f, bufs, nt, stream, fp, None)
+
+            def host_hash():
+                def one(t):
+                    h = t.cpu().view(torch.uint8).numpy()
+                    return [xxhash.xxh64(h[o:o + a.chunk]).intdigest() for o in range(0, len(h), a.chunk)]
+                if nt == 1:  # one tensor: one copy, its chunks hashed on the threads
+                    h = tensors[0].cpu().view(torch.uint8).numpy()
+                    return len(list(pool.map(lambda o: xxhash.xxh64(h[o:o + a.chunk]).intdigest(), range(0, size, a.chunk))))
+                return sum(len(x) for x in pool.map(one, tensors))
+
+            def verify():
+                r = fr.lib.QZSTD_frontVerifyDeviceBatch(fr.f, frames, fr.stride, sizes, n, bufs, None, es, nt, stream, None)
+                return n if r == 0 else r
+
+            legs = (("fingerprint", fingerprint), ("host_hash", host_hash), ("verify", verify))
+            runs = {name + "_ms": [] for name, _ in legs}
+            for name, leg in legs:  # untimed: the slots, the pinned scratch
+                assert leg() == n, name
+                torch.cuda.synchronize()
+            for _ in range(a.reps):
+                for name, leg in legs:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    assert leg() == n, name
+                    torch.cuda.synchronize()
+                    runs[name + "_ms"].append(round((time.perf_counter() - t0) * 1e3, 2))
+            cell.update(runs)
+            # the answer is worth something: the plain-C function over the first and the last chunk, and one bit found at its place
+            host = whole.view(torch.uint8)
+            assert fp[0] == D.fingerprint_of(host[:a.chunk].cpu().numpy().tobytes(), lib=lib)
+            assert fp[n - 1] == D.fingerprint_of(host[size - a.chunk:].cpu().numpy().tobytes(), lib=lib)
+            flags = C.create_string_buffer(n)
+            host[3 * a.chunk + 16385] ^= 1
+            torch.cuda.synchronize()
+            assert fr.lib.QZSTD_frontCheckDeviceBatch(fr.f, bufs, nt, stream, fp, n, flags) == 1 and flags.raw == bytes(3) + b"\x01" + bytes(n - 4)
+            host[3 * a.chunk + 16385] ^= 1
+            torch.cuda.synchronize()
+            cell["d2h_bytes"] = 8 * (size >> 14)
+            cell["h2d_bytes"] = 16 * n
+            cell["fingerprint_stats"] = fr.fingerprint_stats()
+        finally:
+            fr.close()
+        del tensors
+    pool.shutdown()
+    del whole
+    torch.cuda.empty_cache()
+    fingerprint_kernels(a, size, out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--fingerprint", action="store_true")
     ap.add_argument("--probe", action="store_true")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--skip", action="store_true")
@@ -1096,6 +1268,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.fingerprint:
+        return fingerprint_main(a)
     if a.probe:
         return probe_main(a)
     if a.verify:

@@ -5,7 +5,10 @@ the delta calls against a base per buffer (QZSTD_frontCompressDeviceBatchDelta, 
 DeviceFront.compress_device_batch_delta / restore_batch_delta), delta skip (QZSTD_frontSetDeltaSkip, QZSTD_frontDeltaSkipStats:
 DeviceFront.set_delta_skip / delta_skip_stats; qzstd_hip_diff's row, binding and numpy reference; zero_frame()), the verify call
 (QZSTD_frontVerifyDeviceBatch, QZSTD_frontVerifyStats: DeviceFront.verify / verify_stats, verify_tensors(); qzstd_hip_ungroup_cmp's row, binding and
-numpy reference ungroup_cmp_ref()), slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
+numpy reference ungroup_cmp_ref()), the fingerprint calls (QZSTD_frontFingerprintDeviceBatch, QZSTD_frontCheckDeviceBatch,
+QZSTD_frontFingerprintStats: DeviceFront.fingerprint / check / fingerprint_stats, fingerprint_tensors() / check_tensors(); qzstd_hip_fingerprint's
+row and binding; fingerprint_ref(), the restatement of include/qzstd_fingerprint.h, and fingerprint_of(), that header's own function),
+slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
 QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
 the plane probe (QZSTD_frontSetPlaneProbe, QZSTD_frontPlaneProbeStats: DeviceFront.set_plane_probe / plane_probe_stats; qzstd_hip_plane_cost's row and
 binding; plane_cost() / plane_is_raw(), the rule of include/qzstd_planecost.h; reference_frames_probe(): what the calls must produce with the setting on),
@@ -92,6 +95,149 @@ def diff_tile0_ref(lens):
         out.append(total)
         total += (n + 16383) >> 14
     return out
+
+
+class FpRow(C.Structure):
+    """qzstd_hip_fp_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("len", C.c_uint32), ("tile0", C.c_uint32)]
+
+
+def bind_fingerprint_kernel(L):
+    """qzstd_hip_fingerprint on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_fingerprint.restype = C.c_int
+    L.qzstd_hip_fingerprint.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    return L
+
+
+def fp_tiles(n: int) -> int:
+    """QZSTD_HIP_FP_TILES: workgroups of a row = its tile digests (16 KiB each)"""
+    return (n + 16383) >> 14
+
+
+_FP_M = (1 << 64) - 1
+_FP_P1, _FP_P2, _FP_P3, _FP_P4, _FP_P5 = (0x9E3779B185EBCA87, 0xC2B2AE3D27D4EB4F, 0x165667B19E3779F9, 0x85EBCA77C2B2AE63,
+                                          0x27D4EB2F165667C5)  # XXH64's five primes
+
+
+def _fp_round(acc, x):
+    """round(acc, in) = rotl(acc + in * P2, 31) * P1, on numpy uint64 arrays (arithmetic mod 2^64)"""
+    import numpy as np
+    acc = acc + x * np.uint64(_FP_P2)
+    return ((acc << np.uint64(31)) | (acc >> np.uint64(33))) * np.uint64(_FP_P1)
+
+
+def _fp_merge(h, v):
+    """merge(h, v) = (h ^ round(0, v)) * P1 + P4"""
+    import numpy as np
+    return (h ^ _fp_round(np.zeros_like(v), v)) * np.uint64(_FP_P1) + np.uint64(_FP_P4)
+
+
+def fp_tile_ref(data) -> int:
+    """the tile digest restated (a second specification, written from the definition's text, not from include/qzstd_fingerprint.h): n bytes,
+    0 < n <= 16384, as 16-byte little-endian words, bytes at or beyond n read as 0; 256 lanes, lane t from P5 + t * P1 over the words
+    t, t + 256, t + 512, t + 768 that start below n — low half, then high half, one round each; the lanes folded by the fixed binary tree
+    acc[t] = merge(acc[t], acc[t + s]) for s = 1, 2, ..., 128 and t a multiple of 2 s; the digest is lane 0"""
+    import numpy as np
+    raw = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = len(raw)
+    assert 0 < n <= 16384
+    buf = np.zeros(16384, dtype=np.uint8)
+    buf[:n] = raw
+    halves = buf.view("<u8").astype(np.uint64).reshape(4, 256, 2)  # [k][t] = word t + 256 k: (low, high)
+    lanes = np.arange(256, dtype=np.uint64)
+    with np.errstate(over="ignore"):
+        acc = np.uint64(_FP_P5) + lanes * np.uint64(_FP_P1)
+        for k in range(4):
+            took = _fp_round(_fp_round(acc, halves[k, :, 0]), halves[k, :, 1])
+            acc = np.where(16 * (np.arange(256) + 256 * k) < n, took, acc)
+        s = 1
+        while s < 256:
+            t = np.arange(0, 256, 2 * s)
+            acc[t] = _fp_merge(acc[t], acc[t + s])
+            s *= 2
+    return int(acc[0])
+
+
+def fp_fold_ref(tiles, n: int) -> int:
+    """the row fingerprint from its tile digests: h = P5 + len; h = merge(h, tile) for every tile in order; the final avalanche"""
+    rotl = lambda v, r: ((v << r) | (v >> (64 - r))) & _FP_M  # noqa: E731
+    h = (_FP_P5 + n) & _FP_M
+    for v in tiles:
+        h = ((h ^ (rotl(int(v) * _FP_P2 & _FP_M, 31) * _FP_P1 & _FP_M)) * _FP_P1 + _FP_P4) & _FP_M
+    h ^= h >> 33
+    h = h * _FP_P2 & _FP_M
+    h ^= h >> 29
+    h = h * _FP_P3 & _FP_M
+    return h ^ (h >> 32)
+
+
+def fingerprint_ref(data) -> int:
+    """QZSTD_fingerprint restated: the row cut into 16 KiB tiles from its start, fp_tile_ref of each, fp_fold_ref over them with the length"""
+    data = bytes(data)
+    return fp_fold_ref([fp_tile_ref(data[o:o + 16384]) for o in range(0, len(data), 16384)], len(data))
+
+
+FP_LENS = (0, 1, 15, 16, 17, 4095, 4096, 4097, 16383, 16384, 16385, 3 * 16384 + 5)  # the edge lengths of the fingerprint tests
+
+
+def fp_corpus(n: int, seed: int):
+    """the fingerprint tests' input of n bytes (tests/fingerprint/fingerprint_check.c: fill) as a numpy uint8 array: byte i is the low byte
+    of a 32-bit mix of i and the seed — the host checker and the GPU tests assert their properties on the SAME bytes"""
+    import numpy as np
+    with np.errstate(over="ignore"):
+        x = np.arange(n, dtype=np.uint32) * np.uint32(2654435761) + np.uint32(seed * 2246822519 & 0xFFFFFFFF)
+        x ^= x >> np.uint32(15)
+        x *= np.uint32(2246822519)
+        x ^= x >> np.uint32(13)
+    return x.astype(np.uint8)
+
+
+def fp_variants(data):
+    """the pairs the host checker asserts to differ under the plain-C definition, as (name, changed copy of `data`) — one bit in the first
+    byte, the last byte and either side of the 4096 and 16384 boundaries, words w and w + 256 swapped (one lane), neighbouring words swapped
+    (neighbouring lanes), two tiles swapped, a zero byte appended; only the ones the length allows"""
+    import numpy as np
+    n, out = len(data), []
+
+    def changed(name, fn):
+        d = data.copy()
+        fn(d)
+        out.append((name, d))
+
+    def flip(at, bit):
+        def fn(d):
+            d[at] ^= bit
+        return fn
+
+    def swap(a, b, ln):
+        def fn(d):
+            t = d[a:a + ln].copy()
+            d[a:a + ln] = d[b:b + ln]
+            d[b:b + ln] = t
+        return fn
+
+    if n:
+        changed("first byte", flip(0, 0x01))
+        changed("last byte", flip(n - 1, 0x80))
+    for at in (4095, 4096, 16383, 16384):
+        if at < n:
+            changed("byte %d" % at, flip(at, 0x10))
+    if n >= 16 * 260:
+        changed("words 3 and 259", swap(48, 16 * 259, 16))
+        changed("words 3 and 4", swap(48, 64, 16))
+    if n >= 2 * 16384:
+        changed("tiles 0 and 1", swap(0, 16384, 16384))
+    out.append(("a zero byte appended", np.concatenate([data, np.zeros(1, dtype=np.uint8)])))
+    return out
+
+
+def fingerprint_of(data, lib=None) -> int:
+    """QZSTD_fingerprintOf: include/qzstd_fingerprint.h's own function through the front-end library's export"""
+    L = lib if lib is not None else B.Front().lib
+    L.QZSTD_fingerprintOf.restype = C.c_ulonglong
+    L.QZSTD_fingerprintOf.argtypes = [C.c_char_p, C.c_size_t]
+    data = bytes(data)
+    return L.QZSTD_fingerprintOf(data, len(data))
 
 
 class PlaneRow(C.Structure):
@@ -298,6 +444,17 @@ def bind(F):
                                                    C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
         F.QZSTD_frontVerifyStats.restype = None
         F.QZSTD_frontVerifyStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontFingerprintDeviceBatch"):  # (absent from an older library)
+        F.QZSTD_fingerprintOf.restype = C.c_ulonglong
+        F.QZSTD_fingerprintOf.argtypes = [C.c_char_p, C.c_size_t]
+        F.QZSTD_frontFingerprintDeviceBatch.restype = C.c_size_t
+        F.QZSTD_frontFingerprintDeviceBatch.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong),
+                                                        C.POINTER(C.c_size_t)]
+        F.QZSTD_frontCheckDeviceBatch.restype = C.c_size_t
+        F.QZSTD_frontCheckDeviceBatch.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_size_t, C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t,
+                                                  C.c_void_p]
+        F.QZSTD_frontFingerprintStats.restype = None
+        F.QZSTD_frontFingerprintStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -715,6 +872,52 @@ class DeviceFront:
         self.lib.QZSTD_frontVerifyStats(self.f, st)
         return list(st)
 
+    def fingerprint_raw(self, ptrs_and_sizes, stream: int | None = None, null_fp: bool = False):
+        """QZSTD_frontFingerprintDeviceBatch -> (return value, the fingerprints as a flat list or None, firstFrame as a list)"""
+        bufs, nb, n = self.batch(ptrs_and_sizes)
+        fp = (C.c_ulonglong * max(n if n != ERROR else 0, 1))()
+        first = (C.c_size_t * (nb + 1))()
+        r = self.lib.QZSTD_frontFingerprintDeviceBatch(self.f, bufs, nb, C.c_void_p(stream or None), None if null_fp else fp, first)
+        return r, (list(fp)[:n] if r == n else None), list(first)
+
+    def fingerprint(self, ptrs_and_sizes, stream: int | None = None) -> list:
+        """per buffer the fingerprints of its chunks (8 bytes per frame: what the caller keeps with the frames)"""
+        r, fp, first = self.fingerprint_raw(ptrs_and_sizes, stream)
+        if fp is None:
+            raise RuntimeError("QZSTD_frontFingerprintDeviceBatch failed")
+        return [fp[first[i]:first[i + 1]] for i in range(len(ptrs_and_sizes))]
+
+    def check_raw(self, ptrs_and_sizes, expected, stream: int | None = None, n_frames: int | None = None, want_flags: bool = True):
+        """QZSTD_frontCheckDeviceBatch against a flat list of fingerprints (None: a null pointer) -> (return value: the number of differing
+        frames or ERROR, differs as a flat list or None)"""
+        bufs, nb, _ = self.batch(ptrs_and_sizes)
+        n = len(expected) if expected is not None else 0
+        ex = None if expected is None else (C.c_ulonglong * max(n, 1))(*expected)
+        flags = C.create_string_buffer(b"\x07" * max(n, 1), max(n, 1)) if want_flags else None
+        r = self.lib.QZSTD_frontCheckDeviceBatch(self.f, bufs, nb, C.c_void_p(stream or None), ex, n if n_frames is None else n_frames, flags)
+        return r, (list(flags.raw[:n]) if want_flags else None)
+
+    def check(self, ptrs_and_sizes, fingerprints_per_buffer, stream: int | None = None) -> list:
+        """-> [(buffer index, frame index inside the buffer), ...] for the chunks whose fingerprint is another one now; []: the buffers are
+        what was fingerprinted.  Raises when the call fails"""
+        r, flags = self.check_raw(ptrs_and_sizes, [v for fp in fingerprints_per_buffer for v in fp], stream)
+        if r == ERROR:
+            raise RuntimeError("QZSTD_frontCheckDeviceBatch failed")
+        out, c = [], 0
+        for i, fp in enumerate(fingerprints_per_buffer):
+            for j in range(len(fp)):
+                if flags[c]:
+                    out.append((i, j))
+                c += 1
+        assert len(out) == r
+        return out
+
+    def fingerprint_stats(self) -> list:
+        """[0] frames fingerprinted, [1] bytes read on the device, [2] qzstd_hip_fingerprint launches, [3] frames a check found differing"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontFingerprintStats(self.f, st)
+        return list(st)
+
     def restore_stats(self) -> list:
         """[0] frames decoded, [1] bytes of content, [2] bytes copied host->device, [3] ungroup launches"""
         st = (C.c_ulonglong * 4)()
@@ -804,6 +1007,30 @@ def verify_tensors(front: DeviceFront, frames_per_tensor, tensors, bases=None, s
     bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
     bs = None if bases is None else [None if b is None else (b.data_ptr(), b.numel() * b.element_size()) for b in bases]
     return front.verify(frames_per_tensor, bufs, bs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
+
+
+def _tensor_bufs(what: str, tensors, stream):
+    tensors = list(tensors)
+    for t in tensors:
+        if not t.is_cuda or not t.is_contiguous() or t.device != tensors[0].device:
+            raise ValueError("%s: contiguous GPU tensors on one device" % what)
+    if tensors and stream is None:
+        stream = torch.cuda.current_stream(tensors[0].device)
+    return [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors], getattr(stream, "cuda_stream", stream)
+
+
+def fingerprint_tensors(front: DeviceFront, tensors, stream=None) -> list:
+    """per tensor the fingerprints of its chunks, all tensors in ONE QZSTD_frontFingerprintDeviceBatch call: 8 bytes per frame, to be kept
+    with the frames; independent of dtype, base and every setting of the front"""
+    bufs, handle = _tensor_bufs("fingerprint_tensors", tensors, stream)
+    return front.fingerprint(bufs, handle) if bufs else []
+
+
+def check_tensors(front: DeviceFront, tensors, fingerprints_per_tensor, stream=None) -> list:
+    """are the tensors — restored, perhaps weeks later — the tensors that were fingerprinted?  ONE QZSTD_frontCheckDeviceBatch call ->
+    [(tensor, frame), ...] for the chunks that differ; []: the load is good"""
+    bufs, handle = _tensor_bufs("check_tensors", tensors, stream)
+    return front.check(bufs, fingerprints_per_tensor, handle) if bufs else []
 
 
 def restore_slices(front: DeviceFront, frames, buf_sizes, elems, slices, stream=None) -> int:
