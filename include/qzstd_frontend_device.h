@@ -167,6 +167,32 @@ size_t QZSTD_frontRestoreDeviceBatchDelta(QZSTD_Front *f, const void *frames, si
  * XORed (and grouped) on the host; [3] frames restored onto a base */
 void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Element differences for integer columns (include/qzstd_elemdiff.h): QZSTD_ELEM_DIFF OR-ed into an elemSizes[i] entry — 0x81, 0x82, 0x84 or
+ * 0x88; 0x80 alone ("the front's setting, with differences") stays refused, and QZSTD_frontSetByteGroup takes no flag.  Off unless the caller
+ * asks for it, per buffer: row ids, offsets, timestamps, sorted keys and sampled signals shrink, data without order GROWS.  A frame of a flagged
+ * buffer is an ordinary zstd frame whose content is QZSTD_byteGroup(QZSTD_elemDiff(chunk, k), k), the block-per-plane rule unchanged; the
+ * differences are per chunk, so every frame decodes on its own.  NEITHER k NOR THE FACT THAT DIFFERENCES WERE TAKEN IS STORED IN THE FRAME: the
+ * caller keeps both, as it keeps element sizes.  A reader hands the frames to a restore call with the same entries, or decodes a frame itself:
+ * decode, QZSTD_byteUngroup, QZSTD_elemSum.
+ *
+ * QZSTD_frontCompressDeviceBatchTyped, and QZSTD_frontCompressDeviceBatchDelta for a buffer without a base: a flagged buffer's frames are always
+ * staged, never read in place — by one qzstd_hip_group_ediff launch over the flagged frames of a part, beside the launch the part's other
+ * frames get as before.  Checksums cover the transformed content; the plane probe sees the staged blocks as before; a frame whose content is
+ * rebuilt from the arena needs nothing new; a frame with a block the matcher failed has the caller's bytes copied back, QZSTD_elemDiff and
+ * QZSTD_byteGroup applied on the host, and is built by ZSTD_compress2.  Frames of unflagged buffers are byte for byte what they are without
+ * any flag in the call, whatever their neighbours are, and a call without any flag is launch for launch what it was.
+ * QZSTD_frontRestoreDeviceBatchTyped / ...Delta for a buffer without a base: after a part's ungroup launch ONE qzstd_hip_esum launch over the
+ * flagged frames' destinations follows on the same stream and sums them in place.
+ *
+ * (size_t)-1 before anything is queued: a flagged buffer that also has a base, in either direction; a flagged buffer in
+ * QZSTD_frontVerifyDeviceBatch; a flagged buffer that a non-empty slice of QZSTD_frontRestoreDeviceSlices touches (a window needs the sum from
+ * the frame's start); a flagged buffer with a device layer without qzstd_hip_group_ediff (compress) or qzstd_hip_esum (restore).
+ * QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch work on the tensors' own bytes and are THE end-to-end check for flagged buffers. */
+#define QZSTD_ELEM_DIFF 0x80u
+/* since creation: [0] frames whose differences were taken on the GPU (every flagged frame of a staged part), [1] of those, frames whose
+ * content was taken again on the host (a failed block), [2] frames summed by a restore, [3] qzstd_hip_esum launches */
+void QZSTD_frontElemDiffStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 /* Delta skip: chunks EQUAL to their base chunk — a frozen backbone, frozen embeddings, buffers, an evaluation-only interval — found on the GPU
  * and skipped.  Off by default; with the setting off every call is launch for launch and byte for byte what it was.
  *

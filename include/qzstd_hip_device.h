@@ -4,8 +4,9 @@
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
  * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
  * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
- * the content-checksum kernel (QZSTD_frontSetChecksum), the byte histograms' cost per block (QZSTD_frontSetPlaneProbe), and the tile
- * digests of the tensor fingerprints (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch).
+ * the content-checksum kernel (QZSTD_frontSetChecksum), the byte histograms' cost per block (QZSTD_frontSetPlaneProbe), the tile
+ * digests of the tensor fingerprints (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch), and the grouping gather with element
+ * differences and the element sum that undoes them (QZSTD_ELEM_DIFF in an elemSizes entry of the Typed calls).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -360,6 +361,75 @@ typedef struct {
     uint32_t tile0; /* written by the launcher: workgroups of the rows before this one */
 } qzstd_hip_fp_row_t;
 int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows, uint64_t *d_tiles);
+
+/*
+ * Byte-grouping gather with element differences (include/qzstd_elemdiff.h): qzstd_hip_group with a `flags` word in place of `reserved`.
+ * A row without QZSTD_HIP_EDIFF_DIFF lands exactly as qzstd_hip_group lands it; a row with it lands as the grouped layout of
+ * QZSTD_elemDiff(row, len, elem) — z[e] = zigzag(x[e] - x[e-1]), x[-1] = 0, the tail bytes unchanged — and `pad` zero bytes follow.
+ * Elements count from the row's first byte, not from memory alignment: src may have any alignment, also one that is no multiple of elem.
+ *
+ * The tile is qzstd_hip_group's: 16 KiB of ONE row's source across all planes.  The differences are taken in registers between the fetch
+ * and the split into planes: a lane's 16 source bytes hold whole elements, the element in front of them comes from the lane before by a
+ * shuffle, and the first lane of a wave — so also the first of a tile — fetches that one element itself (elem bytes at any alignment, under
+ * the source-read rule: aligned 16-byte loads of words that overlap [src, src + len) only).  The bytes a stage word's owner fetches singly
+ * are computed from the two elements they depend on, fetched the same way.  Everything else — one aligned 16-byte store per stage word, no
+ * atomics, no read-modify-write, stage bytes between rows left alone, `rows` / d_rows, nRows == 0, asynchrony and the refusals before
+ * anything is queued — is qzstd_hip_group's, with "a flags bit other than bit 0" in place of "a reserved that is not 0".  Two launches over
+ * disjoint ascending subsets of a part's rows (this one for the rows with differences, qzstd_hip_group for the rest) do not disturb each other.
+ */
+#define QZSTD_HIP_EDIFF_DIFF 1u /* flags bit 0 */
+typedef struct {
+    uint64_t src;    /* device address of the row's first byte, any alignment */
+    uint64_t dstOff; /* byte offset in d_stage, a multiple of 16 */
+    uint32_t len;    /* bytes, may be 0 */
+    uint32_t pad;    /* zero bytes written behind them; len + pad is a multiple of 16 */
+    uint32_t elem;   /* element size: 1, 2, 4 or 8 */
+    uint32_t flags;  /* QZSTD_HIP_EDIFF_DIFF: differences are taken; other bits 0 */
+} qzstd_hip_group_ediff_row_t;
+int qzstd_hip_group_ediff(int device, void *stream, const qzstd_hip_group_ediff_row_t *rows, uint32_t nRows,
+                          qzstd_hip_group_ediff_row_t *d_rows, void *d_stage, size_t stageBytes);
+
+/*
+ * Element sum, the inverse of the differences, IN PLACE on the destinations: with k = elem, n = len / k and z[e] the little-endian k-byte
+ * integer at dst + e * k, every row becomes x[e] = sum over i <= e of unzigzag(z[i]) mod 2^(8k) — QZSTD_elemSum(dst, dst, len, k).
+ * dst has ANY alignment, also one that is no multiple of elem; a row may be far longer than a frame (len up to 0xFFFFFFE0).
+ *
+ * EXACTLY the bytes [dst, dst + n * k) of every row are written, each once: the 16-byte words that lie wholly inside that range leave as
+ * aligned 16-byte stores, the up to 15 bytes in front of the first such word and behind the last as single bytes — two rows of one launch
+ * may be neighbours in memory and share a 16-byte word.  The len - n * k tail bytes are never written.  Loads are aligned 16-byte loads
+ * of the words that overlap [dst, dst + n * k) and of no other word.
+ *
+ * Work is divided by 16 KiB tiles of a row (QZSTD_HIP_ESUM_TILES; a row shorter than elem has none): the launcher writes tile0 (the running
+ * sum of the rows' tiles) into the caller's rows before the upload; a workgroup finds its row by a binary search over it.  No workgroup
+ * waits for another; three launches, ordered by the stream:
+ *   1  a workgroup per tile stores the tile's 64-bit sum and a copy of the tile's first 16 bytes into d_scratch
+ *   2  ONE workgroup turns the sums into their exclusive prefix sums (over all tiles of the launch; a row's carry into tile t is the
+ *      difference between the prefix at t and the prefix at the row's first tile: addition mod 2^64 is exact for every k)
+ *   3  a workgroup per tile un-zigzags in registers, scans its tile (shuffles inside a wave, one LDS step across the four waves), adds the
+ *      carry, and stores through LDS, where the sums are realigned from element to memory alignment.  A destination word belongs to the
+ *      tile of its first byte in the row; the owner of a word that reaches into the next tile sums that tile's first elements itself, from
+ *      the copy of pass 1 — the next tile's workgroup may have replaced them already — and every tile reads its own first 16 bytes there too.
+ * d_scratch: device memory of QZSTD_HIP_ESUM_SCRATCH_BYTES(total tiles) bytes, 16-aligned, private to the launch until it completes.
+ * No atomics.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_scratch, a d_scratch that is not 16-aligned or smaller than the tiles need, an elem outside
+ * {1, 2, 4, 8}, a reserved that is not 0, a null dst with len >= elem, len > 0xFFFFFFE0, more than 2^31 - 1 tiles.  Destinations that
+ * overlap each other are the caller's error and are not checked.  nRows == 0, or no row with an element: nothing is queued, 0.
+ * Asynchronous on `stream`.
+ */
+#define QZSTD_HIP_ESUM_TILES(len, elem) (((uint64_t)(len) / (elem) + 16384u / (elem) - 1u) / (16384u / (elem)))
+#define QZSTD_HIP_ESUM_SCRATCH_BYTES(tiles) ((size_t)(tiles) * 24u) /* 16 bytes of every tile's head, then 8 of its sum */
+typedef struct {
+    uint64_t dst;      /* device address of the row's first byte, any alignment */
+    uint32_t len;      /* bytes; n = len / elem elements are summed, the rest is left alone */
+    uint32_t elem;     /* element size: 1, 2, 4 or 8 */
+    uint32_t tile0;    /* written by the launcher: tiles of the rows before this one */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_esum_row_t;
+int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *rows, uint32_t nRows, qzstd_hip_esum_row_t *d_rows, void *d_scratch,
+                   size_t scratchBytes);
 
 #if defined(__cplusplus)
 }

@@ -2,7 +2,7 @@
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
  * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
- * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), the XXH64 content checksum, the plane cost (plane probe) and the tile digests of the tensor fingerprints.  They use nothing of the match-finder
+ * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), the XXH64 content checksum, the plane cost (plane probe), the tile digests of the tensor fingerprints, and the grouping gather with element differences and the element sum (integer columns).  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
 #include <hip/hip_runtime.h>
@@ -1573,5 +1573,471 @@ extern "C" int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_
     hipLaunchKernelGGL(qzstd_fingerprint_kernel, dim3((uint32_t)total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows,
                        reinterpret_cast<unsigned long long *>(d_tiles));
     QZ_CHECK(hipGetLastError(), "launch qzstd_fingerprint_kernel");
+    return 0;
+}
+
+/* ---------------------------------------------------------------- element differences and their sum (include/qzstd_hip_device.h, qzstd_elemdiff.h) -- */
+namespace {
+/* the element of K bytes at address a, any alignment: group_fetch's aligned words, the ones that overlap [a, a + K) */
+template <uint32_t K> __device__ inline uint64_t ediff_elem_at(uint64_t a)
+{
+    uint64_t o0, o1;
+    group_fetch(a, K, &o0, &o1);
+    return K == 8u ? o0 : o0 & ((1ull << (8u * (K & 7u))) - 1ull);
+}
+
+/* the 16 source bytes {o1, o0} = 16 / K elements, the element in front of them: each becomes zigzag(x[e] - x[e-1]) in K bytes */
+template <uint32_t K> __device__ inline void ediff_word(uint64_t *o0, uint64_t *o1, uint64_t prev)
+{
+    if constexpr (K == 8u) {
+        const uint64_t d0 = *o0 - prev, d1 = *o1 - *o0;
+        *o0 = (d0 << 1) ^ (0ull - (d0 >> 63));
+        *o1 = (d1 << 1) ^ (0ull - (d1 >> 63));
+    } else {
+        constexpr uint64_t mask = (1ull << (8u * K)) - 1ull;
+        uint64_t in[2] = { *o0, *o1 }, out[2] = { 0ull, 0ull };
+#pragma unroll
+        for (uint32_t h = 0; h < 2u; h++) {
+#pragma unroll
+            for (uint32_t e = 0; e < 8u / K; e++) {
+                const uint64_t x = (in[h] >> (e * 8u * K)) & mask, d = (x - prev) & mask;
+                out[h] |= (((d << 1) ^ (0ull - (d >> (8u * K - 1u)))) & mask) << (e * 8u * K);
+                prev = x;
+            }
+        }
+        *o0 = out[0];
+        *o1 = out[1];
+    }
+}
+
+/* the element that ends the 16 bytes {o1, o0}: what the lane behind needs */
+template <uint32_t K> __device__ inline uint64_t ediff_last(uint64_t o1) { return K == 8u ? o1 : o1 >> (64u - 8u * K); }
+
+/* phase A of a tile with differences: group_fetch, the differences, group_split.  Every lane runs every round (the shuffle is not under a
+ * lane's own condition); a lane without a word in a round fetches nothing.  Lane l of a round holds the word behind lane l - 1's, so the
+ * element in front of its own comes from there; the first lane of a wave fetches it (x[-1] = 0 for the row's first word). */
+template <uint32_t K> __device__ inline void ediff_phase_a(uint64_t srcTile, uint32_t tileBytes, bool rowStart, uint8_t *lds)
+{
+    for (uint32_t w0 = 0; w0 * 16u < tileBytes; w0 += kGroupT) {
+        const uint32_t w = w0 + threadIdx.x;
+        const bool mine = w * 16u < tileBytes;
+        uint64_t o0 = 0, o1 = 0;
+        if (mine) group_fetch(srcTile + w * 16u, tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u, &o0, &o1);
+        uint64_t prev = __shfl_up(ediff_last<K>(o1), 1u, 64);
+        if (mine) {
+            if ((threadIdx.x & 63u) == 0u) prev = (w == 0u && rowStart) ? 0ull : ediff_elem_at<K>(srcTile + w * 16u - K);
+            ediff_word<K>(&o0, &o1, prev);
+            group_split<K>(o0, o1, lds, w);
+        }
+    }
+}
+
+/* group_byte for a row of the differencing gather: byte p of the row's grouped layout, of its differences when `diff` */
+__device__ inline uint64_t ediff_byte(const qzstd_hip_group_ediff_row_t &row, uint32_t n, uint32_t kLog, bool diff, uint64_t p)
+{
+    if (p >= row.len) return 0ull;
+    if (p >= ((uint64_t)n << kLog)) return group_byte_at(row.src + p); /* the tail */
+    const uint32_t j = (uint32_t)p / n, e = (uint32_t)p - j * n;       /* (p < len: 32 bits) */
+    const uint64_t at = row.src + ((uint64_t)e << kLog);
+    if (!diff) return group_byte_at(at + j);
+    uint64_t o0 = 0, o1 = 0;
+    switch (kLog) { /* the element alone in a word: the rest of the word's differences are not looked at */
+    case 0u: o0 = ediff_elem_at<1u>(at); ediff_word<1u>(&o0, &o1, e ? ediff_elem_at<1u>(at - 1u) : 0ull); break;
+    case 1u: o0 = ediff_elem_at<2u>(at); ediff_word<2u>(&o0, &o1, e ? ediff_elem_at<2u>(at - 2u) : 0ull); break;
+    case 2u: o0 = ediff_elem_at<4u>(at); ediff_word<4u>(&o0, &o1, e ? ediff_elem_at<4u>(at - 4u) : 0ull); break;
+    default: o0 = ediff_elem_at<8u>(at); ediff_word<8u>(&o0, &o1, e ? ediff_elem_at<8u>(at - 8u) : 0ull); break;
+    }
+    return (o0 >> (j * 8u)) & 0xFFull;
+}
+
+/* group_patch over ediff_byte */
+__device__ inline void ediff_patch(const qzstd_hip_group_ediff_row_t &row, uint32_t n, uint32_t kLog, bool diff, uint64_t o, uint32_t from,
+                                   uint64_t *o0, uint64_t *o1)
+{
+    *o1 = from > 8u ? *o1 & ((1ull << ((from - 8u) * 8u)) - 1ull) : 0ull;
+    if (from < 8u) *o0 = from ? *o0 & ((1ull << (from * 8u)) - 1ull) : 0ull;
+    if (o + from >= row.len) return; /* padding only */
+    for (uint32_t i = from; i < 16u; i++) {
+        const uint64_t b = ediff_byte(row, n, kLog, diff, o + i);
+        if (i < 8u) *o0 |= b << (i * 8u); else *o1 |= b << ((i - 8u) * 8u);
+    }
+}
+
+/* qzstd_group_kernel's tiles and phases — a kernel of its own, as qzstd_group_xor_kernel is, so that qzstd_group_kernel stays what it was.
+ * A row without the flag goes through that kernel's phase A; a row with it through ediff_phase_a: B sees a tile of zigzagged differences. */
+__global__ __launch_bounds__(kGroupT) void qzstd_group_ediff_kernel(const qzstd_hip_group_ediff_row_t *__restrict__ rows, uint32_t nRows,
+                                                                     uint64_t firstTile, uint4 *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
+    __shared__ uint32_t which;
+    const uint64_t v = firstTile + blockIdx.x;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_group_ediff_row_t row = rows[r];
+    const bool diff = (row.flags & QZSTD_HIP_EDIFF_DIFF) != 0u;
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kGroupTile >> kLog;
+    const uint64_t ext = (uint64_t)row.len + row.pad;
+    const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (ext ? 1ull : 0ull);
+    const uint64_t t = v - ((row.dstOff >> kGroupTileLog) + r);
+    if (t >= tiles) return; /* (the whole workgroup) */
+    const uint32_t e0 = (uint32_t)t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint32_t tileBytes = tileElems << kLog;
+    const uint64_t srcTile = row.src + ((uint64_t)e0 << kLog);
+
+    if (diff) {
+        switch (kLog) {
+        case 0u: ediff_phase_a<1u>(srcTile, tileBytes, e0 == 0u, lds); break;
+        case 1u: ediff_phase_a<2u>(srcTile, tileBytes, e0 == 0u, lds); break;
+        case 2u: ediff_phase_a<4u>(srcTile, tileBytes, e0 == 0u, lds); break;
+        default: ediff_phase_a<8u>(srcTile, tileBytes, e0 == 0u, lds); break;
+        }
+    } else {
+        for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kGroupT) {
+            uint64_t o0, o1;
+            group_fetch(srcTile + w * 16u, tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u, &o0, &o1);
+            switch (kLog) {
+            case 0u: group_split<1u>(o0, o1, lds, w); break;
+            case 1u: group_split<2u>(o0, o1, lds, w); break;
+            case 2u: group_split<4u>(o0, o1, lds, w); break;
+            default: group_split<8u>(o0, o1, lds, w); break;
+            }
+        }
+    }
+    __syncthreads();
+
+    uint4 *out = stage + (row.dstOff >> 4);
+    for (uint32_t j = 0; j < (1u << kLog); j++) {
+        const uint64_t planeAt = (uint64_t)j * n + e0; /* row offset of the tile's first element in plane j */
+        const uint32_t aj = (uint32_t)planeAt & 15u;
+        const uint8_t *plane = lds + j * (tileMax + kGroupSlack);
+        /* c: offset from the stage word that holds planeAt; that word itself belongs here only when it starts at planeAt */
+        for (uint32_t c = (aj ? 16u : 0u) + threadIdx.x * 16u; c < aj + tileElems; c += kGroupT * 16u) {
+            const uint32_t x0 = c - aj, q = x0 & ~15u, sh = x0 & 15u;
+            const uint32_t valid = tileElems - x0 < 16u ? tileElems - x0 : 16u;
+            const uint64_t o = planeAt + x0;
+            const uint4 l = *reinterpret_cast<const uint4 *>(plane + q);
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh) h = *reinterpret_cast<const uint4 *>(plane + q + 16u);
+            uint64_t o0, o1;
+            group_shift(l, h, sh, &o0, &o1);
+            if (valid < 16u) ediff_patch(row, n, kLog, diff, o, valid, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+    if (t + 1u == tiles) {
+        const uint64_t tailAt = ((((uint64_t)n << kLog) + 15u) & ~(uint64_t)15u);
+        for (uint64_t o = tailAt + threadIdx.x * 16u; o < ext; o += kGroupT * 16u) {
+            uint64_t o0 = 0, o1 = 0;
+            ediff_patch(row, n, kLog, diff, o, 0u, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+}
+
+/* ---- the sum.  A tile is 16 KiB of a row's elements: 1024 words of 16 bytes, wave v of the four takes words [256 v, 256 v + 256) in
+ * four rounds of 64 (round q, lane l: word 256 v + 64 q + l — a wave's load is 1 KiB in a row).  A word holds whole elements: the tile
+ * starts at an element, 16 is a multiple of every k. */
+constexpr uint32_t kEsumT = 256u;
+constexpr uint32_t kEsumTileLog = kGroupTileLog;
+constexpr uint32_t kEsumTile = 1u << kEsumTileLog;
+constexpr uint32_t kEsumRounds = kEsumTile / 16u / kEsumT;
+constexpr uint32_t kEsumScanPer = 8u; /* sums per thread and step of the scan kernel */
+static_assert(kEsumRounds == 4u, "four words per lane");
+
+/* the words {o1, o0} = 16 / K zigzagged differences -> their running sums from `sum` on, each in K bytes; returns the sum behind the last
+ * (in 64 bits: 2^(8K) divides 2^64, so the low K bytes of every partial sum are exact whatever the order) */
+template <uint32_t K> __device__ inline uint64_t esum_word(uint64_t *o0, uint64_t *o1, uint64_t sum)
+{
+    if constexpr (K == 8u) {
+        sum += (*o0 >> 1) ^ (0ull - (*o0 & 1ull));
+        *o0 = sum;
+        sum += (*o1 >> 1) ^ (0ull - (*o1 & 1ull));
+        *o1 = sum;
+    } else {
+        constexpr uint64_t mask = (1ull << (8u * K)) - 1ull;
+        uint64_t in[2] = { *o0, *o1 }, out[2] = { 0ull, 0ull };
+#pragma unroll
+        for (uint32_t h = 0; h < 2u; h++) {
+#pragma unroll
+            for (uint32_t e = 0; e < 8u / K; e++) {
+                const uint64_t z = (in[h] >> (e * 8u * K)) & mask;
+                sum += ((z >> 1) ^ (0ull - (z & 1ull))) & mask;
+                out[h] |= (sum & mask) << (e * 8u * K);
+            }
+        }
+        *o0 = out[0];
+        *o1 = out[1];
+    }
+    return sum;
+}
+
+__device__ inline uint64_t esum_word_k(uint32_t kLog, uint64_t *o0, uint64_t *o1, uint64_t sum)
+{
+    switch (kLog) {
+    case 0u: return esum_word<1u>(o0, o1, sum);
+    case 1u: return esum_word<2u>(o0, o1, sum);
+    case 2u: return esum_word<4u>(o0, o1, sum);
+    default: return esum_word<8u>(o0, o1, sum);
+    }
+}
+
+/* what both tile kernels start with: the workgroup's row and tile, and the lane's four words of zigzagged differences (0 where the tile
+ * has none: unzigzag(0) = 0).  With `heads` the tile's word 0 comes from the copy of pass 1, not from memory. */
+struct esum_tile_t {
+    qzstd_hip_esum_row_t row;
+    uint32_t kLog, tileBytes;
+    uint64_t at, rowBytes; /* the tile's first byte in its row; n * k */
+    uint64_t z0[kEsumRounds], z1[kEsumRounds];
+};
+
+__device__ inline bool esum_tile_load(const qzstd_hip_esum_row_t *__restrict__ rows, uint32_t nRows, const uint4 *__restrict__ heads, uint32_t *which,
+                                      esum_tile_t *t)
+{
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        *which = lo;
+    }
+    __syncthreads();
+    t->row = rows[*which];
+    t->kLog = t->row.elem == 8u ? 3u : (t->row.elem == 4u ? 2u : (t->row.elem == 2u ? 1u : 0u));
+    t->rowBytes = (uint64_t)(t->row.len >> t->kLog) << t->kLog;
+    t->at = (uint64_t)(blockIdx.x - t->row.tile0) << kEsumTileLog;
+    if (t->at >= t->rowBytes) return false; /* (the whole workgroup; never: rows without a tile share the tile0 of the row behind them) */
+    t->tileBytes = t->rowBytes - t->at < kEsumTile ? (uint32_t)(t->rowBytes - t->at) : kEsumTile;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+#pragma unroll
+    for (uint32_t q = 0; q < kEsumRounds; q++) {
+        const uint32_t w = wave * (kEsumT * kEsumRounds / 4u) + q * 64u + lane;
+        t->z0[q] = t->z1[q] = 0ull;
+        if (w * 16u < t->tileBytes) {
+            const uint32_t valid = t->tileBytes - w * 16u < 16u ? t->tileBytes - w * 16u : 16u;
+            if (heads && w == 0u) {
+                const uint4 h = heads[blockIdx.x];
+                t->z0[q] = h.x | (uint64_t)h.y << 32;
+                t->z1[q] = h.z | (uint64_t)h.w << 32;
+            } else {
+                group_fetch(t->row.dst + t->at + w * 16u, valid, &t->z0[q], &t->z1[q]);
+            }
+            cmp_mask(valid, &t->z0[q], &t->z1[q]); /* what lies behind the row's last element reads as 0 */
+        }
+    }
+    return true;
+}
+
+/* pass 1: the tile's sum, and its first 16 bytes as they are before anything is summed */
+__global__ __launch_bounds__(kEsumT) void qzstd_esum_tile_kernel(const qzstd_hip_esum_row_t *__restrict__ rows, uint32_t nRows, uint4 *__restrict__ heads,
+                                                                 unsigned long long *__restrict__ sums)
+{
+    __shared__ uint32_t which;
+    __shared__ uint64_t red[kEsumT / 64u];
+    esum_tile_t t;
+    if (!esum_tile_load(rows, nRows, nullptr, &which, &t)) return;
+    if (threadIdx.x == 0) heads[blockIdx.x] = make_uint4((uint32_t)t.z0[0], (uint32_t)(t.z0[0] >> 32), (uint32_t)t.z1[0], (uint32_t)(t.z1[0] >> 32));
+    uint64_t sum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < kEsumRounds; q++) {
+        uint64_t a = t.z0[q], b = t.z1[q];
+        sum = esum_word_k(t.kLog, &a, &b, sum);
+    }
+#pragma unroll
+    for (uint32_t s = 32u; s; s >>= 1) sum += __shfl_xor(sum, (int)s, 64);
+    if ((threadIdx.x & 63u) == 0u) red[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+}
+
+/* pass 2: sums[i] <- sums[0] + .. + sums[i-1], in place, by ONE workgroup: kEsumT * kEsumScanPer of them a step */
+__global__ __launch_bounds__(kEsumT) void qzstd_esum_scan_kernel(unsigned long long *__restrict__ sums, uint32_t total)
+{
+    __shared__ uint64_t red[kEsumT / 64u];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint64_t carry = 0;
+    for (uint32_t c = 0; c < total; c += kEsumT * kEsumScanPer) {
+        const uint32_t i0 = c + threadIdx.x * kEsumScanPer;
+        uint64_t v[kEsumScanPer], mine = 0;
+#pragma unroll
+        for (uint32_t i = 0; i < kEsumScanPer; i++) {
+            v[i] = i0 + i < total ? sums[i0 + i] : 0ull;
+            mine += v[i];
+        }
+        uint64_t incl = mine;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63u) red[wave] = incl;
+        __syncthreads();
+        uint64_t before = carry, all = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < kEsumT / 64u; w++) {
+            if (w < wave) before += red[w];
+            all += red[w];
+        }
+        __syncthreads(); /* red is rewritten by the next step */
+        uint64_t run = before + incl - mine;
+#pragma unroll
+        for (uint32_t i = 0; i < kEsumScanPer; i++) {
+            if (i0 + i < total) sums[i0 + i] = run;
+            run += v[i];
+        }
+        carry += all;
+    }
+}
+
+/* pass 3: see include/qzstd_hip_device.h.  `sums` holds the exclusive prefix sums of pass 2. */
+__global__ __launch_bounds__(kEsumT) void qzstd_esum_apply_kernel(const qzstd_hip_esum_row_t *__restrict__ rows, uint32_t nRows, const uint4 *__restrict__ heads,
+                                                                  const unsigned long long *__restrict__ sums)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kEsumTile + 32u];
+    __shared__ uint32_t which;
+    __shared__ uint64_t red[kEsumT / 64u];
+    esum_tile_t t;
+    if (!esum_tile_load(rows, nRows, heads, &which, &t)) return;
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    /* the lane's words' sums, a wave scan of them per round, the rounds chained through lane 63 */
+    uint64_t excl[kEsumRounds], waveSum = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < kEsumRounds; q++) {
+        uint64_t a = t.z0[q], b = t.z1[q];
+        const uint64_t mine = esum_word_k(t.kLog, &a, &b, 0ull);
+        uint64_t incl = mine;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint64_t o = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        excl[q] = waveSum + incl - mine;
+        waveSum += __shfl(incl, 63, 64);
+    }
+    if (lane == 0u) red[wave] = waveSum;
+    __syncthreads();
+    uint64_t carry = sums[blockIdx.x] - sums[t.row.tile0], tileSum = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < kEsumT / 64u; w++) {
+        if (w < wave) carry += red[w];
+        tileSum += red[w];
+    }
+#pragma unroll
+    for (uint32_t q = 0; q < kEsumRounds; q++) {
+        const uint32_t w = wave * (kEsumT * kEsumRounds / 4u) + q * 64u + lane;
+        if (w * 16u < t.tileBytes) {
+            (void)esum_word_k(t.kLog, &t.z0[q], &t.z1[q], carry + excl[q]);
+            *reinterpret_cast<uint4 *>(lds + w * 16u) = make_uint4((uint32_t)t.z0[q], (uint32_t)(t.z0[q] >> 32), (uint32_t)t.z1[q], (uint32_t)(t.z1[q] >> 32));
+        }
+    }
+    /* the elements of the next tile that complete this tile's last destination word: up to 16 bytes, whole elements, from pass 1's copy */
+    if (threadIdx.x == 0 && t.at + t.tileBytes < t.rowBytes) { /* (the tile is a whole one: tileBytes = 16 KiB) */
+        const uint64_t left = t.rowBytes - t.at - t.tileBytes;
+        const uint4 h = heads[blockIdx.x + 1u];
+        uint64_t a = h.x | (uint64_t)h.y << 32, b = h.z | (uint64_t)h.w << 32;
+        cmp_mask(left < 16u ? (uint32_t)left : 16u, &a, &b);
+        (void)esum_word_k(t.kLog, &a, &b, sums[blockIdx.x] - sums[t.row.tile0] + tileSum);
+        *reinterpret_cast<uint4 *>(lds + kEsumTile) = make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
+    }
+    __syncthreads();
+    /* the destination's 16-byte slots whose first byte inside the row lies in this tile */
+    const uint64_t rowEnd = t.row.dst + t.rowBytes, tileAt = t.row.dst + t.at, tileEnd = tileAt + t.tileBytes;
+    const uint64_t first = t.at ? (tileAt + 15u) & ~(uint64_t)15u : tileAt & ~(uint64_t)15u;
+    for (uint64_t s = first + threadIdx.x * 16u; s < tileEnd; s += kEsumT * 16u) {
+        const uint64_t lo = s < t.row.dst ? t.row.dst : s, hi = s + 16u > rowEnd ? rowEnd : s + 16u;
+        if (lo == s && hi == s + 16u) {
+            const uint32_t off = (uint32_t)(s - tileAt), q = off & ~15u, sh = off & 15u;
+            const uint4 l = *reinterpret_cast<const uint4 *>(lds + q);
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh) h = *reinterpret_cast<const uint4 *>(lds + q + 16u);
+            uint64_t o0, o1;
+            group_shift(l, h, sh, &o0, &o1);
+            *reinterpret_cast<uint4 *>(s) = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        } else {
+            for (uint64_t b = lo; b < hi; b++) *reinterpret_cast<uint8_t *>(b) = lds[b - tileAt];
+        }
+    }
+}
+} // namespace
+
+/* (qzstd_hip_group's checks and launch geometry, row for row) */
+extern "C" int qzstd_hip_group_ediff(int device, void *stream, const qzstd_hip_group_ediff_row_t *rows, uint32_t nRows,
+                                     qzstd_hip_group_ediff_row_t *d_rows, void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_ediff: null pointer or stage not 16-byte aligned");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_group_ediff_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || (r.flags & ~QZSTD_HIP_EDIFF_DIFF))
+            return fail_msg("qzstd_hip_group_ediff: elem not 1, 2, 4 or 8, or unknown flags");
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_ediff: dstOff or len + pad not a multiple of 16");
+        if (r.len && !r.src) return fail_msg("qzstd_hip_group_ediff: null source");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_group_ediff: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_ediff: a row ends past stageBytes");
+        end = r.dstOff + ext;
+        if (ext) {
+            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
+            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_ediff: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_ediff: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group ediff rows)");
+    hipLaunchKernelGGL(qzstd_group_ediff_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows,
+                       firstTile, static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_group_ediff_kernel");
+    return 0;
+}
+
+extern "C" int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *rows, uint32_t nRows, qzstd_hip_esum_row_t *d_rows, void *d_scratch,
+                              size_t scratchBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_scratch || ((uintptr_t)d_scratch & 15u)) return fail_msg("qzstd_hip_esum: null pointer or scratch not 16-byte aligned");
+    uint64_t total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_esum_row_t &r = rows[i];
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
+            return fail_msg("qzstd_hip_esum: elem not 1, 2, 4 or 8, or reserved not 0");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_esum: row too long");
+        if (r.len >= r.elem && !r.dst) return fail_msg("qzstd_hip_esum: null row");
+        total += QZSTD_HIP_ESUM_TILES(r.len, r.elem);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_esum: too many tiles");
+    if (QZSTD_HIP_ESUM_SCRATCH_BYTES(total) > scratchBytes) return fail_msg("qzstd_hip_esum: scratch too small");
+    if (total == 0) return 0; /* no row with an element */
+    const uint32_t tiles = (uint32_t)total;
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_ESUM_TILES(rows[i].len, rows[i].elem);
+    }
+    QZ_SET_DEVICE(device);
+    const hipStream_t s = (hipStream_t)stream;
+    auto *heads = static_cast<uint4 *>(d_scratch);
+    auto *sums = reinterpret_cast<unsigned long long *>(heads + tiles);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D (esum rows)");
+    hipLaunchKernelGGL(qzstd_esum_tile_kernel, dim3(tiles), dim3(kEsumT), 0, s, d_rows, nRows, heads, sums);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_esum_tile_kernel");
+    hipLaunchKernelGGL(qzstd_esum_scan_kernel, dim3(1), dim3(kEsumT), 0, s, sums, tiles);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_esum_scan_kernel");
+    hipLaunchKernelGGL(qzstd_esum_apply_kernel, dim3(tiles), dim3(kEsumT), 0, s, d_rows, nRows, heads, sums);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_esum_apply_kernel");
     return 0;
 }

@@ -16,6 +16,7 @@
 #include "qzstd_hip_device.h"
 #include "qzstd_planecost.h"
 #include "qzstd_fingerprint.h"
+#include "qzstd_elemdiff.h"
 
 #include <dlfcn.h>
 #include <pthread.h>
@@ -93,6 +94,7 @@ struct QZSTD_Front_s {
     unsigned long long groupStats[3];
     /* delta frames (the ...Delta calls): frames with a base by how they were built, and frames restored onto a base */
     unsigned long long deltaStats[4];
+    unsigned long long ediffStats[4]; /* QZSTD_frontElemDiffStats */
     /* delta skip (QZSTD_frontSetDeltaSkip): the setting, and frames compared / found equal, bytes compared, zero frames a restore recognised */
     int deltaSkip;
     unsigned long long skipStats[4];
@@ -455,6 +457,8 @@ extern int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row
                             void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
                            void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_group_ediff(int device, void *stream, const qzstd_hip_group_ediff_row_t *rows, uint32_t nRows,
+                                 qzstd_hip_group_ediff_row_t *d_rows, void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows, qzstd_hip_group_xor_row_t *d_rows,
                                void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
@@ -501,6 +505,8 @@ struct QF_DevSlot_s {
     void *dGroupRows; size_t dGroupRowsCap;
     qzstd_hip_group_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with delta frames: qzstd_hip_group_xor's rows instead */
     void *dXorRows; size_t dXorRowsCap;
+    qzstd_hip_group_ediff_row_t *hEdiffRows; size_t hEdiffRowsCap; /* a part with differenced frames: qzstd_hip_group_ediff's rows, for those frames only */
+    void *dEdiffRows; size_t dEdiffRowsCap;
     size_t *ends; size_t endsCap; /* the block ends of the frame whose descriptors are being written */
     qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
     void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
@@ -529,6 +535,7 @@ typedef struct {
     uint32_t buf;    /* owning buffer */
     uint32_t nb;     /* blocks: QZSTD_byteGroupBlocks(len, k) — ceil(len / 128 KiB) for k = 1 */
     uint32_t k;      /* element size of the byte-grouped layout; 1: the bytes as they are */
+    uint32_t diff;   /* QZSTD_ELEM_DIFF: the content is the grouped layout of QZSTD_elemDiff(chunk, k) */
 } QF_DevFrame;
 
 /* a part: frames [f0, f1) of the job, matched in one launch */
@@ -537,6 +544,7 @@ typedef struct {
     int run; /* the frames are consecutive chunks of ONE buffer: readable in place when aligned, stageable by 2D copies */
     int grouped; /* a frame with k > 1 among them: staged by qzstd_hip_group, never read in place */
     int delta;   /* a frame of a buffer with a base among them: staged by qzstd_hip_group_xor (all its rows), never read in place */
+    int diff;    /* a differenced frame among them: those are staged by qzstd_hip_group_ediff, the others by the part's own launch; never read in place */
 } QF_DevRange;
 
 struct QF_DevPart_s {
@@ -555,13 +563,14 @@ struct QF_DevPart_s {
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
     void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
-                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost };
+                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
     if (s->hRows) qzstd_hip_host_free(s->hRows);
     if (s->hGroupRows) qzstd_hip_host_free(s->hGroupRows);
     if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
+    if (s->hEdiffRows) qzstd_hip_host_free(s->hEdiffRows);
     free(s->ends);
     if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
     if (s->hHash) qzstd_hip_host_free(s->hHash);
@@ -628,16 +637,41 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     void *stage = s->dStage;
     if (qfGrowD(j->dev, &stage, &s->stageCap, stageBytes)) return -1;
     s->dStage = (unsigned char *)stage;
+    if (pr->diff) {
+        /* the differenced frames' rows, in the frames' order, at the frames' own places in the stage; the launch below takes the others */
+        void *h = s->hEdiffRows;
+        size_t c, so = 0, m = 0;
+        if (!qzstd_hip_group_ediff || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hEdiffRowsCap, nf * sizeof(qzstd_hip_group_ediff_row_t))) return -1;
+        s->hEdiffRows = (qzstd_hip_group_ediff_row_t *)h;
+        if (qfGrowD(j->dev, &s->dEdiffRows, &s->dEdiffRowsCap, nf * sizeof(qzstd_hip_group_ediff_row_t))) return -1;
+        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
+            qzstd_hip_group_ediff_row_t *r = &s->hEdiffRows[m];
+            if (!f0[c].diff) continue;
+            if (f0[c].len > 0xFFFFFFE0u) return -1;
+            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->dstOff = so;
+            r->len = (uint32_t)f0[c].len;
+            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
+            r->elem = f0[c].k;
+            r->flags = QZSTD_HIP_EDIFF_DIFF;
+            m++;
+        }
+        if (qzstd_hip_group_ediff(j->dev, s->stream, s->hEdiffRows, (uint32_t)m, (qzstd_hip_group_ediff_row_t *)s->dEdiffRows, s->dStage, stageBytes))
+            return -1;
+        __atomic_fetch_add(&j->f->ediffStats[0], (unsigned long long)m, __ATOMIC_RELAXED);
+        if (m == nf) return 0;
+    }
     if (pr->delta) {
         /* the grouping gather's rows with each frame's base chunk (0: the frame's buffer has none): src ^ base arrives, grouped */
         void *h = s->hXorRows;
-        size_t c, so = 0;
+        size_t c, so = 0, m = 0;
         if (!qzstd_hip_group_xor || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
         s->hXorRows = (qzstd_hip_group_xor_row_t *)h;
         if (qfGrowD(j->dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
-        for (c = 0; c < nf; c++) {
-            qzstd_hip_group_xor_row_t *r = &s->hXorRows[c];
+        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
+            qzstd_hip_group_xor_row_t *r = &s->hXorRows[m];
             const unsigned char *base = (const unsigned char *)j->bases[f0[c].buf].d_ptr;
+            if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1;
             r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
             r->base = base ? (uint64_t)(uintptr_t)(base + f0[c].off) : 0u;
@@ -646,19 +680,20 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
             r->elem = f0[c].k;
             r->reserved = 0;
-            so += qfPad16(f0[c].len);
+            m++;
         }
-        return qzstd_hip_group_xor(j->dev, s->stream, s->hXorRows, (uint32_t)nf, (qzstd_hip_group_xor_row_t *)s->dXorRows, s->dStage, stageBytes);
+        return qzstd_hip_group_xor(j->dev, s->stream, s->hXorRows, (uint32_t)m, (qzstd_hip_group_xor_row_t *)s->dXorRows, s->dStage, stageBytes);
     }
     if (pr->grouped) {
         /* the gather's rows with each frame's element size: the frames arrive in the byte-grouped layout */
         void *h = s->hGroupRows;
-        size_t c, so = 0;
+        size_t c, so = 0, m = 0;
         if (!qzstd_hip_group || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
         s->hGroupRows = (qzstd_hip_group_row_t *)h;
         if (qfGrowD(j->dev, &s->dGroupRows, &s->dGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
-        for (c = 0; c < nf; c++) {
-            qzstd_hip_group_row_t *r = &s->hGroupRows[c];
+        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
+            qzstd_hip_group_row_t *r = &s->hGroupRows[m];
+            if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1;
             r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
             r->dstOff = so;
@@ -666,28 +701,29 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
             r->elem = f0[c].k;
             r->reserved = 0;
-            so += qfPad16(f0[c].len);
+            m++;
         }
-        return qzstd_hip_group(j->dev, s->stream, s->hGroupRows, (uint32_t)nf, (qzstd_hip_group_row_t *)s->dGroupRows, s->dStage, stageBytes);
+        return qzstd_hip_group(j->dev, s->stream, s->hGroupRows, (uint32_t)m, (qzstd_hip_group_row_t *)s->dGroupRows, s->dStage, stageBytes);
     }
     if (qzstd_hip_gather) {
         void *h = s->hRows;
-        size_t c, so = 0;
+        size_t c, so = 0, m = 0;
         if (nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
         s->hRows = (qzstd_hip_gather_row_t *)h;
         if (qfGrowD(j->dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
-        for (c = 0; c < nf; c++) {
-            qzstd_hip_gather_row_t *r = &s->hRows[c];
+        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
+            qzstd_hip_gather_row_t *r = &s->hRows[m];
+            if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1; /* (a row's length and padding are 32-bit) */
             r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
             r->dstOff = so;
             r->len = (uint32_t)f0[c].len;
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-            so += qfPad16(f0[c].len);
+            m++;
         }
-        return qzstd_hip_gather(j->dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_gather_row_t *)s->dRows, s->dStage, stageBytes);
+        return qzstd_hip_gather(j->dev, s->stream, s->hRows, (uint32_t)m, (qzstd_hip_gather_row_t *)s->dRows, s->dStage, stageBytes);
     }
-    if (!pr->run) return -1;
+    if (!pr->run || pr->diff) return -1;
     {
         const size_t chunk = j->f->p.chunkSize, pitch = qfPad16(chunk), full = pr->bytes / chunk, tail = pr->bytes - full * chunk;
         const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
@@ -707,7 +743,7 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
     const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
     /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
-    const int inPlace = !pr->grouped && !pr->delta && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
+    const int inPlace = !pr->grouped && !pr->delta && !pr->diff && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
     size_t c, b = 0, so = 0, seqCapTotal = 0;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
@@ -1169,13 +1205,13 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     /* A byte-grouped frame's content is not what the caller's buffer holds, and in grouped mode this is the common path (a mantissa plane is
      * noise: a raw block).  The arena has everything: the frame's own entries and literals, executed, ARE the grouped content — no second
      * device->host copy, and no look at the stage, which may hold the part after next by now */
-    if ((grouped || dBase) && haveSeqs &&
+    if ((grouped || dBase || fm->diff) && haveSeqs &&
         qzbgRebuild(w->raw, n, ns ? &w->seqs[0].offset : NULL, ns, s->hLit + s->blkLit[b0], nl, w->ends, fm->nb) == 0) {
         if (grouped) __atomic_fetch_add(&f->groupStats[1], 1ull, __ATOMIC_RELAXED);
         if (dBase) __atomic_fetch_add(&f->deltaStats[1], 1ull, __ATOMIC_RELAXED);
     } else {
         unsigned char *to = w->raw;
-        if (grouped || dBase) {
+        if (grouped || dBase || fm->diff) {
             /* a failed block (or entries that do not rebuild): the caller's bytes come back and are grouped here; no sequences are used */
             if (!w->back && !(w->back = (unsigned char *)qzstd_hip_host_alloc(f->p.chunkSize))) return -1;
             to = w->back;
@@ -1199,7 +1235,12 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             QZSTD_byteXor(w->back, w->back, w->raw, n);
             __atomic_fetch_add(&f->deltaStats[2], 1ull, __ATOMIC_RELAXED);
         }
-        if (grouped || dBase) {
+        if (fm->diff) {
+            /* (a differenced frame's buffer has no base) the differences are taken here, in place, before the grouping */
+            if (QZSTD_elemDiff(w->back, w->back, n, fm->k) != n) return -1;
+            __atomic_fetch_add(&f->ediffStats[1], 1ull, __ATOMIC_RELAXED);
+        }
+        if (grouped || dBase || fm->diff) {
             if (QZSTD_byteGroup(w->raw, w->back, n, fm->k) != n) return -1;
             if (grouped) __atomic_fetch_add(&f->groupStats[2], 1ull, __ATOMIC_RELAXED);
         }
@@ -1248,7 +1289,7 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
     size_t i, c = 0, m = 0, nParts = 0;
     if (!fr || !pt) { free(fr); free(pt); return -1; }
     for (i = 0; i < nBufs; i++) {
-        const unsigned k = elemSizes && elemSizes[i] ? elemSizes[i] : group;
+        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : group, k = e & ~QZSTD_ELEM_DIFF;
         size_t off;
         for (off = 0; off < bufs[i].size; off += chunk, c++) {
             const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
@@ -1259,7 +1300,7 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
                 cur->f0 = m;
                 cur->nb = cur->bytes = 0;
                 cur->run = 1;
-                cur->grouped = cur->delta = 0;
+                cur->grouped = cur->delta = cur->diff = 0;
             } else if (fr[m - 1].buf != (uint32_t)i || fr[m - 1].off + chunk != off) {
                 cur->run = 0;
             }
@@ -1270,6 +1311,8 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
             fr[m].buf = (uint32_t)i;
             fr[m].nb = (uint32_t)nb;
             fr[m].k = k;
+            fr[m].diff = e & QZSTD_ELEM_DIFF;
+            if (fr[m].diff) cur->diff = 1;
             if (k > 1u) cur->grouped = 1;
             if (bases && bases[i].d_ptr) cur->delta = 1;
             cur->f1 = ++m;
@@ -1450,7 +1493,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     size_t nFrames, nParts = 0, k, i, total = 0;
     unsigned group;
     unsigned char *equal = NULL;
-    int rc = 0, anyGrouped = 0, anyBase = 0, skip, probe;
+    int rc = 0, anyGrouped = 0, anyBase = 0, anyDiff = 0, skip, probe;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
@@ -1465,7 +1508,13 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     /* each buffer's element size: its own entry, or (0, or no array) the front's setting */
     group = f->group;
     for (i = 0; i < nBufs; i++) {
-        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : group;
+        unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : group;
+        if (e & QZSTD_ELEM_DIFF) {
+            /* differences: with the buffer's own element size only (0x80 alone is refused), and not against a base */
+            if (bases && bases[i].d_ptr) return (size_t)-1;
+            anyDiff = 1;
+            e &= ~QZSTD_ELEM_DIFF;
+        }
         if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
         if (e > 1u) anyGrouped = 1;
     }
@@ -1478,6 +1527,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
     if (anyGrouped && !qzstd_hip_group) return (size_t)-1;  /* byte grouping wanted and a device layer that cannot group */
     if (bases && !qzstd_hip_group_xor) return (size_t)-1;   /* a base given and a device layer that cannot XOR one in */
+    if (anyDiff && !qzstd_hip_group_ediff) return (size_t)-1; /* differences wanted and a device layer that cannot take them */
     skip = bases && f->deltaSkip;
     if (skip && !qzstd_hip_diff) return (size_t)-1;         /* delta skip wanted and a device layer that cannot compare */
     probe = f->planeProbe && (anyGrouped || bases);
@@ -1675,6 +1725,13 @@ void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4])
     for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->deltaStats[k], __ATOMIC_RELAXED) : 0ull;
 }
 
+void QZSTD_frontElemDiffStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->ediffStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
 int QZSTD_frontSetDeltaSkip(QZSTD_Front *f, int on)
 {
     int busy;
@@ -1730,3 +1787,6 @@ int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { ret
 
 /* The fingerprint calls: one launch over the caller's own buffers, on the restore's first slot; included the same way. */
 #include "qzstd_fingerprint.c"
+
+/* Element differences and their sum (include/qzstd_elemdiff.h): free of HIP and libzstd like the byte-grouped layout; included the same way. */
+#include "qzstd_elemdiff.c"

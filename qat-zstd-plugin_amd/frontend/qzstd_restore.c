@@ -27,6 +27,8 @@ extern int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_r
                              const void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
                                  const void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *rows, uint32_t nRows, qzstd_hip_esum_row_t *d_rows, void *d_scratch,
+                          size_t scratchBytes) __attribute__((weak));
 extern int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_win_row_t *d_rows,
                                     const void *d_stage, size_t stageBytes) __attribute__((weak));
 
@@ -39,9 +41,10 @@ typedef struct {
     size_t len;               /* the chunk's length: what the frame must decode to */
     size_t at;                /* offset in its part's stage, a multiple of 16 */
     uint32_t k;               /* element size of the byte-grouped layout the content is in; 1: the bytes as they are */
+    uint32_t diff;            /* QZSTD_ELEM_DIFF: the content is differences, summed on the device after the scatter */
 } QF_RestoreFrame;
 
-typedef struct { size_t f0, f1, bytes, stage, based; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames), frames with a base */
+typedef struct { size_t f0, f1, bytes, stage, based, diffs; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames), frames with a base, differenced frames */
 typedef struct { unsigned char *d_dst; const unsigned char *d_src; size_t len; } QF_ZeroRun; /* consecutive recognised zero frames of one buffer: base -> destination */
 
 struct QF_RestoreSlot_s {
@@ -52,6 +55,8 @@ struct QF_RestoreSlot_s {
     void *dRows; size_t dRowsCap;
     qzstd_hip_ungroup_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with a base among its frames: qzstd_hip_ungroup_xor's rows instead */
     void *dXorRows; size_t dXorRowsCap;
+    qzstd_hip_esum_row_t *hSumRows; size_t hSumRowsCap; /* a part with differenced frames: qzstd_hip_esum's rows, for those frames only, */
+    void *dSumRows, *dSumScratch; size_t dSumRowsCap, dSumScratchCap; /* their device copy and the launch's scratch */
     qzstd_hip_ungroup_win_row_t *hWinRows; size_t hWinRowsCap; /* QZSTD_frontRestoreDeviceSlices: a row per piece (slice x frame) */
     void *dWinRows; size_t dWinRowsCap;
     qzstd_hip_ungroup_cmp_row_t *hCmpRows; size_t hCmpRowsCap; /* QZSTD_frontVerifyDeviceBatch (qzstd_verify.c): a row per frame, */
@@ -83,6 +88,9 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->dRows) qzstd_hip_free(f->restoreSlotDev, s->dRows);
         if (s->dXorRows) qzstd_hip_free(f->restoreSlotDev, s->dXorRows);
         if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
+        if (s->dSumRows) qzstd_hip_free(f->restoreSlotDev, s->dSumRows);
+        if (s->dSumScratch) qzstd_hip_free(f->restoreSlotDev, s->dSumScratch);
+        if (s->hSumRows) qzstd_hip_host_free(s->hSumRows);
         if (s->dWinRows) qzstd_hip_free(f->restoreSlotDev, s->dWinRows);
         if (s->hWinRows) qzstd_hip_host_free(s->hWinRows);
         if (s->dCmpRows) qzstd_hip_free(f->restoreSlotDev, s->dCmpRows);
@@ -132,12 +140,18 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
     struct QF_RestorePart_s part;
     void *ev = NULL;
     size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nRuns = 0, nZero = 0;
-    int dev = -1, rc = 0, anyBase = 0, skip;
+    int dev = -1, rc = 0, anyBase = 0, anyDiff = 0, skip;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
-        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
+        unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
         if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
+        if (e & QZSTD_ELEM_DIFF) {
+            /* differences: with the buffer's own element size only (0x80 alone is refused), and not against a base */
+            if (bases && (bases[i].d_ptr || bases[i].size)) return (size_t)-1;
+            anyDiff = 1;
+            e &= ~QZSTD_ELEM_DIFF;
+        }
         if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
         want += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
     }
@@ -153,6 +167,7 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the ungrouping scatter, or without the device-input entry points at all */
     if (bases && !qzstd_hip_ungroup_xor) return (size_t)-1; /* a base given and a device layer that cannot XOR one in */
+    if (anyDiff && !qzstd_hip_esum) return (size_t)-1;      /* differences to sum and a device layer that cannot */
     for (i = 0; i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
         int d;
@@ -212,7 +227,7 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             if (!cur || cur->bytes + len > partBytes) {
                 cur = &parts[nParts++];
                 cur->f0 = m;
-                cur->bytes = cur->stage = cur->based = 0;
+                cur->bytes = cur->stage = cur->based = cur->diffs = 0;
             }
             table[m].src = src;
             table[m].srcSize = frameSizes[c];
@@ -221,7 +236,9 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             if (table[m].d_base) cur->based++;
             table[m].len = len;
             table[m].at = cur->stage;
-            table[m].k = e;
+            table[m].k = e & ~QZSTD_ELEM_DIFF;
+            table[m].diff = e & QZSTD_ELEM_DIFF;
+            if (table[m].diff) cur->diffs++;
             cur->f1 = ++m;
             cur->bytes += len;
             cur->stage += qfPad16(len);
@@ -271,6 +288,27 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             s->hXorRows = (qzstd_hip_ungroup_xor_row_t *)h;
             if (rc == 0 && qfGrowD(dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) rc = -1;
         }
+        if (rc == 0 && pr->diffs) {
+            /* the differenced frames' destinations, summed in place by one launch behind the scatter */
+            size_t tiles = 0, r = 0;
+            h = s->hSumRows;
+            if (qfGrowH(&h, &s->hSumRowsCap, pr->diffs * sizeof(qzstd_hip_esum_row_t))) rc = -1;
+            s->hSumRows = (qzstd_hip_esum_row_t *)h;
+            for (c = 0; c < nf && rc == 0; c++) {
+                const QF_RestoreFrame *fr = &table[pr->f0 + c];
+                if (!fr->diff) continue;
+                s->hSumRows[r].dst = (uint64_t)(uintptr_t)fr->d_dst;
+                s->hSumRows[r].len = (uint32_t)fr->len;
+                s->hSumRows[r].elem = fr->k;
+                s->hSumRows[r].tile0 = 0;
+                s->hSumRows[r].reserved = 0;
+                tiles += (size_t)QZSTD_HIP_ESUM_TILES(fr->len, fr->k);
+                r++;
+            }
+            if (rc == 0 && (qfGrowD(dev, &s->dSumRows, &s->dSumRowsCap, pr->diffs * sizeof(qzstd_hip_esum_row_t)) ||
+                            qfGrowD(dev, &s->dSumScratch, &s->dSumScratchCap, QZSTD_HIP_ESUM_SCRATCH_BYTES(tiles))))
+                rc = -1;
+        }
         if (rc) break;
         for (c = 0; c < nf; c++) {
             const QF_RestoreFrame *fr = &table[pr->f0 + c];
@@ -310,6 +348,15 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)pr->based, __ATOMIC_RELAXED);
+        if (pr->diffs) {
+            /* behind the scatter on the same stream: the differences lie at their destinations */
+            if (qzstd_hip_esum(dev, s->stream, s->hSumRows, (uint32_t)pr->diffs, (qzstd_hip_esum_row_t *)s->dSumRows, s->dSumScratch, s->dSumScratchCap)) {
+                rc = -1;
+                break;
+            }
+            __atomic_fetch_add(&f->ediffStats[2], (unsigned long long)pr->diffs, __ATOMIC_RELAXED);
+            __atomic_fetch_add(&f->ediffStats[3], 1ull, __ATOMIC_RELAXED);
+        }
     }
     /* nothing the library queued may still write the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
     for (k = 0; slot && k < 2; k++) {
@@ -385,8 +432,8 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
     if (!f || (nBufs && !bufSizes) || (nSlices && !slices) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     chunk = f->p.chunkSize;
     for (i = 0; i < nBufs; i++) {
-        const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
-        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1;
+        const unsigned e = (elemSizes && elemSizes[i] ? elemSizes[i] : f->group) & ~((elemSizes && elemSizes[i]) ? QZSTD_ELEM_DIFF : 0u);
+        if (e != 1u && e != 2u && e != 4u && e != 8u) return (size_t)-1; /* (a differenced buffer: refused below when a slice touches it) */
         want += bufSizes[i] / chunk + (bufSizes[i] % chunk != 0);
     }
     if (want != nFrames || (nFrames && (!frames || !frameSizes))) return (size_t)-1;
@@ -397,6 +444,7 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
             return (size_t)-1; /* not in ascending order, or overlapping in the source */
         if (!s->size) continue;
         if (!s->d_dst) return (size_t)-1;
+        if (elemSizes && (elemSizes[s->buf] & QZSTD_ELEM_DIFF)) return (size_t)-1; /* a window needs the sum from its frame's start */
         nPieces += (s->offset + s->size - 1u) / chunk - s->offset / chunk + 1u;
     }
     if (!qzstd_hip_ungroup_window || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||

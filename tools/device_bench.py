@@ -1245,8 +1245,170 @@ def fingerprint_main(a):
     print(json.dumps(out))
 
 
+def ediff_kernels(a, size, out):
+    """qzstd_hip_group_ediff beside qzstd_hip_group and qzstd_hip_esum beside qzstd_hip_ungroup IN ONE RUN: ONE launch each over the same N GiB
+    as rows of 128 KiB, k = 4 and 8, ms per GiB from events around the launch (rows uploaded inside), alternating, every run listed after one
+    untimed round.  Traffic: the two gathers move 2 bytes per content byte; the summing launch reads the destination twice and writes it once"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_ediff_kernels(plug.lib)
+    L.qzstd_hip_group.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.qzstd_hip_ungroup.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    n = size // a.chunk
+    gib = size / float(1 << 30)
+    torch.manual_seed(0)
+    src = torch.cumsum(torch.randint(5, 41, (size // 8,), device="cuda:0", dtype=torch.int64), 0).view(torch.uint8)
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    dst = torch.empty(size, dtype=torch.uint8, device="cuda:0")
+    tiles = size >> 14
+    scratch = torch.empty(D.esum_scratch_bytes(tiles), dtype=torch.uint8, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.GroupEdiffRow))
+    assert d_rows and src.data_ptr() % 16 == 0 and stage.data_ptr() % 16 == 0 and scratch.data_ptr() % 16 == 0
+    cells = {}
+    try:
+        for k in (4, 8):
+            g_rows, e_rows, u_rows, s_rows = (D.GroupRow * n)(), (D.GroupEdiffRow * n)(), (D.UngroupRow * n)(), (D.EsumRow * n)()
+            for c in range(n):
+                o = c * a.chunk
+                for r in (g_rows[c], e_rows[c]):
+                    r.src, r.dstOff, r.len, r.pad, r.elem = src.data_ptr() + o, o, a.chunk, 16 if c + 1 == n else 0, k
+                e_rows[c].flags = D.EDIFF_DIFF
+                u_rows[c].dst, u_rows[c].srcOff, u_rows[c].len, u_rows[c].elem = dst.data_ptr() + o, o, a.chunk, k
+                s_rows[c].dst, s_rows[c].len, s_rows[c].elem = dst.data_ptr() + o, a.chunk, k
+            legs = (("group", lambda: L.qzstd_hip_group(0, None, g_rows, n, d_rows, stage.data_ptr(), size + 16)),
+                    ("group_ediff", lambda: L.qzstd_hip_group_ediff(0, None, e_rows, n, d_rows, stage.data_ptr(), size + 16)),
+                    ("ungroup", lambda: L.qzstd_hip_ungroup(0, None, u_rows, n, d_rows, stage.data_ptr(), size + 16)),
+                    ("esum", lambda: L.qzstd_hip_esum(0, None, s_rows, n, d_rows, scratch.data_ptr(), scratch.numel())))
+            runs = {name: [] for name, _ in legs}
+            for i in range(a.reps + 1):
+                for name, call in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    assert call() == 0, plug.err()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i:
+                        runs[name].append(round(e0.elapsed_time(e1) / gib, 3))
+            # the last round's order was group_ediff -> ungroup -> esum: the destination holds the source again
+            assert torch.equal(dst.view(torch.int64)[:1 << 16], src.view(torch.int64)[:1 << 16]) and torch.equal(dst[-(1 << 16):], src[-(1 << 16):]), k
+            cells["k%d" % k] = {name + "_ms_per_gib": v for name, v in runs.items()}
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    out["kernels"] = {"rows": n, "row_bytes": a.chunk, "cells": cells,
+                      "timed": "events around ONE launcher call each (rows uploaded inside; esum is three kernels) over the same %d rows of %d bytes, ms per "
+                               "GiB of rows, alternating in one run, every run of %d after one untimed round" % (n, a.chunk, a.reps)}
+
+
+def ediff_main(a):
+    """--ediff: N GiB of int64 timestamps and of int32 offsets as ONE tensor each, 128 KiB frames: the Typed calls with QZSTD_ELEM_DIFF off and on,
+    and what a caller does today — a torch.diff-style pre-pass into a temporary, then the Typed call; the Typed restore, then cumsum — the legs
+    alternating in one run; then the two kernels beside qzstd_hip_group and qzstd_hip_ungroup.  --kernels: the kernel legs alone"""
+    size = int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "reps": a.reps}
+    if a.kernels:
+        ediff_kernels(a, size, out)
+        return print(json.dumps(out))
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out["timed"] = ("GB/s of input, every run, the legs alternating in one run; the window holds the library call, the torch passes of the leg and the "
+                    "closing synchronize.  off / on: QZSTD_frontCompressDeviceBatchTyped and QZSTD_frontRestoreDeviceBatchTyped without and with "
+                    "QZSTD_ELEM_DIFF; torch: d[0] = x[0], d[1:] = x[1:] - x[:-1] into a fresh temporary (over the whole tensor, no zigzag), the Typed "
+                    "call on it, and on the way back the Typed restore followed by cumsum into the destination")
+    out["cells"] = {}
+    torch.manual_seed(1)
+    inputs = (("timestamps_int64", torch.int64, 8,
+               lambda m: 1_700_000_000_000_000 + torch.cumsum(torch.empty(m, device="cuda:0").exponential_(1e-3).to(torch.int64) + 1, 0)),
+              ("offsets_int32", torch.int32, 4, lambda m: torch.cumsum(torch.randint(5, 41, (m,), device="cuda:0", dtype=torch.int64), 0).to(torch.int32)))
+    for name, dtype, k, make in inputs:
+        x = make(size // k)
+        back = torch.empty_like(x)
+        for level in [int(v) for v in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            cell = out["cells"]["%s_level%d" % (name, level)] = {}
+            try:
+                fr.reserve(size)
+
+                import ctypes as C
+                _, sizes = fr._frame_buffers(n)
+                outb = fr.out_batch([(back.data_ptr(), size)])
+                kept = {}
+
+                def compress(t, flag):
+                    bufs, _, frames_n = fr.batch([(t.data_ptr(), size)])
+                    assert frames_n == n
+                    return fr.lib.QZSTD_frontCompressDeviceBatchTyped(fr.f, bufs, bytes([k | flag, 0]), 1, stream, fr._dst, len(fr._dst), sizes, None)
+
+                def pre(t):
+                    d = torch.empty_like(t)
+                    d[0] = t[0]
+                    torch.sub(t[1:], t[:-1], out=d[1:])
+                    return d
+
+                def c_off():
+                    return compress(x, 0)
+
+                def c_on():
+                    return compress(x, D.ELEM_DIFF)
+
+                def c_torch():
+                    return compress(pre(x), 0)
+
+                for leg, f in (("off", c_off), ("on", c_on), ("torch", c_torch)):  # untimed: the slots, the pinned scratch; the frames are kept
+                    assert f() == n, leg
+                    torch.cuda.synchronize()
+                    buf = C.create_string_buffer(n * fr.stride)
+                    C.memmove(buf, fr._dst, n * fr.stride)
+                    kept[leg] = (buf, (C.c_size_t * n)(*sizes[:n]))
+                    cell["compressed_" + leg] = sum(sizes[:n])
+
+                def restore(leg, to, flag):
+                    buf, sz = kept[leg]
+                    return fr.lib.QZSTD_frontRestoreDeviceBatchTyped(fr.f, buf, fr.stride, sz, n, to, bytes([k | flag, 0]), 1, stream)
+
+                def r_off():
+                    return restore("off", outb, 0)
+
+                def r_on():
+                    return restore("on", outb, D.ELEM_DIFF)
+
+                def r_torch():
+                    tmp = torch.empty_like(x)
+                    r = restore("torch", fr.out_batch([(tmp.data_ptr(), size)]), 0)
+                    torch.cumsum(tmp, 0, dtype=dtype, out=back)
+                    return r
+
+                runs = {}
+                for leg, f in (("restore_off", r_off), ("restore_on", r_on), ("restore_torch", r_torch)):
+                    back.zero_()
+                    assert f() == n, leg
+                    torch.cuda.synchronize()
+                    assert torch.equal(back, x), leg
+                legs = (("compress_off", c_off), ("compress_on", c_on), ("compress_torch", c_torch), ("restore_off", r_off), ("restore_on", r_on),
+                        ("restore_torch", r_torch))
+                for _ in range(a.reps):
+                    for leg, f in legs:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert f() == n, leg
+                        torch.cuda.synchronize()
+                        runs.setdefault(leg + "_gbps", []).append(round(size / (time.perf_counter() - t0) / 1e9, 2))
+                cell.update(runs)
+                cell["elem_diff_stats"] = fr.elem_diff_stats()
+            finally:
+                fr.close()
+        del x, back
+        torch.cuda.empty_cache()
+    ediff_kernels(a, size, out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--ediff", action="store_true")
     ap.add_argument("--fingerprint", action="store_true")
     ap.add_argument("--probe", action="store_true")
     ap.add_argument("--verify", action="store_true")
@@ -1268,6 +1430,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.ediff:
+        if a.levels == "1,6,12":
+            a.levels = "1,6"
+        return ediff_main(a)
     if a.fingerprint:
         return fingerprint_main(a)
     if a.probe:

@@ -16,6 +16,9 @@ compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() f
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
 
+Element differences (include/qzstd_elemdiff.h, QZSTD_ELEM_DIFF, QZSTD_frontElemDiffStats): elem_diff / elem_sum, the rows and bindings of
+qzstd_hip_group_ediff and qzstd_hip_esum, DeviceFront.elem_diff_stats, and diff= on compress_tensors() / restore_tensors().
+
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
 import ctypes as C
 import os
@@ -455,6 +458,9 @@ def bind(F):
                                                   C.c_void_p]
         F.QZSTD_frontFingerprintStats.restype = None
         F.QZSTD_frontFingerprintStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontElemDiffStats"):  # (absent from an older library)
+        F.QZSTD_frontElemDiffStats.restype = None
+        F.QZSTD_frontElemDiffStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     return F
 
 
@@ -501,6 +507,69 @@ def group_bytes(data: bytes, k: int, lib=None) -> bytes:
 def ungroup_bytes(data: bytes, k: int, lib=None) -> bytes:
     """QZSTD_byteUngroup: the inverse of group_bytes"""
     return _regroup(_bg(lib).QZSTD_byteUngroup, data, k)
+
+
+class GroupEdiffRow(C.Structure):
+    """qzstd_hip_group_ediff_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32), ("elem", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
+class EsumRow(C.Structure):
+    """qzstd_hip_esum_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("dst", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32), ("tile0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+EDIFF_DIFF = 1  # QZSTD_HIP_EDIFF_DIFF
+
+
+def bind_ediff_kernels(L):
+    """qzstd_hip_group_ediff and qzstd_hip_esum on a loaded device layer (libqatseqprod)"""
+    L.qzstd_hip_group_ediff.restype = C.c_int
+    L.qzstd_hip_group_ediff.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    L.qzstd_hip_esum.restype = C.c_int
+    L.qzstd_hip_esum.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
+    return L
+
+
+def esum_tiles(n: int, k: int) -> int:
+    """QZSTD_HIP_ESUM_TILES: 16 KiB tiles of a row's n // k elements"""
+    return (n // k + 16384 // k - 1) // (16384 // k)
+
+
+def esum_scratch_bytes(tiles: int) -> int:
+    """QZSTD_HIP_ESUM_SCRATCH_BYTES"""
+    return tiles * 24
+
+
+def bind_elemdiff(L):
+    """include/qzstd_elemdiff.h on a loaded library (libqzstdfront, or qzstd_elemdiff.c built alone)"""
+    for fn in (L.QZSTD_elemDiff, L.QZSTD_elemSum):
+        fn.restype = C.c_size_t
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint]
+    return L
+
+
+_elemdiff_lib = None
+
+
+def _ed(lib):
+    global _elemdiff_lib
+    if lib is not None:
+        return lib
+    if _elemdiff_lib is None:
+        _elemdiff_lib = bind_elemdiff(B.Front().lib)
+    return _elemdiff_lib
+
+
+def elem_diff(data: bytes, k: int, lib=None) -> bytes:
+    """QZSTD_elemDiff: one chunk's zigzagged element differences for element size k"""
+    return _regroup(_ed(lib).QZSTD_elemDiff, data, k)
+
+
+def elem_sum(data: bytes, k: int, lib=None) -> bytes:
+    """QZSTD_elemSum: the inverse of elem_diff"""
+    return _regroup(_ed(lib).QZSTD_elemSum, data, k)
 
 
 def group_blocks(n: int, k: int, lib=None) -> list:
@@ -640,6 +709,13 @@ class DeviceFront:
         if r != sum(len(fr) for fr in frames_per_buffer):
             raise RuntimeError("QZSTD_frontRestoreDeviceBatchDelta failed (%d)" % (r if r != ERROR else -1))
         return r
+
+    def elem_diff_stats(self) -> list:
+        """QZSTD_frontElemDiffStats: flagged frames [0] differenced on the GPU, [1] of those differenced again on the host (a failed block),
+        [2] summed by a restore; [3] qzstd_hip_esum launches"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontElemDiffStats(self.f, st)
+        return list(st)
 
     def delta_stats(self) -> list:
         """frames with a base built from [0] sequences + literals, [1] rebuilt content, [2] both buffers copied back; [3] frames restored onto a base"""
@@ -946,14 +1022,33 @@ def element_group(t) -> int:
     return t.element_size() if t.element_size() in (2, 4, 8) else 1
 
 
-def compress_tensors(front: DeviceFront, tensors, stream=None, group=None) -> list:
+ELEM_DIFF = 0x80  # QZSTD_ELEM_DIFF
+
+
+def _diff_flags(what: str, tensors, diff):
+    """diff: None / False (no tensor), True (every tensor), or one bool per tensor -> per tensor QZSTD_ELEM_DIFF or 0"""
+    if diff is None or diff is False:
+        return [0] * len(tensors)
+    if diff is True:
+        return [ELEM_DIFF] * len(tensors)
+    diff = list(diff)
+    if len(diff) != len(tensors):
+        raise ValueError(what + ": diff is a bool, or one bool per tensor")
+    return [ELEM_DIFF if d else 0 for d in diff]
+
+
+def compress_tensors(front: DeviceFront, tensors, stream=None, group=None, diff=None) -> list:
     """per tensor the frames of its bytes, all tensors in ONE call (QZSTD_frontCompressDeviceBatch): contiguous GPU tensors of any dtypes
     and sizes, views with a storage offset included, all on one device.  `stream`: the torch.cuda.Stream (or raw hipStream_t) that
     produced them; default: the current stream of their device.  group="dtype": every tensor byte-grouped by its own element size
-    (QZSTD_frontCompressDeviceBatchTyped; restore_tensor() undoes it); None: the front's setting."""
+    (QZSTD_frontCompressDeviceBatchTyped; restore_tensor() undoes it); None: the front's setting.  diff (with group="dtype" only; off by
+    default): True, or one bool per tensor — element differences (QZSTD_ELEM_DIFF) for integer columns with order; unordered data grows."""
     if group not in (None, "dtype"):
         raise ValueError("compress_tensors: group is None or \"dtype\"")
     tensors = list(tensors)
+    flags = _diff_flags("compress_tensors", tensors, diff)
+    if any(flags) and group != "dtype":
+        raise ValueError("compress_tensors: diff needs group=\"dtype\" (differences are taken with each tensor's own element size)")
     for t in tensors:
         if not t.is_cuda or not t.is_contiguous():
             raise ValueError("compress_tensors: contiguous GPU tensors")
@@ -966,16 +1061,19 @@ def compress_tensors(front: DeviceFront, tensors, stream=None, group=None) -> li
     handle = getattr(stream, "cuda_stream", stream)
     bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
     if group == "dtype":
-        return front.compress_device_batch_typed(bufs, [element_group(t) for t in tensors], handle)
+        return front.compress_device_batch_typed(bufs, [element_group(t) | fl for t, fl in zip(tensors, flags)], handle)
     return front.compress_device_batch(bufs, handle)
 
 
-def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None, group=None) -> int:
+def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None, group=None, diff=None) -> int:
     """the way back of compress_tensors(): per tensor its frames, restored INTO the given contiguous GPU tensors (same sizes, same `group`) in ONE
     call (QZSTD_frontRestoreDeviceBatchTyped: decoded by the front's workers, ungrouped on the GPU) -> the frame count"""
     if group not in (None, "dtype"):
         raise ValueError("restore_tensors: group is None or \"dtype\"")
     tensors = list(tensors)
+    flags = _diff_flags("restore_tensors", tensors, diff)  # (the values compress_tensors() was given: the frames do not hold them)
+    if any(flags) and group != "dtype":
+        raise ValueError("restore_tensors: diff needs group=\"dtype\"")
     for t in tensors:
         if not t.is_cuda or not t.is_contiguous() or t.device != tensors[0].device:
             raise ValueError("restore_tensors: contiguous GPU tensors on one device")
@@ -985,7 +1083,7 @@ def restore_tensors(front: DeviceFront, frames_per_tensor, tensors, stream=None,
         stream = torch.cuda.current_stream(tensors[0].device)
     handle = getattr(stream, "cuda_stream", stream)
     bufs = [(t.data_ptr(), t.numel() * t.element_size()) for t in tensors]
-    return front.restore_batch(frames_per_tensor, bufs, [element_group(t) for t in tensors] if group == "dtype" else None, handle)
+    return front.restore_batch(frames_per_tensor, bufs, [element_group(t) | fl for t, fl in zip(tensors, flags)] if group == "dtype" else None, handle)
 
 
 def verify_tensors(front: DeviceFront, frames_per_tensor, tensors, bases=None, stream=None, group=None) -> list:
