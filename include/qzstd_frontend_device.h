@@ -358,6 +358,45 @@ size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, 
  * [3] frames a check found differing */
 void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Advice: which buffers of a list should carry QZSTD_ELEM_DIFF?  Differences shrink columns with order and GROW data without, so the flag is
+ * per buffer and the caller's decision; this call makes it from statistics instead of compressing every buffer twice.  Per chunk — cut as the
+ * compress calls cut frames — and per 16 KiB tile of its elements the GPU takes the byte histograms of every plane of the grouped layout
+ * twice, once for the elements as they are and once for their zigzagged differences, and reduces them to two order-0 cost words
+ * (include/qzstd_ediffcost.h over include/qzstd_planecost.h: exact 32-bit words, the same on the device and in plain C).  The host sums them per
+ * buffer: P (as they are) and D (differenced), in bytes, and flags the buffer where QZSTD_ediffAdvised(P, D) holds:
+ * D + (D >> QZSTD_EDIFF_ADVISE_MARGIN_SHIFT) < P.  P == D, both 0 included, is not flagged: off is the default.
+ *
+ * elemSizes: as QZSTD_frontCompressDeviceBatchTyped's (1, 2, 4, 8, or 0 for the front's setting; NULL: all 0); an entry that ALREADY carries
+ * QZSTD_ELEM_DIFF is refused like any other bad entry.  advised[i] receives the buffer's resolved element size — never 0 — with
+ * QZSTD_ELEM_DIFF OR-ed in where differences are advised: the array can be passed as it is to QZSTD_frontCompressDeviceBatchTyped and
+ * QZSTD_frontRestoreDeviceBatchTyped, and is kept with the frames as element sizes are.  est (2 * nBufs entries, or NULL): est[2 i] = P and
+ * est[2 i + 1] = D of buffer i.  Returns how many buffers are flagged.
+ *
+ * THE ADVICE IS AN ESTIMATE of what the entropy stage alone can reach.  It does not see matches: the low plane of a sawtooth or an arange
+ * costs its full length in P and next to nothing in a frame, so P is overestimated for such columns (D, whose planes are near-noise or
+ * constant, is within a few points of the differenced frames' size).  It does not see bases: a buffer is judged as if it had none, and the
+ * compress calls refuse a flagged buffer with a base anyway.  It says nothing on whether to byte-group at all.  A caller that knows more may
+ * apply its own rule to est and build the array itself.
+ *
+ * The calling sequence is the fingerprint calls': the host-side pointer and device checks of QZSTD_frontCompressDeviceBatch, the library's stream
+ * waits for `stream`, ONE qzstd_hip_ediff_cost launch with a row per chunk pointing INTO the caller's buffers (nothing is staged, the buffers
+ * are only read: one byte read per content byte), one device->host copy (8 bytes per 16 KiB), a bounded wait, and the sums on the calling
+ * thread.  Rows and words live in grow-only pinned and device scratch kept with the front.  Blocks until done.
+ * (size_t)-1 before anything is queued: everything the batch compress call refuses about bufs (a null array, a null pointer with a size,
+ * memory that is not device memory of one device), a bad or flagged elemSizes entry, advised NULL with nBufs > 0, a call while another one
+ * runs on this front, more than 2^32 - 1 chunks or 2^31 - 1 tiles in one call, and a device layer without qzstd_hip_ediff_cost — every other
+ * call is served by such a layer as before.  A front created with useProducer = 0 is accepted.  No buffers, or only buffers shorter than
+ * their element: advised[] is filled with the resolved sizes, est with zeros, 0 is returned and no GPU is touched. */
+size_t QZSTD_frontAdviseDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs,
+                                    void *stream, unsigned char *advised /* nBufs */, unsigned long long *est /* 2 * nBufs, or NULL */);
+/* since creation, of the calls that succeeded: [0] buffers advised on, [1] of them flagged, [2] bytes read on the device (whole elements),
+ * [3] qzstd_hip_ediff_cost launches */
+void QZSTD_frontAdviseStats(QZSTD_Front *f, unsigned long long stats[4]);
+/* QZSTD_ediffCostChunk / QZSTD_ediffAdvised of include/qzstd_ediffcost.h as exported functions (bindings that cannot include the header):
+ * sums[0] = P and sums[1] = D of one chunk of len bytes with elements of k bytes; both 0 for a k outside {1, 2, 4, 8} */
+void QZSTD_ediffCostOf(const void *chunk, size_t len, unsigned k, unsigned long long sums[2]);
+int QZSTD_ediffAdvisedOf(unsigned long long P, unsigned long long D);
+
 #if defined(__cplusplus)
 }
 #endif

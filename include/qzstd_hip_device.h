@@ -6,7 +6,8 @@
  * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
  * the content-checksum kernel (QZSTD_frontSetChecksum), the byte histograms' cost per block (QZSTD_frontSetPlaneProbe), the tile
  * digests of the tensor fingerprints (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch), and the grouping gather with element
- * differences and the element sum that undoes them (QZSTD_ELEM_DIFF in an elemSizes entry of the Typed calls).
+ * differences and the element sum that undoes them (QZSTD_ELEM_DIFF in an elemSizes entry of the Typed calls), and the plane costs with and
+ * without element differences that advise that flag (QZSTD_frontAdviseDeviceBatch).
  * Additive to qzstd_hip.h (same conventions: 0 on success, < 0 on failure, qzstd_hip_last_error()), which includes this header;
  * exported by the same library (libqatseqprod).
  */
@@ -430,6 +431,40 @@ typedef struct {
 } qzstd_hip_esum_row_t;
 int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *rows, uint32_t nRows, qzstd_hip_esum_row_t *d_rows, void *d_scratch,
                    size_t scratchBytes);
+
+/*
+ * Element-difference cost (QZSTD_frontAdviseDeviceBatch): ONE launch reads every row — `len` bytes anywhere in device memory, at any
+ * alignment, also one that is no multiple of elem; one byte read per content byte — and leaves TWO words per 16 KiB tile of its elements:
+ * d_tiles[2 (tile0 + j)] = plain and d_tiles[2 (tile0 + j) + 1] = diff of include/qzstd_ediffcost.h (QZSTD_ediffCostTile: the order-0 cost of
+ * every byte plane of the tile's elements as they are, and of their zigzagged differences), computed on the device with that header's and
+ * qzstd_planecost.h's own functions.  Tiles are qzstd_hip_esum's (QZSTD_HIP_ESUM_TILES; a row shorter than elem has none, the len - n * elem
+ * tail bytes are in no histogram); differences are per row, x[-1] = 0.  The host sums a row's words.
+ *
+ * One workgroup of 256 threads per tile; its row is found by a binary search over tile0, which the launcher writes (the running sum of the
+ * rows' tiles).  Loads are aligned 16-byte loads of the words that overlap [src, src + n * elem) and of no other word, shifted into place by
+ * the row's own misalignment; a lane's 16 bytes are whole elements counted from the row's first byte, the element in front of them comes
+ * from the lane before by a shuffle that every lane executes, and the first lane of a wave fetches it itself (0 at the row's start) — what
+ * qzstd_hip_group_ediff does.  The 2 * elem histograms live in LDS, each in 16 / elem copies (a lane's copy is its index mod 16 / elem;
+ * 32 KiB for every elem); a plane on which all of a wave's bytes agree — the zero planes of small differences, the constant upper bytes of
+ * timestamps — gets ONE add of the wave's element count by one lane.  A reduction with QZSTD_planeTerm and QZSTD_planeCostOfSum follows, and
+ * one lane stores the tile's two words as one 8-byte store.  No global atomics, no memset, no workgroup waits for another; nothing but
+ * d_tiles[0 .. 2 * total tiles) is written — the rows' bytes are only read.
+ *
+ * `rows` is HOST memory (pinned, for the upload to be asynchronous), is WRITTEN by the launcher (tile0 only, and only by a launch that is
+ * not refused) and must stay unchanged until the stream has passed the call; d_rows: device scratch of nRows entries.  Refused (< 0) before
+ * anything is queued: a null rows, d_rows or d_tiles, a d_tiles that is not 8-byte aligned, a null src with len >= elem, an elem outside
+ * {1, 2, 4, 8}, a reserved that is not 0, len > 0xFFFFFFE0, more than 2^31 - 1 tiles.  nRows == 0, or no row with an element: nothing is
+ * queued, 0.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t src;      /* device address of the row's first byte, any alignment */
+    uint32_t len;      /* bytes; n = len / elem elements are counted, the rest is left out */
+    uint32_t elem;     /* element size: 1, 2, 4 or 8 */
+    uint32_t tile0;    /* written by the launcher: tiles of the rows before this one */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_ediff_cost_row_t;
+int qzstd_hip_ediff_cost(int device, void *stream, qzstd_hip_ediff_cost_row_t *rows, uint32_t nRows, qzstd_hip_ediff_cost_row_t *d_rows,
+                         uint32_t *d_tiles);
 
 #if defined(__cplusplus)
 }

@@ -2041,3 +2041,196 @@ extern "C" int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *ro
     QZ_CHECK(hipGetLastError(), "launch qzstd_esum_apply_kernel");
     return 0;
 }
+
+/* ---------------------------------------------------------------- element-difference cost (include/qzstd_hip_device.h, qzstd_ediffcost.h) -- */
+#include "qzstd_ediffcost.h"
+
+namespace {
+constexpr uint32_t kEcT = 256u;                          /* threads per workgroup: one per bin in the reduction */
+constexpr uint32_t kEcTile = 1u << kGroupTileLog;        /* bytes of a row's elements per workgroup: 16 KiB, four 16-byte words per lane */
+constexpr uint32_t kEcRounds = kEcTile / 16u / kEcT;
+constexpr uint32_t kEcWords = 2u * 256u * 16u;           /* LDS words: 2 K histograms of 256 bins in 16 / K copies each — 32 KiB for every K:
+                                                            four workgroups a CU. Bin b of histogram h, copy c: word (h * 256 + b) * (16 / K) + c */
+static_assert(kEcTile == QZSTD_EDIFF_TILE && kEcRounds == 4u, "the definition's tile: 256 lanes, four words each");
+static_assert(QZSTD_EDIFF_TILES(16385u, 2u) == QZSTD_HIP_ESUM_TILES(16385u, 2u) && QZSTD_EDIFF_TILES(7u, 8u) == QZSTD_HIP_ESUM_TILES(7u, 8u),
+              "one tile rule");
+
+/* the K low bytes of x, repeated over 8 bytes */
+template <uint32_t K> __device__ inline uint64_t ec_repeat(uint64_t x)
+{
+    if constexpr (K == 8u) return x;
+    else if constexpr (K == 4u) return (x & 0xFFFFFFFFull) * 0x0000000100000001ull;
+    else if constexpr (K == 2u) return (x & 0xFFFFull) * 0x0001000100010001ull;
+    else return (x & 0xFFull) * 0x0101010101010101ull;
+}
+
+/* One side's 16 bytes {o1, o0} = 16 / K elements into that side's K histograms (`mine`: the side's first word plus the lane's copy).
+ * Every lane of the wave calls it.  Per plane the wave first asks whether ALL its bytes of the plane equal the first lane's (an XOR with
+ * that lane's first element repeated, OR-ed down to K bytes, one vote): then lane 0 adds the wave's element count to that one bin — the
+ * zero planes of small differences and the constant upper bytes of a column would otherwise put 64 lanes on one word, four times a round
+ * for K = 4.  Otherwise every lane adds its own bytes, on its copy.  `valid`: the lane's bytes that count (a multiple of K; 0 for a lane
+ * without a word, whose o0 and o1 are 0); the bytes behind them are 0 and are not counted. */
+template <uint32_t K> __device__ inline void ec_count(uint32_t *mine, uint64_t o0, uint64_t o1, uint32_t valid, uint32_t waveElems)
+{
+    constexpr uint32_t C = 16u / K;
+    const uint64_t first = (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)o0) |
+                           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(o0 >> 32)) << 32;
+    const uint64_t R = ec_repeat<K>(first);
+    uint64_t t = valid ? (o0 ^ R) | (o1 ^ R) : 0ull;
+    if constexpr (K <= 4u) t |= t >> 32;
+    if constexpr (K <= 2u) t |= t >> 16;
+    if constexpr (K == 1u) t |= t >> 8;
+#pragma unroll
+    for (uint32_t j = 0; j < K; j++) {
+        if (!__any((int)((uint32_t)(t >> (8u * j)) & 0xFFu))) { /* (the same answer in every lane) */
+            if ((threadIdx.x & 63u) == 0u && waveElems) atomicAdd(&mine[(j * 256u + ((uint32_t)(R >> (8u * j)) & 0xFFu)) * C], waveElems);
+        } else if (valid == 16u) {
+#pragma unroll
+            for (uint32_t e = 0; e < C; e++) {
+                const uint32_t i = e * K + j;
+                atomicAdd(&mine[(j * 256u + ((uint32_t)(i < 8u ? o0 >> (i * 8u) : o1 >> ((i - 8u) * 8u)) & 0xFFu)) * C], 1u);
+            }
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < C; e++) {
+                const uint32_t i = e * K + j;
+                if (i < valid) atomicAdd(&mine[(j * 256u + ((uint32_t)(i < 8u ? o0 >> (i * 8u) : o1 >> ((i - 8u) * 8u)) & 0xFFu)) * C], 1u);
+            }
+        }
+    }
+}
+
+/* A tile of `tileBytes` bytes (whole elements) at srcTile -> its two words.  Lane t takes the tile's words t, t + 256, t + 512, t + 768,
+ * fetched as the differencing gather fetches its source (group_fetch: the aligned words that overlap the wanted bytes only, shifted by the
+ * row's OWN misalignment), all four before the first is counted, so that the loads are in flight together; the bytes behind the tile's
+ * last element are masked to 0 (cmp_mask) and never counted.  The element in front of a lane's word comes from the lane before it by a
+ * shuffle that every lane executes; a wave's first lane fetches it (ediff_elem_at), or takes 0 at the row's start — ediff_phase_a's rule.
+ * Then bin t of every histogram: its copies summed, QZSTD_planeTerm, a sum over the wave (xor shuffles) and the four waves (one LDS step),
+ * QZSTD_planeCostOfSum per plane, and thread 0 stores the two words with one 8-byte store. */
+template <uint32_t K> __device__ inline void ec_tile(uint64_t srcTile, uint32_t tileBytes, bool rowStart, uint32_t *hist, uint32_t (*red)[kEcT / 64u],
+                                                     uint2 *out)
+{
+    constexpr uint32_t C = 16u / K;
+    const uint32_t tid = threadIdx.x;
+    uint64_t x0[kEcRounds], x1[kEcRounds], front[kEcRounds];
+#pragma unroll
+    for (uint32_t q = 0; q < kEcRounds; q++) {
+        const uint32_t w = q * kEcT + tid;
+        x0[q] = x1[q] = front[q] = 0ull;
+        if (w * 16u < tileBytes) {
+            const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+            group_fetch(srcTile + w * 16u, valid, &x0[q], &x1[q]);
+            cmp_mask(valid, &x0[q], &x1[q]);
+            if ((tid & 63u) == 0u && !(w == 0u && rowStart)) front[q] = ediff_elem_at<K>(srcTile + w * 16u - K);
+        }
+    }
+    uint32_t *mineX = hist + (tid & (C - 1u)), *mineZ = mineX + K * 256u * C;
+#pragma unroll
+    for (uint32_t q = 0; q < kEcRounds; q++) {
+        const uint32_t w = q * kEcT + tid, wave0 = w & ~63u;
+        const uint32_t valid = w * 16u < tileBytes ? (tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u) : 0u;
+        const uint32_t waveBytes = wave0 * 16u < tileBytes ? (tileBytes - wave0 * 16u < 1024u ? tileBytes - wave0 * 16u : 1024u) : 0u;
+        uint64_t prev = __shfl_up(ediff_last<K>(x1[q]), 1u, 64);
+        if ((tid & 63u) == 0u) prev = front[q];
+        uint64_t z0 = x0[q], z1 = x1[q];
+        ediff_word<K>(&z0, &z1, prev);
+        cmp_mask(valid, &z0, &z1);
+        if (valid == 0u) z0 = z1 = 0ull;
+        ec_count<K>(mineX, x0[q], x1[q], valid, waveBytes / K);
+        ec_count<K>(mineZ, z0, z1, valid, waveBytes / K);
+    }
+    __syncthreads();
+    const uint32_t Lm = QZSTD_planeLog2(tileBytes / K);
+#pragma unroll
+    for (uint32_t h = 0; h < 2u * K; h++) {
+        const uint32_t *bin = &hist[(h * 256u + tid) * C];
+        uint32_t c = 0u;
+        if constexpr (C == 2u) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(bin);
+            c = v.x + v.y;
+        } else {
+#pragma unroll
+            for (uint32_t v4 = 0; v4 < C / 4u; v4++) {
+                const uint4 v = reinterpret_cast<const uint4 *>(bin)[v4];
+                c += v.x + v.y + v.z + v.w;
+            }
+        }
+        uint32_t sum = QZSTD_planeTerm(c, Lm); /* (a plane's terms: at most m * L(m) < 2^26) */
+#pragma unroll
+        for (uint32_t s = 32u; s; s >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)s, 64);
+        if ((tid & 63u) == 0u) red[h][tid >> 6] = sum;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t cost[2] = { 0u, 0u };
+#pragma unroll
+        for (uint32_t h = 0; h < 2u * K; h++) cost[h / K] += QZSTD_planeCostOfSum(red[h][0] + red[h][1] + red[h][2] + red[h][3]);
+        *out = make_uint2(cost[0], cost[1]);
+    }
+}
+
+/* One workgroup per tile of a row's elements; its row is the last one with tile0 <= blockIdx.x (qzstd_diff_kernel's search: rows without
+ * a tile share the tile0 of the row behind them and are never that one).  No atomics but the LDS ones; nothing is read back. */
+__global__ __launch_bounds__(kEcT) void qzstd_ediff_cost_kernel(const qzstd_hip_ediff_cost_row_t *__restrict__ rows, uint32_t nRows,
+                                                                uint2 *__restrict__ tilesOut)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hist[kEcWords];
+    __shared__ uint32_t red[16][kEcT / 64u];
+    __shared__ uint32_t which;
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+    }
+    for (uint32_t i = tid; i < kEcWords / 4u; i += kEcT) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
+    __syncthreads();
+    const qzstd_hip_ediff_cost_row_t row = rows[which];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kEcTile >> kLog;
+    const uint64_t e0 = (uint64_t)(blockIdx.x - row.tile0) * tileMax; /* the tile's first element in its row */
+    if (e0 >= n) return; /* (the whole workgroup; never: see above) */
+    const uint32_t tileBytes = (n - (uint32_t)e0 < tileMax ? n - (uint32_t)e0 : tileMax) << kLog;
+    const uint64_t srcTile = row.src + (e0 << kLog);
+    uint2 *out = tilesOut + blockIdx.x;
+    switch (kLog) {
+    case 0u: ec_tile<1u>(srcTile, tileBytes, e0 == 0u, hist, red, out); break;
+    case 1u: ec_tile<2u>(srcTile, tileBytes, e0 == 0u, hist, red, out); break;
+    case 2u: ec_tile<4u>(srcTile, tileBytes, e0 == 0u, hist, red, out); break;
+    default: ec_tile<8u>(srcTile, tileBytes, e0 == 0u, hist, red, out); break;
+    }
+}
+} // namespace
+
+extern "C" int qzstd_hip_ediff_cost(int device, void *stream, qzstd_hip_ediff_cost_row_t *rows, uint32_t nRows, qzstd_hip_ediff_cost_row_t *d_rows,
+                                    uint32_t *d_tiles)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_tiles & 7u)) return fail_msg("qzstd_hip_ediff_cost: null pointer or tiles not 8-byte aligned");
+    uint64_t total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ediff_cost_row_t &r = rows[i];
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
+            return fail_msg("qzstd_hip_ediff_cost: elem not 1, 2, 4 or 8, or reserved not 0");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ediff_cost: row too long");
+        if (r.len >= r.elem && !r.src) return fail_msg("qzstd_hip_ediff_cost: null row");
+        total += QZSTD_HIP_ESUM_TILES(r.len, r.elem);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ediff_cost: too many tiles");
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_ESUM_TILES(rows[i].len, rows[i].elem);
+    }
+    if (total == 0) return 0; /* no row with an element */
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ediff cost rows)");
+    hipLaunchKernelGGL(qzstd_ediff_cost_kernel, dim3((uint32_t)total), dim3(kEcT), 0, (hipStream_t)stream, d_rows, nRows,
+                       reinterpret_cast<uint2 *>(d_tiles));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ediff_cost_kernel");
+    return 0;
+}

@@ -17,6 +17,7 @@
 #include "qzstd_planecost.h"
 #include "qzstd_fingerprint.h"
 #include "qzstd_elemdiff.h"
+#include "qzstd_ediffcost.h"
 
 #include <dlfcn.h>
 #include <pthread.h>
@@ -110,6 +111,7 @@ struct QZSTD_Front_s {
     int restoreSlotDev;
     unsigned long long verifyStats[4]; /* QZSTD_frontVerifyDeviceBatch: frames compared, of them differing, bytes compared, launches */
     unsigned long long fpStats[4];     /* the fingerprint calls: frames fingerprinted, bytes read on the device, launches, frames a check found differing */
+    unsigned long long adviseStats[4]; /* QZSTD_frontAdviseDeviceBatch: buffers advised on, buffers flagged, bytes read on the device, launches */
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -1790,3 +1792,7 @@ int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { ret
 
 /* Element differences and their sum (include/qzstd_elemdiff.h): free of HIP and libzstd like the byte-grouped layout; included the same way. */
 #include "qzstd_elemdiff.c"
+
+/* The adviser: are element differences worth it for a buffer, from plane costs taken on the GPU; on the restore's first slot like the
+ * fingerprint calls; included the same way. */
+#include "qzstd_advise.c"

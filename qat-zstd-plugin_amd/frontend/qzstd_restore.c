@@ -68,6 +68,10 @@ struct QF_RestoreSlot_s {
     void *dFpRows; size_t dFpRowsCap;
     void *dFpTiles; size_t dFpTilesCap;                        /* the launch's tile digests and their pinned copy */
     uint64_t *hFpTiles; size_t hFpTilesCap;
+    qzstd_hip_ediff_cost_row_t *hAdvRows; size_t hAdvRowsCap;  /* the adviser (qzstd_advise.c, slot 0 only): a row per chunk, */
+    void *dAdvRows; size_t dAdvRowsCap;
+    void *dAdvTiles; size_t dAdvTilesCap;                      /* the launch's two cost words per tile and their pinned copy */
+    uint32_t *hAdvTiles; size_t hAdvTilesCap;
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -101,6 +105,10 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->hFpRows) qzstd_hip_host_free(s->hFpRows);
         if (s->dFpTiles) qzstd_hip_free(f->restoreSlotDev, s->dFpTiles);
         if (s->hFpTiles) qzstd_hip_host_free(s->hFpTiles);
+        if (s->dAdvRows) qzstd_hip_free(f->restoreSlotDev, s->dAdvRows);
+        if (s->hAdvRows) qzstd_hip_host_free(s->hAdvRows);
+        if (s->dAdvTiles) qzstd_hip_free(f->restoreSlotDev, s->dAdvTiles);
+        if (s->hAdvTiles) qzstd_hip_host_free(s->hAdvTiles);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);

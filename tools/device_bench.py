@@ -1406,8 +1406,148 @@ def ediff_main(a):
     print(json.dumps(out))
 
 
+def advise_kernels(a, size, out):
+    """qzstd_hip_ediff_cost beside qzstd_hip_fingerprint and qzstd_hip_plane_cost IN ONE RUN: ONE launch each over the same N GiB as rows of
+    128 KiB, ms per GiB from events around the launch (rows uploaded inside), alternating, every run listed after one untimed round; the
+    cost kernel for k = 1, 2, 4, 8, on noise and on a zero-plane-heavy input (an int64 column of steps 5 .. 40: differenced, seven of its
+    eight planes are zero).  The other two do not depend on k.  Traffic: all three read 1 byte per content byte; the cost kernel does two LDS
+    histogram updates per byte where the plane-cost kernel does one"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_ediff_cost_kernel(D.bind_fingerprint_kernel(D.bind_plane_kernel(plug.lib)))
+    n = size // a.chunk
+    gib = size / float(1 << 30)
+    torch.manual_seed(0)
+    inputs = (("noise", torch.randint(0, 256, (size,), device="cuda:0", dtype=torch.uint8)),
+              ("zero_planes", torch.cumsum(torch.randint(5, 41, (size // 8,), device="cuda:0", dtype=torch.int64), 0).view(torch.uint8)))
+    tiles = torch.empty(2 * (size >> 14), dtype=torch.int32, device="cuda:0")
+    fp_tiles = torch.empty(size >> 14, dtype=torch.int64, device="cuda:0")
+    cost = torch.empty(n, dtype=torch.int32, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.EdiffCostRow))
+    assert d_rows
+    cells = {}
+    lib = D.bind(B.Front().lib)
+    try:
+        for name, src in inputs:
+            assert src.data_ptr() % 16 == 0
+            fp_rows, pl_rows = (D.FpRow * n)(), (D.PlaneRow * n)()
+            ec_rows = {k: (D.EdiffCostRow * n)() for k in (1, 2, 4, 8)}
+            for c in range(n):
+                o = c * a.chunk
+                fp_rows[c].src, fp_rows[c].len = src.data_ptr() + o, a.chunk
+                pl_rows[c].srcOff, pl_rows[c].len = o, a.chunk
+                for k, rows in ec_rows.items():
+                    rows[c].src, rows[c].len, rows[c].elem = src.data_ptr() + o, a.chunk, k
+            legs = [("ediff_cost_k%d" % k, (lambda rows: lambda: L.qzstd_hip_ediff_cost(0, None, rows, n, d_rows, tiles.data_ptr()))(rows))
+                    for k, rows in ec_rows.items()]
+            legs += [("fingerprint", lambda: L.qzstd_hip_fingerprint(0, None, fp_rows, n, d_rows, fp_tiles.data_ptr())),
+                     ("plane_cost", lambda: L.qzstd_hip_plane_cost(0, None, src.data_ptr(), pl_rows, n, d_rows, cost.data_ptr()))]
+            runs = {leg: [] for leg, _ in legs}
+            for i in range(a.reps + 1):
+                for leg, call in legs:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    e0.record()
+                    assert call() == 0, plug.err()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    if i:
+                        runs[leg].append(round(e0.elapsed_time(e1) / gib, 3))
+            # the words are worth something: the last launch (k = 8) over the first and the last row against the plain-C function
+            per = a.chunk >> 14
+            for row in (0, n - 1):
+                w = tiles[2 * row * per:2 * (row + 1) * per].cpu().numpy().astype("uint32").reshape(-1, 2).sum(axis=0)
+                assert (int(w[0]), int(w[1])) == D.ediff_cost_of(src[row * a.chunk:(row + 1) * a.chunk].cpu().numpy().tobytes(), 8, lib=lib), (name, row)
+            cells[name] = {leg + "_ms_per_gib": v for leg, v in runs.items()}
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    out["kernels"] = {"rows": n, "row_bytes": a.chunk, "cells": cells,
+                      "timed": "events around ONE launcher call each (rows uploaded inside) over the same %d rows of %d bytes, ms per GiB of rows, "
+                               "alternating in one run, every run of %d after one untimed round" % (n, a.chunk, a.reps)}
+
+
+def advise_main(a):
+    """--advise: QZSTD_frontAdviseDeviceBatch against what a caller does today to decide on QZSTD_ELEM_DIFF — the Typed compress call twice,
+    flag off and on, and the sizes compared — on N GiB of int32 offsets as one tensor and as tensors of 128 KiB, level 1, the legs alternating
+    in one run; then the kernel beside qzstd_hip_fingerprint and qzstd_hip_plane_cost.  --kernels: the kernel legs alone"""
+    import ctypes as C
+    size = int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "reps": a.reps, "dtype": "int32 offsets, steps 5 .. 40", "level": 1}
+    if a.kernels:
+        advise_kernels(a, size, out)
+        return print(json.dumps(out))
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out["timed"] = ("ms per decision, every run, the legs alternating in one run; the window holds the calls and the closing synchronize: advise = ONE "
+                    "QZSTD_frontAdviseDeviceBatch; twice = QZSTD_frontCompressDeviceBatchTyped at level 1 without and then with QZSTD_ELEM_DIFF "
+                    "on every tensor, and the per-tensor sizes compared on the host")
+    out["cells"] = {}
+    whole = torch.cumsum(torch.randint(5, 41, (size // 4,), device="cuda:0", dtype=torch.int64), 0).to(torch.int32)
+    for layout, nt in (("one_tensor", 1), ("%d_tensors" % n, n)):
+        per = size // nt
+        tensors = [whole[i * (per // 4):(i + 1) * (per // 4)] for i in range(nt)]
+        fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+        cell = out["cells"][layout] = {}
+        try:
+            fr.reserve(size)
+            bufs, _, frames_n = fr.batch([(x.data_ptr(), per) for x in tensors])
+            assert frames_n == n
+            _, sizes = fr._frame_buffers(n)
+            first = (C.c_size_t * (nt + 1))()
+            es = bytes([4] * nt) + b"\0"
+            es_on = bytes([4 | D.ELEM_DIFF] * nt) + b"\0"
+            adv = C.create_string_buffer(nt)
+            est = (C.c_ulonglong * (2 * nt))()
+
+            def advise():
+                return fr.lib.QZSTD_frontAdviseDeviceBatch(fr.f, bufs, es, nt, stream, adv, est)
+
+            def twice():
+                per_tensor = []
+                for e in (es, es_on):
+                    assert fr.lib.QZSTD_frontCompressDeviceBatchTyped(fr.f, bufs, e, nt, stream, fr._dst, len(fr._dst), sizes, first) == n
+                    s = sizes[:n]
+                    per_tensor.append([sum(s[first[i]:first[i + 1]]) for i in range(nt)])
+                return sum(1 for off, on in zip(*per_tensor) if on < off)
+
+            legs = (("advise", advise), ("twice", twice))
+            runs = {name + "_ms": [] for name, _ in legs}
+            for name, leg in legs:  # untimed: the slots, the pinned scratch
+                cell[name + "_flagged"] = leg()
+                torch.cuda.synchronize()
+            for _ in range(a.reps):
+                for name, leg in legs:
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    assert leg() == cell[name + "_flagged"], name
+                    torch.cuda.synchronize()
+                    runs[name + "_ms"].append(round((time.perf_counter() - t0) * 1e3, 2))
+            cell.update(runs)
+            # the estimate is worth something: the plain-C function over the first chunk-sized tensor, and both layouts sum to the same words
+            cell["est_sum"] = [sum(est[0::2]), sum(est[1::2])]
+            if nt > 1:
+                host = tensors[0].view(torch.uint8).cpu().numpy().tobytes()
+                assert (est[0], est[1]) == D.ediff_cost(host, 4, a.chunk, lib=fr.lib)
+                assert per != a.chunk or cell["est_sum"] == out["cells"]["one_tensor"]["est_sum"]
+            cell["d2h_bytes"] = 8 * (size >> 14)
+            cell["h2d_bytes"] = 24 * n
+            cell["advise_stats"] = fr.advise_stats()
+        finally:
+            fr.close()
+        del tensors
+    del whole
+    torch.cuda.empty_cache()
+    advise_kernels(a, size, out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--advise", action="store_true")
     ap.add_argument("--ediff", action="store_true")
     ap.add_argument("--fingerprint", action="store_true")
     ap.add_argument("--probe", action="store_true")
@@ -1430,6 +1570,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.advise:
+        return advise_main(a)
     if a.ediff:
         if a.levels == "1,6,12":
             a.levels = "1,6"

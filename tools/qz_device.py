@@ -18,6 +18,8 @@ ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped d
 
 Element differences (include/qzstd_elemdiff.h, QZSTD_ELEM_DIFF, QZSTD_frontElemDiffStats): elem_diff / elem_sum, the rows and bindings of
 qzstd_hip_group_ediff and qzstd_hip_esum, DeviceFront.elem_diff_stats, and diff= on compress_tensors() / restore_tensors().
+The adviser (include/qzstd_ediffcost.h, QZSTD_frontAdviseDeviceBatch, QZSTD_frontAdviseStats): DeviceFront.advise / advise_raw / advise_stats,
+advise_tensors(), ediff_cost_of / ediff_cost / ediff_advised (the header's functions through the exports), qzstd_hip_ediff_cost's row and binding.
 
 torch is imported before the library is loaded, so that the process has ONE HIP runtime (the one torch brought)."""
 import ctypes as C
@@ -461,6 +463,16 @@ def bind(F):
     if hasattr(F, "QZSTD_frontElemDiffStats"):  # (absent from an older library)
         F.QZSTD_frontElemDiffStats.restype = None
         F.QZSTD_frontElemDiffStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontAdviseDeviceBatch"):  # (absent from an older library)
+        F.QZSTD_frontAdviseDeviceBatch.restype = C.c_size_t
+        F.QZSTD_frontAdviseDeviceBatch.argtypes = [C.c_void_p, C.POINTER(DeviceBuf), C.c_char_p, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                   C.POINTER(C.c_ulonglong)]
+        F.QZSTD_frontAdviseStats.restype = None
+        F.QZSTD_frontAdviseStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_ediffCostOf.restype = None
+        F.QZSTD_ediffCostOf.argtypes = [C.c_char_p, C.c_size_t, C.c_uint, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_ediffAdvisedOf.restype = C.c_int
+        F.QZSTD_ediffAdvisedOf.argtypes = [C.c_ulonglong, C.c_ulonglong]
     return F
 
 
@@ -540,6 +552,42 @@ def esum_tiles(n: int, k: int) -> int:
 def esum_scratch_bytes(tiles: int) -> int:
     """QZSTD_HIP_ESUM_SCRATCH_BYTES"""
     return tiles * 24
+
+
+class EdiffCostRow(C.Structure):
+    """qzstd_hip_ediff_cost_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32), ("tile0", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def bind_ediff_cost_kernel(L):
+    """qzstd_hip_ediff_cost on a loaded device layer (libqatseqprod, or tests/mock/mock_hip_ediff_cost.c built alone)"""
+    L.qzstd_hip_ediff_cost.restype = C.c_int
+    L.qzstd_hip_ediff_cost.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    return L
+
+
+def ediff_cost_of(data: bytes, k: int, lib=None) -> tuple:
+    """QZSTD_ediffCostOf: (P, D) of one chunk — the summed order-0 plane costs of its k-byte elements as they are and differenced
+    (include/qzstd_ediffcost.h's own function through the front-end library's export)"""
+    L = lib if lib is not None else bind(B.Front().lib)
+    s = (C.c_ulonglong * 2)()
+    L.QZSTD_ediffCostOf(bytes(data), len(data), k, s)
+    return int(s[0]), int(s[1])
+
+
+def ediff_cost(data: bytes, k: int, chunk: int, lib=None) -> tuple:
+    """(P, D) of a buffer: ediff_cost_of summed over its chunks, as QZSTD_frontAdviseDeviceBatch sums them"""
+    P = D = 0
+    for o in range(0, len(data), chunk):
+        p, d = ediff_cost_of(data[o:o + chunk], k, lib)
+        P, D = P + p, D + d
+    return P, D
+
+
+def ediff_advised(P: int, D: int, lib=None) -> bool:
+    """QZSTD_ediffAdvisedOf: the rule that flags a buffer"""
+    L = lib if lib is not None else bind(B.Front().lib)
+    return bool(L.QZSTD_ediffAdvisedOf(P, D))
 
 
 def bind_elemdiff(L):
@@ -994,6 +1042,31 @@ class DeviceFront:
         self.lib.QZSTD_frontFingerprintStats(self.f, st)
         return list(st)
 
+    def advise_raw(self, ptrs_and_sizes, elem_sizes=None, stream: int | None = None, null_advised: bool = False, want_est: bool = True):
+        """QZSTD_frontAdviseDeviceBatch -> (return value: the number of flagged buffers or ERROR, advised as a list of ints — 0x07 where
+        the call wrote nothing —, est as [(P, D), ...] or None); elem_sizes: one of 0 (the front's setting), 1, 2, 4, 8 per buffer, or None"""
+        bufs, nb, _ = self.batch(ptrs_and_sizes)
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        adv = C.create_string_buffer(b"\x07" * max(nb, 1), max(nb, 1))
+        est = (C.c_ulonglong * max(2 * nb, 1))() if want_est else None
+        r = self.lib.QZSTD_frontAdviseDeviceBatch(self.f, bufs, es, nb, C.c_void_p(stream or None), None if null_advised else adv, est)
+        return r, list(adv.raw[:nb]), ([(int(est[2 * i]), int(est[2 * i + 1])) for i in range(nb)] if want_est else None)
+
+    def advise(self, ptrs_and_sizes, elem_sizes=None, stream: int | None = None):
+        """-> (the elemSizes array to pass to the Typed compress and restore calls: each buffer's element size, with ELEM_DIFF where element
+        differences are advised; [(P, D), ...]: the estimated order-0 sizes without and with differences).  Raises when the call fails"""
+        r, adv, est = self.advise_raw(ptrs_and_sizes, elem_sizes, stream)
+        if r == ERROR:
+            raise RuntimeError("QZSTD_frontAdviseDeviceBatch failed")
+        assert r == sum(1 for a in adv if a & ELEM_DIFF)
+        return adv, est
+
+    def advise_stats(self) -> list:
+        """[0] buffers advised on, [1] of them flagged, [2] bytes read on the device, [3] qzstd_hip_ediff_cost launches"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontAdviseStats(self.f, st)
+        return list(st)
+
     def restore_stats(self) -> list:
         """[0] frames decoded, [1] bytes of content, [2] bytes copied host->device, [3] ungroup launches"""
         st = (C.c_ulonglong * 4)()
@@ -1129,6 +1202,16 @@ def check_tensors(front: DeviceFront, tensors, fingerprints_per_tensor, stream=N
     [(tensor, frame), ...] for the chunks that differ; []: the load is good"""
     bufs, handle = _tensor_bufs("check_tensors", tensors, stream)
     return front.check(bufs, fingerprints_per_tensor, handle) if bufs else []
+
+
+def advise_tensors(front: DeviceFront, tensors, stream=None) -> list:
+    """per tensor whether element differences are advised (ONE QZSTD_frontAdviseDeviceBatch call over the tensors' own bytes, each with its
+    dtype's element size): the list to pass as diff= to compress_tensors() / restore_tensors() with group="dtype", and to keep with the frames"""
+    bufs, handle = _tensor_bufs("advise_tensors", tensors, stream)
+    if not bufs:
+        return []
+    adv, _ = front.advise(bufs, [element_group(t) for t in tensors], handle)
+    return [bool(a & ELEM_DIFF) for a in adv]
 
 
 def restore_slices(front: DeviceFront, frames, buf_sizes, elems, slices, stream=None) -> int:
