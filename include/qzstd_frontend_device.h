@@ -295,6 +295,50 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
 /* since creation: [0] non-empty slices restored, [1] bytes written to destinations, [2] frames decoded for them, [3] rows launched */
 void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4]);
 
+/* Source slices: QZSTD_frontCompressDeviceBatchDelta for buffers that are NOT contiguous in device memory — a column view W[:, a:b] of a fused
+ * matrix, a pitched allocation, a parameter kept in another order than the checkpoint stores, scattered cache pages, a tensor loaded as slices
+ * by QZSTD_frontRestoreDeviceSlices and saved again — without the `.contiguous()` copy, a temporary of the buffers' size.  Logical buffer i has
+ * bufSizes[i] bytes; the non-empty slices of a buffer, in order, tile [0, bufSizes[i]) exactly, each with the device address of its bytes.
+ * A buffer has a base when its slices carry d_base (the same slice of the base, which may be d_src itself); all of them do, or none.
+ *
+ * Everything about the result is QZSTD_frontCompressDeviceBatchDelta's for the same bytes held contiguously: frames are cut every chunkSize
+ * bytes of the LOGICAL buffer, the frame count, firstFrame, strides and QZSTD_frontDeviceBatchFrames of the sizes are the same, and EVERY
+ * FRAME IS BYTE FOR BYTE the frame that call returns with the same elemSizes, bases and front settings (byte group, checksum, plane probe,
+ * delta skip); `stream` (it orders the last writer of every slice and base) and blocking are as there.  The frame format knows nothing of
+ * where a chunk's bytes came from, so restore, slices, verify and fingerprints read these frames as before and the caller keeps nothing new.
+ *
+ * A frame that lies inside one slice is handled as a frame of a contiguous buffer is, so a call in which every frame does — one slice per
+ * buffer in particular — queues the launches of the Delta call.  A part that holds a frame made of several slices is always staged, by ONE
+ * qzstd_hip_group_pieces launch over all its rows: the frame is assembled in the stage from its pieces, XORed with their bases and grouped
+ * in the same pass.  Where such a frame's bytes are needed on the host (a block the matcher failed) they come back with one copy per piece,
+ * the base's likewise; delta skip compares such a frame piece by piece in the same single launch.  QZSTD_frontDeviceStats,
+ * ...ByteGroupStats, ...DeltaStats, ...DeltaSkipStats, ...ChecksumStats and ...PlaneProbeStats count this call as they count the Delta call.
+ *
+ * (size_t)-1 before anything is queued: everything the Delta call refuses that applies here; bufSizes or slices NULL with a count above 0; a
+ * slice with buf >= nBufs; slices out of order; a gap, an overlap, or an end past its buffer; a buffer with based and unbased slices; a NULL
+ * d_src with size > 0; a source or base whose first or last byte is not device memory, or that lies on another device than the rest
+ * (consecutive slices that follow each other in memory are looked up as ONE range, as in QZSTD_frontRestoreDeviceSlices); an element size
+ * with QZSTD_ELEM_DIFF — the differencing gather does not assemble pieces: out of scope here, make such a buffer contiguous and use the
+ * Typed call; and, for a call with a frame made of several slices, a device layer without qzstd_hip_group_pieces (such a layer serves a
+ * call without such a frame, and every other call, as before).
+ * Look-ups: where the device layer tells the extent of the allocation that holds an address (qzstd_hip_pointer_extent) and the extent's own
+ * last byte looks up as memory of the same device, a range that lies inside the allocation looked up last is accepted without a look-up of
+ * its own — a view's 10^5 rows cost one — so "first or last byte" becomes "inside an allocation of the device" for such ranges.  That
+ * is as good as the runtime's answer: an address range that is reserved and only partly mapped fails the last-byte test and is looked up
+ * range by range, but a reservation with an unmapped hole in its MIDDLE would pass, and has not been tested. */
+typedef struct {
+    size_t buf;          /* index into bufSizes: the logical buffer this slice belongs to */
+    size_t offset, size; /* bytes [offset, offset + size) of that buffer; size may be 0 */
+    const void *d_src;   /* device address of those bytes, any alignment */
+    const void *d_base;  /* NULL, or the device address of the same slice of the buffer's base; may equal d_src */
+} QZSTD_DeviceSrcSlice;
+size_t QZSTD_frontCompressDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs,
+                                       const QZSTD_DeviceSrcSlice *slices, size_t nSlices, void *stream, void *dst, size_t dstCapacity,
+                                       size_t *frameSizes, size_t *firstFrame);
+/* since creation, of the calls that succeeded: [0] non-empty slices, [1] their bytes, [2] frames assembled from more than one piece,
+ * [3] qzstd_hip_group_pieces launches (one per part that holds such a frame) */
+void QZSTD_frontSrcSliceStats(QZSTD_Front *f, unsigned long long stats[4]);
+
 /* Verify: do the frames just written reproduce the tensors that are on the device NOW — asked before the previous checkpoint is dropped?  A
  * delta frame is only as good as the base it is applied to and the element size it is ungrouped with, and neither is in the frame; a content
  * checksum covers the grouped delta, not the tensor.  A mistake in the caller's bookkeeping (another base, another element size, frames in

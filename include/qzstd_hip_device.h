@@ -2,7 +2,8 @@
  * qzstd_hip_device.h — the device layer's entry points for DEVICE-RESIDENT input (QZSTD_frontCompressDevice in
  * qzstd_frontend_device.h): pointer look-up, events on a caller's stream, a strided device copy, the compaction kernel and the gather kernel
  * (QZSTD_frontCompressDeviceBatch), the byte-grouping gather and its inverse, the ungrouping scatter (QZSTD_frontRestoreDeviceBatchTyped),
- * both also with a base XORed in (the ...Delta calls), the scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
+ * both also with a base XORed in (the ...Delta calls), the gather also for rows assembled from pieces (QZSTD_frontCompressDeviceSlices), the
+ * scatter also for windows of the staged frames (QZSTD_frontRestoreDeviceSlices),
  * the comparison of staged frames with live bytes (QZSTD_frontVerifyDeviceBatch), the comparison of rows with their bases (QZSTD_frontSetDeltaSkip),
  * the content-checksum kernel (QZSTD_frontSetChecksum), the byte histograms' cost per block (QZSTD_frontSetPlaneProbe), the tile
  * digests of the tensor fingerprints (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch), and the grouping gather with element
@@ -23,6 +24,12 @@ extern "C" {
 /* the library's device index of a pointer into DEVICE memory (hipPointerGetAttributes); < 0 for host, pinned-host, managed or
  * unknown memory and for a device the library does not use.  Starts no work on any GPU. */
 int qzstd_hip_pointer_device(const void *p);
+/* qzstd_hip_pointer_device, and the ALLOCATION that holds p: every byte of [*lo, *lo + *size) is memory of the returned device.  *size is 0
+ * (and *lo NULL) where p is no device memory or the runtime does not tell: the caller then looks addresses up one by one.  A caller with
+ * 10^5 ranges inside one tensor looks the tensor up once (QZSTD_frontCompressDeviceSlices).  The extent is the runtime's answer
+ * (hipMemGetAddressRange): for an address range that is reserved and mapped piece by piece it may name more than is mapped — a caller
+ * checks the extent's last byte with qzstd_hip_pointer_device before it relies on it.  Starts no work on any GPU. */
+int qzstd_hip_pointer_extent(const void *p, const void **lo, size_t *size);
 /* events, so that the library's streams wait for work a caller queued on a stream of its own (NULL = the default stream) */
 void *qzstd_hip_event_create(int device);
 void qzstd_hip_event_destroy(int device, void *event);
@@ -178,6 +185,49 @@ typedef struct {
 } qzstd_hip_ungroup_xor_row_t;
 int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_xor_row_t *d_rows,
                           const void *d_stage, size_t stageBytes);
+
+/*
+ * Byte-grouping gather from PIECES (QZSTD_frontCompressDeviceSlices): qzstd_hip_group_xor for rows whose content is assembled from pieces that
+ * lie anywhere in device memory — a column view, a pitched allocation, scattered pages.  A row owns pieces[piece0 .. piece0 + nPieces); for
+ * piece p of the row and i < p.len, c[p.off + i] = src_p[i] ^ base_p[i] (no XOR when base == 0); the stage receives the byte-grouped layout
+ * of c[0 .. len) for k = elem at dstOff, and `pad` zero bytes follow.  A row with one piece lands exactly as qzstd_hip_group_xor lands it.
+ *
+ * The guarantees are qzstd_hip_group's, for pieces: one aligned 16-byte store per stage word, by one lane; no atomics and no
+ * read-modify-write of the stage; stage bytes between rows are left alone.  src and base are read only with aligned 16-byte loads of words
+ * that overlap THAT PIECE's [src, src + len) or [base, base + len), and of no other word — a piece may end at the last byte of an allocation,
+ * and no load is justified by the neighbouring piece.  src == base is allowed; pieces may be one byte long, may begin and end inside an
+ * element, and sixteen of them may feed one lane's 16 bytes.  Neither sources nor bases are written.
+ *
+ * Work is divided as in qzstd_hip_group: a workgroup per 16 KiB tile of one row's content across all planes, the row found by a binary search.
+ * One lane then narrows the row's pieces to those that hold the tile's first and last byte (two binary searches over `off`); a lane whose 16
+ * content bytes lie inside one piece takes them with one fetch per side, a lane whose bytes straddle pieces assembles them piece by piece,
+ * every sub-fetch under the read rule above, and the single bytes that a stage word's owner fetches itself (the next element range, the next
+ * plane, the tail) go through the same lookup over all of the row's pieces.  The table is read from device memory, not cached in LDS.
+ *
+ * `rows` and `pieces` are HOST memory (pinned, for the uploads to be asynchronous) and must stay unchanged until the stream has passed the
+ * call; the launcher checks them and uploads them to d_rows and d_pieces, device scratch of nRows and nPieces entries.  Refused (< 0) before
+ * anything is queued: everything qzstd_hip_group_xor refuses (the null source is a piece's), a null pieces or d_pieces with nPieces > 0, a
+ * piece0 + nPieces past the table, a piece with len == 0 or a null src, pieces of a row that do not tile [0, len) exactly in ascending
+ * order (so nPieces == 0 only for len == 0).  No value of a piece's `base` is refused.  nRows == 0: nothing happens.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t src;  /* device address of the piece's first byte, any alignment */
+    uint64_t base; /* device address of `len` bytes XORed in, any alignment, also another one mod 16 than src; 0 = none */
+    uint32_t off;  /* the piece's first byte in its row's content c[] */
+    uint32_t len;  /* bytes, > 0 */
+} qzstd_hip_group_piece_t;
+typedef struct {
+    uint64_t dstOff;   /* byte offset in d_stage, a multiple of 16 */
+    uint32_t len;      /* content bytes, may be 0 */
+    uint32_t pad;      /* zero bytes written behind them; len + pad is a multiple of 16 */
+    uint32_t elem;     /* 1, 2, 4 or 8 */
+    uint32_t piece0;   /* the row's first piece */
+    uint32_t nPieces;  /* its pieces tile [0, len) exactly, ascending, none empty; 0 only for len == 0 */
+    uint32_t reserved; /* 0 */
+} qzstd_hip_group_pieces_row_t;
+int qzstd_hip_group_pieces(int device, void *stream, const qzstd_hip_group_pieces_row_t *rows, uint32_t nRows,
+                           qzstd_hip_group_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                           qzstd_hip_group_piece_t *d_pieces, void *d_stage, size_t stageBytes);
 
 /*
  * Windowed ungrouping scatter (QZSTD_frontRestoreDeviceSlices): qzstd_hip_ungroup_xor for a WINDOW of a staged frame.  The frame lies at

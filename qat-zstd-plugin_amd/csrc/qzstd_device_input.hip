@@ -1,7 +1,8 @@
 /*
  * qzstd_device_input.hip — the kernels for input that already lives in device memory, and the part of include/qzstd_hip_device.h that
  * launches them: compaction of a launch's sequences and literals into one arena, the gather of rows into a stage, the byte-grouping
- * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the scatter also for
+ * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the gather also for
+ * rows assembled from pieces (source slices), the scatter also for
  * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), the XXH64 content checksum, the plane cost (plane probe), the tile digests of the tensor fingerprints, and the grouping gather with element differences and the element sum (integer columns).  They use nothing of the match-finder
  * (qzstd_kernels.hip).
  */
@@ -635,6 +636,234 @@ extern "C" int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_gro
     hipLaunchKernelGGL(qzstd_group_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_xor_kernel");
+    return 0;
+}
+
+/* ---- the same for rows whose content is assembled from pieces (qzstd_hip_group_pieces).  A kernel of its own, as qzstd_group_xor_kernel is:
+ * the two above stay what they were.  group_shift, group_split, group_fetch and group_byte_at are shared; what is new is the way from a
+ * content offset to a piece and an address.  The piece table is not cached in LDS: a tile of one-byte pieces has 16384 of them (384 KiB),
+ * so a cache could only hold a prefix and would need a second path behind it; instead the workgroup narrows the table to the tile's pieces
+ * once, and a lane's search runs over that range — no step at all for a tile inside one piece, one or two for 8 KiB pieces, and the
+ * entries it touches are the same few lines for the whole wave. */
+namespace {
+/* the last piece of [lo, hi] whose off is at or before c (pieces ascend and tile the row: pieces[lo].off <= c) */
+__device__ inline uint32_t pieces_find(const qzstd_hip_group_piece_t *__restrict__ pieces, uint32_t lo, uint32_t hi, uint32_t c)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (pieces[mid].off <= c) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+/* bytes [0, m) of {t1, t0} to bytes [at, at + m) of {o1, o0}; at + m <= 16, m >= 1; what lies behind byte m of t is dropped */
+__device__ inline void pieces_place(uint64_t t0, uint64_t t1, uint32_t m, uint32_t at, uint64_t *o0, uint64_t *o1)
+{
+    if (m < 8u) { t0 &= (1ull << (m * 8u)) - 1ull; t1 = 0ull; }
+    else if (m < 16u) t1 = m > 8u ? t1 & ((1ull << ((m - 8u) * 8u)) - 1ull) : 0ull;
+    const uint32_t bits = (at & 7u) * 8u;
+    if (at & 8u) { *o1 |= t0 << bits; }
+    else {
+        *o0 |= t0 << bits;
+        *o1 |= bits ? (t1 << bits) | (t0 >> (64u - bits)) : t1;
+    }
+}
+
+/* the `valid` content bytes from content offset c on (src ^ base), p the piece that holds c: one group_fetch per side when they lie inside
+ * p, else piece by piece — every sub-fetch asks for exactly the bytes of ITS piece, so group_fetch loads only words that overlap that
+ * piece's [src, src + len) and [base, base + len) */
+__device__ inline void pieces_fetch(const qzstd_hip_group_piece_t *__restrict__ pieces, uint32_t p, uint32_t c, uint32_t valid, uint64_t *o0,
+                                    uint64_t *o1)
+{
+    qzstd_hip_group_piece_t pc = pieces[p];
+    uint32_t in = c - pc.off;
+    if (valid <= pc.len - in) {
+        group_fetch(pc.src + in, valid, o0, o1);
+        if (pc.base) {
+            uint64_t b0, b1;
+            group_fetch(pc.base + in, valid, &b0, &b1);
+            *o0 ^= b0;
+            *o1 ^= b1;
+        }
+        return;
+    }
+    *o0 = 0ull;
+    *o1 = 0ull;
+    for (uint32_t at = 0;;) {
+        const uint32_t m = valid - at < pc.len - in ? valid - at : pc.len - in;
+        uint64_t t0, t1;
+        group_fetch(pc.src + in, m, &t0, &t1);
+        if (pc.base) {
+            uint64_t b0, b1;
+            group_fetch(pc.base + in, m, &b0, &b1);
+            t0 ^= b0;
+            t1 ^= b1;
+        }
+        pieces_place(t0, t1, m, at, o0, o1);
+        at += m;
+        if (at >= valid) break;
+        pc = pieces[++p]; /* (the pieces tile the row: the next one begins where this one ends) */
+        in = 0u;
+    }
+}
+
+/* group_xor_byte through the lookup: byte p of the row's grouped layout (0 from len on); the search runs over all of the row's pieces,
+ * for the byte may lie in another tile */
+__device__ inline uint64_t pieces_byte(const qzstd_hip_group_pieces_row_t &row, const qzstd_hip_group_piece_t *__restrict__ pieces, uint32_t n,
+                                       uint32_t kLog, uint64_t p)
+{
+    if (p >= row.len) return 0ull;
+    uint32_t s = (uint32_t)p; /* (p < len: 32 bits) */
+    if (p < ((uint64_t)n << kLog)) {
+        const uint32_t j = (uint32_t)p / n;
+        s = (((uint32_t)p - j * n) << kLog) + j;
+    }
+    const qzstd_hip_group_piece_t pc = pieces[pieces_find(pieces, row.piece0, row.piece0 + row.nPieces - 1u, s)];
+    const uint64_t b = group_byte_at(pc.src + (s - pc.off));
+    return pc.base ? b ^ group_byte_at(pc.base + (s - pc.off)) : b;
+}
+
+/* group_patch over pieces_byte */
+__device__ inline void pieces_patch(const qzstd_hip_group_pieces_row_t &row, const qzstd_hip_group_piece_t *__restrict__ pieces, uint32_t n,
+                                    uint32_t kLog, uint64_t o, uint32_t from, uint64_t *o0, uint64_t *o1)
+{
+    *o1 = from > 8u ? *o1 & ((1ull << ((from - 8u) * 8u)) - 1ull) : 0ull;
+    if (from < 8u) *o0 = from ? *o0 & ((1ull << (from * 8u)) - 1ull) : 0ull;
+    if (o + from >= row.len) return; /* padding only */
+    for (uint32_t i = from; i < 16u; i++) {
+        const uint64_t b = pieces_byte(row, pieces, n, kLog, o + i);
+        if (i < 8u) *o0 |= b << (i * 8u); else *o1 |= b << ((i - 8u) * 8u);
+    }
+}
+
+/* qzstd_group_xor_kernel's tiles and phases.  Before A, one lane finds the pieces that hold the tile's first and last content byte; in A a
+ * lane finds the piece of its first byte among them and fetches through pieces_fetch: B sees a tile of the assembled src ^ base. */
+__global__ __launch_bounds__(kGroupT) void qzstd_group_pieces_kernel(const qzstd_hip_group_pieces_row_t *__restrict__ rows, uint32_t nRows,
+                                                                      const qzstd_hip_group_piece_t *__restrict__ pieces, uint64_t firstTile,
+                                                                      uint4 *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
+    __shared__ uint32_t which, pieceLo, pieceHi;
+    const uint64_t v = firstTile + blockIdx.x;
+    if (threadIdx.x == 0) {
+        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+        const qzstd_hip_group_pieces_row_t &rw = rows[lo];
+        const uint64_t t = v - ((rw.dstOff >> kGroupTileLog) + lo);
+        const uint32_t whole = rw.len & ~(rw.elem - 1u); /* the content bytes that are elements: tiles cover [0, whole) */
+        pieceLo = pieceHi = rw.piece0;
+        if ((t << kGroupTileLog) < whole) {
+            const uint32_t c0 = (uint32_t)t << kGroupTileLog, c1 = whole - c0 < kGroupTile ? whole - 1u : c0 + kGroupTile - 1u;
+            pieceLo = pieces_find(pieces, rw.piece0, rw.piece0 + rw.nPieces - 1u, c0);
+            pieceHi = pieces_find(pieces, pieceLo, rw.piece0 + rw.nPieces - 1u, c1);
+        }
+    }
+    __syncthreads();
+    const uint32_t r = which;
+    const qzstd_hip_group_pieces_row_t row = rows[r];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kGroupTile >> kLog;
+    const uint64_t ext = (uint64_t)row.len + row.pad;
+    const uint64_t tiles = n ? ((uint64_t)n + tileMax - 1u) / tileMax : (ext ? 1ull : 0ull);
+    const uint64_t t = v - ((row.dstOff >> kGroupTileLog) + r);
+    if (t >= tiles) return; /* (the whole workgroup) */
+    const uint32_t e0 = (uint32_t)t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint32_t tileBytes = tileElems << kLog;
+    const uint32_t cTile = e0 << kLog; /* the tile's first content byte */
+    const uint32_t pLo = pieceLo, pHi = pieceHi;
+
+    for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kGroupT) {
+        const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+        const uint32_t c = cTile + w * 16u;
+        uint64_t o0, o1;
+        pieces_fetch(pieces, pLo == pHi ? pLo : pieces_find(pieces, pLo, pHi, c), c, valid, &o0, &o1);
+        switch (kLog) {
+        case 0u: group_split<1u>(o0, o1, lds, w); break;
+        case 1u: group_split<2u>(o0, o1, lds, w); break;
+        case 2u: group_split<4u>(o0, o1, lds, w); break;
+        default: group_split<8u>(o0, o1, lds, w); break;
+        }
+    }
+    __syncthreads();
+
+    uint4 *out = stage + (row.dstOff >> 4);
+    for (uint32_t j = 0; j < (1u << kLog); j++) {
+        const uint64_t planeAt = (uint64_t)j * n + e0; /* row offset of the tile's first element in plane j */
+        const uint32_t aj = (uint32_t)planeAt & 15u;
+        const uint8_t *plane = lds + j * (tileMax + kGroupSlack);
+        /* c: offset from the stage word that holds planeAt; that word itself belongs here only when it starts at planeAt */
+        for (uint32_t c = (aj ? 16u : 0u) + threadIdx.x * 16u; c < aj + tileElems; c += kGroupT * 16u) {
+            const uint32_t x0 = c - aj, q = x0 & ~15u, sh = x0 & 15u;
+            const uint32_t valid = tileElems - x0 < 16u ? tileElems - x0 : 16u;
+            const uint64_t o = planeAt + x0;
+            const uint4 l = *reinterpret_cast<const uint4 *>(plane + q);
+            uint4 h = make_uint4(0u, 0u, 0u, 0u);
+            if (sh) h = *reinterpret_cast<const uint4 *>(plane + q + 16u);
+            uint64_t o0, o1;
+            group_shift(l, h, sh, &o0, &o1);
+            if (valid < 16u) pieces_patch(row, pieces, n, kLog, o, valid, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+    if (t + 1u == tiles) {
+        const uint64_t tailAt = ((((uint64_t)n << kLog) + 15u) & ~(uint64_t)15u);
+        for (uint64_t o = tailAt + threadIdx.x * 16u; o < ext; o += kGroupT * 16u) {
+            uint64_t o0 = 0, o1 = 0;
+            pieces_patch(row, pieces, n, kLog, o, 0u, &o0, &o1);
+            out[o >> 4] = make_uint4((uint32_t)o0, (uint32_t)(o0 >> 32), (uint32_t)o1, (uint32_t)(o1 >> 32));
+        }
+    }
+}
+} // namespace
+
+/* (qzstd_hip_group_xor's checks and launch geometry, row for row, and the piece table's: every row's pieces tile its content) */
+extern "C" int qzstd_hip_group_pieces(int device, void *stream, const qzstd_hip_group_pieces_row_t *rows, uint32_t nRows,
+                                      qzstd_hip_group_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                                      qzstd_hip_group_piece_t *d_pieces, void *d_stage, size_t stageBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_pieces: null pointer or stage not 16-byte aligned");
+    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_group_pieces: null piece table");
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_group_pieces_row_t &r = rows[i];
+        const uint64_t ext = (uint64_t)r.len + r.pad;
+        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
+            return fail_msg("qzstd_hip_group_pieces: elem not 1, 2, 4 or 8, or reserved not 0");
+        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_pieces: dstOff or len + pad not a multiple of 16");
+        if (r.dstOff < end) return fail_msg("qzstd_hip_group_pieces: rows overlap in the stage or are not in ascending order");
+        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_pieces: a row ends past stageBytes");
+        if ((uint64_t)r.piece0 + r.nPieces > nPieces) return fail_msg("qzstd_hip_group_pieces: a row's pieces end past the table");
+        uint64_t at = 0;
+        for (uint32_t p = r.piece0; p < r.piece0 + r.nPieces; p++) {
+            if (!pieces[p].len || !pieces[p].src) return fail_msg("qzstd_hip_group_pieces: an empty piece or a null source");
+            if (pieces[p].off != at) return fail_msg("qzstd_hip_group_pieces: a row's pieces do not tile its content in ascending order");
+            at += pieces[p].len;
+        }
+        if (at != r.len) return fail_msg("qzstd_hip_group_pieces: a row's pieces do not tile its content in ascending order");
+        end = r.dstOff + ext;
+        if (ext) {
+            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
+            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_pieces: stage span too large");
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
+    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_pieces: too many tiles");
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group pieces rows)");
+    if (nPieces)
+        QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
+                 "hipMemcpyAsync H2D (group pieces table)");
+    hipLaunchKernelGGL(qzstd_group_pieces_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
+                       firstTile, static_cast<uint4 *>(d_stage));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_group_pieces_kernel");
     return 0;
 }
 

@@ -340,6 +340,20 @@ int qzstd_hip_pointer_device(const void *p)
     return -1;
 }
 
+int qzstd_hip_pointer_extent(const void *p, const void **lo, size_t *size)
+{
+    if (lo) *lo = nullptr;
+    if (size) *size = 0;
+    const int d = qzstd_hip_pointer_device(p);
+    if (d < 0 || !lo || !size) return d;
+    hipDeviceptr_t b = nullptr;
+    size_t n = 0;
+    if (hipMemGetAddressRange(&b, &n, (hipDeviceptr_t)const_cast<void *>(p)) != hipSuccess) { (void)hipGetLastError(); return d; }
+    const char *first = static_cast<const char *>((const void *)b), *at = static_cast<const char *>(p);
+    if (b && at >= first && (size_t)(at - first) < n) { *lo = (const void *)b; *size = n; }
+    return d;
+}
+
 void *qzstd_hip_event_create(int device)
 {
     hipEvent_t e = nullptr;

@@ -112,6 +112,7 @@ struct QZSTD_Front_s {
     unsigned long long verifyStats[4]; /* QZSTD_frontVerifyDeviceBatch: frames compared, of them differing, bytes compared, launches */
     unsigned long long fpStats[4];     /* the fingerprint calls: frames fingerprinted, bytes read on the device, launches, frames a check found differing */
     unsigned long long adviseStats[4]; /* QZSTD_frontAdviseDeviceBatch: buffers advised on, buffers flagged, bytes read on the device, launches */
+    unsigned long long srcSliceStats[4]; /* QZSTD_frontCompressDeviceSlices: slices, their bytes, frames of more than one piece, qzstd_hip_group_pieces launches */
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -443,8 +444,13 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * block descriptor over the stage, one word per block back with the compaction headers: the block's order-0 cost (include/qzstd_planecost.h).
  * A frame with a block that QZSTD_planeIsRaw predicts raw is assembled by qfAssembleFrame — the library writes the Raw_Blocks, libzstd codes
  * the remaining blocks once — and never entropy-coded twice.  With the setting off nothing is launched and every frame is what it was.
+ *
+ * Source slices (QZSTD_frontCompressDeviceSlices, qzstd_srcslices.c): the buffers' bytes lie in pieces anywhere in device memory.  The
+ * per-frame table says where every frame lies (src, base): a frame inside one piece is a frame like any other, a frame across several has
+ * no address, makes its part one that qzstd_hip_group_pieces stages, and is read piece by piece wherever its bytes are needed on the host.
  */
 extern int qzstd_hip_pointer_device(const void *p) __attribute__((weak));
+extern int qzstd_hip_pointer_extent(const void *p, const void **lo, size_t *size) __attribute__((weak));
 extern void *qzstd_hip_event_create(int device) __attribute__((weak));
 extern void qzstd_hip_event_destroy(int device, void *event) __attribute__((weak));
 extern int qzstd_hip_event_record(int device, void *event, void *stream) __attribute__((weak));
@@ -463,6 +469,9 @@ extern int qzstd_hip_group_ediff(int device, void *stream, const qzstd_hip_group
                                  qzstd_hip_group_ediff_row_t *d_rows, void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows, qzstd_hip_group_xor_row_t *d_rows,
                                void *d_stage, size_t stageBytes) __attribute__((weak));
+extern int qzstd_hip_group_pieces(int device, void *stream, const qzstd_hip_group_pieces_row_t *rows, uint32_t nRows,
+                                  qzstd_hip_group_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                                  qzstd_hip_group_piece_t *d_pieces, void *d_stage, size_t stageBytes) __attribute__((weak));
 extern int qzstd_hip_xxh64(int device, void *stream, const void *d_base, const qzstd_hip_hash_row_t *rows, uint32_t nRows,
                            qzstd_hip_hash_row_t *d_rows, uint64_t *d_out) __attribute__((weak));
 extern int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows,
@@ -509,6 +518,10 @@ struct QF_DevSlot_s {
     void *dXorRows; size_t dXorRowsCap;
     qzstd_hip_group_ediff_row_t *hEdiffRows; size_t hEdiffRowsCap; /* a part with differenced frames: qzstd_hip_group_ediff's rows, for those frames only */
     void *dEdiffRows; size_t dEdiffRowsCap;
+    qzstd_hip_group_pieces_row_t *hPieceRows; size_t hPieceRowsCap; /* a part with a frame of several pieces: qzstd_hip_group_pieces's rows instead, */
+    void *dPieceRows; size_t dPieceRowsCap;
+    qzstd_hip_group_piece_t *hPieces; size_t hPiecesCap;            /* and their piece table */
+    void *dPieces; size_t dPiecesCap;
     size_t *ends; size_t endsCap; /* the block ends of the frame whose descriptors are being written */
     qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
     void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
@@ -529,9 +542,28 @@ struct QF_DevSlot_s {
     const unsigned char *hLit; size_t litTotal; /* the arena's literal bytes, in hArena */
 };
 
+/* the source slices of a QZSTD_frontCompressDeviceSlices call (qzstd_srcslices.c): the non-empty ones, buffer after buffer, ascending and
+ * without gaps inside a buffer; NULL in the job of every other call */
+typedef struct {
+    size_t off, size;               /* bytes [off, off + size) of the buffer */
+    const unsigned char *src, *base; /* where they lie; base NULL: the buffer has none */
+} QF_SrcPiece;
+typedef struct {
+    const QF_SrcPiece *pieces;
+    const size_t *first; /* nBufs + 1 entries: buffer i owns pieces [first[i], first[i + 1]) */
+    size_t total;        /* bytes of all buffers */
+    int dev;             /* the device all of them lie on (-1: there are none) */
+    int multi;           /* a frame of the call is made of more than one piece */
+    unsigned long long *counts; /* the call's own: [0] frames staged from more than one piece, [1] qzstd_hip_group_pieces launches */
+} QF_SrcMap;
+
 /* one frame of a device job (the per-frame table, built once per call): where its bytes lie and which blocks of its part are its own */
 typedef struct {
     size_t off, len; /* offset in its buffer, length (chunkSize, or what is left of the buffer) */
+    const unsigned char *src, *base; /* the frame's first byte and its base chunk's (NULL: no base); both NULL for a frame of several pieces */
+    size_t p0;       /* a call with source slices: the first piece of the map that holds bytes of the frame, */
+    uint32_t np;     /* and how many do (1: the frame lies at src as in every other call); 0 in every other call */
+    uint32_t based;  /* the frame's buffer has a base: its content is chunk ^ base chunk */
     size_t b0;       /* first block in its part */
     size_t idx;      /* its index in the call: dst + idx * stride, frameSizes[idx] (the table leaves out the frames a delta skip found equal) */
     uint32_t buf;    /* owning buffer */
@@ -547,12 +579,12 @@ typedef struct {
     int grouped; /* a frame with k > 1 among them: staged by qzstd_hip_group, never read in place */
     int delta;   /* a frame of a buffer with a base among them: staged by qzstd_hip_group_xor (all its rows), never read in place */
     int diff;    /* a differenced frame among them: those are staged by qzstd_hip_group_ediff, the others by the part's own launch; never read in place */
+    int pieces;  /* a frame of several pieces among them: staged by qzstd_hip_group_pieces (all its rows), never read in place */
 } QF_DevRange;
 
 struct QF_DevPart_s {
-    const QZSTD_DeviceBuf *bufs; /* the caller's buffers (the raw-bytes path reads a frame from its own) */
-    const QZSTD_DeviceBuf *bases; /* the buffers' bases (d_ptr NULL: none), or NULL for a call without any */
-    const QF_DevFrame *frames;   /* the job's table */
+    const QF_SrcMap *sm;         /* the call's source slices, or NULL (the raw-bytes path reads a frame of several pieces piece by piece) */
+    const QF_DevFrame *frames;   /* the job's table (the raw-bytes path reads a frame from where its entry says) */
     size_t f0, f1;               /* frames of the job */
     size_t nb;                   /* blocks */
     const QF_DevSlot *slot;
@@ -565,7 +597,7 @@ struct QF_DevPart_s {
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
     void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
-                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows };
+                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows, s->dPieceRows, s->dPieces };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
@@ -573,6 +605,8 @@ static void qfSlotFree(int dev, QF_DevSlot *s)
     if (s->hGroupRows) qzstd_hip_host_free(s->hGroupRows);
     if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
     if (s->hEdiffRows) qzstd_hip_host_free(s->hEdiffRows);
+    if (s->hPieceRows) qzstd_hip_host_free(s->hPieceRows);
+    if (s->hPieces) qzstd_hip_host_free(s->hPieces);
     free(s->ends);
     if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
     if (s->hHash) qzstd_hip_host_free(s->hHash);
@@ -616,8 +650,7 @@ static int qfGrowH(void **p, size_t *cap, size_t need)
 
 typedef struct {
     QZSTD_Front *f;
-    const QZSTD_DeviceBuf *bufs;
-    const QZSTD_DeviceBuf *bases; /* NULL: no buffer of the call has a base */
+    const QF_SrcMap *sm;       /* NULL: the buffers are contiguous (every call but QZSTD_frontCompressDeviceSlices) */
     const QF_DevFrame *frames; /* the per-frame table: frame c of the job */
     const QF_DevRange *parts;
     size_t nParts, blk;        /* blk: the launches' largest block, min(chunkSize, 128 KiB) */
@@ -628,6 +661,8 @@ typedef struct {
 } QF_DevJob;
 
 static size_t qfPad16(size_t n) { return (n + 15u) & ~(size_t)15u; }
+static int qfStagePieces(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, size_t stageBytes); /* qzstd_srcslices.c */
+static int qfFramePiecesD2H(const QF_DevPart *pt, void *stream, const QF_DevFrame *fm, unsigned char *to, int base);
 
 /* stages a part's frames at 16-aligned offsets of the slot's stage, zero bytes behind each (the matcher reads 16-aligned blocks and up to
  * the next multiple of 16 past each).  One gather launch when the device layer has it; else — a run of one buffer's chunks only — a memset
@@ -650,7 +685,7 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
             qzstd_hip_group_ediff_row_t *r = &s->hEdiffRows[m];
             if (!f0[c].diff) continue;
             if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->src = (uint64_t)(uintptr_t)f0[c].src;
             r->dstOff = so;
             r->len = (uint32_t)f0[c].len;
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
@@ -663,6 +698,7 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         __atomic_fetch_add(&j->f->ediffStats[0], (unsigned long long)m, __ATOMIC_RELAXED);
         if (m == nf) return 0;
     }
+    if (pr->pieces) return qfStagePieces(j, s, pr, stageBytes);
     if (pr->delta) {
         /* the grouping gather's rows with each frame's base chunk (0: the frame's buffer has none): src ^ base arrives, grouped */
         void *h = s->hXorRows;
@@ -672,11 +708,10 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         if (qfGrowD(j->dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
         for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
             qzstd_hip_group_xor_row_t *r = &s->hXorRows[m];
-            const unsigned char *base = (const unsigned char *)j->bases[f0[c].buf].d_ptr;
             if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
-            r->base = base ? (uint64_t)(uintptr_t)(base + f0[c].off) : 0u;
+            r->src = (uint64_t)(uintptr_t)f0[c].src;
+            r->base = (uint64_t)(uintptr_t)f0[c].base;
             r->dstOff = so;
             r->len = (uint32_t)f0[c].len;
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
@@ -697,7 +732,7 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
             qzstd_hip_group_row_t *r = &s->hGroupRows[m];
             if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->src = (uint64_t)(uintptr_t)f0[c].src;
             r->dstOff = so;
             r->len = (uint32_t)f0[c].len;
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
@@ -717,7 +752,7 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
             qzstd_hip_gather_row_t *r = &s->hRows[m];
             if (f0[c].diff) continue; /* (staged above) */
             if (f0[c].len > 0xFFFFFFE0u) return -1; /* (a row's length and padding are 32-bit) */
-            r->src = (uint64_t)(uintptr_t)((const unsigned char *)j->bufs[f0[c].buf].d_ptr + f0[c].off);
+            r->src = (uint64_t)(uintptr_t)f0[c].src;
             r->dstOff = so;
             r->len = (uint32_t)f0[c].len;
             r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
@@ -728,7 +763,7 @@ static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     if (!pr->run || pr->diff) return -1;
     {
         const size_t chunk = j->f->p.chunkSize, pitch = qfPad16(chunk), full = pr->bytes / chunk, tail = pr->bytes - full * chunk;
-        const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
+        const unsigned char *base = f0->src;
         if (qzstd_hip_memset(j->dev, s->stream, s->dStage, 0, stageBytes)) return -1;
         if (full && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage, pitch, base, chunk, chunk, full)) return -1;
         if (tail && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
@@ -743,9 +778,9 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     const QF_DevFrame *f0 = &j->frames[pr->f0];
     const size_t nf = pr->f1 - pr->f0, nb = pr->nb, blk = j->blk;
     const size_t cap = qzstd_hip_sequence_bound(blk), capPad = (cap + 1u) & ~(size_t)1u;
-    const unsigned char *base = (const unsigned char *)j->bufs[f0->buf].d_ptr + f0->off;
+    const unsigned char *base = f0->src;
     /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
-    const int inPlace = !pr->grouped && !pr->delta && !pr->diff && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
+    const int inPlace = !pr->grouped && !pr->delta && !pr->diff && !pr->pieces && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
     size_t c, b = 0, so = 0, seqCapTotal = 0;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
@@ -904,8 +939,7 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     out->hashed = s->hashed;
     out->probed = s->probed;
     out->failSub = j->failSub;
-    out->bufs = j->bufs;
-    out->bases = j->bases;
+    out->sm = j->sm;
     out->frames = j->frames;
     out->f0 = pr->f0;
     out->f1 = pr->f1;
@@ -1101,7 +1135,7 @@ static int qfAssembleFrame(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
     f->sizes[fm->idx] = pos;
     __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
     if (fm->k > 1u) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
-    if (pt->bases && pt->bases[fm->buf].d_ptr) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
+    if (fm->based) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->probeStats[1], (unsigned long long)nRaw, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->probeStats[2], 1ull, __ATOMIC_RELAXED);
     return 0;
@@ -1124,7 +1158,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     size_t b, ns = 0, nl = 0, k, r = 0;
     int failedBlock = 0, haveSeqs = 0, maybeRle = 0;
     const int grouped = fm->k > 1u;
-    const unsigned char *dBase = pt->bases ? (const unsigned char *)pt->bases[fm->buf].d_ptr : NULL; /* the frame's content is chunk ^ base chunk */
+    const int dBase = fm->based != 0u; /* the frame's content is chunk ^ base chunk */
     unsigned char *dst = f->dst + fm->idx * f->stride;
     /* the frame's block ends (every 128 KiB; a byte-grouped frame's planes first) */
     if (w->endsCap < fm->nb) {
@@ -1219,7 +1253,8 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             to = w->back;
             haveSeqs = 0;
         }
-        if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, to, (const unsigned char *)pt->bufs[fm->buf].d_ptr + fm->off, n)) return -1;
+        /* (a frame of several source slices: one copy per piece into the same buffer) */
+        if (fm->np > 1u ? qfFramePiecesD2H(pt, w->rawStream, fm, to, 0) : qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, to, fm->src, n)) return -1;
         if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
             /* the copy still reads the caller's buffer: the call must not return before it is done */
             (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
@@ -1228,7 +1263,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
         __atomic_fetch_add(&f->devStats[2], (unsigned long long)n, __ATOMIC_RELAXED);
         if (dBase) {
             /* the base's bytes too (into raw, which the grouping below overwrites), XORed into the caller's */
-            if (qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, dBase + fm->off, n)) return -1;
+            if (fm->np > 1u ? qfFramePiecesD2H(pt, w->rawStream, fm, w->raw, 1) : qzstd_hip_memcpy_d2h(pt->dev, w->rawStream, w->raw, fm->base, n)) return -1;
             if (qzstd_hip_stream_wait(pt->dev, w->rawStream, QF_DEV_WAIT_MS) != 0) {
                 (void)qzstd_hip_stream_sync(pt->dev, w->rawStream);
                 return -1;
@@ -1281,8 +1316,18 @@ size_t QZSTD_frontDeviceBatchFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf 
  * length); at least one frame.  equal: NULL, or per frame of the call 1 for a frame found equal to its base chunk (QZSTD_frontSetDeltaSkip):
  * it is left out of the table and of the parts, so frame m of the table is frame fr[m].idx of the call, and the frames around it are not
  * consecutive chunks. */
-static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
-                        unsigned group, size_t nBufs, const unsigned char *equal,
+/* source slices: the pieces that hold bytes [off, off + len) of their buffer, len > 0 — *p, the piece a search starts from, moves on to the
+ * first of them (frames ascend, so it only moves forward), and their count is returned */
+static size_t qfSrcFramePieces(const QF_SrcMap *sm, size_t *p, size_t off, size_t len)
+{
+    size_t np = 1;
+    while (sm->pieces[*p].off + sm->pieces[*p].size <= off) (*p)++;
+    while (sm->pieces[*p + np - 1u].off + sm->pieces[*p + np - 1u].size < off + len) np++;
+    return np;
+}
+
+static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
+                        const unsigned char *elemSizes, unsigned group, size_t nBufs, const unsigned char *equal,
                         size_t nFrames, size_t partBytes, size_t blk, QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
 {
     const size_t chunk = f->p.chunkSize, maxBlocks = 4u * (partBytes / blk ? partBytes / blk : 1u);
@@ -1292,22 +1337,37 @@ static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const
     if (!fr || !pt) { free(fr); free(pt); return -1; }
     for (i = 0; i < nBufs; i++) {
         const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : group, k = e & ~QZSTD_ELEM_DIFF;
-        size_t off;
+        size_t off, p = sm ? sm->first[i] : 0; /* (source slices: the piece that holds the frame's first byte) */
         for (off = 0; off < bufs[i].size; off += chunk, c++) {
             const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
             const size_t nb = QZSTD_byteGroupBlocks(len, k, NULL, 0);
+            const unsigned char *src = (const unsigned char *)bufs[i].d_ptr + off, *base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr + off : NULL;
+            size_t np = 0;
+            if (sm) {
+                /* the slices tile the buffer: a frame inside one of them lies at an address like any other frame, one across several has none */
+                np = qfSrcFramePieces(sm, &p, off, len);
+                src = np == 1u ? sm->pieces[p].src + (off - sm->pieces[p].off) : NULL;
+                base = np == 1u && sm->pieces[p].base ? sm->pieces[p].base + (off - sm->pieces[p].off) : NULL;
+            }
             if (equal && equal[c]) continue;
             if (!cur || cur->bytes + len > partBytes || cur->nb + nb > maxBlocks) {
                 cur = &pt[nParts++];
                 cur->f0 = m;
                 cur->nb = cur->bytes = 0;
                 cur->run = 1;
-                cur->grouped = cur->delta = cur->diff = 0;
-            } else if (fr[m - 1].buf != (uint32_t)i || fr[m - 1].off + chunk != off) {
+                cur->grouped = cur->delta = cur->diff = cur->pieces = 0;
+            } else if (fr[m - 1].buf != (uint32_t)i || fr[m - 1].off + chunk != off || (sm && (!src || !fr[m - 1].src || fr[m - 1].src + chunk != src))) {
                 cur->run = 0;
             }
+            if (np > 1u) { cur->pieces = 1; cur->run = 0; }
+            if (np > 0xFFFFFFFFu) { free(fr); free(pt); return -1; }
             fr[m].off = off;
             fr[m].len = len;
+            fr[m].src = src;
+            fr[m].base = base;
+            fr[m].p0 = p;
+            fr[m].np = (uint32_t)np;
+            fr[m].based = bases && bases[i].d_ptr;
             fr[m].b0 = cur->nb;
             fr[m].idx = c;
             fr[m].buf = (uint32_t)i;
@@ -1483,8 +1543,13 @@ static int qfDiffPass(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_Device
 
 /* both device entry points.  batch: the call needs the gather (frames of several buffers in one part); the single-buffer call stages a part it
  * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not */
-static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
-                               int batch, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
+static int qfDiffPassSlices(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
+                            size_t nBufs, size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes); /* qzstd_srcslices.c */
+
+/* sm: NULL, or (QZSTD_frontCompressDeviceSlices, which has checked the slices and looked their memory up) where the buffers' bytes lie; bufs and
+ * bases then hold each buffer's size and the address of its FIRST slice, which is the buffer's own when its slices follow each other in memory */
+static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
+                               const unsigned char *elemSizes, size_t nBufs, int batch, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
     QF_DevJob j;
     QF_DevSlot *slot;
@@ -1529,13 +1594,15 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (f->checksum && !qzstd_hip_xxh64) return (size_t)-1; /* checksums wanted and a device layer that cannot hash */
     if (anyGrouped && !qzstd_hip_group) return (size_t)-1;  /* byte grouping wanted and a device layer that cannot group */
     if (bases && !qzstd_hip_group_xor) return (size_t)-1;   /* a base given and a device layer that cannot XOR one in */
+    if (sm && sm->multi && !qzstd_hip_group_pieces) return (size_t)-1; /* a frame of several pieces and a device layer that cannot assemble one */
     if (anyDiff && !qzstd_hip_group_ediff) return (size_t)-1; /* differences wanted and a device layer that cannot take them */
     skip = bases && f->deltaSkip;
     if (skip && !qzstd_hip_diff) return (size_t)-1;         /* delta skip wanted and a device layer that cannot compare */
     probe = f->planeProbe && (anyGrouped || bases);
     if (probe && !qzstd_hip_plane_cost) return (size_t)-1;  /* plane probe wanted and a device layer that cannot take histograms */
-    j.dev = -1;
-    for (i = 0; i < nBufs; i++) {
+    j.dev = sm ? sm->dev : -1;
+    total = sm ? sm->total : 0;
+    for (i = 0; !sm && i < nBufs; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
         int d;
         if (!bufs[i].size) continue;
@@ -1566,8 +1633,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     pthread_once(&qfSeqOnce, qfResolveSeqApi);
 
     j.f = f;
-    j.bufs = bufs;
-    j.bases = bases;
+    j.sm = sm;
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.probe = probe;
     j.failSub = probe && getenv("QZSTD_FRONT_PROBE_FAIL_SUB") != NULL;
@@ -1592,12 +1658,13 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     /* delta skip: the chunks equal to their base chunk are found first and get their zero frames; the parts are planned without them */
     if (rc == 0 && skip) {
         if (!(equal = (unsigned char *)malloc(nFrames))) rc = -1;
-        else rc = qfDiffPass(f, &slot[0], j.dev, bufs, bases, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes);
+        else rc = sm ? qfDiffPassSlices(f, &slot[0], j.dev, bufs, bases, sm, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes)
+                     : qfDiffPass(f, &slot[0], j.dev, bufs, bases, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes);
     }
     if (rc == 0) {
         const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
         const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        rc = qfPlanDevice(f, bufs, bases, elemSizes, group, nBufs, equal, nFrames, want, j.blk, &frames, &parts, &nParts);
+        rc = qfPlanDevice(f, bufs, bases, sm, elemSizes, group, nBufs, equal, nFrames, want, j.blk, &frames, &parts, &nParts);
     }
     j.frames = frames;
     j.parts = parts;
@@ -1652,25 +1719,25 @@ size_t QZSTD_frontCompressDevice(QZSTD_Front *f, const void *d_src, size_t srcSi
     QZSTD_DeviceBuf one;
     one.d_ptr = d_src;
     one.size = srcSize;
-    return qfCompressDevice(f, &one, NULL, NULL, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
+    return qfCompressDevice(f, &one, NULL, NULL, NULL, 1, 0, stream, dst, dstCapacity, frameSizes, NULL);
 }
 
 size_t QZSTD_frontCompressDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, void *dst, size_t dstCapacity,
                                       size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, NULL, NULL, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, NULL, NULL, NULL, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 size_t QZSTD_frontCompressDeviceBatchTyped(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream,
                                            void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, NULL, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, NULL, NULL, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 size_t QZSTD_frontCompressDeviceBatchDelta(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes,
                                            size_t nBufs, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
-    return qfCompressDevice(f, bufs, bases, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return qfCompressDevice(f, bufs, bases, NULL, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
 void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
@@ -1796,3 +1863,7 @@ int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { ret
 /* The adviser: are element differences worth it for a buffer, from plane costs taken on the GPU; on the restore's first slot like the
  * fingerprint calls; included the same way. */
 #include "qzstd_advise.c"
+
+/* The compress call whose buffers are lists of source slices: its checks, the staging from pieces and the places that read a frame's bytes
+ * piece by piece; included the same way. */
+#include "qzstd_srcslices.c"

@@ -112,6 +112,19 @@ qzstd_hip_fingerprint, qzstd_hip_diff (two sides) and qzstd_hip_xxh64, ms per Gi
 under rocprofv3).
 
   python tools/device_bench.py --fingerprint --gib 1 --reps 3 [--kernels]
+
+--srcslices: a tensor that is not contiguous, written (QZSTD_frontCompressDeviceSlices) — the left half of an [N x 65536, 16384]-byte matrix of
+bf16 N(0, 0.02) weights: N x 65536 slices of 8 KiB, frames of 128 KiB, levels 1 and 6, without and with a base (the same view of a second
+matrix, an N(0, 1e-5) update away).  Three legs, alternating in one run, every run listed, GB/s of input, compressed bytes (equal across the
+legs: asserted) and torch's peak extra device memory:
+  slices      one QZSTD_frontCompressDeviceSlices call on the view's rows
+  contiguous  what a caller does today: view.contiguous() (the base's too) inside the window + the Typed / Delta call
+  typed       the Typed / Delta call on a tensor that is contiguous already: what the pieces cost
+then, in the same run, the kernel through the C ABI with events around ONE launcher call each (tables uploaded inside, from pinned memory)
+over an N GiB stage of 128 KiB rows, alternating: qzstd_hip_group_xor, and qzstd_hip_group_pieces with pieces of a whole frame, 8 KiB, 2 KiB and
+64 bytes, for k = 1, 2, 4, 8, ms per GiB; and the upload of each piece table alone.  --kernels: the kernel legs alone.
+
+  python tools/device_bench.py --srcslices --gib 1 --reps 3 [--levels 1,6] [--kernels]
 """
 import argparse
 import json
@@ -1545,8 +1558,180 @@ def advise_main(a):
     print(json.dumps(out))
 
 
+def srcslices_kernels(a, size, out):
+    """qzstd_hip_group_pieces beside qzstd_hip_group_xor IN ONE RUN: ONE launch each over the same N GiB as rows of 128 KiB, without a base, ms
+    per GiB from events around the launcher call (rows and pieces uploaded inside, from pinned memory), alternating, every run listed after
+    one untimed round; pieces of a whole frame, 8 KiB, 2 KiB and 64 bytes — cut out of the same contiguous source, so the bytes read are the
+    same and only the table differs — for k = 1, 2, 4, 8; the stage of every pieces launch is compared with the group_xor launch's"""
+    import ctypes as C
+    import numpy as np
+    plug = B.Plugin()
+    L = D.bind_pieces_kernel(D.bind_xor_kernels(plug.lib))
+    n = size // a.chunk
+    gib = size / float(1 << 30)
+    torch.manual_seed(0)
+    src = torch.randint(0, 256, (size,), device="cuda:0", dtype=torch.uint8)
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    stage2 = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    assert src.data_ptr() % 16 == 0 and stage.data_ptr() % 16 == 0 and stage2.data_ptr() % 16 == 0
+    piece_t = np.dtype([("src", "<u8"), ("base", "<u8"), ("off", "<u4"), ("len", "<u4")])
+    row_t = np.dtype([("dstOff", "<u8"), ("len", "<u4"), ("pad", "<u4"), ("elem", "<u4"), ("piece0", "<u4"), ("nPieces", "<u4"), ("reserved", "<u4")])
+    widths = (("frame", a.chunk), ("8k", 8192), ("2k", 2048), ("64", 64))
+    most = size // 64
+    pin_p = torch.empty(most * piece_t.itemsize, dtype=torch.uint8).pin_memory()
+    pin_r = torch.empty(n * row_t.itemsize, dtype=torch.uint8).pin_memory()
+    d_pieces = L.qzstd_hip_malloc(0, most * piece_t.itemsize)
+    d_rows = L.qzstd_hip_malloc(0, n * max(row_t.itemsize, C.sizeof(D.GroupXorRow)))
+    assert d_pieces and d_rows
+    cells = {}
+    try:
+        for k in (1, 2, 4, 8):
+            xrows = (D.GroupXorRow * n)()
+            for c in range(n):
+                x = xrows[c]
+                x.src, x.base, x.dstOff, x.len, x.pad, x.elem = src.data_ptr() + c * a.chunk, 0, c * a.chunk, a.chunk, 16 if c + 1 == n else 0, k
+            rows = pin_r.numpy().view(row_t)
+            cell = cells["k%d" % k] = {}
+
+            def timed(call):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                assert call() == 0, plug.err()
+                e1.record()
+                torch.cuda.synchronize()
+                return round(e0.elapsed_time(e1) / gib, 3)
+
+            runs = {"group_xor": []}
+            for i in range(a.reps + 1):
+                t = timed(lambda: L.qzstd_hip_group_xor(0, None, xrows, n, d_rows, stage.data_ptr(), size + 16))
+                if i:
+                    runs["group_xor"].append(t)
+            for name, w in widths:
+                per = a.chunk // w
+                np_ = n * per
+                pieces = pin_p.numpy()[:np_ * piece_t.itemsize].view(piece_t)
+                pieces["src"] = np.uint64(src.data_ptr()) + np.arange(np_, dtype=np.uint64) * np.uint64(w)
+                pieces["base"] = 0
+                pieces["off"] = (np.arange(np_, dtype=np.uint64) % np.uint64(per)) * np.uint64(w)
+                pieces["len"] = w
+                rows["dstOff"] = np.arange(n, dtype=np.uint64) * np.uint64(a.chunk)
+                rows["len"], rows["pad"], rows["elem"], rows["nPieces"], rows["reserved"] = a.chunk, 0, k, per, 0
+                rows["pad"][n - 1] = 16
+                rows["piece0"] = np.arange(n, dtype=np.uint64) * np.uint64(per)
+                key = "pieces_" + name
+                runs[key], runs[key + "_table_upload"] = [], []
+                dev_copy = torch.empty(np_ * piece_t.itemsize, dtype=torch.uint8, device="cuda:0")
+                for i in range(a.reps + 1):
+                    t = timed(lambda: L.qzstd_hip_group_pieces(0, None, rows.ctypes.data, n, d_rows, pieces.ctypes.data, np_, d_pieces, stage2.data_ptr(),
+                                                               size + 16))
+                    u = timed(lambda: (dev_copy.copy_(pin_p[:np_ * piece_t.itemsize], non_blocking=True), 0)[1])
+                    if i:
+                        runs[key].append(t)
+                        runs[key + "_table_upload"].append(u)
+                assert torch.equal(stage, stage2), (k, name)
+                stage2.zero_()
+                del dev_copy
+            cell.update({leg + "_ms_per_gib": v for leg, v in runs.items()})
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+        L.qzstd_hip_free(0, d_pieces)
+    out["kernels"] = {"rows": n, "row_bytes": a.chunk, "cells": cells, "piece_table_bytes": {name: size // w * 24 for name, w in widths},
+                      "timed": "events around ONE launcher call each (rows and pieces uploaded inside, from pinned memory) over the same %d rows of %d "
+                               "bytes of random bytes, no base, ms per GiB of rows, every run of %d after one untimed round; *_table_upload: the same "
+                               "events around a copy of the piece table alone" % (n, a.chunk, a.reps)}
+
+
+def srcslices_main(a):
+    """--srcslices: QZSTD_frontCompressDeviceSlices on a column view against view.contiguous() + the Typed / Delta call and against that call on a
+    contiguous tensor; then the kernel beside qzstd_hip_group_xor.  --kernels: the kernel legs alone"""
+    import ctypes as C
+    rows_n = (int(a.gib * 65536) + 15) & ~15
+    rowb, width = 16384, 8192
+    size = rows_n * width
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "reps": a.reps, "dtype": "bf16 N(0, 0.02)", "matrix_bytes": [rows_n, rowb],
+           "slices": rows_n, "slice_bytes": width}
+    if a.kernels:
+        srcslices_kernels(a, int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1), out)
+        return print(json.dumps(out))
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out["timed"] = ("GB/s of input, every run, the legs alternating in one run; the window holds the calls (the slice and buffer arrays exist before "
+                    "it), for `contiguous` the .contiguous() copies, and the closing synchronize")
+    out["peak_extra_device_bytes"] = ("torch's peak allocation above the level before the call (the .contiguous() temporaries); the library's own "
+                                      "stages are the same in all legs and not included")
+    mat = (torch.randn(rows_n * rowb // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8).view(rows_n, rowb)
+    bmat = ((mat.view(torch.bfloat16).float() + torch.randn(rows_n, rowb // 2, device="cuda:0") * 1e-5).to(torch.bfloat16)).view(torch.uint8).view(rows_n, rowb)
+    mat, bmat = bmat, mat  # (the new checkpoint is the update; the base is what it came from)
+    view, bview = mat[:, :width], bmat[:, :width]
+    flat, bflat = view.contiguous(), bview.contiguous()
+    out["cells"] = {}
+    for level in [int(x) for x in a.levels.split(",")]:
+        fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+        try:
+            fr.reserve(size)
+            _, sizes = fr._frame_buffers(n)
+            first = (C.c_size_t * 2)()
+            es = bytes([2]) + b"\0"
+            bs = (C.c_size_t * 1)(size)
+            for based in (False, True):
+                sl = [(0, r * width, width, view.data_ptr() + r * rowb, bview.data_ptr() + r * rowb if based else None) for r in range(rows_n)]
+                arr = fr.src_slice_array(sl)
+                fbufs, fbase = fr.batch([(flat.data_ptr(), size)])[0], fr.batch([(bflat.data_ptr(), size)])[0]
+
+                def leg_slices():
+                    return fr.call_compress_slices(bs, 1, es, arr, rows_n, sizes, first, stream)
+
+                def delta(t, b):
+                    return fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, fr.batch([(t.data_ptr(), size)])[0],
+                                                                      fr.batch([(b.data_ptr(), size)])[0] if based else None, es, 1, stream,
+                                                                      fr._dst, len(fr._dst), sizes, first)
+
+                def leg_contiguous():
+                    return delta(view.contiguous(), bview.contiguous() if based else None)
+
+                def leg_typed():
+                    return fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, fbufs, fbase if based else None, es, 1, stream, fr._dst, len(fr._dst), sizes, first)
+
+                legs = (("slices", leg_slices), ("contiguous", leg_contiguous), ("typed", leg_typed))
+                cell = out["cells"]["level%d_%s" % (level, "base" if based else "nobase")] = {}
+                frames = {}
+                for name, leg in legs:  # untimed, and checked
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    m0, s0, p0 = torch.cuda.memory_allocated(), fr.stats(), fr.src_slice_stats()
+                    assert leg() == n, name
+                    torch.cuda.synchronize()
+                    peak, s1 = torch.cuda.max_memory_allocated() - m0, fr.stats()
+                    frames[name] = fr.frames(n, sizes)
+                    cell[name] = {"compressed_bytes": sum(len(x) for x in frames[name]), "peak_extra_device_bytes": peak,
+                                  "d2h_bytes_per_input_byte": round((s1[2] - s0[2]) / size, 4), "gbps": []}
+                    if name == "slices":
+                        cell[name]["src_slice_stats"] = [y - x for x, y in zip(p0, fr.src_slice_stats())]
+                assert frames["slices"] == frames["contiguous"] == frames["typed"], (level, based)
+                del frames
+                for _ in range(a.reps):
+                    for name, leg in legs:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert leg() == n, name
+                        torch.cuda.synchronize()
+                        cell[name]["gbps"].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+        finally:
+            fr.close()
+    del mat, bmat, view, bview, flat, bflat
+    torch.cuda.empty_cache()
+    srcslices_kernels(a, int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1), out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--srcslices", action="store_true")
     ap.add_argument("--advise", action="store_true")
     ap.add_argument("--ediff", action="store_true")
     ap.add_argument("--fingerprint", action="store_true")
@@ -1570,6 +1755,10 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.srcslices:
+        if a.levels == "1,6,12":
+            a.levels = "1,6"
+        return srcslices_main(a)
     if a.advise:
         return advise_main(a)
     if a.ediff:

@@ -338,6 +338,30 @@ class DeviceSlice(C.Structure):
     _fields_ = [("buf", C.c_size_t), ("offset", C.c_size_t), ("size", C.c_size_t), ("d_dst", C.c_void_p), ("d_base", C.c_void_p)]
 
 
+class DeviceSrcSlice(C.Structure):
+    """QZSTD_DeviceSrcSlice (include/qzstd_frontend_device.h)"""
+    _fields_ = [("buf", C.c_size_t), ("offset", C.c_size_t), ("size", C.c_size_t), ("d_src", C.c_void_p), ("d_base", C.c_void_p)]
+
+
+class GroupPiece(C.Structure):
+    """qzstd_hip_group_piece_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("src", C.c_uint64), ("base", C.c_uint64), ("off", C.c_uint32), ("len", C.c_uint32)]
+
+
+class GroupPiecesRow(C.Structure):
+    """qzstd_hip_group_pieces_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("dstOff", C.c_uint64), ("len", C.c_uint32), ("pad", C.c_uint32), ("elem", C.c_uint32), ("piece0", C.c_uint32),
+                ("nPieces", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+def bind_pieces_kernel(L):
+    """qzstd_hip_group_pieces on a loaded device layer (libqatseqprod, or a mock of it)"""
+    L.qzstd_hip_group_pieces.restype = C.c_int
+    L.qzstd_hip_group_pieces.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                         C.c_size_t]
+    return L
+
+
 def bind_window_kernel(L):
     """qzstd_hip_ungroup_window on a loaded device layer (libqatseqprod)"""
     L.qzstd_hip_ungroup_window.restype = C.c_int
@@ -429,6 +453,12 @@ def bind(F):
                                                      C.c_char_p, C.c_size_t, C.POINTER(DeviceSlice), C.c_size_t, C.c_void_p]
         F.QZSTD_frontSliceStats.restype = None
         F.QZSTD_frontSliceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontCompressDeviceSlices"):  # (absent from an older library)
+        F.QZSTD_frontCompressDeviceSlices.restype = C.c_size_t
+        F.QZSTD_frontCompressDeviceSlices.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.c_char_p, C.c_size_t, C.POINTER(DeviceSrcSlice), C.c_size_t,
+                                                      C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        F.QZSTD_frontSrcSliceStats.restype = None
+        F.QZSTD_frontSrcSliceStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     if hasattr(F, "QZSTD_frontSetDeltaSkip"):  # (absent from an older library)
         F.QZSTD_frontSetDeltaSkip.restype = C.c_int
         F.QZSTD_frontSetDeltaSkip.argtypes = [C.c_void_p, C.c_int]
@@ -741,6 +771,49 @@ class DeviceFront:
         if frames is None:
             raise RuntimeError("QZSTD_frontCompressDeviceBatchDelta failed (%d)" % (r if r != ERROR else -1))
         return frames
+
+    def src_slice_array(self, slices):
+        """-> QZSTD_DeviceSrcSlice array for [(buffer index, offset, size, source address, base address or None), ...]"""
+        arr = (DeviceSrcSlice * max(len(slices), 1))()
+        for a, (buf, off, size, src, base) in zip(arr, slices):
+            a.buf, a.offset, a.size, a.d_src, a.d_base = buf, off, size, src or None, base or None
+        return arr
+
+    def call_compress_slices(self, buf_sizes, n_bufs: int, elem_sizes, slice_arr, n_slices: int, sizes, first, stream: int | None = None):
+        """QZSTD_frontCompressDeviceSlices alone on prepared arguments (a c_size_t array of sizes, src_slice_array(), reserve_frames()) -> its
+        return value; frames stay in the destination"""
+        return self.lib.QZSTD_frontCompressDeviceSlices(self.f, buf_sizes, elem_sizes, n_bufs, slice_arr, n_slices, C.c_void_p(stream or None),
+                                                        self._dst, len(self._dst), sizes, first)
+
+    def compress_device_slices_raw(self, buf_sizes, elem_sizes, slices, stream: int | None = None):
+        """QZSTD_frontCompressDeviceSlices -> (return value, per buffer its list of frames or None); buf_sizes: the logical buffers' sizes (or
+        None for no array), slices: [(buffer index, offset, size, source address, base address or None), ...] (or None for no array)"""
+        nb = 0 if buf_sizes is None else len(buf_sizes)
+        n = sum(-(-b // self.chunk) for b in buf_sizes or ())
+        _, sizes = self._frame_buffers(n)
+        first = (C.c_size_t * (nb + 1))()
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        bs = None if buf_sizes is None else (C.c_size_t * max(nb, 1))(*buf_sizes)
+        r = self.call_compress_slices(bs, nb, es, None if slices is None else self.src_slice_array(slices), 0 if slices is None else len(slices),
+                                      sizes, first, stream)
+        self.last = (n, sizes)
+        if r != n:
+            return r, None
+        fr = self._frames(n, sizes)
+        return r, [fr[first[i]:first[i + 1]] for i in range(nb)]
+
+    def compress_device_slices(self, buf_sizes, elem_sizes, slices, stream: int | None = None) -> list:
+        r, frames = self.compress_device_slices_raw(buf_sizes, elem_sizes, slices, stream)
+        if frames is None:
+            raise RuntimeError("QZSTD_frontCompressDeviceSlices failed (%d)" % (r if r != ERROR else -1))
+        return frames
+
+    def src_slice_stats(self) -> list:
+        """QZSTD_frontSrcSliceStats: [0] non-empty slices of the calls that succeeded, [1] their bytes, [2] frames assembled from more than
+        one piece, [3] qzstd_hip_group_pieces launches"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontSrcSliceStats(self.f, st)
+        return list(st)
 
     def restore_batch_delta_raw(self, frames_per_buffer, ptrs_and_sizes, bases, elem_sizes=None, stream: int | None = None, compact: bool = False,
                                 n_frames: int | None = None):
