@@ -305,7 +305,8 @@ void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4]);
  * bytes of the LOGICAL buffer, the frame count, firstFrame, strides and QZSTD_frontDeviceBatchFrames of the sizes are the same, and EVERY
  * FRAME IS BYTE FOR BYTE the frame that call returns with the same elemSizes, bases and front settings (byte group, checksum, plane probe,
  * delta skip); `stream` (it orders the last writer of every slice and base) and blocking are as there.  The frame format knows nothing of
- * where a chunk's bytes came from, so restore, slices, verify and fingerprints read these frames as before and the caller keeps nothing new.
+ * where a chunk's bytes came from, so restore, slices, verify and fingerprints read these frames as before and the caller keeps nothing new;
+ * the TENSORS the frames are checked against may stay slices too: QZSTD_frontVerifyDeviceSlices, ...FingerprintDeviceSlices, ...CheckDeviceSlices.
  *
  * A frame that lies inside one slice is handled as a frame of a contiguous buffer is, so a call in which every frame does — one slice per
  * buffer in particular — queues the launches of the Delta call.  A part that holds a frame made of several slices is always staged, by ONE
@@ -401,6 +402,43 @@ size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, 
 /* since creation, of the calls that succeeded: [0] frames fingerprinted, [1] bytes read on the device, [2] qzstd_hip_fingerprint launches,
  * [3] frames a check found differing */
 void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4]);
+
+/* Fingerprint, check and verify with SOURCE SLICES: the three calls above for buffers that are not contiguous in device memory, given as
+ * QZSTD_frontCompressDeviceSlices takes them — so that a view saved from slices is verified and fingerprinted, and a view restored by
+ * QZSTD_frontRestoreDeviceSlices is checked, without the `.contiguous()` copy either.  The slice list obeys that call's rules: the non-empty
+ * slices of a buffer, in order, tile [0, bufSizes[i]) exactly; d_src is the live (or restored) bytes of the slice.  In the verify call d_base
+ * is the same slice of the base the buffer was written against, or NULL: all slices of a buffer carry one, or none does; it may equal d_src.
+ * In the two fingerprint calls d_base is IGNORED — never read, never looked up, mixed based and unbased slices are no error — so the list
+ * given to the compress call serves unchanged.
+ *
+ * Frames are cut every chunkSize bytes of the LOGICAL buffer, and every answer is the contiguous call's for the same bytes held
+ * contiguously: fp[c], differs[], the return values and firstDiff[c] (the lowest differing offset inside frame c's chunk, QZSTD_VERIFY_SAME,
+ * QZSTD_VERIFY_UNDECODED), with QZSTD_frontSetDeltaSkip on and off — a recognised zero frame made of several slices is compared live
+ * against base piece by piece, and is not decoded — and for every element size.
+ *
+ * A frame that lies inside one piece (slices that follow each other in memory, bases included, are one piece) is handled as a frame of a
+ * contiguous buffer is: a call, or a verify part, in which every frame does — one slice per buffer in particular — queues exactly the
+ * launches of the contiguous call.  A fingerprint call with at least one frame made of several pieces takes ONE
+ * qzstd_hip_fingerprint_pieces launch over all its rows, a verify part that holds such a frame ONE qzstd_hip_ungroup_cmp_pieces launch
+ * over all its rows, in the contiguous launch's place.  Rows and the piece table live in grow-only pinned and device scratch kept with the
+ * front.  QZSTD_frontFingerprintStats and QZSTD_frontVerifyStats count these calls as they count the contiguous ones.
+ *
+ * (size_t)-1 before anything is queued: everything the contiguous counterpart refuses that applies (QZSTD_ELEM_DIFF in the verify call
+ * among it; the fingerprint calls take no element sizes); everything QZSTD_frontCompressDeviceSlices refuses about bufSizes and slices,
+ * with that call's look-ups (consecutive ranges count as one, qzstd_hip_pointer_extent where the layer tells it); in the verify call a
+ * buffer with based and unbased slices; and, for a call with a frame made of several pieces, a device layer without the kernel from
+ * pieces — such a layer serves a call without such a frame, and every other call, as before.  A front created with useProducer = 0 is
+ * accepted.  No slices, or only empty ones: 0, and no GPU is touched. */
+size_t QZSTD_frontFingerprintDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, size_t nBufs, const QZSTD_DeviceSrcSlice *slices, size_t nSlices,
+                                          void *stream, unsigned long long *fp, size_t *firstFrame /* nBufs + 1, or NULL */);
+size_t QZSTD_frontCheckDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, size_t nBufs, const QZSTD_DeviceSrcSlice *slices, size_t nSlices,
+                                    void *stream, const unsigned long long *expected, size_t nFrames, unsigned char *differs /* or NULL */);
+size_t QZSTD_frontVerifyDeviceSlices(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                     const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs, const QZSTD_DeviceSrcSlice *slices,
+                                     size_t nSlices, void *stream, size_t *firstDiff /* nFrames entries, or NULL */);
+/* since creation, of the three calls that succeeded: [0] non-empty slices, [1] their bytes, [2] frames assembled from more than one piece,
+ * [3] launches of qzstd_hip_fingerprint_pieces and qzstd_hip_ungroup_cmp_pieces */
+void QZSTD_frontSliceCheckStats(QZSTD_Front *f, unsigned long long stats[4]);
 
 /* Advice: which buffers of a list should carry QZSTD_ELEM_DIFF?  Differences shrink columns with order and GROW data without, so the flag is
  * per buffer and the caller's decision; this call makes it from statistics instead of compressing every buffer twice.  Per chunk — cut as the

@@ -414,6 +414,68 @@ typedef struct {
 int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows, uint64_t *d_tiles);
 
 /*
+ * Fingerprint from PIECES (QZSTD_frontFingerprintDeviceSlices / QZSTD_frontCheckDeviceSlices): qzstd_hip_fingerprint for rows whose content
+ * is the concatenation of pieces that lie anywhere in device memory (the piece table of qzstd_hip_group_pieces: a row owns
+ * pieces[piece0 .. piece0 + nPieces), c[p.off + i] = src_p[i]).  d_tiles[tile0 + j] = QZSTD_fpTile over the j-th 16 KiB of c[] (the last
+ * tile: what is left), by the header's own functions: exactly what qzstd_hip_fingerprint leaves for the same bytes held contiguously.
+ *
+ * Work is divided as in qzstd_hip_fingerprint: a workgroup of 256 threads per 16 KiB tile of a row, the row found by a binary search over
+ * tile0 (written by the launcher).  One lane narrows the row's pieces to those that hold the tile's first and last byte; every lane takes
+ * its four words (t, t + 256, t + 512, t + 768) through the lookup of qzstd_hip_group_pieces — one fetch for a word inside a piece, piece
+ * by piece for a word that straddles pieces, up to sixteen one-byte pieces per word — and the rounds, the tree and the single 8-byte
+ * store are qzstd_hip_fingerprint's.  No atomics, no memset, no read-modify-write; nothing but d_tiles[0 .. sum of the rows'
+ * QZSTD_HIP_FP_TILES) is written.  Sources are read only with aligned 16-byte loads of words that overlap THAT PIECE's [src, src + len),
+ * and of no other word — a piece may end on an allocation's last byte; a base is never read.  No workgroup waits for another.  The piece
+ * table is read from device memory, not cached in LDS.
+ *
+ * `rows` and `pieces` are HOST memory (pinned, for the uploads to be asynchronous); `rows` is WRITTEN by the launcher (tile0 only, and only
+ * by a launch that is not refused); both must stay unchanged until the stream has passed the call; d_rows and d_pieces: device scratch of
+ * nRows and nPieces entries.  Refused (< 0) before anything is queued: what qzstd_hip_fingerprint refuses (the null source is a piece's),
+ * what qzstd_hip_group_pieces refuses about the table (a null pieces or d_pieces with nPieces > 0, a piece0 + nPieces past the table, a
+ * piece with len == 0 or a null src, pieces of a row that do not tile [0, len) exactly in ascending order), and a piece whose `base` is
+ * not 0.  nRows == 0, or only empty rows: nothing is queued, 0.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint32_t len;     /* content bytes, may be 0 */
+    uint32_t tile0;   /* written by the launcher: workgroups of the rows before this one */
+    uint32_t piece0;  /* the row's first piece */
+    uint32_t nPieces; /* its pieces tile [0, len) exactly, ascending, none empty; 0 only for len == 0 */
+} qzstd_hip_fp_pieces_row_t;
+int qzstd_hip_fingerprint_pieces(int device, void *stream, qzstd_hip_fp_pieces_row_t *rows, uint32_t nRows, qzstd_hip_fp_pieces_row_t *d_rows,
+                                 const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, qzstd_hip_group_piece_t *d_pieces, uint64_t *d_tiles);
+
+/*
+ * Ungrouping comparison with PIECES (QZSTD_frontVerifyDeviceSlices): qzstd_hip_ungroup_cmp for rows whose live bytes (and base) are pieces
+ * that lie anywhere in device memory.  With u[] as qzstd_hip_ungroup_cmp defines it (all zeros for a ZERO row, whose stage is never read),
+ * a row MATCHES when u[p.off + i] ^ base_p[i] == src_p[i] for every piece p of the row and every i < p.len; base 0 means no XOR;
+ * src == base is allowed.  Tiles, the tail with the last tile, QZSTD_HIP_CMP_TILES, the ONE word per tile (QZSTD_HIP_CMP_SAME, or the
+ * lowest differing row offset) and the wave-min / LDS reduction are qzstd_hip_ungroup_cmp's; one lane narrows the row's pieces to those
+ * that hold the tile's first and last byte, and a lane fetches src ^ base of its 16 bytes through the lookup of qzstd_hip_group_pieces.
+ *
+ * No atomics, no memset, no read-modify-write; nothing but d_tiles[0 .. total tiles) is written.  Sources and bases are read only with
+ * aligned 16-byte loads of words that overlap THAT PIECE's [src, src + len) or [base, base + len), and of no other word — a piece may end
+ * on an allocation's last byte; stage loads are qzstd_hip_ungroup_cmp's.  No workgroup waits for another.  The piece table is read from
+ * device memory, not cached in LDS.
+ *
+ * `rows` and `pieces` are HOST memory (pinned); `rows` is WRITTEN by the launcher (tile0 only, and only by a launch that is not refused);
+ * both must stay unchanged until the stream has passed the call.  Refused (< 0) before anything is queued: what qzstd_hip_ungroup_cmp
+ * refuses (the null ref is a piece's null src) and what qzstd_hip_group_pieces refuses about the table.  No value of a piece's `base` is
+ * refused.  nRows == 0, or only empty rows: nothing is queued, 0.  Asynchronous on `stream`.
+ */
+typedef struct {
+    uint64_t srcOff;  /* the frame's offset in d_stage, a multiple of 16 (not looked at for a ZERO row) */
+    uint32_t len;     /* content bytes, may be 0 */
+    uint32_t elem;    /* 1, 2, 4 or 8: the grouped layout the frame lies in */
+    uint32_t flags;   /* QZSTD_HIP_CMP_ZERO; other bits 0 */
+    uint32_t tile0;   /* written by the launcher: workgroups of the rows before this one */
+    uint32_t piece0;  /* the row's first piece */
+    uint32_t nPieces; /* its pieces tile [0, len) exactly, ascending, none empty; 0 only for len == 0 */
+} qzstd_hip_ungroup_cmp_pieces_row_t;
+int qzstd_hip_ungroup_cmp_pieces(int device, void *stream, qzstd_hip_ungroup_cmp_pieces_row_t *rows, uint32_t nRows,
+                                 qzstd_hip_ungroup_cmp_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                                 qzstd_hip_group_piece_t *d_pieces, const void *d_stage, size_t stageBytes, uint32_t *d_tiles);
+
+/*
  * Byte-grouping gather with element differences (include/qzstd_elemdiff.h): qzstd_hip_group with a `flags` word in place of `reserved`.
  * A row without QZSTD_HIP_EDIFF_DIFF lands exactly as qzstd_hip_group lands it; a row with it lands as the grouped layout of
  * QZSTD_elemDiff(row, len, elem) — z[e] = zigzag(x[e] - x[e-1]), x[-1] = 0, the tail bytes unchanged — and `pad` zero bytes follow.

@@ -1805,6 +1805,270 @@ extern "C" int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_
     return 0;
 }
 
+/* ---------------------------------------------------------------- fingerprint and comparison from pieces (include/qzstd_hip_device.h) -- */
+/* Kernels of their own, as qzstd_group_pieces_kernel is: qzstd_fingerprint_kernel and qzstd_ungroup_cmp_kernel stay what they were.  The
+ * way from a content offset to a piece and an address is qzstd_group_pieces_kernel's (pieces_find, pieces_fetch), and so is the reason the
+ * piece table stays in device memory: a tile of one-byte pieces has 16384 entries. */
+namespace {
+/* the pieces of [first, first + count) that hold content bytes c0 and c1 (c0 <= c1, both inside the row) */
+__device__ inline void pieces_narrow(const qzstd_hip_group_piece_t *__restrict__ pieces, uint32_t first, uint32_t count, uint32_t c0, uint32_t c1,
+                                     uint32_t *lo, uint32_t *hi)
+{
+    *lo = pieces_find(pieces, first, first + count - 1u, c0);
+    *hi = pieces_find(pieces, *lo, first + count - 1u, c1);
+}
+
+/* qzstd_fingerprint_kernel over a row's pieces: the search for the row, then one lane narrows the row's pieces to the tile's; a lane's four
+ * words come through pieces_fetch (no piece of a launch has a base: the launcher refuses one), all four before the first round; masking,
+ * rounds, tree and the store are the neighbour's. */
+__global__ __launch_bounds__(kFpT) void qzstd_fingerprint_pieces_kernel(const qzstd_hip_fp_pieces_row_t *__restrict__ rows, uint32_t nRows,
+                                                                        const qzstd_hip_group_piece_t *__restrict__ pieces,
+                                                                        unsigned long long *__restrict__ tilesOut)
+{
+    __shared__ uint32_t which, pieceLo, pieceHi;
+    __shared__ uint64_t red[kFpT / 64u];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+        const qzstd_hip_fp_pieces_row_t rw = rows[lo];
+        const uint64_t a = (uint64_t)(blockIdx.x - rw.tile0) << kFpTileLog;
+        pieceLo = pieceHi = rw.piece0;
+        if (a < rw.len) {
+            const uint32_t c0 = (uint32_t)a, c1 = rw.len - c0 < (1u << kFpTileLog) ? rw.len - 1u : c0 + (1u << kFpTileLog) - 1u;
+            pieces_narrow(pieces, rw.piece0, rw.nPieces, c0, c1, &pieceLo, &pieceHi);
+        }
+    }
+    __syncthreads();
+    const qzstd_hip_fp_pieces_row_t row = rows[which];
+    const uint64_t at64 = (uint64_t)(blockIdx.x - row.tile0) << kFpTileLog; /* the tile's first byte in its row */
+    if (at64 >= row.len) return; /* (the whole workgroup; never: rows without a tile share the tile0 of the row behind them) */
+    const uint32_t at = (uint32_t)at64;
+    const uint32_t tileBytes = row.len - at < (1u << kFpTileLog) ? row.len - at : 1u << kFpTileLog;
+    const uint32_t pLo = pieceLo, pHi = pieceHi;
+    uint64_t w0[kFpWords], w1[kFpWords];
+#pragma unroll
+    for (uint32_t k = 0; k < kFpWords; k++) {
+        const uint32_t w = tid + k * kFpT;
+        w0[k] = w1[k] = 0ull;
+        if (w * 16u < tileBytes) {
+            const uint32_t valid = tileBytes - w * 16u < 16u ? tileBytes - w * 16u : 16u;
+            const uint32_t c = at + w * 16u;
+            pieces_fetch(pieces, pLo == pHi ? pLo : pieces_find(pieces, pLo, pHi, c), c, valid, &w0[k], &w1[k]);
+            cmp_mask(valid, &w0[k], &w1[k]); /* the row's last word: what lies behind the row reads as 0 */
+        }
+    }
+    uint64_t acc = QZSTD_fpLaneInit(tid);
+#pragma unroll
+    for (uint32_t k = 0; k < kFpWords; k++)
+        if ((tid + k * kFpT) * 16u < tileBytes) acc = QZSTD_fpWord(acc, w0[k], w1[k]);
+#pragma unroll
+    for (uint32_t s = 1u; s < 64u; s <<= 1) {
+        const uint64_t other = __shfl_down(acc, s, 64);
+        acc = QZSTD_fpMerge(acc, other);
+    }
+    if ((tid & 63u) == 0u) red[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        const uint64_t a = QZSTD_fpMerge(red[0], red[1]), b = QZSTD_fpMerge(red[2], red[3]); /* s = 64 */
+        tilesOut[blockIdx.x] = QZSTD_fpMerge(a, b);                                          /* s = 128 */
+    }
+}
+
+/* qzstd_ungroup_cmp_kernel over a row's pieces: phase A is the neighbour's; before it, one lane narrows the row's pieces to those of the
+ * tile's bytes [t0, t1) of u[]; in phase B the two group_fetch of ref and base are ONE pieces_fetch of src ^ base at the content offset. */
+__global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_pieces_kernel(const qzstd_hip_ungroup_cmp_pieces_row_t *__restrict__ rows, uint32_t nRows,
+                                                                              const qzstd_hip_group_piece_t *__restrict__ pieces,
+                                                                              const uint8_t *__restrict__ stage, uint32_t *__restrict__ tilesOut)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
+    __shared__ uint32_t which, pieceLo, pieceHi;
+    __shared__ uint32_t red[kUngroupT / 64u];
+    const uint32_t tid = threadIdx.x;
+    if (tid == 0) {
+        uint32_t lo = 0, hi = nRows - 1u;
+        while (lo < hi) {
+            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+        }
+        which = lo;
+        const qzstd_hip_ungroup_cmp_pieces_row_t rw = rows[lo];
+        const uint32_t kl = rw.elem == 8u ? 3u : (rw.elem == 4u ? 2u : (rw.elem == 2u ? 1u : 0u));
+        const uint32_t nn = rw.len >> kl, tm = kUngroupTile >> kl;
+        const uint32_t nt = nn ? (uint32_t)(((uint64_t)nn + tm - 1u) / tm) : (rw.len ? 1u : 0u);
+        const uint32_t tt = blockIdx.x - rw.tile0;
+        pieceLo = pieceHi = rw.piece0;
+        if (tt < nt) {
+            const uint32_t first = tt * tm, elems = nn - first < tm ? nn - first : tm;
+            const uint32_t c0 = first << kl, c1 = tt + 1u == nt ? rw.len : (first + elems) << kl; /* (c0 < c1: a tile holds bytes) */
+            pieces_narrow(pieces, rw.piece0, rw.nPieces, c0, c1 - 1u, &pieceLo, &pieceHi);
+        }
+    }
+    __syncthreads();
+    const qzstd_hip_ungroup_cmp_pieces_row_t row = rows[which];
+    const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
+    const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
+    const uint32_t tiles = n ? (uint32_t)(((uint64_t)n + tileMax - 1u) / tileMax) : (row.len ? 1u : 0u);
+    const uint32_t t = blockIdx.x - row.tile0;
+    if (t >= tiles) return; /* (the whole workgroup; never: rows without a tile share the tile0 of the row behind them) */
+    const bool zero = (row.flags & 1u) != 0u;
+    const uint32_t e0 = t * tileMax;
+    const uint32_t tileElems = n - e0 < tileMax ? n - e0 : tileMax;
+    const uint8_t *stageRow = stage + row.srcOff;
+    const uint32_t pLo = pieceLo, pHi = pieceHi;
+    if (!zero) ungroup_load(stageRow, n, kLog, e0, tileElems, lds, tid); /* (row is the workgroup's: the branch is uniform) */
+    __syncthreads();
+
+    const uint32_t t0 = e0 << kLog, lim = (e0 + tileElems) << kLog; /* the tile's bytes of u[]: what its strips hold (len <= 0xFFFFFFE0) */
+    const uint32_t t1 = t + 1u == tiles ? row.len : lim;           /* the tail behind the elements goes with the last tile */
+    uint32_t first = kCmpSame;
+    for (uint32_t rel = tid * 16u; rel < t1 - t0; rel += kUngroupT * 16u) { /* (t1 - t0 <= 16 KiB + 7: no wrap near 4 GiB) */
+        const uint32_t o = t0 + rel, valid = t1 - o < 16u ? t1 - o : 16u;
+        uint64_t u0 = 0ull, u1 = 0ull;
+        if (!zero) {
+            uint4 v = make_uint4(0u, 0u, 0u, 0u);
+            if (o < lim) {
+                switch (kLog) {
+                case 0u: v = ungroup_word<1u>(lds, n, e0, o); break;
+                case 1u: v = ungroup_word<2u>(lds, n, e0, o); break;
+                case 2u: v = ungroup_word<4u>(lds, n, e0, o); break;
+                default: v = ungroup_word<8u>(lds, n, e0, o); break;
+                }
+            }
+            if (lim - o < valid || o >= lim) { /* the word reaches into the tail: those bytes one by one, from the stage */
+                uint32_t d[4] = { v.x, v.y, v.z, v.w };
+                for (uint32_t b = o < lim ? lim - o : 0u; b < valid; b++)
+                    d[b >> 2] = (d[b >> 2] & ~(0xFFu << ((b & 3u) * 8u))) | ungroup_byte(stageRow, n, kLog, o + b) << ((b & 3u) * 8u);
+                v = make_uint4(d[0], d[1], d[2], d[3]);
+            }
+            u0 = v.x | (uint64_t)v.y << 32;
+            u1 = v.z | (uint64_t)v.w << 32;
+        }
+        uint64_t r0, r1;
+        pieces_fetch(pieces, pLo == pHi ? pLo : pieces_find(pieces, pLo, pHi, o), o, valid, &r0, &r1); /* src ^ base */
+        u0 ^= r0;
+        u1 ^= r1;
+        cmp_mask(valid, &u0, &u1); /* the row's last word: what lies behind the row, in the strips' slack and in memory, does not count */
+        if (u0 | u1) {
+            const uint32_t at = o + (u0 ? (uint32_t)__builtin_ctzll(u0) >> 3 : 8u + ((uint32_t)__builtin_ctzll(u1) >> 3));
+            first = at < first ? at : first; /* (a lane's offsets ascend: only its first one is kept) */
+        }
+    }
+#pragma unroll
+    for (uint32_t d = 32u; d; d >>= 1) {
+        const uint32_t other = (uint32_t)__shfl_xor((int)first, (int)d, 64);
+        first = other < first ? other : first;
+    }
+    if ((tid & 63u) == 0u) red[tid >> 6] = first;
+    __syncthreads();
+    if (tid == 0) {
+        uint32_t m = red[0];
+#pragma unroll
+        for (uint32_t w = 1; w < kUngroupT / 64u; w++) m = red[w] < m ? red[w] : m;
+        tilesOut[blockIdx.x] = m;
+    }
+}
+
+/* the piece table's checks, qzstd_hip_group_pieces's: row [piece0, piece0 + count) tiles [0, len); noBase: a base is refused too */
+inline const char *pieces_check(const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, uint32_t piece0, uint32_t count, uint32_t len, bool noBase)
+{
+    if ((uint64_t)piece0 + count > nPieces) return "a row's pieces end past the table";
+    uint64_t at = 0;
+    for (uint32_t p = piece0; p < piece0 + count; p++) {
+        if (!pieces[p].len || !pieces[p].src) return "an empty piece or a null source";
+        if (noBase && pieces[p].base) return "a piece with a base";
+        if (pieces[p].off != at) return "a row's pieces do not tile its content in ascending order";
+        at += pieces[p].len;
+    }
+    return at == len ? nullptr : "a row's pieces do not tile its content in ascending order";
+}
+} // namespace
+
+extern "C" int qzstd_hip_fingerprint_pieces(int device, void *stream, qzstd_hip_fp_pieces_row_t *rows, uint32_t nRows, qzstd_hip_fp_pieces_row_t *d_rows,
+                                            const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, qzstd_hip_group_piece_t *d_pieces,
+                                            uint64_t *d_tiles)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_tiles) return fail_msg("qzstd_hip_fingerprint_pieces: null pointer");
+    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_fingerprint_pieces: null piece table");
+    uint64_t total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_fp_pieces_row_t &r = rows[i];
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_fingerprint_pieces: row too long");
+        if (const char *why = pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, true)) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "qzstd_hip_fingerprint_pieces: %s", why);
+            return fail_msg(msg);
+        }
+        total += QZSTD_HIP_FP_TILES(r.len);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_fingerprint_pieces: too many tiles");
+    if (total == 0) return 0; /* nothing but empty rows */
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_FP_TILES(rows[i].len);
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (fingerprint pieces rows)");
+    QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
+             "hipMemcpyAsync H2D (fingerprint pieces table)");
+    hipLaunchKernelGGL(qzstd_fingerprint_pieces_kernel, dim3((uint32_t)total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
+                       reinterpret_cast<unsigned long long *>(d_tiles));
+    QZ_CHECK(hipGetLastError(), "launch qzstd_fingerprint_pieces_kernel");
+    return 0;
+}
+
+extern "C" int qzstd_hip_ungroup_cmp_pieces(int device, void *stream, qzstd_hip_ungroup_cmp_pieces_row_t *rows, uint32_t nRows,
+                                            qzstd_hip_ungroup_cmp_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                                            qzstd_hip_group_piece_t *d_pieces, const void *d_stage, size_t stageBytes, uint32_t *d_tiles)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null pointer or stage not 16-byte aligned");
+    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null piece table");
+    uint64_t end = 0, total = 0;
+    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
+    for (uint32_t i = 0; i < nRows; i++) {
+        const qzstd_hip_ungroup_cmp_pieces_row_t &r = rows[i];
+        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: elem not 1, 2, 4 or 8");
+        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return fail_msg("qzstd_hip_ungroup_cmp_pieces: unknown flags");
+        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: frame too long");
+        if (const char *why = pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, false)) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "qzstd_hip_ungroup_cmp_pieces: %s", why);
+            return fail_msg(msg);
+        }
+        if (!(r.flags & QZSTD_HIP_CMP_ZERO)) { /* a ZERO row's srcOff is not looked at */
+            if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: srcOff not a multiple of 16");
+            if (r.len && !d_stage) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null stage");
+            if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_cmp_pieces: frames overlap in the stage or are not in ascending order");
+            if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_cmp_pieces: a frame ends past stageBytes");
+            end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
+        }
+        total += QZSTD_HIP_CMP_TILES(r.len, r.elem);
+    }
+    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_cmp_pieces: too many tiles");
+    if (total == 0) return 0; /* nothing but empty rows */
+    total = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = (uint32_t)total;
+        total += QZSTD_HIP_CMP_TILES(rows[i].len, rows[i].elem);
+    }
+    QZ_SET_DEVICE(device);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup cmp pieces rows)");
+    QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
+             "hipMemcpyAsync H2D (ungroup cmp pieces table)");
+    hipLaunchKernelGGL(qzstd_ungroup_cmp_pieces_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
+                       static_cast<const uint8_t *>(d_stage), d_tiles);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_cmp_pieces_kernel");
+    return 0;
+}
+
 /* ---------------------------------------------------------------- element differences and their sum (include/qzstd_hip_device.h, qzstd_elemdiff.h) -- */
 namespace {
 /* the element of K bytes at address a, any alignment: group_fetch's aligned words, the ones that overlap [a, a + K) */

@@ -13,14 +13,21 @@
 
 extern int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows,
                                  uint64_t *d_tiles) __attribute__((weak));
+extern int qzstd_hip_fingerprint_pieces(int device, void *stream, qzstd_hip_fp_pieces_row_t *rows, uint32_t nRows, qzstd_hip_fp_pieces_row_t *d_rows,
+                                        const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, qzstd_hip_group_piece_t *d_pieces,
+                                        uint64_t *d_tiles) __attribute__((weak));
 
 unsigned long long QZSTD_fingerprintOf(const void *p, size_t len) { return p || !len ? QZSTD_fingerprint(p, len) : 0ull; }
 
 /* both calls: fp[c] receives the fingerprint of frame c (fp may be NULL when expected is not); with `expected`, differs[c] (or NULL) says
- * whether it is another one, and the return value counts those frames instead of all */
-static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, unsigned long long *fp, size_t *firstFrame,
-                                  const unsigned long long *expected, int check, size_t nExpected, unsigned char *differs)
+ * whether it is another one, and the return value counts those frames instead of all.  sm: NULL, or the source slices of the calls of
+ * qzstd_slicecheck.c (looked up already; bufs holds the sizes): a frame inside one piece is the row it is in a contiguous buffer, and a call
+ * with a frame of several pieces is ONE qzstd_hip_fingerprint_pieces launch over all its rows instead */
+static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, const QF_SrcMap *sm, void *stream, unsigned long long *fp,
+                                  size_t *firstFrame, const unsigned long long *expected, int check, size_t nExpected, unsigned char *differs)
 {
+    const int pieces = sm && sm->multi;
+    size_t nPieces = 0, m = 0, multi = 0;
     QF_RestoreSlot *s;
     void *ev = NULL, *h;
     size_t i, c = 0, nFrames = 0, nTiles = 0, total = 0, t = 0, nDiff = 0;
@@ -41,7 +48,12 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
     if (!qzstd_hip_fingerprint || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the fingerprint kernel, or without the device-input entry points at all */
-    for (i = 0; i < nBufs; i++) {
+    if (pieces && !qzstd_hip_fingerprint_pieces) return (size_t)-1; /* a frame of several pieces and a device layer that cannot read one */
+    if (sm) {
+        dev = sm->dev;
+        total = sm->total;
+    }
+    for (i = 0; i < nBufs && !sm; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
         int d;
         if (!bufs[i].size) continue;
@@ -76,6 +88,22 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
         if (qfGrowH(&h, &s->hFpRowsCap, nFrames * sizeof(qzstd_hip_fp_row_t))) rc = -1;
         s->hFpRows = (qzstd_hip_fp_row_t *)h;
     }
+    if (rc == 0 && pieces) {
+        size_t p, off;
+        for (i = 0; i < nBufs; i++)
+            for (off = 0, p = sm->first[i]; off < bufs[i].size; off += f->p.chunkSize)
+                nPieces += qfSrcFramePieces(sm, &p, off, bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
+        if (nPieces > 0xFFFFFFFFu) rc = -1;
+        h = s->hFpPieceRows;
+        if (rc == 0 && qfGrowH(&h, &s->hFpPieceRowsCap, nFrames * sizeof(qzstd_hip_fp_pieces_row_t))) rc = -1;
+        s->hFpPieceRows = (qzstd_hip_fp_pieces_row_t *)h;
+        h = s->hChkPieces;
+        if (rc == 0 && qfGrowH(&h, &s->hChkPiecesCap, nPieces * sizeof(qzstd_hip_group_piece_t))) rc = -1;
+        s->hChkPieces = (qzstd_hip_group_piece_t *)h;
+        if (rc == 0 && (qfGrowD(dev, &s->dFpPieceRows, &s->dFpPieceRowsCap, nFrames * sizeof(qzstd_hip_fp_pieces_row_t)) ||
+                        qfGrowD(dev, &s->dChkPieces, &s->dChkPiecesCap, nPieces * sizeof(qzstd_hip_group_piece_t))))
+            rc = -1;
+    }
     if (rc == 0) {
         h = s->hFpTiles;
         if (qfGrowH(&h, &s->hFpTilesCap, nTiles * sizeof(uint64_t))) rc = -1;
@@ -89,15 +117,31 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
     if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, s->stream, ev))) rc = -1;
     if (rc == 0) {
         for (i = 0, c = 0; i < nBufs; i++) {
-            size_t off;
+            size_t off, p = sm ? sm->first[i] : 0;
             for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
-                qzstd_hip_fp_row_t *r = &s->hFpRows[c];
+                qzstd_hip_fp_row_t *r = &s->hFpRows[c]; /* (its len is the frame's in either launch: the fold below reads it) */
                 r->src = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
                 r->len = (uint32_t)(bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
                 r->tile0 = 0;
+                if (sm) {
+                    const size_t np = qfSrcFramePieces(sm, &p, off, r->len);
+                    r->src = np == 1u ? (uint64_t)(uintptr_t)(sm->pieces[p].src + (off - sm->pieces[p].off)) : 0u;
+                    if (pieces) {
+                        qzstd_hip_fp_pieces_row_t *q = &s->hFpPieceRows[c];
+                        q->len = r->len;
+                        q->tile0 = 0;
+                        q->piece0 = (uint32_t)m;
+                        q->nPieces = (uint32_t)np;
+                        qfSrcFrameTable(sm, p, np, off, r->len, 0, &s->hChkPieces[m]);
+                        m += np;
+                        if (np > 1u) multi++;
+                    }
+                }
             }
         }
-        if (qzstd_hip_fingerprint(dev, s->stream, s->hFpRows, (uint32_t)nFrames, (qzstd_hip_fp_row_t *)s->dFpRows, (uint64_t *)s->dFpTiles) ||
+        if ((pieces ? qzstd_hip_fingerprint_pieces(dev, s->stream, s->hFpPieceRows, (uint32_t)nFrames, (qzstd_hip_fp_pieces_row_t *)s->dFpPieceRows,
+                                                   s->hChkPieces, (uint32_t)nPieces, (qzstd_hip_group_piece_t *)s->dChkPieces, (uint64_t *)s->dFpTiles)
+                    : qzstd_hip_fingerprint(dev, s->stream, s->hFpRows, (uint32_t)nFrames, (qzstd_hip_fp_row_t *)s->dFpRows, (uint64_t *)s->dFpTiles)) ||
             qzstd_hip_memcpy_d2h(dev, s->stream, s->hFpTiles, s->dFpTiles, nTiles * sizeof(uint64_t)))
             rc = -1;
     }
@@ -123,6 +167,10 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
         __atomic_fetch_add(&f->fpStats[1], (unsigned long long)total, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->fpStats[2], 1ull, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->fpStats[3], (unsigned long long)nDiff, __ATOMIC_RELAXED);
+        if (pieces) {
+            sm->counts[0] += (unsigned long long)multi; /* (the call adds them to the front's) */
+            sm->counts[1] += 1ull;
+        }
     }
     pthread_mutex_lock(&f->mu);
     f->devBusy = 0;
@@ -133,13 +181,13 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
 size_t QZSTD_frontFingerprintDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, unsigned long long *fp,
                                          size_t *firstFrame)
 {
-    return qfFingerprintDevice(f, bufs, nBufs, stream, fp, firstFrame, NULL, 0, 0, NULL);
+    return qfFingerprintDevice(f, bufs, nBufs, NULL, stream, fp, firstFrame, NULL, 0, 0, NULL);
 }
 
 size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, void *stream, const unsigned long long *expected,
                                    size_t nFrames, unsigned char *differs)
 {
-    return qfFingerprintDevice(f, bufs, nBufs, stream, NULL, NULL, expected, 1, nFrames, differs);
+    return qfFingerprintDevice(f, bufs, nBufs, NULL, stream, NULL, NULL, expected, 1, nFrames, differs);
 }
 
 void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4])

@@ -113,6 +113,7 @@ struct QZSTD_Front_s {
     unsigned long long fpStats[4];     /* the fingerprint calls: frames fingerprinted, bytes read on the device, launches, frames a check found differing */
     unsigned long long adviseStats[4]; /* QZSTD_frontAdviseDeviceBatch: buffers advised on, buffers flagged, bytes read on the device, launches */
     unsigned long long srcSliceStats[4]; /* QZSTD_frontCompressDeviceSlices: slices, their bytes, frames of more than one piece, qzstd_hip_group_pieces launches */
+    unsigned long long sliceCheckStats[4]; /* the fingerprint, check and verify calls with source slices: slices, their bytes, frames of more than one piece, launches of the two kernels from pieces */
 };
 
 /* A claim: chunks [c0, c1) of the job.  Where the entropy stage sets the pace (levels 1-4: with a libzstd that entropy-codes 1.6 GB/s per core
@@ -554,7 +555,7 @@ typedef struct {
     size_t total;        /* bytes of all buffers */
     int dev;             /* the device all of them lie on (-1: there are none) */
     int multi;           /* a frame of the call is made of more than one piece */
-    unsigned long long *counts; /* the call's own: [0] frames staged from more than one piece, [1] qzstd_hip_group_pieces launches */
+    unsigned long long *counts; /* the call's own: [0] frames staged (fingerprinted, compared) from more than one piece, [1] launches of the kernel from pieces */
 } QF_SrcMap;
 
 /* one frame of a device job (the per-frame table, built once per call): where its bytes lie and which blocks of its part are its own */
@@ -1326,6 +1327,21 @@ static size_t qfSrcFramePieces(const QF_SrcMap *sm, size_t *p, size_t off, size_
     return np;
 }
 
+/* the piece table of such a frame for the kernels that read pieces: pieces [p, p + np) of the map cut to bytes [off, off + len) of their
+ * buffer, offsets counted from the frame's first byte; bases: with the pieces' bases (else 0: none is ever read) */
+static void qfSrcFrameTable(const QF_SrcMap *sm, size_t p, size_t np, size_t off, size_t len, int bases, qzstd_hip_group_piece_t *out)
+{
+    size_t k;
+    for (k = 0; k < np; k++) {
+        const QF_SrcPiece *q = &sm->pieces[p + k];
+        const size_t lo = q->off > off ? q->off : off, hi = q->off + q->size < off + len ? q->off + q->size : off + len;
+        out[k].src = (uint64_t)(uintptr_t)(q->src + (lo - q->off));
+        out[k].base = bases && q->base ? (uint64_t)(uintptr_t)(q->base + (lo - q->off)) : 0u;
+        out[k].off = (uint32_t)(lo - off);
+        out[k].len = (uint32_t)(hi - lo);
+    }
+}
+
 static int qfPlanDevice(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
                         const unsigned char *elemSizes, unsigned group, size_t nBufs, const unsigned char *equal,
                         size_t nFrames, size_t partBytes, size_t blk, QF_DevFrame **framesOut, QF_DevRange **partsOut, size_t *nPartsOut)
@@ -1867,3 +1883,7 @@ int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes) { ret
 /* The compress call whose buffers are lists of source slices: its checks, the staging from pieces and the places that read a frame's bytes
  * piece by piece; included the same way. */
 #include "qzstd_srcslices.c"
+
+/* The fingerprint, check and verify calls whose buffers are lists of source slices: the same checks, and the bodies of qzstd_fingerprint.c
+ * and qzstd_verify.c with the piece map; included the same way. */
+#include "qzstd_slicecheck.c"

@@ -72,6 +72,12 @@ struct QF_RestoreSlot_s {
     void *dAdvRows; size_t dAdvRowsCap;
     void *dAdvTiles; size_t dAdvTilesCap;                      /* the launch's two cost words per tile and their pinned copy */
     uint32_t *hAdvTiles; size_t hAdvTilesCap;
+    qzstd_hip_fp_pieces_row_t *hFpPieceRows; size_t hFpPieceRowsCap; /* the calls with source slices (qzstd_slicecheck.c), a launch with a frame of */
+    void *dFpPieceRows; size_t dFpPieceRowsCap;                      /* several pieces: qzstd_hip_fingerprint_pieces's rows instead (slot 0 only), */
+    qzstd_hip_ungroup_cmp_pieces_row_t *hCmpPieceRows; size_t hCmpPieceRowsCap; /* qzstd_hip_ungroup_cmp_pieces's rows instead, */
+    void *dCmpPieceRows; size_t dCmpPieceRowsCap;
+    qzstd_hip_group_piece_t *hChkPieces; size_t hChkPiecesCap;       /* and the launch's piece table */
+    void *dChkPieces; size_t dChkPiecesCap;
 };
 
 /* the part the workers decode (QZSTD_Front.restore) */
@@ -109,6 +115,12 @@ static void qfRestoreSlotsFree(QZSTD_Front *f)
         if (s->hAdvRows) qzstd_hip_host_free(s->hAdvRows);
         if (s->dAdvTiles) qzstd_hip_free(f->restoreSlotDev, s->dAdvTiles);
         if (s->hAdvTiles) qzstd_hip_host_free(s->hAdvTiles);
+        if (s->dFpPieceRows) qzstd_hip_free(f->restoreSlotDev, s->dFpPieceRows);
+        if (s->hFpPieceRows) qzstd_hip_host_free(s->hFpPieceRows);
+        if (s->dCmpPieceRows) qzstd_hip_free(f->restoreSlotDev, s->dCmpPieceRows);
+        if (s->hCmpPieceRows) qzstd_hip_host_free(s->hCmpPieceRows);
+        if (s->dChkPieces) qzstd_hip_free(f->restoreSlotDev, s->dChkPieces);
+        if (s->hChkPieces) qzstd_hip_host_free(s->hChkPieces);
         if (s->hStage) qzstd_hip_host_free(s->hStage);
         if (s->hRows) qzstd_hip_host_free(s->hRows);
         if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);

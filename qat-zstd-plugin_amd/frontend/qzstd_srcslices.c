@@ -2,7 +2,7 @@
  * qzstd_srcslices.c — QZSTD_frontCompressDeviceSlices (include/qzstd_frontend_device.h): the Delta compress call for buffers that are not
  * contiguous in device memory.  Included by qzstd_frontend.c (its types and helpers are used as they are).
  *
- * The call checks its slices, looks their memory up and hands qfCompressDevice a map of the non-empty ones (QF_SrcMap: slices that follow each
+ * The call checks its slices, looks their memory up (qfSrcMapBuild, which the calls of qzstd_slicecheck.c use too) and hands qfCompressDevice a map of the non-empty ones (QF_SrcMap: slices that follow each
  * other in memory, bases included, are one piece there) beside a buffer table that holds the sizes.  The per-frame table then says where each frame lies: a frame inside ONE slice has an address, as a frame of a contiguous
  * buffer has, and takes every path such a frame takes — staged by the same launches or read in place; a frame across several slices has
  * none, and the three places that would read its bytes from an address read them piece by piece instead:
@@ -192,81 +192,100 @@ static int qfSrcRangeOnDevice(const unsigned char *p, size_t n, int *dev, QF_Src
     return qzstd_hip_pointer_device(p + n - 1) == d ? 0 : -1;
 }
 
-size_t QZSTD_frontCompressDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs,
-                                       const QZSTD_DeviceSrcSlice *slices, size_t nSlices, void *stream, void *dst, size_t dstCapacity,
-                                       size_t *frameSizes, size_t *firstFrame)
-{
+/* a call's source slices, checked, looked up and merged into pieces: the map and what it points to (qfSrcMapFree) */
+typedef struct {
     QF_SrcMap sm;
+    QF_SrcPiece *pieces;
+    size_t *first;
+    QZSTD_DeviceBuf *bufs, *bases; /* nBufs each: the sizes, and the address of a buffer's first byte (its base's; NULL and 0: none) */
+    size_t nSlices;                /* the non-empty ones */
+    int anyBase;
+    unsigned long long counts[2];  /* sm.counts */
+} QF_SrcSlices;
+
+static void qfSrcMapFree(QF_SrcSlices *o)
+{
+    free(o->pieces);
+    free(o->first);
+    free(o->bufs);
+}
+
+/* the slice list of QZSTD_frontCompressDeviceSlices and of the calls of qzstd_slicecheck.c: the host-side checks (nothing has touched a
+ * GPU when one of them fails), the look-ups of the memory, and the map of the non-empty slices — slices that follow each other in memory,
+ * bases included, are ONE piece.  withBases 0: d_base is ignored — not checked, not looked up, not part of the merging rule, and no piece
+ * has one.  0, or -1 with nothing to free. */
+static int qfSrcMapBuild(const QZSTD_Front *f, const size_t *bufSizes, size_t nBufs, const QZSTD_DeviceSrcSlice *slices, size_t nSlices, int withBases,
+                         QF_SrcSlices *o)
+{
     QF_SrcPiece *pieces;
     QZSTD_DeviceBuf *bufs, *bases;
     size_t *first;
-    size_t i, b = 0, last = 0, at = 0, nPieces = 0, m = 0, ret;
-    unsigned long long counts[2] = { 0ull, 0ull };
+    size_t i, b = 0, last = 0, at = 0, nPieces = 0, m = 0;
     int mode = -1, anyBase = 0, dev = -1;
-    /* host-side checks: nothing has touched a GPU when one of them fails */
-    if (!f || (nBufs && !bufSizes) || (nSlices && !slices) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
-    for (i = 0; i < nBufs; i++)
-        if (((elemSizes && elemSizes[i] ? elemSizes[i] : f->group) & QZSTD_ELEM_DIFF) != 0u) return (size_t)-1; /* the differencing gather knows no pieces */
+    memset(o, 0, sizeof(*o));
+    if (!f || (nBufs && !bufSizes) || (nSlices && !slices) || nBufs > 0xFFFFFFFFu) return -1;
     /* the non-empty slices, in order, tile every buffer; a buffer's slices all carry a base or none does */
     for (i = 0; i < nSlices; i++) {
         const QZSTD_DeviceSrcSlice *s = &slices[i];
-        if (s->buf >= nBufs || s->buf < last) return (size_t)-1; /* (empty slices too are in their buffers' order) */
+        if (s->buf >= nBufs || s->buf < last) return -1; /* (empty slices too are in their buffers' order) */
         last = s->buf;
-        if (s->offset > bufSizes[s->buf] || s->size > bufSizes[s->buf] - s->offset) return (size_t)-1;
+        if (s->offset > bufSizes[s->buf] || s->size > bufSizes[s->buf] - s->offset) return -1;
         if (!s->size) continue;
         for (; b < s->buf; b++, at = 0, mode = -1)
-            if (at != bufSizes[b]) return (size_t)-1; /* the buffer before ends short */
-        if (s->offset != at || !s->d_src) return (size_t)-1; /* a gap, an overlap or out of order */
-        if (mode >= 0 && mode != (s->d_base != NULL)) return (size_t)-1;
-        mode = s->d_base != NULL;
-        anyBase |= mode;
+            if (at != bufSizes[b]) return -1; /* the buffer before ends short */
+        if (s->offset != at || !s->d_src) return -1; /* a gap, an overlap or out of order */
+        if (withBases) {
+            if (mode >= 0 && mode != (s->d_base != NULL)) return -1;
+            mode = s->d_base != NULL;
+            anyBase |= mode;
+        }
         at += s->size;
         nPieces++;
     }
     for (; b < nBufs; b++, at = 0)
-        if (at != bufSizes[b]) return (size_t)-1;
-    if (!qzstd_hip_pointer_device) return (size_t)-1; /* a device layer without the device-input entry points */
+        if (at != bufSizes[b]) return -1;
+    if (!qzstd_hip_pointer_device) return -1; /* a device layer without the device-input entry points */
     {
         /* sources (and bases) that follow each other in memory are ONE range, as in the Slices restore; a range is looked up when it ends */
         const unsigned char *d0 = NULL, *dEnd = NULL, *b0 = NULL, *bEnd = NULL;
         QF_SrcExtent dKnown = { NULL, NULL }, bKnown = { NULL, NULL };
         for (i = 0; i < nSlices; i++) {
-            const unsigned char *p = (const unsigned char *)slices[i].d_src, *q = (const unsigned char *)slices[i].d_base;
+            const unsigned char *p = (const unsigned char *)slices[i].d_src, *q = withBases ? (const unsigned char *)slices[i].d_base : NULL;
             if (!slices[i].size) continue;
             if (p != dEnd) {
-                if (dEnd && qfSrcRangeOnDevice(d0, (size_t)(dEnd - d0), &dev, &dKnown)) return (size_t)-1;
+                if (dEnd && qfSrcRangeOnDevice(d0, (size_t)(dEnd - d0), &dev, &dKnown)) return -1;
                 d0 = p;
             }
             dEnd = p + slices[i].size;
             if (q != bEnd || !q) {
-                if (bEnd && qfSrcRangeOnDevice(b0, (size_t)(bEnd - b0), &dev, &bKnown)) return (size_t)-1;
+                if (bEnd && qfSrcRangeOnDevice(b0, (size_t)(bEnd - b0), &dev, &bKnown)) return -1;
                 b0 = q;
             }
             bEnd = q ? q + slices[i].size : NULL;
         }
-        if (dEnd && qfSrcRangeOnDevice(d0, (size_t)(dEnd - d0), &dev, &dKnown)) return (size_t)-1;
-        if (bEnd && qfSrcRangeOnDevice(b0, (size_t)(bEnd - b0), &dev, &bKnown)) return (size_t)-1;
+        if (dEnd && qfSrcRangeOnDevice(d0, (size_t)(dEnd - d0), &dev, &dKnown)) return -1;
+        if (bEnd && qfSrcRangeOnDevice(b0, (size_t)(bEnd - b0), &dev, &bKnown)) return -1;
     }
     pieces = (QF_SrcPiece *)malloc((nPieces + 1u) * sizeof(*pieces));
     first = (size_t *)malloc((nBufs + 1u) * sizeof(*first));
     bufs = (QZSTD_DeviceBuf *)calloc(2u * nBufs + 1u, sizeof(*bufs));
-    if (!pieces || !first || !bufs) { free(pieces); free(first); free(bufs); return (size_t)-1; }
+    if (!pieces || !first || !bufs) { free(pieces); free(first); free(bufs); return -1; }
     bases = bufs + nBufs;
-    memset(&sm, 0, sizeof(sm));
     for (i = 0, b = 0; b < nBufs; b++) {
         first[b] = m;
         bufs[b].size = bufSizes[b];
         for (; i < nSlices && slices[i].buf == b; i++) {
+            const unsigned char *base = withBases ? (const unsigned char *)slices[i].d_base : NULL;
             if (!slices[i].size) continue;
             if (m > first[b] && pieces[m - 1].src + pieces[m - 1].size == (const unsigned char *)slices[i].d_src &&
-                (pieces[m - 1].base ? pieces[m - 1].base + pieces[m - 1].size : NULL) == (const unsigned char *)slices[i].d_base) {
+                (pieces[m - 1].base ? pieces[m - 1].base + pieces[m - 1].size : NULL) == base) {
                 pieces[m - 1].size += slices[i].size; /* it follows the slice before in memory, and so does its base: one piece */
                 continue;
             }
             pieces[m].off = slices[i].offset;
             pieces[m].size = slices[i].size;
             pieces[m].src = (const unsigned char *)slices[i].d_src;
-            pieces[m].base = (const unsigned char *)slices[i].d_base;
+            pieces[m].base = base;
             m++;
         }
         if (m > first[b]) {
@@ -274,29 +293,47 @@ size_t QZSTD_frontCompressDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, c
             bufs[b].d_ptr = pieces[first[b]].src;
             if (pieces[first[b]].base) { bases[b].d_ptr = pieces[first[b]].base; bases[b].size = bufSizes[b]; }
         }
-        sm.total += bufSizes[b];
+        o->sm.total += bufSizes[b];
     }
     first[nBufs] = m;
-    sm.pieces = pieces;
-    sm.first = first;
-    sm.dev = dev;
-    sm.counts = counts;
+    o->pieces = pieces;
+    o->first = first;
+    o->bufs = bufs;
+    o->bases = bases;
+    o->nSlices = nPieces;
+    o->anyBase = anyBase;
+    o->sm.pieces = pieces;
+    o->sm.first = first;
+    o->sm.dev = dev;
+    o->sm.counts = o->counts;
     /* (chunkSize is fixed when the front is created: reading it needs no lock) */
-    for (b = 0; b < nBufs && !sm.multi; b++) {
+    for (b = 0; b < nBufs && !o->sm.multi; b++) {
         size_t off, p = first[b];
-        for (off = 0; off < bufSizes[b] && !sm.multi; off += f->p.chunkSize)
-            sm.multi = qfSrcFramePieces(&sm, &p, off, bufSizes[b] - off < f->p.chunkSize ? bufSizes[b] - off : f->p.chunkSize) > 1u;
+        for (off = 0; off < bufSizes[b] && !o->sm.multi; off += f->p.chunkSize)
+            o->sm.multi = qfSrcFramePieces(&o->sm, &p, off, bufSizes[b] - off < f->p.chunkSize ? bufSizes[b] - off : f->p.chunkSize) > 1u;
     }
-    ret = qfCompressDevice(f, bufs, anyBase ? bases : NULL, &sm, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
+    return 0;
+}
+
+size_t QZSTD_frontCompressDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, const unsigned char *elemSizes, size_t nBufs,
+                                       const QZSTD_DeviceSrcSlice *slices, size_t nSlices, void *stream, void *dst, size_t dstCapacity,
+                                       size_t *frameSizes, size_t *firstFrame)
+{
+    QF_SrcSlices o;
+    size_t i, ret;
+    /* host-side checks: nothing has touched a GPU when one of them fails */
+    if (!f || (nBufs && !bufSizes) || (nSlices && !slices) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
+    for (i = 0; i < nBufs; i++)
+        if (((elemSizes && elemSizes[i] ? elemSizes[i] : f->group) & QZSTD_ELEM_DIFF) != 0u) return (size_t)-1; /* the differencing gather knows no pieces */
+    if (qfSrcMapBuild(f, bufSizes, nBufs, slices, nSlices, 1, &o)) return (size_t)-1;
+    ret = qfCompressDevice(f, o.bufs, o.anyBase ? o.bases : NULL, &o.sm, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
     if (ret != (size_t)-1) {
-        __atomic_fetch_add(&f->srcSliceStats[0], (unsigned long long)nPieces, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->srcSliceStats[1], (unsigned long long)sm.total, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->srcSliceStats[2], counts[0], __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->srcSliceStats[3], counts[1], __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->srcSliceStats[0], (unsigned long long)o.nSlices, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->srcSliceStats[1], (unsigned long long)o.sm.total, __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->srcSliceStats[2], o.counts[0], __ATOMIC_RELAXED);
+        __atomic_fetch_add(&f->srcSliceStats[3], o.counts[1], __ATOMIC_RELAXED);
     }
-    free(pieces);
-    free(first);
-    free(bufs);
+    qfSrcMapFree(&o);
     return ret;
 }
 

@@ -17,18 +17,23 @@
 
 extern int qzstd_hip_ungroup_cmp(int device, void *stream, qzstd_hip_ungroup_cmp_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_cmp_row_t *d_rows,
                                  const void *d_stage, size_t stageBytes, uint32_t *d_tiles) __attribute__((weak));
+extern int qzstd_hip_ungroup_cmp_pieces(int device, void *stream, qzstd_hip_ungroup_cmp_pieces_row_t *rows, uint32_t nRows,
+                                        qzstd_hip_ungroup_cmp_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
+                                        qzstd_hip_group_piece_t *d_pieces, const void *d_stage, size_t stageBytes, uint32_t *d_tiles)
+    __attribute__((weak));
 
 /* one frame of the call: the row it becomes */
 typedef struct {
-    const unsigned char *d_ref;  /* the live chunk */
+    const unsigned char *d_ref;  /* the live chunk; NULL for a frame of several pieces (a call with source slices) */
     const unsigned char *d_base; /* its base chunk, or NULL */
+    size_t off, p0, np;          /* a call with source slices: the frame's offset in its buffer and the pieces of the map that hold its bytes */
     size_t len;
     size_t m;                    /* its frame in the decode table; (size_t)-1: a ZERO row, not decoded */
     uint32_t k;
 } QF_VerifyRow;
 
 /* frames [c0, c1) of the call, of them decoded [f0, f1) of the table: decoded content bytes, stage bytes, compared bytes (ZERO rows too), tile words */
-typedef struct { size_t c0, c1, f0, f1, bytes, stage, compared, tiles; } QF_VerifyRange;
+typedef struct { size_t c0, c1, f0, f1, bytes, stage, compared, tiles, pieces, multi; } QF_VerifyRange; /* (pieces, multi: the frames' pieces, and the frames with more than one) */
 
 /* the tile words of the part a slot last ran (its stream has passed them): per frame the first one that is not "same" */
 static void qfVerifyHarvest(QZSTD_Front *f, QF_RestoreSlot *s, const QF_VerifyRange *parts, const QF_VerifyRow *rows, size_t *firstDiff, size_t *nDiff)
@@ -51,9 +56,12 @@ static void qfVerifyHarvest(QZSTD_Front *f, QF_RestoreSlot *s, const QF_VerifyRa
     __atomic_fetch_add(&f->verifyStats[1], (unsigned long long)differing, __ATOMIC_RELAXED);
 }
 
-size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
-                                    const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
-                                    void *stream, size_t *firstDiff)
+/* the call's body.  sm: NULL, or the source slices of QZSTD_frontVerifyDeviceSlices (qzstd_slicecheck.c; looked up already, bufs and bases
+ * hold the sizes): a frame inside one piece is the row it is in a contiguous buffer, and a part with a frame of several pieces is ONE
+ * qzstd_hip_ungroup_cmp_pieces launch over all its rows instead */
+static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                             const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm, const unsigned char *elemSizes,
+                             size_t nBufs, void *stream, size_t *firstDiff)
 {
     QF_RestoreFrame *table = NULL; /* the frames that are decoded */
     size_t *callOf = NULL;         /* their numbers in the call */
@@ -65,7 +73,7 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
     QF_RestoreSlot *slot;
     struct QF_RestorePart_s part;
     void *ev = NULL;
-    size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nDiff = 0;
+    size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nDiff = 0, tp;
     int dev = -1, rc = 0, anyBase = 0, skip;
     /* host-side checks, the restore's: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
@@ -85,7 +93,9 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
     if (!qzstd_hip_ungroup_cmp || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the ungrouping comparison, or without the device-input entry points at all */
-    for (i = 0; i < nBufs; i++) {
+    if (sm && sm->multi && !qzstd_hip_ungroup_cmp_pieces) return (size_t)-1; /* a frame of several pieces and a device layer that cannot read one */
+    if (sm) dev = sm->dev;
+    for (i = 0; i < nBufs && !sm; i++) {
         const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
         int d;
         if (!bufs[i].size) continue;
@@ -119,7 +129,7 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
     for (i = 0; i < nBufs && rc == 0; i++) {
         const unsigned e = elemSizes && elemSizes[i] ? elemSizes[i] : f->group;
         const unsigned char *base = bases && bases[i].d_ptr ? (const unsigned char *)bases[i].d_ptr : NULL;
-        size_t off;
+        size_t off, p = sm ? sm->first[i] : 0;
         for (off = 0; off < bufs[i].size; off += f->p.chunkSize, pos += frameSizes[c], c++) {
             const size_t len = bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize;
             const unsigned char *src = (const unsigned char *)frames + (frameStride ? c * frameStride : pos);
@@ -132,10 +142,24 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
                 cur = &parts[nParts++];
                 cur->c0 = c;
                 cur->f0 = cur->f1 = m;
-                cur->bytes = cur->stage = cur->compared = cur->tiles = 0;
+                cur->bytes = cur->stage = cur->compared = cur->tiles = cur->pieces = cur->multi = 0;
             }
             rows[c].d_ref = (const unsigned char *)bufs[i].d_ptr + off;
             rows[c].d_base = base ? base + off : NULL;
+            rows[c].off = off;
+            rows[c].p0 = 0;
+            rows[c].np = 1;
+            if (sm) {
+                const QF_SrcPiece *q;
+                rows[c].np = qfSrcFramePieces(sm, &p, off, len);
+                rows[c].p0 = p;
+                q = &sm->pieces[p];
+                rows[c].d_ref = rows[c].np == 1u ? q->src + (off - q->off) : NULL;
+                rows[c].d_base = rows[c].np == 1u && q->base ? q->base + (off - q->off) : NULL;
+                if (cur->pieces + rows[c].np > 0xFFFFFFFFu) { rc = -1; break; }
+            }
+            cur->pieces += rows[c].np;
+            cur->multi += rows[c].np > 1u;
             rows[c].len = len;
             rows[c].k = e;
             rows[c].m = (size_t)-1;
@@ -192,8 +216,32 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
                         qfGrowD(dev, &s->dCmpRows, &s->dCmpRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_row_t)) ||
                         qfGrowD(dev, &s->dTiles, &s->dTilesCap, pr->tiles * sizeof(uint32_t))))
             rc = -1;
+        if (rc == 0 && pr->multi) {
+            h = s->hCmpPieceRows;
+            if (qfGrowH(&h, &s->hCmpPieceRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t))) rc = -1;
+            s->hCmpPieceRows = (qzstd_hip_ungroup_cmp_pieces_row_t *)h;
+            h = s->hChkPieces;
+            if (rc == 0 && qfGrowH(&h, &s->hChkPiecesCap, pr->pieces * sizeof(qzstd_hip_group_piece_t))) rc = -1;
+            s->hChkPieces = (qzstd_hip_group_piece_t *)h;
+            if (rc == 0 && (qfGrowD(dev, &s->dCmpPieceRows, &s->dCmpPieceRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t)) ||
+                            qfGrowD(dev, &s->dChkPieces, &s->dChkPiecesCap, pr->pieces * sizeof(qzstd_hip_group_piece_t))))
+                rc = -1;
+        }
         if (rc) break;
-        for (c = 0; c < nr; c++) {
+        for (c = 0, tp = 0; pr->multi && c < nr; c++) {
+            const QF_VerifyRow *vr = &rows[pr->c0 + c];
+            qzstd_hip_ungroup_cmp_pieces_row_t *r = &s->hCmpPieceRows[c];
+            r->srcOff = vr->m == (size_t)-1 ? 0u : table[vr->m].at;
+            r->len = (uint32_t)vr->len;
+            r->elem = vr->k;
+            r->flags = vr->m == (size_t)-1 ? QZSTD_HIP_CMP_ZERO : 0u;
+            r->tile0 = 0;
+            r->piece0 = (uint32_t)tp;
+            r->nPieces = (uint32_t)vr->np;
+            qfSrcFrameTable(sm, vr->p0, vr->np, vr->off, vr->len, 1, &s->hChkPieces[tp]);
+            tp += vr->np;
+        }
+        for (c = 0; !pr->multi && c < nr; c++) {
             const QF_VerifyRow *vr = &rows[pr->c0 + c];
             qzstd_hip_ungroup_cmp_row_t *r = &s->hCmpRows[c];
             r->ref = (uint64_t)(uintptr_t)vr->d_ref;
@@ -225,8 +273,11 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
             }
             if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage)) { rc = -1; break; }
         }
-        if (qzstd_hip_ungroup_cmp(dev, s->stream, s->hCmpRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_row_t *)s->dCmpRows, s->dStage, pr->stage,
-                                  (uint32_t *)s->dTiles) ||
+        if ((pr->multi ? qzstd_hip_ungroup_cmp_pieces(dev, s->stream, s->hCmpPieceRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_pieces_row_t *)s->dCmpPieceRows,
+                                                      s->hChkPieces, (uint32_t)pr->pieces, (qzstd_hip_group_piece_t *)s->dChkPieces, s->dStage,
+                                                      pr->stage, (uint32_t *)s->dTiles)
+                       : qzstd_hip_ungroup_cmp(dev, s->stream, s->hCmpRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_row_t *)s->dCmpRows, s->dStage,
+                                               pr->stage, (uint32_t *)s->dTiles)) ||
             qzstd_hip_memcpy_d2h(dev, s->stream, s->hTiles, s->dTiles, pr->tiles * sizeof(uint32_t))) {
             rc = -1;
             break;
@@ -235,6 +286,10 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
         __atomic_fetch_add(&f->verifyStats[0], (unsigned long long)nr, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->verifyStats[2], (unsigned long long)pr->compared, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->verifyStats[3], 1ull, __ATOMIC_RELAXED);
+        if (pr->multi) {
+            sm->counts[0] += (unsigned long long)pr->multi; /* (the call adds them to the front's) */
+            sm->counts[1] += 1ull;
+        }
     }
     /* nothing the library queued may still run when the call returns: a bounded wait first, then an unbounded one */
     for (k = 0; slot && k < 2; k++) {
@@ -261,6 +316,13 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
     f->devBusy = 0;
     pthread_mutex_unlock(&f->mu);
     return rc == 0 ? nDiff : (size_t)-1;
+}
+
+size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
+                                    const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs,
+                                    void *stream, size_t *firstDiff)
+{
+    return qfVerifyDevice(f, frames, frameStride, frameSizes, nFrames, bufs, bases, NULL, elemSizes, nBufs, stream, firstDiff);
 }
 
 void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4])

@@ -125,6 +125,10 @@ over an N GiB stage of 128 KiB rows, alternating: qzstd_hip_group_xor, and qzstd
 64 bytes, for k = 1, 2, 4, 8, ms per GiB; and the upload of each piece table alone.  --kernels: the kernel legs alone.
 
   python tools/device_bench.py --srcslices --gib 1 --reps 3 [--levels 1,6] [--kernels]
+--slicecheck: the same view, checked without a contiguous copy — QZSTD_frontFingerprintDeviceSlices, QZSTD_frontCheckDeviceSlices and
+QZSTD_frontVerifyDeviceSlices against view.contiguous() + the contiguous call and against that call on a contiguous tensor, level 1, with and
+without a base for the verify call; then (or alone, --kernels) the two kernels from pieces beside qzstd_hip_fingerprint / qzstd_hip_ungroup_cmp
+  python tools/device_bench.py --slicecheck --gib 1 --reps 3 [--kernels]
 """
 import argparse
 import json
@@ -1729,9 +1733,209 @@ def srcslices_main(a):
     print(json.dumps(out))
 
 
+def slicecheck_kernels(a, size, out):
+    """qzstd_hip_fingerprint_pieces beside qzstd_hip_fingerprint and qzstd_hip_ungroup_cmp_pieces beside qzstd_hip_ungroup_cmp IN ONE RUN: ONE
+    launch each over the same N GiB as rows of 128 KiB, ms per GiB from events around the launcher call (rows and pieces uploaded inside, from
+    pinned memory), alternating, every run listed after one untimed round; pieces of a whole frame, 8 KiB, 2 KiB and 64 bytes — cut out of the
+    same contiguous source, so the bytes read are the same and only the table differs; the comparison for k = 2 and 4 without a base, its
+    stage the grouped source (every word says SAME); the tile words of every pieces launch are compared with the contiguous launch's"""
+    import ctypes as C
+    import numpy as np
+    plug = B.Plugin()
+    L = D.bind_check_pieces_kernels(D.bind_cmp_kernel(D.bind_fingerprint_kernel(D.bind_xor_kernels(plug.lib))))
+    n = size // a.chunk
+    gib = size / float(1 << 30)
+    torch.manual_seed(0)
+    src = torch.randint(0, 256, (size,), device="cuda:0", dtype=torch.uint8)
+    stage = torch.empty(size + 16, dtype=torch.uint8, device="cuda:0")
+    assert src.data_ptr() % 16 == 0 and stage.data_ptr() % 16 == 0
+    piece_t = np.dtype([("src", "<u8"), ("base", "<u8"), ("off", "<u4"), ("len", "<u4")])
+    fprow_t = np.dtype([("len", "<u4"), ("tile0", "<u4"), ("piece0", "<u4"), ("nPieces", "<u4")])
+    cmprow_t = np.dtype([("srcOff", "<u8"), ("len", "<u4"), ("elem", "<u4"), ("flags", "<u4"), ("tile0", "<u4"), ("piece0", "<u4"), ("nPieces", "<u4")])
+    widths = (("frame", a.chunk), ("8k", 8192), ("2k", 2048), ("64", 64))
+    most = size // 64
+    tiles_n = n * (a.chunk // 16384)
+    pin_p = torch.empty(most * piece_t.itemsize, dtype=torch.uint8).pin_memory()
+    pin_r = torch.empty(n * cmprow_t.itemsize, dtype=torch.uint8).pin_memory()
+    d_pieces = L.qzstd_hip_malloc(0, most * piece_t.itemsize)
+    d_rows = L.qzstd_hip_malloc(0, n * max(cmprow_t.itemsize, C.sizeof(D.GroupXorRow), C.sizeof(D.UngroupCmpRow)))
+    assert d_pieces and d_rows and a.chunk % 16384 == 0
+    fp_a, fp_b = torch.zeros(tiles_n, dtype=torch.int64, device="cuda:0"), torch.zeros(tiles_n, dtype=torch.int64, device="cuda:0")
+    cw_a, cw_b = torch.zeros(tiles_n, dtype=torch.int32, device="cuda:0"), torch.zeros(tiles_n, dtype=torch.int32, device="cuda:0")
+
+    def timed(call):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record()
+        assert call() == 0, plug.err()
+        e1.record()
+        torch.cuda.synchronize()
+        return round(e0.elapsed_time(e1) / gib, 3)
+
+    def table(w):
+        per = a.chunk // w
+        np_ = n * per
+        pieces = pin_p.numpy()[:np_ * piece_t.itemsize].view(piece_t)
+        pieces["src"] = np.uint64(src.data_ptr()) + np.arange(np_, dtype=np.uint64) * np.uint64(w)
+        pieces["base"] = 0
+        pieces["off"] = (np.arange(np_, dtype=np.uint64) % np.uint64(per)) * np.uint64(w)
+        pieces["len"] = w
+        return pieces, np_, per
+
+    cells = {}
+    try:
+        # the fingerprint pair
+        crows = (D.FpRow * n)()
+        for c in range(n):
+            crows[c].src, crows[c].len, crows[c].tile0 = src.data_ptr() + c * a.chunk, a.chunk, 0
+        runs = {"fingerprint": []}
+        rows = pin_r.numpy()[:n * fprow_t.itemsize].view(fprow_t)
+        for name, w in widths:
+            pieces, np_, per = table(w)
+            rows["len"], rows["tile0"], rows["nPieces"] = a.chunk, 0, per
+            rows["piece0"] = np.arange(n, dtype=np.uint64) * np.uint64(per)
+            key = "pieces_" + name
+            runs[key] = []
+            for i in range(a.reps + 1):
+                t0 = timed(lambda: L.qzstd_hip_fingerprint(0, None, crows, n, d_rows, fp_a.data_ptr()))
+                t1 = timed(lambda: L.qzstd_hip_fingerprint_pieces(0, None, rows.ctypes.data, n, d_rows, pieces.ctypes.data, np_, d_pieces, fp_b.data_ptr()))
+                if i:
+                    runs["fingerprint"].append(t0)
+                    runs[key].append(t1)
+            assert torch.equal(fp_a, fp_b), name
+            fp_b.zero_()
+        cells["fingerprint"] = {leg + "_ms_per_gib": v for leg, v in runs.items()}
+        # the comparison pair
+        for k in (2, 4):
+            xrows = (D.GroupXorRow * n)()
+            for c in range(n):
+                x = xrows[c]
+                x.src, x.base, x.dstOff, x.len, x.pad, x.elem = src.data_ptr() + c * a.chunk, 0, c * a.chunk, a.chunk, 16 if c + 1 == n else 0, k
+            assert L.qzstd_hip_group_xor(0, None, xrows, n, d_rows, stage.data_ptr(), size + 16) == 0, plug.err()
+            torch.cuda.synchronize()
+            vrows = (D.UngroupCmpRow * n)()
+            for c in range(n):
+                v = vrows[c]
+                v.ref, v.base, v.srcOff, v.len, v.elem, v.flags, v.tile0 = src.data_ptr() + c * a.chunk, 0, c * a.chunk, a.chunk, k, 0, 0
+            runs = {"ungroup_cmp": []}
+            rows = pin_r.numpy().view(cmprow_t)
+            for name, w in widths:
+                pieces, np_, per = table(w)
+                rows["srcOff"] = np.arange(n, dtype=np.uint64) * np.uint64(a.chunk)
+                rows["len"], rows["elem"], rows["flags"], rows["tile0"], rows["nPieces"] = a.chunk, k, 0, 0, per
+                rows["piece0"] = np.arange(n, dtype=np.uint64) * np.uint64(per)
+                key = "pieces_" + name
+                runs[key] = []
+                for i in range(a.reps + 1):
+                    t0 = timed(lambda: L.qzstd_hip_ungroup_cmp(0, None, vrows, n, d_rows, stage.data_ptr(), size, cw_a.data_ptr()))
+                    t1 = timed(lambda: L.qzstd_hip_ungroup_cmp_pieces(0, None, rows.ctypes.data, n, d_rows, pieces.ctypes.data, np_, d_pieces,
+                                                                      stage.data_ptr(), size, cw_b.data_ptr()))
+                    if i:
+                        runs["ungroup_cmp"].append(t0)
+                        runs[key].append(t1)
+                assert torch.equal(cw_a, cw_b) and bool((cw_a == -1).all()), (k, name)
+                cw_b.zero_()
+            cells["ungroup_cmp_k%d" % k] = {leg + "_ms_per_gib": v for leg, v in runs.items()}
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+        L.qzstd_hip_free(0, d_pieces)
+    out["kernels"] = {"rows": n, "row_bytes": a.chunk, "cells": cells, "piece_table_bytes": {name: size // w * 24 for name, w in widths},
+                      "timed": "events around ONE launcher call each (rows and pieces uploaded inside, from pinned memory) over the same %d rows of %d "
+                               "bytes of random bytes, no base, ms per GiB of rows; the contiguous kernel and the kernel from pieces alternate, every "
+                               "run of %d after one untimed round" % (n, a.chunk, a.reps)}
+
+
+def slicecheck_main(a):
+    """--slicecheck: QZSTD_frontFingerprintDeviceSlices, QZSTD_frontCheckDeviceSlices and QZSTD_frontVerifyDeviceSlices on a column view (the
+    --srcslices setting) against view.contiguous() + the contiguous call and against that call on a tensor that is contiguous already; then the
+    two kernels beside their contiguous neighbours.  --kernels: the kernel legs alone"""
+    import ctypes as C
+    rows_n = (int(a.gib * 65536) + 15) & ~15
+    rowb, width = 16384, 8192
+    size = rows_n * width
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "reps": a.reps, "dtype": "bf16 N(0, 0.02)", "matrix_bytes": [rows_n, rowb],
+           "slices": rows_n, "slice_bytes": width}
+    if a.kernels:
+        slicecheck_kernels(a, int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1), out)
+        return print(json.dumps(out))
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    torch.manual_seed(1)
+    stream = torch.cuda.current_stream().cuda_stream
+    n = size // a.chunk
+    out["timed"] = ("GB/s of tensor bytes, every run, the legs alternating in one run; the window holds the call (the slice and buffer arrays exist "
+                    "before it), for `contiguous` the .contiguous() copies, and the closing synchronize")
+    out["peak_extra_device_bytes"] = ("torch's peak allocation above the level before the call (the .contiguous() temporaries); the library's own "
+                                      "scratch is the same in all legs and not included")
+    mat = (torch.randn(rows_n * rowb // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8).view(rows_n, rowb)
+    bmat = ((mat.view(torch.bfloat16).float() + torch.randn(rows_n, rowb // 2, device="cuda:0") * 1e-5).to(torch.bfloat16)).view(torch.uint8).view(rows_n, rowb)
+    mat, bmat = bmat, mat  # (the new checkpoint is the update; the base is what it came from)
+    view, bview = mat[:, :width], bmat[:, :width]
+    flat, bflat = view.contiguous(), bview.contiguous()
+    out["cells"] = {}
+    fr = D.DeviceFront(a.threads, 1, a.chunk, lib=lib)
+    try:
+        fr.reserve(size)
+        _, sizes = fr._frame_buffers(n)
+        first = (C.c_size_t * 2)()
+        es = bytes([2]) + b"\0"
+        bs = (C.c_size_t * 1)(size)
+        fp = (C.c_ulonglong * n)()
+        got = (C.c_ulonglong * n)()
+        flags = C.create_string_buffer(n)
+        fd = (C.c_size_t * n)()
+        fbufs, fbase = fr.batch([(flat.data_ptr(), size)])[0], fr.batch([(bflat.data_ptr(), size)])[0]
+        assert fr.lib.QZSTD_frontFingerprintDeviceBatch(fr.f, fbufs, 1, stream, fp, None) == n
+        for based in (False, True):
+            sl = [(0, r * width, width, view.data_ptr() + r * rowb, bview.data_ptr() + r * rowb if based else None) for r in range(rows_n)]
+            arr = fr.src_slice_array(sl)
+            assert fr.lib.QZSTD_frontCompressDeviceBatchDelta(fr.f, fbufs, fbase if based else None, es, 1, stream, fr._dst, len(fr._dst), sizes, first) == n
+            cbuf = lambda t: fr.batch([(t.data_ptr(), size)])[0]  # noqa: E731
+            calls = {
+                "fingerprint": (lambda: fr.lib.QZSTD_frontFingerprintDeviceSlices(fr.f, bs, 1, arr, rows_n, stream, got, None),
+                                lambda t, b: fr.lib.QZSTD_frontFingerprintDeviceBatch(fr.f, cbuf(t), 1, stream, got, None), n),
+                "check": (lambda: fr.lib.QZSTD_frontCheckDeviceSlices(fr.f, bs, 1, arr, rows_n, stream, fp, n, flags),
+                          lambda t, b: fr.lib.QZSTD_frontCheckDeviceBatch(fr.f, cbuf(t), 1, stream, fp, n, flags), 0),
+                "verify": (lambda: fr.lib.QZSTD_frontVerifyDeviceSlices(fr.f, fr._dst, fr.stride, sizes, n, bs, es, 1, arr, rows_n, stream, fd),
+                           lambda t, b: fr.lib.QZSTD_frontVerifyDeviceBatch(fr.f, fr._dst, fr.stride, sizes, n, cbuf(t), cbuf(b) if based else None, es, 1,
+                                                                            stream, fd), 0)}
+            for what, (on_slices, on_buffer, want) in calls.items():
+                if based and what != "verify":
+                    continue  # (a base is no part of a fingerprint)
+                legs = (("slices", on_slices), ("contiguous", lambda: on_buffer(view.contiguous(), bview.contiguous() if based else None)),
+                        ("typed", lambda: on_buffer(flat, bflat)))
+                cell = out["cells"]["%s_%s" % (what, "base" if based else "nobase")] = {}
+                for name, leg in legs:  # untimed, and checked
+                    torch.cuda.synchronize()
+                    torch.cuda.reset_peak_memory_stats()
+                    m0, p0 = torch.cuda.memory_allocated(), fr.slice_check_stats()
+                    assert leg() == want, (what, name)
+                    torch.cuda.synchronize()
+                    cell[name] = {"peak_extra_device_bytes": torch.cuda.max_memory_allocated() - m0, "gbps": []}
+                    if what == "fingerprint":
+                        assert list(got) == list(fp), name
+                    if name == "slices":
+                        cell[name]["slice_check_stats"] = [y - x for x, y in zip(p0, fr.slice_check_stats())]
+                for _ in range(a.reps):
+                    for name, leg in legs:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        assert leg() == want, (what, name)
+                        torch.cuda.synchronize()
+                        cell[name]["gbps"].append(round(size / (time.perf_counter() - t0) / 1e9, 3))
+    finally:
+        fr.close()
+    del mat, bmat, view, bview, flat, bflat
+    torch.cuda.empty_cache()
+    slicecheck_kernels(a, int(a.gib * (1 << 30)) & ~(64 * a.chunk - 1), out)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--srcslices", action="store_true")
+    ap.add_argument("--slicecheck", action="store_true")
     ap.add_argument("--advise", action="store_true")
     ap.add_argument("--ediff", action="store_true")
     ap.add_argument("--fingerprint", action="store_true")
@@ -1755,6 +1959,8 @@ def main():
     ap.add_argument("--chunk", type=int, default=131072)
     ap.add_argument("--levels", default="1,6,12")
     a = ap.parse_args()
+    if a.slicecheck:
+        return slicecheck_main(a)
     if a.srcslices:
         if a.levels == "1,6,12":
             a.levels = "1,6"

@@ -362,6 +362,27 @@ def bind_pieces_kernel(L):
     return L
 
 
+class FpPiecesRow(C.Structure):
+    """qzstd_hip_fp_pieces_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("len", C.c_uint32), ("tile0", C.c_uint32), ("piece0", C.c_uint32), ("nPieces", C.c_uint32)]
+
+
+class UngroupCmpPiecesRow(C.Structure):
+    """qzstd_hip_ungroup_cmp_pieces_row_t (include/qzstd_hip_device.h)"""
+    _fields_ = [("srcOff", C.c_uint64), ("len", C.c_uint32), ("elem", C.c_uint32), ("flags", C.c_uint32), ("tile0", C.c_uint32),
+                ("piece0", C.c_uint32), ("nPieces", C.c_uint32)]
+
+
+def bind_check_pieces_kernels(L):
+    """qzstd_hip_fingerprint_pieces / qzstd_hip_ungroup_cmp_pieces on a loaded device layer (libqatseqprod, or a mock of it)"""
+    L.qzstd_hip_fingerprint_pieces.restype = C.c_int
+    L.qzstd_hip_fingerprint_pieces.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    L.qzstd_hip_ungroup_cmp_pieces.restype = C.c_int
+    L.qzstd_hip_ungroup_cmp_pieces.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                               C.c_size_t, C.c_void_p]
+    return L
+
+
 def bind_window_kernel(L):
     """qzstd_hip_ungroup_window on a loaded device layer (libqatseqprod)"""
     L.qzstd_hip_ungroup_window.restype = C.c_int
@@ -490,6 +511,18 @@ def bind(F):
                                                   C.c_void_p]
         F.QZSTD_frontFingerprintStats.restype = None
         F.QZSTD_frontFingerprintStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontFingerprintDeviceSlices"):  # (absent from an older library)
+        F.QZSTD_frontFingerprintDeviceSlices.restype = C.c_size_t
+        F.QZSTD_frontFingerprintDeviceSlices.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(DeviceSrcSlice), C.c_size_t, C.c_void_p,
+                                                         C.POINTER(C.c_ulonglong), C.POINTER(C.c_size_t)]
+        F.QZSTD_frontCheckDeviceSlices.restype = C.c_size_t
+        F.QZSTD_frontCheckDeviceSlices.argtypes = [C.c_void_p, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(DeviceSrcSlice), C.c_size_t, C.c_void_p,
+                                                   C.POINTER(C.c_ulonglong), C.c_size_t, C.c_void_p]
+        F.QZSTD_frontVerifyDeviceSlices.restype = C.c_size_t
+        F.QZSTD_frontVerifyDeviceSlices.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_size_t, C.POINTER(C.c_size_t),
+                                                    C.c_char_p, C.c_size_t, C.POINTER(DeviceSrcSlice), C.c_size_t, C.c_void_p, C.POINTER(C.c_size_t)]
+        F.QZSTD_frontSliceCheckStats.restype = None
+        F.QZSTD_frontSliceCheckStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
     if hasattr(F, "QZSTD_frontElemDiffStats"):  # (absent from an older library)
         F.QZSTD_frontElemDiffStats.restype = None
         F.QZSTD_frontElemDiffStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
@@ -1113,6 +1146,58 @@ class DeviceFront:
         """[0] frames fingerprinted, [1] bytes read on the device, [2] qzstd_hip_fingerprint launches, [3] frames a check found differing"""
         st = (C.c_ulonglong * 4)()
         self.lib.QZSTD_frontFingerprintStats(self.f, st)
+        return list(st)
+
+    def _slice_args(self, buf_sizes, slices):
+        nb = 0 if buf_sizes is None else len(buf_sizes)
+        bs = None if buf_sizes is None else (C.c_size_t * max(nb, 1))(*buf_sizes)
+        return bs, nb, (None if slices is None else self.src_slice_array(slices)), (0 if slices is None else len(slices))
+
+    def fingerprint_slices_raw(self, buf_sizes, slices, stream: int | None = None, null_fp: bool = False):
+        """QZSTD_frontFingerprintDeviceSlices (buf_sizes and slices as compress_device_slices_raw's) -> (return value, the fingerprints as a
+        flat list or None, firstFrame as a list)"""
+        bs, nb, arr, ns = self._slice_args(buf_sizes, slices)
+        n = sum(-(-b // self.chunk) for b in buf_sizes or ())
+        fp = (C.c_ulonglong * max(n, 1))()
+        first = (C.c_size_t * (nb + 1))()
+        r = self.lib.QZSTD_frontFingerprintDeviceSlices(self.f, bs, nb, arr, ns, C.c_void_p(stream or None), None if null_fp else fp, first)
+        return r, (list(fp)[:n] if r == n else None), list(first)
+
+    def fingerprint_slices(self, buf_sizes, slices, stream: int | None = None) -> list:
+        """per logical buffer the fingerprints of its chunks"""
+        r, fp, first = self.fingerprint_slices_raw(buf_sizes, slices, stream)
+        if fp is None:
+            raise RuntimeError("QZSTD_frontFingerprintDeviceSlices failed")
+        return [fp[first[i]:first[i + 1]] for i in range(len(buf_sizes))]
+
+    def check_slices_raw(self, buf_sizes, slices, expected, stream: int | None = None, n_frames: int | None = None, want_flags: bool = True):
+        """QZSTD_frontCheckDeviceSlices against a flat list of fingerprints (None: a null pointer) -> (return value: the number of differing
+        frames or ERROR, differs as a flat list or None)"""
+        bs, nb, arr, ns = self._slice_args(buf_sizes, slices)
+        n = len(expected) if expected is not None else 0
+        ex = None if expected is None else (C.c_ulonglong * max(n, 1))(*expected)
+        flags = C.create_string_buffer(b"\x07" * max(n, 1), max(n, 1)) if want_flags else None
+        r = self.lib.QZSTD_frontCheckDeviceSlices(self.f, bs, nb, arr, ns, C.c_void_p(stream or None), ex, n if n_frames is None else n_frames, flags)
+        return r, (list(flags.raw[:n]) if want_flags else None)
+
+    def verify_slices_raw(self, frames_per_buffer, buf_sizes, elem_sizes, slices, stream: int | None = None, compact: bool = False,
+                          n_frames: int | None = None, want_offsets: bool = True):
+        """QZSTD_frontVerifyDeviceSlices: per buffer its list of frames, compared with the LIVE slices [(buffer index, offset, size, source
+        address, base address or None), ...] -> (return value: the number of differing frames or ERROR, firstDiff as a flat list or None)"""
+        flat = [f for fr in frames_per_buffer for f in fr]
+        first = (C.c_size_t * max(len(flat), 1))(*([7] * max(len(flat), 1))) if want_offsets else None
+        bs, nb, arr, ns = self._slice_args(buf_sizes, slices)
+        buf, stride, sizes = self.pack_frames(flat, compact)
+        es = None if elem_sizes is None else bytes(bytearray(elem_sizes)) + b"\0"
+        r = self.lib.QZSTD_frontVerifyDeviceSlices(self.f, buf, stride, sizes, len(flat) if n_frames is None else n_frames, bs, es, nb, arr, ns,
+                                                   C.c_void_p(stream or None), first)
+        return r, (list(first)[:len(flat)] if want_offsets else None)
+
+    def slice_check_stats(self) -> list:
+        """QZSTD_frontSliceCheckStats: [0] non-empty slices of the calls that succeeded, [1] their bytes, [2] frames assembled from more than
+        one piece, [3] launches of qzstd_hip_fingerprint_pieces and qzstd_hip_ungroup_cmp_pieces"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontSliceCheckStats(self.f, st)
         return list(st)
 
     def advise_raw(self, ptrs_and_sizes, elem_sizes=None, stream: int | None = None, null_advised: bool = False, want_est: bool = True):
