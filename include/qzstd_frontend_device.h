@@ -258,6 +258,42 @@ void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4]);
 unsigned QZSTD_planeCostOf(const unsigned hist[256], unsigned len);
 int QZSTD_planeIsRawOf(unsigned cost, unsigned len, unsigned matchedBytes);
 
+/* Plane code, OFF by default: blocks whose matches are not worth their sequences — the sign/exponent plane of float weights — are written as
+ * Huffman-only Compressed blocks whose streams the GPU codes (include/qzstd_hufblock.h).  With the setting off every call is launch for launch
+ * and byte for byte what it was.
+ *
+ * With it on, the front behaves as with the plane probe on (whatever that setting says), and a part that would be probed gets
+ * qzstd_hip_huf_code INSTEAD of qzstd_hip_plane_cost: the same cost word per block, a size word and a dense offset per block (they travel
+ * with the compaction headers and the costs: no wait of their own), and for the blocks of 1 KiB and more that a Huffman code shrinks, 128
+ * bytes of code lengths, the jump table and the four streams, packed densely: one more copy behind the header wait.  A block is TAKEN when
+ * QZSTD_hufTakes holds over its size word, the bytes of its QZSTD_hufBlockBody, its length and its compaction header.  A frame whose every
+ * block is raw-predicted or taken is assembled WITHOUT ANY libzstd CALL: the header of an assembled frame, per raw-predicted block what the
+ * probe writes, per taken block a 3-byte Compressed_Block header and QZSTD_hufBlockBody — literals section header, tree description (written
+ * on the host from the code lengths), jump table and streams as the GPU left them, and one 0x00: no sequences.  All or nothing per frame: a
+ * frame with any other block takes exactly the path it takes with the probe on.  Checksums are those of assembled frames;
+ * the zero frames of a delta skip and frames with a failed block are untouched.  The frames are ordinary zstd frames: the restore, slices and
+ * verify calls and any zstd decoder read them as before.
+ *
+ * Not done: a taken block's literals and entries still come back in the arena, so device-to-host bytes per input byte go up,
+ * not down; the matcher is not skipped for taken blocks; no sequences are coded and nothing is decoded on the GPU; blocks under 1 KiB are
+ * never taken.
+ *
+ * With the setting on, a call with a grouped or based frame and a device layer without qzstd_hip_huf_code returns (size_t)-1 before anything
+ * is queued.  QZSTD_frontDeviceStats [2] counts the words and the dense area; QZSTD_frontPlaneProbeStats counts as with the probe on (a frame
+ * assembled here in [2], its raw blocks in [1]).
+ *
+ * Set: 0, or -1 for f NULL or while a call runs on the front.  Get: 0 / 1 (0 for f NULL). */
+int QZSTD_frontSetPlaneCode(QZSTD_Front *f, int on);
+int QZSTD_frontGetPlaneCode(const QZSTD_Front *f);
+/* since creation: [0] rows (blocks) the kernel coded, [1] blocks taken, [2] frames assembled without a libzstd call (all their blocks
+ * raw-predicted or taken), [3] frames with a taken block that fell back to the probe's path */
+void QZSTD_frontPlaneCodeStats(QZSTD_Front *f, unsigned long long stats[4]);
+/* QZSTD_hufBlockBody (over the 128 bytes of code lengths as qzstd_hip_huf_code leaves them) and QZSTD_hufTakes of include/qzstd_hufblock.h as
+ * exported functions (bindings that cannot include the header) */
+size_t QZSTD_hufBlockBodyOf(const unsigned char lengths[128], unsigned len, const unsigned char *streams, size_t streamBytes, unsigned char *dst,
+                            size_t cap);
+int QZSTD_hufTakesOf(unsigned streamBytes, unsigned bodyBytes, unsigned len, unsigned litBytes, unsigned count);
+
 /* Slices: byte ranges of the buffers AS THEY WERE WRITTEN restored into device memory — a checkpoint written by one rank layout and loaded
  * by another (a row shard: one contiguous slice per tensor; a column shard of an [R, C] matrix: R slices of one buffer) — without a
  * temporary of the buffers' size and without decoding the frames no slice touches.  frames / frameStride / frameSizes / nFrames are the WHOLE

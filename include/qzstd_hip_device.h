@@ -386,6 +386,40 @@ int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzs
                          qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost);
 
 /*
+ * Huffman literals coder (include/qzstd_hufblock.h): the rows of qzstd_hip_plane_cost, and per row the SAME cost word in d_cost — a caller
+ * queues this launch instead of that one — plus, for the rows worth it, the jump table and the four Huffman streams of a zstd
+ * Compressed_Literals_Block, computed on the device with that header's own definitions.
+ *
+ * Per row (one workgroup of 256 threads): the byte histogram in LDS as in the cost kernel (aligned 16-byte loads of the words that overlap
+ * the row and of no other word), the cost word, the code lengths (the bytes that occur are ranked by the workgroup, then
+ * QZSTD_hufLengthsSorted on one lane), the canonical codes; then one wave per stream, a lane per run of consecutive bytes: the lanes sum
+ * their runs' code lengths, a scan per stream in the stream's reversed order gives every run its bit offset, and the lanes pack — whole 32-bit
+ * words straight to memory, the words a lane shares with its neighbours merged in LDS and stored once.
+ *
+ *   d_size[i]   the row's size word: bytes of jump table + streams, or 0 — len outside QZSTD_HUF_LEN_MIN .. QZSTD_HUF_LEN_MAX, fewer than two
+ *               distinct bytes, or jump table + streams not below len - ((len >> 6) + 2) (QZSTD_hufSizeWord)
+ *   d_off[i]    where row i's bytes start in d_dense, i = 0 .. nRows; d_off[nRows] is the bytes used.  A multiple of 16 each.
+ *   d_dense     for every row with a size word, in row order: QZSTD_HUF_LENGTHS_BYTES (128) of code lengths, a nibble each
+ *               (QZSTD_hufPackLengths), the d_size[i] bytes, and zeros up to the next multiple of 16.  Other rows take no room.
+ *
+ * Four launches on `stream`: a scan of the rows' scratch needs, the coder (into d_scratch, a row's bytes at a place of its own), a scan of
+ * the size words into d_off, and a copy into d_dense; no workgroup waits for another.  No global atomics, no memset; nothing is written
+ * but d_rows, d_cost, d_size, d_off[0 .. nRows], d_dense[0 .. d_off[nRows]) and d_scratch.
+ *
+ * qzstd_hip_huf_code_bytes(rows, nRows): the bytes of d_dense that every outcome fits in — the sum of QZSTD_HIP_HUF_ROW_BYTES(len) — or
+ * (size_t)-1 when that is 4 GiB or more.  d_scratch needs QZSTD_HIP_HUF_SCRATCH_BYTES(nRows, that).  Both 16-byte aligned.
+ *
+ * `rows` is HOST memory as for qzstd_hip_plane_cost.  Refused (< 0) before anything is queued: what qzstd_hip_plane_cost refuses, a null
+ * d_size, d_off, d_dense or d_scratch, a d_dense or d_scratch that is not 16-byte aligned or too small.  nRows == 0: nothing happens.
+ */
+#define QZSTD_HIP_HUF_ROW_BYTES(len) ((len) >= 1024u && (len) <= 131072u ? (((size_t)(len) + 15u) & ~(size_t)15u) + 128u : (size_t)0)
+#define QZSTD_HIP_HUF_SCRATCH_BYTES(nRows, denseBytes) (((((size_t)(nRows) + 1u) * 4u + 15u) & ~(size_t)15u) + (size_t)(denseBytes))
+size_t qzstd_hip_huf_code_bytes(const qzstd_hip_plane_row_t *rows, uint32_t nRows);
+int qzstd_hip_huf_code(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                       qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost, uint32_t *d_size, uint32_t *d_off, void *d_dense, size_t denseBytes,
+                       void *d_scratch, size_t scratchBytes);
+
+/*
  * Fingerprint (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch): ONE launch digests every row — `len` bytes anywhere in device
  * memory, at any alignment — tile by tile: d_tiles[tile0 + j] = QZSTD_fpTile of include/qzstd_fingerprint.h over the row's j-th 16 KiB (the
  * last tile: what is left), computed on the device with that header's own functions.  The host folds a row's tile digests into its

@@ -1715,6 +1715,314 @@ extern "C" int qzstd_hip_plane_cost(int device, void *stream, const void *d_base
     return 0;
 }
 
+/* ---------------------------------------------------------------- Huffman literals coder (include/qzstd_hip_device.h, qzstd_hufblock.h) -- */
+#include "qzstd_hufblock.h"
+
+namespace {
+constexpr uint32_t kHufT = kPlaneT; /* four waves: one per stream */
+
+__device__ inline uint32_t huf_round16(uint32_t x) { return (x + 15u) & ~15u; }
+
+/* off[i] <- f(0) + .. + f(i - 1) for i = 0 .. n, by ONE workgroup, kHufT rows a step.  sizes == nullptr: f(i) = QZSTD_HIP_HUF_ROW_BYTES of row
+ * i's len (a row's place in the scratch); else f(i) = the bytes row i takes in the dense area, 0 without a size word.  The launcher has
+ * checked that the sums stay below 2^32. */
+__global__ __launch_bounds__(kHufT) void qzstd_huf_scan_kernel(const qzstd_hip_plane_row_t *__restrict__ rows, const uint32_t *__restrict__ sizes,
+                                                               uint32_t n, uint32_t *__restrict__ off)
+{
+    __shared__ uint32_t red[kHufT / 64u];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    uint32_t carry = 0u;
+    for (uint32_t c = 0; c < n; c += kHufT) {
+        const uint32_t i = c + threadIdx.x;
+        uint32_t mine = 0u;
+        if (i < n) {
+            if (sizes) mine = sizes[i] ? huf_round16(QZSTD_HUF_LENGTHS_BYTES + sizes[i]) : 0u;
+            else mine = (uint32_t)QZSTD_HIP_HUF_ROW_BYTES(rows[i].len);
+        }
+        uint32_t incl = mine;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t o = (uint32_t)__shfl_up((int)incl, d, 64);
+            if (lane >= d) incl += o;
+        }
+        if (lane == 63u) red[wave] = incl;
+        __syncthreads();
+        uint32_t before = carry, all = 0u;
+#pragma unroll
+        for (uint32_t w = 0; w < kHufT / 64u; w++) {
+            if (w < wave) before += red[w];
+            all += red[w];
+        }
+        __syncthreads(); /* red is rewritten by the next step */
+        if (i < n) off[i] = before + incl - mine;
+        carry += all;
+    }
+    if (threadIdx.x == 0) off[n] = carry;
+}
+
+/* One workgroup per row; see include/qzstd_hip_device.h.  A row's bytes go to stage + stageOff[row]: 128 bytes of lengths, then the jump table
+ * and the streams, as 32-bit words (the place is 16-byte aligned; the last word may reach up to 3 bytes past the streams, inside the row's
+ * QZSTD_HIP_HUF_ROW_BYTES).
+ *
+ * The bits of jump table + streams are one string of 8 * size bits, cut among the 256 threads in the order q = 64 * stream + (63 - lane):
+ * thread q writes the bits [S[q], S[q + 1]) — its run's codes from the run's last byte to its first; the stream's first lane also the closing
+ * 1 bit and the zeros up to the byte; q = 0 also the jump table in front.  A word that lies wholly inside a thread's bits is stored by it.
+ * A word shared by several threads is put together in edge[q], q the thread that holds the word's FIRST bit (found by a search over S; for a
+ * thread's last, unfinished word that is the thread itself), with LDS atomic ORs, and stored by that thread after the barrier. */
+__global__ __launch_bounds__(kHufT) void qzstd_huf_code_kernel(const uint8_t *__restrict__ base, const qzstd_hip_plane_row_t *__restrict__ rows,
+                                                               const uint32_t *__restrict__ stageOff, uint32_t *__restrict__ cost,
+                                                               uint32_t *__restrict__ size, uint8_t *__restrict__ stage)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t hist[256u * kPlaneCopies];
+    __shared__ uint32_t cnt[256], keys[256], tab[256], S[kHufT + 1u], edge[kHufT], red[kHufT / 64u], streamBits[4];
+    __shared__ uint8_t nbits[256];
+    __shared__ QZSTD_hufWksp ws;
+    const uint32_t tid = threadIdx.x;
+    const qzstd_hip_plane_row_t row = rows[blockIdx.x];
+    const uint32_t len = row.len;
+    for (uint32_t i = tid; i < 256u * kPlaneCopies; i += kHufT) hist[i] = 0u;
+    edge[tid] = 0u;
+    __syncthreads();
+    const uint64_t a = (uint64_t)(uintptr_t)base + row.srcOff;
+    {   /* the histogram and the cost word: qzstd_plane_cost_kernel's */
+        const uint32_t head = (uint32_t)a & 15u;
+        const uint4 *words = reinterpret_cast<const uint4 *>(a - head);
+        const uint32_t span = head + len;
+        const uint32_t nWords = len ? (span + 15u) >> 4 : 0u;
+        uint32_t *mine = &hist[tid & (kPlaneCopies - 1u)];
+        for (uint32_t w = tid; w < nWords; w += kHufT) {
+            const uint4 v = words[w];
+            const uint32_t d[4] = { v.x, v.y, v.z, v.w };
+            const uint32_t lo = w ? 0u : head, hi = span - w * 16u < 16u ? span - w * 16u : 16u;
+            if (lo == 0u && hi == 16u) {
+#pragma unroll
+                for (uint32_t b = 0; b < 16u; b++) atomicAdd(&mine[((d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu) * kPlaneCopies], 1u);
+            } else {
+#pragma unroll
+                for (uint32_t b = 0; b < 16u; b++)
+                    if (b >= lo && b < hi) atomicAdd(&mine[((d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu) * kPlaneCopies], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t c = 0u;
+    {
+        const uint4 *h = reinterpret_cast<const uint4 *>(&hist[tid * kPlaneCopies]);
+#pragma unroll
+        for (uint32_t j = 0; j < kPlaneCopies / 4u; j++) {
+            const uint4 q = h[j];
+            c += q.x + q.y + q.z + q.w;
+        }
+    }
+    cnt[tid] = c;
+    uint32_t sum = QZSTD_planeTerm(c, QZSTD_planeLog2(len));
+#pragma unroll
+    for (uint32_t s = 32u; s; s >>= 1) sum += (uint32_t)__shfl_xor((int)sum, (int)s, 64);
+    if ((tid & 63u) == 0u) red[tid >> 6] = sum;
+    const uint32_t present = (uint32_t)__syncthreads_count(c != 0u);
+    if (tid == 0) {
+        uint32_t total = red[0];
+#pragma unroll
+        for (uint32_t w = 1; w < kHufT / 64u; w++) total += red[w];
+        cost[blockIdx.x] = QZSTD_planeCostOfSum(total);
+    }
+    if (len < QZSTD_HUF_LEN_MIN || len > QZSTD_HUF_LEN_MAX || present < 2u) { /* (the same for every thread) */
+        if (tid == 0) size[blockIdx.x] = 0u;
+        return;
+    }
+    /* the bytes that occur, ascending by (count, value): every thread ranks its own */
+    if (c) {
+        const uint32_t key = (c << 8) | tid;
+        uint32_t rank = 0u;
+        for (uint32_t u = 0; u < 256u; u++) {
+            const uint32_t cu = cnt[u];
+            rank += (cu != 0u && ((cu << 8) | u) < key) ? 1u : 0u;
+        }
+        keys[rank] = key;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        (void)QZSTD_hufLengthsSorted(keys, present, nbits, &ws);
+        QZSTD_hufCodes(nbits, tab);
+    }
+    __syncthreads();
+    /* one wave per stream, a lane per run of consecutive bytes */
+    const uint32_t k = tid >> 6, lane = tid & 63u, q = k * 64u + (63u - lane);
+    uint32_t segStart, segEnd;
+    QZSTD_hufStreamSpan(len, k, &segStart, &segEnd);
+    const uint32_t segLen = segEnd - segStart, run = (segLen + 63u) >> 6;
+    const uint32_t rs = segStart + (lane * run < segLen ? lane * run : segLen);
+    const uint32_t re = segStart + ((lane + 1u) * run < segLen ? (lane + 1u) * run : segLen);
+    const uint64_t A0 = a + rs, A1 = a + re; /* the run's bytes; A0 == A1: none */
+    uint32_t bits = 0u;
+    if (A1 > A0) {
+        for (uint64_t wa = A0 & ~15ull; wa < A1; wa += 16u) {
+            const uint4 v = *reinterpret_cast<const uint4 *>(wa);
+            const uint32_t d[4] = { v.x, v.y, v.z, v.w };
+            const uint32_t lo = wa < A0 ? (uint32_t)(A0 - wa) : 0u, hi = A1 - wa < 16u ? (uint32_t)(A1 - wa) : 16u;
+#pragma unroll
+            for (uint32_t b = 0; b < 16u; b++)
+                if (b >= lo && b < hi) bits += tab[(d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu] >> 16;
+        }
+    }
+    /* the run's bit offset in its stream: the bits of the runs behind it (the stream is written from its last byte) */
+    uint32_t incl = bits;
+#pragma unroll
+    for (uint32_t d = 1; d < 64u; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_down((int)incl, d, 64);
+        if (lane + d < 64u) incl += o;
+    }
+    if (lane == 0u) streamBits[k] = incl;
+    __syncthreads();
+    uint32_t byteOff[5];
+    byteOff[0] = QZSTD_HUF_JUMP_BYTES;
+#pragma unroll
+    for (uint32_t j = 0; j < 4u; j++) byteOff[j + 1u] = byteOff[j] + QZSTD_hufStreamBytes(streamBits[j]);
+    const uint32_t sizeWord = QZSTD_hufSizeWord(byteOff[4], len);
+    if (!sizeWord) { /* (the same for every thread) */
+        if (tid == 0) size[blockIdx.x] = 0u;
+        return;
+    }
+    S[q] = q ? 8u * byteOff[k] + (incl - bits) : 0u;
+    if (tid == 0) S[kHufT] = 8u * sizeWord;
+    __syncthreads();
+    uint8_t *mine = stage + stageOff[blockIdx.x];
+    uint32_t *out = reinterpret_cast<uint32_t *>(mine + QZSTD_HUF_LENGTHS_BYTES);
+    const uint32_t myStart = S[q], myNext = S[q + 1u];
+    if (myNext > myStart) {
+        uint32_t wordIdx = myStart >> 5, fill = myStart & 31u, owner = q;
+        bool headShared = fill != 0u;
+        uint64_t acc = 0ull;
+        if (headShared) { /* the last thread whose bits begin at or before the word's first bit */
+            const uint32_t x = myStart & ~31u;
+            uint32_t lo = 0u, hi = q; /* S[lo] <= x < S[hi] */
+            while (hi - lo > 1u) {
+                const uint32_t mid = (lo + hi) >> 1;
+                if (S[mid] <= x) lo = mid;
+                else hi = mid;
+            }
+            owner = lo;
+        }
+        auto emit = [&](uint32_t v, uint32_t nb) {
+            acc |= (uint64_t)v << fill;
+            fill += nb;
+            if (fill >= 32u) {
+                if (headShared) {
+                    atomicOr(&edge[owner], (uint32_t)acc);
+                    headShared = false;
+                } else {
+                    out[wordIdx] = (uint32_t)acc;
+                }
+                acc >>= 32;
+                fill -= 32u;
+                wordIdx++;
+            }
+        };
+        if (q == 0u) {
+#pragma unroll
+            for (uint32_t j = 0; j < 3u; j++) emit(byteOff[j + 1u] - byteOff[j], 16u);
+        }
+        if (A1 > A0) {
+            for (uint64_t wa = (A1 - 1u) & ~15ull;; wa -= 16u) {
+                const uint4 v = *reinterpret_cast<const uint4 *>(wa);
+                const uint32_t d[4] = { v.x, v.y, v.z, v.w };
+                const uint32_t lo = wa < A0 ? (uint32_t)(A0 - wa) : 0u, hi = A1 - wa < 16u ? (uint32_t)(A1 - wa) : 16u;
+#pragma unroll
+                for (uint32_t b = 16u; b-- > 0u;) {
+                    if (b >= lo && b < hi) {
+                        const uint32_t t = tab[(d[b >> 2] >> ((b & 3u) * 8u)) & 0xFFu];
+                        emit(t & 0xFFFFu, t >> 16);
+                    }
+                }
+                if (wa <= (A0 & ~15ull)) break;
+            }
+        }
+        if (lane == 0u) {
+            emit(1u, 1u);
+            emit(0u, 7u - (streamBits[k] & 7u));
+        }
+        if (fill) atomicOr(&edge[headShared ? owner : q], (uint32_t)acc);
+    }
+    __syncthreads();
+    if (myNext > myStart && (myNext & 31u) && myStart <= (myNext & ~31u)) out[myNext >> 5] = edge[q];
+    if (tid < QZSTD_HUF_LENGTHS_BYTES / 4u) {
+        uint32_t w = 0u;
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; j++) w |= (uint32_t)(nbits[8u * tid + 2u * j] | (nbits[8u * tid + 2u * j + 1u] << 4)) << (8u * j);
+        reinterpret_cast<uint32_t *>(mine)[tid] = w;
+    }
+    if (tid == 0) size[blockIdx.x] = sizeWord;
+}
+
+/* the kept rows' bytes from their places in the scratch to the dense area, 16 bytes a thread; what lies behind lengths + size in the last 16 is
+ * written as zeros */
+__global__ __launch_bounds__(kHufT) void qzstd_huf_pack_kernel(const uint32_t *__restrict__ size, const uint32_t *__restrict__ stageOff,
+                                                               const uint32_t *__restrict__ off, const uint8_t *__restrict__ stage,
+                                                               uint8_t *__restrict__ dense)
+{
+    const uint32_t sz = size[blockIdx.x];
+    if (!sz) return;
+    const uint32_t bytes = QZSTD_HUF_LENGTHS_BYTES + sz, nWords = (bytes + 15u) >> 4;
+    const uint4 *src = reinterpret_cast<const uint4 *>(stage + stageOff[blockIdx.x]);
+    uint4 *dst = reinterpret_cast<uint4 *>(dense + off[blockIdx.x]);
+    for (uint32_t w = threadIdx.x; w < nWords; w += kHufT) {
+        uint4 v = src[w];
+        const uint32_t valid = bytes - w * 16u;
+        if (valid < 16u) {
+            uint32_t d[4] = { v.x, v.y, v.z, v.w };
+#pragma unroll
+            for (uint32_t j = 0; j < 4u; j++) {
+                const uint32_t nv = valid > 4u * j ? (valid - 4u * j < 4u ? valid - 4u * j : 4u) : 0u;
+                d[j] &= nv >= 4u ? 0xFFFFFFFFu : (1u << (8u * nv)) - 1u;
+            }
+            v = make_uint4(d[0], d[1], d[2], d[3]);
+        }
+        dst[w] = v;
+    }
+}
+} // namespace
+
+extern "C" size_t qzstd_hip_huf_code_bytes(const qzstd_hip_plane_row_t *rows, uint32_t nRows)
+{
+    unsigned long long sum = 0u;
+    for (uint32_t i = 0; i < nRows; i++) sum += QZSTD_HIP_HUF_ROW_BYTES(rows[i].len);
+    return sum >= 0xFFFFFFF0ull ? (size_t)-1 : (size_t)sum;
+}
+
+extern "C" int qzstd_hip_huf_code(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                                  qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost, uint32_t *d_size, uint32_t *d_off, void *d_dense,
+                                  size_t denseBytes, void *d_scratch, size_t scratchBytes)
+{
+    if (nRows == 0) return 0;
+    if (!rows || !d_rows || !d_cost) return fail_msg("qzstd_hip_huf_code: null pointer");
+    if (nRows > 0x7FFFFFFFu) return fail_msg("qzstd_hip_huf_code: too many rows");
+    for (uint32_t i = 0; i < nRows; i++) {
+        if (rows[i].len > QZSTD_PLANE_LEN_MAX) return fail_msg("qzstd_hip_huf_code: a row longer than 128 KiB");
+        if (rows[i].reserved) return fail_msg("qzstd_hip_huf_code: reserved not 0");
+        if (rows[i].len && !d_base) return fail_msg("qzstd_hip_huf_code: null base");
+    }
+    if (!d_size || !d_off || !d_dense || !d_scratch) return fail_msg("qzstd_hip_huf_code: null output");
+    if (((uintptr_t)d_dense & 15u) || ((uintptr_t)d_scratch & 15u)) return fail_msg("qzstd_hip_huf_code: dense area or scratch not 16-byte aligned");
+    const size_t need = qzstd_hip_huf_code_bytes(rows, nRows);
+    if (need == (size_t)-1) return fail_msg("qzstd_hip_huf_code: 4 GiB of rows or more");
+    if (denseBytes < need || scratchBytes < QZSTD_HIP_HUF_SCRATCH_BYTES(nRows, need)) return fail_msg("qzstd_hip_huf_code: dense area or scratch too small");
+    QZ_SET_DEVICE(device);
+    hipStream_t s = (hipStream_t)stream;
+    uint32_t *stageOff = static_cast<uint32_t *>(d_scratch);
+    uint8_t *stage = static_cast<uint8_t *>(d_scratch) + QZSTD_HIP_HUF_SCRATCH_BYTES(nRows, 0u);
+    uint8_t *dense = static_cast<uint8_t *>(d_dense);
+    QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D (huf rows)");
+    hipLaunchKernelGGL(qzstd_huf_scan_kernel, dim3(1), dim3(kHufT), 0, s, d_rows, static_cast<const uint32_t *>(nullptr), nRows, stageOff);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_huf_scan_kernel");
+    hipLaunchKernelGGL(qzstd_huf_code_kernel, dim3(nRows), dim3(kHufT), 0, s, static_cast<const uint8_t *>(d_base), d_rows, stageOff, d_cost, d_size, stage);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_huf_code_kernel");
+    hipLaunchKernelGGL(qzstd_huf_scan_kernel, dim3(1), dim3(kHufT), 0, s, d_rows, d_size, nRows, d_off);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_huf_scan_kernel");
+    hipLaunchKernelGGL(qzstd_huf_pack_kernel, dim3(nRows), dim3(kHufT), 0, s, d_size, stageOff, d_off, stage, dense);
+    QZ_CHECK(hipGetLastError(), "launch qzstd_huf_pack_kernel");
+    return 0;
+}
+
 /* ---------------------------------------------------------------- fingerprint (include/qzstd_hip_device.h, qzstd_fingerprint.h) -- */
 #include "qzstd_fingerprint.h"
 

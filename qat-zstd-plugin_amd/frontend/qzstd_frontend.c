@@ -15,6 +15,7 @@
 #include "qzstd_bytegroup_internal.h"
 #include "qzstd_hip_device.h"
 #include "qzstd_planecost.h"
+#include "qzstd_hufblock.h"
 #include "qzstd_fingerprint.h"
 #include "qzstd_elemdiff.h"
 #include "qzstd_ediffcost.h"
@@ -102,6 +103,10 @@ struct QZSTD_Front_s {
     /* plane probe (QZSTD_frontSetPlaneProbe): the setting, and blocks probed / written raw here, frames assembled here / fallen back */
     int planeProbe;
     unsigned long long probeStats[4];
+    /* plane code (QZSTD_frontSetPlaneCode): the setting, and rows the kernel coded / blocks taken / frames assembled without libzstd / frames
+     * with a taken block that fell back */
+    int planeCode;
+    unsigned long long codeStats[4];
     /* the restore calls (qzstd_restore.c): the part the workers decode (NULL: a compress job), the counters, and two slots kept from call to
      * call (pinned buffer, device stage, stream) for device restoreSlotDev */
     const struct QF_RestorePart_s *restore;
@@ -479,6 +484,10 @@ extern int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, 
                           uint32_t *d_flags) __attribute__((weak));
 extern int qzstd_hip_plane_cost(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
                                 qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost) __attribute__((weak));
+extern size_t qzstd_hip_huf_code_bytes(const qzstd_hip_plane_row_t *rows, uint32_t nRows) __attribute__((weak));
+extern int qzstd_hip_huf_code(int device, void *stream, const void *d_base, const qzstd_hip_plane_row_t *rows, uint32_t nRows,
+                              qzstd_hip_plane_row_t *d_rows, uint32_t *d_cost, uint32_t *d_size, uint32_t *d_off, void *d_dense, size_t denseBytes,
+                              void *d_scratch, size_t scratchBytes) __attribute__((weak));
 
 #define QF_PART_BYTES ((size_t)64 << 20)
 #define QF_DEV_WAIT_MS 60000u
@@ -535,6 +544,12 @@ struct QF_DevSlot_s {
     void *dPlaneRows, *dPlaneCost; size_t dPlaneRowsCap, dPlaneCostCap;
     uint32_t *hPlaneCost; size_t hPlaneCostCap;
     int probed; /* as `hashed`: the queued part's costs are in dPlaneCost; the fetched part's in hPlaneCost */
+    /* plane code: per block a size word and a dense offset (nb + (nb + 1) words, one device area and one pinned), the dense area of code
+     * lengths, jump tables and streams on both sides, the coder's scratch */
+    void *dHufWords, *dHufDense, *dHufScratch; size_t dHufWordsCap, dHufDenseCap, dHufScratchCap;
+    uint32_t *hHufWords; size_t hHufWordsCap;
+    unsigned char *hHufDense; size_t hHufDenseCap;
+    int coded; /* as `probed`: the queued part went through qzstd_hip_huf_code; the fetched part's words and dense area are in hHufWords / hHufDense */
     qzstd_hip_block_t *hDesc; size_t hDescCap;
     void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
     size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
@@ -592,13 +607,15 @@ struct QF_DevPart_s {
     int dev;
     int hashed; /* checksums on: frame c's content hash is slot->hHash[c - f0] */
     int probed; /* plane probe: block b's order-0 cost is slot->hPlaneCost[b] */
+    int coded;  /* plane code: block b's size word is slot->hHufWords[b], its bytes lie at slot->hHufDense + slot->hHufWords[nb + b] */
     int failSub; /* test switch ($QZSTD_FRONT_PROBE_FAIL_SUB): the assembled frames' libzstd call counts as failed */
 };
 
 static void qfSlotFree(int dev, QF_DevSlot *s)
 {
     void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
-                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows, s->dPieceRows, s->dPieces };
+                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows, s->dPieceRows, s->dPieces, s->dHufWords, s->dHufDense,
+                  s->dHufScratch };
     size_t i;
     for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
     if (s->hDesc) qzstd_hip_host_free(s->hDesc);
@@ -615,6 +632,8 @@ static void qfSlotFree(int dev, QF_DevSlot *s)
     if (s->hDiffFlags) qzstd_hip_host_free(s->hDiffFlags);
     if (s->hPlaneRows) qzstd_hip_host_free(s->hPlaneRows);
     if (s->hPlaneCost) qzstd_hip_host_free(s->hPlaneCost);
+    if (s->hHufWords) qzstd_hip_host_free(s->hHufWords);
+    if (s->hHufDense) qzstd_hip_host_free(s->hHufDense);
     if (s->hArena) qzstd_hip_host_free(s->hArena);
     if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
     free(s->blkSeq);
@@ -658,6 +677,7 @@ typedef struct {
     int dev, level;
     int checksum;              /* the front's setting when the call began */
     int probe;                 /* plane probe: the front's setting when the call began, for a call with a grouped or based frame */
+    int code;                  /* plane code: likewise; a call with it has `probe` too */
     int failSub;               /* $QZSTD_FRONT_PROBE_FAIL_SUB (tests) */
 } QF_DevJob;
 
@@ -852,6 +872,7 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
         s->hashed = 1;
     }
     s->probed = 0;
+    s->coded = 0;
     if (j->probe && (pr->grouped || pr->delta)) {
         /* the blocks' byte histograms, reduced to their order-0 cost on the device: a row per descriptor, over the stage (such a part is
          * never read in place) */
@@ -866,9 +887,22 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
             s->hPlaneRows[b].len = s->hDesc[b].srcLen;
             s->hPlaneRows[b].reserved = 0;
         }
-        if (qzstd_hip_plane_cost(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
-                                 (uint32_t *)s->dPlaneCost))
+        if (j->code) {
+            /* plane code: the coder leaves the same cost words, and the blocks worth it Huffman-coded — this launch instead of that one */
+            const size_t dense = qzstd_hip_huf_code_bytes(s->hPlaneRows, (uint32_t)nb);
+            if (dense == (size_t)-1 || qfGrowD(dev, &s->dHufWords, &s->dHufWordsCap, (2u * nb + 1u) * sizeof(uint32_t)) ||
+                qfGrowD(dev, &s->dHufDense, &s->dHufDenseCap, dense + 16u) ||
+                qfGrowD(dev, &s->dHufScratch, &s->dHufScratchCap, QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
+                return -1;
+            if (qzstd_hip_huf_code(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
+                                   (uint32_t *)s->dPlaneCost, (uint32_t *)s->dHufWords, (uint32_t *)s->dHufWords + nb, s->dHufDense, dense,
+                                   s->dHufScratch, QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
+                return -1;
+            s->coded = 1;
+        } else if (qzstd_hip_plane_cost(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
+                                        (uint32_t *)s->dPlaneCost)) {
             return -1;
+        }
         s->probed = 1;
     }
     return 0;
@@ -880,7 +914,7 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
     const size_t nb = pr->nb;
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb);
     const qzstd_hip_compact_hdr_t *hdr;
-    size_t b, seqs = 0, lits = 0, bytes;
+    size_t b, seqs = 0, lits = 0, bytes, dense = 0;
     if (s->hArenaCap < eo) {
         void *h = s->hArena;
         if (qfGrowH(&h, &s->hArenaCap, eo + pr->bytes + (pr->bytes >> 2) + QF_LIT_SLACK)) return -1;
@@ -899,6 +933,13 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         if (qfGrowH(&h, &s->hPlaneCostCap, nb * sizeof(uint32_t))) return -1;
         s->hPlaneCost = (uint32_t *)h;
         if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hPlaneCost, s->dPlaneCost, nb * sizeof(uint32_t))) return -1;
+    }
+    if (s->coded) {
+        /* and so do the size words and the dense offsets: 8 bytes per block and 4 */
+        void *h = s->hHufWords;
+        if (qfGrowH(&h, &s->hHufWordsCap, (2u * nb + 1u) * sizeof(uint32_t))) return -1;
+        s->hHufWords = (uint32_t *)h;
+        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHufWords, s->dHufWords, (2u * nb + 1u) * sizeof(uint32_t))) return -1;
     }
     if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
         return -1;
@@ -928,17 +969,33 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         s->hArena = n;
         s->hArenaCap = eo + bytes + QF_LIT_SLACK + (bytes >> 3);
     }
-    if (bytes && (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena + eo, (const unsigned char *)s->dArena + eo, bytes) ||
-                  qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0))
-        return -1;
+    if (s->coded) {
+        /* the dense area: one more copy behind the header wait, as long as the offsets say; it shares the entries' wait */
+        dense = s->hHufWords[2u * nb];
+        if (dense) {
+            void *h = s->hHufDense;
+            if (qfGrowH(&h, &s->hHufDenseCap, dense)) return -1;
+            s->hHufDense = (unsigned char *)h;
+            if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHufDense, s->dHufDense, dense)) return -1;
+        }
+    }
+    if (bytes && qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena + eo, (const unsigned char *)s->dArena + eo, bytes)) return -1;
+    if ((bytes || dense) && qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0) return -1;
     memset(s->hArena + eo + bytes, 0, QF_LIT_SLACK);
     s->hLit = s->hArena + eo + 8u * seqs;
     s->litTotal = lits;
     __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u) +
-                                                           (s->probed ? nb * 4u : 0u)), __ATOMIC_RELAXED);
+                                                           (s->probed ? nb * 4u : 0u) + (s->coded ? (2u * nb + 1u) * 4u + dense : 0u)),
+                       __ATOMIC_RELAXED);
     if (s->probed) __atomic_fetch_add(&j->f->probeStats[0], (unsigned long long)nb, __ATOMIC_RELAXED);
+    if (s->coded) {
+        unsigned long long coded = 0;
+        for (b = 0; b < nb; b++) coded += s->hHufWords[b] != 0u;
+        __atomic_fetch_add(&j->f->codeStats[0], coded, __ATOMIC_RELAXED);
+    }
     out->hashed = s->hashed;
     out->probed = s->probed;
+    out->coded = s->coded;
     out->failSub = j->failSub;
     out->sm = j->sm;
     out->frames = j->frames;
@@ -1139,9 +1196,94 @@ static int qfAssembleFrame(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
     if (fm->based) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->probeStats[1], (unsigned long long)nRaw, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->probeStats[2], 1ull, __ATOMIC_RELAXED);
+    if (pt->coded && nRaw == nb) __atomic_fetch_add(&f->codeStats[2], 1ull, __ATOMIC_RELAXED); /* (all raw: no libzstd call either) */
     return 0;
 fallback:
     __atomic_fetch_add(&f->probeStats[3], 1ull, __ATOMIC_RELAXED);
+    return 1;
+}
+
+/* plane code: the bytes of block b's QZSTD_hufBlockBody (0: none, or the block is not taken by QZSTD_hufTakes) */
+static size_t qfBlockTaken(const QF_DevSlot *s, const qzstd_hip_compact_hdr_t *h, size_t nbPart, size_t b, size_t len)
+{
+    const uint32_t size = s->hHufWords[b];
+    const unsigned char *at;
+    uint8_t nbits[256], tree[QZSTD_HUF_TREE_MAX];
+    size_t t, body;
+    if (!size || len < QZSTD_HUF_LEN_MIN || len > QZSTD_HUF_LEN_MAX || h->count == QZSTD_HIP_NSEQ_ERROR) return 0;
+    at = s->hHufDense + s->hHufWords[nbPart + b];
+    QZSTD_hufUnpackLengths(at, nbits);
+    t = QZSTD_hufWriteTree(nbits, tree, sizeof(tree));
+    if (!t) return 0;
+    body = (len <= 16383u ? 4u : 5u) + t + size + 1u;
+    return QZSTD_hufTakes(size, (uint32_t)body, (uint32_t)len, h->litBytes, h->count) ? body : 0;
+}
+
+/* Plane code: frame c of a coded part, assembled WITHOUT any libzstd call when every block of it is raw-predicted (qfBlockIsRaw) or taken
+ * (QZSTD_hufTakes) and at least one is taken:
+ *   raw-predicted block -> as in qfAssembleFrame;
+ *   taken block         -> a 3-byte Compressed_Block header and QZSTD_hufBlockBody over the code lengths and streams from the GPU.
+ * All or nothing: a Compressed block of libzstd's sub-frame may repeat the Huffman table of the block before it, and a block coded here in
+ * front of it would change that table — a frame with any other block takes exactly the path it takes with the probe on.
+ * -> 0: dst holds the frame and everything is counted; 1: not such a frame (counted in [3] when it had a taken block); -1: out of memory. */
+static int qfAssembleCoded(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, const QF_DevFrame *fm, size_t c, unsigned char *dst)
+{
+    const QF_DevSlot *s = pt->slot;
+    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const size_t n = fm->len, b0 = fm->b0, nb = fm->nb, cap = f->stride;
+    size_t e, o, nRaw = 0, nTaken = 0, pos;
+    for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+        const size_t len = w->ends[e] - o, b = b0 + e;
+        if (qfBlockIsRaw(s, &hdr[b], b, len)) nRaw++;
+        else if (qfBlockTaken(s, &hdr[b], pt->nb, b, len)) nTaken++;
+    }
+    if (!nTaken) return 1;
+    if (nRaw + nTaken < nb || 13u + 3u * nb + 4u > cap) goto fallback;
+    pos = qfFrameHeader(dst, n, pt->hashed);
+    for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
+        const size_t len = w->ends[e] - o, b = b0 + e;
+        const unsigned last = e + 1 == nb ? 1u : 0u;
+        if (qfBlockIsRaw(s, &hdr[b], b, len)) {
+            const unsigned h = (unsigned)(len << 3) | last; /* Block_Size, Raw_Block, Last_Block */
+            if (pos + 3 + len + 4u > cap) goto fallback;
+            dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16);
+            if (hdr[b].count == 1u && hdr[b].litBytes == len) {
+                memcpy(dst + pos, s->hLit + s->blkLit[b], len);
+            } else if (qzbgRebuild(dst + pos, len, &w->seqs[s->blkSeq[b] - s->blkSeq[b0]].offset, hdr[b].count, s->hLit + s->blkLit[b],
+                                   hdr[b].litBytes, &len, 1) != 0) {
+                goto fallback;
+            }
+            pos += len;
+        } else {
+            const unsigned char *at = s->hHufDense + s->hHufWords[pt->nb + b];
+            uint8_t nbits[256];
+            size_t body;
+            unsigned h;
+            if (pos + 3u + len + 4u > cap) goto fallback; /* (a taken body is below len) */
+            QZSTD_hufUnpackLengths(at, nbits);
+            body = QZSTD_hufBlockBody(nbits, (uint32_t)len, at + QZSTD_HUF_LENGTHS_BYTES, s->hHufWords[b], dst + pos + 3u, len);
+            if (!body) goto fallback;
+            h = (unsigned)(body << 3) | (2u << 1) | last; /* Block_Size, Compressed_Block, Last_Block */
+            dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16);
+            pos += body;
+        }
+    }
+    if (pt->hashed) {
+        const uint64_t h = s->hHash[c];
+        dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16); dst[pos++] = (unsigned char)(h >> 24);
+        __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
+    }
+    f->sizes[fm->idx] = pos;
+    __atomic_fetch_add(&f->devStats[0], 1ull, __ATOMIC_RELAXED);
+    if (fm->k > 1u) __atomic_fetch_add(&f->groupStats[0], 1ull, __ATOMIC_RELAXED);
+    if (fm->based) __atomic_fetch_add(&f->deltaStats[0], 1ull, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->probeStats[1], (unsigned long long)nRaw, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->probeStats[2], 1ull, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->codeStats[1], (unsigned long long)nTaken, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->codeStats[2], 1ull, __ATOMIC_RELAXED);
+    return 0;
+fallback:
+    __atomic_fetch_add(&f->codeStats[3], 1ull, __ATOMIC_RELAXED);
     return 1;
 }
 
@@ -1194,6 +1336,11 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
             w->seqs[k].rep = 0;
         }
         haveSeqs = 1;
+        if (pt->coded) {
+            /* plane code: a frame of raw-predicted and taken blocks alone is assembled here; every other frame goes on as with the probe on */
+            const int a = qfAssembleCoded(f, w, pt, fm, c, dst);
+            if (a <= 0) return a;
+        }
         if (pt->probed) {
             /* plane probe: a frame with a raw-predicted block is assembled here; every other frame goes on as with the setting off */
             const int a = qfAssembleFrame(f, w, pt, fm, c, maybeRle, dst);
@@ -1576,7 +1723,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     size_t nFrames, nParts = 0, k, i, total = 0;
     unsigned group;
     unsigned char *equal = NULL;
-    int rc = 0, anyGrouped = 0, anyBase = 0, anyDiff = 0, skip, probe;
+    int rc = 0, anyGrouped = 0, anyBase = 0, anyDiff = 0, skip, probe, code;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || !dst || !frameSizes || !f->p.useProducer || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++)
@@ -1614,8 +1761,10 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (anyDiff && !qzstd_hip_group_ediff) return (size_t)-1; /* differences wanted and a device layer that cannot take them */
     skip = bases && f->deltaSkip;
     if (skip && !qzstd_hip_diff) return (size_t)-1;         /* delta skip wanted and a device layer that cannot compare */
-    probe = f->planeProbe && (anyGrouped || bases);
-    if (probe && !qzstd_hip_plane_cost) return (size_t)-1;  /* plane probe wanted and a device layer that cannot take histograms */
+    code = f->planeCode && (anyGrouped || bases);
+    if (code && (!qzstd_hip_huf_code || !qzstd_hip_huf_code_bytes)) return (size_t)-1; /* plane code wanted and a device layer without the coder */
+    probe = code || (f->planeProbe && (anyGrouped || bases));
+    if (probe && !code && !qzstd_hip_plane_cost) return (size_t)-1;  /* plane probe wanted and a device layer that cannot take histograms */
     j.dev = sm ? sm->dev : -1;
     total = sm ? sm->total : 0;
     for (i = 0; !sm && i < nBufs; i++) {
@@ -1652,6 +1801,7 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     j.sm = sm;
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.probe = probe;
+    j.code = code;
     j.failSub = probe && getenv("QZSTD_FRONT_PROBE_FAIL_SUB") != NULL;
     j.blk = f->p.chunkSize < QZSTD_HIP_BLOCK_MAX ? f->p.chunkSize : QZSTD_HIP_BLOCK_MAX;
     {
@@ -1855,6 +2005,40 @@ void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4])
     int k;
     if (!stats) return;
     for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->probeStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+int QZSTD_frontSetPlaneCode(QZSTD_Front *f, int on)
+{
+    int busy;
+    if (!f) return -1;
+    pthread_mutex_lock(&f->mu);
+    busy = f->devBusy || f->running;
+    if (!busy) f->planeCode = on != 0;
+    pthread_mutex_unlock(&f->mu);
+    return busy ? -1 : 0;
+}
+
+int QZSTD_frontGetPlaneCode(const QZSTD_Front *f) { return f ? f->planeCode : 0; }
+
+void QZSTD_frontPlaneCodeStats(QZSTD_Front *f, unsigned long long stats[4])
+{
+    int k;
+    if (!stats) return;
+    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->codeStats[k], __ATOMIC_RELAXED) : 0ull;
+}
+
+/* include/qzstd_hufblock.h as exported functions (bindings that cannot include the header): the block body (0: none) of `len` bytes from the
+ * 128 bytes of code lengths and the jump table + streams that qzstd_hip_huf_code leaves, and the rule */
+size_t QZSTD_hufBlockBodyOf(const unsigned char lengths[128], unsigned len, const unsigned char *streams, size_t streamBytes, unsigned char *dst,
+                            size_t cap)
+{
+    uint8_t nbits[256];
+    QZSTD_hufUnpackLengths(lengths, nbits);
+    return QZSTD_hufBlockBody(nbits, len, streams, streamBytes, dst, cap);
+}
+int QZSTD_hufTakesOf(unsigned streamBytes, unsigned bodyBytes, unsigned len, unsigned litBytes, unsigned count)
+{
+    return QZSTD_hufTakes(streamBytes, bodyBytes, len, litBytes, count);
 }
 
 unsigned QZSTD_planeCostOf(const unsigned hist[256], unsigned len) { return len <= QZSTD_PLANE_LEN_MAX ? QZSTD_planeCost(hist, len) : len; }

@@ -101,6 +101,12 @@ bytes of bf16 N(0, 0.02) weights: a handful of values) and over the grouped stag
 
   python tools/device_bench.py --probe --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
 
+--code: the plane code (QZSTD_frontSetPlaneCode) on --probe's data and settings, the legs probe on / code on alternating in one run: GB/s,
+compressed bytes, D2H per input byte, the share of frames assembled without libzstd; --kernels: qzstd_hip_huf_code beside
+qzstd_hip_plane_cost, ms per GiB, in the same run.
+
+  python tools/device_bench.py --code --gib 1 --reps 3 [--levels 1,6,12] [--kernels]
+
 --fingerprint: the load-time check (QZSTD_frontFingerprintDeviceBatch / QZSTD_frontCheckDeviceBatch) — N GiB of bf16 N(0, 0.02) weights as one
 tensor and as N x 8192 tensors of 128 KiB.  Three legs, alternating in one run, every run listed, ms per call (the call and the closing
 synchronize):
@@ -1103,6 +1109,111 @@ def probe_main(a):
     print(json.dumps(out))
 
 
+def code_kernels(a, size):
+    """--code --kernels: qzstd_hip_huf_code (its four launches) beside qzstd_hip_plane_cost over the same N GiB of exponent plane and of noise,
+    rows of --chunk bytes, ms per GiB from events around the call, the two alternating"""
+    import ctypes as C
+    plug = B.Plugin()
+    L = D.bind_huf_kernel(D.bind_plane_kernel(plug.lib))
+    n = size // a.chunk
+    torch.manual_seed(0)
+    w = (torch.randn(size // 2, device="cuda:0") * 0.02).to(torch.bfloat16).view(torch.uint8)
+    expo = w.view(-1, 2)[:, 1].repeat(2).contiguous()  # the high bytes, twice: N GiB of exponent plane
+    del w
+    noise = torch.randint(0, 256, (size,), dtype=torch.uint8, device="cuda:0")
+    rows = (D.PlaneRow * n)(*[D.PlaneRow(c * a.chunk, a.chunk, 0) for c in range(n)])
+    need = L.qzstd_hip_huf_code_bytes(rows, n)
+    words = torch.empty(3 * n + 1, dtype=torch.int32, device="cuda:0")
+    dense = torch.empty(need + 16, dtype=torch.uint8, device="cuda:0")
+    scratch = torch.empty(D.huf_scratch_bytes(n, need) + 16, dtype=torch.uint8, device="cuda:0")
+    d_rows = L.qzstd_hip_malloc(0, n * C.sizeof(D.PlaneRow))
+    assert d_rows and dense.data_ptr() % 16 == 0 and scratch.data_ptr() % 16 == 0
+    gib = size / float(1 << 30)
+    out = {"bytes": size, "rows": n, "row_bytes": a.chunk,
+           "timed": "events around one call (rows uploaded inside), ms per GiB, every run of %d after one untimed, the kernels alternating" % a.reps}
+    calls = {}
+    for name, t in (("exponent", expo), ("noise", noise)):
+        calls["plane_cost_%s_ms_per_gib" % name] = lambda t=t: L.qzstd_hip_plane_cost(0, None, t.data_ptr(), rows, n, d_rows, words.data_ptr())
+        calls["huf_code_%s_ms_per_gib" % name] = lambda t=t: L.qzstd_hip_huf_code(
+            0, None, t.data_ptr(), rows, n, d_rows, words.data_ptr(), words.data_ptr() + 4 * n, words.data_ptr() + 8 * n, dense.data_ptr(), need,
+            scratch.data_ptr(), D.huf_scratch_bytes(n, need))
+    try:
+        for key in calls:
+            out[key] = []
+        for i in range(a.reps + 1):
+            for key, call in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                e0.record()
+                assert call() == 0, plug.err()
+                e1.record()
+                torch.cuda.synchronize()
+                if i:
+                    out[key].append(round(e0.elapsed_time(e1) / gib, 3))
+                if key.startswith("huf_code"):
+                    out[key.replace("_ms_per_gib", "_dense_bytes_per_input_byte")] = round(int(words[3 * n]) / size, 5)
+    finally:
+        L.qzstd_hip_free(0, d_rows)
+    print(json.dumps(out))
+
+
+def code_main(a):
+    """--code: the grouped device call with the plane probe on and with the plane code on"""
+    size = int(a.gib * (1 << 30)) & ~(a.chunk - 1)
+    if a.kernels:
+        return code_kernels(a, size)
+    B.Zstd()
+    B.Plugin()
+    lib = B.Front().lib
+    n = size // a.chunk
+    torch.manual_seed(0)
+    out = {"bytes": size, "chunk": a.chunk, "threads": a.threads, "data": {},
+           "timed": "QZSTD_frontCompressDevice with byte grouping on, GB/s of input, every run of %d, the plane probe on and the plane code on alternating" % a.reps}
+
+    def setting(fr, code):
+        assert fr.set_plane_code(code) == 0 and fr.set_plane_probe(not code) == 0
+
+    for kind, dt, k in (("bf16", torch.bfloat16, 2), ("fp32", torch.float32, 4)):
+        t = (torch.randn(size // k, device="cuda:0") * 0.02).to(dt)
+        torch.cuda.synchronize()
+        res = out["data"][kind] = {"elem": k, "levels": {}}
+        for level in [int(x) for x in a.levels.split(",")]:
+            fr = D.DeviceFront(a.threads, level, a.chunk, lib=lib)
+            try:
+                fr.reserve(size)
+                stream = torch.cuda.current_stream().cuda_stream
+                assert fr.set_byte_group(k) == 0
+                cell = {"probe_gbps": [], "code_gbps": []}
+                for code in (0, 1):  # untimed: first touch of the destination, the device slots, the pinned arenas
+                    tag = "code" if code else "probe"
+                    setting(fr, code)
+                    s0, c0 = fr.stats(), fr.plane_code_stats()
+                    r, sizes = fr.call_device(t.data_ptr(), size, stream)
+                    assert r == n, tag
+                    s1, c1 = fr.stats(), fr.plane_code_stats()
+                    cell["compressed_" + tag] = sum(sizes[c] for c in range(n))
+                    cell["d2h_bytes_per_input_byte_" + tag] = round((s1[2] - s0[2]) / size, 5)
+                    if code:
+                        cell["rows_coded_blocks_taken"] = [c1[0] - c0[0], c1[1] - c0[1]]
+                        cell["frames_without_libzstd_share"] = round((c1[2] - c0[2]) / n, 4)
+                        cell["frames_fell_back_share"] = round((c1[3] - c0[3]) / n, 4)
+                for _ in range(a.reps):
+                    for code in (0, 1):
+                        setting(fr, code)
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        r, _ = fr.call_device(t.data_ptr(), size, stream)
+                        dt_s = time.perf_counter() - t0
+                        assert r == n
+                        cell["code_gbps" if code else "probe_gbps"].append(round(size / dt_s / 1e9, 3))
+                res["levels"][str(level)] = cell
+            finally:
+                fr.close()
+        del t
+        torch.cuda.empty_cache()
+    print(json.dumps(out))
+
+
 def fingerprint_kernels(a, size, out):
     """qzstd_hip_fingerprint beside qzstd_hip_diff and qzstd_hip_xxh64 IN ONE RUN: ONE launch each over the same N GiB as rows of 128 KiB, ms per
     GiB from events around the launch (rows uploaded inside), the three alternating, every run listed after one untimed round"""
@@ -1940,6 +2051,7 @@ def main():
     ap.add_argument("--ediff", action="store_true")
     ap.add_argument("--fingerprint", action="store_true")
     ap.add_argument("--probe", action="store_true")
+    ap.add_argument("--code", action="store_true", help="the plane code (QZSTD_frontSetPlaneCode) beside the plane probe; --kernels: the coder beside the cost kernel")
     ap.add_argument("--verify", action="store_true")
     ap.add_argument("--skip", action="store_true")
     ap.add_argument("--slices", action="store_true")
@@ -1973,6 +2085,8 @@ def main():
         return ediff_main(a)
     if a.fingerprint:
         return fingerprint_main(a)
+    if a.code:
+        return code_main(a)
     if a.probe:
         return probe_main(a)
     if a.verify:

@@ -12,6 +12,8 @@ slices of the written buffers (QZSTD_frontRestoreDeviceSlices,
 QZSTD_frontSliceStats: DeviceFront.restore_slices, restore_slices(), shard_slices() and restore_shards() for shards of 2-D tensors),
 the plane probe (QZSTD_frontSetPlaneProbe, QZSTD_frontPlaneProbeStats: DeviceFront.set_plane_probe / plane_probe_stats; qzstd_hip_plane_cost's row and
 binding; plane_cost() / plane_is_raw(), the rule of include/qzstd_planecost.h; reference_frames_probe(): what the calls must produce with the setting on),
+the plane code (QZSTD_frontSetPlaneCode, QZSTD_frontPlaneCodeStats: DeviceFront.set_plane_code / plane_code_stats; qzstd_hip_huf_code's binding over
+the plane rows; bind_hufblock() / huf_block(): include/qzstd_hufblock.h alone; reference_frames_code(): what the calls must produce with the setting on),
 compress_tensor() for a contiguous GPU tensor of any dtype, compress_tensors() for a list of them in one call (group="dtype": byte-grouped by
 each tensor's element size), restore_tensors() for the way back in one call and restore_tensor() for it on the host; the byte-grouped layout itself (include/qzstd_bytegroup.h) as group_bytes /
 ungroup_bytes / group_blocks, and reference_frames_grouped(): what the grouped device calls must produce.
@@ -257,6 +259,29 @@ def bind_plane_kernel(L):
     return L
 
 
+HUF_LEN_MIN, HUF_LEN_MAX, HUF_LENGTHS_BYTES = 1024, 131072, 128  # include/qzstd_hufblock.h
+
+
+def huf_row_bytes(n: int) -> int:
+    """QZSTD_HIP_HUF_ROW_BYTES: what a row of n bytes can take in the dense area of qzstd_hip_huf_code at the most"""
+    return ((n + 15) & ~15) + HUF_LENGTHS_BYTES if HUF_LEN_MIN <= n <= HUF_LEN_MAX else 0
+
+
+def huf_scratch_bytes(rows: int, dense: int) -> int:
+    """QZSTD_HIP_HUF_SCRATCH_BYTES"""
+    return (((rows + 1) * 4 + 15) & ~15) + dense
+
+
+def bind_huf_kernel(L):
+    """qzstd_hip_huf_code and qzstd_hip_huf_code_bytes on a loaded device layer (libqatseqprod; rows: PlaneRow)"""
+    L.qzstd_hip_huf_code_bytes.restype = C.c_size_t
+    L.qzstd_hip_huf_code_bytes.argtypes = [C.c_void_p, C.c_uint32]
+    L.qzstd_hip_huf_code.restype = C.c_int
+    L.qzstd_hip_huf_code.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t]
+    return L
+
+
 def plane_cost(block: bytes, lib=None) -> int:
     """QZSTD_planeCost (include/qzstd_planecost.h, through the front-end library's export) of a block's byte histogram: its order-0 cost in bytes"""
     import numpy as np
@@ -487,6 +512,17 @@ def bind(F):
         F.QZSTD_frontGetDeltaSkip.argtypes = [C.c_void_p]
         F.QZSTD_frontDeltaSkipStats.restype = None
         F.QZSTD_frontDeltaSkipStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+    if hasattr(F, "QZSTD_frontSetPlaneCode"):  # (absent from an older library)
+        F.QZSTD_frontSetPlaneCode.restype = C.c_int
+        F.QZSTD_frontSetPlaneCode.argtypes = [C.c_void_p, C.c_int]
+        F.QZSTD_frontGetPlaneCode.restype = C.c_int
+        F.QZSTD_frontGetPlaneCode.argtypes = [C.c_void_p]
+        F.QZSTD_frontPlaneCodeStats.restype = None
+        F.QZSTD_frontPlaneCodeStats.argtypes = [C.c_void_p, C.POINTER(C.c_ulonglong)]
+        F.QZSTD_hufBlockBodyOf.restype = C.c_size_t
+        F.QZSTD_hufBlockBodyOf.argtypes = [C.c_char_p, C.c_uint, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t]
+        F.QZSTD_hufTakesOf.restype = C.c_int
+        F.QZSTD_hufTakesOf.argtypes = [C.c_uint] * 5
     if hasattr(F, "QZSTD_frontSetPlaneProbe"):  # (absent from an older library)
         F.QZSTD_frontSetPlaneProbe.restype = C.c_int
         F.QZSTD_frontSetPlaneProbe.argtypes = [C.c_void_p, C.c_int]
@@ -899,6 +935,20 @@ class DeviceFront:
 
     def get_plane_probe(self) -> int:
         return self.lib.QZSTD_frontGetPlaneProbe(self.f)
+
+    def set_plane_code(self, on) -> int:
+        """QZSTD_frontSetPlaneCode: as with the plane probe on, and the blocks QZSTD_hufTakes takes are Huffman-coded on the GPU; a frame of
+        raw-predicted and taken blocks alone is assembled without any libzstd call"""
+        return self.lib.QZSTD_frontSetPlaneCode(self.f, 1 if on else 0)
+
+    def get_plane_code(self) -> int:
+        return self.lib.QZSTD_frontGetPlaneCode(self.f)
+
+    def plane_code_stats(self) -> list:
+        """[rows the kernel coded, blocks taken, frames assembled without libzstd, frames with a taken block that fell back]"""
+        st = (C.c_ulonglong * 4)()
+        self.lib.QZSTD_frontPlaneCodeStats(self.f, st)
+        return list(st)
 
     def plane_probe_stats(self) -> list:
         """[0] blocks probed, [1] blocks written raw by the library, [2] frames assembled by the library, [3] frames that fell back"""
@@ -1645,4 +1695,101 @@ def reference_frames_probe(zstd, oracle, data: bytes, chunk: int, level: int, k:
             out.append(bytes(fr))
     finally:
         zstd.free(zc)
+    return out
+
+
+def bind_hufblock(H):
+    """tests/hufblock/hufblock_check.c built -shared: include/qzstd_hufblock.h alone (hb_lengths, hb_streams, hb_size_word, hb_body, hb_takes)"""
+    H.hb_lengths.restype = C.c_uint
+    H.hb_lengths.argtypes = [C.c_char_p, C.c_uint, C.c_void_p]
+    H.hb_streams.restype = C.c_size_t
+    H.hb_streams.argtypes = [C.c_char_p, C.c_uint, C.c_void_p, C.c_void_p, C.c_size_t]
+    H.hb_size_word.restype = C.c_uint
+    H.hb_size_word.argtypes = [C.c_uint, C.c_uint]
+    H.hb_body.restype = C.c_size_t
+    H.hb_body.argtypes = [C.c_void_p, C.c_uint, C.c_char_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_int]
+    H.hb_takes.restype = C.c_int
+    H.hb_takes.argtypes = [C.c_uint] * 5
+    H.hb_takes_at.restype = C.c_int
+    H.hb_takes_at.argtypes = [C.c_uint] * 6
+    H.hb_seq_eighths.restype = C.c_uint
+    return H
+
+
+def huf_block(huf, block: bytes, lit_bytes: int, count: int):
+    """(size word, block body or None) of one block by include/qzstd_hufblock.h alone (huf: bind_hufblock): the size word qzstd_hip_huf_code
+    leaves for it, and its QZSTD_hufBlockBody when QZSTD_hufTakes takes it given its compaction header's litBytes and count"""
+    n = len(block)
+    if not HUF_LEN_MIN <= n <= HUF_LEN_MAX:
+        return 0, None
+    nbits = (C.c_ubyte * 256)()
+    if not huf.hb_lengths(block, n, nbits):
+        return 0, None
+    streams = C.create_string_buffer(n)
+    size = huf.hb_size_word(huf.hb_streams(block, n, nbits, streams, n), n)
+    if not size:
+        return 0, None
+    body = C.create_string_buffer(n + 256)
+    b = huf.hb_body(nbits, n, streams.raw[:size], size, body, n + 256, 0)
+    if not b or not huf.hb_takes(size, b, n, lit_bytes, count):
+        return size, None
+    return size, body.raw[:b]
+
+
+def reference_frames_code(zstd, oracle, huf, data: bytes, chunk: int, level: int, k: int, checksum: bool = False, lib=None,
+                          counts: dict | None = None) -> list:
+    """what the grouped device calls must produce with the plane code on (QZSTD_frontSetPlaneCode), beside reference_frames_probe: per frame
+    the ORACLE's sequences for each block, the probe's rule, and include/qzstd_hufblock.h alone (huf: bind_hufblock) for the size word, the
+    block body and QZSTD_hufTakes.  A frame whose every block is raw-predicted or taken, one at least taken, is the library's frame header,
+    a Raw_Block per raw-predicted block and a Compressed_Block of the body per taken one, with `checksum` the four bytes libzstd appends to
+    the same content; every other frame is reference_frames_probe's.  counts receives reference_frames_probe's keys (a frame assembled here
+    counts in "assembled", its raw blocks in "raw") and "coded" (blocks with a size word), "taken" (blocks), "nolib" (frames assembled
+    without a libzstd call: these and the probe's all-raw ones), "code_fallback" (frames with a taken block that are the probe's)"""
+    blk = min(chunk, 131072)
+    prof = oracle.profile(level, blk)
+    cap = B.sequence_bound(blk)
+    counts = counts if counts is not None else {}
+    for key in ("blocks", "raw", "assembled", "allraw", "fallback", "slack", "coded", "taken", "nolib", "code_fallback"):
+        counts.setdefault(key, 0)
+    out = []
+    for o in range(0, len(data), chunk):
+        piece = data[o:o + chunk]
+        g = group_bytes(piece, k, lib)
+        blocks, start = [], 0
+        for end in group_blocks(len(g), k, lib):
+            b = g[start:end]
+            n, sq = oracle.find(prof, b, cap=cap)
+            if n == B.SEQ_ERROR:
+                raise RuntimeError("the oracle failed a block")
+            lit_bytes = sum(s.litLength for s in sq[:n])
+            raw = plane_is_raw(plane_cost(b, lib), len(b), len(b) - lit_bytes, lib)
+            size, body = huf_block(huf, b, lit_bytes, n)
+            counts["coded"] += 1 if size else 0
+            blocks.append((b, raw, None if raw else body))
+            start = end
+        n_taken = sum(1 for b in blocks if b[2] is not None)
+        if not n_taken or any(not raw and body is None for _, raw, body in blocks):
+            sub = {}
+            out.append(reference_frames_probe(zstd, oracle, piece, chunk, level, k, checksum=checksum, lib=lib, counts=sub)[0])
+            for key, v in sub.items():
+                counts[key] += v
+            counts["nolib"] += sub["allraw"]
+            counts["code_fallback"] += 1 if n_taken else 0
+            continue
+        fr = bytearray(frame_header(len(g), checksum))
+        for i, (b, raw, body) in enumerate(blocks):
+            last = 1 if i + 1 == len(blocks) else 0
+            if raw:
+                fr += (len(b) << 3 | last).to_bytes(3, "little") + b
+                counts["slack"] += (len(b) >> 6) + 2
+            else:
+                fr += (len(body) << 3 | 2 << 1 | last).to_bytes(3, "little") + body
+        if checksum:
+            fr += reference_frames_grouped(zstd, oracle, piece, chunk, level, k, checksum=True, lib=lib)[0][-4:]
+        counts["blocks"] += len(blocks)
+        counts["raw"] += sum(1 for b in blocks if b[1])
+        counts["assembled"] += 1
+        counts["taken"] += n_taken
+        counts["nolib"] += 1
+        out.append(bytes(fr))
     return out
