@@ -4,11 +4,13 @@
  * gather for typed rows and the ungrouping scatter that undoes it, both also with a base XORed in on the way (delta frames), the gather also for
  * rows assembled from pieces (source slices), the scatter also for
  * windows of the staged frames (slices), the comparison of staged frames with live bytes (verify), the comparison of rows with their bases (delta skip), the XXH64 content checksum, the plane cost (plane probe), the tile digests of the tensor fingerprints, and the grouping gather with element differences and the element sum (integer columns).  They use nothing of the match-finder
- * (qzstd_kernels.hip).
+ * (qzstd_kernels.hip).  What the launchers of row tables and their kernels share — the checks, the refusals' text, the workgroup's search
+ * for its row — stands once, in the section "row tables" behind the plain gather's kernel.
  */
 #include <hip/hip_runtime.h>
 
 #include <stdint.h>
+#include <stdio.h>
 
 #include "qzstd_hip.h"
 #include "qzstd_hip_device.h"
@@ -252,24 +254,191 @@ __global__ __launch_bounds__(kGatherT) void qzstd_gather_kernel(const qzstd_hip_
 }
 } // namespace
 
+/* ---------------------------------------------------------------- row tables: what their launchers and their kernels share -- */
+/* Every launcher below takes a table of rows, checks it, copies it to the device and starts one workgroup per tile of a row; a workgroup
+ * finds its row by a search over the table.  There are two ways of numbering the workgroups, and each has ONE check on the host and ONE
+ * search on the device, here:
+ *   stage numbering  (group, group_xor, group_pieces, group_ediff by dstOff; ungroup, ungroup_xor by srcOff)  workgroup v is tile
+ *                    v - start(r) of row r, start(r) = (off >> 14) + r: strictly ascending in r, and a row's tiles (at most
+ *                    ceil(extent / 16 KiB)) end before the next row's start, so the launcher needs no prefix sums over the rows.  A
+ *                    workgroup whose number falls behind its row's last tile has nothing to do.  stage_rows_check / stage_row_of
+ *   tile0 numbering  (ungroup_window, ungroup_cmp, diff, fingerprint, esum, ediff_cost and those from pieces)  the launcher writes every
+ *                    row's first workgroup into the row, tile0: rows without a tile share the tile0 of the row behind them and are never
+ *                    the one a search finds.  tile0_rows / tile0_row_of
+ * A refusal reads "<launcher>: <reason>", returns < 0, queues nothing and writes nothing, the caller's rows included. */
+namespace {
+constexpr uint32_t kGroupTileLog = 14u; /* bytes of one row per workgroup, under both numberings: 16 KiB, 16 KiB / elem elements */
+constexpr uint32_t kGroupTile = 1u << kGroupTileLog;
+
+inline int refuse(const char *who, const char *why)
+{
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", who, why);
+    return fail_msg(msg);
+}
+
+/* the rules that hold for every table: each returns nullptr, or the reason it is broken */
+inline const char *elem_check(uint32_t elem) { return elem != 1u && elem != 2u && elem != 4u && elem != 8u ? "elem not 1, 2, 4 or 8" : nullptr; }
+inline const char *len_check(uint32_t len) { return len > 0xFFFFFFE0u ? "a row longer than 0xFFFFFFE0 bytes" : nullptr; }
+/* (one grid dimension, and tile numbers that stay positive as int) */
+inline const char *tiles_check(uint64_t tiles) { return tiles > 0x7FFFFFFFull ? "too many tiles" : nullptr; }
+/* (the stage's 16-byte words in 32 bits, with room for a workgroup's last step) */
+inline const char *stage_span_check(uint64_t end) { return (end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords ? "stage span too large" : nullptr; }
+
+inline uint64_t round16(uint64_t len) { return (len + 15u) & ~(uint64_t)15u; }
+
+/* A row's place in the stage: behind the row before it — `again`: AT the row before it, the next window of the same frame — and its `fit`
+ * bytes from `off` on inside stageBytes.  Moves *end behind the row's extent. */
+inline const char *stage_place(uint64_t off, uint64_t ext, uint64_t fit, size_t stageBytes, bool again, uint64_t *end)
+{
+    if (!again && off < *end) return "rows overlap in the stage or are not in ascending order";
+    if (off > (uint64_t)stageBytes || fit > (uint64_t)stageBytes - off) return "a row ends past stageBytes";
+    *end = off + ext;
+    return nullptr;
+}
+
+/* the place of a staged frame that a comparison reads */
+inline const char *frame_place(uint64_t srcOff, uint32_t len, const void *d_stage, size_t stageBytes, uint64_t *end)
+{
+    if (srcOff & 15u) return "srcOff not a multiple of 16";
+    if (len && !d_stage) return "null stage";
+    return stage_place(srcOff, round16(len), len, stageBytes, false, end);
+}
+
+/* a row assembled from pieces: its pieces [piece0, piece0 + count) of the table tile [0, len); noBase: a base is refused too */
+inline const char *pieces_check(const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, uint32_t piece0, uint32_t count, uint32_t len, bool noBase)
+{
+    if ((uint64_t)piece0 + count > nPieces) return "a row's pieces end past the table";
+    uint64_t at = 0;
+    for (uint32_t p = piece0; p < piece0 + count; p++) {
+        if (!pieces[p].len || !pieces[p].src) return "an empty piece or a null source";
+        if (noBase && pieces[p].base) return "a piece with a base";
+        if (pieces[p].off != at) return "a row's pieces do not tile its content in ascending order";
+        at += pieces[p].len;
+    }
+    return at == len ? nullptr : "a row's pieces do not tile its content in ascending order";
+}
+
+/* ---- stage numbering, host side */
+struct stage_row_t { uint64_t off, ext, fit; uint32_t len, elem; }; /* what the check looks at: stage offset, extent, the bytes that must lie inside
+                                                                       stageBytes, content length, element size */
+struct row_own_t { const char *early, *mid, *late; };               /* a launcher's own refusals for a row (nullptr: none), at their places in the order */
+struct stage_launch_t { uint64_t end, firstTile; uint32_t tiles; }; /* end of the last row; the launch: tiles == 0, nothing to do */
+
+/* Row by row, the first offending row decides: elem, own.early, offset and extent multiples of 16, own.mid, the place (stage_place),
+ * own.late; then the stage's span, and for typed rows the launch's tiles.  Typed == false: rows without elem (the plain gather's), no tiles. */
+template <bool Typed = true, class Row, class Place, class Own>
+int stage_rows_check(const char *who, const Row *rows, uint32_t nRows, size_t stageBytes, Place place, Own own, stage_launch_t *go)
+{
+    uint64_t end = 0, endTile = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        const stage_row_t p = place(rows[i]);
+        const row_own_t mine = own(rows[i]);
+        const char *why = Typed ? elem_check(p.elem) : nullptr;
+        if (!why) why = mine.early;
+        if (!why && ((p.off & 15u) || (p.ext & 15u))) why = "the row's stage offset or its extent (len + pad) not a multiple of 16";
+        if (!why) why = mine.mid;
+        if (!why) why = stage_place(p.off, p.ext, p.fit, stageBytes, false, &end);
+        if (!why) why = mine.late;
+        if (why) return refuse(who, why);
+        if (Typed && p.ext) { /* the row's tiles in the launch's numbering */
+            const uint64_t n = p.len / p.elem, tileMax = kGroupTile / p.elem;
+            endTile = (p.off >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
+        }
+    }
+    if (const char *why = stage_span_check(end)) return refuse(who, why);
+    *go = { end, place(rows[0]).off >> kGroupTileLog, 0u };
+    if (endTile == 0) return 0; /* nothing but empty rows */
+    if (const char *why = tiles_check(endTile - go->firstTile)) return refuse(who, why);
+    go->tiles = (uint32_t)(endTile - go->firstTile);
+    return 0;
+}
+
+/* the gathers' rows (dstOff; len + pad bytes, all of them inside the stage) and the scatters' (srcOff; len bytes of a 16-byte multiple) */
+template <class Row, class Own> int group_rows_check(const char *who, const Row *rows, uint32_t nRows, size_t stageBytes, Own own, stage_launch_t *go)
+{
+    return stage_rows_check(who, rows, nRows, stageBytes,
+                            [](const Row &r) { return stage_row_t{ r.dstOff, (uint64_t)r.len + r.pad, (uint64_t)r.len + r.pad, r.len, r.elem }; }, own, go);
+}
+template <class Row, class Own> int ungroup_rows_check(const char *who, const Row *rows, uint32_t nRows, size_t stageBytes, Own own, stage_launch_t *go)
+{
+    return stage_rows_check(who, rows, nRows, stageBytes, [](const Row &r) { return stage_row_t{ r.srcOff, round16(r.len), r.len, r.len, r.elem }; },
+                            own, go);
+}
+const auto kGatherOwn = [](const auto &r) { return row_own_t{ nullptr, r.len && !r.src ? "null source" : nullptr, nullptr }; };
+const auto kGroupOwn = [](const auto &r) { return row_own_t{ r.reserved ? "reserved not 0" : nullptr, r.len && !r.src ? "null source" : nullptr, nullptr }; };
+const auto kUngroupOwn = [](const auto &r) { return row_own_t{ nullptr, r.len && !r.dst ? "null destination" : nullptr, nullptr }; };
+
+/* ---- tile0 numbering, host side: every row is checked and its tiles are counted, the count is held against the limit, and ONLY THEN is
+ * tile0 written.  check(row, i): nullptr or the reason; tiles(row): the row's workgroups. */
+template <class Row, class Check, class Tiles>
+int tile0_count(const char *who, const Row *rows, uint32_t nRows, Check check, Tiles tiles, uint32_t *total)
+{
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        if (const char *why = check(rows[i], i)) return refuse(who, why);
+        sum += tiles(rows[i]);
+    }
+    if (const char *why = tiles_check(sum)) return refuse(who, why);
+    *total = (uint32_t)sum;
+    return 0;
+}
+
+template <class Row, class Tiles> void tile0_write(Row *rows, uint32_t nRows, Tiles tiles)
+{
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < nRows; i++) {
+        rows[i].tile0 = at;
+        at += (uint32_t)tiles(rows[i]);
+    }
+}
+
+/* `always`: tile0 is written even when no row has a tile (the caller's rows then say so); else such a table is left as it came */
+template <class Row, class Check, class Tiles>
+int tile0_rows(const char *who, Row *rows, uint32_t nRows, Check check, Tiles tiles, bool always, uint32_t *total)
+{
+    if (tile0_count(who, rows, nRows, check, tiles, total)) return -1;
+    if (*total || always) tile0_write(rows, nRows, tiles);
+    return 0;
+}
+
+/* ---- the workgroup's row, device side (one lane runs it; the kernels keep the result in LDS) */
+/* stage numbering: the last row whose first tile is at or before v */
+template <class Row>
+__device__ __forceinline__ uint32_t stage_row_of(const Row *__restrict__ rows, uint32_t nRows, uint64_t Row::*off, uint64_t v)
+{
+    uint32_t lo = 0, hi = nRows - 1u;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if ((rows[mid].*off >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+
+/* tile0 numbering: the last row whose first workgroup is this one or one before it */
+template <class Row> __device__ __forceinline__ uint32_t tile0_row_of(const Row *__restrict__ rows, uint32_t nRows)
+{
+    uint32_t lo = 0, hi = nRows - 1u;
+    while (lo < hi) {
+        const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
+        if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
+    }
+    return lo;
+}
+} // namespace
+
 extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather_row_t *rows, uint32_t nRows, qzstd_hip_gather_row_t *d_rows,
                                 void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_gather";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_gather: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_gather_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_gather: dstOff or len + pad not a multiple of 16");
-        if (r.len && !r.src) return fail_msg("qzstd_hip_gather: null source");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_gather: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_gather: a row ends past stageBytes");
-        end = r.dstOff + ext;
-    }
-    /* 16-byte words in 32 bits, with room for a workgroup's last step */
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_gather: stage span too large");
-    const uint32_t firstWord = (uint32_t)(rows[0].dstOff >> 4), endWord = (uint32_t)(end >> 4);
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    stage_launch_t go;
+    if (stage_rows_check<false>(who, rows, nRows, stageBytes,
+                                [](const qzstd_hip_gather_row_t &r) { return stage_row_t{ r.dstOff, (uint64_t)r.len + r.pad, (uint64_t)r.len + r.pad, r.len, 0u }; },
+                                kGatherOwn, &go))
+        return -1;
+    const uint32_t firstWord = (uint32_t)(rows[0].dstOff >> 4), endWord = (uint32_t)(go.end >> 4);
     if (endWord == firstWord) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (gather rows)");
@@ -282,19 +451,9 @@ extern "C" int qzstd_hip_gather(int device, void *stream, const qzstd_hip_gather
 
 /* ---------------------------------------------------------------- byte-grouping gather (include/qzstd_hip_device.h) -- */
 namespace {
-constexpr uint32_t kGroupT = 256u;                    /* threads per workgroup */
-constexpr uint32_t kGroupTileLog = 14u;               /* source bytes of one row per workgroup: 16 KiB, 16 KiB / elem elements */
-constexpr uint32_t kGroupTile = 1u << kGroupTileLog;
+constexpr uint32_t kGroupT = 256u;                    /* threads per workgroup; a workgroup takes kGroupTile source bytes of one row */
 constexpr uint32_t kGroupSlack = 32u;                 /* bytes behind each plane in LDS: a stage word's two aligned 16-byte reads stay inside */
 constexpr uint32_t kGroupLds = kGroupTile + 8u * kGroupSlack;
-
-/* Workgroup v of the launch's numbering is tile v - start(r) of row r, start(r) = (dstOff >> 14) + r: strictly ascending in r, and a row's
- * tiles (at most ceil((len + pad) / 16 KiB)) end before the next row's start, so the launcher needs no prefix sums over the rows.  A
- * workgroup whose number falls behind its row's last tile has nothing to do. */
-__device__ inline uint64_t group_row_start(const qzstd_hip_group_row_t *__restrict__ rows, uint32_t r)
-{
-    return (rows[r].dstOff >> kGroupTileLog) + r;
-}
 
 /* byte p of the row's grouped layout (0 from len on), by one aligned 16-byte load of the word that holds its source byte */
 __device__ inline uint64_t group_byte(const qzstd_hip_group_row_t &row, uint32_t n, uint32_t kLog, uint64_t p)
@@ -370,14 +529,7 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_kernel(const qzstd_hip_gr
     __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
     __shared__ uint32_t which;
     const uint64_t v = firstTile + blockIdx.x;
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (group_row_start(rows, mid) <= v) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (threadIdx.x == 0) which = stage_row_of(rows, nRows, &qzstd_hip_group_row_t::dstOff, v);
     __syncthreads();
     const uint32_t r = which;
     const qzstd_hip_group_row_t row = rows[r];
@@ -501,14 +653,7 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_xor_kernel(const qzstd_hi
     __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
     __shared__ uint32_t which;
     const uint64_t v = firstTile + blockIdx.x;
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (threadIdx.x == 0) which = stage_row_of(rows, nRows, &qzstd_hip_group_xor_row_t::dstOff, v);
     __syncthreads();
     const uint32_t r = which;
     const qzstd_hip_group_xor_row_t row = rows[r];
@@ -575,65 +720,33 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_xor_kernel(const qzstd_hi
 extern "C" int qzstd_hip_group(int device, void *stream, const qzstd_hip_group_row_t *rows, uint32_t nRows, qzstd_hip_group_row_t *d_rows,
                                void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_group";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_group_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
-            return fail_msg("qzstd_hip_group: elem not 1, 2, 4 or 8, or reserved not 0");
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group: dstOff or len + pad not a multiple of 16");
-        if (r.len && !r.src) return fail_msg("qzstd_hip_group: null source");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_group: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group: a row ends past stageBytes");
-        end = r.dstOff + ext;
-        if (ext) { /* the row's tiles in the launch's numbering (qzstd_group_kernel) */
-            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
-            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    stage_launch_t go;
+    if (group_rows_check(who, rows, nRows, stageBytes, kGroupOwn, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group rows)");
-    hipLaunchKernelGGL(qzstd_group_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+    hipLaunchKernelGGL(qzstd_group_kernel, dim3(go.tiles), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, go.firstTile,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_kernel");
     return 0;
 }
 
-/* (qzstd_hip_group's checks and launch geometry, row for row; a row's base may be anything, 0 included) */
+/* (a row's base may be anything, 0 included) */
 extern "C" int qzstd_hip_group_xor(int device, void *stream, const qzstd_hip_group_xor_row_t *rows, uint32_t nRows,
                                    qzstd_hip_group_xor_row_t *d_rows, void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_group_xor";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_xor: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_group_xor_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
-            return fail_msg("qzstd_hip_group_xor: elem not 1, 2, 4 or 8, or reserved not 0");
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_xor: dstOff or len + pad not a multiple of 16");
-        if (r.len && !r.src) return fail_msg("qzstd_hip_group_xor: null source");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_group_xor: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_xor: a row ends past stageBytes");
-        end = r.dstOff + ext;
-        if (ext) {
-            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
-            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_xor: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_xor: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    stage_launch_t go;
+    if (group_rows_check(who, rows, nRows, stageBytes, kGroupOwn, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group xor rows)");
-    hipLaunchKernelGGL(qzstd_group_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+    hipLaunchKernelGGL(qzstd_group_xor_kernel, dim3(go.tiles), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, go.firstTile,
                        static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_xor_kernel");
     return 0;
@@ -746,11 +859,7 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_pieces_kernel(const qzstd
     __shared__ uint32_t which, pieceLo, pieceHi;
     const uint64_t v = firstTile + blockIdx.x;
     if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
-        }
+        const uint32_t lo = stage_row_of(rows, nRows, &qzstd_hip_group_pieces_row_t::dstOff, v);
         which = lo;
         const qzstd_hip_group_pieces_row_t &rw = rows[lo];
         const uint64_t t = v - ((rw.dstOff >> kGroupTileLog) + lo);
@@ -821,48 +930,28 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_pieces_kernel(const qzstd
 }
 } // namespace
 
-/* (qzstd_hip_group_xor's checks and launch geometry, row for row, and the piece table's: every row's pieces tile its content) */
+/* (the content has no address of its own: in the place of the null source test, every row's pieces tile its content) */
 extern "C" int qzstd_hip_group_pieces(int device, void *stream, const qzstd_hip_group_pieces_row_t *rows, uint32_t nRows,
                                       qzstd_hip_group_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
                                       qzstd_hip_group_piece_t *d_pieces, void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_group_pieces";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_pieces: null pointer or stage not 16-byte aligned");
-    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_group_pieces: null piece table");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_group_pieces_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
-            return fail_msg("qzstd_hip_group_pieces: elem not 1, 2, 4 or 8, or reserved not 0");
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_pieces: dstOff or len + pad not a multiple of 16");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_group_pieces: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_pieces: a row ends past stageBytes");
-        if ((uint64_t)r.piece0 + r.nPieces > nPieces) return fail_msg("qzstd_hip_group_pieces: a row's pieces end past the table");
-        uint64_t at = 0;
-        for (uint32_t p = r.piece0; p < r.piece0 + r.nPieces; p++) {
-            if (!pieces[p].len || !pieces[p].src) return fail_msg("qzstd_hip_group_pieces: an empty piece or a null source");
-            if (pieces[p].off != at) return fail_msg("qzstd_hip_group_pieces: a row's pieces do not tile its content in ascending order");
-            at += pieces[p].len;
-        }
-        if (at != r.len) return fail_msg("qzstd_hip_group_pieces: a row's pieces do not tile its content in ascending order");
-        end = r.dstOff + ext;
-        if (ext) {
-            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
-            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_pieces: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_pieces: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    if (nPieces && (!pieces || !d_pieces)) return refuse(who, "null piece table");
+    const auto own = [&](const qzstd_hip_group_pieces_row_t &r) {
+        return row_own_t{ r.reserved ? "reserved not 0" : nullptr, nullptr, pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, false) };
+    };
+    stage_launch_t go;
+    if (group_rows_check(who, rows, nRows, stageBytes, own, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group pieces rows)");
     if (nPieces)
         QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
                  "hipMemcpyAsync H2D (group pieces table)");
-    hipLaunchKernelGGL(qzstd_group_pieces_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
-                       firstTile, static_cast<uint4 *>(d_stage));
+    hipLaunchKernelGGL(qzstd_group_pieces_kernel, dim3(go.tiles), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces, go.firstTile,
+                       static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_pieces_kernel");
     return 0;
 }
@@ -1041,21 +1130,14 @@ __device__ inline void ungroup_store(const Row &row, const uint8_t *__restrict__
     }
 }
 
-/* One workgroup per tile: elements [e0, e0 + tileElems) of one row — 16 KiB of its destination — in the launch numbering of
- * qzstd_group_kernel with srcOff in dstOff's place.  No destination byte is read, none is written twice, none outside [dst, dst + len). */
+/* One workgroup per tile: elements [e0, e0 + tileElems) of one row — 16 KiB of its destination — in the stage numbering by srcOff (stage_row_of).
+ * No destination byte is read, none is written twice, none outside [dst, dst + len). */
 template <class Row>
 __device__ __forceinline__ void ungroup_tile(const Row *__restrict__ rows, uint32_t nRows, uint64_t firstTile, const uint8_t *__restrict__ stage,
                                              uint8_t *lds, uint32_t *which)
 {
     const uint64_t v = firstTile + blockIdx.x;
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if ((rows[mid].srcOff >> kUngroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
-        }
-        *which = lo;
-    }
+    if (threadIdx.x == 0) *which = stage_row_of(rows, nRows, &Row::srcOff, v);
     __syncthreads();
     const uint32_t r = *which;
     const Row row = rows[r];
@@ -1093,63 +1175,33 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_xor_kernel(const qzst
 extern "C" int qzstd_hip_ungroup(int device, void *stream, const qzstd_hip_ungroup_row_t *rows, uint32_t nRows, qzstd_hip_ungroup_row_t *d_rows,
                                  const void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_ungroup";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ungroup_row_t &r = rows[i];
-        const uint64_t ext = ((uint64_t)r.len + 15u) & ~(uint64_t)15u;
-        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup: elem not 1, 2, 4 or 8");
-        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup: srcOff not a multiple of 16");
-        if (r.len && !r.dst) return fail_msg("qzstd_hip_ungroup: null destination");
-        if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup: rows overlap in the stage or are not in ascending order");
-        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup: a row ends past stageBytes");
-        end = r.srcOff + ext;
-        if (r.len) { /* the row's tiles in the launch's numbering (qzstd_ungroup_kernel) */
-            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
-            endTile = (r.srcOff >> kUngroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].srcOff >> kUngroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    stage_launch_t go;
+    if (ungroup_rows_check(who, rows, nRows, stageBytes, kUngroupOwn, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup rows)");
-    hipLaunchKernelGGL(qzstd_ungroup_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+    hipLaunchKernelGGL(qzstd_ungroup_kernel, dim3(go.tiles), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, go.firstTile,
                        static_cast<const uint8_t *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_kernel");
     return 0;
 }
 
-/* (qzstd_hip_ungroup's checks and launch geometry, row for row; a row's base may be anything, 0 and the row's dst included) */
+/* (a row's base may be anything, 0 and the row's dst included) */
 extern "C" int qzstd_hip_ungroup_xor(int device, void *stream, const qzstd_hip_ungroup_xor_row_t *rows, uint32_t nRows,
                                      qzstd_hip_ungroup_xor_row_t *d_rows, const void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_ungroup_xor";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_xor: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ungroup_xor_row_t &r = rows[i];
-        const uint64_t ext = ((uint64_t)r.len + 15u) & ~(uint64_t)15u;
-        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_xor: elem not 1, 2, 4 or 8");
-        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_xor: srcOff not a multiple of 16");
-        if (r.len && !r.dst) return fail_msg("qzstd_hip_ungroup_xor: null destination");
-        if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_xor: rows overlap in the stage or are not in ascending order");
-        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_xor: a row ends past stageBytes");
-        end = r.srcOff + ext;
-        if (r.len) {
-            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
-            endTile = (r.srcOff >> kUngroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup_xor: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].srcOff >> kUngroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_xor: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    stage_launch_t go;
+    if (ungroup_rows_check(who, rows, nRows, stageBytes, kUngroupOwn, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup xor rows)");
-    hipLaunchKernelGGL(qzstd_ungroup_xor_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, firstTile,
+    hipLaunchKernelGGL(qzstd_ungroup_xor_kernel, dim3(go.tiles), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, go.firstTile,
                        static_cast<const uint8_t *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_xor_kernel");
     return 0;
@@ -1160,8 +1212,7 @@ namespace {
 /* the frame tile that owns byte p (< len) of a frame's ungrouped content: 16 KiB of the elements each, the tail with the last one */
 __host__ __device__ inline uint32_t window_tile(uint32_t p, uint32_t tiles) { return (p >> kUngroupTileLog) < tiles ? (p >> kUngroupTileLog) : tiles - 1u; }
 
-/* One workgroup per frame tile that a row's window intersects; the row of a workgroup is the last one with tile0 <= blockIdx.x (rows without
- * a workgroup share the tile0 of the row behind them and are never that one).  Its body is written on its own and not through ungroup_tile /
+/* One workgroup per frame tile that a row's window intersects, in the tile0 numbering (tile0_row_of).  Its body is written on its own and not through ungroup_tile /
  * ungroup_store: a window has its own origin (winOff), its own clipping of the tile and its own strips, and the two whole-row kernels stay the
  * code they were.  The pieces are shared: ungroup_load and ungroup_word take any element origin, here the first element of the workgroup's
  * share [lo, hi) of the window instead of the tile's, so only that share's part of each plane strip comes into LDS. */
@@ -1171,17 +1222,10 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_window_kernel(const q
     __shared__ __attribute__((aligned(16))) uint8_t lds[kUngroupLds];
     __shared__ uint32_t which;
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (tid == 0) which = tile0_row_of(rows, nRows);
     __syncthreads();
     const qzstd_hip_ungroup_win_row_t row = rows[which];
-    if (!row.winLen) return; /* (never: see above) */
+    if (!row.winLen) return; /* (never: rows without a workgroup are not found, tile0_row_of) */
     const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
     const uint32_t n = row.len >> kLog, tileMax = kUngroupTile >> kLog;
     const uint32_t tiles = n ? (uint32_t)(((uint64_t)n + tileMax - 1u) / tileMax) : 1u;
@@ -1252,48 +1296,36 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_window_kernel(const q
 extern "C" int qzstd_hip_ungroup_window(int device, void *stream, qzstd_hip_ungroup_win_row_t *rows, uint32_t nRows,
                                         qzstd_hip_ungroup_win_row_t *d_rows, const void *d_stage, size_t stageBytes)
 {
+    using row_t = qzstd_hip_ungroup_win_row_t;
+    constexpr const char *who = "qzstd_hip_ungroup_window";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_window: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ungroup_win_row_t &r = rows[i];
-        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_window: elem not 1, 2, 4 or 8");
-        if (r.reserved) return fail_msg("qzstd_hip_ungroup_window: reserved not 0");
-        if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_window: srcOff not a multiple of 16");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_window: frame too long");
-        if ((uint64_t)r.winOff + r.winLen > r.len) return fail_msg("qzstd_hip_ungroup_window: a window ends past its frame");
-        if (r.winLen && !r.dst) return fail_msg("qzstd_hip_ungroup_window: null destination");
-        if (i && r.srcOff == rows[i - 1].srcOff) { /* the same frame again: the next window of it */
-            if (r.len != rows[i - 1].len || r.elem != rows[i - 1].elem || r.winOff < (uint64_t)rows[i - 1].winOff + rows[i - 1].winLen)
-                return fail_msg("qzstd_hip_ungroup_window: windows of one frame differ in len or elem, overlap or are not in ascending order");
-        } else if (r.srcOff < end) {
-            return fail_msg("qzstd_hip_ungroup_window: frames overlap in the stage or are not in ascending order");
-        }
-        if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_window: a frame ends past stageBytes");
-        end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
-        if (r.winLen) {
-            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
-            const uint32_t tiles = n ? (uint32_t)((n + tileMax - 1u) / tileMax) : 1u;
-            total += window_tile(r.winOff + r.winLen - 1u, tiles) - window_tile(r.winOff, tiles) + 1u;
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_ungroup_window: stage span too large");
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_window: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    uint64_t end = 0;
+    const auto check = [&](const row_t &r, uint32_t i) -> const char * {
+        if (const char *why = elem_check(r.elem)) return why;
+        if (r.reserved) return "reserved not 0";
+        if (r.srcOff & 15u) return "srcOff not a multiple of 16";
+        if (const char *why = len_check(r.len)) return why;
+        if ((uint64_t)r.winOff + r.winLen > r.len) return "a window ends past its frame";
+        if (r.winLen && !r.dst) return "null destination";
+        const bool again = i && r.srcOff == rows[i - 1].srcOff; /* the same frame again: the next window of it */
+        if (again && (r.len != rows[i - 1].len || r.elem != rows[i - 1].elem || r.winOff < (uint64_t)rows[i - 1].winOff + rows[i - 1].winLen))
+            return "windows of one frame differ in len or elem, overlap or are not in ascending order";
+        if (const char *why = stage_place(r.srcOff, round16(r.len), r.len, stageBytes, again, &end)) return why;
+        return i + 1u == nRows ? stage_span_check(end) : nullptr; /* (of the whole table: behind the last row's own checks) */
+    };
+    const auto tiles = [](const row_t &r) -> uint32_t { /* the frame tiles that the window intersects */
+        if (!r.winLen) return 0u;
+        const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
+        const uint32_t frameTiles = n ? (uint32_t)((n + tileMax - 1u) / tileMax) : 1u;
+        return window_tile(r.winOff + r.winLen - 1u, frameTiles) - window_tile(r.winOff, frameTiles) + 1u;
+    };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, tiles, false, &total)) return -1;
     if (total == 0) return 0; /* nothing but empty windows */
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        qzstd_hip_ungroup_win_row_t &r = rows[i];
-        r.tile0 = (uint32_t)total;
-        if (r.winLen) {
-            const uint64_t n = r.len / r.elem, tileMax = kUngroupTile / r.elem;
-            const uint32_t tiles = n ? (uint32_t)((n + tileMax - 1u) / tileMax) : 1u;
-            total += window_tile(r.winOff + r.winLen - 1u, tiles) - window_tile(r.winOff, tiles) + 1u;
-        }
-    }
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup window rows)");
-    hipLaunchKernelGGL(qzstd_ungroup_window_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
+    hipLaunchKernelGGL(qzstd_ungroup_window_kernel, dim3(total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
                        static_cast<const uint8_t *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_window_kernel");
     return 0;
@@ -1312,8 +1344,8 @@ __device__ inline void cmp_mask(uint32_t valid, uint64_t *o0, uint64_t *o1)
 }
 
 /* qzstd_ungroup_xor_kernel with its store replaced by a comparison.  One workgroup per 16 KiB tile of a frame's ungrouped content u[] (the tail
- * with the last tile, a frame shorter than an element one tile); its row is the last one with tile0 <= blockIdx.x (qzstd_ungroup_window_kernel's
- * search).  Phase A is ungroup_load: the tile's plane strips, stage to LDS — nothing for a ZERO row, whose u[] is zeros and whose stage is
+ * with the last tile, a frame shorter than an element one tile), in the tile0 numbering (tile0_row_of).
+ * Phase A is ungroup_load: the tile's plane strips, stage to LDS — nothing for a ZERO row, whose u[] is zeros and whose stage is
  * never read.  Phase B walks the tile's bytes [t0, t1) of u[] in 16-byte steps FROM THE TILE'S START (nothing is stored, so no side's
  * alignment has to be met): a lane assembles u's 16 bytes with ungroup_word, takes the few bytes behind the strips' end — the tail — singly
  * from the stage (ungroup_byte), fetches base and ref as the comparison with a base fetches its sides (group_fetch: the aligned words that
@@ -1326,14 +1358,7 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_kernel(const qzst
     __shared__ uint32_t which;
     __shared__ uint32_t red[kUngroupT / 64u];
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (tid == 0) which = tile0_row_of(rows, nRows);
     __syncthreads();
     const qzstd_hip_ungroup_cmp_row_t row = rows[which];
     const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
@@ -1408,35 +1433,25 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_kernel(const qzst
 extern "C" int qzstd_hip_ungroup_cmp(int device, void *stream, qzstd_hip_ungroup_cmp_row_t *rows, uint32_t nRows,
                                      qzstd_hip_ungroup_cmp_row_t *d_rows, const void *d_stage, size_t stageBytes, uint32_t *d_tiles)
 {
+    using row_t = qzstd_hip_ungroup_cmp_row_t;
+    constexpr const char *who = "qzstd_hip_ungroup_cmp";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_cmp: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ungroup_cmp_row_t &r = rows[i];
-        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_cmp: elem not 1, 2, 4 or 8");
-        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return fail_msg("qzstd_hip_ungroup_cmp: unknown flags");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_cmp: frame too long");
-        if (r.len && !r.ref) return fail_msg("qzstd_hip_ungroup_cmp: null ref");
-        if (!(r.flags & QZSTD_HIP_CMP_ZERO)) { /* a ZERO row's srcOff is not looked at */
-            if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_cmp: srcOff not a multiple of 16");
-            if (r.len && !d_stage) return fail_msg("qzstd_hip_ungroup_cmp: null stage");
-            if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_cmp: frames overlap in the stage or are not in ascending order");
-            if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_cmp: a frame ends past stageBytes");
-            end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
-        }
-        total += QZSTD_HIP_CMP_TILES(r.len, r.elem);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_cmp: too many tiles");
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    uint64_t end = 0;
+    const auto check = [&](const row_t &r, uint32_t) -> const char * {
+        if (const char *why = elem_check(r.elem)) return why;
+        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return "unknown flags";
+        if (const char *why = len_check(r.len)) return why;
+        if (r.len && !r.ref) return "null ref";
+        if (r.flags & QZSTD_HIP_CMP_ZERO) return nullptr; /* a ZERO row's srcOff is not looked at */
+        return frame_place(r.srcOff, r.len, d_stage, stageBytes, &end);
+    };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, [](const row_t &r) { return QZSTD_HIP_CMP_TILES(r.len, r.elem); }, false, &total)) return -1;
     if (total == 0) return 0; /* nothing but empty rows */
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_CMP_TILES(rows[i].len, rows[i].elem);
-    }
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup cmp rows)");
-    hipLaunchKernelGGL(qzstd_ungroup_cmp_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
+    hipLaunchKernelGGL(qzstd_ungroup_cmp_kernel, dim3(total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows,
                        static_cast<const uint8_t *>(d_stage), d_tiles);
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_cmp_kernel");
     return 0;
@@ -1447,27 +1462,19 @@ namespace {
 constexpr uint32_t kDiffT = 256u;               /* threads per workgroup */
 constexpr uint32_t kDiffTileLog = kGroupTileLog; /* bytes of one row per workgroup: 16 KiB, four 16-byte words per lane */
 
-/* One workgroup per 16 KiB tile of a row; its row is the last one with tile0 <= blockIdx.x (qzstd_ungroup_window_kernel's search: rows
- * without a tile share the tile0 of the row behind them and are never that one).  Both sides are fetched as the grouping gather fetches
+/* One workgroup per 16 KiB tile of a row, in the tile0 numbering (tile0_row_of).  Both sides are fetched as the grouping gather fetches
  * its source — group_fetch: the aligned word that holds the first wanted byte and the next one only when wanted bytes lie in it, shifted
  * by that side's OWN misalignment, so the bytes in front of a and b never arrive — and the bytes behind the row's last one are masked
  * before the lane's OR.  A wave that saw a difference stores the 1 from one lane: no atomics, the flag is never read. */
 __global__ __launch_bounds__(kDiffT) void qzstd_diff_kernel(const qzstd_hip_diff_row_t *__restrict__ rows, uint32_t nRows, uint32_t *__restrict__ flags)
 {
     __shared__ uint32_t which;
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (threadIdx.x == 0) which = tile0_row_of(rows, nRows);
     __syncthreads();
     const uint32_t r = which;
     const qzstd_hip_diff_row_t row = rows[r];
     const uint64_t at = (uint64_t)(blockIdx.x - row.tile0) << kDiffTileLog; /* the tile's first byte in its row */
-    if (at >= row.len) return; /* (never: see above) */
+    if (at >= row.len) return; /* (never: rows without a tile are not found, tile0_row_of) */
     const uint32_t tileBytes = row.len - at < (1u << kDiffTileLog) ? (uint32_t)(row.len - at) : 1u << kDiffTileLog;
     uint64_t acc = 0;
     for (uint32_t w = threadIdx.x; w * 16u < tileBytes; w += kDiffT) {
@@ -1489,27 +1496,19 @@ __global__ __launch_bounds__(kDiffT) void qzstd_diff_kernel(const qzstd_hip_diff
 
 extern "C" int qzstd_hip_diff(int device, void *stream, qzstd_hip_diff_row_t *rows, uint32_t nRows, qzstd_hip_diff_row_t *d_rows, uint32_t *d_flags)
 {
+    using row_t = qzstd_hip_diff_row_t;
+    constexpr const char *who = "qzstd_hip_diff";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_flags) return fail_msg("qzstd_hip_diff: null pointer");
-    uint64_t total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_diff_row_t &r = rows[i];
-        if (r.len && (!r.a || !r.b)) return fail_msg("qzstd_hip_diff: null row");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_diff: row too long");
-        total += ((uint64_t)r.len + (1u << kDiffTileLog) - 1u) >> kDiffTileLog;
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_diff: too many tiles");
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += ((uint64_t)rows[i].len + (1u << kDiffTileLog) - 1u) >> kDiffTileLog;
-    }
+    if (!rows || !d_rows || !d_flags) return refuse(who, "null pointer");
+    const auto check = [](const row_t &r, uint32_t) -> const char * { return r.len && (!r.a || !r.b) ? "null row" : len_check(r.len); };
+    const auto tiles = [](const row_t &r) { return ((uint64_t)r.len + (1u << kDiffTileLog) - 1u) >> kDiffTileLog; };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, tiles, true, &total)) return -1;
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemsetAsync(d_flags, 0, (size_t)nRows * sizeof(uint32_t), (hipStream_t)stream), "hipMemsetAsync (diff flags)");
     if (total == 0) return 0; /* nothing but empty rows: their flags are 0 */
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (diff rows)");
-    hipLaunchKernelGGL(qzstd_diff_kernel, dim3((uint32_t)total), dim3(kDiffT), 0, (hipStream_t)stream, d_rows, nRows, d_flags);
+    hipLaunchKernelGGL(qzstd_diff_kernel, dim3(total), dim3(kDiffT), 0, (hipStream_t)stream, d_rows, nRows, d_flags);
     QZ_CHECK(hipGetLastError(), "launch qzstd_diff_kernel");
     return 0;
 }
@@ -2032,7 +2031,7 @@ constexpr uint32_t kFpTileLog = QZSTD_FP_TILE_LOG; /* bytes of one row per workg
 constexpr uint32_t kFpWords = (1u << kFpTileLog) / 16u / kFpT;
 static_assert(kFpT == 256u && kFpWords == 4u && kFpTileLog == kDiffTileLog, "the definition's tile: 256 lanes, four words each");
 
-/* One workgroup per 16 KiB tile of a row; its row is the last one with tile0 <= blockIdx.x (qzstd_diff_kernel's search).  Lane t fetches
+/* One workgroup per 16 KiB tile of a row, in the tile0 numbering (tile0_row_of).  Lane t fetches
  * the tile's words t, t + 256, t + 512, t + 768 as the comparison fetches its sides — group_fetch: the aligned words that overlap the wanted
  * bytes only, shifted by the row's OWN misalignment — all four before the first round, so that the loads are in flight together; the bytes
  * behind the row's last one are masked to 0 (cmp_mask) before they enter a round.  Then the definition's tree: six steps inside the wave
@@ -2044,14 +2043,7 @@ __global__ __launch_bounds__(kFpT) void qzstd_fingerprint_kernel(const qzstd_hip
     __shared__ uint32_t which;
     __shared__ uint64_t red[kFpT / 64u];
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (tid == 0) which = tile0_row_of(rows, nRows);
     __syncthreads();
     const qzstd_hip_fp_row_t row = rows[which];
     const uint64_t at = (uint64_t)(blockIdx.x - row.tile0) << kFpTileLog; /* the tile's first byte in its row */
@@ -2088,26 +2080,17 @@ __global__ __launch_bounds__(kFpT) void qzstd_fingerprint_kernel(const qzstd_hip
 
 extern "C" int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows, uint64_t *d_tiles)
 {
+    using row_t = qzstd_hip_fp_row_t;
+    constexpr const char *who = "qzstd_hip_fingerprint";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_tiles) return fail_msg("qzstd_hip_fingerprint: null pointer");
-    uint64_t total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_fp_row_t &r = rows[i];
-        if (r.len && !r.src) return fail_msg("qzstd_hip_fingerprint: null row");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_fingerprint: row too long");
-        total += QZSTD_HIP_FP_TILES(r.len);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_fingerprint: too many tiles");
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_FP_TILES(rows[i].len);
-    }
+    if (!rows || !d_rows || !d_tiles) return refuse(who, "null pointer");
+    const auto check = [](const row_t &r, uint32_t) -> const char * { return r.len && !r.src ? "null row" : len_check(r.len); };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, [](const row_t &r) { return QZSTD_HIP_FP_TILES(r.len); }, true, &total)) return -1;
     if (total == 0) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (fingerprint rows)");
-    hipLaunchKernelGGL(qzstd_fingerprint_kernel, dim3((uint32_t)total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows,
+    hipLaunchKernelGGL(qzstd_fingerprint_kernel, dim3(total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows,
                        reinterpret_cast<unsigned long long *>(d_tiles));
     QZ_CHECK(hipGetLastError(), "launch qzstd_fingerprint_kernel");
     return 0;
@@ -2137,11 +2120,7 @@ __global__ __launch_bounds__(kFpT) void qzstd_fingerprint_pieces_kernel(const qz
     __shared__ uint64_t red[kFpT / 64u];
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
+        const uint32_t lo = tile0_row_of(rows, nRows);
         which = lo;
         const qzstd_hip_fp_pieces_row_t rw = rows[lo];
         const uint64_t a = (uint64_t)(blockIdx.x - rw.tile0) << kFpTileLog;
@@ -2198,11 +2177,7 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_pieces_kernel(con
     __shared__ uint32_t red[kUngroupT / 64u];
     const uint32_t tid = threadIdx.x;
     if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
+        const uint32_t lo = tile0_row_of(rows, nRows);
         which = lo;
         const qzstd_hip_ungroup_cmp_pieces_row_t rw = rows[lo];
         const uint32_t kl = rw.elem == 8u ? 3u : (rw.elem == 4u ? 2u : (rw.elem == 2u ? 1u : 0u));
@@ -2280,53 +2255,29 @@ __global__ __launch_bounds__(kUngroupT) void qzstd_ungroup_cmp_pieces_kernel(con
         tilesOut[blockIdx.x] = m;
     }
 }
-
-/* the piece table's checks, qzstd_hip_group_pieces's: row [piece0, piece0 + count) tiles [0, len); noBase: a base is refused too */
-inline const char *pieces_check(const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, uint32_t piece0, uint32_t count, uint32_t len, bool noBase)
-{
-    if ((uint64_t)piece0 + count > nPieces) return "a row's pieces end past the table";
-    uint64_t at = 0;
-    for (uint32_t p = piece0; p < piece0 + count; p++) {
-        if (!pieces[p].len || !pieces[p].src) return "an empty piece or a null source";
-        if (noBase && pieces[p].base) return "a piece with a base";
-        if (pieces[p].off != at) return "a row's pieces do not tile its content in ascending order";
-        at += pieces[p].len;
-    }
-    return at == len ? nullptr : "a row's pieces do not tile its content in ascending order";
-}
 } // namespace
 
 extern "C" int qzstd_hip_fingerprint_pieces(int device, void *stream, qzstd_hip_fp_pieces_row_t *rows, uint32_t nRows, qzstd_hip_fp_pieces_row_t *d_rows,
                                             const qzstd_hip_group_piece_t *pieces, uint32_t nPieces, qzstd_hip_group_piece_t *d_pieces,
                                             uint64_t *d_tiles)
 {
+    using row_t = qzstd_hip_fp_pieces_row_t;
+    constexpr const char *who = "qzstd_hip_fingerprint_pieces";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_tiles) return fail_msg("qzstd_hip_fingerprint_pieces: null pointer");
-    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_fingerprint_pieces: null piece table");
-    uint64_t total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_fp_pieces_row_t &r = rows[i];
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_fingerprint_pieces: row too long");
-        if (const char *why = pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, true)) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "qzstd_hip_fingerprint_pieces: %s", why);
-            return fail_msg(msg);
-        }
-        total += QZSTD_HIP_FP_TILES(r.len);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_fingerprint_pieces: too many tiles");
+    if (!rows || !d_rows || !d_tiles) return refuse(who, "null pointer");
+    if (nPieces && (!pieces || !d_pieces)) return refuse(who, "null piece table");
+    const auto check = [&](const row_t &r, uint32_t) -> const char * {
+        if (const char *why = len_check(r.len)) return why;
+        return pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, true);
+    };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, [](const row_t &r) { return QZSTD_HIP_FP_TILES(r.len); }, false, &total)) return -1;
     if (total == 0) return 0; /* nothing but empty rows */
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_FP_TILES(rows[i].len);
-    }
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (fingerprint pieces rows)");
     QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
              "hipMemcpyAsync H2D (fingerprint pieces table)");
-    hipLaunchKernelGGL(qzstd_fingerprint_pieces_kernel, dim3((uint32_t)total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
+    hipLaunchKernelGGL(qzstd_fingerprint_pieces_kernel, dim3(total), dim3(kFpT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
                        reinterpret_cast<unsigned long long *>(d_tiles));
     QZ_CHECK(hipGetLastError(), "launch qzstd_fingerprint_pieces_kernel");
     return 0;
@@ -2336,42 +2287,28 @@ extern "C" int qzstd_hip_ungroup_cmp_pieces(int device, void *stream, qzstd_hip_
                                             qzstd_hip_ungroup_cmp_pieces_row_t *d_rows, const qzstd_hip_group_piece_t *pieces, uint32_t nPieces,
                                             qzstd_hip_group_piece_t *d_pieces, const void *d_stage, size_t stageBytes, uint32_t *d_tiles)
 {
+    using row_t = qzstd_hip_ungroup_cmp_pieces_row_t;
+    constexpr const char *who = "qzstd_hip_ungroup_cmp_pieces";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null pointer or stage not 16-byte aligned");
-    if (nPieces && (!pieces || !d_pieces)) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null piece table");
-    uint64_t end = 0, total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ungroup_cmp_pieces_row_t &r = rows[i];
-        if (r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: elem not 1, 2, 4 or 8");
-        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return fail_msg("qzstd_hip_ungroup_cmp_pieces: unknown flags");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: frame too long");
-        if (const char *why = pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, false)) {
-            char msg[160];
-            snprintf(msg, sizeof(msg), "qzstd_hip_ungroup_cmp_pieces: %s", why);
-            return fail_msg(msg);
-        }
-        if (!(r.flags & QZSTD_HIP_CMP_ZERO)) { /* a ZERO row's srcOff is not looked at */
-            if (r.srcOff & 15u) return fail_msg("qzstd_hip_ungroup_cmp_pieces: srcOff not a multiple of 16");
-            if (r.len && !d_stage) return fail_msg("qzstd_hip_ungroup_cmp_pieces: null stage");
-            if (r.srcOff < end) return fail_msg("qzstd_hip_ungroup_cmp_pieces: frames overlap in the stage or are not in ascending order");
-            if (r.srcOff > (uint64_t)stageBytes || r.len > (uint64_t)stageBytes - r.srcOff) return fail_msg("qzstd_hip_ungroup_cmp_pieces: a frame ends past stageBytes");
-            end = r.srcOff + (((uint64_t)r.len + 15u) & ~(uint64_t)15u);
-        }
-        total += QZSTD_HIP_CMP_TILES(r.len, r.elem);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ungroup_cmp_pieces: too many tiles");
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    if (nPieces && (!pieces || !d_pieces)) return refuse(who, "null piece table");
+    uint64_t end = 0;
+    const auto check = [&](const row_t &r, uint32_t) -> const char * {
+        if (const char *why = elem_check(r.elem)) return why;
+        if (r.flags & ~QZSTD_HIP_CMP_ZERO) return "unknown flags";
+        if (const char *why = len_check(r.len)) return why;
+        if (const char *why = pieces_check(pieces, nPieces, r.piece0, r.nPieces, r.len, false)) return why;
+        if (r.flags & QZSTD_HIP_CMP_ZERO) return nullptr; /* a ZERO row's srcOff is not looked at */
+        return frame_place(r.srcOff, r.len, d_stage, stageBytes, &end);
+    };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, [](const row_t &r) { return QZSTD_HIP_CMP_TILES(r.len, r.elem); }, false, &total)) return -1;
     if (total == 0) return 0; /* nothing but empty rows */
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_CMP_TILES(rows[i].len, rows[i].elem);
-    }
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ungroup cmp pieces rows)");
     QZ_CHECK(hipMemcpyAsync(d_pieces, pieces, (size_t)nPieces * sizeof(*pieces), hipMemcpyHostToDevice, (hipStream_t)stream),
              "hipMemcpyAsync H2D (ungroup cmp pieces table)");
-    hipLaunchKernelGGL(qzstd_ungroup_cmp_pieces_kernel, dim3((uint32_t)total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
+    hipLaunchKernelGGL(qzstd_ungroup_cmp_pieces_kernel, dim3(total), dim3(kUngroupT), 0, (hipStream_t)stream, d_rows, nRows, d_pieces,
                        static_cast<const uint8_t *>(d_stage), d_tiles);
     QZ_CHECK(hipGetLastError(), "launch qzstd_ungroup_cmp_pieces_kernel");
     return 0;
@@ -2472,14 +2409,7 @@ __global__ __launch_bounds__(kGroupT) void qzstd_group_ediff_kernel(const qzstd_
     __shared__ __attribute__((aligned(16))) uint8_t lds[kGroupLds];
     __shared__ uint32_t which;
     const uint64_t v = firstTile + blockIdx.x;
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u; /* the last row whose first tile is at or before v */
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if ((rows[mid].dstOff >> kGroupTileLog) + mid <= v) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (threadIdx.x == 0) which = stage_row_of(rows, nRows, &qzstd_hip_group_ediff_row_t::dstOff, v);
     __syncthreads();
     const uint32_t r = which;
     const qzstd_hip_group_ediff_row_t row = rows[r];
@@ -2604,14 +2534,7 @@ struct esum_tile_t {
 __device__ inline bool esum_tile_load(const qzstd_hip_esum_row_t *__restrict__ rows, uint32_t nRows, const uint4 *__restrict__ heads, uint32_t *which,
                                       esum_tile_t *t)
 {
-    if (threadIdx.x == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        *which = lo;
-    }
+    if (threadIdx.x == 0) *which = tile0_row_of(rows, nRows);
     __syncthreads();
     t->row = rows[*which];
     t->kLog = t->row.elem == 8u ? 3u : (t->row.elem == 4u ? 2u : (t->row.elem == 2u ? 1u : 0u));
@@ -2771,64 +2694,52 @@ __global__ __launch_bounds__(kEsumT) void qzstd_esum_apply_kernel(const qzstd_hi
 }
 } // namespace
 
-/* (qzstd_hip_group's checks and launch geometry, row for row) */
 extern "C" int qzstd_hip_group_ediff(int device, void *stream, const qzstd_hip_group_ediff_row_t *rows, uint32_t nRows,
                                      qzstd_hip_group_ediff_row_t *d_rows, void *d_stage, size_t stageBytes)
 {
+    constexpr const char *who = "qzstd_hip_group_ediff";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return fail_msg("qzstd_hip_group_ediff: null pointer or stage not 16-byte aligned");
-    uint64_t end = 0, endTile = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_group_ediff_row_t &r = rows[i];
-        const uint64_t ext = (uint64_t)r.len + r.pad;
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || (r.flags & ~QZSTD_HIP_EDIFF_DIFF))
-            return fail_msg("qzstd_hip_group_ediff: elem not 1, 2, 4 or 8, or unknown flags");
-        if ((r.dstOff & 15u) || (ext & 15u)) return fail_msg("qzstd_hip_group_ediff: dstOff or len + pad not a multiple of 16");
-        if (r.len && !r.src) return fail_msg("qzstd_hip_group_ediff: null source");
-        if (r.dstOff < end) return fail_msg("qzstd_hip_group_ediff: rows overlap in the stage or are not in ascending order");
-        if (r.dstOff > (uint64_t)stageBytes || ext > (uint64_t)stageBytes - r.dstOff) return fail_msg("qzstd_hip_group_ediff: a row ends past stageBytes");
-        end = r.dstOff + ext;
-        if (ext) {
-            const uint64_t n = r.len / r.elem, tileMax = kGroupTile / r.elem;
-            endTile = (r.dstOff >> kGroupTileLog) + i + (n ? (n + tileMax - 1u) / tileMax : 1u);
-        }
-    }
-    if ((end >> 4) > 0xFFFFFFFFull - 2u * kGatherWords) return fail_msg("qzstd_hip_group_ediff: stage span too large");
-    if (endTile == 0) return 0; /* nothing but empty rows */
-    const uint64_t firstTile = rows[0].dstOff >> kGroupTileLog;
-    if (endTile - firstTile > 0x7FFFFFFFull) return fail_msg("qzstd_hip_group_ediff: too many tiles");
+    if (!rows || !d_rows || !d_stage || ((uintptr_t)d_stage & 15u)) return refuse(who, "null pointer or stage not 16-byte aligned");
+    const auto own = [](const qzstd_hip_group_ediff_row_t &r) {
+        return row_own_t{ r.flags & ~QZSTD_HIP_EDIFF_DIFF ? "unknown flags" : nullptr, r.len && !r.src ? "null source" : nullptr, nullptr };
+    };
+    stage_launch_t go;
+    if (group_rows_check(who, rows, nRows, stageBytes, own, &go)) return -1;
+    if (!go.tiles) return 0; /* nothing but empty rows */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (group ediff rows)");
-    hipLaunchKernelGGL(qzstd_group_ediff_kernel, dim3((uint32_t)(endTile - firstTile)), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows,
-                       firstTile, static_cast<uint4 *>(d_stage));
+    hipLaunchKernelGGL(qzstd_group_ediff_kernel, dim3(go.tiles), dim3(kGroupT), 0, (hipStream_t)stream, d_rows, nRows, go.firstTile,
+                       static_cast<uint4 *>(d_stage));
     QZ_CHECK(hipGetLastError(), "launch qzstd_group_ediff_kernel");
     return 0;
 }
 
+namespace {
+/* the element sum's and the element-difference cost's rows: `mem` is the row's address, needed when the row has an element */
+inline const char *elems_row_check(uint32_t elem, uint32_t reserved, uint32_t len, uint64_t mem)
+{
+    if (const char *why = elem_check(elem)) return why;
+    if (reserved) return "reserved not 0";
+    if (const char *why = len_check(len)) return why;
+    return len >= elem && !mem ? "null row" : nullptr;
+}
+} // namespace
+
 extern "C" int qzstd_hip_esum(int device, void *stream, qzstd_hip_esum_row_t *rows, uint32_t nRows, qzstd_hip_esum_row_t *d_rows, void *d_scratch,
                               size_t scratchBytes)
 {
+    using row_t = qzstd_hip_esum_row_t;
+    constexpr const char *who = "qzstd_hip_esum";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_scratch || ((uintptr_t)d_scratch & 15u)) return fail_msg("qzstd_hip_esum: null pointer or scratch not 16-byte aligned");
-    uint64_t total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_esum_row_t &r = rows[i];
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
-            return fail_msg("qzstd_hip_esum: elem not 1, 2, 4 or 8, or reserved not 0");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_esum: row too long");
-        if (r.len >= r.elem && !r.dst) return fail_msg("qzstd_hip_esum: null row");
-        total += QZSTD_HIP_ESUM_TILES(r.len, r.elem);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_esum: too many tiles");
-    if (QZSTD_HIP_ESUM_SCRATCH_BYTES(total) > scratchBytes) return fail_msg("qzstd_hip_esum: scratch too small");
-    if (total == 0) return 0; /* no row with an element */
-    const uint32_t tiles = (uint32_t)total;
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_ESUM_TILES(rows[i].len, rows[i].elem);
-    }
+    if (!rows || !d_rows || !d_scratch || ((uintptr_t)d_scratch & 15u)) return refuse(who, "null pointer or scratch not 16-byte aligned");
+    const auto check = [](const row_t &r, uint32_t) { return elems_row_check(r.elem, r.reserved, r.len, r.dst); };
+    const auto tilesOf = [](const row_t &r) { return QZSTD_HIP_ESUM_TILES(r.len, r.elem); };
+    uint32_t tiles;
+    /* (tile0_rows's steps, with the scratch held against the count before anything is written) */
+    if (tile0_count(who, rows, nRows, check, tilesOf, &tiles)) return -1;
+    if (QZSTD_HIP_ESUM_SCRATCH_BYTES(tiles) > scratchBytes) return refuse(who, "scratch too small");
+    if (tiles == 0) return 0; /* no row with an element */
+    tile0_write(rows, nRows, tilesOf);
     QZ_SET_DEVICE(device);
     const hipStream_t s = (hipStream_t)stream;
     auto *heads = static_cast<uint4 *>(d_scratch);
@@ -2970,8 +2881,7 @@ template <uint32_t K> __device__ inline void ec_tile(uint64_t srcTile, uint32_t 
     }
 }
 
-/* One workgroup per tile of a row's elements; its row is the last one with tile0 <= blockIdx.x (qzstd_diff_kernel's search: rows without
- * a tile share the tile0 of the row behind them and are never that one).  No atomics but the LDS ones; nothing is read back. */
+/* One workgroup per tile of a row's elements, in the tile0 numbering (tile0_row_of).  No atomics but the LDS ones; nothing is read back. */
 __global__ __launch_bounds__(kEcT) void qzstd_ediff_cost_kernel(const qzstd_hip_ediff_cost_row_t *__restrict__ rows, uint32_t nRows,
                                                                 uint2 *__restrict__ tilesOut)
 {
@@ -2979,21 +2889,14 @@ __global__ __launch_bounds__(kEcT) void qzstd_ediff_cost_kernel(const qzstd_hip_
     __shared__ uint32_t red[16][kEcT / 64u];
     __shared__ uint32_t which;
     const uint32_t tid = threadIdx.x;
-    if (tid == 0) {
-        uint32_t lo = 0, hi = nRows - 1u;
-        while (lo < hi) {
-            const uint32_t mid = lo + ((hi - lo + 1u) >> 1);
-            if (rows[mid].tile0 <= blockIdx.x) lo = mid; else hi = mid - 1u;
-        }
-        which = lo;
-    }
+    if (tid == 0) which = tile0_row_of(rows, nRows);
     for (uint32_t i = tid; i < kEcWords / 4u; i += kEcT) reinterpret_cast<uint4 *>(hist)[i] = make_uint4(0u, 0u, 0u, 0u);
     __syncthreads();
     const qzstd_hip_ediff_cost_row_t row = rows[which];
     const uint32_t kLog = row.elem == 8u ? 3u : (row.elem == 4u ? 2u : (row.elem == 2u ? 1u : 0u));
     const uint32_t n = row.len >> kLog, tileMax = kEcTile >> kLog;
     const uint64_t e0 = (uint64_t)(blockIdx.x - row.tile0) * tileMax; /* the tile's first element in its row */
-    if (e0 >= n) return; /* (the whole workgroup; never: see above) */
+    if (e0 >= n) return; /* (the whole workgroup; never: rows without a tile are not found, tile0_row_of) */
     const uint32_t tileBytes = (n - (uint32_t)e0 < tileMax ? n - (uint32_t)e0 : tileMax) << kLog;
     const uint64_t srcTile = row.src + (e0 << kLog);
     uint2 *out = tilesOut + blockIdx.x;
@@ -3009,28 +2912,17 @@ __global__ __launch_bounds__(kEcT) void qzstd_ediff_cost_kernel(const qzstd_hip_
 extern "C" int qzstd_hip_ediff_cost(int device, void *stream, qzstd_hip_ediff_cost_row_t *rows, uint32_t nRows, qzstd_hip_ediff_cost_row_t *d_rows,
                                     uint32_t *d_tiles)
 {
+    using row_t = qzstd_hip_ediff_cost_row_t;
+    constexpr const char *who = "qzstd_hip_ediff_cost";
     if (nRows == 0) return 0;
-    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_tiles & 7u)) return fail_msg("qzstd_hip_ediff_cost: null pointer or tiles not 8-byte aligned");
-    uint64_t total = 0;
-    /* everything is checked before tile0 is written: a refused launch leaves the caller's rows as they were */
-    for (uint32_t i = 0; i < nRows; i++) {
-        const qzstd_hip_ediff_cost_row_t &r = rows[i];
-        if ((r.elem != 1u && r.elem != 2u && r.elem != 4u && r.elem != 8u) || r.reserved != 0u)
-            return fail_msg("qzstd_hip_ediff_cost: elem not 1, 2, 4 or 8, or reserved not 0");
-        if (r.len > 0xFFFFFFE0u) return fail_msg("qzstd_hip_ediff_cost: row too long");
-        if (r.len >= r.elem && !r.src) return fail_msg("qzstd_hip_ediff_cost: null row");
-        total += QZSTD_HIP_ESUM_TILES(r.len, r.elem);
-    }
-    if (total > 0x7FFFFFFFull) return fail_msg("qzstd_hip_ediff_cost: too many tiles");
-    total = 0;
-    for (uint32_t i = 0; i < nRows; i++) {
-        rows[i].tile0 = (uint32_t)total;
-        total += QZSTD_HIP_ESUM_TILES(rows[i].len, rows[i].elem);
-    }
+    if (!rows || !d_rows || !d_tiles || ((uintptr_t)d_tiles & 7u)) return refuse(who, "null pointer or tiles not 8-byte aligned");
+    const auto check = [](const row_t &r, uint32_t) { return elems_row_check(r.elem, r.reserved, r.len, r.src); };
+    uint32_t total;
+    if (tile0_rows(who, rows, nRows, check, [](const row_t &r) { return QZSTD_HIP_ESUM_TILES(r.len, r.elem); }, true, &total)) return -1;
     if (total == 0) return 0; /* no row with an element */
     QZ_SET_DEVICE(device);
     QZ_CHECK(hipMemcpyAsync(d_rows, rows, (size_t)nRows * sizeof(*rows), hipMemcpyHostToDevice, (hipStream_t)stream), "hipMemcpyAsync H2D (ediff cost rows)");
-    hipLaunchKernelGGL(qzstd_ediff_cost_kernel, dim3((uint32_t)total), dim3(kEcT), 0, (hipStream_t)stream, d_rows, nRows,
+    hipLaunchKernelGGL(qzstd_ediff_cost_kernel, dim3(total), dim3(kEcT), 0, (hipStream_t)stream, d_rows, nRows,
                        reinterpret_cast<uint2 *>(d_tiles));
     QZ_CHECK(hipGetLastError(), "launch qzstd_ediff_cost_kernel");
     return 0;
