@@ -5,10 +5,10 @@
  * bytes.  Part of qzstd_frontend.c's translation unit, included behind qzstd_elemdiff.c; like the fingerprint calls it uses the restore's
  * first slot (its stream, and grow-only pinned and device scratch kept there between calls).
  *
- * A call is: the host-side checks of the batch compress call, the slot's stream waiting for the caller's, ONE qzstd_hip_ediff_cost launch
- * with a row per chunk that points INTO the caller's buffers (nothing is staged or copied on the device), one device->host copy of the
- * tiles' words (8 bytes per 16 KiB), a bounded wait, and the sums per buffer on the calling thread.  Nothing of the producer or the workers
- * is used: a front created with useProducer = 0 serves the call.
+ * A call is: the host-side checks of the batch compress call; the scaffold of qzstd_frontend.c (qfCallBegin .. qfCallEnd) with ONE stream;
+ * ONE qzstd_hip_ediff_cost launch with a row per chunk that points INTO the caller's buffers (nothing is staged or copied on the device);
+ * one device->host copy of the tiles' words (8 bytes per 16 KiB); and the sums per buffer on the calling thread.  Nothing of the producer or
+ * the workers is used: a front created with useProducer = 0 serves the call.
  */
 
 extern int qzstd_hip_ediff_cost(int device, void *stream, qzstd_hip_ediff_cost_row_t *rows, uint32_t nRows, qzstd_hip_ediff_cost_row_t *d_rows,
@@ -28,11 +28,13 @@ int QZSTD_ediffAdvisedOf(unsigned long long P, unsigned long long D) { return QZ
 size_t QZSTD_frontAdviseDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const unsigned char *elemSizes, size_t nBufs, void *stream,
                                     unsigned char *advised, unsigned long long *est)
 {
-    QF_RestoreSlot *s = NULL;
-    void *ev = NULL, *h;
+    QF_Call call;
+    QF_RestoreSlot *s;
+    qzstd_hip_ediff_cost_row_t *rows;
+    const uint32_t *tiles;
     size_t i, c = 0, nRows = 0, nTiles = 0, t = 0, nFlagged = 0;
     unsigned long long total = 0;
-    int dev = -1, rc = 0;
+    int dev, rc = 0;
     /* host-side checks, the batch compress call's: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && (!bufs || !advised)) || nBufs > 0xFFFFFFFFu || f->p.chunkSize > 0xFFFFFFE0u) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
@@ -47,56 +49,34 @@ size_t QZSTD_frontAdviseDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs,
     if (!qzstd_hip_ediff_cost || !qzstd_hip_pointer_device || !qzstd_hip_event_create || !qzstd_hip_event_record || !qzstd_hip_stream_wait_event ||
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the cost kernel, or without the device-input entry points at all */
-    for (i = 0; i < nBufs; i++) {
-        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
-        int d;
-        if (!bufs[i].size) continue;
-        d = qzstd_hip_pointer_device(p);
-        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
-        dev = d;
-    }
-    if (nTiles) {
-        pthread_mutex_lock(&f->mu);
-        if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-        f->devBusy = 1;
-        pthread_mutex_unlock(&f->mu);
-    }
+    call.f = f;
+    call.restore = 1;
+    call.nStreams = 1; /* the restore side's first slot alone, as the fingerprint calls */
+    call.dev = -1;
+    if (qfCallBufs(&call, bufs, NULL, nBufs)) return (size_t)-1;
+    /* `advised` and `est` are not written by a call that is refused; a call without a buffer that holds an element takes nothing — off is
+     * the default, and no GPU is touched — but is counted */
+    if (nTiles && qfCallBegin(&call, stream)) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
         advised[i] = (unsigned char)(elemSizes && elemSizes[i] ? elemSizes[i] : f->group);
         if (est) est[2u * i] = est[2u * i + 1u] = 0ull;
     }
-    if (nTiles == 0) { /* no buffer with an element: off is the default, and no GPU is touched */
+    if (nTiles == 0) {
         __atomic_fetch_add(&f->adviseStats[0], (unsigned long long)nBufs, __ATOMIC_RELAXED);
         return 0;
     }
-
-    /* the restore's slots, kept with the front between calls: the first one's stream and scratch */
-    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
-    if (!f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
-    f->restoreSlotDev = dev;
+    dev = call.dev;
     s = f->restoreSlot;
-    if (rc == 0 && !s->stream && !(s->stream = qzstd_hip_stream_create(dev))) rc = -1;
-    if (rc == 0) {
-        h = s->hAdvRows;
-        if (qfGrowH(&h, &s->hAdvRowsCap, nRows * sizeof(qzstd_hip_ediff_cost_row_t))) rc = -1;
-        s->hAdvRows = (qzstd_hip_ediff_cost_row_t *)h;
-    }
-    if (rc == 0) {
-        h = s->hAdvTiles;
-        if (qfGrowH(&h, &s->hAdvTilesCap, nTiles * 2u * sizeof(uint32_t))) rc = -1;
-        s->hAdvTiles = (uint32_t *)h;
-    }
-    if (rc == 0 && (qfGrowD(dev, &s->dAdvRows, &s->dAdvRowsCap, nRows * sizeof(qzstd_hip_ediff_cost_row_t)) ||
-                    qfGrowD(dev, &s->dAdvTiles, &s->dAdvTilesCap, nTiles * 2u * sizeof(uint32_t))))
+
+    rows = (qzstd_hip_ediff_cost_row_t *)qfBufH(&s->pin.advRows, nRows * sizeof(qzstd_hip_ediff_cost_row_t));
+    tiles = rows ? (const uint32_t *)qfBufH(&s->pin.advTiles, nTiles * 2u * sizeof(uint32_t)) : NULL;
+    if (!tiles || !qfBufD(dev, &s->dev.advRows, nRows * sizeof(qzstd_hip_ediff_cost_row_t)) || !qfBufD(dev, &s->dev.advTiles, nTiles * 2u * sizeof(uint32_t)))
         rc = -1;
-    /* the slot's stream waits for what the caller queued on `stream` so far: whatever last wrote the buffers */
-    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, s->stream, ev))) rc = -1;
     if (rc == 0) {
         for (i = 0, c = 0; i < nBufs; i++) {
             size_t off;
             for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) { /* chunks as the compress calls cut frames */
-                qzstd_hip_ediff_cost_row_t *r = &s->hAdvRows[c];
+                qzstd_hip_ediff_cost_row_t *r = &rows[c];
                 r->src = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
                 r->len = (uint32_t)(bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
                 r->elem = advised[i];
@@ -105,23 +85,19 @@ size_t QZSTD_frontAdviseDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs,
                 total += (unsigned long long)(r->len / r->elem) * r->elem;
             }
         }
-        if (qzstd_hip_ediff_cost(dev, s->stream, s->hAdvRows, (uint32_t)nRows, (qzstd_hip_ediff_cost_row_t *)s->dAdvRows, (uint32_t *)s->dAdvTiles) ||
-            qzstd_hip_memcpy_d2h(dev, s->stream, s->hAdvTiles, s->dAdvTiles, nTiles * 2u * sizeof(uint32_t)))
+        if (qzstd_hip_ediff_cost(dev, s->stream, rows, (uint32_t)nRows, (qzstd_hip_ediff_cost_row_t *)s->dev.advRows.p, (uint32_t *)s->dev.advTiles.p) ||
+            qzstd_hip_memcpy_d2h(dev, s->stream, s->pin.advTiles.p, s->dev.advTiles.p, nTiles * 2u * sizeof(uint32_t)))
             rc = -1;
     }
-    /* nothing the library queued may still read the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
-    if (s && s->stream && qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
-        (void)qzstd_hip_stream_sync(dev, s->stream);
-        rc = -1;
-    }
+    if (qfCallWait(&call)) rc = -1;
     for (i = 0, c = 0; i < nBufs && rc == 0; i++) {
         unsigned long long P = 0, D = 0;
         size_t off;
         for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
-            size_t n = (size_t)QZSTD_HIP_ESUM_TILES(s->hAdvRows[c].len, s->hAdvRows[c].elem);
+            size_t n = (size_t)QZSTD_HIP_ESUM_TILES(rows[c].len, rows[c].elem);
             for (; n; n--, t++) {
-                P += s->hAdvTiles[2u * t];
-                D += s->hAdvTiles[2u * t + 1u];
+                P += tiles[2u * t];
+                D += tiles[2u * t + 1u];
             }
         }
         if (est) { est[2u * i] = P; est[2u * i + 1u] = D; }
@@ -130,22 +106,14 @@ size_t QZSTD_frontAdviseDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs,
             nFlagged++;
         }
     }
-    if (ev) qzstd_hip_event_destroy(dev, ev);
     if (rc == 0) {
         __atomic_fetch_add(&f->adviseStats[0], (unsigned long long)nBufs, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->adviseStats[1], (unsigned long long)nFlagged, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->adviseStats[2], total, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->adviseStats[3], 1ull, __ATOMIC_RELAXED);
     }
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc ? (size_t)-1 : nFlagged;
 }
 
-void QZSTD_frontAdviseStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->adviseStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontAdviseStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->adviseStats : NULL, stats, 4); }

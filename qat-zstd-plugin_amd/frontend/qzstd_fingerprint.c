@@ -5,10 +5,10 @@
  * qzstd_frontend.c's translation unit, included behind qzstd_verify.c; it uses the restore's first slot (its stream, and grow-only pinned
  * and device scratch kept there between calls).
  *
- * A call is: the host-side checks of the batch compress call, the slot's stream waiting for the caller's, ONE qzstd_hip_fingerprint launch
- * with a row per frame that points INTO the caller's buffers (nothing is staged or copied on the device), one device->host copy of the tile
- * digests (8 bytes per 16 KiB), a bounded wait, and QZSTD_fpFold per frame on the calling thread.  Nothing of the producer or the workers is
- * used: a front created with useProducer = 0 serves the calls.
+ * A call is: the host-side checks of the batch compress call; the scaffold of qzstd_frontend.c (qfCallBegin .. qfCallEnd) with ONE stream;
+ * ONE qzstd_hip_fingerprint launch with a row per frame that points INTO the caller's buffers (nothing is staged or copied on the device);
+ * one device->host copy of the tile digests (8 bytes per 16 KiB); and QZSTD_fpFold per frame on the calling thread.  Nothing of the producer
+ * or the workers is used: a front created with useProducer = 0 serves the calls.
  */
 
 extern int qzstd_hip_fingerprint(int device, void *stream, qzstd_hip_fp_row_t *rows, uint32_t nRows, qzstd_hip_fp_row_t *d_rows,
@@ -28,16 +28,21 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
 {
     const int pieces = sm && sm->multi;
     size_t nPieces = 0, m = 0, multi = 0;
+    QF_Call call;
     QF_RestoreSlot *s;
-    void *ev = NULL, *h;
+    qzstd_hip_fp_row_t *rows;
+    qzstd_hip_fp_pieces_row_t *pieceRows = NULL;
+    qzstd_hip_group_piece_t *chk = NULL;
+    const uint64_t *tiles;
     size_t i, c = 0, nFrames = 0, nTiles = 0, total = 0, t = 0, nDiff = 0;
-    int dev = -1, rc = 0;
+    int dev, rc = 0;
     /* host-side checks, the batch compress call's: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
         if (!bufs[i].d_ptr && bufs[i].size) return (size_t)-1;
         nFrames += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
         nTiles += (bufs[i].size / f->p.chunkSize) * (size_t)QZSTD_HIP_FP_TILES(f->p.chunkSize) + (size_t)QZSTD_HIP_FP_TILES(bufs[i].size % f->p.chunkSize);
+        total += bufs[i].size;
     }
     if (check) {
         if (nExpected != nFrames || (nFrames && !expected)) return (size_t)-1;
@@ -49,77 +54,41 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the fingerprint kernel, or without the device-input entry points at all */
     if (pieces && !qzstd_hip_fingerprint_pieces) return (size_t)-1; /* a frame of several pieces and a device layer that cannot read one */
-    if (sm) {
-        dev = sm->dev;
-        total = sm->total;
+    call.f = f;
+    call.restore = 1;
+    call.nStreams = 1; /* the restore side's first slot alone: its stream and scratch */
+    call.dev = sm ? sm->dev : -1; /* (a call with source slices has looked its memory up: qfSrcMapBuild) */
+    if (!sm && qfCallBufs(&call, bufs, NULL, nBufs)) return (size_t)-1;
+    /* a call without a frame takes nothing, not even devBusy, as the compress calls */
+    if (nFrames == 0) {
+        qfFirstFrames(f, bufs, nBufs, firstFrame);
+        return 0;
     }
-    for (i = 0; i < nBufs && !sm; i++) {
-        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
-        int d;
-        if (!bufs[i].size) continue;
-        d = qzstd_hip_pointer_device(p);
-        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
-        dev = d;
-        total += bufs[i].size;
-    }
-    if (nFrames) {
-        pthread_mutex_lock(&f->mu);
-        if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-        f->devBusy = 1;
-        pthread_mutex_unlock(&f->mu);
-    }
-    if (firstFrame) {
-        for (i = 0, c = 0; i < nBufs; i++) {
-            firstFrame[i] = c;
-            c += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
-        }
-        firstFrame[nBufs] = c;
-    }
-    if (nFrames == 0) return 0;
-
-    /* the restore's slots, kept with the front between calls: the first one's stream and scratch */
-    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
-    if (!f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
-    f->restoreSlotDev = dev;
+    if (qfCallBegin(&call, stream)) return (size_t)-1; /* (firstFrame is not written by a call that is refused) */
+    qfFirstFrames(f, bufs, nBufs, firstFrame);
+    dev = call.dev;
     s = f->restoreSlot;
-    if (rc == 0 && !s->stream && !(s->stream = qzstd_hip_stream_create(dev))) rc = -1;
-    if (rc == 0) {
-        h = s->hFpRows;
-        if (qfGrowH(&h, &s->hFpRowsCap, nFrames * sizeof(qzstd_hip_fp_row_t))) rc = -1;
-        s->hFpRows = (qzstd_hip_fp_row_t *)h;
-    }
+
+    rows = (qzstd_hip_fp_row_t *)qfBufH(&s->pin.fpRows, nFrames * sizeof(qzstd_hip_fp_row_t)); /* (kept in either launch: the fold below reads a row's len) */
+    if (!rows) rc = -1;
     if (rc == 0 && pieces) {
         size_t p, off;
         for (i = 0; i < nBufs; i++)
             for (off = 0, p = sm->first[i]; off < bufs[i].size; off += f->p.chunkSize)
                 nPieces += qfSrcFramePieces(sm, &p, off, bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
-        if (nPieces > 0xFFFFFFFFu) rc = -1;
-        h = s->hFpPieceRows;
-        if (rc == 0 && qfGrowH(&h, &s->hFpPieceRowsCap, nFrames * sizeof(qzstd_hip_fp_pieces_row_t))) rc = -1;
-        s->hFpPieceRows = (qzstd_hip_fp_pieces_row_t *)h;
-        h = s->hChkPieces;
-        if (rc == 0 && qfGrowH(&h, &s->hChkPiecesCap, nPieces * sizeof(qzstd_hip_group_piece_t))) rc = -1;
-        s->hChkPieces = (qzstd_hip_group_piece_t *)h;
-        if (rc == 0 && (qfGrowD(dev, &s->dFpPieceRows, &s->dFpPieceRowsCap, nFrames * sizeof(qzstd_hip_fp_pieces_row_t)) ||
-                        qfGrowD(dev, &s->dChkPieces, &s->dChkPiecesCap, nPieces * sizeof(qzstd_hip_group_piece_t))))
+        if (nPieces > 0xFFFFFFFFu || !(pieceRows = (qzstd_hip_fp_pieces_row_t *)qfBufH(&s->pin.fpPieceRows, nFrames * sizeof(qzstd_hip_fp_pieces_row_t))) ||
+            !(chk = (qzstd_hip_group_piece_t *)qfBufH(&s->pin.chkPieces, nPieces * sizeof(qzstd_hip_group_piece_t))) ||
+            !qfBufD(dev, &s->dev.fpPieceRows, nFrames * sizeof(qzstd_hip_fp_pieces_row_t)) ||
+            !qfBufD(dev, &s->dev.chkPieces, nPieces * sizeof(qzstd_hip_group_piece_t)))
             rc = -1;
     }
-    if (rc == 0) {
-        h = s->hFpTiles;
-        if (qfGrowH(&h, &s->hFpTilesCap, nTiles * sizeof(uint64_t))) rc = -1;
-        s->hFpTiles = (uint64_t *)h;
-    }
-    if (rc == 0 && (qfGrowD(dev, &s->dFpRows, &s->dFpRowsCap, nFrames * sizeof(qzstd_hip_fp_row_t)) ||
-                    qfGrowD(dev, &s->dFpTiles, &s->dFpTilesCap, nTiles * sizeof(uint64_t))))
-        rc = -1;
-    /* the slot's stream waits for what the caller queued on `stream` so far: whatever last wrote the buffers */
-    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, s->stream, ev))) rc = -1;
+    tiles = rc == 0 ? (const uint64_t *)qfBufH(&s->pin.fpTiles, nTiles * sizeof(uint64_t)) : NULL;
+    if (!tiles || !qfBufD(dev, &s->dev.fpRows, nFrames * sizeof(qzstd_hip_fp_row_t)) || !qfBufD(dev, &s->dev.fpTiles, nTiles * sizeof(uint64_t))) rc = -1;
     if (rc == 0) {
         for (i = 0, c = 0; i < nBufs; i++) {
             size_t off, p = sm ? sm->first[i] : 0;
             for (off = 0; off < bufs[i].size; off += f->p.chunkSize, c++) {
-                qzstd_hip_fp_row_t *r = &s->hFpRows[c]; /* (its len is the frame's in either launch: the fold below reads it) */
+                qzstd_hip_fp_row_t *r = &rows[c];
                 r->src = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
                 r->len = (uint32_t)(bufs[i].size - off < f->p.chunkSize ? bufs[i].size - off : f->p.chunkSize);
                 r->tile0 = 0;
@@ -127,32 +96,28 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
                     const size_t np = qfSrcFramePieces(sm, &p, off, r->len);
                     r->src = np == 1u ? (uint64_t)(uintptr_t)(sm->pieces[p].src + (off - sm->pieces[p].off)) : 0u;
                     if (pieces) {
-                        qzstd_hip_fp_pieces_row_t *q = &s->hFpPieceRows[c];
+                        qzstd_hip_fp_pieces_row_t *q = &pieceRows[c];
                         q->len = r->len;
                         q->tile0 = 0;
                         q->piece0 = (uint32_t)m;
                         q->nPieces = (uint32_t)np;
-                        qfSrcFrameTable(sm, p, np, off, r->len, 0, &s->hChkPieces[m]);
+                        qfSrcFrameTable(sm, p, np, off, r->len, 0, &chk[m]);
                         m += np;
                         if (np > 1u) multi++;
                     }
                 }
             }
         }
-        if ((pieces ? qzstd_hip_fingerprint_pieces(dev, s->stream, s->hFpPieceRows, (uint32_t)nFrames, (qzstd_hip_fp_pieces_row_t *)s->dFpPieceRows,
-                                                   s->hChkPieces, (uint32_t)nPieces, (qzstd_hip_group_piece_t *)s->dChkPieces, (uint64_t *)s->dFpTiles)
-                    : qzstd_hip_fingerprint(dev, s->stream, s->hFpRows, (uint32_t)nFrames, (qzstd_hip_fp_row_t *)s->dFpRows, (uint64_t *)s->dFpTiles)) ||
-            qzstd_hip_memcpy_d2h(dev, s->stream, s->hFpTiles, s->dFpTiles, nTiles * sizeof(uint64_t)))
+        if ((pieces ? qzstd_hip_fingerprint_pieces(dev, s->stream, pieceRows, (uint32_t)nFrames, (qzstd_hip_fp_pieces_row_t *)s->dev.fpPieceRows.p, chk,
+                                                   (uint32_t)nPieces, (qzstd_hip_group_piece_t *)s->dev.chkPieces.p, (uint64_t *)s->dev.fpTiles.p)
+                    : qzstd_hip_fingerprint(dev, s->stream, rows, (uint32_t)nFrames, (qzstd_hip_fp_row_t *)s->dev.fpRows.p, (uint64_t *)s->dev.fpTiles.p)) ||
+            qzstd_hip_memcpy_d2h(dev, s->stream, s->pin.fpTiles.p, s->dev.fpTiles.p, nTiles * sizeof(uint64_t)))
             rc = -1;
     }
-    /* nothing the library queued may still read the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
-    if (s && s->stream && qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
-        (void)qzstd_hip_stream_sync(dev, s->stream);
-        rc = -1;
-    }
+    if (qfCallWait(&call)) rc = -1;
     for (c = 0; c < nFrames && rc == 0; c++) {
-        const size_t n = (size_t)QZSTD_HIP_FP_TILES(s->hFpRows[c].len);
-        const unsigned long long v = QZSTD_fpFold(s->hFpTiles + t, n, s->hFpRows[c].len);
+        const size_t n = (size_t)QZSTD_HIP_FP_TILES(rows[c].len);
+        const unsigned long long v = QZSTD_fpFold(tiles + t, n, rows[c].len);
         t += n;
         if (fp) fp[c] = v;
         if (check) {
@@ -161,7 +126,6 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
             nDiff += (size_t)d;
         }
     }
-    if (ev) qzstd_hip_event_destroy(dev, ev);
     if (rc == 0) {
         __atomic_fetch_add(&f->fpStats[0], (unsigned long long)nFrames, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->fpStats[1], (unsigned long long)total, __ATOMIC_RELAXED);
@@ -172,9 +136,7 @@ static size_t qfFingerprintDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, s
             sm->counts[1] += 1ull;
         }
     }
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc ? (size_t)-1 : (check ? nDiff : nFrames);
 }
 
@@ -190,9 +152,4 @@ size_t QZSTD_frontCheckDeviceBatch(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, 
     return qfFingerprintDevice(f, bufs, nBufs, NULL, stream, NULL, NULL, expected, 1, nFrames, differs);
 }
 
-void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->fpStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontFingerprintStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->fpStats : NULL, stats, 4); }

@@ -422,6 +422,9 @@ void QZSTD_freeFront(QZSTD_Front *f)
  * arena's headers and then the arena itself D2H into pinned memory.  The workers entropy-code part k straight from its arena
  * (ZSTD_compressSequencesAndLiterals) while the GPU works on parts k + 1 and k + 2.  The calling thread does the GPU side.
  *
+ * What the call does before and behind that — the look-ups, devBusy, the slots, the event pair, the closing waits — is the scaffold's
+ * (qfCallBegin .. qfCallEnd below), which every device call of the front-end shares; the slots' memory is QF_Buf's.
+ *
  * The new entry points of the device layer are weak references: a device layer without them (an older library, the CPU suite's mock)
  * makes QZSTD_frontCompressDevice fail and leaves the rest of the front-end as it was.
  *
@@ -516,46 +519,103 @@ static void qfResolveSeqApi(void)
     dlclose(h); /* (RTLD_NOLOAD: the library stays, it was loaded before) */
 }
 
-/* one device slot: a part's buffers, device and pinned */
+/* Grow-only memory of one kind — device memory of the slot's device (qfBufD) or pinned host memory (qfBufH) — kept from call to call.
+ * Growing frees and allocates anew: the contents are NOT kept (the one buffer whose contents must move along, the pinned arena, says so
+ * where it grows: qfFetchPart).  A need of 0 bytes allocates 16; after a failure the buffer is empty (NULL, capacity 0).  -> the memory,
+ * or NULL */
+typedef struct { void *p; size_t cap; } QF_Buf;
+#define QF_NBUFS(group) (sizeof(group) / sizeof(QF_Buf))
+
+static void *qfBufD(int dev, QF_Buf *b, size_t need)
+{
+    if (b->cap >= need && b->p) return b->p;
+    if (b->p) qzstd_hip_free(dev, b->p);
+    b->p = qzstd_hip_malloc(dev, need ? need : 16);
+    b->cap = b->p ? need : 0;
+    return b->p;
+}
+
+static void *qfBufH(QF_Buf *b, size_t need)
+{
+    if (b->cap >= need && b->p) return b->p;
+    if (b->p) qzstd_hip_host_free(b->p);
+    b->p = qzstd_hip_host_alloc(need ? need : 16);
+    b->cap = b->p ? need : 0;
+    return b->p;
+}
+
+/* a slot's `dev` or `pin` group: n buffers that follow each other */
+static void qfBufsFree(int dev, int pinned, void *group, size_t n)
+{
+    QF_Buf *b = (QF_Buf *)group;
+    for (; n; n--, b++) {
+        if (b->p && pinned) qzstd_hip_host_free(b->p);
+        else if (b->p) qzstd_hip_free(dev, b->p);
+        b->p = NULL;
+        b->cap = 0;
+    }
+}
+
+/* One device slot of the compress calls: a part's buffers.  `dev` (device memory) and `pin` (pinned host memory) hold QF_Buf members and
+ * NOTHING ELSE, so that qfDevSlotsFree walks them as arrays: a new buffer is one more member, and it cannot be forgotten there. */
 struct QF_DevSlot_s {
     void *stream;
-    unsigned char *dStage; size_t stageCap;   /* the part copied to 16-aligned frames, when the caller's buffers cannot be read in place */
-    qzstd_hip_gather_row_t *hRows; size_t hRowsCap; /* the gather's rows, one per frame (pinned), and their device copy */
-    void *dRows; size_t dRowsCap;
-    qzstd_hip_group_row_t *hGroupRows; size_t hGroupRowsCap; /* a part with byte-grouped frames: qzstd_hip_group's rows instead */
-    void *dGroupRows; size_t dGroupRowsCap;
-    qzstd_hip_group_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with delta frames: qzstd_hip_group_xor's rows instead */
-    void *dXorRows; size_t dXorRowsCap;
-    qzstd_hip_group_ediff_row_t *hEdiffRows; size_t hEdiffRowsCap; /* a part with differenced frames: qzstd_hip_group_ediff's rows, for those frames only */
-    void *dEdiffRows; size_t dEdiffRowsCap;
-    qzstd_hip_group_pieces_row_t *hPieceRows; size_t hPieceRowsCap; /* a part with a frame of several pieces: qzstd_hip_group_pieces's rows instead, */
-    void *dPieceRows; size_t dPieceRowsCap;
-    qzstd_hip_group_piece_t *hPieces; size_t hPiecesCap;            /* and their piece table */
-    void *dPieces; size_t dPiecesCap;
+    struct {
+        QF_Buf stage;      /* the part copied to 16-aligned frames, when the caller's buffers cannot be read in place */
+        QF_Buf rows, groupRows, xorRows, ediffRows, pieceRows, pieces; /* the device copies of the staging launches' rows (pin, below) */
+        QF_Buf hashRows, hash;          /* checksums: the rows' device copy, the hashes */
+        QF_Buf diffRows, diffFlags;     /* delta skip */
+        QF_Buf planeRows, planeCost;    /* plane probe */
+        QF_Buf hufWords, hufDense, hufScratch; /* plane code: per block a size word and a dense offset (nb + (nb + 1) words), the dense area of
+                                                * code lengths, jump tables and streams, the coder's scratch */
+        QF_Buf desc, seqs, count, work, cwork, arena;
+    } dev;
+    struct {
+        QF_Buf desc;       /* qzstd_hip_block_t per block */
+        QF_Buf rows;       /* qzstd_hip_gather_row_t: the gather's rows, one per frame */
+        QF_Buf groupRows;  /* qzstd_hip_group_row_t: a part with byte-grouped frames */
+        QF_Buf xorRows;    /* qzstd_hip_group_xor_row_t: a part with delta frames */
+        QF_Buf ediffRows;  /* qzstd_hip_group_ediff_row_t: a part's differenced frames only */
+        QF_Buf pieceRows, pieces; /* qzstd_hip_group_pieces_row_t and their piece table: a part with a frame of several pieces */
+        QF_Buf hashRows, hash;    /* qzstd_hip_hash_row_t per frame, uint64_t per frame */
+        QF_Buf diffRows, diffFlags; /* qzstd_hip_diff_row_t per compared piece, uint32_t per row */
+        QF_Buf planeRows, planeCost; /* qzstd_hip_plane_row_t per block, uint32_t per block */
+        QF_Buf hufWords, hufDense;   /* uint32_t, bytes */
+        QF_Buf arena;      /* the compaction's headers, packed entries and literals */
+    } pin;
     size_t *ends; size_t endsCap; /* the block ends of the frame whose descriptors are being written */
-    qzstd_hip_hash_row_t *hHashRows; size_t hHashRowsCap; /* checksums: one row per frame (pinned), the device copy, the hashes on both sides */
-    void *dHashRows, *dHash; size_t dHashRowsCap, dHashCap;
-    uint64_t *hHash; size_t hHashCap;
-    qzstd_hip_diff_row_t *hDiffRows; size_t hDiffRowsCap; /* delta skip: a row per compared frame (pinned), the device copy, the flags on both sides */
-    void *dDiffRows, *dDiffFlags; size_t dDiffRowsCap, dDiffFlagsCap;
-    uint32_t *hDiffFlags; size_t hDiffFlagsCap;
-    int hashed; /* the part queued on this slot has its frames' hashes in dHash; the part fetched from it has them in hHash */
-    qzstd_hip_plane_row_t *hPlaneRows; size_t hPlaneRowsCap; /* plane probe: a row per block (pinned), the device copy, the costs on both sides */
-    void *dPlaneRows, *dPlaneCost; size_t dPlaneRowsCap, dPlaneCostCap;
-    uint32_t *hPlaneCost; size_t hPlaneCostCap;
-    int probed; /* as `hashed`: the queued part's costs are in dPlaneCost; the fetched part's in hPlaneCost */
-    /* plane code: per block a size word and a dense offset (nb + (nb + 1) words, one device area and one pinned), the dense area of code
-     * lengths, jump tables and streams on both sides, the coder's scratch */
-    void *dHufWords, *dHufDense, *dHufScratch; size_t dHufWordsCap, dHufDenseCap, dHufScratchCap;
-    uint32_t *hHufWords; size_t hHufWordsCap;
-    unsigned char *hHufDense; size_t hHufDenseCap;
-    int coded; /* as `probed`: the queued part went through qzstd_hip_huf_code; the fetched part's words and dense area are in hHufWords / hHufDense */
-    qzstd_hip_block_t *hDesc; size_t hDescCap;
-    void *dDesc, *dSeqs, *dCount, *dWork, *dCWork, *dArena;
-    size_t dDescCap, dSeqsCap, dCountCap, dWorkCap, dCWorkCap, dArenaCap;
-    unsigned char *hArena; size_t hArenaCap;
+    int hashed; /* the part queued on this slot has its frames' hashes in dev.hash; the part fetched from it has them in pin.hash */
+    int probed; /* as `hashed`: the queued part's costs are in dev.planeCost; the fetched part's in pin.planeCost */
+    int coded;  /* as `probed`: the queued part went through qzstd_hip_huf_code; the fetched part's words and dense area are in pin.hufWords / pin.hufDense */
     size_t *blkSeq, *blkLit; size_t blkCap;   /* per block: first entry, first literal byte (host prefix sums of the headers) */
-    const unsigned char *hLit; size_t litTotal; /* the arena's literal bytes, in hArena */
+    const unsigned char *hLit; size_t litTotal; /* the arena's literal bytes, in pin.arena */
+};
+#define QF_HDR(s) ((const qzstd_hip_compact_hdr_t *)(s)->pin.arena.p)
+
+/* One slot of the restore side (qzstd_restore.c and the calls that use its slots: verify, fingerprint, advise); `dev` and `pin` as above,
+ * walked by qfRestoreSlotsFree. */
+struct QF_RestoreSlot_s {
+    void *stream;
+    struct {
+        QF_Buf stage;                 /* the device copy of the part's decoded frames */
+        QF_Buf rows, xorRows, sumRows, sumScratch, winRows; /* the restore calls' rows, and qzstd_hip_esum's scratch */
+        QF_Buf cmpRows, tiles;        /* verify: rows, tile words */
+        QF_Buf fpRows, fpTiles;       /* fingerprint (slot 0 only): rows, tile digests */
+        QF_Buf advRows, advTiles;     /* adviser (slot 0 only): rows, two cost words per tile */
+        QF_Buf fpPieceRows, cmpPieceRows, chkPieces; /* the calls with source slices: the rows of the kernels from pieces, their piece table */
+    } dev;
+    struct {
+        QF_Buf stage;                 /* the part's decoded frames, every frame at a 16-aligned offset */
+        QF_Buf rows;                  /* qzstd_hip_ungroup_row_t per frame */
+        QF_Buf xorRows;               /* qzstd_hip_ungroup_xor_row_t: a part with a base among its frames */
+        QF_Buf sumRows;               /* qzstd_hip_esum_row_t: a part's differenced frames only */
+        QF_Buf winRows;               /* qzstd_hip_ungroup_win_row_t per piece (slice x frame) */
+        QF_Buf cmpRows, tiles;        /* qzstd_hip_ungroup_cmp_row_t per frame, uint32_t per tile */
+        QF_Buf fpRows, fpTiles;       /* qzstd_hip_fp_row_t per frame, uint64_t per tile */
+        QF_Buf advRows, advTiles;     /* qzstd_hip_ediff_cost_row_t per chunk, 2 x uint32_t per tile */
+        QF_Buf fpPieceRows, cmpPieceRows, chkPieces; /* qzstd_hip_fp_pieces_row_t, qzstd_hip_ungroup_cmp_pieces_row_t, qzstd_hip_group_piece_t */
+    } pin;
+    size_t pending; /* verify: the part (+ 1) whose tile words are on their way; 0: none */
 };
 
 /* the source slices of a QZSTD_frontCompressDeviceSlices call (qzstd_srcslices.c): the non-empty ones, buffer after buffer, ascending and
@@ -605,67 +665,166 @@ struct QF_DevPart_s {
     size_t nb;                   /* blocks */
     const QF_DevSlot *slot;
     int dev;
-    int hashed; /* checksums on: frame c's content hash is slot->hHash[c - f0] */
-    int probed; /* plane probe: block b's order-0 cost is slot->hPlaneCost[b] */
-    int coded;  /* plane code: block b's size word is slot->hHufWords[b], its bytes lie at slot->hHufDense + slot->hHufWords[nb + b] */
+    int hashed; /* checksums on: frame c's content hash is word c - f0 of slot->pin.hash */
+    int probed; /* plane probe: block b's order-0 cost is word b of slot->pin.planeCost */
+    int coded;  /* plane code: block b's size word is word b of slot->pin.hufWords, its bytes lie in slot->pin.hufDense at word nb + b */
     int failSub; /* test switch ($QZSTD_FRONT_PROBE_FAIL_SUB): the assembled frames' libzstd call counts as failed */
 };
 
-static void qfSlotFree(int dev, QF_DevSlot *s)
+/* n counters of the front as a caller reads them (all 0 for no front) */
+static void qfStats(const unsigned long long *from, unsigned long long *stats, int n)
 {
-    void *d[] = { s->dStage, s->dRows, s->dGroupRows, s->dXorRows, s->dDesc, s->dSeqs, s->dCount, s->dWork, s->dCWork, s->dArena, s->dHashRows, s->dHash,
-                  s->dDiffRows, s->dDiffFlags, s->dPlaneRows, s->dPlaneCost, s->dEdiffRows, s->dPieceRows, s->dPieces, s->dHufWords, s->dHufDense,
-                  s->dHufScratch };
-    size_t i;
-    for (i = 0; i < sizeof(d) / sizeof(d[0]); i++) if (d[i]) qzstd_hip_free(dev, d[i]);
-    if (s->hDesc) qzstd_hip_host_free(s->hDesc);
-    if (s->hRows) qzstd_hip_host_free(s->hRows);
-    if (s->hGroupRows) qzstd_hip_host_free(s->hGroupRows);
-    if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
-    if (s->hEdiffRows) qzstd_hip_host_free(s->hEdiffRows);
-    if (s->hPieceRows) qzstd_hip_host_free(s->hPieceRows);
-    if (s->hPieces) qzstd_hip_host_free(s->hPieces);
-    free(s->ends);
-    if (s->hHashRows) qzstd_hip_host_free(s->hHashRows);
-    if (s->hHash) qzstd_hip_host_free(s->hHash);
-    if (s->hDiffRows) qzstd_hip_host_free(s->hDiffRows);
-    if (s->hDiffFlags) qzstd_hip_host_free(s->hDiffFlags);
-    if (s->hPlaneRows) qzstd_hip_host_free(s->hPlaneRows);
-    if (s->hPlaneCost) qzstd_hip_host_free(s->hPlaneCost);
-    if (s->hHufWords) qzstd_hip_host_free(s->hHufWords);
-    if (s->hHufDense) qzstd_hip_host_free(s->hHufDense);
-    if (s->hArena) qzstd_hip_host_free(s->hArena);
-    if (s->stream) qzstd_hip_stream_destroy(dev, s->stream);
-    free(s->blkSeq);
-    free(s->blkLit);
-    memset(s, 0, sizeof(*s));
+    int k;
+    if (!stats) return;
+    for (k = 0; k < n; k++) stats[k] = from ? __atomic_load_n(&from[k], __ATOMIC_RELAXED) : 0ull;
 }
 
 static void qfDevSlotsFree(QZSTD_Front *f)
 {
-    if (!f->devSlot) return;
-    qfSlotFree(f->devSlotDev, &f->devSlot[0]);
-    qfSlotFree(f->devSlotDev, &f->devSlot[1]);
+    int k;
+    for (k = 0; f->devSlot && k < 2; k++) {
+        QF_DevSlot *s = &f->devSlot[k];
+        qfBufsFree(f->devSlotDev, 0, &s->dev, QF_NBUFS(s->dev));
+        qfBufsFree(f->devSlotDev, 1, &s->pin, QF_NBUFS(s->pin));
+        if (s->stream) qzstd_hip_stream_destroy(f->devSlotDev, s->stream);
+        free(s->ends);
+        free(s->blkSeq);
+        free(s->blkLit);
+    }
     free(f->devSlot);
     f->devSlot = NULL;
 }
 
-static int qfGrowD(int dev, void **p, size_t *cap, size_t need)
+static void qfRestoreSlotsFree(QZSTD_Front *f)
 {
-    if (*cap >= need && *p) return 0;
-    if (*p) qzstd_hip_free(dev, *p);
-    *p = qzstd_hip_malloc(dev, need ? need : 16);
-    *cap = *p ? need : 0;
-    return *p ? 0 : -1;
+    int k;
+    for (k = 0; f->restoreSlot && k < 2; k++) {
+        QF_RestoreSlot *s = &f->restoreSlot[k];
+        qfBufsFree(f->restoreSlotDev, 0, &s->dev, QF_NBUFS(s->dev));
+        qfBufsFree(f->restoreSlotDev, 1, &s->pin, QF_NBUFS(s->pin));
+        if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
+    }
+    free(f->restoreSlot);
+    f->restoreSlot = NULL;
 }
 
-static int qfGrowH(void **p, size_t *cap, size_t need)
+/* ---- the scaffold of a device call.  Every call is: its own host-side checks (nothing has touched a GPU when one of them fails); the
+ * look-up of its buffers (qfCallRange / qfCallBufs: all of them memory of ONE device, or the device a QF_SrcMap already knows in `dev`);
+ * qfCallBegin; its planning and launches on the streams of the family's slots; qfCallWait; what it reads of the slots' pinned memory and
+ * counts; qfCallEnd.  A call that has nothing to do returns before qfCallBegin and takes nothing. */
+typedef struct {
+    QZSTD_Front *f;
+    int restore;  /* the slot family: the restore side's (f->restoreSlot: restore, verify, fingerprint, advise) or the compress side's (f->devSlot) */
+    int nStreams; /* 2, or 1: the call uses slot 0 alone, and only its stream is created, made to wait and waited for */
+    int dev;      /* -1 until a look-up (or the caller, from a QF_SrcMap) has set it */
+    void *ev;
+} QF_Call;
+
+static void **qfCallStream(const QF_Call *c, int k)
 {
-    if (*cap >= need && *p) return 0;
-    if (*p) qzstd_hip_host_free(*p);
-    *p = qzstd_hip_host_alloc(need ? need : 16);
-    *cap = *p ? need : 0;
-    return *p ? 0 : -1;
+    if (c->restore) return c->f->restoreSlot ? &c->f->restoreSlot[k].stream : NULL;
+    return c->f->devSlot ? &c->f->devSlot[k].stream : NULL;
+}
+
+/* [p, p + n) is memory of one device, the call's (the first range looked up sets it); an empty range is not looked up */
+static int qfCallRange(QF_Call *c, const void *p, size_t n)
+{
+    int d;
+    if (!n) return 0;
+    d = qzstd_hip_pointer_device(p);
+    if (d < 0 || qzstd_hip_pointer_device((const unsigned char *)p + n - 1) != d || (c->dev >= 0 && d != c->dev)) return -1;
+    c->dev = d;
+    return 0;
+}
+
+/* every buffer, and behind each its base when the call has bases and the buffer one */
+static int qfCallBufs(QF_Call *c, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, size_t nBufs)
+{
+    size_t i;
+    for (i = 0; i < nBufs; i++)
+        if (qfCallRange(c, bufs[i].d_ptr, bufs[i].size) || (bases && bases[i].d_ptr && qfCallRange(c, bases[i].d_ptr, bases[i].size))) return -1;
+    return 0;
+}
+
+/* nothing the library queued may still read or write the caller's buffers when a call returns: a bounded wait on every stream of the call,
+ * then an unbounded one.  Also what stands between the launches and the reading of the slots' pinned memory.  -> 0, or -1 after a time-out */
+static int qfCallWait(const QF_Call *c)
+{
+    int k, rc = 0;
+    for (k = 0; k < c->nStreams; k++) {
+        void **s = qfCallStream(c, k);
+        if (!s || !*s) continue;
+        if (qzstd_hip_stream_wait(c->dev, *s, QF_DEV_WAIT_MS) != 0) {
+            (void)qzstd_hip_stream_sync(c->dev, *s);
+            rc = -1;
+        }
+    }
+    return rc;
+}
+
+static void qfCallEnd(QF_Call *c)
+{
+    if (c->ev) qzstd_hip_event_destroy(c->dev, c->ev);
+    c->ev = NULL;
+    pthread_mutex_lock(&c->f->mu);
+    c->f->devBusy = 0;
+    pthread_mutex_unlock(&c->f->mu);
+}
+
+/* Takes devBusy (refused while another device call or a job is in progress); frees the family's slots when they were another device's and
+ * makes two — they stay with the front between calls: allocating and freeing pinned and device memory costs more than a part takes —;
+ * creates the streams the call uses; and makes them wait for what the caller queued on `stream` so far: the work that produced (or last
+ * used) the buffers.  -> 0; -1: refused or failed, and nothing is held */
+static int qfCallBegin(QF_Call *c, void *stream)
+{
+    QZSTD_Front *f = c->f;
+    int k, rc = 0;
+    c->ev = NULL;
+    pthread_mutex_lock(&f->mu);
+    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return -1; }
+    f->devBusy = 1;
+    pthread_mutex_unlock(&f->mu);
+    if (c->restore) {
+        if (f->restoreSlot && f->restoreSlotDev != c->dev) qfRestoreSlotsFree(f);
+        if (!f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
+        f->restoreSlotDev = c->dev;
+    } else {
+        if (f->devSlot && f->devSlotDev != c->dev) qfDevSlotsFree(f);
+        if (!f->devSlot && !(f->devSlot = (QF_DevSlot *)calloc(2, sizeof(QF_DevSlot)))) rc = -1;
+        f->devSlotDev = c->dev;
+    }
+    for (k = 0; k < c->nStreams && rc == 0; k++) {
+        void **s = qfCallStream(c, k);
+        if (!*s && !(*s = qzstd_hip_stream_create(c->dev))) rc = -1;
+    }
+    if (rc == 0 && !(c->ev = qzstd_hip_event_create(c->dev))) rc = -1;
+    if (rc == 0 && qzstd_hip_event_record(c->dev, c->ev, stream)) rc = -1;
+    for (k = 0; k < c->nStreams && rc == 0; k++)
+        if (qzstd_hip_stream_wait_event(c->dev, *qfCallStream(c, k), c->ev)) rc = -1;
+    if (rc) {
+        (void)qfCallWait(c);
+        qfCallEnd(c);
+    }
+    return rc;
+}
+
+/* firstFrame[i]: the first frame of buffer i in a call's numbering; firstFrame[nBufs]: the frames of the call */
+static void qfFirstFrames(const QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, size_t nBufs, size_t *firstFrame)
+{
+    size_t i, c = 0;
+    if (!firstFrame) return;
+    for (i = 0; i < nBufs; i++) {
+        firstFrame[i] = c;
+        c += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
+    }
+    firstFrame[nBufs] = c;
+}
+
+/* $QZSTD_FRONT_DEVICE_PART: bytes of input (of decoded content) per part — whole frames, at least one —, default 64 MiB */
+static size_t qfPartBytes(void)
+{
+    const char *pb = getenv("QZSTD_FRONT_DEVICE_PART");
+    return pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
 }
 
 typedef struct {
@@ -685,109 +844,122 @@ static size_t qfPad16(size_t n) { return (n + 15u) & ~(size_t)15u; }
 static int qfStagePieces(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, size_t stageBytes); /* qzstd_srcslices.c */
 static int qfFramePiecesD2H(const QF_DevPart *pt, void *stream, const QF_DevFrame *fm, unsigned char *to, int base);
 
-/* stages a part's frames at 16-aligned offsets of the slot's stage, zero bytes behind each (the matcher reads 16-aligned blocks and up to
- * the next multiple of 16 past each).  One gather launch when the device layer has it; else — a run of one buffer's chunks only — a memset
- * and up to two 2D copies (the last chunk alone when it is short) */
+/* The rows of a staging launch: one per frame of the part that is differenced (diffed 1) or not (0), in the frames' order.  Frame c of
+ * the part lies in the stage at the sum of the padded lengths before it, whichever launch stages it; a row's length and padding are
+ * 32-bit; a frame is padded to the next multiple of 16 and the part's last one by 16 bytes more (the matcher reads 16-aligned blocks and
+ * up to the next multiple of 16 past each).  `put` writes row m of its own type.  Grows the row buffers for nf rows of rowSize bytes.
+ * -> the rows written, or (size_t)-1 */
+typedef void (*QF_RowPut)(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx);
+
+static size_t qfStageRows(const QF_DevJob *j, const QF_DevRange *pr, int diffed, QF_Buf *pin, QF_Buf *dev, size_t rowSize, QF_RowPut put, void *ctx)
+{
+    const QF_DevFrame *f0 = &j->frames[pr->f0];
+    const size_t nf = pr->f1 - pr->f0;
+    size_t c, so = 0, m = 0;
+    void *rows;
+    if (nf > 0xFFFFFFFFu || !(rows = qfBufH(pin, nf * rowSize)) || !qfBufD(j->dev, dev, nf * rowSize)) return (size_t)-1;
+    for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
+        if ((f0[c].diff != 0u) != (diffed != 0)) continue; /* (staged by the part's other launch) */
+        if (f0[c].len > 0xFFFFFFE0u) return (size_t)-1;
+        put(rows, m++, &f0[c], so, (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u), ctx);
+    }
+    return m;
+}
+
+static void qfPutGather(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx)
+{
+    qzstd_hip_gather_row_t *r = (qzstd_hip_gather_row_t *)rows + m;
+    (void)ctx;
+    r->src = (uint64_t)(uintptr_t)fm->src;
+    r->dstOff = dstOff;
+    r->len = (uint32_t)fm->len;
+    r->pad = pad;
+}
+
+/* the gather's rows with each frame's element size: the frames arrive in the byte-grouped layout */
+static void qfPutGroup(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx)
+{
+    qzstd_hip_group_row_t *r = (qzstd_hip_group_row_t *)rows + m;
+    (void)ctx;
+    r->src = (uint64_t)(uintptr_t)fm->src;
+    r->dstOff = dstOff;
+    r->len = (uint32_t)fm->len;
+    r->pad = pad;
+    r->elem = fm->k;
+    r->reserved = 0;
+}
+
+/* the grouping gather's rows with each frame's base chunk (0: the frame's buffer has none): src ^ base arrives, grouped */
+static void qfPutXor(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx)
+{
+    qzstd_hip_group_xor_row_t *r = (qzstd_hip_group_xor_row_t *)rows + m;
+    (void)ctx;
+    r->src = (uint64_t)(uintptr_t)fm->src;
+    r->base = (uint64_t)(uintptr_t)fm->base;
+    r->dstOff = dstOff;
+    r->len = (uint32_t)fm->len;
+    r->pad = pad;
+    r->elem = fm->k;
+    r->reserved = 0;
+}
+
+static void qfPutEdiff(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx)
+{
+    qzstd_hip_group_ediff_row_t *r = (qzstd_hip_group_ediff_row_t *)rows + m;
+    (void)ctx;
+    r->src = (uint64_t)(uintptr_t)fm->src;
+    r->dstOff = dstOff;
+    r->len = (uint32_t)fm->len;
+    r->pad = pad;
+    r->elem = fm->k;
+    r->flags = QZSTD_HIP_EDIFF_DIFF;
+}
+
+/* stages a part's frames in the slot's stage (qfStageRows says where).  The differenced frames by a launch of their own, at the frames' own
+ * places; the others by ONE launch of the part's kind; without the gather — a run of one buffer's chunks only — a memset and up to two 2D
+ * copies (the last chunk alone when it is short) */
 static int qfStagePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, size_t stageBytes)
 {
     const QF_DevFrame *f0 = &j->frames[pr->f0];
     const size_t nf = pr->f1 - pr->f0;
-    void *stage = s->dStage;
-    if (qfGrowD(j->dev, &stage, &s->stageCap, stageBytes)) return -1;
-    s->dStage = (unsigned char *)stage;
+    const int dev = j->dev;
+    size_t m;
+    if (!qfBufD(dev, &s->dev.stage, stageBytes)) return -1;
     if (pr->diff) {
-        /* the differenced frames' rows, in the frames' order, at the frames' own places in the stage; the launch below takes the others */
-        void *h = s->hEdiffRows;
-        size_t c, so = 0, m = 0;
-        if (!qzstd_hip_group_ediff || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hEdiffRowsCap, nf * sizeof(qzstd_hip_group_ediff_row_t))) return -1;
-        s->hEdiffRows = (qzstd_hip_group_ediff_row_t *)h;
-        if (qfGrowD(j->dev, &s->dEdiffRows, &s->dEdiffRowsCap, nf * sizeof(qzstd_hip_group_ediff_row_t))) return -1;
-        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
-            qzstd_hip_group_ediff_row_t *r = &s->hEdiffRows[m];
-            if (!f0[c].diff) continue;
-            if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)f0[c].src;
-            r->dstOff = so;
-            r->len = (uint32_t)f0[c].len;
-            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-            r->elem = f0[c].k;
-            r->flags = QZSTD_HIP_EDIFF_DIFF;
-            m++;
-        }
-        if (qzstd_hip_group_ediff(j->dev, s->stream, s->hEdiffRows, (uint32_t)m, (qzstd_hip_group_ediff_row_t *)s->dEdiffRows, s->dStage, stageBytes))
+        if (!qzstd_hip_group_ediff) return -1;
+        m = qfStageRows(j, pr, 1, &s->pin.ediffRows, &s->dev.ediffRows, sizeof(qzstd_hip_group_ediff_row_t), qfPutEdiff, NULL);
+        if (m == (size_t)-1 || qzstd_hip_group_ediff(dev, s->stream, (const qzstd_hip_group_ediff_row_t *)s->pin.ediffRows.p, (uint32_t)m,
+                                                     (qzstd_hip_group_ediff_row_t *)s->dev.ediffRows.p, s->dev.stage.p, stageBytes))
             return -1;
         __atomic_fetch_add(&j->f->ediffStats[0], (unsigned long long)m, __ATOMIC_RELAXED);
         if (m == nf) return 0;
     }
     if (pr->pieces) return qfStagePieces(j, s, pr, stageBytes);
     if (pr->delta) {
-        /* the grouping gather's rows with each frame's base chunk (0: the frame's buffer has none): src ^ base arrives, grouped */
-        void *h = s->hXorRows;
-        size_t c, so = 0, m = 0;
-        if (!qzstd_hip_group_xor || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
-        s->hXorRows = (qzstd_hip_group_xor_row_t *)h;
-        if (qfGrowD(j->dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_group_xor_row_t))) return -1;
-        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
-            qzstd_hip_group_xor_row_t *r = &s->hXorRows[m];
-            if (f0[c].diff) continue; /* (staged above) */
-            if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)f0[c].src;
-            r->base = (uint64_t)(uintptr_t)f0[c].base;
-            r->dstOff = so;
-            r->len = (uint32_t)f0[c].len;
-            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-            r->elem = f0[c].k;
-            r->reserved = 0;
-            m++;
-        }
-        return qzstd_hip_group_xor(j->dev, s->stream, s->hXorRows, (uint32_t)m, (qzstd_hip_group_xor_row_t *)s->dXorRows, s->dStage, stageBytes);
+        if (!qzstd_hip_group_xor) return -1;
+        m = qfStageRows(j, pr, 0, &s->pin.xorRows, &s->dev.xorRows, sizeof(qzstd_hip_group_xor_row_t), qfPutXor, NULL);
+        return m == (size_t)-1 ? -1 : qzstd_hip_group_xor(dev, s->stream, (const qzstd_hip_group_xor_row_t *)s->pin.xorRows.p, (uint32_t)m,
+                                                          (qzstd_hip_group_xor_row_t *)s->dev.xorRows.p, s->dev.stage.p, stageBytes);
     }
     if (pr->grouped) {
-        /* the gather's rows with each frame's element size: the frames arrive in the byte-grouped layout */
-        void *h = s->hGroupRows;
-        size_t c, so = 0, m = 0;
-        if (!qzstd_hip_group || nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
-        s->hGroupRows = (qzstd_hip_group_row_t *)h;
-        if (qfGrowD(j->dev, &s->dGroupRows, &s->dGroupRowsCap, nf * sizeof(qzstd_hip_group_row_t))) return -1;
-        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
-            qzstd_hip_group_row_t *r = &s->hGroupRows[m];
-            if (f0[c].diff) continue; /* (staged above) */
-            if (f0[c].len > 0xFFFFFFE0u) return -1;
-            r->src = (uint64_t)(uintptr_t)f0[c].src;
-            r->dstOff = so;
-            r->len = (uint32_t)f0[c].len;
-            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-            r->elem = f0[c].k;
-            r->reserved = 0;
-            m++;
-        }
-        return qzstd_hip_group(j->dev, s->stream, s->hGroupRows, (uint32_t)m, (qzstd_hip_group_row_t *)s->dGroupRows, s->dStage, stageBytes);
+        if (!qzstd_hip_group) return -1;
+        m = qfStageRows(j, pr, 0, &s->pin.groupRows, &s->dev.groupRows, sizeof(qzstd_hip_group_row_t), qfPutGroup, NULL);
+        return m == (size_t)-1 ? -1 : qzstd_hip_group(dev, s->stream, (const qzstd_hip_group_row_t *)s->pin.groupRows.p, (uint32_t)m,
+                                                      (qzstd_hip_group_row_t *)s->dev.groupRows.p, s->dev.stage.p, stageBytes);
     }
     if (qzstd_hip_gather) {
-        void *h = s->hRows;
-        size_t c, so = 0, m = 0;
-        if (nf > 0xFFFFFFFFu || qfGrowH(&h, &s->hRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
-        s->hRows = (qzstd_hip_gather_row_t *)h;
-        if (qfGrowD(j->dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_gather_row_t))) return -1;
-        for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
-            qzstd_hip_gather_row_t *r = &s->hRows[m];
-            if (f0[c].diff) continue; /* (staged above) */
-            if (f0[c].len > 0xFFFFFFE0u) return -1; /* (a row's length and padding are 32-bit) */
-            r->src = (uint64_t)(uintptr_t)f0[c].src;
-            r->dstOff = so;
-            r->len = (uint32_t)f0[c].len;
-            r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-            m++;
-        }
-        return qzstd_hip_gather(j->dev, s->stream, s->hRows, (uint32_t)m, (qzstd_hip_gather_row_t *)s->dRows, s->dStage, stageBytes);
+        m = qfStageRows(j, pr, 0, &s->pin.rows, &s->dev.rows, sizeof(qzstd_hip_gather_row_t), qfPutGather, NULL);
+        return m == (size_t)-1 ? -1 : qzstd_hip_gather(dev, s->stream, (const qzstd_hip_gather_row_t *)s->pin.rows.p, (uint32_t)m,
+                                                       (qzstd_hip_gather_row_t *)s->dev.rows.p, s->dev.stage.p, stageBytes);
     }
     if (!pr->run || pr->diff) return -1;
     {
         const size_t chunk = j->f->p.chunkSize, pitch = qfPad16(chunk), full = pr->bytes / chunk, tail = pr->bytes - full * chunk;
         const unsigned char *base = f0->src;
-        if (qzstd_hip_memset(j->dev, s->stream, s->dStage, 0, stageBytes)) return -1;
-        if (full && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage, pitch, base, chunk, chunk, full)) return -1;
-        if (tail && qzstd_hip_memcpy2d_d2d(j->dev, s->stream, s->dStage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
+        unsigned char *stage = (unsigned char *)s->dev.stage.p;
+        if (qzstd_hip_memset(dev, s->stream, stage, 0, stageBytes)) return -1;
+        if (full && qzstd_hip_memcpy2d_d2d(dev, s->stream, stage, pitch, base, chunk, chunk, full)) return -1;
+        if (tail && qzstd_hip_memcpy2d_d2d(dev, s->stream, stage + full * pitch, tail, base + full * chunk, tail, tail, 1)) return -1;
     }
     return 0;
 }
@@ -803,13 +975,10 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     /* in place: one buffer's chunks, address, chunk and length multiples of 16 (every block then starts 16-aligned and ends inside the buffer) */
     const int inPlace = !pr->grouped && !pr->delta && !pr->diff && !pr->pieces && pr->run && ((uintptr_t)base & 15u) == 0 && (j->f->p.chunkSize & 15u) == 0 && (pr->bytes & 15u) == 0;
     size_t c, b = 0, so = 0, seqCapTotal = 0;
+    qzstd_hip_block_t *desc;
     int dev = j->dev;
     if (nb > 0xFFFFFFFFu) return -1;
-    {
-        void *h = s->hDesc;
-        if (qfGrowH(&h, &s->hDescCap, nb * sizeof(qzstd_hip_block_t))) return -1;
-        s->hDesc = (qzstd_hip_block_t *)h;
-    }
+    if (!(desc = (qzstd_hip_block_t *)qfBufH(&s->pin.desc, nb * sizeof(qzstd_hip_block_t)))) return -1;
     for (c = 0; c < nf; c++) {
         const size_t at = inPlace ? f0[c].off - f0->off : so; /* the frame's first byte from the launch's base */
         size_t o = 0, e;
@@ -823,7 +992,7 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
         }
         if (QZSTD_byteGroupBlocks(f0[c].len, f0[c].k, s->ends, s->endsCap) != f0[c].nb) return -1;
         for (e = 0; e < f0[c].nb; o = s->ends[e], e++, b++) {
-            qzstd_hip_block_t *d = &s->hDesc[b];
+            qzstd_hip_block_t *d = &desc[b];
             d->srcLen = (uint32_t)(s->ends[e] - o);
             d->srcOff = at + o;
             d->seqOff = b * capPad;
@@ -835,39 +1004,34 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
         so += qfPad16(f0[c].len);
     }
     if (b != nb) return -1;
-    if (!s->stream && !(s->stream = qzstd_hip_stream_create(dev))) return -1;
     {
         const size_t work = qzstd_hip_workspace_bytes(j->level, (uint32_t)nb, (uint32_t)blk);
         const size_t arena = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb) + 8u * seqCapTotal + pr->bytes;
-        if (qfGrowD(dev, &s->dDesc, &s->dDescCap, nb * sizeof(qzstd_hip_block_t)) || qfGrowD(dev, &s->dSeqs, &s->dSeqsCap, nb * capPad * 16u) ||
-            qfGrowD(dev, &s->dCount, &s->dCountCap, nb * 4u) || qfGrowD(dev, &s->dWork, &s->dWorkCap, work) ||
-            qfGrowD(dev, &s->dCWork, &s->dCWorkCap, qzstd_hip_compact_workspace_bytes((uint32_t)nb)) || qfGrowD(dev, &s->dArena, &s->dArenaCap, arena))
+        if (!qfBufD(dev, &s->dev.desc, nb * sizeof(qzstd_hip_block_t)) || !qfBufD(dev, &s->dev.seqs, nb * capPad * 16u) ||
+            !qfBufD(dev, &s->dev.count, nb * 4u) || !qfBufD(dev, &s->dev.work, work) ||
+            !qfBufD(dev, &s->dev.cwork, qzstd_hip_compact_workspace_bytes((uint32_t)nb)) || !qfBufD(dev, &s->dev.arena, arena))
             return -1;
     }
     if (!inPlace) {
         if (qfStagePart(j, s, pr, so + 16u)) return -1;
-        base = s->dStage;
+        base = (const unsigned char *)s->dev.stage.p;
     }
-    if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dDesc, s->hDesc, nb * sizeof(qzstd_hip_block_t)) ||
-        qzstd_hip_find_sequences(dev, s->stream, j->level, base, (const qzstd_hip_block_t *)s->dDesc, (uint32_t)nb, (uint32_t)blk, s->dSeqs,
-                                 (uint32_t *)s->dCount, s->dWork, s->dWorkCap) ||
-        qzstd_hip_compact(dev, s->stream, base, (const qzstd_hip_block_t *)s->dDesc, (uint32_t)nb, s->dSeqs, (const uint32_t *)s->dCount,
-                          s->dArena, s->dArenaCap, s->dCWork, s->dCWorkCap))
+    if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dev.desc.p, desc, nb * sizeof(qzstd_hip_block_t)) ||
+        qzstd_hip_find_sequences(dev, s->stream, j->level, base, (const qzstd_hip_block_t *)s->dev.desc.p, (uint32_t)nb, (uint32_t)blk, s->dev.seqs.p,
+                                 (uint32_t *)s->dev.count.p, s->dev.work.p, s->dev.work.cap) ||
+        qzstd_hip_compact(dev, s->stream, base, (const qzstd_hip_block_t *)s->dev.desc.p, (uint32_t)nb, s->dev.seqs.p, (const uint32_t *)s->dev.count.p,
+                          s->dev.arena.p, s->dev.arena.cap, s->dev.cwork.p, s->dev.cwork.cap))
         return -1;
     s->hashed = 0;
     if (j->checksum) {
         /* the frames' content hashes, from the bytes the match-finder was given: frame c at the offset its first block has */
-        void *h = s->hHashRows;
-        if (qfGrowH(&h, &s->hHashRowsCap, nf * sizeof(qzstd_hip_hash_row_t))) return -1;
-        s->hHashRows = (qzstd_hip_hash_row_t *)h;
-        if (qfGrowD(dev, &s->dHashRows, &s->dHashRowsCap, nf * sizeof(qzstd_hip_hash_row_t)) || qfGrowD(dev, &s->dHash, &s->dHashCap, nf * 8u))
-            return -1;
+        qzstd_hip_hash_row_t *rows = (qzstd_hip_hash_row_t *)qfBufH(&s->pin.hashRows, nf * sizeof(qzstd_hip_hash_row_t));
+        if (!rows || !qfBufD(dev, &s->dev.hashRows, nf * sizeof(qzstd_hip_hash_row_t)) || !qfBufD(dev, &s->dev.hash, nf * 8u)) return -1;
         for (c = 0; c < nf; c++) {
-            s->hHashRows[c].srcOff = s->hDesc[f0[c].b0].srcOff;
-            s->hHashRows[c].len = f0[c].len;
+            rows[c].srcOff = desc[f0[c].b0].srcOff;
+            rows[c].len = f0[c].len;
         }
-        if (nf > 0xFFFFFFFFu || qzstd_hip_xxh64(dev, s->stream, base, s->hHashRows, (uint32_t)nf, (qzstd_hip_hash_row_t *)s->dHashRows,
-                                                 (uint64_t *)s->dHash))
+        if (nf > 0xFFFFFFFFu || qzstd_hip_xxh64(dev, s->stream, base, rows, (uint32_t)nf, (qzstd_hip_hash_row_t *)s->dev.hashRows.p, (uint64_t *)s->dev.hash.p))
             return -1;
         s->hashed = 1;
     }
@@ -876,31 +1040,26 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
     if (j->probe && (pr->grouped || pr->delta)) {
         /* the blocks' byte histograms, reduced to their order-0 cost on the device: a row per descriptor, over the stage (such a part is
          * never read in place) */
-        void *h = s->hPlaneRows;
-        if (qfGrowH(&h, &s->hPlaneRowsCap, nb * sizeof(qzstd_hip_plane_row_t))) return -1;
-        s->hPlaneRows = (qzstd_hip_plane_row_t *)h;
-        if (qfGrowD(dev, &s->dPlaneRows, &s->dPlaneRowsCap, nb * sizeof(qzstd_hip_plane_row_t)) ||
-            qfGrowD(dev, &s->dPlaneCost, &s->dPlaneCostCap, nb * sizeof(uint32_t)))
+        qzstd_hip_plane_row_t *rows = (qzstd_hip_plane_row_t *)qfBufH(&s->pin.planeRows, nb * sizeof(qzstd_hip_plane_row_t));
+        if (!rows || !qfBufD(dev, &s->dev.planeRows, nb * sizeof(qzstd_hip_plane_row_t)) || !qfBufD(dev, &s->dev.planeCost, nb * sizeof(uint32_t)))
             return -1;
         for (b = 0; b < nb; b++) {
-            s->hPlaneRows[b].srcOff = s->hDesc[b].srcOff;
-            s->hPlaneRows[b].len = s->hDesc[b].srcLen;
-            s->hPlaneRows[b].reserved = 0;
+            rows[b].srcOff = desc[b].srcOff;
+            rows[b].len = desc[b].srcLen;
+            rows[b].reserved = 0;
         }
         if (j->code) {
             /* plane code: the coder leaves the same cost words, and the blocks worth it Huffman-coded — this launch instead of that one */
-            const size_t dense = qzstd_hip_huf_code_bytes(s->hPlaneRows, (uint32_t)nb);
-            if (dense == (size_t)-1 || qfGrowD(dev, &s->dHufWords, &s->dHufWordsCap, (2u * nb + 1u) * sizeof(uint32_t)) ||
-                qfGrowD(dev, &s->dHufDense, &s->dHufDenseCap, dense + 16u) ||
-                qfGrowD(dev, &s->dHufScratch, &s->dHufScratchCap, QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
+            const size_t dense = qzstd_hip_huf_code_bytes(rows, (uint32_t)nb);
+            if (dense == (size_t)-1 || !qfBufD(dev, &s->dev.hufWords, (2u * nb + 1u) * sizeof(uint32_t)) || !qfBufD(dev, &s->dev.hufDense, dense + 16u) ||
+                !qfBufD(dev, &s->dev.hufScratch, QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
                 return -1;
-            if (qzstd_hip_huf_code(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
-                                   (uint32_t *)s->dPlaneCost, (uint32_t *)s->dHufWords, (uint32_t *)s->dHufWords + nb, s->dHufDense, dense,
-                                   s->dHufScratch, QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
+            if (qzstd_hip_huf_code(dev, s->stream, base, rows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dev.planeRows.p, (uint32_t *)s->dev.planeCost.p,
+                                   (uint32_t *)s->dev.hufWords.p, (uint32_t *)s->dev.hufWords.p + nb, s->dev.hufDense.p, dense, s->dev.hufScratch.p,
+                                   QZSTD_HIP_HUF_SCRATCH_BYTES(nb, dense)))
                 return -1;
             s->coded = 1;
-        } else if (qzstd_hip_plane_cost(dev, s->stream, base, s->hPlaneRows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dPlaneRows,
-                                        (uint32_t *)s->dPlaneCost)) {
+        } else if (qzstd_hip_plane_cost(dev, s->stream, base, rows, (uint32_t)nb, (qzstd_hip_plane_row_t *)s->dev.planeRows.p, (uint32_t *)s->dev.planeCost.p)) {
             return -1;
         }
         s->probed = 1;
@@ -911,37 +1070,24 @@ static int qfQueuePart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr)
 /* waits for a queued part, brings its arena back (one D2H) and fills the per-block offsets; -> the part for the workers */
 static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, QF_DevPart *out)
 {
-    const size_t nb = pr->nb;
+    const size_t nb = pr->nb, nf = pr->f1 - pr->f0;
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(nb);
     const qzstd_hip_compact_hdr_t *hdr;
+    const uint32_t *words = NULL;
+    unsigned char *arena;
     size_t b, seqs = 0, lits = 0, bytes, dense = 0;
-    if (s->hArenaCap < eo) {
-        void *h = s->hArena;
-        if (qfGrowH(&h, &s->hArenaCap, eo + pr->bytes + (pr->bytes >> 2) + QF_LIT_SLACK)) return -1;
-        s->hArena = (unsigned char *)h;
-    }
-    if (s->hashed) {
-        /* the hashes travel with the headers: one more copy per part, 8 bytes per frame, no wait of its own */
-        void *h = s->hHash;
-        if (qfGrowH(&h, &s->hHashCap, (pr->f1 - pr->f0) * 8u)) return -1;
-        s->hHash = (uint64_t *)h;
-        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHash, s->dHash, (pr->f1 - pr->f0) * 8u)) return -1;
-    }
-    if (s->probed) {
-        /* the blocks' costs travel with the headers as the hashes do: 4 bytes per block */
-        void *h = s->hPlaneCost;
-        if (qfGrowH(&h, &s->hPlaneCostCap, nb * sizeof(uint32_t))) return -1;
-        s->hPlaneCost = (uint32_t *)h;
-        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hPlaneCost, s->dPlaneCost, nb * sizeof(uint32_t))) return -1;
-    }
-    if (s->coded) {
-        /* and so do the size words and the dense offsets: 8 bytes per block and 4 */
-        void *h = s->hHufWords;
-        if (qfGrowH(&h, &s->hHufWordsCap, (2u * nb + 1u) * sizeof(uint32_t))) return -1;
-        s->hHufWords = (uint32_t *)h;
-        if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHufWords, s->dHufWords, (2u * nb + 1u) * sizeof(uint32_t))) return -1;
-    }
-    if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena, s->dArena, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
+    if (s->pin.arena.cap < eo && !qfBufH(&s->pin.arena, eo + pr->bytes + (pr->bytes >> 2) + QF_LIT_SLACK)) return -1;
+    /* the hashes travel with the headers: one more copy per part, 8 bytes per frame, no wait of its own */
+    if (s->hashed && (!qfBufH(&s->pin.hash, nf * 8u) || qzstd_hip_memcpy_d2h(j->dev, s->stream, s->pin.hash.p, s->dev.hash.p, nf * 8u))) return -1;
+    /* the blocks' costs travel with the headers as the hashes do: 4 bytes per block */
+    if (s->probed && (!qfBufH(&s->pin.planeCost, nb * sizeof(uint32_t)) ||
+                      qzstd_hip_memcpy_d2h(j->dev, s->stream, s->pin.planeCost.p, s->dev.planeCost.p, nb * sizeof(uint32_t))))
+        return -1;
+    /* and so do the size words and the dense offsets: 8 bytes per block and 4 */
+    if (s->coded && (!(words = (const uint32_t *)qfBufH(&s->pin.hufWords, (2u * nb + 1u) * sizeof(uint32_t))) ||
+                     qzstd_hip_memcpy_d2h(j->dev, s->stream, s->pin.hufWords.p, s->dev.hufWords.p, (2u * nb + 1u) * sizeof(uint32_t))))
+        return -1;
+    if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->pin.arena.p, s->dev.arena.p, nb * 8u) || qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0)
         return -1;
     if (s->blkCap < nb) {
         free(s->blkSeq);
@@ -951,7 +1097,7 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         s->blkCap = s->blkSeq && s->blkLit ? nb : 0;
         if (!s->blkCap) return -1;
     }
-    hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    hdr = QF_HDR(s);
     for (b = 0; b < nb; b++) {
         s->blkSeq[b] = seqs;
         s->blkLit[b] = lits;
@@ -960,37 +1106,33 @@ static int qfFetchPart(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr,
         lits += hdr[b].litBytes;
     }
     bytes = 8u * seqs + lits;
-    if (s->hArenaCap < eo + bytes + QF_LIT_SLACK) {
-        /* grown (an eighth more than this part needs): the headers move along */
+    if (s->pin.arena.cap < eo + bytes + QF_LIT_SLACK) {
+        /* THE buffer that grows and keeps its contents, by hand (an eighth more than this part needs): the headers move along */
         unsigned char *n = (unsigned char *)qzstd_hip_host_alloc(eo + bytes + QF_LIT_SLACK + (bytes >> 3));
         if (!n) return -1;
-        memcpy(n, s->hArena, nb * 8u);
-        qzstd_hip_host_free(s->hArena);
-        s->hArena = n;
-        s->hArenaCap = eo + bytes + QF_LIT_SLACK + (bytes >> 3);
+        memcpy(n, s->pin.arena.p, nb * 8u);
+        qzstd_hip_host_free(s->pin.arena.p);
+        s->pin.arena.p = n;
+        s->pin.arena.cap = eo + bytes + QF_LIT_SLACK + (bytes >> 3);
     }
+    arena = (unsigned char *)s->pin.arena.p;
     if (s->coded) {
         /* the dense area: one more copy behind the header wait, as long as the offsets say; it shares the entries' wait */
-        dense = s->hHufWords[2u * nb];
-        if (dense) {
-            void *h = s->hHufDense;
-            if (qfGrowH(&h, &s->hHufDenseCap, dense)) return -1;
-            s->hHufDense = (unsigned char *)h;
-            if (qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hHufDense, s->dHufDense, dense)) return -1;
-        }
+        dense = words[2u * nb];
+        if (dense && (!qfBufH(&s->pin.hufDense, dense) || qzstd_hip_memcpy_d2h(j->dev, s->stream, s->pin.hufDense.p, s->dev.hufDense.p, dense))) return -1;
     }
-    if (bytes && qzstd_hip_memcpy_d2h(j->dev, s->stream, s->hArena + eo, (const unsigned char *)s->dArena + eo, bytes)) return -1;
+    if (bytes && qzstd_hip_memcpy_d2h(j->dev, s->stream, arena + eo, (const unsigned char *)s->dev.arena.p + eo, bytes)) return -1;
     if ((bytes || dense) && qzstd_hip_stream_wait(j->dev, s->stream, QF_DEV_WAIT_MS) != 0) return -1;
-    memset(s->hArena + eo + bytes, 0, QF_LIT_SLACK);
-    s->hLit = s->hArena + eo + 8u * seqs;
+    memset(arena + eo + bytes, 0, QF_LIT_SLACK);
+    s->hLit = arena + eo + 8u * seqs;
     s->litTotal = lits;
-    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? (pr->f1 - pr->f0) * 8u : 0u) +
+    __atomic_fetch_add(&j->f->devStats[2], (unsigned long long)(nb * 8u + bytes + (s->hashed ? nf * 8u : 0u) +
                                                            (s->probed ? nb * 4u : 0u) + (s->coded ? (2u * nb + 1u) * 4u + dense : 0u)),
                        __ATOMIC_RELAXED);
     if (s->probed) __atomic_fetch_add(&j->f->probeStats[0], (unsigned long long)nb, __ATOMIC_RELAXED);
     if (s->coded) {
         unsigned long long coded = 0;
-        for (b = 0; b < nb; b++) coded += s->hHufWords[b] != 0u;
+        for (b = 0; b < nb; b++) coded += words[b] != 0u;
         __atomic_fetch_add(&j->f->codeStats[0], coded, __ATOMIC_RELAXED);
     }
     out->hashed = s->hashed;
@@ -1047,7 +1189,7 @@ static size_t qfFrameHeader(unsigned char *out, size_t len, int checksum)
 static int qfBlockIsRaw(const QF_DevSlot *s, const qzstd_hip_compact_hdr_t *h, size_t b, size_t len)
 {
     return len <= QZSTD_PLANE_LEN_MAX && h->count != QZSTD_HIP_NSEQ_ERROR && h->litBytes <= len &&
-           QZSTD_planeIsRaw(s->hPlaneCost[b], (uint32_t)len, (uint32_t)(len - h->litBytes));
+           QZSTD_planeIsRaw(((const uint32_t *)s->pin.planeCost.p)[b], (uint32_t)len, (uint32_t)(len - h->litBytes));
 }
 
 static int qfGrowBytes(unsigned char **p, size_t *cap, size_t need)
@@ -1075,7 +1217,7 @@ static int qfAssembleFrame(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
 {
     static const unsigned char didBytes[4] = { 0, 1, 2, 4 }, fcsBytes[4] = { 0, 2, 4, 8 };
     const QF_DevSlot *s = pt->slot;
-    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const qzstd_hip_compact_hdr_t *hdr = QF_HDR(s);
     const size_t n = fm->len, b0 = fm->b0, nb = fm->nb, cap = f->stride;
     size_t e, o, nRaw = 0, subSeqs = 0, subLit = 0, subSize = 0, runs = 0, firstSub = 0, pos, sp = 0, r = 0;
     int prevRaw = 1;
@@ -1186,7 +1328,7 @@ static int qfAssembleFrame(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
     }
     if (nRaw < nb) (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
     if (pt->hashed) {
-        const uint64_t h = s->hHash[c];
+        const uint64_t h = ((const uint64_t *)s->pin.hash.p)[c];
         dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16); dst[pos++] = (unsigned char)(h >> 24);
         __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
     }
@@ -1206,12 +1348,13 @@ fallback:
 /* plane code: the bytes of block b's QZSTD_hufBlockBody (0: none, or the block is not taken by QZSTD_hufTakes) */
 static size_t qfBlockTaken(const QF_DevSlot *s, const qzstd_hip_compact_hdr_t *h, size_t nbPart, size_t b, size_t len)
 {
-    const uint32_t size = s->hHufWords[b];
+    const uint32_t *words = (const uint32_t *)s->pin.hufWords.p;
+    const uint32_t size = words[b];
     const unsigned char *at;
     uint8_t nbits[256], tree[QZSTD_HUF_TREE_MAX];
     size_t t, body;
     if (!size || len < QZSTD_HUF_LEN_MIN || len > QZSTD_HUF_LEN_MAX || h->count == QZSTD_HIP_NSEQ_ERROR) return 0;
-    at = s->hHufDense + s->hHufWords[nbPart + b];
+    at = (const unsigned char *)s->pin.hufDense.p + words[nbPart + b];
     QZSTD_hufUnpackLengths(at, nbits);
     t = QZSTD_hufWriteTree(nbits, tree, sizeof(tree));
     if (!t) return 0;
@@ -1229,7 +1372,7 @@ static size_t qfBlockTaken(const QF_DevSlot *s, const qzstd_hip_compact_hdr_t *h
 static int qfAssembleCoded(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, const QF_DevFrame *fm, size_t c, unsigned char *dst)
 {
     const QF_DevSlot *s = pt->slot;
-    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const qzstd_hip_compact_hdr_t *hdr = QF_HDR(s);
     const size_t n = fm->len, b0 = fm->b0, nb = fm->nb, cap = f->stride;
     size_t e, o, nRaw = 0, nTaken = 0, pos;
     for (e = 0, o = 0; e < nb; o = w->ends[e], e++) {
@@ -1255,13 +1398,14 @@ static int qfAssembleCoded(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
             }
             pos += len;
         } else {
-            const unsigned char *at = s->hHufDense + s->hHufWords[pt->nb + b];
+            const uint32_t *words = (const uint32_t *)s->pin.hufWords.p;
+            const unsigned char *at = (const unsigned char *)s->pin.hufDense.p + words[pt->nb + b];
             uint8_t nbits[256];
             size_t body;
             unsigned h;
             if (pos + 3u + len + 4u > cap) goto fallback; /* (a taken body is below len) */
             QZSTD_hufUnpackLengths(at, nbits);
-            body = QZSTD_hufBlockBody(nbits, (uint32_t)len, at + QZSTD_HUF_LENGTHS_BYTES, s->hHufWords[b], dst + pos + 3u, len);
+            body = QZSTD_hufBlockBody(nbits, (uint32_t)len, at + QZSTD_HUF_LENGTHS_BYTES, words[b], dst + pos + 3u, len);
             if (!body) goto fallback;
             h = (unsigned)(body << 3) | (2u << 1) | last; /* Block_Size, Compressed_Block, Last_Block */
             dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16);
@@ -1269,7 +1413,7 @@ static int qfAssembleCoded(QZSTD_Front *f, QF_Worker *w, const QF_DevPart *pt, c
         }
     }
     if (pt->hashed) {
-        const uint64_t h = s->hHash[c];
+        const uint64_t h = ((const uint64_t *)s->pin.hash.p)[c];
         dst[pos++] = (unsigned char)h; dst[pos++] = (unsigned char)(h >> 8); dst[pos++] = (unsigned char)(h >> 16); dst[pos++] = (unsigned char)(h >> 24);
         __atomic_fetch_add(&f->cksumStats[0], 1ull, __ATOMIC_RELAXED);
     }
@@ -1295,9 +1439,9 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
     const size_t cg = pt->f0 + c;
     const QF_DevFrame *fm = &pt->frames[cg];
     const size_t n = fm->len, b0 = fm->b0, b1 = b0 + fm->nb;
-    const qzstd_hip_compact_hdr_t *hdr = (const qzstd_hip_compact_hdr_t *)(const void *)s->hArena;
+    const qzstd_hip_compact_hdr_t *hdr = QF_HDR(s);
     const size_t eo = QZSTD_HIP_COMPACT_ENTRIES_OFF(pt->nb);
-    const unsigned long long *ent = (const unsigned long long *)(const void *)(s->hArena + eo);
+    const unsigned long long *ent = (const unsigned long long *)(const void *)((const unsigned char *)s->pin.arena.p + eo);
     size_t b, ns = 0, nl = 0, k, r = 0;
     int failedBlock = 0, haveSeqs = 0, maybeRle = 0;
     const int grouped = fm->k > 1u;
@@ -1358,7 +1502,7 @@ static int qfDeviceFrame(QZSTD_Front *f, QF_Worker *w, size_t c)
                 (void)ZSTD_CCtx_setParameter(w->zc, ZSTD_c_blockDelimiters, 0);
                 if (pt->hashed) {
                     /* Content_Checksum_Flag (bit 2 of the frame header descriptor) and the hash's low 32 bits behind the last block */
-                    const uint64_t h = s->hHash[c];
+                    const uint64_t h = ((const uint64_t *)s->pin.hash.p)[c];
                     dst[4] |= 4u;
                     dst[r] = (unsigned char)h;
                     dst[r + 1] = (unsigned char)(h >> 8);
@@ -1474,6 +1618,13 @@ static size_t qfSrcFramePieces(const QF_SrcMap *sm, size_t *p, size_t off, size_
     return np;
 }
 
+/* piece q of the map, cut to a frame: its bytes [*lo, *hi) of bytes [off, off + len) of the buffer */
+static void qfPieceInFrame(const QF_SrcPiece *q, size_t off, size_t len, size_t *lo, size_t *hi)
+{
+    *lo = q->off > off ? q->off : off;
+    *hi = q->off + q->size < off + len ? q->off + q->size : off + len;
+}
+
 /* the piece table of such a frame for the kernels that read pieces: pieces [p, p + np) of the map cut to bytes [off, off + len) of their
  * buffer, offsets counted from the frame's first byte; bases: with the pieces' bases (else 0: none is ever read) */
 static void qfSrcFrameTable(const QF_SrcMap *sm, size_t p, size_t np, size_t off, size_t len, int bases, qzstd_hip_group_piece_t *out)
@@ -1481,7 +1632,8 @@ static void qfSrcFrameTable(const QF_SrcMap *sm, size_t p, size_t np, size_t off
     size_t k;
     for (k = 0; k < np; k++) {
         const QF_SrcPiece *q = &sm->pieces[p + k];
-        const size_t lo = q->off > off ? q->off : off, hi = q->off + q->size < off + len ? q->off + q->size : off + len;
+        size_t lo, hi;
+        qfPieceInFrame(q, off, len, &lo, &hi);
         out[k].src = (uint64_t)(uintptr_t)(q->src + (lo - q->off));
         out[k].base = bases && q->base ? (uint64_t)(uintptr_t)(q->base + (lo - q->off)) : 0u;
         out[k].off = (uint32_t)(lo - off);
@@ -1641,86 +1793,100 @@ static int qfIsZeroFrame(const unsigned char *fr, size_t frSize, size_t len, uns
 }
 
 /* The pre-pass of a delta call with the setting on: ONE qzstd_hip_diff launch on the slot's stream (which already waits for the caller's),
- * a row per frame of every buffer that has a base, the flags back in one copy, a bounded wait.  equal[c] (nFrames entries) becomes 1 for a
- * frame whose chunk equals its base chunk — its canonical zero frame is written to dst here and its size to frameSizes — and 0 for every
- * other frame, those of buffers without a base included: they are never compared. */
-static int qfDiffPass(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, size_t nBufs,
-                      size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes)
+ * the flags back in one copy, a bounded wait.  A frame of a buffer that has a base is compared piece by piece, a row per piece (rows of
+ * its own, so that a frame's flags are its own): the pieces of the source map that hold its bytes, or — no map, the buffers are
+ * contiguous — ONE piece, bufs[i].d_ptr + off against bases[i].d_ptr + off.  equal[c] (nFrames entries) becomes 1 for a frame none of
+ * whose rows differs — its canonical zero frame is written to dst here and its size to frameSizes — and 0 for every other frame, those
+ * of buffers without a base included: they are never compared. */
+static int qfDiffPass(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
+                      size_t nBufs, size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes)
 {
     const size_t chunk = f->p.chunkSize;
     QF_ZeroHash z;
-    size_t i, off, c = 0, rows = 0, r = 0, nEqual = 0;
+    size_t i, off, c = 0, rows = 0, frames = 0, r = 0, nEqual = 0, p = 0;
     unsigned long long bytes = 0;
-    void *h;
+    qzstd_hip_diff_row_t *row;
+    const uint32_t *flags;
     memset(equal, 0, nFrames);
     memset(&z, 0, sizeof(z));
-    for (i = 0; i < nBufs; i++)
-        if (bases[i].d_ptr) rows += bufs[i].size / chunk + (bufs[i].size % chunk != 0);
+    for (i = 0; i < nBufs; i++) {
+        if (!bases[i].d_ptr) continue;
+        for (off = 0, p = sm ? sm->first[i] : 0; off < bufs[i].size; off += chunk, frames++)
+            rows += sm ? qfSrcFramePieces(sm, &p, off, bufs[i].size - off < chunk ? bufs[i].size - off : chunk) : 1u;
+    }
     if (rows == 0) return 0;
     if (rows > 0xFFFFFFFFu || chunk > 0xFFFFFFE0u) return -1; /* (a launch's rows and a row's length are 32-bit) */
     if (qfZeroFrameBound(chunk) > f->stride) return -1;
-    h = s->hDiffRows;
-    if (qfGrowH(&h, &s->hDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t))) return -1;
-    s->hDiffRows = (qzstd_hip_diff_row_t *)h;
-    h = s->hDiffFlags;
-    if (qfGrowH(&h, &s->hDiffFlagsCap, rows * sizeof(uint32_t))) return -1;
-    s->hDiffFlags = (uint32_t *)h;
-    if (qfGrowD(dev, &s->dDiffRows, &s->dDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t)) ||
-        qfGrowD(dev, &s->dDiffFlags, &s->dDiffFlagsCap, rows * sizeof(uint32_t)))
+    row = (qzstd_hip_diff_row_t *)qfBufH(&s->pin.diffRows, rows * sizeof(qzstd_hip_diff_row_t));
+    flags = (const uint32_t *)qfBufH(&s->pin.diffFlags, rows * sizeof(uint32_t));
+    if (!row || !flags || !qfBufD(dev, &s->dev.diffRows, rows * sizeof(qzstd_hip_diff_row_t)) || !qfBufD(dev, &s->dev.diffFlags, rows * sizeof(uint32_t)))
         return -1;
     for (i = 0; i < nBufs; i++) {
         if (!bases[i].d_ptr) continue;
-        for (off = 0; off < bufs[i].size; off += chunk, r++) {
-            qzstd_hip_diff_row_t *row = &s->hDiffRows[r];
-            row->a = (uint64_t)(uintptr_t)((const unsigned char *)bufs[i].d_ptr + off);
-            row->b = (uint64_t)(uintptr_t)((const unsigned char *)bases[i].d_ptr + off);
-            row->len = (uint32_t)(bufs[i].size - off < chunk ? bufs[i].size - off : chunk);
-            row->tile0 = 0;
-            bytes += row->len;
+        for (off = 0, p = sm ? sm->first[i] : 0; off < bufs[i].size; off += chunk) {
+            const size_t len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
+            size_t np = sm ? qfSrcFramePieces(sm, &p, off, len) : 1u, k;
+            for (k = 0; k < np; k++, row++) {
+                size_t lo = off, hi = off + len;
+                const unsigned char *a = (const unsigned char *)bufs[i].d_ptr + off, *b = (const unsigned char *)bases[i].d_ptr + off;
+                if (sm) {
+                    const QF_SrcPiece *q = &sm->pieces[p + k];
+                    qfPieceInFrame(q, off, len, &lo, &hi);
+                    a = q->src + (lo - q->off);
+                    b = q->base + (lo - q->off);
+                }
+                row->a = (uint64_t)(uintptr_t)a;
+                row->b = (uint64_t)(uintptr_t)b;
+                row->len = (uint32_t)(hi - lo);
+                row->tile0 = 0;
+            }
+            bytes += len;
         }
     }
-    if (qzstd_hip_diff(dev, s->stream, s->hDiffRows, (uint32_t)rows, (qzstd_hip_diff_row_t *)s->dDiffRows, (uint32_t *)s->dDiffFlags) ||
-        qzstd_hip_memcpy_d2h(dev, s->stream, s->hDiffFlags, s->dDiffFlags, rows * sizeof(uint32_t)))
+    if (qzstd_hip_diff(dev, s->stream, (qzstd_hip_diff_row_t *)s->pin.diffRows.p, (uint32_t)rows, (qzstd_hip_diff_row_t *)s->dev.diffRows.p,
+                       (uint32_t *)s->dev.diffFlags.p) ||
+        qzstd_hip_memcpy_d2h(dev, s->stream, s->pin.diffFlags.p, s->dev.diffFlags.p, rows * sizeof(uint32_t)))
         return -1;
     if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
         (void)qzstd_hip_stream_sync(dev, s->stream); /* the launch still reads the caller's buffers */
         return -1;
     }
-    for (i = 0, r = 0; i < nBufs; i++) {
+    for (i = 0; i < nBufs; i++) {
         const size_t nf = bufs[i].size / chunk + (bufs[i].size % chunk != 0);
         if (bases[i].d_ptr) {
-            for (off = 0; off < nf; off++, r++) {
-                if (s->hDiffFlags[r]) continue;
+            for (off = 0, p = sm ? sm->first[i] : 0; off < nf; off++) {
+                const size_t len = bufs[i].size - off * chunk < chunk ? bufs[i].size - off * chunk : chunk;
+                size_t np = sm ? qfSrcFramePieces(sm, &p, off * chunk, len) : 1u;
+                uint32_t any = 0;
+                for (; np; np--, r++) any |= flags[r];
+                if (any) continue;
                 equal[c + off] = 1;
-                frameSizes[c + off] = qfZeroFrame(dst + (c + off) * f->stride, s->hDiffRows[r].len, f->checksum, &z, chunk);
+                frameSizes[c + off] = qfZeroFrame(dst + (c + off) * f->stride, len, f->checksum, &z, chunk);
                 nEqual++;
             }
         }
         c += nf;
     }
-    __atomic_fetch_add(&f->skipStats[0], (unsigned long long)rows, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->skipStats[0], (unsigned long long)frames, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->skipStats[1], (unsigned long long)nEqual, __ATOMIC_RELAXED);
     __atomic_fetch_add(&f->skipStats[2], bytes, __ATOMIC_RELAXED);
     return 0;
 }
 
 /* both device entry points.  batch: the call needs the gather (frames of several buffers in one part); the single-buffer call stages a part it
- * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not */
-static int qfDiffPassSlices(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
-                            size_t nBufs, size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes); /* qzstd_srcslices.c */
-
-/* sm: NULL, or (QZSTD_frontCompressDeviceSlices, which has checked the slices and looked their memory up) where the buffers' bytes lie; bufs and
+ * cannot read in place with the gather when the device layer has it and with a memset and 2D copies when not.
+ * sm: NULL, or (QZSTD_frontCompressDeviceSlices, which has checked the slices and looked their memory up) where the buffers' bytes lie; bufs and
  * bases then hold each buffer's size and the address of its FIRST slice, which is the buffer's own when its slices follow each other in memory */
 static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
                                const unsigned char *elemSizes, size_t nBufs, int batch, void *stream, void *dst, size_t dstCapacity, size_t *frameSizes, size_t *firstFrame)
 {
     QF_DevJob j;
+    QF_Call call;
     QF_DevSlot *slot;
     QF_DevPart part[2];
     QF_DevFrame *frames = NULL;
     QF_DevRange *parts = NULL;
-    void *ev = NULL;
-    size_t nFrames, nParts = 0, k, i, total = 0;
+    size_t nFrames, nParts = 0, k, i, total;
     unsigned group;
     unsigned char *equal = NULL;
     int rc = 0, anyGrouped = 0, anyBase = 0, anyDiff = 0, skip, probe, code;
@@ -1765,40 +1931,24 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
     if (code && (!qzstd_hip_huf_code || !qzstd_hip_huf_code_bytes)) return (size_t)-1; /* plane code wanted and a device layer without the coder */
     probe = code || (f->planeProbe && (anyGrouped || bases));
     if (probe && !code && !qzstd_hip_plane_cost) return (size_t)-1;  /* plane probe wanted and a device layer that cannot take histograms */
-    j.dev = sm ? sm->dev : -1;
-    total = sm ? sm->total : 0;
-    for (i = 0; !sm && i < nBufs; i++) {
-        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
-        int d;
-        if (!bufs[i].size) continue;
-        d = qzstd_hip_pointer_device(p);
-        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (j.dev >= 0 && d != j.dev)) return (size_t)-1;
-        j.dev = d;
-        total += bufs[i].size;
-        if (bases && bases[i].d_ptr) {
-            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
-            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
-        }
+    call.f = f;
+    call.restore = 0;
+    call.nStreams = 2;
+    call.dev = sm ? sm->dev : -1; /* (a call with source slices has looked its memory up: qfSrcMapBuild) */
+    if (!sm && qfCallBufs(&call, bufs, bases, nBufs)) return (size_t)-1;
+    /* a call without a frame takes nothing, not even devBusy: it succeeds while another call is in progress */
+    if (nFrames == 0) {
+        qfFirstFrames(f, bufs, nBufs, firstFrame);
+        return 0;
     }
-    if (nFrames) {
-        pthread_mutex_lock(&f->mu);
-        if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-        f->devBusy = 1;
-        pthread_mutex_unlock(&f->mu);
-    }
-    if (firstFrame) {
-        size_t c = 0;
-        for (i = 0; i < nBufs; i++) {
-            firstFrame[i] = c;
-            c += bufs[i].size / f->p.chunkSize + (bufs[i].size % f->p.chunkSize != 0);
-        }
-        firstFrame[nBufs] = c;
-    }
-    if (nFrames == 0) return 0;
+    if (qfCallBegin(&call, stream)) return (size_t)-1; /* (firstFrame is not written by a call that is refused) */
+    qfFirstFrames(f, bufs, nBufs, firstFrame);
     pthread_once(&qfSeqOnce, qfResolveSeqApi);
+    for (i = 0, total = 0; i < nBufs; i++) total += bufs[i].size;
 
     j.f = f;
     j.sm = sm;
+    j.dev = call.dev;
     j.checksum = f->checksum; /* (fixed for the call: devBusy keeps QZSTD_frontSetChecksum out) */
     j.probe = probe;
     j.code = code;
@@ -1809,29 +1959,13 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
         j.level = f->p.level | ((rep && atoi(rep) > 0) ? QZSTD_HIP_LEVEL_REPCODES : 0);
     }
     memset(part, 0, sizeof(part));
-    /* the slots stay with the front between calls (allocating and freeing pinned and device memory costs more than a part takes) */
-    if (f->devSlot && f->devSlotDev != j.dev) qfDevSlotsFree(f);
-    if (!f->devSlot && !(f->devSlot = (QF_DevSlot *)calloc(2, sizeof(QF_DevSlot)))) rc = -1;
-    f->devSlotDev = j.dev;
     slot = f->devSlot;
-    /* the library's streams wait for what the caller queued on `stream` so far: the work that produced the buffers */
-    for (k = 0; slot && k < 2 && rc == 0; k++)
-        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(j.dev))) rc = -1;
-    if (rc == 0 && !(ev = qzstd_hip_event_create(j.dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(j.dev, ev, stream) || qzstd_hip_stream_wait_event(j.dev, slot[0].stream, ev) ||
-                    qzstd_hip_stream_wait_event(j.dev, slot[1].stream, ev)))
-        rc = -1;
     /* delta skip: the chunks equal to their base chunk are found first and get their zero frames; the parts are planned without them */
-    if (rc == 0 && skip) {
+    if (skip) {
         if (!(equal = (unsigned char *)malloc(nFrames))) rc = -1;
-        else rc = sm ? qfDiffPassSlices(f, &slot[0], j.dev, bufs, bases, sm, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes)
-                     : qfDiffPass(f, &slot[0], j.dev, bufs, bases, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes);
+        else rc = qfDiffPass(f, &slot[0], j.dev, bufs, bases, sm, nBufs, nFrames, equal, (unsigned char *)dst, frameSizes);
     }
-    if (rc == 0) {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of input per part (whole frames, at least one), default 64 MiB */
-        const size_t want = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-        rc = qfPlanDevice(f, bufs, bases, sm, elemSizes, group, nBufs, equal, nFrames, want, j.blk, &frames, &parts, &nParts);
-    }
+    if (rc == 0) rc = qfPlanDevice(f, bufs, bases, sm, elemSizes, group, nBufs, equal, nFrames, qfPartBytes(), j.blk, &frames, &parts, &nParts);
     j.frames = frames;
     j.parts = parts;
     j.nParts = nParts;
@@ -1860,22 +1994,12 @@ static size_t qfCompressDevice(QZSTD_Front *f, const QZSTD_DeviceBuf *bufs, cons
             rc = qfFetchPart(&j, &slot[(k + 1) % 2], &parts[k + 1], &part[(k + 1) % 2]);
         }
     }
-    /* nothing the library queued may still read the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
-    for (k = 0; slot && k < 2; k++) {
-        if (!slot[k].stream) continue;
-        if (qzstd_hip_stream_wait(j.dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
-            (void)qzstd_hip_stream_sync(j.dev, slot[k].stream);
-            rc = -1;
-        }
-    }
-    if (ev) qzstd_hip_event_destroy(j.dev, ev);
+    if (qfCallWait(&call)) rc = -1;
     free(frames);
     free(parts);
     free(equal);
     if (rc == 0) __atomic_fetch_add(&f->devStats[3], (unsigned long long)total, __ATOMIC_RELAXED);
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc == 0 ? nFrames : (size_t)-1;
 }
 
@@ -1906,126 +2030,56 @@ size_t QZSTD_frontCompressDeviceBatchDelta(QZSTD_Front *f, const QZSTD_DeviceBuf
     return qfCompressDevice(f, bufs, bases, NULL, elemSizes, nBufs, 1, stream, dst, dstCapacity, frameSizes, firstFrame);
 }
 
-void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->devStats[k], __ATOMIC_RELAXED) : 0ull;
-}
-
-int QZSTD_frontSetChecksum(QZSTD_Front *f, int on)
+/* a setting changes only while no device call and no job is in progress; -> 0, or -1: busy */
+static int qfSetIdle(QZSTD_Front *f, int *field, int value)
 {
     int busy;
-    if (!f) return -1;
     pthread_mutex_lock(&f->mu);
     busy = f->devBusy || f->running;
-    if (!busy) f->checksum = on != 0;
+    if (!busy) *field = value;
     pthread_mutex_unlock(&f->mu);
     return busy ? -1 : 0;
 }
+
+void QZSTD_frontDeviceStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->devStats : NULL, stats, 4); }
+
+int QZSTD_frontSetChecksum(QZSTD_Front *f, int on) { return f ? qfSetIdle(f, &f->checksum, on != 0) : -1; }
 
 int QZSTD_frontGetChecksum(const QZSTD_Front *f) { return f ? f->checksum : 0; }
 
-void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 2; k++) stats[k] = f ? __atomic_load_n(&f->cksumStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontChecksumStats(QZSTD_Front *f, unsigned long long stats[2]) { qfStats(f ? f->cksumStats : NULL, stats, 2); }
 
 int QZSTD_frontSetByteGroup(QZSTD_Front *f, unsigned elemSize)
 {
-    int busy;
     if (!f || (elemSize != 1u && elemSize != 2u && elemSize != 4u && elemSize != 8u)) return -1;
-    pthread_mutex_lock(&f->mu);
-    busy = f->devBusy || f->running;
-    if (!busy) f->group = elemSize;
-    pthread_mutex_unlock(&f->mu);
-    return busy ? -1 : 0;
+    return qfSetIdle(f, (int *)&f->group, (int)elemSize); /* (the one setting that is unsigned) */
 }
 
 unsigned QZSTD_frontGetByteGroup(const QZSTD_Front *f) { return f ? f->group : 1u; }
 
-void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 3; k++) stats[k] = f ? __atomic_load_n(&f->groupStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontByteGroupStats(QZSTD_Front *f, unsigned long long stats[3]) { qfStats(f ? f->groupStats : NULL, stats, 3); }
 
-void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->deltaStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontDeltaStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->deltaStats : NULL, stats, 4); }
 
-void QZSTD_frontElemDiffStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->ediffStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontElemDiffStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->ediffStats : NULL, stats, 4); }
 
-int QZSTD_frontSetDeltaSkip(QZSTD_Front *f, int on)
-{
-    int busy;
-    if (!f) return -1;
-    pthread_mutex_lock(&f->mu);
-    busy = f->devBusy || f->running;
-    if (!busy) f->deltaSkip = on != 0;
-    pthread_mutex_unlock(&f->mu);
-    return busy ? -1 : 0;
-}
+int QZSTD_frontSetDeltaSkip(QZSTD_Front *f, int on) { return f ? qfSetIdle(f, &f->deltaSkip, on != 0) : -1; }
 
 int QZSTD_frontGetDeltaSkip(const QZSTD_Front *f) { return f ? f->deltaSkip : 0; }
 
-void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->skipStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontDeltaSkipStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->skipStats : NULL, stats, 4); }
 
-int QZSTD_frontSetPlaneProbe(QZSTD_Front *f, int on)
-{
-    int busy;
-    if (!f) return -1;
-    pthread_mutex_lock(&f->mu);
-    busy = f->devBusy || f->running;
-    if (!busy) f->planeProbe = on != 0;
-    pthread_mutex_unlock(&f->mu);
-    return busy ? -1 : 0;
-}
+int QZSTD_frontSetPlaneProbe(QZSTD_Front *f, int on) { return f ? qfSetIdle(f, &f->planeProbe, on != 0) : -1; }
 
 int QZSTD_frontGetPlaneProbe(const QZSTD_Front *f) { return f ? f->planeProbe : 0; }
 
-void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->probeStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontPlaneProbeStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->probeStats : NULL, stats, 4); }
 
-int QZSTD_frontSetPlaneCode(QZSTD_Front *f, int on)
-{
-    int busy;
-    if (!f) return -1;
-    pthread_mutex_lock(&f->mu);
-    busy = f->devBusy || f->running;
-    if (!busy) f->planeCode = on != 0;
-    pthread_mutex_unlock(&f->mu);
-    return busy ? -1 : 0;
-}
+int QZSTD_frontSetPlaneCode(QZSTD_Front *f, int on) { return f ? qfSetIdle(f, &f->planeCode, on != 0) : -1; }
 
 int QZSTD_frontGetPlaneCode(const QZSTD_Front *f) { return f ? f->planeCode : 0; }
 
-void QZSTD_frontPlaneCodeStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->codeStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontPlaneCodeStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->codeStats : NULL, stats, 4); }
 
 /* include/qzstd_hufblock.h as exported functions (bindings that cannot include the header): the block body (0: none) of `len` bytes from the
  * 128 bytes of code lengths and the jump table + streams that qzstd_hip_huf_code leaves, and the rule */

@@ -20,6 +20,8 @@
  * cut into parts the same way, and a part is scattered by ONE qzstd_hip_ungroup_window launch, a row per piece (slice x frame).
  * QZSTD_frontVerifyDeviceBatch (qzstd_verify.c, included behind this file) uses the same slots and the same decode, and compares where these
  * calls scatter.
+ * Every call is built on the scaffold of qzstd_frontend.c (qfCallBegin .. qfCallEnd: the look-ups, devBusy, the restore side's two slots, the
+ * event pair, the closing waits); the slots' buffers are QF_RestoreSlot's, there too.
  * Nothing of the producer (the match-finder service, the announcements) is used: a front created with useProducer = 0 restores as well.
  */
 
@@ -47,39 +49,6 @@ typedef struct {
 typedef struct { size_t f0, f1, bytes, stage, based, diffs; } QF_RestoreRange; /* frames [f0, f1): content bytes, stage bytes (16-aligned frames), frames with a base, differenced frames */
 typedef struct { unsigned char *d_dst; const unsigned char *d_src; size_t len; } QF_ZeroRun; /* consecutive recognised zero frames of one buffer: base -> destination */
 
-struct QF_RestoreSlot_s {
-    void *stream;
-    unsigned char *hStage; size_t hStageCap; /* pinned: the part's decoded frames */
-    void *dStage; size_t dStageCap;          /* their device copy, read by qzstd_hip_ungroup */
-    qzstd_hip_ungroup_row_t *hRows; size_t hRowsCap; /* a row per frame (pinned), and the device copy */
-    void *dRows; size_t dRowsCap;
-    qzstd_hip_ungroup_xor_row_t *hXorRows; size_t hXorRowsCap; /* a part with a base among its frames: qzstd_hip_ungroup_xor's rows instead */
-    void *dXorRows; size_t dXorRowsCap;
-    qzstd_hip_esum_row_t *hSumRows; size_t hSumRowsCap; /* a part with differenced frames: qzstd_hip_esum's rows, for those frames only, */
-    void *dSumRows, *dSumScratch; size_t dSumRowsCap, dSumScratchCap; /* their device copy and the launch's scratch */
-    qzstd_hip_ungroup_win_row_t *hWinRows; size_t hWinRowsCap; /* QZSTD_frontRestoreDeviceSlices: a row per piece (slice x frame) */
-    void *dWinRows; size_t dWinRowsCap;
-    qzstd_hip_ungroup_cmp_row_t *hCmpRows; size_t hCmpRowsCap; /* QZSTD_frontVerifyDeviceBatch (qzstd_verify.c): a row per frame, */
-    void *dCmpRows; size_t dCmpRowsCap;
-    void *dTiles; size_t dTilesCap;                            /* the launch's tile words and their pinned copy, */
-    uint32_t *hTiles; size_t hTilesCap;
-    size_t pending;                                            /* and the part (+ 1) whose tile words are on their way; 0: none */
-    qzstd_hip_fp_row_t *hFpRows; size_t hFpRowsCap;            /* the fingerprint calls (qzstd_fingerprint.c, slot 0 only): a row per frame, */
-    void *dFpRows; size_t dFpRowsCap;
-    void *dFpTiles; size_t dFpTilesCap;                        /* the launch's tile digests and their pinned copy */
-    uint64_t *hFpTiles; size_t hFpTilesCap;
-    qzstd_hip_ediff_cost_row_t *hAdvRows; size_t hAdvRowsCap;  /* the adviser (qzstd_advise.c, slot 0 only): a row per chunk, */
-    void *dAdvRows; size_t dAdvRowsCap;
-    void *dAdvTiles; size_t dAdvTilesCap;                      /* the launch's two cost words per tile and their pinned copy */
-    uint32_t *hAdvTiles; size_t hAdvTilesCap;
-    qzstd_hip_fp_pieces_row_t *hFpPieceRows; size_t hFpPieceRowsCap; /* the calls with source slices (qzstd_slicecheck.c), a launch with a frame of */
-    void *dFpPieceRows; size_t dFpPieceRowsCap;                      /* several pieces: qzstd_hip_fingerprint_pieces's rows instead (slot 0 only), */
-    qzstd_hip_ungroup_cmp_pieces_row_t *hCmpPieceRows; size_t hCmpPieceRowsCap; /* qzstd_hip_ungroup_cmp_pieces's rows instead, */
-    void *dCmpPieceRows; size_t dCmpPieceRowsCap;
-    qzstd_hip_group_piece_t *hChkPieces; size_t hChkPiecesCap;       /* and the launch's piece table */
-    void *dChkPieces; size_t dChkPiecesCap;
-};
-
 /* the part the workers decode (QZSTD_Front.restore) */
 struct QF_RestorePart_s {
     const QF_RestoreFrame *frames; /* the job's table */
@@ -87,47 +56,6 @@ struct QF_RestorePart_s {
     unsigned char *hStage;
     unsigned char *bad; /* NULL, or a byte per frame of the table: set to 1 for the frame a worker stopped at (QZSTD_frontVerifyDeviceBatch) */
 };
-
-static void qfRestoreSlotsFree(QZSTD_Front *f)
-{
-    int k;
-    if (!f->restoreSlot) return;
-    for (k = 0; k < 2; k++) {
-        QF_RestoreSlot *s = &f->restoreSlot[k];
-        if (s->dStage) qzstd_hip_free(f->restoreSlotDev, s->dStage);
-        if (s->dRows) qzstd_hip_free(f->restoreSlotDev, s->dRows);
-        if (s->dXorRows) qzstd_hip_free(f->restoreSlotDev, s->dXorRows);
-        if (s->hXorRows) qzstd_hip_host_free(s->hXorRows);
-        if (s->dSumRows) qzstd_hip_free(f->restoreSlotDev, s->dSumRows);
-        if (s->dSumScratch) qzstd_hip_free(f->restoreSlotDev, s->dSumScratch);
-        if (s->hSumRows) qzstd_hip_host_free(s->hSumRows);
-        if (s->dWinRows) qzstd_hip_free(f->restoreSlotDev, s->dWinRows);
-        if (s->hWinRows) qzstd_hip_host_free(s->hWinRows);
-        if (s->dCmpRows) qzstd_hip_free(f->restoreSlotDev, s->dCmpRows);
-        if (s->hCmpRows) qzstd_hip_host_free(s->hCmpRows);
-        if (s->dTiles) qzstd_hip_free(f->restoreSlotDev, s->dTiles);
-        if (s->hTiles) qzstd_hip_host_free(s->hTiles);
-        if (s->dFpRows) qzstd_hip_free(f->restoreSlotDev, s->dFpRows);
-        if (s->hFpRows) qzstd_hip_host_free(s->hFpRows);
-        if (s->dFpTiles) qzstd_hip_free(f->restoreSlotDev, s->dFpTiles);
-        if (s->hFpTiles) qzstd_hip_host_free(s->hFpTiles);
-        if (s->dAdvRows) qzstd_hip_free(f->restoreSlotDev, s->dAdvRows);
-        if (s->hAdvRows) qzstd_hip_host_free(s->hAdvRows);
-        if (s->dAdvTiles) qzstd_hip_free(f->restoreSlotDev, s->dAdvTiles);
-        if (s->hAdvTiles) qzstd_hip_host_free(s->hAdvTiles);
-        if (s->dFpPieceRows) qzstd_hip_free(f->restoreSlotDev, s->dFpPieceRows);
-        if (s->hFpPieceRows) qzstd_hip_host_free(s->hFpPieceRows);
-        if (s->dCmpPieceRows) qzstd_hip_free(f->restoreSlotDev, s->dCmpPieceRows);
-        if (s->hCmpPieceRows) qzstd_hip_host_free(s->hCmpPieceRows);
-        if (s->dChkPieces) qzstd_hip_free(f->restoreSlotDev, s->dChkPieces);
-        if (s->hChkPieces) qzstd_hip_host_free(s->hChkPieces);
-        if (s->hStage) qzstd_hip_host_free(s->hStage);
-        if (s->hRows) qzstd_hip_host_free(s->hRows);
-        if (s->stream) qzstd_hip_stream_destroy(f->restoreSlotDev, s->stream);
-    }
-    free(f->restoreSlot);
-    f->restoreSlot = NULL;
-}
 
 /* a worker's share of a part: chunks [c0, c1) of the job are frames of f->restore */
 static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
@@ -148,6 +76,36 @@ static int qfRestoreSegment(QZSTD_Front *f, QF_Worker *w, const QF_Seg *sg)
     return 0;
 }
 
+/* the workers decode frames [f0, f0 + nf) of the table into hStage; -> 0, or -1: a frame that does not decode, decodes to another length or
+ * fails its checksum (bad: NULL, or a byte per frame of the table, set for the frame a worker stopped at) */
+static int qfRestoreDecode(QZSTD_Front *f, const QF_RestoreFrame *table, size_t f0, size_t nf, unsigned char *hStage, unsigned char *bad)
+{
+    struct QF_RestorePart_s part;
+    int failed;
+    part.frames = table;
+    part.f0 = f0;
+    part.hStage = hStage;
+    part.bad = bad;
+    pthread_mutex_lock(&f->mu);
+    f->restore = &part;
+    f->src = NULL;
+    f->srcSize = 0;
+    failed = qfRunJobLocked(f, nf);
+    f->restore = NULL;
+    pthread_mutex_unlock(&f->mu);
+    return failed ? -1 : 0;
+}
+
+/* what every restore part counts once its copy and scatter are queued */
+static void qfRestoreCount(QZSTD_Front *f, size_t nf, size_t bytes, size_t stage, size_t based)
+{
+    __atomic_fetch_add(&f->restoreStats[0], (unsigned long long)nf, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)bytes, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)stage, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
+    __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)based, __ATOMIC_RELAXED);
+}
+
 static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameStride, const size_t *frameSizes, size_t nFrames,
                               const QZSTD_DeviceOutBuf *bufs, const QZSTD_DeviceBuf *bases, const unsigned char *elemSizes, size_t nBufs, void *stream)
 {
@@ -156,11 +114,10 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
     QF_ZeroRun *runs = NULL; /* delta skip: what the recognised zero frames leave to do, a device->device copy per run */
     unsigned char *scratch = NULL;
     QF_ZeroHash zh;
+    QF_Call call;
     QF_RestoreSlot *slot;
-    struct QF_RestorePart_s part;
-    void *ev = NULL;
     size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nRuns = 0, nZero = 0;
-    int dev = -1, rc = 0, anyBase = 0, anyDiff = 0, skip;
+    int dev, rc = 0, anyBase = 0, anyDiff = 0, skip;
     /* host-side checks: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
@@ -188,28 +145,19 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         return (size_t)-1; /* a device layer without the ungrouping scatter, or without the device-input entry points at all */
     if (bases && !qzstd_hip_ungroup_xor) return (size_t)-1; /* a base given and a device layer that cannot XOR one in */
     if (anyDiff && !qzstd_hip_esum) return (size_t)-1;      /* differences to sum and a device layer that cannot */
-    for (i = 0; i < nBufs; i++) {
-        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
-        int d;
-        if (!bufs[i].size) continue;
-        d = qzstd_hip_pointer_device(p);
-        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
-        dev = d;
-        if (bases && bases[i].d_ptr) {
-            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
-            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
-        }
-    }
-    if (nFrames == 0) return 0;
-    pthread_mutex_lock(&f->mu);
-    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-    f->devBusy = 1;
-    pthread_mutex_unlock(&f->mu);
+    call.f = f;
+    call.restore = 1;
+    call.nStreams = 2;
+    call.dev = -1;
+    for (i = 0; i < nBufs; i++) /* (qfCallBufs with destinations for buffers) */
+        if (qfCallRange(&call, bufs[i].d_ptr, bufs[i].size) || (bases && bases[i].d_ptr && qfCallRange(&call, bases[i].d_ptr, bases[i].size)))
+            return (size_t)-1;
+    if (nFrames == 0) return 0; /* (an empty call takes nothing, as on the compress side) */
+    if (qfCallBegin(&call, stream)) return (size_t)-1;
+    dev = call.dev;
+    slot = f->restoreSlot;
 
-    {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART"); /* bytes of content per part (whole frames, at least one), default 64 MiB */
-        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-    }
+    partBytes = qfPartBytes();
     table = (QF_RestoreFrame *)malloc(nFrames * sizeof(*table));
     parts = (QF_RestoreRange *)malloc(nFrames * sizeof(*parts));
     if (!table || !parts) rc = -1;
@@ -264,18 +212,6 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             cur->stage += qfPad16(len);
         }
     }
-    /* the slots stay with the front between calls, as the compress side's */
-    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
-    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
-    f->restoreSlotDev = dev;
-    slot = f->restoreSlot;
-    for (k = 0; slot && k < 2 && rc == 0; k++)
-        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
-    /* the library's streams wait for what the caller queued on `stream` so far: whatever last used the buffers */
-    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
-                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
-        rc = -1;
     /* the recognised frames that are not restored in place: base -> destination, one copy per run of consecutive chunks (a wholly frozen
      * tensor: one copy; a run above 1 GiB is cut there, below the 2D copy's largest pitch), on the slots' streams in turn; the destinations
      * are no other frame's */
@@ -290,87 +226,67 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
         const QF_RestoreRange *pr = &parts[k];
         const size_t nf = pr->f1 - pr->f0;
         QF_RestoreSlot *s = &slot[k % 2];
-        void *h;
-        int failed;
+        unsigned char *hStage;
+        qzstd_hip_ungroup_row_t *rows;
+        qzstd_hip_ungroup_xor_row_t *xorRows = NULL;
+        qzstd_hip_esum_row_t *sumRows = NULL;
         /* part k - 2 was copied and scattered from this slot: its stream must have passed both before the buffers are written (or grown) */
         if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
-        h = s->hStage;
-        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
-        s->hStage = (unsigned char *)h;
-        h = s->hRows;
-        if (rc == 0 && qfGrowH(&h, &s->hRowsCap, nf * sizeof(qzstd_hip_ungroup_row_t))) rc = -1;
-        s->hRows = (qzstd_hip_ungroup_row_t *)h;
-        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) || qfGrowD(dev, &s->dRows, &s->dRowsCap, nf * sizeof(qzstd_hip_ungroup_row_t))))
-            rc = -1;
-        if (rc == 0 && pr->based) {
-            h = s->hXorRows;
-            if (qfGrowH(&h, &s->hXorRowsCap, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) rc = -1;
-            s->hXorRows = (qzstd_hip_ungroup_xor_row_t *)h;
-            if (rc == 0 && qfGrowD(dev, &s->dXorRows, &s->dXorRowsCap, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) rc = -1;
-        }
-        if (rc == 0 && pr->diffs) {
-            /* the differenced frames' destinations, summed in place by one launch behind the scatter */
-            size_t tiles = 0, r = 0;
-            h = s->hSumRows;
-            if (qfGrowH(&h, &s->hSumRowsCap, pr->diffs * sizeof(qzstd_hip_esum_row_t))) rc = -1;
-            s->hSumRows = (qzstd_hip_esum_row_t *)h;
-            for (c = 0; c < nf && rc == 0; c++) {
-                const QF_RestoreFrame *fr = &table[pr->f0 + c];
-                if (!fr->diff) continue;
-                s->hSumRows[r].dst = (uint64_t)(uintptr_t)fr->d_dst;
-                s->hSumRows[r].len = (uint32_t)fr->len;
-                s->hSumRows[r].elem = fr->k;
-                s->hSumRows[r].tile0 = 0;
-                s->hSumRows[r].reserved = 0;
-                tiles += (size_t)QZSTD_HIP_ESUM_TILES(fr->len, fr->k);
-                r++;
-            }
-            if (rc == 0 && (qfGrowD(dev, &s->dSumRows, &s->dSumRowsCap, pr->diffs * sizeof(qzstd_hip_esum_row_t)) ||
-                            qfGrowD(dev, &s->dSumScratch, &s->dSumScratchCap, QZSTD_HIP_ESUM_SCRATCH_BYTES(tiles))))
-                rc = -1;
-        }
-        if (rc) break;
-        for (c = 0; c < nf; c++) {
-            const QF_RestoreFrame *fr = &table[pr->f0 + c];
-            if (pr->based) {
-                s->hXorRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
-                s->hXorRows[c].base = (uint64_t)(uintptr_t)fr->d_base;
-                s->hXorRows[c].srcOff = fr->at;
-                s->hXorRows[c].len = (uint32_t)fr->len;
-                s->hXorRows[c].elem = fr->k;
-                continue;
-            }
-            s->hRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
-            s->hRows[c].srcOff = fr->at;
-            s->hRows[c].len = (uint32_t)fr->len;
-            s->hRows[c].elem = fr->k;
-        }
-        part.frames = table;
-        part.f0 = pr->f0;
-        part.hStage = s->hStage;
-        part.bad = NULL;
-        pthread_mutex_lock(&f->mu);
-        f->restore = &part;
-        f->src = NULL;
-        f->srcSize = 0;
-        failed = qfRunJobLocked(f, nf);
-        f->restore = NULL;
-        pthread_mutex_unlock(&f->mu);
-        if (failed) { rc = -1; break; } /* a frame that does not decode, decodes to another length or fails its checksum */
-        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage) ||
-            (pr->based ? qzstd_hip_ungroup_xor(dev, s->stream, s->hXorRows, (uint32_t)nf, (qzstd_hip_ungroup_xor_row_t *)s->dXorRows, s->dStage, pr->stage)
-                       : qzstd_hip_ungroup(dev, s->stream, s->hRows, (uint32_t)nf, (qzstd_hip_ungroup_row_t *)s->dRows, s->dStage, pr->stage))) {
+        hStage = (unsigned char *)qfBufH(&s->pin.stage, pr->stage);
+        rows = hStage ? (qzstd_hip_ungroup_row_t *)qfBufH(&s->pin.rows, nf * sizeof(qzstd_hip_ungroup_row_t)) : NULL;
+        if (!rows || !qfBufD(dev, &s->dev.stage, pr->stage) || !qfBufD(dev, &s->dev.rows, nf * sizeof(qzstd_hip_ungroup_row_t))) { rc = -1; break; }
+        if (pr->based && (!(xorRows = (qzstd_hip_ungroup_xor_row_t *)qfBufH(&s->pin.xorRows, nf * sizeof(qzstd_hip_ungroup_xor_row_t))) ||
+                          !qfBufD(dev, &s->dev.xorRows, nf * sizeof(qzstd_hip_ungroup_xor_row_t)))) {
             rc = -1;
             break;
         }
-        __atomic_fetch_add(&f->restoreStats[0], (unsigned long long)nf, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)pr->bytes, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)pr->based, __ATOMIC_RELAXED);
+        if (pr->diffs) {
+            /* the differenced frames' destinations, summed in place by one launch behind the scatter */
+            size_t tiles = 0, r = 0;
+            if (!(sumRows = (qzstd_hip_esum_row_t *)qfBufH(&s->pin.sumRows, pr->diffs * sizeof(qzstd_hip_esum_row_t)))) { rc = -1; break; }
+            for (c = 0; c < nf; c++) {
+                const QF_RestoreFrame *fr = &table[pr->f0 + c];
+                if (!fr->diff) continue;
+                sumRows[r].dst = (uint64_t)(uintptr_t)fr->d_dst;
+                sumRows[r].len = (uint32_t)fr->len;
+                sumRows[r].elem = fr->k;
+                sumRows[r].tile0 = 0;
+                sumRows[r].reserved = 0;
+                tiles += (size_t)QZSTD_HIP_ESUM_TILES(fr->len, fr->k);
+                r++;
+            }
+            if (!qfBufD(dev, &s->dev.sumRows, pr->diffs * sizeof(qzstd_hip_esum_row_t)) ||
+                !qfBufD(dev, &s->dev.sumScratch, QZSTD_HIP_ESUM_SCRATCH_BYTES(tiles))) {
+                rc = -1;
+                break;
+            }
+        }
+        for (c = 0; c < nf; c++) {
+            const QF_RestoreFrame *fr = &table[pr->f0 + c];
+            if (pr->based) {
+                xorRows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
+                xorRows[c].base = (uint64_t)(uintptr_t)fr->d_base;
+                xorRows[c].srcOff = fr->at;
+                xorRows[c].len = (uint32_t)fr->len;
+                xorRows[c].elem = fr->k;
+                continue;
+            }
+            rows[c].dst = (uint64_t)(uintptr_t)fr->d_dst;
+            rows[c].srcOff = fr->at;
+            rows[c].len = (uint32_t)fr->len;
+            rows[c].elem = fr->k;
+        }
+        if (qfRestoreDecode(f, table, pr->f0, nf, hStage, NULL)) { rc = -1; break; }
+        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dev.stage.p, hStage, pr->stage) ||
+            (pr->based ? qzstd_hip_ungroup_xor(dev, s->stream, xorRows, (uint32_t)nf, (qzstd_hip_ungroup_xor_row_t *)s->dev.xorRows.p, s->dev.stage.p, pr->stage)
+                       : qzstd_hip_ungroup(dev, s->stream, rows, (uint32_t)nf, (qzstd_hip_ungroup_row_t *)s->dev.rows.p, s->dev.stage.p, pr->stage))) {
+            rc = -1;
+            break;
+        }
+        qfRestoreCount(f, nf, pr->bytes, pr->stage, pr->based);
         if (pr->diffs) {
             /* behind the scatter on the same stream: the differences lie at their destinations */
-            if (qzstd_hip_esum(dev, s->stream, s->hSumRows, (uint32_t)pr->diffs, (qzstd_hip_esum_row_t *)s->dSumRows, s->dSumScratch, s->dSumScratchCap)) {
+            if (qzstd_hip_esum(dev, s->stream, sumRows, (uint32_t)pr->diffs, (qzstd_hip_esum_row_t *)s->dev.sumRows.p, s->dev.sumScratch.p, s->dev.sumScratch.cap)) {
                 rc = -1;
                 break;
             }
@@ -378,23 +294,13 @@ static size_t qfRestoreDevice(QZSTD_Front *f, const void *frames, size_t frameSt
             __atomic_fetch_add(&f->ediffStats[3], 1ull, __ATOMIC_RELAXED);
         }
     }
-    /* nothing the library queued may still write the caller's buffers when the call returns: a bounded wait first, then an unbounded one */
-    for (k = 0; slot && k < 2; k++) {
-        if (!slot[k].stream) continue;
-        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
-            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
-            rc = -1;
-        }
-    }
-    if (ev) qzstd_hip_event_destroy(dev, ev);
+    if (qfCallWait(&call)) rc = -1;
     if (rc == 0) __atomic_fetch_add(&f->skipStats[3], (unsigned long long)nZero, __ATOMIC_RELAXED);
     free(table);
     free(parts);
     free(runs);
     free(scratch);
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc == 0 ? nFrames : (size_t)-1;
 }
 
@@ -424,7 +330,7 @@ size_t QZSTD_frontRestoreDevice(QZSTD_Front *f, const void *frames, size_t frame
  * QZSTD_frontRestoreDeviceSlices: byte ranges of the buffers as they were written, restored from the frames they intersect and from no other.
  * The needed frames get a table of their own (frame m of the job is the m-th needed one), cut into parts as above; a part's rows are its
  * PIECES (slice x frame, in order: all pieces of a frame follow each other, so they lie in its part), scattered by ONE
- * qzstd_hip_ungroup_window launch.  Slots, decode, copy, events and the closing waits are qfRestoreDevice's.
+ * qzstd_hip_ungroup_window launch.  Decode (qfRestoreDecode), copy and counters (qfRestoreCount) are qfRestoreDevice's.
  */
 typedef struct {
     size_t m;                    /* the needed frame it is cut from */
@@ -442,9 +348,8 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
     QF_SliceRange *parts = NULL;
     QF_SlicePiece *pieces = NULL;
     size_t *first = NULL;
+    QF_Call call;
     QF_RestoreSlot *slot;
-    struct QF_RestorePart_s part;
-    void *ev = NULL;
     size_t i, c, k, nParts = 0, want = 0, partBytes, nPieces = 0, nNeeded = 0, np = 0, g = 0, pos = 0, lastG = (size_t)-1, chunk;
     unsigned long long nonEmpty = 0, written = 0;
     int dev = -1, rc = 0;
@@ -495,15 +400,14 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
         if (bEnd && qzstd_hip_pointer_device(bEnd - 1) != dev) return (size_t)-1;
     }
     if (nPieces == 0) return 0;
-    pthread_mutex_lock(&f->mu);
-    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-    f->devBusy = 1;
-    pthread_mutex_unlock(&f->mu);
+    call.f = f;
+    call.restore = 1;
+    call.nStreams = 2;
+    call.dev = dev; /* (looked up above, a range of slices at a time: the scaffold's look-up is per buffer) */
+    if (qfCallBegin(&call, stream)) return (size_t)-1;
+    slot = f->restoreSlot;
 
-    {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART");
-        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-    }
+    partBytes = qfPartBytes();
     table = (QF_RestoreFrame *)malloc(nPieces * sizeof(*table)); /* (no more needed frames than pieces) */
     parts = (QF_SliceRange *)malloc(nPieces * sizeof(*parts));
     pieces = (QF_SlicePiece *)malloc(nPieces * sizeof(*pieces));
@@ -559,36 +463,19 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
             cur->p1 = ++np;
         }
     }
-    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
-    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
-    f->restoreSlotDev = dev;
-    slot = f->restoreSlot;
-    for (k = 0; slot && k < 2 && rc == 0; k++)
-        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
-    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
-                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
-        rc = -1;
     for (k = 0; k < nParts && rc == 0; k++) {
         const QF_SliceRange *pr = &parts[k];
         const size_t nf = pr->f1 - pr->f0, nr = pr->p1 - pr->p0;
         QF_RestoreSlot *s = &slot[k % 2];
-        void *h;
-        int failed;
+        unsigned char *hStage;
+        qzstd_hip_ungroup_win_row_t *rows;
         if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
-        h = s->hStage;
-        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
-        s->hStage = (unsigned char *)h;
-        h = s->hWinRows;
-        if (rc == 0 && qfGrowH(&h, &s->hWinRowsCap, nr * sizeof(qzstd_hip_ungroup_win_row_t))) rc = -1;
-        s->hWinRows = (qzstd_hip_ungroup_win_row_t *)h;
-        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) ||
-                        qfGrowD(dev, &s->dWinRows, &s->dWinRowsCap, nr * sizeof(qzstd_hip_ungroup_win_row_t))))
-            rc = -1;
-        if (rc) break;
+        hStage = (unsigned char *)qfBufH(&s->pin.stage, pr->stage);
+        rows = hStage ? (qzstd_hip_ungroup_win_row_t *)qfBufH(&s->pin.winRows, nr * sizeof(qzstd_hip_ungroup_win_row_t)) : NULL;
+        if (!rows || !qfBufD(dev, &s->dev.stage, pr->stage) || !qfBufD(dev, &s->dev.winRows, nr * sizeof(qzstd_hip_ungroup_win_row_t))) { rc = -1; break; }
         for (c = 0; c < nr; c++) {
             const QF_SlicePiece *pc = &pieces[pr->p0 + c];
-            qzstd_hip_ungroup_win_row_t *r = &s->hWinRows[c];
+            qzstd_hip_ungroup_win_row_t *r = &rows[c];
             r->dst = (uint64_t)(uintptr_t)pc->d_dst;
             r->base = (uint64_t)(uintptr_t)pc->d_base;
             r->srcOff = table[pc->m].at;
@@ -598,63 +485,29 @@ size_t QZSTD_frontRestoreDeviceSlices(QZSTD_Front *f, const void *frames, size_t
             r->winLen = pc->winLen;
             r->tile0 = r->reserved = 0;
         }
-        part.frames = table;
-        part.f0 = pr->f0;
-        part.hStage = s->hStage;
-        part.bad = NULL;
-        pthread_mutex_lock(&f->mu);
-        f->restore = &part;
-        f->src = NULL;
-        f->srcSize = 0;
-        failed = qfRunJobLocked(f, nf);
-        f->restore = NULL;
-        pthread_mutex_unlock(&f->mu);
-        if (failed) { rc = -1; break; }
-        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage) ||
-            qzstd_hip_ungroup_window(dev, s->stream, s->hWinRows, (uint32_t)nr, (qzstd_hip_ungroup_win_row_t *)s->dWinRows, s->dStage, pr->stage)) {
+        if (qfRestoreDecode(f, table, pr->f0, nf, hStage, NULL)) { rc = -1; break; }
+        if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dev.stage.p, hStage, pr->stage) ||
+            qzstd_hip_ungroup_window(dev, s->stream, rows, (uint32_t)nr, (qzstd_hip_ungroup_win_row_t *)s->dev.winRows.p, s->dev.stage.p, pr->stage)) {
             rc = -1;
             break;
         }
-        __atomic_fetch_add(&f->restoreStats[0], (unsigned long long)nf, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[1], (unsigned long long)pr->bytes, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[2], (unsigned long long)pr->stage, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->restoreStats[3], 1ull, __ATOMIC_RELAXED);
-        __atomic_fetch_add(&f->deltaStats[3], (unsigned long long)pr->based, __ATOMIC_RELAXED);
+        qfRestoreCount(f, nf, pr->bytes, pr->stage, pr->based);
         __atomic_fetch_add(&f->sliceStats[2], (unsigned long long)nf, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->sliceStats[3], (unsigned long long)nr, __ATOMIC_RELAXED);
     }
-    for (k = 0; slot && k < 2; k++) {
-        if (!slot[k].stream) continue;
-        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
-            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
-            rc = -1;
-        }
-    }
+    if (qfCallWait(&call)) rc = -1;
     if (rc == 0) {
         __atomic_fetch_add(&f->sliceStats[0], nonEmpty, __ATOMIC_RELAXED);
         __atomic_fetch_add(&f->sliceStats[1], written, __ATOMIC_RELAXED);
     }
-    if (ev) qzstd_hip_event_destroy(dev, ev);
     free(table);
     free(parts);
     free(pieces);
     free(first);
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc == 0 ? nNeeded : (size_t)-1;
 }
 
-void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->sliceStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontSliceStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->sliceStats : NULL, stats, 4); }
 
-void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->restoreStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontRestoreStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->restoreStats : NULL, stats, 4); }

@@ -56,9 +56,4 @@ size_t QZSTD_frontVerifyDeviceSlices(QZSTD_Front *f, const void *frames, size_t 
     return ret;
 }
 
-void QZSTD_frontSliceCheckStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->sliceCheckStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontSliceCheckStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->sliceCheckStats : NULL, stats, 4); }

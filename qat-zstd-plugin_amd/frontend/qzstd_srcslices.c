@@ -2,69 +2,56 @@
  * qzstd_srcslices.c — QZSTD_frontCompressDeviceSlices (include/qzstd_frontend_device.h): the Delta compress call for buffers that are not
  * contiguous in device memory.  Included by qzstd_frontend.c (its types and helpers are used as they are).
  *
- * The call checks its slices, looks their memory up (qfSrcMapBuild, which the calls of qzstd_slicecheck.c use too) and hands qfCompressDevice a map of the non-empty ones (QF_SrcMap: slices that follow each
- * other in memory, bases included, are one piece there) beside a buffer table that holds the sizes.  The per-frame table then says where each frame lies: a frame inside ONE slice has an address, as a frame of a contiguous
- * buffer has, and takes every path such a frame takes — staged by the same launches or read in place; a frame across several slices has
- * none, and the three places that would read its bytes from an address read them piece by piece instead:
+ * The call checks its slices, looks their memory up (qfSrcMapBuild, which the calls of qzstd_slicecheck.c use too) and hands qfCompressDevice
+ * a map of the non-empty ones (QF_SrcMap: slices that follow each other in memory, bases included, are one piece there) beside a buffer table
+ * that holds the sizes.  The per-frame table then says where each frame lies: a frame inside ONE slice has an address, as a frame of a
+ * contiguous buffer has, and takes every path such a frame takes — staged by the same launches or read in place; a frame across several
+ * slices has none, and the places that would read its bytes from an address read them piece by piece instead:
  *   qfStagePieces      a part with such a frame is staged by ONE qzstd_hip_group_pieces launch over all its rows (the delta parts' rule),
  *                      a piece per (slice x frame) with the slice's base beside it
  *   qfFramePiecesD2H   the raw-bytes path of qfDeviceFrame: one device->host copy per piece into the buffer the single copy fills
- *   qfDiffPassSlices   delta skip: a qzstd_hip_diff row per piece; a frame is equal when none of its rows' flags is set
+ *   qfDiffPass         (qzstd_frontend.c) delta skip: a qzstd_hip_diff row per piece; a frame is equal when none of its rows' flags is set
  * Everything behind the stage never learns where the bytes came from.
  */
 
-/* piece q of the map, cut to the frame: its bytes [*lo, *hi) of the buffer */
-static void qfPieceInFrame(const QF_SrcPiece *q, const QF_DevFrame *fm, size_t *lo, size_t *hi)
+/* a row of qzstd_hip_group_pieces and, behind the rows before it, its pieces: with each slice's base beside it */
+typedef struct { const QF_SrcMap *sm; qzstd_hip_group_piece_t *pieces; size_t np, multi; } QF_PiecePut;
+static void qfPutPieces(void *rows, size_t m, const QF_DevFrame *fm, uint64_t dstOff, uint32_t pad, void *ctx)
 {
-    *lo = q->off > fm->off ? q->off : fm->off;
-    *hi = q->off + q->size < fm->off + fm->len ? q->off + q->size : fm->off + fm->len;
+    qzstd_hip_group_pieces_row_t *r = (qzstd_hip_group_pieces_row_t *)rows + m;
+    QF_PiecePut *x = (QF_PiecePut *)ctx;
+    r->dstOff = dstOff;
+    r->len = (uint32_t)fm->len;
+    r->pad = pad;
+    r->elem = fm->k;
+    r->piece0 = (uint32_t)x->np;
+    r->nPieces = fm->np;
+    r->reserved = 0;
+    qfSrcFrameTable(x->sm, fm->p0, fm->np, fm->off, fm->len, 1, &x->pieces[x->np]);
+    x->np += fm->np;
+    if (fm->np > 1u) x->multi++;
 }
 
 static int qfStagePieces(const QF_DevJob *j, QF_DevSlot *s, const QF_DevRange *pr, size_t stageBytes)
 {
     const QF_DevFrame *f0 = &j->frames[pr->f0];
     const size_t nf = pr->f1 - pr->f0;
-    size_t c, so = 0, np = 0, m = 0, multi = 0;
-    void *h;
-    if (!qzstd_hip_group_pieces || !j->sm || nf > 0xFFFFFFFFu) return -1;
+    QF_PiecePut x;
+    size_t c, np = 0;
+    if (!qzstd_hip_group_pieces || !j->sm || pr->diff) return -1; /* (the differencing gather knows no pieces: the call has refused them) */
     for (c = 0; c < nf; c++) np += f0[c].np;
     if (np > 0xFFFFFFFFu) return -1;
-    h = s->hPieceRows;
-    if (qfGrowH(&h, &s->hPieceRowsCap, nf * sizeof(qzstd_hip_group_pieces_row_t))) return -1;
-    s->hPieceRows = (qzstd_hip_group_pieces_row_t *)h;
-    h = s->hPieces;
-    if (qfGrowH(&h, &s->hPiecesCap, np * sizeof(qzstd_hip_group_piece_t))) return -1;
-    s->hPieces = (qzstd_hip_group_piece_t *)h;
-    if (qfGrowD(j->dev, &s->dPieceRows, &s->dPieceRowsCap, nf * sizeof(qzstd_hip_group_pieces_row_t)) ||
-        qfGrowD(j->dev, &s->dPieces, &s->dPiecesCap, np * sizeof(qzstd_hip_group_piece_t)))
+    x.sm = j->sm;
+    x.np = x.multi = 0;
+    if (!(x.pieces = (qzstd_hip_group_piece_t *)qfBufH(&s->pin.pieces, np * sizeof(qzstd_hip_group_piece_t))) ||
+        !qfBufD(j->dev, &s->dev.pieces, np * sizeof(qzstd_hip_group_piece_t)) ||
+        qfStageRows(j, pr, 0, &s->pin.pieceRows, &s->dev.pieceRows, sizeof(qzstd_hip_group_pieces_row_t), qfPutPieces, &x) != nf)
         return -1;
-    for (c = 0; c < nf; so += qfPad16(f0[c].len), c++) {
-        qzstd_hip_group_pieces_row_t *r = &s->hPieceRows[c];
-        uint32_t k;
-        if (f0[c].len > 0xFFFFFFE0u || f0[c].diff) return -1;
-        r->dstOff = so;
-        r->len = (uint32_t)f0[c].len;
-        r->pad = (uint32_t)(qfPad16(f0[c].len) - f0[c].len) + (c + 1 == nf ? 16u : 0u);
-        r->elem = f0[c].k;
-        r->piece0 = (uint32_t)m;
-        r->nPieces = f0[c].np;
-        r->reserved = 0;
-        for (k = 0; k < f0[c].np; k++, m++) {
-            const QF_SrcPiece *q = &j->sm->pieces[f0[c].p0 + k];
-            qzstd_hip_group_piece_t *p = &s->hPieces[m];
-            size_t lo, hi;
-            qfPieceInFrame(q, &f0[c], &lo, &hi);
-            p->src = (uint64_t)(uintptr_t)(q->src + (lo - q->off));
-            p->base = q->base ? (uint64_t)(uintptr_t)(q->base + (lo - q->off)) : 0u;
-            p->off = (uint32_t)(lo - f0[c].off);
-            p->len = (uint32_t)(hi - lo);
-        }
-        if (f0[c].np > 1u) multi++;
-    }
-    if (qzstd_hip_group_pieces(j->dev, s->stream, s->hPieceRows, (uint32_t)nf, (qzstd_hip_group_pieces_row_t *)s->dPieceRows, s->hPieces, (uint32_t)np,
-                               (qzstd_hip_group_piece_t *)s->dPieces, s->dStage, stageBytes))
+    if (qzstd_hip_group_pieces(j->dev, s->stream, (const qzstd_hip_group_pieces_row_t *)s->pin.pieceRows.p, (uint32_t)nf,
+                               (qzstd_hip_group_pieces_row_t *)s->dev.pieceRows.p, x.pieces, (uint32_t)np, (qzstd_hip_group_piece_t *)s->dev.pieces.p,
+                               s->dev.stage.p, stageBytes))
         return -1;
-    j->sm->counts[0] += (unsigned long long)multi; /* (the calling thread stages; the call adds them to the front's when it has succeeded) */
+    j->sm->counts[0] += (unsigned long long)x.multi; /* (the calling thread stages; the call adds them to the front's when it has succeeded) */
     j->sm->counts[1] += 1ull;
     return 0;
 }
@@ -77,88 +64,9 @@ static int qfFramePiecesD2H(const QF_DevPart *pt, void *stream, const QF_DevFram
     for (k = 0; k < fm->np; k++) {
         const QF_SrcPiece *q = &pt->sm->pieces[fm->p0 + k];
         size_t lo, hi;
-        qfPieceInFrame(q, fm, &lo, &hi);
+        qfPieceInFrame(q, fm->off, fm->len, &lo, &hi);
         if (qzstd_hip_memcpy_d2h(pt->dev, stream, to + (lo - fm->off), (base ? q->base : q->src) + (lo - q->off), hi - lo)) return -1;
     }
-    return 0;
-}
-
-/* qfDiffPass for a call with source slices: the same launch, copy, wait, zero frames and counters; a compared frame has a row per piece
- * (rows of its own, so that a frame's flags are its own), and is equal when none of them is set */
-static int qfDiffPassSlices(QZSTD_Front *f, QF_DevSlot *s, int dev, const QZSTD_DeviceBuf *bufs, const QZSTD_DeviceBuf *bases, const QF_SrcMap *sm,
-                            size_t nBufs, size_t nFrames, unsigned char *equal, unsigned char *dst, size_t *frameSizes)
-{
-    const size_t chunk = f->p.chunkSize;
-    QF_ZeroHash z;
-    size_t i, off, c = 0, rows = 0, frames = 0, r = 0, nEqual = 0, p;
-    unsigned long long bytes = 0;
-    void *h;
-    memset(equal, 0, nFrames);
-    memset(&z, 0, sizeof(z));
-    for (i = 0; i < nBufs; i++) {
-        if (!bases[i].d_ptr) continue;
-        for (off = 0, p = sm->first[i]; off < bufs[i].size; off += chunk, frames++)
-            rows += qfSrcFramePieces(sm, &p, off, bufs[i].size - off < chunk ? bufs[i].size - off : chunk);
-    }
-    if (rows == 0) return 0;
-    if (rows > 0xFFFFFFFFu || chunk > 0xFFFFFFE0u) return -1;
-    if (qfZeroFrameBound(chunk) > f->stride) return -1;
-    h = s->hDiffRows;
-    if (qfGrowH(&h, &s->hDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t))) return -1;
-    s->hDiffRows = (qzstd_hip_diff_row_t *)h;
-    h = s->hDiffFlags;
-    if (qfGrowH(&h, &s->hDiffFlagsCap, rows * sizeof(uint32_t))) return -1;
-    s->hDiffFlags = (uint32_t *)h;
-    if (qfGrowD(dev, &s->dDiffRows, &s->dDiffRowsCap, rows * sizeof(qzstd_hip_diff_row_t)) ||
-        qfGrowD(dev, &s->dDiffFlags, &s->dDiffFlagsCap, rows * sizeof(uint32_t)))
-        return -1;
-    for (i = 0; i < nBufs; i++) {
-        if (!bases[i].d_ptr) continue;
-        for (off = 0, p = sm->first[i]; off < bufs[i].size; off += chunk) {
-            QF_DevFrame fm;
-            size_t np, k;
-            fm.off = off;
-            fm.len = bufs[i].size - off < chunk ? bufs[i].size - off : chunk;
-            np = qfSrcFramePieces(sm, &p, off, fm.len);
-            for (k = 0; k < np; k++, r++) {
-                const QF_SrcPiece *q = &sm->pieces[p + k];
-                qzstd_hip_diff_row_t *row = &s->hDiffRows[r];
-                size_t lo, hi;
-                qfPieceInFrame(q, &fm, &lo, &hi);
-                row->a = (uint64_t)(uintptr_t)(q->src + (lo - q->off));
-                row->b = (uint64_t)(uintptr_t)(q->base + (lo - q->off));
-                row->len = (uint32_t)(hi - lo);
-                row->tile0 = 0;
-            }
-            bytes += fm.len;
-        }
-    }
-    if (qzstd_hip_diff(dev, s->stream, s->hDiffRows, (uint32_t)rows, (qzstd_hip_diff_row_t *)s->dDiffRows, (uint32_t *)s->dDiffFlags) ||
-        qzstd_hip_memcpy_d2h(dev, s->stream, s->hDiffFlags, s->dDiffFlags, rows * sizeof(uint32_t)))
-        return -1;
-    if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) {
-        (void)qzstd_hip_stream_sync(dev, s->stream); /* the launch still reads the caller's slices */
-        return -1;
-    }
-    for (i = 0, r = 0; i < nBufs; i++) {
-        const size_t nf = bufs[i].size / chunk + (bufs[i].size % chunk != 0);
-        if (bases[i].d_ptr) {
-            for (off = 0, p = sm->first[i]; off < nf; off++) {
-                const size_t len = bufs[i].size - off * chunk < chunk ? bufs[i].size - off * chunk : chunk;
-                size_t np = qfSrcFramePieces(sm, &p, off * chunk, len);
-                uint32_t any = 0;
-                for (; np; np--, r++) any |= s->hDiffFlags[r];
-                if (any) continue;
-                equal[c + off] = 1;
-                frameSizes[c + off] = qfZeroFrame(dst + (c + off) * f->stride, len, f->checksum, &z, chunk);
-                nEqual++;
-            }
-        }
-        c += nf;
-    }
-    __atomic_fetch_add(&f->skipStats[0], (unsigned long long)frames, __ATOMIC_RELAXED);
-    __atomic_fetch_add(&f->skipStats[1], (unsigned long long)nEqual, __ATOMIC_RELAXED);
-    __atomic_fetch_add(&f->skipStats[2], bytes, __ATOMIC_RELAXED);
     return 0;
 }
 
@@ -337,9 +245,4 @@ size_t QZSTD_frontCompressDeviceSlices(QZSTD_Front *f, const size_t *bufSizes, c
     return ret;
 }
 
-void QZSTD_frontSrcSliceStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->srcSliceStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontSrcSliceStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->srcSliceStats : NULL, stats, 4); }

@@ -3,7 +3,7 @@
  * left reproduce the tensors that are on the device NOW?  The restore with a comparison in the scatter's place: nothing of the caller's is
  * written, no temporary of the buffers' size exists, and the answer says where the first difference of every frame lies.  Part of
  * qzstd_frontend.c's translation unit, included behind qzstd_restore.c, whose slots (QF_RestoreSlot), part type and workers' decode
- * (qfRestoreSegment) it uses.
+ * (qfRestoreDecode) it uses; the call's prologue and epilogue are the scaffold's (qfCallBegin .. qfCallEnd, qzstd_frontend.c).
  *
  * The call's frames are cut into parts of whole frames, at most QF_PART_BYTES ($QZSTD_FRONT_DEVICE_PART) of DECODED content each.  Per part,
  * on one of the two restore slots: the workers decode its frames into the pinned buffer; the calling thread queues the host->device copy,
@@ -39,6 +39,7 @@ typedef struct { size_t c0, c1, f0, f1, bytes, stage, compared, tiles, pieces, m
 static void qfVerifyHarvest(QZSTD_Front *f, QF_RestoreSlot *s, const QF_VerifyRange *parts, const QF_VerifyRow *rows, size_t *firstDiff, size_t *nDiff)
 {
     const QF_VerifyRange *pr;
+    const uint32_t *tiles = (const uint32_t *)s->pin.tiles.p;
     size_t c, t = 0, differing = 0;
     if (!s->pending) return;
     pr = &parts[s->pending - 1u];
@@ -47,7 +48,7 @@ static void qfVerifyHarvest(QZSTD_Front *f, QF_RestoreSlot *s, const QF_VerifyRa
         const size_t n = (size_t)QZSTD_HIP_CMP_TILES(rows[c].len, rows[c].k);
         size_t i, at = QZSTD_VERIFY_SAME;
         for (i = 0; i < n; i++)
-            if (s->hTiles[t + i] != QZSTD_HIP_CMP_SAME) { at = s->hTiles[t + i]; break; }
+            if (tiles[t + i] != QZSTD_HIP_CMP_SAME) { at = tiles[t + i]; break; }
         t += n;
         if (firstDiff) firstDiff[c] = at;
         if (at != QZSTD_VERIFY_SAME) differing++;
@@ -70,11 +71,10 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
     QF_VerifyRange *parts = NULL;
     unsigned char *scratch = NULL;
     QF_ZeroHash zh;
+    QF_Call call;
     QF_RestoreSlot *slot;
-    struct QF_RestorePart_s part;
-    void *ev = NULL;
     size_t i, c = 0, m = 0, k, nParts = 0, want = 0, partBytes, pos = 0, nDiff = 0, tp;
-    int dev = -1, rc = 0, anyBase = 0, skip;
+    int dev, rc = 0, anyBase = 0, skip;
     /* host-side checks, the restore's: nothing has touched a GPU when one of them fails */
     if (!f || (nBufs && !bufs) || nBufs > 0xFFFFFFFFu) return (size_t)-1;
     for (i = 0; i < nBufs; i++) {
@@ -94,29 +94,17 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
         !qzstd_hip_event_destroy)
         return (size_t)-1; /* a device layer without the ungrouping comparison, or without the device-input entry points at all */
     if (sm && sm->multi && !qzstd_hip_ungroup_cmp_pieces) return (size_t)-1; /* a frame of several pieces and a device layer that cannot read one */
-    if (sm) dev = sm->dev;
-    for (i = 0; i < nBufs && !sm; i++) {
-        const unsigned char *p = (const unsigned char *)bufs[i].d_ptr;
-        int d;
-        if (!bufs[i].size) continue;
-        d = qzstd_hip_pointer_device(p);
-        if (d < 0 || qzstd_hip_pointer_device(p + bufs[i].size - 1) != d || (dev >= 0 && d != dev)) return (size_t)-1;
-        dev = d;
-        if (bases && bases[i].d_ptr) {
-            const unsigned char *b = (const unsigned char *)bases[i].d_ptr;
-            if (qzstd_hip_pointer_device(b) != d || qzstd_hip_pointer_device(b + bases[i].size - 1) != d) return (size_t)-1;
-        }
-    }
+    call.f = f;
+    call.restore = 1;
+    call.nStreams = 2;
+    call.dev = sm ? sm->dev : -1; /* (a call with source slices has looked its memory up: qfSrcMapBuild) */
+    if (!sm && qfCallBufs(&call, bufs, bases, nBufs)) return (size_t)-1;
     if (nFrames == 0) return 0;
-    pthread_mutex_lock(&f->mu);
-    if (f->devBusy || f->running) { pthread_mutex_unlock(&f->mu); return (size_t)-1; }
-    f->devBusy = 1;
-    pthread_mutex_unlock(&f->mu);
+    if (qfCallBegin(&call, stream)) return (size_t)-1;
+    dev = call.dev;
+    slot = f->restoreSlot;
 
-    {
-        const char *pb = getenv("QZSTD_FRONT_DEVICE_PART");
-        partBytes = pb && *pb && atoll(pb) > 0 ? (size_t)atoll(pb) : QF_PART_BYTES;
-    }
+    partBytes = qfPartBytes();
     skip = bases && f->deltaSkip;
     memset(&zh, 0, sizeof(zh));
     table = (QF_RestoreFrame *)malloc(nFrames * sizeof(*table));
@@ -182,55 +170,35 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
             cur->tiles += (size_t)QZSTD_HIP_CMP_TILES(len, e);
         }
     }
-    /* the restore's slots, kept with the front between calls */
-    if (f->restoreSlot && f->restoreSlotDev != dev) qfRestoreSlotsFree(f);
-    if (rc == 0 && !f->restoreSlot && !(f->restoreSlot = (QF_RestoreSlot *)calloc(2, sizeof(QF_RestoreSlot)))) rc = -1;
-    f->restoreSlotDev = dev;
-    slot = f->restoreSlot;
-    for (k = 0; slot && k < 2 && rc == 0; k++)
-        if (!slot[k].stream && !(slot[k].stream = qzstd_hip_stream_create(dev))) rc = -1;
-    /* the library's streams wait for what the caller queued on `stream` so far: whatever last wrote the tensors and the bases */
-    if (rc == 0 && !(ev = qzstd_hip_event_create(dev))) rc = -1;
-    if (rc == 0 && (qzstd_hip_event_record(dev, ev, stream) || qzstd_hip_stream_wait_event(dev, slot[0].stream, ev) ||
-                    qzstd_hip_stream_wait_event(dev, slot[1].stream, ev)))
-        rc = -1;
     for (k = 0; k < nParts && rc == 0; k++) {
         const QF_VerifyRange *pr = &parts[k];
         const size_t nf = pr->f1 - pr->f0, nr = pr->c1 - pr->c0;
         QF_RestoreSlot *s = &slot[k % 2];
-        void *h;
+        unsigned char *hStage;
+        qzstd_hip_ungroup_cmp_row_t *cmpRows;
+        qzstd_hip_ungroup_cmp_pieces_row_t *pieceRows = NULL;
+        qzstd_hip_group_piece_t *chk = NULL;
         /* part k - 2 ran on this slot: its stream must have passed the copy, the launch and the tile words' way back before they are read
          * and the buffers written (or grown) */
         if (qzstd_hip_stream_wait(dev, s->stream, QF_DEV_WAIT_MS) != 0) { rc = -1; break; }
         qfVerifyHarvest(f, s, parts, rows, firstDiff, &nDiff);
-        h = s->hStage;
-        if (qfGrowH(&h, &s->hStageCap, pr->stage)) rc = -1;
-        s->hStage = (unsigned char *)h;
-        h = s->hCmpRows;
-        if (rc == 0 && qfGrowH(&h, &s->hCmpRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_row_t))) rc = -1;
-        s->hCmpRows = (qzstd_hip_ungroup_cmp_row_t *)h;
-        h = s->hTiles;
-        if (rc == 0 && qfGrowH(&h, &s->hTilesCap, pr->tiles * sizeof(uint32_t))) rc = -1;
-        s->hTiles = (uint32_t *)h;
-        if (rc == 0 && (qfGrowD(dev, &s->dStage, &s->dStageCap, pr->stage) ||
-                        qfGrowD(dev, &s->dCmpRows, &s->dCmpRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_row_t)) ||
-                        qfGrowD(dev, &s->dTiles, &s->dTilesCap, pr->tiles * sizeof(uint32_t))))
+        hStage = (unsigned char *)qfBufH(&s->pin.stage, pr->stage);
+        cmpRows = hStage ? (qzstd_hip_ungroup_cmp_row_t *)qfBufH(&s->pin.cmpRows, nr * sizeof(qzstd_hip_ungroup_cmp_row_t)) : NULL;
+        if (!cmpRows || !qfBufH(&s->pin.tiles, pr->tiles * sizeof(uint32_t)) || !qfBufD(dev, &s->dev.stage, pr->stage) ||
+            !qfBufD(dev, &s->dev.cmpRows, nr * sizeof(qzstd_hip_ungroup_cmp_row_t)) || !qfBufD(dev, &s->dev.tiles, pr->tiles * sizeof(uint32_t))) {
             rc = -1;
-        if (rc == 0 && pr->multi) {
-            h = s->hCmpPieceRows;
-            if (qfGrowH(&h, &s->hCmpPieceRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t))) rc = -1;
-            s->hCmpPieceRows = (qzstd_hip_ungroup_cmp_pieces_row_t *)h;
-            h = s->hChkPieces;
-            if (rc == 0 && qfGrowH(&h, &s->hChkPiecesCap, pr->pieces * sizeof(qzstd_hip_group_piece_t))) rc = -1;
-            s->hChkPieces = (qzstd_hip_group_piece_t *)h;
-            if (rc == 0 && (qfGrowD(dev, &s->dCmpPieceRows, &s->dCmpPieceRowsCap, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t)) ||
-                            qfGrowD(dev, &s->dChkPieces, &s->dChkPiecesCap, pr->pieces * sizeof(qzstd_hip_group_piece_t))))
-                rc = -1;
+            break;
         }
-        if (rc) break;
+        if (pr->multi && (!(pieceRows = (qzstd_hip_ungroup_cmp_pieces_row_t *)qfBufH(&s->pin.cmpPieceRows, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t))) ||
+                          !(chk = (qzstd_hip_group_piece_t *)qfBufH(&s->pin.chkPieces, pr->pieces * sizeof(qzstd_hip_group_piece_t))) ||
+                          !qfBufD(dev, &s->dev.cmpPieceRows, nr * sizeof(qzstd_hip_ungroup_cmp_pieces_row_t)) ||
+                          !qfBufD(dev, &s->dev.chkPieces, pr->pieces * sizeof(qzstd_hip_group_piece_t)))) {
+            rc = -1;
+            break;
+        }
         for (c = 0, tp = 0; pr->multi && c < nr; c++) {
             const QF_VerifyRow *vr = &rows[pr->c0 + c];
-            qzstd_hip_ungroup_cmp_pieces_row_t *r = &s->hCmpPieceRows[c];
+            qzstd_hip_ungroup_cmp_pieces_row_t *r = &pieceRows[c];
             r->srcOff = vr->m == (size_t)-1 ? 0u : table[vr->m].at;
             r->len = (uint32_t)vr->len;
             r->elem = vr->k;
@@ -238,12 +206,12 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
             r->tile0 = 0;
             r->piece0 = (uint32_t)tp;
             r->nPieces = (uint32_t)vr->np;
-            qfSrcFrameTable(sm, vr->p0, vr->np, vr->off, vr->len, 1, &s->hChkPieces[tp]);
+            qfSrcFrameTable(sm, vr->p0, vr->np, vr->off, vr->len, 1, &chk[tp]);
             tp += vr->np;
         }
         for (c = 0; !pr->multi && c < nr; c++) {
             const QF_VerifyRow *vr = &rows[pr->c0 + c];
-            qzstd_hip_ungroup_cmp_row_t *r = &s->hCmpRows[c];
+            qzstd_hip_ungroup_cmp_row_t *r = &cmpRows[c];
             r->ref = (uint64_t)(uintptr_t)vr->d_ref;
             r->base = (uint64_t)(uintptr_t)vr->d_base;
             r->srcOff = vr->m == (size_t)-1 ? 0u : table[vr->m].at;
@@ -253,32 +221,20 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
             r->tile0 = 0;
         }
         if (nf) {
-            int failed;
-            part.frames = table;
-            part.f0 = pr->f0;
-            part.hStage = s->hStage;
-            part.bad = bad;
-            pthread_mutex_lock(&f->mu);
-            f->restore = &part;
-            f->src = NULL;
-            f->srcSize = 0;
-            failed = qfRunJobLocked(f, nf);
-            f->restore = NULL;
-            pthread_mutex_unlock(&f->mu);
-            if (failed) { /* a frame that does not decode, decodes to another length or fails its checksum */
+            if (qfRestoreDecode(f, table, pr->f0, nf, hStage, bad)) {
                 for (c = pr->f0; firstDiff && c < pr->f1; c++)
                     if (bad[c]) firstDiff[callOf[c]] = QZSTD_VERIFY_UNDECODED;
                 rc = -1;
                 break;
             }
-            if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dStage, s->hStage, pr->stage)) { rc = -1; break; }
+            if (qzstd_hip_memcpy_h2d(dev, s->stream, s->dev.stage.p, hStage, pr->stage)) { rc = -1; break; }
         }
-        if ((pr->multi ? qzstd_hip_ungroup_cmp_pieces(dev, s->stream, s->hCmpPieceRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_pieces_row_t *)s->dCmpPieceRows,
-                                                      s->hChkPieces, (uint32_t)pr->pieces, (qzstd_hip_group_piece_t *)s->dChkPieces, s->dStage,
-                                                      pr->stage, (uint32_t *)s->dTiles)
-                       : qzstd_hip_ungroup_cmp(dev, s->stream, s->hCmpRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_row_t *)s->dCmpRows, s->dStage,
-                                               pr->stage, (uint32_t *)s->dTiles)) ||
-            qzstd_hip_memcpy_d2h(dev, s->stream, s->hTiles, s->dTiles, pr->tiles * sizeof(uint32_t))) {
+        if ((pr->multi ? qzstd_hip_ungroup_cmp_pieces(dev, s->stream, pieceRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_pieces_row_t *)s->dev.cmpPieceRows.p,
+                                                      chk, (uint32_t)pr->pieces, (qzstd_hip_group_piece_t *)s->dev.chkPieces.p, s->dev.stage.p,
+                                                      pr->stage, (uint32_t *)s->dev.tiles.p)
+                       : qzstd_hip_ungroup_cmp(dev, s->stream, cmpRows, (uint32_t)nr, (qzstd_hip_ungroup_cmp_row_t *)s->dev.cmpRows.p, s->dev.stage.p,
+                                               pr->stage, (uint32_t *)s->dev.tiles.p)) ||
+            qzstd_hip_memcpy_d2h(dev, s->stream, s->pin.tiles.p, s->dev.tiles.p, pr->tiles * sizeof(uint32_t))) {
             rc = -1;
             break;
         }
@@ -291,30 +247,20 @@ static size_t qfVerifyDevice(QZSTD_Front *f, const void *frames, size_t frameStr
             sm->counts[1] += 1ull;
         }
     }
-    /* nothing the library queued may still run when the call returns: a bounded wait first, then an unbounded one */
-    for (k = 0; slot && k < 2; k++) {
-        if (!slot[k].stream) continue;
-        if (qzstd_hip_stream_wait(dev, slot[k].stream, QF_DEV_WAIT_MS) != 0) {
-            (void)qzstd_hip_stream_sync(dev, slot[k].stream);
-            rc = -1;
-        }
-    }
+    if (qfCallWait(&call)) rc = -1;
     /* the last parts' tile words, in the parts' order (part nParts - 2 ran on the other slot than the last one) */
-    for (k = 0; slot && k < 2; k++) {
+    for (k = 0; k < 2; k++) {
         QF_RestoreSlot *s = &slot[(nParts + k) % 2];
         if (rc == 0) qfVerifyHarvest(f, s, parts, rows, firstDiff, &nDiff);
         s->pending = 0;
     }
-    if (ev) qzstd_hip_event_destroy(dev, ev);
     free(table);
     free(callOf);
     free(bad);
     free(rows);
     free(parts);
     free(scratch);
-    pthread_mutex_lock(&f->mu);
-    f->devBusy = 0;
-    pthread_mutex_unlock(&f->mu);
+    qfCallEnd(&call);
     return rc == 0 ? nDiff : (size_t)-1;
 }
 
@@ -325,9 +271,4 @@ size_t QZSTD_frontVerifyDeviceBatch(QZSTD_Front *f, const void *frames, size_t f
     return qfVerifyDevice(f, frames, frameStride, frameSizes, nFrames, bufs, bases, NULL, elemSizes, nBufs, stream, firstDiff);
 }
 
-void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4])
-{
-    int k;
-    if (!stats) return;
-    for (k = 0; k < 4; k++) stats[k] = f ? __atomic_load_n(&f->verifyStats[k], __ATOMIC_RELAXED) : 0ull;
-}
+void QZSTD_frontVerifyStats(QZSTD_Front *f, unsigned long long stats[4]) { qfStats(f ? f->verifyStats : NULL, stats, 4); }
